@@ -1,9 +1,16 @@
 #!/usr/bin/env python3
 """bench.py - DiT denoise steps/sec (+ VAE decode ms) at 768x512x25 distilled on MI355X, one JSON line.
 
-  python bench.py --gpus N --steps K --warmup W [--mode replica|cfg-pair|sp|vae-tiles]
+  python bench.py --gpus N --steps K --warmup W [--mode replica|cfg-pair|sp|vae-tiles] [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
       bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, runs W untimed and K timed steps, and prints the line (`value`, `ms_per_step` = ms of one timed step). `--full`
+adds what takes runs of its own after the timed region: in replica mode the `roofline` / `attention` / `row_kernels` pass, the `vae`
+and `pre_loop` legs and, at N = 1, `cpu_baseline`. `--dump-outputs DIR` writes what the timed path returned in its LAST timed step as
+DIR/<name>.npy (rank 0): for replica, cfg-pair and sp `latent` (float32, what the step returned) and `velocity` (float64, what its
+Euler update applied: the step's output at full scale; `*_quant` for the --quant run), for vae-tiles `frames_sample` - 2^22 values of
+the decoded frames at indices drawn with a fixed seed. Inputs are seeded, so equal arguments give equal inputs.
 
 `python bench.py --gpus N` with N > 1 and no launcher in the environment starts the N ranks itself (torch.distributed.run as a child
 process, before this process touches the GPU) and relays rank 0's JSON line; a WORLD_SIZE that disagrees with --gpus is an error,
@@ -28,12 +35,12 @@ Modes (what N GPUs do; the path shards at the granularity of forwards / samples 
   vae-tiles  (configs[4]) 26 latent frames, tile 8 / overlap 1: the four tiles decoded round-robin by the ranks, raw tiles
              broadcast, blended on every rank; value = decodes / s.
 
-roofline: dominant kernel family = the bf16 MFMA GEMM. achieved = sum of the GEMM launches' algorithmic FLOPs (2*M*N*K) / sum of
+roofline (--full): dominant kernel family = the bf16 MFMA GEMM. achieved = sum of the GEMM launches' algorithmic FLOPs (2*M*N*K) / sum of
 their durations over K steps, measured with HIP events recorded on the launch stream around every GEMM launch (ltx_prof_*) in a
 second pass of the same K steps right after the timed region (the event packets cost ~6 % of a step, so `value` comes from the
 un-instrumented pass). peak = 2500 TFLOP/s dense bf16. traffic = fabric-side bytes per GEMM launch from the rocprofv3 PMC passes
 committed under profiles/ (tools/pmc_traffic.py; `traffic_source` names the file - it is not re-measured inside this process).
-cpu_baseline: the oracle (numpy restatement of the reference path, kind "port") timed on the host cores for ONE WHOLE denoise step
+cpu_baseline (--full): the oracle (numpy restatement of the reference path, kind "port") timed on the host cores for ONE WHOLE denoise step
 and ONE WHOLE VAE decode of the same workload, un-extrapolated (`extrapolated` is true only when a probe
 predicts that the host would need more than the leg's budget, in which case whole blocks / a small latent are scaled and said so).
 """
@@ -152,13 +159,14 @@ def cpu_baseline_vae(F, H, W, budget_s=150.0):
     t0 = time.perf_counter()
     frames = o.decode_video(w, lat)
     el = time.perf_counter() - t0
-    used = max(o._CONV_BLAS_THREADS, o._HOST_THREADS)
+    blas = o.blas_threads(o._CONV_BLAS_THREADS)  # the oracle never raises BLAS above the threads it started with
+    used = max(blas, o._HOST_THREADS)
     return {"decode_ms": round(1e3 * el, 1), "extrapolated": False, "cores": min(ncores, used), "host_cores": ncores,
-            "blas_threads": o._CONV_BLAS_THREADS, "pool_threads": o._HOST_THREADS, "tflops": round(vae_flops(F, H, W) / el / 1e12, 3),
+            "blas_threads": blas, "pool_threads": o._HOST_THREADS, "tflops": round(vae_flops(F, H, W) / el / 1e12, 3),
             "unit": f"ms per whole decode of the {F}x{H}x{W} latent",
             "sample": f"ONE whole oracle.decode_video of the {F}x{H}x{W} latent -> {frames.shape[0]}x{frames.shape[1]}x{frames.shape[2]} "
                       f"frames ({vae_flops(F, H, W) / 1e12:.2f} TFLOP over 42 convs) in {el:.1f} s: numpy f32, one sgemm per conv tap on "
-                      f"{o._CONV_BLAS_THREADS} BLAS threads (the fastest setting for that shape on a 256-core host, tools/host_blas_probe.py) + "
+                      f"{blas} BLAS threads (the fastest setting for that shape on a 256-core host, tools/host_blas_probe.py) + "
                       f"{o._HOST_THREADS} threads for the position-wise passes, {ncores} schedulable host cores"}
 
 
@@ -216,9 +224,9 @@ def cpu_baseline(T, S, F, H, W, budget_s=300.0):
     t0 = time.perf_counter()
     o.transformer_block(wc, 0, x, ctxp, temb, cfg, rope, None)
     per_block = time.perf_counter() - t0
-    used = max(o._DIT_BLAS_THREADS, o._HOST_THREADS)
-    nthreads = o._DIT_BLAS_THREADS
-    common = {"unit": "steps/s", "cores": min(ncores, used), "host_cores": ncores, "blas_threads": o._DIT_BLAS_THREADS,
+    nthreads = o.blas_threads(o._DIT_BLAS_THREADS)  # the oracle never raises BLAS above the threads it started with
+    used = max(nthreads, o._HOST_THREADS)
+    common = {"unit": "steps/s", "cores": min(ncores, used), "host_cores": ncores, "blas_threads": nthreads,
               "pool_threads": o._HOST_THREADS, "kind": "port"}
     if per_block * 48 > budget_s:
         nblk = max(1, int(budget_s / 4 / per_block))
@@ -324,6 +332,11 @@ def main():
     ap.add_argument("--steps", type=int, default=8)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--mode", choices=("replica", "cfg-pair", "sp", "vae-tiles"), default="replica")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run what needs runs of its own: the instrumented roofline pass, the VAE and pre-loop "
+                         "legs and the CPU baseline (replica mode; --no-prof / --no-vae / --no-aux / --no-cpu-baseline drop single ones)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last timed step to DIR/<name>.npy (float32 / float64, rank 0)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-vae", action="store_true")
     ap.add_argument("--vae-to", choices=("all", "root"), default="all",
@@ -426,6 +439,9 @@ def main():
     cfg = ltx.default_transformer_config()
     runner = {"replica": run_replica, "cfg-pair": run_cfg_pair, "sp": run_sp, "vae-tiles": run_vae_tiles}[args.mode]
     out = runner(args, ctx, ltx, dmod, torch, dist, dev, cfg, rank, world, side)
+    outputs = out.pop("_outputs", {})
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, outputs)
     out["n_ranks_seen"] = n_ranks_seen
     if args.rehearse_one_gpu:
         out["rehearsal"] = f"{world} ranks share ONE GPU over gloo: code-path rehearsal, not a scaling measurement"
@@ -440,6 +456,47 @@ def main():
         dist.barrier()
         dist.destroy_process_group()
     ctx.close()
+
+
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SAMPLE = 1 << 22
+
+
+def host_output(t, sample_seed=0):
+    """Host float32 copy of a device output for --dump-outputs; above DUMP_SAMPLE values, DUMP_SAMPLE of them (flattened) at sorted
+    indices drawn with a fixed seed."""
+    import numpy as np
+    import torch
+
+    if t.numel() <= DUMP_SAMPLE:
+        return t.detach().float().cpu().numpy()
+    idx = np.sort(np.random.default_rng(sample_seed).integers(0, t.numel(), DUMP_SAMPLE))
+    return t.detach().reshape(-1)[torch.from_numpy(idx).to(t.device)].float().cpu().numpy()
+
+
+def denoise_outputs(before, after, sig, j):
+    """--dump-outputs of a denoise step j: `latent`, what the step returned, and `velocity`, what its Euler update applied
+    (latent += (sig[j+1] - sig[j]) * velocity, ltx_denoise_dev) recovered in float64: the step's whole contribution at full
+    scale, where the returned latent may hold it scaled by a small sigma step."""
+    import numpy as np
+
+    a, b = host_output(after), host_output(before)
+    return {"latent": a, "velocity": (a.astype(np.float64) - b) / (float(sig[j + 1]) - float(sig[j]))}
+
+
+def dump_outputs(dirname, outputs):
+    """--dump-outputs: one DIR/<name>.npy per array the timed path computed in its last timed step (float64 stays float64, anything
+    else is written as float32)."""
+    import numpy as np
+
+    if not outputs:
+        raise SystemExit("bench.py: --dump-outputs: this mode collected no outputs")
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64 if np.asarray(v).dtype == np.float64 else np.float32) for k, v in outputs.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_MAX_BYTES, f"--dump-outputs: {total} bytes, above the {DUMP_MAX_BYTES} byte budget"
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def timed(torch, dist, world, dev, fn, warmup, steps):
@@ -510,22 +567,28 @@ def run_replica(args, ctx, ltx, dmod, torch, dist, dev, cfg, rank, world, side):
     latent = torch.empty((1, 128, F, H, W), dtype=torch.float32, device=dev)
     ctx.op_fill_normal_f32(latent, seed=42 + rank)  # independent sample per rank
     sig = ltx.sigmas(True, 8, T)
+    last, kept = args.warmup + args.steps - 1, {}
 
     def step(i):
         j = i % 8
+        if args.dump_outputs and i == last:
+            kept["before"] = latent.clone()
         ctx.denoise_dev(latent, sig[j:j + 2], context, mask, F, H, W, ctx_version=7, mask_all_ones=True)
         if j == 7:  # schedule finished: start the next sample from fresh noise (keeps values in range)
+            if args.dump_outputs and i == last:
+                kept["after"] = latent.clone()  # the last timed step's result, before the refill overwrites it
             ctx.op_fill_normal_f32(latent, seed=1000 + i + rank)
 
     el = timed(torch, dist, world, dev, step, args.warmup, args.steps)
     per_rank = list(timed.per_rank)
+    outputs = denoise_outputs(kept["before"], kept.get("after", latent), sig, last % 8) if args.dump_outputs else {}
 
-    # Roofline leg: the SAME K steps again with a HIP-event pair recorded on the launch stream around every GEMM /
+    # Roofline leg (--full): the SAME K steps again with a HIP-event pair recorded on the launch stream around every GEMM /
     # attention launch. The event packets themselves cost ~6 % of a step (2 x 434 launches), so they are kept out
     # of the region `value` is computed from; the per-launch durations they yield are unaffected by that overhead.
     roofline = None
     extra = {}
-    if not args.no_prof:
+    if args.full and not args.no_prof:
         ctx.prof_collect(0, reset=True)
         ctx.prof_enable(True)
         torch.cuda.synchronize()
@@ -573,12 +636,12 @@ def run_replica(args, ctx, ltx, dmod, torch, dist, dev, cfg, rank, world, side):
         out["roofline"] = roofline
     out.update(extra)
 
-    if rank == 0 and not args.no_vae:
+    if args.full and rank == 0 and not args.no_vae:
         try:
             out["vae"] = bench_vae(ctx, ltx, torch, dev, F, H, W)
         except Exception as e:  # the DiT line must still be reported
             out["vae"] = {"error": str(e)}
-    if rank == 0 and not args.no_aux:
+    if args.full and rank == 0 and not args.no_aux:
         try:
             out["pre_loop"] = bench_pre_loop(ctx, ltx, torch, dev)
         except Exception as e:
@@ -590,20 +653,22 @@ def run_replica(args, ctx, ltx, dmod, torch, dist, dev, cfg, rank, world, side):
             put("sp", leg_sp(args, ctx, ltx, dmod, torch, dist, dev, cfg, rank, world, side, 2))
 
         guarded_extra_legs(out, rank, legs_fn, 240.0)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(T, S_TEXT, F, H, W)
         try:
             out["cpu_baseline"]["vae"] = cpu_baseline_vae(F, H, W)
         except Exception as e:  # noqa: BLE001
             out["cpu_baseline"]["vae"] = {"error": repr(e)}
+    out["_outputs"] = outputs
     return out
 
 
 # ---------------------------------------------------------------------------------------------------------------
 # cfg-pair: BASELINE configs[2]
 # ---------------------------------------------------------------------------------------------------------------
-def leg_cfg_pair(args, ctx, ltx, dmod, torch, dist, dev, cfg, rank, world, side, steps, warmup=1):
-    """dev schedule, CFG 4.0 on 768x512x25. world == 1: the batched B = 2 forward; else one pair per two ranks."""
+def leg_cfg_pair(args, ctx, ltx, dmod, torch, dist, dev, cfg, rank, world, side, steps, warmup=1, keep=None):
+    """dev schedule, CFG 4.0 on 768x512x25. world == 1: the batched B = 2 forward; else one pair per two ranks. keep: a dict that gets
+    denoise_outputs() of the last timed step (--dump-outputs)."""
     F, H, W = ltx.latent_shape(WIDTH, HEIGHT, FRAMES)
     T = F * H * W
     context = torch.empty((2, S_TEXT, cfg.caption_channels), dtype=torch.bfloat16, device=dev)  # [negative, positive]
@@ -619,14 +684,21 @@ def leg_cfg_pair(args, ctx, ltx, dmod, torch, dist, dev, cfg, rank, world, side,
         dmod.bootstrap(ctx, group)  # RCCL communicator of THIS pair, created by the library from an id carried over gloo
         shard = ltx.SHARD_CFG
     n0 = ctx.dist_info()["collectives"]
+    last, kept = warmup + steps - 1, {}
 
     def step(i):
         j = i % 40
+        if keep is not None and i == last:
+            kept["before"] = latent.clone()
         ctx.denoise_dev(latent, sig[j:j + 2], context, mask, F, H, W, ctx_version=11, mask_all_ones=True, cfg_scale=4.0, shard=shard)
         if j == 39:
+            if keep is not None and i == last:
+                kept["after"] = latent.clone()  # the last timed step's result, before the refill overwrites it
             ctx.op_fill_normal_f32(latent, seed=5000 + i + pair)
 
     el = timed(torch, dist, world, dev, step, warmup, steps)
+    if keep is not None:
+        keep.update(denoise_outputs(kept["before"], kept.get("after", latent), sig, last % 40))
     res = {"steps_per_s": round(max(1, world // 2) * steps / el, 4), "ms_per_step": round(1e3 * el / steps, 3), "steps": steps,
            "pairs": max(1, world // 2), "cfg_scale": 4.0,
            "how": "one B=2 forward per step on one GPU" if world == 1 else
@@ -644,7 +716,8 @@ def leg_cfg_pair(args, ctx, ltx, dmod, torch, dist, dev, cfg, rank, world, side,
 
 def run_cfg_pair(args, ctx, ltx, dmod, torch, dist, dev, cfg, rank, world, side):
     ctx.dit_init_synthetic(cfg, seed=1234)
-    r = leg_cfg_pair(args, ctx, ltx, dmod, torch, dist, dev, cfg, rank, world, side, args.steps, args.warmup)
+    outputs = {} if args.dump_outputs else None
+    r = leg_cfg_pair(args, ctx, ltx, dmod, torch, dist, dev, cfg, rank, world, side, args.steps, args.warmup, keep=outputs)
     el = r["ms_per_step"] * 1e-3 * args.steps
     out = base_line(args, world, el, r["steps_per_s"], "weak",
                     "dev 40-step schedule, CFG 4.0 (negative + positive forward per step), 768x512x25 -> 1536 tokens, 1024 text keys, "
@@ -652,13 +725,15 @@ def run_cfg_pair(args, ctx, ltx, dmod, torch, dist, dev, cfg, rank, world, side)
                     {"tokens": 1536, "text_keys": S_TEXT, "parallelism": f"{r['pairs']} CFG pair(s): " + r["how"]})
     out["metric"] = "DiT denoise steps/sec, 768x512x25 dev CFG 4.0 (BASELINE configs[2])"
     out["cfg_pair"] = r
+    out["_outputs"] = outputs or {}
     return out
 
 
 # ---------------------------------------------------------------------------------------------------------------
 # sp: one 9984-token sample over all ranks (BASELINE configs[4] shape)
 # ---------------------------------------------------------------------------------------------------------------
-def leg_sp(args, ctx, ltx, dmod, torch, dist, dev, cfg, rank, world, side, steps, warmup=1):
+def leg_sp(args, ctx, ltx, dmod, torch, dist, dev, cfg, rank, world, side, steps, warmup=1, keep=None):
+    """keep: a dict that gets denoise_outputs() of the last timed step (--dump-outputs)."""
     F, H, W = ltx.latent_shape(768, 512, 201)
     T = F * H * W
     assert (F, H, W) == (26, 16, 24)
@@ -675,14 +750,21 @@ def leg_sp(args, ctx, ltx, dmod, torch, dist, dev, cfg, rank, world, side, steps
         dmod.bootstrap(ctx, side)
         shard = ltx.SHARD_SEQUENCE
     n0 = ctx.dist_info()["collectives"]
+    last, kept = warmup + steps - 1, {}
 
     def step(i):
         j = i % 8
+        if keep is not None and i == last:
+            kept["before"] = latent.clone()
         ctx.denoise_dev(latent, sig[j:j + 2], context, mask, F, H, W, ctx_version=13, mask_all_ones=True, shard=shard)
         if j == 7:
+            if keep is not None and i == last:
+                kept["after"] = latent.clone()  # the last timed step's result, before the refill overwrites it
             ctx.op_fill_normal_f32(latent, seed=7000 + i)
 
     el = timed(torch, dist, world, dev, step, warmup, steps)
+    if keep is not None:
+        keep.update(denoise_outputs(kept["before"], kept.get("after", latent), sig, last % 8))
     res = {"steps_per_s": round(steps / el, 4), "ms_per_step": round(1e3 * el / steps, 3), "steps": steps, "tokens": T,
            "tokens_per_rank": T // world,
            "how": "whole sample on one GPU" if world == 1 else
@@ -700,7 +782,8 @@ def leg_sp(args, ctx, ltx, dmod, torch, dist, dev, cfg, rank, world, side, steps
 
 def run_sp(args, ctx, ltx, dmod, torch, dist, dev, cfg, rank, world, side):
     ctx.dit_init_synthetic(cfg, seed=1234)
-    r = leg_sp(args, ctx, ltx, dmod, torch, dist, dev, cfg, rank, world, side, args.steps, args.warmup)
+    outputs, q_out = ({}, {}) if args.dump_outputs else (None, None)
+    r = leg_sp(args, ctx, ltx, dmod, torch, dist, dev, cfg, rank, world, side, args.steps, args.warmup, keep=outputs)
     if "skipped" in r:
         raise SystemExit("bench.py --mode sp: " + r["skipped"])
     if args.quant and world == 1:
@@ -710,7 +793,9 @@ def run_sp(args, ctx, ltx, dmod, torch, dist, dev, cfg, rank, world, side):
         mem0 = ctx.dit_memory_info()
         ctx.dit_quantize(args.quant)
         mem1 = ctx.dit_memory_info()
-        q = leg_sp(args, ctx, ltx, dmod, torch, dist, dev, cfg, rank, world, side, args.steps, args.warmup)
+        q = leg_sp(args, ctx, ltx, dmod, torch, dist, dev, cfg, rank, world, side, args.steps, args.warmup, keep=q_out)
+        if q_out:
+            outputs.update({k + "_quant": v for k, v in q_out.items()})
         r["quant"] = {"bits": args.quant, "group": 64, "steps_per_s": q["steps_per_s"], "ms_per_step": q["ms_per_step"],
                       "vs_bf16": round(q["ms_per_step"] / r["ms_per_step"], 4),
                       "weights_before": mem0, "weights_after": mem1,
@@ -722,6 +807,7 @@ def run_sp(args, ctx, ltx, dmod, torch, dist, dev, cfg, rank, world, side):
                     {"tokens": r["tokens"], "text_keys": S_TEXT, "parallelism": f"sequence parallel x{world}: " + r["how"]})
     out["metric"] = "DiT denoise steps/sec, 768x512x201 distilled, one sample (BASELINE configs[4] shape)"
     out["sp"] = r
+    out["_outputs"] = outputs or {}
     return out
 
 
@@ -747,6 +833,8 @@ def run_vae_tiles(args, ctx, ltx, dmod, torch, dist, dev, cfg, rank, world, side
             ctx.vae_decode_dev(lat, F, H, W, frames, tile=tile, overlap=ov)
 
     el = timed(torch, dist, world, dev, step, args.warmup, args.steps)
+    # every call decodes the same latent into `frames`: after the timed region it holds the last step's frames (rank 0 always does)
+    outputs = {"frames_sample": host_output(frames)} if args.dump_outputs and rank == 0 else {}
     out = base_line(args, world, el, args.steps / el, "strong",
                     f"VAE decode of 26 latent frames at 768x512, temporal tiles {plan} (tile 8, overlap 1) -> {nf} frames, tiles "
                     f"round-robin over {world} rank(s), raw tiles " + ("broadcast, blend + clip on every rank" if args.vae_to == "all" else
@@ -764,6 +852,7 @@ def run_vae_tiles(args, ctx, ltx, dmod, torch, dist, dev, cfg, rank, world, side
             out["rank_frames_identical"] = bool(all(torch.equal(allv[0], v) for v in allv))
         out["busy_ranks"] = min(world, len(plan))
         ctx.dist_shutdown()
+    out["_outputs"] = outputs
     return out
 
 

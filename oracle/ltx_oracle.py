@@ -38,22 +38,35 @@ _CONV_BLAS_THREADS = max(1, min(int(os.environ.get("LTX_ORACLE_CONV_BLAS_THREADS
 try:
     from threadpoolctl import ThreadpoolController as _TPC
     _tpc = None
+    _blas_cap = None
 
-    def _dit_blas():
-        global _tpc
+    def _blas_limit(n):
+        """Limit the BLAS pools to n threads, never above the count they started with. OpenBLAS fixes that count when it loads
+        (OPENBLAS_NUM_THREADS / OMP_NUM_THREADS, else the core count), and scipy's bundled copy (0.3.28) segfaults in its next sgemm
+        when it is raised past it - e.g. the conv path's 64 under OMP_NUM_THREADS=16. The cap is read once, from the pools the
+        controller sees; a pool loaded after that is not in the controller and keeps its own count."""
+        global _tpc, _blas_cap
         if _tpc is None:
             _tpc = _TPC()
-        return _tpc.limit(limits=_DIT_BLAS_THREADS, user_api="blas")
+            _blas_cap = min([p["num_threads"] for p in _tpc.select(user_api="blas").info()] or [n])
+        return _tpc.limit(limits=max(1, min(n, _blas_cap)), user_api="blas")
+
+    def blas_threads(n):
+        """the thread count `_blas_limit(n)` sets (n until the controller exists)"""
+        return n if _blas_cap is None else max(1, min(n, _blas_cap))
+
+    def _dit_blas():
+        return _blas_limit(_DIT_BLAS_THREADS)
 
     def _conv_blas():
         """the conv path's one tall sgemm per tap: scipy's OpenBLAS starts a thread per core (256 on the GPU box: 0.7 TFLOP/s on the
         128-channel tap shape) and is fastest with 64 (5.7 TFLOP/s; tools/host_blas_probe.py)"""
-        global _tpc
-        if _tpc is None:
-            _tpc = _TPC()
-        return _tpc.limit(limits=_CONV_BLAS_THREADS, user_api="blas")
+        return _blas_limit(_CONV_BLAS_THREADS)
 except Exception:  # noqa: BLE001 - threadpoolctl missing: the library default
     import contextlib
+
+    def blas_threads(n):
+        return n
 
     def _dit_blas():
         return contextlib.nullcontext()

@@ -93,3 +93,72 @@ def test_cpu_baseline_legs_run_on_a_small_case():
     assert r2["extrapolated"] is True and r2["value"] > 0 and "scaled x48/" in r2["sample"]
     v = bench.cpu_baseline_vae(1, 2, 2, budget_s=1e9)
     assert v["extrapolated"] is False and v["decode_ms"] > 0 and "ONE whole oracle.decode_video" in v["sample"]
+
+
+def test_dump_outputs_writes_float32_within_budget(tmp_path):
+    """--dump-outputs helpers: small outputs are copied whole, large ones sampled at the same seeded indices every time, files are
+    float32 (float64 stays float64), the 64 MB budget is enforced, and a denoise step's velocity is recovered from its Euler update."""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import torch
+
+    import bench
+
+    small = torch.arange(12, dtype=torch.float32).reshape(3, 4)
+    assert np.array_equal(bench.host_output(small), small.numpy())
+    big = torch.randn(bench.DUMP_SAMPLE + 1000, dtype=torch.float64)
+    s1, s2 = bench.host_output(big), bench.host_output(big)
+    assert s1.shape == (bench.DUMP_SAMPLE,) and s1.dtype == np.float32 and np.array_equal(s1, s2)
+    assert np.isin(s1[:100], big.float().numpy()).all()
+    bench.dump_outputs(str(tmp_path / "d"), {"a": small.numpy().astype(np.float16), "b": s1.astype(np.float64)})
+    assert sorted(os.listdir(tmp_path / "d")) == ["a.npy", "b.npy"]
+    assert np.load(tmp_path / "d" / "a.npy").dtype == np.float32 and np.load(tmp_path / "d" / "b.npy").dtype == np.float64
+    sig = np.array([1.0, 0.99375, 0.0], np.float32)
+    x, v = torch.randn(2, 3, 4), torch.randn(2, 3, 4)
+    for j in (0, 1):
+        o = bench.denoise_outputs(x, x + (float(sig[j + 1]) - float(sig[j])) * v, sig, j)
+        assert o["latent"].dtype == np.float32 and o["velocity"].dtype == np.float64
+        assert np.allclose(o["velocity"], v.numpy(), atol=1e-3 if j == 0 else 1e-6)
+    with pytest.raises(AssertionError):
+        bench.dump_outputs(str(tmp_path / "e"), {"x": np.zeros(bench.DUMP_MAX_BYTES // 4 + 1, np.float32)})
+
+
+def test_options_of_the_plain_and_full_runs_are_documented():
+    r = subprocess.run([sys.executable, BENCH, "--help"], capture_output=True, text=True, env=_clean_env(), timeout=120)
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs" in r.stdout
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean_and_dumps_the_last_step(tmp_path, gpu_ctx):
+    """A plain run: exactly --steps timed steps, the headline fields and nothing that needs runs of its own (those are --full's);
+    --dump-outputs writes the latent the last timed step returned and the velocity it applied. Warm-up 5 + 3 steps ends on the
+    schedule's last step, whose result the loop would overwrite with fresh noise: the dump must hold the denoised latent, and two runs
+    with equal arguments agree."""
+    import numpy as np
+    import torch
+
+    dumps = []
+    for k in range(2):
+        d = tmp_path / f"out{k}"
+        r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "3", "--warmup", "5", "--dump-outputs", str(d)],
+                           capture_output=True, text=True, env=_clean_env(), timeout=600)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1
+        out = json.loads(lines[0])
+        assert out["steps"] == 3 and out["warmup"] == 5 and out["unit"] == "steps/s" and out["higher_is_better"] is True
+        assert out["dtype"] == "bf16" and out["ms_per_step"] > 0 and abs(out["value"] - 1e3 / out["ms_per_step"]) < 0.01 * out["value"]
+        assert not {"roofline", "attention", "row_kernels", "vae", "pre_loop", "cpu_baseline"} & set(out), sorted(out)
+        assert sorted(os.listdir(d)) == ["latent.npy", "velocity.npy"]
+        lat, vel = np.load(d / "latent.npy"), np.load(d / "velocity.npy")
+        assert lat.dtype == np.float32 and lat.shape == (1, 128, 4, 16, 24) and np.isfinite(lat).all()
+        assert vel.dtype == np.float64 and vel.shape == lat.shape and np.isfinite(vel).all() and float(np.abs(vel).max()) > 0
+        dumps.append((lat, vel))
+    refill = torch.empty((1, 128, 4, 16, 24), dtype=torch.float32, device="cuda")
+    gpu_ctx.op_fill_normal_f32(refill, seed=1000 + 7)  # what bench.py's loop writes after step 7 (rank 0)
+    torch.cuda.synchronize()
+    assert not np.allclose(dumps[0][0], refill.cpu().numpy(), atol=1e-2)
+    for k, name in enumerate(("latent", "velocity")):
+        rel = float(np.linalg.norm(dumps[0][k] - dumps[1][k]) / np.linalg.norm(dumps[0][k]))
+        print(f"bench --dump-outputs, two runs: {name} rel-L2 {rel:.3e}")
+        assert rel <= 1e-3, (name, rel)

@@ -82,6 +82,28 @@ def test_conv3d_blas_form_equals_the_einsum_form(oracle, shape, cout, causal):
     assert np.array_equal(oracle.conv3d_full(x, w, None, causal), oracle.conv3d_full(x, w, np.zeros(cout, np.float32), causal))
 
 
+def test_blas_limits_stay_within_the_threads_the_environment_gave():
+    """OMP_NUM_THREADS fixes how many threads OpenBLAS starts with, and scipy's bundled OpenBLAS segfaults when a limit raises it past
+    that. The oracle asks for 16 (DiT) / 64 (conv) BLAS threads: under OMP_NUM_THREADS=1 both must come out as 1 and the conv path
+    must still agree with the einsum form. Runs in a child process, whose BLAS pools start under that environment."""
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = ("import numpy as np, ltx_oracle as o\n"
+            "rng = np.random.default_rng(7)\n"
+            "x = rng.standard_normal((1, 64, 4, 32, 48)).astype(np.float32)\n"   # taps large enough for OpenBLAS to thread
+            "w = rng.standard_normal((64, 64, 3, 3, 3)).astype(np.float32)\n"
+            "a, c = o.conv3d_full_einsum(x, w, None), o.conv3d_full(x, w, None)\n"
+            "assert float(np.abs(a - c).max()) <= 2e-6 * float(np.abs(a).max())\n"
+            "o.linear(x.reshape(-1, 48), w.reshape(-1, 48))\n"
+            "print(o.blas_threads(o._CONV_BLAS_THREADS), o.blas_threads(o._DIT_BLAS_THREADS))\n")
+    env = dict(os.environ, OMP_NUM_THREADS="1", OPENBLAS_NUM_THREADS="1", PYTHONPATH=os.path.join(root, "oracle"))
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=env, timeout=300)
+    assert r.returncode == 0, (r.returncode, r.stdout[-1000:], r.stderr[-2000:])
+    assert r.stdout.split() == ["1", "1"], r.stdout
+
+
 @pytest.mark.parametrize("per_frame", [False, True])
 def test_conv_nd_zero_and_causal_zero_vs_torch(oracle, per_frame):
     """The zero-padded convs of the latent upscaler (SpatialUpscaler.swift:78-92,139-145) and of the VAE encoder

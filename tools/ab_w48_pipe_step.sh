@@ -9,7 +9,7 @@ gen() { for v in "" "--bias" "--prescaled" "--bias --prescaled"; do W48_PIPE=$1 
 for leg in cross1 step cross2; do
   mode=${leg%[12]}
   gen $mode
-  timeout -k 10 300 python bench.py > $out/$leg.json 2> $out/$leg.err
+  timeout -k 10 300 python bench.py --full > $out/$leg.json 2> $out/$leg.err
   python - $out/$leg.json $leg <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))

@@ -1,5 +1,5 @@
 import os, sys, importlib, numpy as np, torch
-sys.path.insert(0, '/root/repo' if os.path.exists('/root/repo/tests') else os.environ.get('GRAFT_REPO_ROOT', '.'))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))  # the repository root, wherever it is checked out
 ltx = importlib.import_module('ltx-video-swift-mlx_amd')
 ctx = ltx.Context(0)
 def run(impl, T, S, H, seed=0):
