@@ -529,6 +529,23 @@ int ltx_op_norm_mod(ltx_ctx* ctx, const float* x, const float* scale, const floa
 /* q/k RMSNorm (weight w[D]) + split RoPE (cos/sin [T][D/2] or NULL) -> bf16 */
 int ltx_op_qknorm_rope(ltx_ctx* ctx, const float* x, long ldx, const float* w, const float* cos_t, const float* sin_t,
                        int T, int rows, int D, float eps, uint16_t* out);
+/* ltx_op_norm_mod with every argument of the launcher (test seam: the shapes and strides the DiT passes select kernels the call above
+ * cannot reach): x [rows][ldx] f32, out [rows][ldo] bf16, the modulation row of output row r is scale/shift + b * mod_bstride with
+ * b = row_map ? row_map[r] : r / rows_per_batch (row_map: device int32 [rows] or NULL; per-token timestep groups of image-to-video). */
+int ltx_op_norm_mod_ex(ltx_ctx* ctx, const float* x, long ldx, const float* scale, const float* shift, long mod_bstride,
+                       int rows_per_batch, const int32_t* row_map, int rows, int D, int norm_kind, float eps,
+                       int round_norm_bf16, uint16_t* out, long ldo);
+/* ltx_op_qknorm_rope for the q and k of a fused projection in ONE launch, as the DiT's self-attention runs it (test seam): job 0
+ * (x0, w0, out0) and job 1 (x1 == NULL: one job) share ldx, ldo and the tables; rows are f32, or bf16 at the same element offsets
+ * with x_bf16 != 0 (ldx counts elements of that type); out_scale0 multiplies job 0's row before its one rounding to bf16 (the folded
+ * softmax scale), job 1's is 1. */
+int ltx_op_qknorm_rope_pair(ltx_ctx* ctx, const void* x0, const float* w0, uint16_t* out0, const void* x1, const float* w1,
+                            uint16_t* out1, long ldx, long ldo, const float* cos_t, const float* sin_t, int T, int rows, int D,
+                            float eps, float out_scale0, int x_bf16);
+/* 1 when the VAE decoder's upsampler conv C -> 4C at (F, H, W) carries the next stage's first PixelNorm in its epilogue (the conv
+ * launcher's own rule, which the decoder asks; options "conv_halo" and the 32-bit offset limits of the halo-staged kernels enter it),
+ * 0 when that PixelNorm runs as a row pass. Host-side, no device. */
+int ltx_conv_takes_d2s_pn(int F, int H, int W, int C);
 /* deterministic device fills used by bench.py to create synthetic inputs */
 int ltx_op_fill_normal_bf16(ltx_ctx* ctx, uint16_t* p, long n, uint64_t seed, float mean, float stddev);
 int ltx_op_fill_normal_f32(ltx_ctx* ctx, float* p, long n, uint64_t seed, float mean, float stddev);

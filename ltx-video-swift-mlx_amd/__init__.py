@@ -136,6 +136,11 @@ def get_option(key):
     return v.value
 
 
+def conv_takes_d2s_pn(F, H, W, C):
+    """``ltx_conv_takes_d2s_pn``: does the decoder's upsampler conv C -> 4C at (F, H, W) carry the next stage's first PixelNorm?"""
+    return bool(lib.ltx_conv_takes_d2s_pn(F, H, W, C))
+
+
 def option_table():
     """[(name, default, min, max, numerics, doc)] of every switch (``ltx_option_info``)."""
     n = lib.ltx_option_info(-1, None, None, None, None, None, None)
@@ -705,6 +710,21 @@ class Context:
     def op_qknorm_rope(self, x, w, cos, sin, T, out, eps=1e-6):
         rows, D = out.shape
         self._ck(lib.ltx_op_qknorm_rope(self._h, _ptr(x), x.stride(0), _ptr(w), _ptr(cos), _ptr(sin), T, rows, D, eps, _ptr(out)))
+
+    def op_norm_mod_ex(self, x, scale, shift, out, rows, D, mod_bstride=0, rows_per_batch=None, row_map=None, norm_kind=0, eps=1e-6,
+                       round_norm_bf16=False):
+        """``ltx_op_norm_mod_ex``: x / out are 2-D tensors whose row strides are ldx / ldo (``rows`` x ``D`` of them are used)."""
+        self._ck(lib.ltx_op_norm_mod_ex(self._h, x.data_ptr(), x.stride(0), _ptr(scale), _ptr(shift), mod_bstride,
+                                        rows if rows_per_batch is None else rows_per_batch, _ptr(row_map), rows, D, norm_kind, eps,
+                                        int(round_norm_bf16), out.data_ptr(), out.stride(0)))
+
+    def op_qknorm_rope_pair(self, x0, w0, out0, x1, w1, out1, cos, sin, T, rows, D, eps=1e-6, out_scale0=1.0):
+        """``ltx_op_qknorm_rope_pair``: x0 / x1 are views of f32 or bf16 rows with one row stride (x1 None: one job)."""
+        assert x1 is None or (x1.stride(0) == x0.stride(0) and out1.stride(0) == out0.stride(0) and x1.dtype == x0.dtype)
+        vp = lambda t: None if t is None else t.data_ptr()  # strided views of wider buffers
+        self._ck(lib.ltx_op_qknorm_rope_pair(self._h, vp(x0), _ptr(w0), vp(out0), vp(x1), _ptr(w1), vp(out1), x0.stride(0),
+                                             out0.stride(0), _ptr(cos), _ptr(sin), T, rows, D, eps, out_scale0,
+                                             int(x0.element_size() == 2)))
 
     def op_fill_normal_bf16(self, t, seed, mean=0.0, std=1.0):
         self._ck(lib.ltx_op_fill_normal_bf16(self._h, _ptr(t), t.numel(), seed, mean, std))

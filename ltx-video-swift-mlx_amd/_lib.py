@@ -175,6 +175,9 @@ SIGNATURES = {
     "ltx_attention_key_splits": (_i, [_i, _i, _i, _i]),
     "ltx_op_norm_mod": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _i, _vp]),
     "ltx_op_qknorm_rope": (_i, [_vp, _vp, _l, _vp, _vp, _vp, _i, _i, _i, _f, _vp]),
+    "ltx_op_norm_mod_ex": (_i, [_vp, _vp, _l, _vp, _vp, _l, _i, _vp, _i, _i, _i, _f, _i, _vp, _l]),
+    "ltx_op_qknorm_rope_pair": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _l, _l, _vp, _vp, _i, _i, _i, _f, _f, _i]),
+    "ltx_conv_takes_d2s_pn": (_i, [_i, _i, _i, _i]),
     "ltx_op_fill_normal_bf16": (_i, [_vp, _vp, _l, _u64, _f, _f]),
     "ltx_op_fill_normal_f32": (_i, [_vp, _vp, _l, _u64, _f, _f]),
 }

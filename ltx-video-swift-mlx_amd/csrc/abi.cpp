@@ -1191,6 +1191,34 @@ int ltx_op_qknorm_rope(ltx_ctx* ctx, const float* x, long ldx, const float* w, c
     return guarded(ctx, [&] { launch_qknorm_rope(x, ldx, w, cos_t, sin_t, T, out, D, rows, D, eps, ctx->stream); });
 }
 
+int ltx_op_norm_mod_ex(ltx_ctx* ctx, const float* x, long ldx, const float* scale, const float* shift, long mod_bstride,
+                       int rows_per_batch, const int32_t* row_map, int rows, int D, int norm_kind, float eps,
+                       int round_norm_bf16, uint16_t* out, long ldo) {
+    if (!ctx) return LTX_ERR_INVALID_CONFIGURATION;
+    return guarded(ctx, [&] {
+        launch_norm_mod(x, ldx, scale, shift, mod_bstride, rows_per_batch, out, ldo, rows, D, norm_kind, eps, round_norm_bf16, ctx->stream, row_map);
+    });
+}
+
+int ltx_op_qknorm_rope_pair(ltx_ctx* ctx, const void* x0, const float* w0, uint16_t* out0, const void* x1, const float* w1,
+                            uint16_t* out1, long ldx, long ldo, const float* cos_t, const float* sin_t, int T, int rows, int D,
+                            float eps, float out_scale0, int x_bf16) {
+    if (!ctx) return LTX_ERR_INVALID_CONFIGURATION;
+    return guarded(ctx, [&] {
+        launch_qknorm_rope2((const float*)x0, w0, out0, (const float*)x1, w1, out1, ldx, ldo, cos_t, sin_t, T, rows, D, eps, ctx->stream,
+                            out_scale0, x_bf16 != 0);
+    });
+}
+
+int ltx_conv_takes_d2s_pn(int F, int H, int W, int C) {
+    GemmArgs g;  // an upsampler conv C -> 4C of the VAE decoder at (F, H, W), as vae.cpp forms it
+    g.ldb = 27L * C; g.M = (int)((long)F * H * W); g.N = 4 * C; g.K = 27 * C;
+    g.conv = 1;
+    g.geom.F = F; g.geom.H = H; g.geom.W = W; g.geom.C = C;
+    g.ep.d2s = 1;
+    return (long)F * H * W <= 0x7fffffffL && gemm_conv_takes_d2s_pn(g) ? 1 : 0;
+}
+
 int ltx_op_fill_normal_bf16(ltx_ctx* ctx, uint16_t* p, long n, uint64_t seed, float mean, float stddev) {
     if (!ctx) return LTX_ERR_INVALID_CONFIGURATION;
     return guarded(ctx, [&] { launch_fill_normal_bf16(p, n, seed, mean, stddev, ctx->stream); });

@@ -141,6 +141,10 @@ struct NormAfter {
     const int32_t* row_map = nullptr;
 };
 void launch_gemm_bf16(const GemmArgs& args, hipStream_t stream, const NormAfter* norm_after);
+// Does launch_gemm_bf16 accept GemmEpilogue::pn_out on this depth-to-space conv launch (d2s == 1, N == 8 x 128: the VAE upsampler in
+// front of the 128-channel stage)? Only the halo-staged kernels carry that epilogue, so this is the launcher's own rule for them,
+// option "conv_halo" and the 32-bit offset limits included. A caller asks BEFORE it sets pn_out and keeps its row pass on `false`.
+bool gemm_conv_takes_d2s_pn(const GemmArgs& args);
 // can a launch of this shape take B as 8-bit codes (GemmArgs::Bq)?
 bool gemm_takes_codes(int M, int N, int K);
 bool gemm_fewrow_takes(int M, int N, int K, int splits);

@@ -2437,8 +2437,14 @@ static void launch_conv_halo2(const GemmArgs& a, hipStream_t stream) {
     const int nrt = conv_halo2_takes(a);
     if (nrt == 1) launch_conv_halo2_nrt<1>(a, stream);
     else if (nrt == 2) launch_conv_halo2_nrt<2>(a, stream);
-    else launch_conv_halo2_nrt<4>(a, stream);
+    else {
+        LTX_REQUIRE(nrt == 4, "conv halo2: the launch is not one the tall kernel takes (W=%d H=%d N=%d M=%d)", a.geom.W, a.geom.H, a.N, a.M);
+        launch_conv_halo2_nrt<4>(a, stream);
+    }
 }
+// Both halo-staged kernels carry the depth-to-space + PixelNorm epilogue, and conv_halo2_takes is a subset of conv_halo_takes (it starts
+// with it), so the wider rule decides; it reads no device property and can be asked without one.
+bool gemm_conv_takes_d2s_pn(const GemmArgs& a) { return a.ep.d2s == 1 && a.N == 8 * 128 && a.split_k <= 1 && conv_halo_takes(a); }
 template <int BN>
 static void launch_conv_halo(const GemmArgs& a, hipStream_t stream) {
     constexpr int smem = 2 * 32 * 1024 + 6 * BN * ROW_BYTES;
@@ -2638,7 +2644,7 @@ void launch_gemm_bf16(const GemmArgs& a_in, hipStream_t stream) {
             // the fused PixelNorm output needs every channel of a row in ONE 128-column tile and the epilogue in the GEMM launch
             // (round 5: or, with the depth-to-space store of an upsampler, N == 8 x 128: a tile is one sub-position's 128 channels; only the
             // halo-staged kernels carry that epilogue)
-            LTX_REQUIRE(((a.N == 128 && !a.ep.d2s) || (a.ep.d2s == 1 && a.N == 8 * 128 && conv_halo_takes(a))) && a.split_k <= 1 &&
+            LTX_REQUIRE(((a.N == 128 && !a.ep.d2s) || gemm_conv_takes_d2s_pn(a)) && a.split_k <= 1 &&
                             (a.ep.pn_scale == nullptr) == (a.ep.pn_shift == nullptr),
                         "gemm: fused PixelNorm output needs N == 128 (got %d; 1024 with a depth-to-space store on a halo-staged launch) and no split-K", a.N);
             // (A last partial round - the 128-channel stage at 768x512 is 3200 tiles = 12.5 rounds - is NOT worth a launch of its own here:

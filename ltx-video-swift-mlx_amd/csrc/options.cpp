@@ -25,7 +25,7 @@ const LtxOptInfo kInfo[OPT_COUNT] = {
     {"finish_norm", 1, 0, 1, 0, "0: the next block's adaLN pass as its own launch"},
     {"finish_rows", 1, 1, 4, 0, "rows per workgroup of the fused split-K finish + norm pass (1, 2, 4)"},
     {"norm_rows", 0, 0, 4, 0, "rows per workgroup of the norm + modulation pass (0 = launcher's choice, 2, 4)"},
-    {"qknorm_no_pair", 0, 0, 1, 0, "1: q and k RMSNorm + RoPE as two launches"},
+    {"qknorm_no_pair", 0, 0, 1, 1, "1: q and k RMSNorm + RoPE on the one-job rows kernel (the same sums in the same order, but the compiler fuses the two kernels' multiply-adds differently: about 1e-5 of the elements round the other way)"},
     {"conv_halo", 1, 0, 1, 0, "0: no halo-staged conv kernel"},
     {"conv_persist", 1, 0, 1, 0, "0: halo-staged conv kernel with one workgroup per tile"},
     {"conv_block", 1, 0, 1, 0, "0: plain tile order for single-column convs"},

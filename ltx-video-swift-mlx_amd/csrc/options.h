@@ -27,7 +27,7 @@ enum LtxOpt {
     OPT_FINISH_NORM,      // 0 = the next block's adaLN pass as its own launch (default 1: rides on the split-K finish)
     OPT_FINISH_ROWS,      // rows per workgroup of the fused finish + norm pass: 1 (default), 2, 4 - clamped to what divides M and rows_per_batch
     OPT_NORM_ROWS,        // rows per workgroup of norm_mod_rows_kernel: 0 = launcher's choice, 2, 4
-    OPT_QKNORM_NO_PAIR,   // 1 = q and k RMSNorm + RoPE as two launches
+    OPT_QKNORM_NO_PAIR,   // 1 = q and k RMSNorm + RoPE on the rows kernel (NOT bit-neutral, measured: 1e-5 of the elements differ by one rounding)
     OPT_CONV_HALO,        // 0 = no halo-staged conv kernel
     OPT_CONV_PERSIST,     // 0 = halo kernel one workgroup per tile
     OPT_CONV_BLOCK,       // 0 = plain tile order for single-column convs

@@ -223,8 +223,7 @@ struct Dims {
 
 // `skws`/`skws_elems`: split-K workspace (floats) - convs with too few output tiles to fill the chip (the 1024-channel
 // stage: 1536 positions -> 64 tiles of 192x128) split their 27*Cin reduction over several workgroups per tile
-void conv3d(const bf16_t* x, const Dims& d, const ConvW& cw, GemmEpilogue ep, hipStream_t st, float* skws = nullptr,
-            long skws_elems = 0) {
+GemmArgs conv3d_args(const bf16_t* x, const Dims& d, const ConvW& cw, GemmEpilogue ep, float* skws = nullptr, long skws_elems = 0) {
     GemmArgs g;
     g.A = x;
     g.B = cw.w;
@@ -250,7 +249,11 @@ void conv3d(const bf16_t* x, const Dims& d, const ConvW& cw, GemmEpilogue ep, hi
         g.split_ws = skws;  // also lets the launcher run a last partial round of tiles as a split-K launch
         g.split_ws_elems = skws_elems;
     }
-    launch_gemm_bf16(g, st);
+    return g;
+}
+void conv3d(const bf16_t* x, const Dims& d, const ConvW& cw, GemmEpilogue ep, hipStream_t st, float* skws = nullptr,
+            long skws_elems = 0) {
+    launch_gemm_bf16(conv3d_args(x, d, cw, ep, skws, skws_elems), st);
 }
 
 // One VAEResBlock3d (VideoDecoder.swift:75-131) on the f32 stream x [P][C], in place. `md` = the block's modulation rows (shift1,
@@ -398,9 +401,10 @@ int decode_tile(ltx_ctx* ctx, VaeModel* m, const float* latent, long chan_stride
             // The upsampler in front of the 128-channel stage (round 5): a 128-column tile of this launch is one sub-position with ALL
             // channels of its voxel, so the epilogue also emits the first res-block's input - PixelNorm + its modulation + SiLU - where a
             // row pass re-read the whole upsampled f32 stream (315 MB at 768x512). Only where a halo-staged kernel takes the launch (they
-            // carry that epilogue) and the conv's input is not the buffer the next stage starts from.
-            const bool halo_w = (d.W <= 192 && d.W >= 48 && 192 % d.W == 0) || d.W % 192 == 0;
-            if (C / 2 == 128 && m->groups[g + 1].C == 128 && halo_w && d.H >= 2 && hin != hb && ltx_opt(OPT_CONV_D2S_PN) != 0) {
+            // carry that epilogue: the launcher's own rule decides, so option "conv_halo" = 0 and streams beyond the kernels' 32-bit
+            // offsets keep the row pass) and the conv's input is not the buffer the next stage starts from.
+            if (C / 2 == 128 && m->groups[g + 1].C == 128 && hin != hb && ltx_opt(OPT_CONV_D2S_PN) != 0 &&
+                gemm_conv_takes_d2s_pn(conv3d_args(hin, d, m->up[g], e))) {
                 const float* nmd = mods + mod_ofs_group[g + 1];
                 e.pn_out = hb;
                 e.ld_pn = 128;

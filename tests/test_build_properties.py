@@ -64,3 +64,26 @@ def test_tall_conv_kernel_has_no_scratch_access_inside_its_counted_waits(tmp_pat
         loop = body[barriers[0]:barriers[10]]
         assert not [ln for ln in loop if "scratch_" in ln], f"NRT = {nrt}: scratch access inside the K loop"
         assert sum("v_mfma_f32_16x16x32_bf16" in ln for ln in loop) == 9 * 48, nrt
+
+
+def test_product_library_has_no_undefined_getenv():
+    """The product library never reads the environment (its switches are the table behind ltx_ctx_set_option): it must not even import
+    getenv. Setting variables before a forward cannot show that - nothing would move either way; the dynamic symbol table can."""
+    so = os.path.join(CSRC, "build", "libltxhip.so")
+    if not os.path.exists(so):
+        import sys
+
+        sys.path.insert(0, ROOT)
+        import __graft_entry__ as g
+
+        g.build()
+    if shutil.which("nm"):
+        out = subprocess.run(["nm", "-D", "--undefined-only", so], check=True, capture_output=True, text=True).stdout
+    elif shutil.which("readelf"):
+        out = "\n".join(ln for ln in subprocess.run(["readelf", "--dyn-syms", "-W", so], check=True, capture_output=True, text=True).stdout.splitlines()
+                        if " UND " in ln)
+    else:
+        pytest.skip("neither nm nor readelf is installed")
+    undefined = {ln.split()[-1].split("@")[0] for ln in out.splitlines() if ln.split()}
+    assert "malloc" in undefined or "memcpy" in undefined, "the listing is not a symbol table"
+    assert not {s for s in undefined if "getenv" in s}, undefined

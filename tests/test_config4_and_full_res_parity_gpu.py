@@ -360,6 +360,7 @@ def test_conv_kernel_variants_agree_bit_for_bit_per_epilogue(ltx, oracle, vae_fr
         return run
 
     cases = {"res-block 128 ch (PixelNorm + residual epilogue)": res_block(3, 1, 5, 64, 192),
+             "res-block 128 ch at W = 384 (the tall kernel's one-image-row instance; 73 728 rows)": res_block(3, 1, 3, 64, 384),
              "res-block 256 ch (plain residual, tail window)": res_block(2, 0, 13, 64, 96),
              "upsampler 256 ch (depth-to-space store)": upsample(2, 5, 32, 96),
              "whole decode 2x8x12 (un-patchify store, partial tiles)": decode(2, 8, 12)}

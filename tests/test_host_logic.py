@@ -68,6 +68,25 @@ def test_abi_revision_and_option_table(ltx):
             assert old not in blob, old
 
 
+def test_conv_takes_d2s_pn_is_the_conv_launchers_rule(ltx):
+    """gemm_conv_takes_d2s_pn through ltx_conv_takes_d2s_pn (host-side, no device): the VAE decoder fuses the 128-channel stage's first
+    PixelNorm into the 256 -> 1024 upsampler conv exactly where a halo-staged kernel takes that launch. Known answers from
+    conv_halo_takes (gemm.hip): W in {48, 64, 96, 192} or a multiple of 192, H >= 2, at least 192 rows, M * C < 2^31 (32-bit element
+    offsets), and option `conv_halo` on."""
+    assert ltx.conv_takes_d2s_pn(13, 64, 96, 256)          # the headline decode (768 x 512 x 25)
+    assert ltx.conv_takes_d2s_pn(5, 8, 192, 256) and ltx.conv_takes_d2s_pn(13, 128, 192, 256) and ltx.conv_takes_d2s_pn(3, 8, 48, 256)
+    assert not ltx.conv_takes_d2s_pn(13, 64, 80, 256)      # 192 % 80 != 0
+    assert not ltx.conv_takes_d2s_pn(13, 1, 192, 256)      # one image row
+    assert not ltx.conv_takes_d2s_pn(1, 2, 48, 256)        # 96 rows: less than one tile
+    assert not ltx.conv_takes_d2s_pn(13, 64, 96, 128)      # N = 512: not eight sub-positions of 128 channels
+    # 32-bit element offsets: F x 8 x 192 rows x 256 channels reaches 2^31 between F = 5461 and 5462
+    assert 5461 * 8 * 192 * 256 < 2 ** 31 <= 5462 * 8 * 192 * 256
+    assert ltx.conv_takes_d2s_pn(5461, 8, 192, 256) and not ltx.conv_takes_d2s_pn(5462, 8, 192, 256)
+    with ltx.options(conv_halo=0):
+        assert not ltx.conv_takes_d2s_pn(13, 64, 96, 256) and not ltx.conv_takes_d2s_pn(5, 8, 192, 256)
+    assert ltx.get_option("conv_halo") == 1 and ltx.conv_takes_d2s_pn(13, 64, 96, 256)
+
+
 # ---- R1 ----
 @pytest.mark.parametrize("whf,expect", [((256, 256, 9), (2, 8, 8)), ((768, 512, 25), (4, 16, 24)),
                                         ((1536, 1024, 25), (4, 32, 48)), ((768, 512, 201), (26, 16, 24)),
