@@ -298,6 +298,48 @@ int ltx_vae_encoder_latent_frames(int T);
 int ltx_map_vae_encoder_key(const char* file_key, char* out, int cap);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Audio decode leg (decodeAudio, Vocoder.swift:325-361): audio latent -> AudioVAE.decode -> stereo mel -> LTX2Vocoder -> 24 kHz
+ * stereo waveform. The dual (video + audio) transformer that PRODUCES the audio latent is not part of this library yet: the latent
+ * is an input. Precision: weights rounded to bf16 at load, bf16 conv operands, f32 accumulation, f32 residual streams.
+ * ---------------------------------------------------------------------------------------------------------- */
+/* Replaces AudioVAE() + loadAudioVAEWeights / applyAudioVAEWeights (ModelDownloader.swift:1116-1158): keeps `decoder.*`, `latents_mean`
+ * and `latents_std`, drops everything else; Conv2d weights are PyTorch (out, in, kh, kw) under `...conv.weight`. Channel counts come
+ * from the tensor shapes (multiples of 32). Kept tensors that are no parameter (or have the wrong rank) count as unmatched, absent
+ * biases / statistics as missing (ltx_load_report); an absent convolution weight fails with LTX_ERR_WEIGHT_LOADING_FAILED. */
+int ltx_audio_vae_load(ltx_ctx* ctx, const char* safetensors_path);
+/* Random-init decoder of the reference architecture (AudioVAE.swift:265-323); base_channels 0 = 128. */
+int ltx_audio_vae_init_synthetic(ltx_ctx* ctx, int base_channels, uint64_t seed);
+int ltx_audio_vae_unload(ltx_ctx* ctx);
+/* Replaces LTX2Vocoder() + loadVocoderWeights / applyVocoderWeights (ModelDownloader.swift:1160-1194, Vocoder.swift:273-311): Conv1d
+ * weights are (out, in, k), `upsamplers.N.weight` is (in, out, k). Reporting as above. */
+int ltx_vocoder_load(ltx_ctx* ctx, const char* safetensors_path);
+/* Random-init vocoder (Vocoder.swift:144-211); hidden_channels 0 = 1024. */
+int ltx_vocoder_init_synthetic(ltx_ctx* ctx, int hidden_channels, uint64_t seed);
+int ltx_vocoder_unload(ltx_ctx* ctx);
+/* Replaces AudioVAE.decode (AudioVAE.swift:407-456): latent [8][T][16] f32 (normalised, as the denoise loop leaves it) ->
+ * mel [2][max(4T-3, 1)][64] f32. HOST pointers. */
+int ltx_audio_vae_decode(ltx_ctx* ctx, const float* latent, int T, float* mel);
+/* Same with DEVICE pointers, asynchronous on the context stream. */
+int ltx_audio_vae_decode_dev(ltx_ctx* ctx, const float* latent, int T, float* mel);
+/* Replaces LTX2Vocoder.callAsFunction (Vocoder.swift:217-266): mel [2][T_mel][64] f32 -> waveform [2][240 * T_mel] f32 in (-1, 1).
+ * HOST pointers. */
+int ltx_vocoder_forward(ltx_ctx* ctx, const float* mel, int T_mel, float* waveform);
+int ltx_vocoder_forward_dev(ltx_ctx* ctx, const float* mel, int T_mel, float* waveform);
+/* Replaces decodeAudio(latents:audioVAE:vocoder:) (Vocoder.swift:325-361): the two chained, the mel never leaves the device.
+ * latent [8][T][16] f32 -> waveform [2][ltx_audio_sample_count(T)] f32. HOST pointers. */
+int ltx_audio_decode(ltx_ctx* ctx, const float* latent, int T, float* waveform);
+int ltx_audio_decode_dev(ltx_ctx* ctx, const float* latent, int T, float* waveform);
+/* computeAudioLatentFrames (LTXPipeline.swift:530-534): round(f32(video_frames / fps) * f32(16000 / 160 / 4)). Pure host code. */
+int ltx_audio_latent_frames(int video_frames, float fps);
+/* max(4T - 3, 1) (AudioVAE.swift:413) and 240 times that (Vocoder.swift:130); the vocoder's output rate, 24000 (Vocoder.swift:153). */
+int ltx_audio_mel_frames(int T);
+long ltx_audio_sample_count(int T);
+int ltx_audio_sample_rate(void);
+/* AudioExporter.exportToWAV (AudioExporter.swift:19-92): waveform [2][n] f32 -> gain, clamp to [-1, 1], int16 by truncation toward
+ * zero of x * 32767.0f, interleaved L/R behind the 44-byte PCM header. Pure host code. */
+int ltx_write_wav(const char* path, const float* waveform, long n, int sample_rate, float gain);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Text-embedding connector (VideoGemmaTextEncoderModel.encodeFromHiddenStates,
  * LTXTextEncoder.swift:574-643 - call site LTXPipeline.swift:640-700): from the 49 Gemma-3 hidden states to the
  * [B,T,3840] bf16 context + all-ones mask that ltx_denoise / ltx_dit_forward take. The language model itself is not
@@ -546,6 +588,22 @@ int ltx_op_qknorm_rope_pair(ltx_ctx* ctx, const void* x0, const float* w0, uint1
  * launcher's own rule, which the decoder asks; options "conv_halo" and the 32-bit offset limits of the halo-staged kernels enter it),
  * 0 when that PixelNorm runs as a row pass. Host-side, no device. */
 int ltx_conv_takes_d2s_pn(int F, int H, int W, int C);
+/* The audio leg's convolutions (csrc/audio_conv.hip), one launch family: x channels-last bf16, f32 accumulation. tile: -1 auto, else
+ * the instance by output-channel width (128, 64, 32). Cin must be a multiple of 32. Epilogue arguments as the launcher takes them:
+ * resid f32 (same layout as out_f32) is added; f32_act 0 none / 2 tanh; transposed != 0 stores out_f32 as [Cout][rows]; out_bf16
+ * [rows][Cout] receives act(v) with bf16_act 0 none / 1 LeakyReLU(slope). Either output may be NULL, not both.
+ * ltx_op_conv1d: Conv1d with "same" padding (Vocoder.swift:34-51): x [L][Cin], w [Cout][k][Cin] (tap-major), odd k <= 16. */
+int ltx_op_conv1d(ltx_ctx* ctx, const uint16_t* x, int L, int Cin, const uint16_t* w, const float* bias, int Cout, int k, int dilation,
+                  int tile, const float* resid, int f32_act, int transposed, float* out_f32, int bf16_act, float slope,
+                  uint16_t* out_bf16);
+/* ConvTransposed1d (Vocoder.swift:81-102) as `stride` phase launches: x [L][Cin], w in the PyTorch layout [Cin][Cout][k],
+ * padding == (k - stride) / 2 -> out [stride * L][Cout]. */
+int ltx_op_conv_transpose1d(ltx_ctx* ctx, const uint16_t* x, int L, int Cin, const uint16_t* w, const float* bias, int Cout, int k,
+                            int stride, int padding, int tile, float* out_f32, int bf16_act, float slope, uint16_t* out_bf16);
+/* AudioCausalConv2d (AudioVAE.swift:37-104), ksize 3 or 1: x [H][W][Cin], w [Cout][ksize*ksize][Cin] (tap = kh*ksize + kw); output row
+ * h sees input rows h-2 .. h only -> out [H][W][Cout]. */
+int ltx_op_conv2d_causal(ltx_ctx* ctx, const uint16_t* x, int H, int W, int Cin, const uint16_t* w, const float* bias, int Cout, int ksize,
+                         int tile, const float* resid, int transposed, float* out_f32, uint16_t* out_bf16);
 /* deterministic device fills used by bench.py to create synthetic inputs */
 int ltx_op_fill_normal_bf16(ltx_ctx* ctx, uint16_t* p, long n, uint64_t seed, float mean, float stddev);
 int ltx_op_fill_normal_f32(ltx_ctx* ctx, float* p, long n, uint64_t seed, float mean, float stddev);

@@ -212,6 +212,30 @@ def write_png(path, rgb):
     _check(lib.ltx_write_png(str(path).encode(), a.ctypes.data, w, h))
 
 
+def audio_latent_frames(video_frames, fps=24.0):
+    """``computeAudioLatentFrames`` (LTXPipeline.swift:530-534)."""
+    return lib.ltx_audio_latent_frames(int(video_frames), float(fps))
+
+
+def audio_mel_frames(T):
+    return lib.ltx_audio_mel_frames(int(T))
+
+
+def audio_sample_count(T):
+    return lib.ltx_audio_sample_count(int(T))
+
+
+def audio_sample_rate():
+    return lib.ltx_audio_sample_rate()
+
+
+def write_wav(path, waveform, sample_rate=None, gain=1.0):
+    """``AudioExporter.exportToWAV``: waveform (2, n) f32 -> 16-bit stereo PCM file."""
+    a = np.ascontiguousarray(waveform, dtype=np.float32)
+    assert a.ndim == 2 and a.shape[0] == 2
+    _check(lib.ltx_write_wav(str(path).encode(), a.ctypes.data, a.shape[1], int(sample_rate or audio_sample_rate()), float(gain)))
+
+
 def map_vae_encoder_key(key):
     """``mapVAEEncoderWeights`` (ModelDownloader.swift:1222-1283); None for non-encoder tensors."""
     return _map_key(lib.ltx_map_vae_encoder_key, key)
@@ -529,6 +553,78 @@ class Context:
     def vae_encode_dev(self, pixels, latent, normalize=False):
         _, _, T, H, W = pixels.shape
         self._ck(lib.ltx_vae_encode_dev(self._h, _ptr(pixels), T, H, W, int(normalize), _ptr(latent)))
+
+    # ---- audio decode leg (audio VAE decoder + vocoder) ----
+    def audio_vae_load(self, path):
+        self._ck(lib.ltx_audio_vae_load(self._h, str(path).encode()))
+
+    def audio_vae_init_synthetic(self, base_channels=0, seed=55):
+        self._ck(lib.ltx_audio_vae_init_synthetic(self._h, base_channels, seed))
+
+    def audio_vae_unload(self):
+        self._ck(lib.ltx_audio_vae_unload(self._h))
+
+    def vocoder_load(self, path):
+        self._ck(lib.ltx_vocoder_load(self._h, str(path).encode()))
+
+    def vocoder_init_synthetic(self, hidden_channels=0, seed=56):
+        self._ck(lib.ltx_vocoder_init_synthetic(self._h, hidden_channels, seed))
+
+    def vocoder_unload(self):
+        self._ck(lib.ltx_vocoder_unload(self._h))
+
+    def audio_vae_decode(self, latent):
+        """``AudioVAE.decode``: latent (8, T, 16) f32 -> mel (2, max(4T-3, 1), 64) f32 (host arrays)."""
+        lat = np.ascontiguousarray(latent, dtype=np.float32)
+        assert lat.shape[0] == 8 and lat.shape[2] == 16
+        T = lat.shape[1]
+        mel = np.empty((2, audio_mel_frames(T), 64), dtype=np.float32)
+        self._ck(lib.ltx_audio_vae_decode(self._h, _ptr(lat), T, _ptr(mel)))
+        return mel
+
+    def audio_vae_decode_dev(self, latent, mel):
+        self._ck(lib.ltx_audio_vae_decode_dev(self._h, _ptr(latent), latent.shape[1], _ptr(mel)))
+
+    def vocoder_forward(self, mel):
+        """``LTX2Vocoder``: mel (2, T, 64) f32 -> waveform (2, 240 T) f32 (host arrays)."""
+        m = np.ascontiguousarray(mel, dtype=np.float32)
+        assert m.shape[0] == 2 and m.shape[2] == 64
+        wave = np.empty((2, 240 * m.shape[1]), dtype=np.float32)
+        self._ck(lib.ltx_vocoder_forward(self._h, _ptr(m), m.shape[1], _ptr(wave)))
+        return wave
+
+    def vocoder_forward_dev(self, mel, waveform):
+        self._ck(lib.ltx_vocoder_forward_dev(self._h, _ptr(mel), mel.shape[1], _ptr(waveform)))
+
+    def audio_decode(self, latent):
+        """``decodeAudio``: latent (8, T, 16) f32 -> waveform (2, audio_sample_count(T)) f32 (host arrays)."""
+        lat = np.ascontiguousarray(latent, dtype=np.float32)
+        assert lat.shape[0] == 8 and lat.shape[2] == 16
+        wave = np.empty((2, audio_sample_count(lat.shape[1])), dtype=np.float32)
+        self._ck(lib.ltx_audio_decode(self._h, _ptr(lat), lat.shape[1], _ptr(wave)))
+        return wave
+
+    def audio_decode_dev(self, latent, waveform):
+        self._ck(lib.ltx_audio_decode_dev(self._h, _ptr(latent), latent.shape[1], _ptr(waveform)))
+
+    def op_conv1d(self, x, w, bias, dilation=1, tile=-1, resid=None, f32_act=0, transposed=False, out_f32=None, bf16_act=0, slope=0.1,
+                  out_bf16=None):
+        L, Cin = x.shape
+        Cout, k, _ = w.shape
+        self._ck(lib.ltx_op_conv1d(self._h, _ptr(x), L, Cin, _ptr(w), _ptr(bias), Cout, k, dilation, tile, _ptr(resid), f32_act,
+                                   int(transposed), _ptr(out_f32), bf16_act, slope, _ptr(out_bf16)))
+
+    def op_conv_transpose1d(self, x, w, bias, stride, padding, tile=-1, out_f32=None, bf16_act=0, slope=0.1, out_bf16=None):
+        L, Cin = x.shape
+        _, Cout, k = w.shape
+        self._ck(lib.ltx_op_conv_transpose1d(self._h, _ptr(x), L, Cin, _ptr(w), _ptr(bias), Cout, k, stride, padding, tile, _ptr(out_f32),
+                                             bf16_act, slope, _ptr(out_bf16)))
+
+    def op_conv2d_causal(self, x, w, bias, ksize=3, tile=-1, resid=None, transposed=False, out_f32=None, out_bf16=None):
+        H, W, Cin = x.shape
+        Cout = w.shape[0]
+        self._ck(lib.ltx_op_conv2d_causal(self._h, _ptr(x), H, W, Cin, _ptr(w), _ptr(bias), Cout, ksize, tile, _ptr(resid),
+                                          int(transposed), _ptr(out_f32), _ptr(out_bf16)))
 
     # ---- text-embedding connector (SURVEY 8(f) item 1) ----
     def connector_load(self, path, cfg=None):

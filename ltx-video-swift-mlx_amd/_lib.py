@@ -178,6 +178,26 @@ SIGNATURES = {
     "ltx_op_norm_mod_ex": (_i, [_vp, _vp, _l, _vp, _vp, _l, _i, _vp, _i, _i, _i, _f, _i, _vp, _l]),
     "ltx_op_qknorm_rope_pair": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _l, _l, _vp, _vp, _i, _i, _i, _f, _f, _i]),
     "ltx_conv_takes_d2s_pn": (_i, [_i, _i, _i, _i]),
+    "ltx_audio_vae_load": (_i, [_vp, C.c_char_p]),
+    "ltx_audio_vae_init_synthetic": (_i, [_vp, _i, _u64]),
+    "ltx_audio_vae_unload": (_i, [_vp]),
+    "ltx_vocoder_load": (_i, [_vp, C.c_char_p]),
+    "ltx_vocoder_init_synthetic": (_i, [_vp, _i, _u64]),
+    "ltx_vocoder_unload": (_i, [_vp]),
+    "ltx_audio_vae_decode": (_i, [_vp, _vp, _i, _vp]),
+    "ltx_audio_vae_decode_dev": (_i, [_vp, _vp, _i, _vp]),
+    "ltx_vocoder_forward": (_i, [_vp, _vp, _i, _vp]),
+    "ltx_vocoder_forward_dev": (_i, [_vp, _vp, _i, _vp]),
+    "ltx_audio_decode": (_i, [_vp, _vp, _i, _vp]),
+    "ltx_audio_decode_dev": (_i, [_vp, _vp, _i, _vp]),
+    "ltx_audio_latent_frames": (_i, [_i, _f]),
+    "ltx_audio_mel_frames": (_i, [_i]),
+    "ltx_audio_sample_count": (_l, [_i]),
+    "ltx_audio_sample_rate": (_i, []),
+    "ltx_write_wav": (_i, [C.c_char_p, _vp, _l, _i, _f]),
+    "ltx_op_conv1d": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _vp, _i, _f, _vp]),
+    "ltx_op_conv_transpose1d": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _f, _vp]),
+    "ltx_op_conv2d_causal": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp]),
     "ltx_op_fill_normal_bf16": (_i, [_vp, _vp, _l, _u64, _f, _f]),
     "ltx_op_fill_normal_f32": (_i, [_vp, _vp, _l, _u64, _f, _f]),
 }

@@ -4,6 +4,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <functional>
 #include <vector>
 
 #include "../../include/ltxhip.h"
@@ -18,6 +19,7 @@
 #include "upscaler.h"
 #include "vae.h"
 #include "vae_encoder.h"
+#include "audio.h"
 #include "runtime.h"
 #include "linear_ops.h"
 
@@ -178,6 +180,8 @@ void ltx_ctx_destroy(ltx_ctx* ctx) {
     if (ctx->upscaler) upscaler_destroy(ctx->upscaler);
     if (ctx->connector) connector_destroy(ctx->connector);
     if (ctx->vae_encoder) vae_encoder_destroy(ctx->vae_encoder);
+    audio_vae_destroy(ctx->audio_vae);
+    vocoder_destroy(ctx->vocoder);
     if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
 }
@@ -1448,6 +1452,308 @@ int ltx_frames_to_u8(const float* frames, long n, uint8_t* out) {
 
 int ltx_write_png(const char* path, const uint8_t* rgb, int width, int height) {
     return write_png_rgb8(path, rgb, width, height) ? LTX_OK : LTX_ERR_FILE_NOT_FOUND;
+}
+
+/* ---- audio decode leg (audio.h) ---- */
+namespace {
+void drop_audio_vae(ltx_ctx* ctx) {
+    if (ctx->audio_vae) {
+        HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        audio_vae_destroy(ctx->audio_vae);
+        ctx->audio_vae = nullptr;
+    }
+}
+void drop_vocoder(ltx_ctx* ctx) {
+    if (ctx->vocoder) {
+        HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        vocoder_destroy(ctx->vocoder);
+        ctx->vocoder = nullptr;
+    }
+}
+AudioVaeModel* need_audio_vae(ltx_ctx* ctx) {
+    if (!ctx->audio_vae) LTX_THROW(LTXS_MODEL_NOT_LOADED, "Model not loaded: audio VAE not loaded");
+    return ctx->audio_vae;
+}
+VocoderModel* need_vocoder(ltx_ctx* ctx) {
+    if (!ctx->vocoder) LTX_THROW(LTXS_MODEL_NOT_LOADED, "Model not loaded: vocoder not loaded");
+    return ctx->vocoder;
+}
+void audio_decode_common(ltx_ctx* ctx, const float* latent_dev, int T, float* wave_dev) {
+    AudioVaeModel* v = need_audio_vae(ctx);
+    VocoderModel* g = need_vocoder(ctx);
+    LTX_REQUIRE(latent_dev && wave_dev && T >= 1, "ltx_audio_decode: bad arguments");
+    const int Tm = audio_mel_frames(T);
+    ctx->audio_mel.ensure((size_t)2 * Tm * 64 * 4);
+    audio_vae_decode(ctx, v, latent_dev, T, ctx->audio_mel.as<float>());
+    vocoder_forward(ctx, g, ctx->audio_mel.as<float>(), Tm, wave_dev);
+}
+// host-pointer wrapper: stage in, run, stage out, synchronise
+void audio_staged(ltx_ctx* ctx, const float* in, size_t n_in, float* out, size_t n_out,
+                  const std::function<void(const float*, float*)>& run) {
+    LTX_REQUIRE(in && out, "audio: null host pointer");
+    ctx->h2d[0].ensure(n_in * 4);
+    ctx->h2d[1].ensure(n_out * 4);
+    HIP_CHECK(hipMemcpyAsync(ctx->h2d[0].p, in, n_in * 4, hipMemcpyHostToDevice, ctx->stream));
+    run(ctx->h2d[0].as<float>(), ctx->h2d[1].as<float>());
+    HIP_CHECK(hipMemcpyAsync(out, ctx->h2d[1].p, n_out * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_CHECK(hipStreamSynchronize(ctx->stream));
+}
+}  // namespace
+
+int ltx_audio_vae_load(ltx_ctx* ctx, const char* path) {
+    if (!ctx || !path) return LTX_ERR_INVALID_CONFIGURATION;
+    return guarded(ctx, [&] {
+        drop_audio_vae(ctx);
+        AudioVaeModel* m = audio_vae_create();
+        try {
+            audio_vae_load(ctx, m, path);
+        } catch (...) {
+            audio_vae_destroy(m);
+            throw;
+        }
+        ctx->audio_vae = m;
+    });
+}
+int ltx_audio_vae_init_synthetic(ltx_ctx* ctx, int base_channels, uint64_t seed) {
+    if (!ctx) return LTX_ERR_INVALID_CONFIGURATION;
+    return guarded(ctx, [&] {
+        drop_audio_vae(ctx);
+        AudioVaeModel* m = audio_vae_create();
+        try {
+            audio_vae_init_synthetic(ctx, m, base_channels > 0 ? base_channels : 128, seed);
+        } catch (...) {
+            audio_vae_destroy(m);
+            throw;
+        }
+        ctx->audio_vae = m;
+    });
+}
+int ltx_audio_vae_unload(ltx_ctx* ctx) {
+    if (!ctx) return LTX_ERR_INVALID_CONFIGURATION;
+    return guarded(ctx, [&] { drop_audio_vae(ctx); });
+}
+int ltx_vocoder_load(ltx_ctx* ctx, const char* path) {
+    if (!ctx || !path) return LTX_ERR_INVALID_CONFIGURATION;
+    return guarded(ctx, [&] {
+        drop_vocoder(ctx);
+        VocoderModel* m = vocoder_create();
+        try {
+            vocoder_load(ctx, m, path);
+        } catch (...) {
+            vocoder_destroy(m);
+            throw;
+        }
+        ctx->vocoder = m;
+    });
+}
+int ltx_vocoder_init_synthetic(ltx_ctx* ctx, int hidden_channels, uint64_t seed) {
+    if (!ctx) return LTX_ERR_INVALID_CONFIGURATION;
+    return guarded(ctx, [&] {
+        drop_vocoder(ctx);
+        VocoderModel* m = vocoder_create();
+        try {
+            vocoder_init_synthetic(ctx, m, hidden_channels > 0 ? hidden_channels : 1024, seed);
+        } catch (...) {
+            vocoder_destroy(m);
+            throw;
+        }
+        ctx->vocoder = m;
+    });
+}
+int ltx_vocoder_unload(ltx_ctx* ctx) {
+    if (!ctx) return LTX_ERR_INVALID_CONFIGURATION;
+    return guarded(ctx, [&] { drop_vocoder(ctx); });
+}
+
+int ltx_audio_vae_decode_dev(ltx_ctx* ctx, const float* latent, int T, float* mel) {
+    if (!ctx) return LTX_ERR_INVALID_CONFIGURATION;
+    return guarded(ctx, [&] { audio_vae_decode(ctx, need_audio_vae(ctx), latent, T, mel); });
+}
+int ltx_audio_vae_decode(ltx_ctx* ctx, const float* latent, int T, float* mel) {
+    if (!ctx) return LTX_ERR_INVALID_CONFIGURATION;
+    return guarded(ctx, [&] {
+        AudioVaeModel* m = need_audio_vae(ctx);
+        LTX_REQUIRE(T >= 1 && T <= 4096, "ltx_audio_vae_decode: T=%d", T);
+        audio_staged(ctx, latent, (size_t)8 * T * 16, mel, (size_t)2 * audio_mel_frames(T) * 64,
+                     [&](const float* i, float* o) { audio_vae_decode(ctx, m, i, T, o); });
+    });
+}
+int ltx_vocoder_forward_dev(ltx_ctx* ctx, const float* mel, int T_mel, float* waveform) {
+    if (!ctx) return LTX_ERR_INVALID_CONFIGURATION;
+    return guarded(ctx, [&] { vocoder_forward(ctx, need_vocoder(ctx), mel, T_mel, waveform); });
+}
+int ltx_vocoder_forward(ltx_ctx* ctx, const float* mel, int T_mel, float* waveform) {
+    if (!ctx) return LTX_ERR_INVALID_CONFIGURATION;
+    return guarded(ctx, [&] {
+        VocoderModel* m = need_vocoder(ctx);
+        LTX_REQUIRE(T_mel >= 1 && T_mel <= 16384, "ltx_vocoder_forward: T_mel=%d", T_mel);
+        audio_staged(ctx, mel, (size_t)2 * T_mel * 64, waveform, (size_t)2 * 240 * T_mel,
+                     [&](const float* i, float* o) { vocoder_forward(ctx, m, i, T_mel, o); });
+    });
+}
+int ltx_audio_decode_dev(ltx_ctx* ctx, const float* latent, int T, float* waveform) {
+    if (!ctx) return LTX_ERR_INVALID_CONFIGURATION;
+    return guarded(ctx, [&] { audio_decode_common(ctx, latent, T, waveform); });
+}
+int ltx_audio_decode(ltx_ctx* ctx, const float* latent, int T, float* waveform) {
+    if (!ctx) return LTX_ERR_INVALID_CONFIGURATION;
+    return guarded(ctx, [&] {
+        need_audio_vae(ctx);
+        need_vocoder(ctx);
+        LTX_REQUIRE(T >= 1 && T <= 4096, "ltx_audio_decode: T=%d", T);
+        audio_staged(ctx, latent, (size_t)8 * T * 16, waveform, (size_t)2 * 240 * audio_mel_frames(T),
+                     [&](const float* i, float* o) { audio_decode_common(ctx, i, T, o); });
+    });
+}
+
+int ltx_audio_latent_frames(int video_frames, float fps) { return video_frames < 1 || !(fps > 0) ? 0 : audio_latent_frames(video_frames, fps); }
+int ltx_audio_mel_frames(int T) { return T < 1 ? 0 : audio_mel_frames(T); }
+long ltx_audio_sample_count(int T) { return T < 1 ? 0 : 240L * audio_mel_frames(T); }
+int ltx_audio_sample_rate(void) { return 24000; }
+int ltx_write_wav(const char* path, const float* waveform, long n, int sample_rate, float gain) {
+    if (!path || !waveform || n < 0 || sample_rate < 1 || n > (1L << 28)) return LTX_ERR_INVALID_CONFIGURATION;
+    return write_wav_pcm16(path, waveform, n, sample_rate, gain) ? LTX_OK : LTX_ERR_FILE_NOT_FOUND;
+}
+
+/* ---- audio conv test hooks ---- */
+namespace {
+void audio_op_epilogue(AConvArgs& a, const float* resid, int f32_act, int transposed, float* out_f32, long rows_out, int bf16_act,
+                       float slope, uint16_t* out_bf16) {
+    a.resid = resid;
+    a.out_f32 = out_f32;
+    a.f32_act = f32_act;
+    a.f32_transposed = transposed ? 1 : 0;
+    a.ldo = transposed ? rows_out : a.Cout;
+    a.out_bf16 = out_bf16;
+    a.ldb = a.Cout;
+    a.bf16_act = bf16_act;
+    a.slope = slope;
+}
+}  // namespace
+
+int ltx_op_conv1d(ltx_ctx* ctx, const uint16_t* x, int L, int Cin, const uint16_t* w, const float* bias, int Cout, int k, int dilation,
+                  int tile, const float* resid, int f32_act, int transposed, float* out_f32, int bf16_act, float slope,
+                  uint16_t* out_bf16) {
+    if (!ctx) return LTX_ERR_INVALID_CONFIGURATION;
+    return guarded(ctx, [&] {
+        LTX_REQUIRE(x && w && L >= 1 && L <= (1 << 24) && Cin >= 1 && Cin <= 4096 && Cout >= 1 && Cout <= 4096, "ltx_op_conv1d: bad shape");
+        LTX_REQUIRE(k >= 1 && k <= ACONV_MAX_TAPS && k % 2 == 1 && dilation >= 1 && (k - 1) / 2 * dilation <= ACONV_HALO,
+                    "ltx_op_conv1d: k=%d dilation=%d (odd k <= %d, reach <= %d rows)", k, dilation, (int)ACONV_MAX_TAPS, (int)ACONV_HALO);
+        LTX_REQUIRE(Cin % 32 == 0, "ltx_op_conv1d: Cin=%d must be a multiple of 32", Cin);
+        const size_t row = (size_t)Cin * 2;
+        ctx->audio_op[0].ensure((size_t)(L + 2 * ACONV_HALO) * row);
+        char* base = ctx->audio_op[0].as<char>();
+        HIP_CHECK(hipMemsetAsync(base, 0, ACONV_HALO * row, ctx->stream));
+        HIP_CHECK(hipMemsetAsync(base + (size_t)(ACONV_HALO + L) * row, 0, ACONV_HALO * row, ctx->stream));
+        HIP_CHECK(hipMemcpyAsync(base + ACONV_HALO * row, x, (size_t)L * row, hipMemcpyDeviceToDevice, ctx->stream));
+        AConvArgs a;
+        a.x = (const bf16_t*)(base + ACONV_HALO * row);
+        a.ldx = Cin;
+        a.w = w;
+        a.bias = bias;
+        a.P = L;
+        a.Cin = Cin;
+        a.Cout = Cout;
+        a.ntaps = k;
+        for (int j = 0; j < k; ++j) a.off[j] = (j - (k - 1) / 2) * dilation;
+        audio_op_epilogue(a, resid, f32_act, transposed, out_f32, L, bf16_act, slope, out_bf16);
+        launch_audio_conv(a, tile, ctx->stream);
+    });
+}
+
+int ltx_op_conv_transpose1d(ltx_ctx* ctx, const uint16_t* x, int L, int Cin, const uint16_t* w, const float* bias, int Cout, int k,
+                            int stride, int padding, int tile, float* out_f32, int bf16_act, float slope, uint16_t* out_bf16) {
+    if (!ctx) return LTX_ERR_INVALID_CONFIGURATION;
+    return guarded(ctx, [&] {
+        LTX_REQUIRE(x && w && L >= 1 && L <= (1 << 22) && Cin >= 1 && Cin <= 4096 && Cout >= 1 && Cout <= 4096, "ltx_op_conv_transpose1d: bad shape");
+        LTX_REQUIRE(Cin % 32 == 0, "ltx_op_conv_transpose1d: Cin=%d must be a multiple of 32", Cin);
+        LTX_REQUIRE(stride >= 1 && stride <= 8 && k >= stride && k <= 64 && (k - stride) % 2 == 0 && padding == (k - stride) / 2,
+                    "ltx_op_conv_transpose1d: k=%d stride=%d padding=%d (padding must be (k - stride) / 2: output length stride * L)", k,
+                    stride, padding);
+        const size_t row = (size_t)Cin * 2;
+        ctx->audio_op[0].ensure((size_t)(L + 2 * ACONV_HALO) * row);
+        char* base = ctx->audio_op[0].as<char>();
+        HIP_CHECK(hipMemsetAsync(base, 0, ACONV_HALO * row, ctx->stream));
+        HIP_CHECK(hipMemsetAsync(base + (size_t)(ACONV_HALO + L) * row, 0, ACONV_HALO * row, ctx->stream));
+        HIP_CHECK(hipMemcpyAsync(base + ACONV_HALO * row, x, (size_t)L * row, hipMemcpyDeviceToDevice, ctx->stream));
+        // the phase slabs are built on the host exactly as the vocoder loader builds them (test hook: one round trip)
+        std::vector<bf16_t> wh((size_t)Cin * Cout * k);
+        HIP_CHECK(hipMemcpyAsync(wh.data(), w, wh.size() * 2, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        std::vector<bf16_t> slabs;
+        std::vector<std::vector<int>> offs((size_t)stride);
+        std::vector<size_t> at((size_t)stride);
+        for (int r = 0; r < stride; ++r) {
+            const std::vector<int> js = convt_phase_taps(k, stride, padding, r, &offs[r]);
+            LTX_REQUIRE(!js.empty() && (int)js.size() <= ACONV_MAX_TAPS, "ltx_op_conv_transpose1d: phase %d has %zu taps", r, js.size());
+            for (int o : offs[r]) LTX_REQUIRE(o >= -ACONV_HALO && o <= ACONV_HALO, "ltx_op_conv_transpose1d: offset %d beyond the halo", o);
+            at[r] = slabs.size();
+            slabs.resize(slabs.size() + (size_t)Cout * js.size() * Cin);
+            bf16_t* s = slabs.data() + at[r];
+            for (int o = 0; o < Cout; ++o)
+                for (size_t t = 0; t < js.size(); ++t)
+                    for (int c = 0; c < Cin; ++c) s[((size_t)o * js.size() + t) * Cin + c] = wh[((size_t)c * Cout + o) * k + js[t]];
+        }
+        ctx->audio_op[1].ensure(slabs.size() * 2);
+        HIP_CHECK(hipMemcpyAsync(ctx->audio_op[1].p, slabs.data(), slabs.size() * 2, hipMemcpyHostToDevice, ctx->stream));
+        HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        for (int r = 0; r < stride; ++r) {
+            AConvArgs a;
+            a.x = (const bf16_t*)(base + ACONV_HALO * row);
+            a.ldx = Cin;
+            a.w = ctx->audio_op[1].as<bf16_t>() + at[r];
+            a.bias = bias;
+            a.P = L;
+            a.Cin = Cin;
+            a.Cout = Cout;
+            a.ntaps = (int)offs[r].size();
+            for (int t = 0; t < a.ntaps; ++t) a.off[t] = offs[r][t];
+            a.omul = stride;
+            a.oadd = r;
+            audio_op_epilogue(a, nullptr, AACT_NONE, 0, out_f32, (long)L * stride, bf16_act, slope, out_bf16);
+            launch_audio_conv(a, tile, ctx->stream);
+        }
+    });
+}
+
+int ltx_op_conv2d_causal(ltx_ctx* ctx, const uint16_t* x, int H, int W, int Cin, const uint16_t* w, const float* bias, int Cout, int ksize,
+                         int tile, const float* resid, int transposed, float* out_f32, uint16_t* out_bf16) {
+    if (!ctx) return LTX_ERR_INVALID_CONFIGURATION;
+    return guarded(ctx, [&] {
+        LTX_REQUIRE(x && w && H >= 1 && H <= 65536 && W >= 1 && W <= 4096 && Cin >= 1 && Cin <= 4096 && Cout >= 1 && Cout <= 4096,
+                    "ltx_op_conv2d_causal: bad shape");
+        LTX_REQUIRE(ksize == 1 || ksize == 3, "ltx_op_conv2d_causal: kernel %d (1 or 3)", ksize);
+        LTX_REQUIRE(Cin % 32 == 0, "ltx_op_conv2d_causal: Cin=%d must be a multiple of 32", Cin);
+        const int wp = W + 2;
+        const size_t row = (size_t)Cin * 2;
+        const size_t bytes = (size_t)(H + 3) * wp * row;
+        ctx->audio_op[0].ensure(bytes);
+        char* base = ctx->audio_op[0].as<char>();
+        HIP_CHECK(hipMemsetAsync(base, 0, bytes, ctx->stream));
+        HIP_CHECK(hipMemcpy2DAsync(base + ((size_t)2 * wp + 1) * row, wp * row, x, W * row, W * row, H, hipMemcpyDeviceToDevice, ctx->stream));
+        AConvArgs a;
+        a.x = (const bf16_t*)base;
+        a.ldx = Cin;
+        a.w = w;
+        a.bias = bias;
+        a.P = H * wp;
+        a.Cin = Cin;
+        a.Cout = Cout;
+        if (ksize == 3) {
+            a.ntaps = 9;
+            for (int kh = 0; kh < 3; ++kh)
+                for (int kw = 0; kw < 3; ++kw) a.off[kh * 3 + kw] = kh * wp + kw;
+        } else {
+            a.ntaps = 1;
+            a.off[0] = 2 * wp + 1;
+        }
+        a.wp = wp;
+        a.wv = W;
+        a.opitch = W;
+        a.bpitch = W;
+        audio_op_epilogue(a, resid, AACT_NONE, transposed, out_f32, (long)H * W, AACT_NONE, 0.f, out_bf16);
+        launch_audio_conv(a, tile, ctx->stream);
+    });
 }
 
 }  // extern "C"

@@ -87,6 +87,8 @@ struct VaeModel;
 struct ConnectorModel;
 struct VaeEncoderModel;
 struct UpscalerModel;
+struct AudioVaeModel;
+struct VocoderModel;
 struct DistState;
 
 // ---- live per-kernel timing (HIP events recorded on the launch stream around each launch of a kernel family) ----
@@ -135,6 +137,9 @@ struct ltx_ctx {
     ConnectorModel* connector = nullptr;
     VaeEncoderModel* vae_encoder = nullptr;
     DistState* dist = nullptr;  // multi-GPU state (dist.h); null = single GPU
+    AudioVaeModel* audio_vae = nullptr;  // audio decode leg (audio.h)
+    VocoderModel* vocoder = nullptr;
+    DevBuf audio_mel, audio_op[2];  // the mel between the two audio models; haloed operands of the audio conv test hooks
     // staging buffers for host-pointer entry points
     DevBuf h2d[8];
     // load report of the last *_load call (mirrors the reference's "unmatched/missing" debug logs)

@@ -212,6 +212,26 @@ class LTXPipeline {
         return n;
     }
     void loadUpscaler(const std::string& path) { check(ltx_upscaler_load(ctx_, path.c_str())); }
+    // loadAudioModels / decodeAudio (LTXPipeline.swift audio branch; Vocoder.swift:325-361): the audio VAE decoder + vocoder. The dual
+    // (video + audio) transformer is not part of this build, so the audio latent [8][T][16] is an input. Empty paths with
+    // synthetic = true give random-init models of the reference architecture (smoke runs without weight files).
+    void loadAudioModels(const std::string& audioVAEPath, const std::string& vocoderPath, bool synthetic = false) {
+        if (synthetic && audioVAEPath.empty()) check(ltx_audio_vae_init_synthetic(ctx_, 0, 55));
+        else check(ltx_audio_vae_load(ctx_, audioVAEPath.c_str()));
+        if (synthetic && vocoderPath.empty()) check(ltx_vocoder_init_synthetic(ctx_, 0, 56));
+        else check(ltx_vocoder_load(ctx_, vocoderPath.c_str()));
+    }
+    void unloadAudioModels() {
+        check(ltx_audio_vae_unload(ctx_));
+        check(ltx_vocoder_unload(ctx_));
+    }
+    // -> waveform [2][ltx_audio_sample_count(T)] f32 at ltx_audio_sample_rate() Hz
+    std::vector<float> decodeAudio(const std::vector<float>& latents, int T) {
+        if (T < 1 || latents.size() != size_t(8) * T * 16) throw LTXError(LTXError::invalidConfiguration, "audio latent must be [8][T][16]");
+        std::vector<float> wave(size_t(2) * ltx_audio_sample_count(T));
+        check(ltx_audio_decode(ctx_, latents.data(), T, wave.data()));
+        return wave;
+    }
     // loadVAEEncoder / encodeImage (LTXPipeline.swift:1871-1932) without the image file I/O: pixels [1][3][1][H][W] f32 in [-1,1]
     // -> ImageConditioning whose latent is already normalised with the decoder's statistics (loadModels first).
     void loadVAEEncoder(const std::string& vaeWeightsPath) { check(ltx_vae_encoder_load(ctx_, vaeWeightsPath.c_str(), 0)); }

@@ -54,6 +54,9 @@ struct Args {
                  "  [--embeddings file] [--vae-weights file] [--upscaler-weights file] [--distilled-lora-path file]\n"
                  "  [--vae-tile N] [--vae-overlap N] [--png-dir dir] [--gemma-hidden-states file] [--connector-weights file]\n"
                  "  [--image-tensor file] [--noise-rng native|mlx] [--hip-option name=value]...\n"
+                 "decode-audio  Audio latent -> 24 kHz stereo WAV (audio VAE decoder + vocoder)\n"
+                 "  (--latent file.safetensors [key audio_latent, (8,T,16)] | --synthetic [--frames 121]) [--audio-vae-weights file]\n"
+                 "  [--vocoder-weights file] [--audio-gain 1.0] [-o out.wav]\n"
                  "options     List the library's launcher switches (name, default, range, numerics flag) for --hip-option\n";
     std::exit(code);
 }
@@ -397,6 +400,59 @@ int run_bench(int argc, char** argv) {
     return 0;
 }
 
+// decode-audio: the decode leg of generateVideoWithAudio (Vocoder.swift:325-361 + AudioExporter.swift:19-92) on a given audio latent.
+int run_decode_audio(int argc, char** argv) {
+    std::string latentPath, vaePath, vocPath, output = "output.wav";
+    bool synthetic = false;
+    int frames = 121;
+    float gain = 1.f;
+    auto need = [&](int& i) -> std::string {
+        if (i + 1 >= argc) throw ValidationError(std::string("Missing value for '") + argv[i] + "'");
+        return argv[++i];
+    };
+    for (int i = 2; i < argc; ++i) {
+        const std::string k = argv[i];
+        if (k == "--latent") latentPath = need(i);
+        else if (k == "--synthetic") synthetic = true;
+        else if (k == "--audio-vae-weights") vaePath = need(i);
+        else if (k == "--vocoder-weights") vocPath = need(i);
+        else if (k == "--audio-gain") gain = std::stof(need(i));
+        else if (k == "-f" || k == "--frames") frames = std::stoi(need(i));
+        else if (k == "-o" || k == "--output") output = need(i);
+        else throw ValidationError("Unknown option '" + k + "'");
+    }
+    if (latentPath.empty() && !synthetic) throw ValidationError("decode-audio needs --latent <file.safetensors> or --synthetic");
+    if (!synthetic && (vaePath.empty() || vocPath.empty()))
+        throw ValidationError("decode-audio needs --audio-vae-weights and --vocoder-weights (or --synthetic)");
+    int T = 0;
+    std::vector<float> latent;
+    if (!latentPath.empty()) {
+        long shape[8] = {0};
+        const int nd = ltx_st_info(latentPath.c_str(), "audio_latent", shape);
+        const int o = nd == 4 ? 1 : 0;  // (1, 8, T, 16) or (8, T, 16)
+        if ((nd != 3 && nd != 4) || shape[o] != 8 || shape[o + 2] != 16 || shape[o + 1] < 1)
+            throw ValidationError("--latent: tensor 'audio_latent' of shape (8, T, 16) expected");
+        T = (int)shape[o + 1];
+        latent.resize(size_t(8) * T * 16);
+        if (ltx_st_read(latentPath.c_str(), "audio_latent", 0, latent.data(), (long)latent.size()) != (long)latent.size())
+            throw ValidationError("--latent: cannot read 'audio_latent'");
+    } else {
+        if (frames < 1) throw ValidationError("--frames must be positive");
+        T = ltx_audio_latent_frames(frames, 24.0f);
+        latent.resize(size_t(8) * T * 16);
+        if (ltx_mlx_random_normal(42, 0, latent.data(), (long)latent.size()) != 0) throw ValidationError("noise generation failed");
+    }
+    LTXPipeline pipeline;
+    pipeline.loadAudioModels(vaePath, vocPath, synthetic);
+    const std::vector<float> wave = pipeline.decodeAudio(latent, T);
+    const long n = ltx_audio_sample_count(T);
+    if (ltx_write_wav(output.c_str(), wave.data(), n, ltx_audio_sample_rate(), gain) != 0)
+        throw LTXError(LTXError::fileNotFound, "cannot write " + output);
+    std::cout << "Audio: " << T << " latent frames -> " << ltx_audio_mel_frames(T) << " mel frames -> " << n << " samples/channel at "
+              << ltx_audio_sample_rate() << " Hz -> " << output << "\n";
+    return 0;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -427,6 +483,7 @@ int main(int argc, char** argv) {
         if (sub == "download") throw ValidationError("download is not available: this path has no network access");
         if (sub == "generate") return run_generate(parse_generate(argc, argv, 2));
         if (sub == "bench") return run_bench(argc, argv);
+        if (sub == "decode-audio") return run_decode_audio(argc, argv);
         throw ValidationError("Unknown subcommand '" + sub + "'");
     } catch (const ValidationError& e) {
         std::cerr << "Error: " << e.what() << "\n";

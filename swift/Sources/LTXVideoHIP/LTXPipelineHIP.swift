@@ -121,6 +121,19 @@ public final class LTXPipelineHIP {
         return lat
     }
 
+    /// Audio VAE decoder + vocoder (loadAudioVAEWeights / loadVocoderWeights, ModelDownloader.swift:1116-1194).
+    public func loadAudioModels(audioVAE: String, vocoder: String) throws {
+        try check(ltx_audio_vae_load(ctx, audioVAE))
+        try check(ltx_vocoder_load(ctx, vocoder))
+    }
+
+    /// decodeAudio (Vocoder.swift:325-361): audio latent [8][T][16] -> stereo waveform [2][ltx_audio_sample_count(T)] at 24 kHz.
+    public func decodeAudio(latents: [Float], frames: Int) throws -> [Float] {
+        var wave = [Float](repeating: 0, count: 2 * Int(ltx_audio_sample_count(Int32(frames))))
+        try check(ltx_audio_decode(ctx, latents, Int32(frames), &wave))
+        return wave
+    }
+
     /// The denoise loop + decode of generateVideo / generateVideoFromImage (LTXPipeline.swift:586-1046, 1953-2125).
     /// `noise` is the initial N(0,1) latent [1][128][F'][H'][W'] (draw it with MLXRandom so `seed` keeps its meaning);
     /// `imageLatent` (+ optional per-step `injectionNoise`) switches on image-to-video conditioning.
