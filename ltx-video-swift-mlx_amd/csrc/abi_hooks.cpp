@@ -1,0 +1,399 @@
+// abi_hooks.cpp - extern "C" surface of libltxhip.so (include/ltxhip.h), part 3 of 3: what tests, tools and the bench use to reach
+// below the models - the ltx_op_* kernel hooks, the ltx_prof_* timers, the device fills and the parameter export. No product code
+// path goes through this file.
+#include <vector>
+
+#include "abi_internal.h"
+#include "attention.h"
+#include "audio.h"
+#include "elementwise.h"
+#include "gemm.h"
+#include "linear_ops.h"
+
+namespace {
+
+// the context-owned workspace that the hooks lend a launcher, as the model graphs lend theirs
+void op_workspace(ltx_ctx* ctx, size_t bytes) {
+    if (ctx->op_ws.ensure(bytes)) HIP_CHECK(hipStreamSynchronize(ctx->stream));
+}
+
+// Zero-haloed, channels-last operand of the audio conv hooks, built in ctx->audio_op[0]: `lines` lines of `width` rows (Cin bf16
+// each) of x land at row first + l * pitch of a buffer of `total` rows, every other row is zero. Returns row 0 of the buffer.
+const bf16_t* audio_halo_operand(ltx_ctx* ctx, const uint16_t* x, int Cin, int lines, int width, int pitch, size_t first, size_t total) {
+    const size_t row = (size_t)Cin * 2;
+    ctx->audio_op[0].ensure(total * row);
+    char* base = ctx->audio_op[0].as<char>();
+    if (pitch == width) {  // one contiguous signal: only the two halos need zeroing
+        HIP_CHECK(hipMemsetAsync(base, 0, first * row, ctx->stream));
+        const size_t end = first + (size_t)lines * width;
+        HIP_CHECK(hipMemsetAsync(base + end * row, 0, (total - end) * row, ctx->stream));
+        HIP_CHECK(hipMemcpyAsync(base + first * row, x, (size_t)lines * width * row, hipMemcpyDeviceToDevice, ctx->stream));
+    } else {
+        HIP_CHECK(hipMemsetAsync(base, 0, total * row, ctx->stream));
+        HIP_CHECK(hipMemcpy2DAsync(base + first * row, pitch * row, x, width * row, width * row, lines, hipMemcpyDeviceToDevice, ctx->stream));
+    }
+    return (const bf16_t*)base;
+}
+
+void audio_op_epilogue(AConvArgs& a, const float* resid, int f32_act, int transposed, float* out_f32, long rows_out, int bf16_act,
+                       float slope, uint16_t* out_bf16) {
+    a.resid = resid;
+    a.out_f32 = out_f32;
+    a.f32_act = f32_act;
+    a.f32_transposed = transposed ? 1 : 0;
+    a.ldo = transposed ? rows_out : a.Cout;
+    a.out_bf16 = out_bf16;
+    a.ldb = a.Cout;
+    a.bf16_act = bf16_act;
+    a.slope = slope;
+}
+
+}  // namespace
+
+extern "C" {
+
+long ltx_dit_export_param(ltx_ctx* ctx, const char* module_key, float* out, long cap) {
+    if (!ctx || !module_key) return -LTX_ERR_INVALID_CONFIGURATION;
+    long n = 0;
+    const int rc = guarded(ctx, [&] {
+        DiTModel* m = need(ctx->dit, kNoDit);
+        auto it = m->slots.find(module_key);
+        LTX_REQUIRE(it != m->slots.end(), "ltx_dit_export_param: no parameter '%s'", module_key);
+        const ParamSlot& sl = it->second;
+        n = sl.numel;
+        if (!out) return;
+        LTX_REQUIRE(cap >= n, "ltx_dit_export_param: buffer too small (%ld < %ld)", cap, n);
+        HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        dit_export_slot(ctx, m, sl, out);
+    });
+    return rc == 0 ? n : -rc;
+}
+
+int ltx_prof_enable(ltx_ctx* ctx, int on) {
+    return with_ctx(ctx, [&] {
+        HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        ctx->prof.collect();
+        ctx->prof.on = on != 0;
+    });
+}
+
+int ltx_prof_collect(ltx_ctx* ctx, int kind, double* total_ms, long* launches, double* work, int reset) {
+    if (!ctx || kind < 0 || kind >= PROF_NKINDS) return LTX_ERR_INVALID_CONFIGURATION;
+    return guarded(ctx, [&] {
+        HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        ctx->prof.collect();
+        if (total_ms) *total_ms = ctx->prof.total_ms[kind];
+        if (launches) *launches = ctx->prof.launches[kind];
+        if (work) *work = ctx->prof.total_work[kind];
+        if (reset) ctx->prof.reset();
+    });
+}
+
+int ltx_op_fill_normal_bf16(ltx_ctx* ctx, uint16_t* p, long n, uint64_t seed, float mean, float stddev) {
+    return with_ctx(ctx, [&] { launch_fill_normal_bf16(p, n, seed, mean, stddev, ctx->stream); });
+}
+int ltx_op_fill_normal_f32(ltx_ctx* ctx, float* p, long n, uint64_t seed, float mean, float stddev) {
+    return with_ctx(ctx, [&] { launch_fill_normal_f32(p, n, seed, mean, stddev, 0, ctx->stream); });
+}
+
+// ---- GEMM ----
+int ltx_op_gemm_bf16(ltx_ctx* ctx, const uint16_t* A, long lda, const uint16_t* B, long ldb, const float* bias, int M,
+                     int N, int K, int act, int tile_cfg, float* out_f32, long ld_f32, uint16_t* out_bf16,
+                     long ld_bf16) {
+    return with_ctx(ctx, [&] {
+        GemmArgs g;
+        g.A = A; g.lda = lda; g.B = B; g.ldb = ldb; g.M = M; g.N = N; g.K = K;
+        g.ep.bias_n = bias;
+        g.ep.act = act;
+        g.ep.out_f32 = out_f32; g.ep.ld_f32 = ld_f32;
+        g.ep.out_bf16 = out_bf16; g.ep.ld_bf16 = ld_bf16;
+        if (tile_cfg >= 100) {  // S*100 + cfg: S-way split-K on a ring tile (workspace owned by the context)
+            g.split_k = tile_cfg / 100;
+            tile_cfg %= 100;
+            op_workspace(ctx, (size_t)g.split_k * M * N * 4);
+            g.split_ws = ctx->op_ws.as<float>();
+            g.split_ws_elems = (long)(ctx->op_ws.bytes / 4);
+        }
+        if (tile_cfg < 0) launch_gemm_bf16(g, ctx->stream); else launch_gemm_bf16_cfg(g, tile_cfg, ctx->stream);
+    });
+}
+
+int ltx_op_gemm_q8(ltx_ctx* ctx, const uint16_t* A, long lda, const uint8_t* codes, const uint16_t* scales, const uint16_t* biases,
+                   const float* bias, int M, int N, int K, int split_k, int via_scratch, int tile_cfg, float* out_f32, long ld_f32) {
+    return with_ctx(ctx, [&] {
+        LTX_REQUIRE(A && codes && scales && biases && out_f32 && split_k >= 1, "ltx_op_gemm_q8: null argument");
+        LTX_REQUIRE(gemm_takes_codes(M, N, K), "ltx_op_gemm_q8: few-row launches only (M <= 256, K %% 64 == 0, K >= 256, N %% 4 == 0; M=%d N=%d K=%d)", M, N, K);
+        GemmArgs g;
+        g.A = A; g.lda = lda; g.ldb = K; g.M = M; g.N = N; g.K = K;
+        g.ep.bias_n = bias;
+        g.ep.out_f32 = out_f32; g.ep.ld_f32 = ld_f32;
+        DevBuf scratch;
+        if (via_scratch) {  // the path every other launch of a quantised Linear takes: codes -> bf16 scratch matrix -> the same kernel
+            scratch.ensure((size_t)N * K * 2);
+            launch_dequant(codes, scales, biases, N, K, 8, scratch.as<bf16_t>(), ctx->stream);
+            g.B = scratch.as<bf16_t>();
+        } else {
+            g.Bq = codes; g.Bqs = scales; g.Bqb = biases;
+        }
+        if (split_k > 1) {
+            g.split_k = split_k;
+            op_workspace(ctx, (size_t)split_k * M * N * 4);
+            g.split_ws = ctx->op_ws.as<float>();
+        }
+        LTX_REQUIRE(tile_cfg == 29 || (tile_cfg == 30 && gemm_fewrow_takes(M, N, K, split_k)), "ltx_op_gemm_q8: tile_cfg 29 (ring kernel) or 30 (few-row kernel: M <= 128, N %% 64 == 0, whole 256-wide macro-tiles of K per split)");
+        launch_gemm_bf16_cfg(g, tile_cfg, ctx->stream);
+        if (via_scratch) HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    });
+}
+
+int ltx_op_value_projection_t(ltx_ctx* ctx, const uint16_t* X, long ldx, int tokens, const uint16_t* W, const float* bias, int out_features,
+                              int in_features, uint16_t* vt, long ldvt) {
+    return with_ctx(ctx, [&] {
+        LinearW w;
+        w.w = (bf16_t*)W;
+        w.b = (float*)bias;
+        w.out = out_features;
+        w.in = in_features;
+        gemm_vt(X, ldx, tokens, w, vt, ldvt, ctx->stream);
+    });
+}
+
+int ltx_op_gemm_bf16_gated_residual(ltx_ctx* ctx, const uint16_t* A, long lda, const uint16_t* B, long ldb,
+                                    const float* bias, const float* gate, float gate_scalar, int M, int N, int K,
+                                    float* x, long ldx, uint16_t* mirror, long ld_mirror) {
+    return with_ctx(ctx, [&] {
+        GemmArgs g;
+        g.A = A; g.lda = lda; g.B = B; g.ldb = ldb; g.M = M; g.N = N; g.K = K;
+        g.ep.bias_n = bias;
+        g.ep.out_f32 = x; g.ep.ld_f32 = ldx;
+        g.ep.resid = 1;
+        g.ep.gate = gate; g.ep.gate_bstride = 0; g.ep.rows_per_batch = M; g.ep.gate_scalar = gate_scalar;
+        g.ep.out_bf16 = mirror; g.ep.ld_bf16 = ld_mirror;
+        launch_gemm_bf16(g, ctx->stream);
+    });
+}
+
+int ltx_op_gemm_bf16_gated_residual_norm(ltx_ctx* ctx, const uint16_t* A, long lda, const uint16_t* B, long ldb,
+                                         const float* bias, const float* gate, float gate_scalar, int M, int N, int K,
+                                         float* x, long ldx, const float* scale, const float* shift, float eps,
+                                         uint16_t* xn, long ldxn, int fused) {
+    return with_ctx(ctx, [&] {
+        LTX_REQUIRE(A && B && x && scale && shift && xn, "ltx_op_gemm_bf16_gated_residual_norm: null argument");
+        GemmArgs g;
+        g.A = A; g.lda = lda; g.B = B; g.ldb = ldb; g.M = M; g.N = N; g.K = K;
+        g.ep.bias_n = bias;
+        g.ep.out_f32 = x; g.ep.ld_f32 = ldx;
+        g.ep.resid = 1;
+        g.ep.gate = gate; g.ep.gate_bstride = 0; g.ep.rows_per_batch = M; g.ep.gate_scalar = gate_scalar;
+        // the DiT graph's launches bring a workspace and leave the split to the launcher
+        op_workspace(ctx, (size_t)2 * M * N * 4);
+        g.split_k = 0;
+        g.split_ws = ctx->op_ws.as<float>();
+        g.split_ws_elems = (long)(ctx->op_ws.bytes / 4);
+        NormAfter na;
+        na.scale = scale; na.shift = shift; na.mod_bstride = 0; na.rows_per_batch = M;
+        na.out = xn; na.ldo = ldxn; na.eps = eps; na.norm_kind = LTX_NORM_RMS;
+        if (fused) {
+            launch_gemm_bf16(g, ctx->stream, &na);
+        } else {
+            launch_gemm_bf16(g, ctx->stream);
+            launch_norm_mod(x, ldx, scale, shift, 0, M, xn, ldxn, M, N, LTX_NORM_RMS, eps, 0, ctx->stream);
+        }
+    });
+}
+
+int ltx_op_gemv_f32(ltx_ctx* ctx, const float* a, long lda, const uint16_t* W, long ldw, const float* bias, float* out,
+                    long ldo, int M, int N, int K, int in_act) {
+    return with_ctx(ctx, [&] { launch_gemv_f32(a, lda, W, ldw, bias, out, ldo, M, N, K, in_act, ctx->stream); });
+}
+
+int ltx_op_conv3d(ltx_ctx* ctx, const uint16_t* x, int F, int H, int W, int Cin, const uint16_t* w, const float* bias,
+                  int Cout, int causal, float* out) {
+    return with_ctx(ctx, [&] {
+        GemmArgs g;
+        g.A = x; g.B = w; g.ldb = 27L * Cin;
+        g.M = F * H * W; g.N = Cout; g.K = 27 * Cin;
+        g.conv = 1;
+        g.geom.F = F; g.geom.H = H; g.geom.W = W; g.geom.C = Cin; g.geom.causal = causal; g.geom.pad_mode = 0;
+        g.ep.bias_n = bias;
+        g.ep.out_f32 = out; g.ep.ld_f32 = Cout;
+        // a workspace, as the VAE graph passes one: the launcher may run a last partial round of tiles as a split-K launch
+        op_workspace(ctx, (size_t)64 << 20);
+        g.split_ws = ctx->op_ws.as<float>();
+        g.split_ws_elems = (long)(ctx->op_ws.bytes / 4);
+        launch_gemm_bf16(g, ctx->stream);
+    });
+}
+
+int ltx_conv_takes_d2s_pn(int F, int H, int W, int C) {
+    GemmArgs g;  // an upsampler conv C -> 4C of the VAE decoder at (F, H, W), as vae.cpp forms it
+    g.ldb = 27L * C; g.M = (int)((long)F * H * W); g.N = 4 * C; g.K = 27 * C;
+    g.conv = 1;
+    g.geom.F = F; g.geom.H = H; g.geom.W = W; g.geom.C = C;
+    g.ep.d2s = 1;
+    return (long)F * H * W <= 0x7fffffffL && gemm_conv_takes_d2s_pn(g) ? 1 : 0;
+}
+
+// ---- attention and row kernels ----
+int ltx_op_attention(ltx_ctx* ctx, const uint16_t* Q, const uint16_t* K, const uint16_t* Vt, long ldvt,
+                     const float* bias, int B, int H, int Tq, int Tk, float scale, uint16_t* O) {
+    return with_ctx(ctx, [&] {
+        AttnArgs a;
+        const long D = (long)H * 128;
+        a.Q = Q; a.ldq = D; a.q_bstride = (long)Tq * D;
+        a.K = K; a.ldk = D; a.k_bstride = (long)Tk * D;
+        a.Vt = Vt; a.ldvt = ldvt; a.vt_bstride = D * ldvt;
+        a.O = O; a.ldo = D; a.o_bstride = (long)Tq * D;
+        a.bias = bias; a.bias_bstride = Tk;
+        a.B = B; a.H = H; a.Tq = Tq; a.Tk = Tk; a.scale = scale;
+        a.q_prescaled = scale <= 0.f ? 1 : 0;  // Q already carries scale * log2(e): scores are base-2 exponents
+        // few queries against many keys: lend the launcher room to divide the keys over workgroups, as the DiT forward does
+        if (const long need_bytes = attn_split_ws_bytes(B, H, Tq, Tk)) {
+            op_workspace(ctx, (size_t)need_bytes);
+            a.split_ws = ctx->op_ws.p;
+            a.split_ws_bytes = (long)ctx->op_ws.bytes;
+        }
+        launch_attention(a, ctx->stream);
+    });
+}
+
+int ltx_attention_key_splits(int B, int H, int Tq, int Tk) {
+    if (B < 1 || H < 1 || Tq < 1 || Tk < 1) return 1;
+    return attn_key_splits(B, H, Tq, Tk);
+}
+
+int ltx_op_norm_mod(ltx_ctx* ctx, const float* x, const float* scale, const float* shift, int rows, int D,
+                    int norm_kind, float eps, int round_norm_bf16, uint16_t* out) {
+    return with_ctx(ctx, [&] {
+        launch_norm_mod(x, D, scale, shift, 0, rows, out, D, rows, D, norm_kind, eps, round_norm_bf16, ctx->stream);
+    });
+}
+
+int ltx_op_qknorm_rope(ltx_ctx* ctx, const float* x, long ldx, const float* w, const float* cos_t, const float* sin_t,
+                       int T, int rows, int D, float eps, uint16_t* out) {
+    return with_ctx(ctx, [&] { launch_qknorm_rope(x, ldx, w, cos_t, sin_t, T, out, D, rows, D, eps, ctx->stream); });
+}
+
+int ltx_op_norm_mod_ex(ltx_ctx* ctx, const float* x, long ldx, const float* scale, const float* shift, long mod_bstride,
+                       int rows_per_batch, const int32_t* row_map, int rows, int D, int norm_kind, float eps,
+                       int round_norm_bf16, uint16_t* out, long ldo) {
+    return with_ctx(ctx, [&] {
+        launch_norm_mod(x, ldx, scale, shift, mod_bstride, rows_per_batch, out, ldo, rows, D, norm_kind, eps, round_norm_bf16, ctx->stream, row_map);
+    });
+}
+
+int ltx_op_qknorm_rope_pair(ltx_ctx* ctx, const void* x0, const float* w0, uint16_t* out0, const void* x1, const float* w1,
+                            uint16_t* out1, long ldx, long ldo, const float* cos_t, const float* sin_t, int T, int rows, int D,
+                            float eps, float out_scale0, int x_bf16) {
+    return with_ctx(ctx, [&] {
+        launch_qknorm_rope2((const float*)x0, w0, out0, (const float*)x1, w1, out1, ldx, ldo, cos_t, sin_t, T, rows, D, eps, ctx->stream,
+                            out_scale0, x_bf16 != 0);
+    });
+}
+
+// ---- audio convolutions ----
+int ltx_op_conv1d(ltx_ctx* ctx, const uint16_t* x, int L, int Cin, const uint16_t* w, const float* bias, int Cout, int k, int dilation,
+                  int tile, const float* resid, int f32_act, int transposed, float* out_f32, int bf16_act, float slope,
+                  uint16_t* out_bf16) {
+    return with_ctx(ctx, [&] {
+        LTX_REQUIRE(x && w && L >= 1 && L <= (1 << 24) && Cin >= 1 && Cin <= 4096 && Cout >= 1 && Cout <= 4096, "ltx_op_conv1d: bad shape");
+        LTX_REQUIRE(k >= 1 && k <= ACONV_MAX_TAPS && k % 2 == 1 && dilation >= 1 && (k - 1) / 2 * dilation <= ACONV_HALO,
+                    "ltx_op_conv1d: k=%d dilation=%d (odd k <= %d, reach <= %d rows)", k, dilation, (int)ACONV_MAX_TAPS, (int)ACONV_HALO);
+        LTX_REQUIRE(Cin % 32 == 0, "ltx_op_conv1d: Cin=%d must be a multiple of 32", Cin);
+        AConvArgs a;
+        a.x = audio_halo_operand(ctx, x, Cin, 1, L, L, ACONV_HALO, (size_t)L + 2 * ACONV_HALO) + (size_t)ACONV_HALO * Cin;
+        a.ldx = Cin;
+        a.w = w;
+        a.bias = bias;
+        a.P = L;
+        a.Cin = Cin;
+        a.Cout = Cout;
+        a.ntaps = k;
+        for (int j = 0; j < k; ++j) a.off[j] = (j - (k - 1) / 2) * dilation;
+        audio_op_epilogue(a, resid, f32_act, transposed, out_f32, L, bf16_act, slope, out_bf16);
+        launch_audio_conv(a, tile, ctx->stream);
+    });
+}
+
+int ltx_op_conv_transpose1d(ltx_ctx* ctx, const uint16_t* x, int L, int Cin, const uint16_t* w, const float* bias, int Cout, int k,
+                            int stride, int padding, int tile, float* out_f32, int bf16_act, float slope, uint16_t* out_bf16) {
+    return with_ctx(ctx, [&] {
+        LTX_REQUIRE(x && w && L >= 1 && L <= (1 << 22) && Cin >= 1 && Cin <= 4096 && Cout >= 1 && Cout <= 4096, "ltx_op_conv_transpose1d: bad shape");
+        LTX_REQUIRE(Cin % 32 == 0, "ltx_op_conv_transpose1d: Cin=%d must be a multiple of 32", Cin);
+        LTX_REQUIRE(stride >= 1 && stride <= 8 && k >= stride && k <= 64 && (k - stride) % 2 == 0 && padding == (k - stride) / 2,
+                    "ltx_op_conv_transpose1d: k=%d stride=%d padding=%d (padding must be (k - stride) / 2: output length stride * L)", k,
+                    stride, padding);
+        const bf16_t* x0 = audio_halo_operand(ctx, x, Cin, 1, L, L, ACONV_HALO, (size_t)L + 2 * ACONV_HALO) + (size_t)ACONV_HALO * Cin;
+        // the phase slabs come from the vocoder loader's own builder, convt_phase_slab (test hook: one round trip through the host)
+        std::vector<bf16_t> wh((size_t)Cin * Cout * k);
+        HIP_CHECK(hipMemcpyAsync(wh.data(), w, wh.size() * 2, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        std::vector<float> wf(wh.size());
+        for (size_t i = 0; i < wh.size(); ++i) wf[i] = host_bf16_to_f32(wh[i]);
+        std::vector<bf16_t> slabs;
+        std::vector<std::vector<int>> offs((size_t)stride);
+        std::vector<size_t> at((size_t)stride);
+        for (int r = 0; r < stride; ++r) {
+            const std::vector<int> js = convt_phase_taps(k, stride, padding, r, &offs[r]);
+            LTX_REQUIRE(!js.empty() && (int)js.size() <= ACONV_MAX_TAPS, "ltx_op_conv_transpose1d: phase %d has %zu taps", r, js.size());
+            for (int o : offs[r]) LTX_REQUIRE(o >= -ACONV_HALO && o <= ACONV_HALO, "ltx_op_conv_transpose1d: offset %d beyond the halo", o);
+            at[r] = slabs.size();
+            for (float v : convt_phase_slab(wf.data(), Cin, Cout, k, js, Cin)) slabs.push_back(host_f32_to_bf16(v));  // exact: v is a bf16 value
+        }
+        ctx->audio_op[1].ensure(slabs.size() * 2);
+        HIP_CHECK(hipMemcpyAsync(ctx->audio_op[1].p, slabs.data(), slabs.size() * 2, hipMemcpyHostToDevice, ctx->stream));
+        HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        for (int r = 0; r < stride; ++r) {
+            AConvArgs a;
+            a.x = x0;
+            a.ldx = Cin;
+            a.w = ctx->audio_op[1].as<bf16_t>() + at[r];
+            a.bias = bias;
+            a.P = L;
+            a.Cin = Cin;
+            a.Cout = Cout;
+            a.ntaps = (int)offs[r].size();
+            for (int t = 0; t < a.ntaps; ++t) a.off[t] = offs[r][t];
+            a.omul = stride;
+            a.oadd = r;
+            audio_op_epilogue(a, nullptr, AACT_NONE, 0, out_f32, (long)L * stride, bf16_act, slope, out_bf16);
+            launch_audio_conv(a, tile, ctx->stream);
+        }
+    });
+}
+
+int ltx_op_conv2d_causal(ltx_ctx* ctx, const uint16_t* x, int H, int W, int Cin, const uint16_t* w, const float* bias, int Cout, int ksize,
+                         int tile, const float* resid, int transposed, float* out_f32, uint16_t* out_bf16) {
+    return with_ctx(ctx, [&] {
+        LTX_REQUIRE(x && w && H >= 1 && H <= 65536 && W >= 1 && W <= 4096 && Cin >= 1 && Cin <= 4096 && Cout >= 1 && Cout <= 4096,
+                    "ltx_op_conv2d_causal: bad shape");
+        LTX_REQUIRE(ksize == 1 || ksize == 3, "ltx_op_conv2d_causal: kernel %d (1 or 3)", ksize);
+        LTX_REQUIRE(Cin % 32 == 0, "ltx_op_conv2d_causal: Cin=%d must be a multiple of 32", Cin);
+        const int wp = W + 2;
+        AConvArgs a;
+        // the padded [(H+3)][W+2][Cin] operand of audio.h: image row h at padded row h+2, column w at w+1
+        a.x = audio_halo_operand(ctx, x, Cin, H, W, wp, (size_t)2 * wp + 1, (size_t)(H + 3) * wp);
+        a.ldx = Cin;
+        a.w = w;
+        a.bias = bias;
+        a.P = H * wp;
+        a.Cin = Cin;
+        a.Cout = Cout;
+        if (ksize == 3) {
+            a.ntaps = 9;
+            for (int kh = 0; kh < 3; ++kh)
+                for (int kw = 0; kw < 3; ++kw) a.off[kh * 3 + kw] = kh * wp + kw;
+        } else {
+            a.ntaps = 1;
+            a.off[0] = 2 * wp + 1;
+        }
+        a.wp = wp;
+        a.wv = W;
+        a.opitch = W;
+        a.bpitch = W;
+        audio_op_epilogue(a, resid, AACT_NONE, transposed, out_f32, (long)H * W, AACT_NONE, 0.f, out_bf16);
+        launch_audio_conv(a, tile, ctx->stream);
+    });
+}
+
+}  // extern "C"

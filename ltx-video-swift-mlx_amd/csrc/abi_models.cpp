@@ -1,0 +1,789 @@
+// abi_models.cpp - extern "C" surface of libltxhip.so (include/ltxhip.h), part 2 of 3: the model entry points. Per component:
+// *_load / *_init_synthetic / *_unload over one model slot of the context (abi_internal.h: replace_model / unload_model / need),
+// then the *_dev entry point on device pointers and its host-pointer twin, which stages through stage_in / stage_out around the same
+// body. Also the denoise loop and the multi-GPU group.
+#include <algorithm>
+#include <vector>
+
+#include "abi_internal.h"
+#include "audio.h"
+#include "connector.h"
+#include "dist.h"
+#include "elementwise.h"
+#include "pipeline.h"
+#include "upscaler.h"
+#include "vae.h"
+#include "vae_encoder.h"
+
+namespace {
+
+// FNV-1a over 8-byte words: cheap change detector for host-pointer context buffers
+uint64_t hash_bytes(const void* p, size_t n, uint64_t h) {
+    const uint8_t* b = (const uint8_t*)p;
+    size_t i = 0;
+    for (; i + 8 <= n; i += 8) {
+        uint64_t w;
+        memcpy(&w, b + i, 8);
+        h = (h ^ w) * 0x100000001B3ull;
+        h ^= h >> 29;
+    }
+    for (; i < n; ++i) h = (h ^ b[i]) * 0x100000001B3ull;
+    return h ? h : 1;
+}
+
+// What a host-pointer entry point knows about its text context: `version` names the bytes of context (+ mask) for the DiT's context
+// cache (never 0, which means "do not cache"), `all_ones` says that no key is masked. A null `context` asks for the mask scan alone
+// and gives version 0.
+struct ContextSignature {
+    uint64_t version = 0;
+    int all_ones = 1;
+};
+ContextSignature context_signature(const void* context, size_t context_bytes, const int32_t* mask, long mask_elems) {
+    ContextSignature s;
+    if (context) s.version = hash_bytes(context, context_bytes, 0xCBF29CE484222325ull);
+    if (mask) {
+        if (context) s.version = hash_bytes(mask, (size_t)mask_elems * 4, s.version);
+        for (long i = 0; i < mask_elems; ++i)
+            if (mask[i] != 1) { s.all_ones = 0; break; }
+    }
+    return s;
+}
+
+DiTForwardArgs dit_args(const uint16_t* latent, const uint16_t* context, const float* timesteps, const int32_t* mask, int mask_all_ones,
+                        int B, int F, int H, int W, int S, uint64_t ctx_version, float* velocity) {
+    DiTForwardArgs a;
+    a.latent = latent;
+    a.context = context;
+    a.timesteps = timesteps;
+    a.mask = mask;
+    a.mask_all_ones = mask_all_ones;
+    a.B = B; a.F = F; a.H = H; a.W = W; a.S = S;
+    a.ctx_version = ctx_version;
+    a.velocity = velocity;
+    return a;
+}
+
+VaeDecodeArgs vae_args(const float* latent, int F, int H, int W, int has_timestep, float timestep, const float* noise, int tile,
+                       int overlap, float* frames, long frames_cap, int* n_frames_out) {
+    VaeDecodeArgs a;
+    a.latent = latent; a.F = F; a.H = H; a.W = W;
+    a.has_timestep = has_timestep; a.timestep = timestep; a.noise = noise;
+    a.tile = tile; a.overlap = overlap;
+    a.frames = frames; a.frames_cap = frames_cap; a.n_frames_out = n_frames_out;
+    return a;
+}
+
+ConnectorConfig to_conn_cfg(const ltx_connector_config* c) {
+    ConnectorConfig k;
+    if (c) {
+        k.dim = c->dim; k.heads = c->heads; k.layers = c->layers; k.registers = c->registers; k.states = c->states;
+        k.theta = c->theta; k.max_pos = c->max_pos;
+    }
+    return k;
+}
+
+// ---- bodies shared by a *_dev entry point and its host-pointer twin (all pointers are device pointers) ----
+void upscale_body(ltx_ctx* ctx, const float* latent, int F, int H, int W, float* out) {
+    UpscalerModel* u = need(ctx->upscaler, kNoUpscaler);
+    VaeModel* v = need(ctx->vae, kNoVae);  // per-channel statistics come from the VAE (LTXPipeline.swift:2598-2599)
+    upscaler_forward(ctx, u, latent, F, H, W, v->mean, v->std_, out);
+}
+
+void adain_body(ltx_ctx* ctx, float* latent, long n, const float* reference, long n_ref, int channels, float factor) {
+    ctx->dn_stats.ensure((size_t)channels * 4 * 4 + 64);
+    float* sx = ctx->dn_stats.as<float>();
+    float* sr = sx + 2 * channels;
+    launch_mean_var(latent, n, channels, sx, ctx->stream);
+    launch_mean_var(reference, n_ref, channels, sr, ctx->stream);
+    launch_adain(latent, sx, sr, factor, n, channels, ctx->stream);
+}
+
+void encode_body(ltx_ctx* ctx, const float* pixels, int T, int H, int W, int normalize, float* latent) {
+    VaeEncoderModel* m = need(ctx->vae_encoder, kNoVaeEncoder);
+    const float* mean = nullptr;
+    const float* stdv = nullptr;
+    if (normalize) {
+        const VaeModel* v = need(ctx->vae, kNoVaeStats);
+        mean = v->mean;
+        stdv = v->std_;
+    }
+    vae_encoder_encode(ctx, m, pixels, T, H, W, mean, stdv, latent, nullptr);
+}
+
+void audio_decode_body(ltx_ctx* ctx, const float* latent, int T, float* wave) {
+    AudioVaeModel* v = need(ctx->audio_vae, kNoAudioVae);
+    VocoderModel* g = need(ctx->vocoder, kNoVocoder);
+    LTX_REQUIRE(latent && wave && T >= 1, "ltx_audio_decode: bad arguments");
+    const int Tm = audio_mel_frames(T);
+    ctx->audio_mel.ensure((size_t)2 * Tm * 64 * 4);
+    audio_vae_decode(ctx, v, latent, T, ctx->audio_mel.as<float>());
+    vocoder_forward(ctx, g, ctx->audio_mel.as<float>(), Tm, wave);
+}
+
+// host-pointer side of the three audio entry points: one f32 input, one f32 output, through H2D_IN / H2D_OUT
+const float* audio_stage_in(ltx_ctx* ctx, const float* in, size_t n_in, float* out, size_t n_out) {
+    LTX_REQUIRE(in && out, "audio: null host pointer");
+    ctx->h2d[H2D_IN].ensure(n_in * 4);
+    ctx->h2d[H2D_OUT].ensure(n_out * 4);
+    stage_in(ctx, ctx->h2d[H2D_IN], in, n_in * 4);
+    return ctx->h2d[H2D_IN].as<float>();
+}
+void audio_stage_out(ltx_ctx* ctx, float* out, size_t n_out) {
+    stage_out(ctx, out, ctx->h2d[H2D_OUT], n_out * 4);
+    stage_sync(ctx);
+}
+
+void fill_params(DenoiseParams& p, const ltx_denoise_options* o) {
+    if (!o) return;
+    // ABI revision 2: the caller declares how much of the struct it knows; nothing past that is read (round-4 advice: a host compiled
+    // against the older, shorter struct must not have `step_stats` read past its end)
+    const size_t sz = o->struct_size;
+    LTX_REQUIRE(sz >= offsetof(ltx_denoise_options, shard) + sizeof(o->shard) && sz <= 4096,
+                "ltx_denoise_options.struct_size = %zu: set it to sizeof(ltx_denoise_options) (LTX_DENOISE_OPTIONS_INIT); this library is ABI revision %d",
+                sz, LTX_ABI_VERSION);
+    p.cfg_scale = o->cfg_scale;
+    p.guidance_rescale = o->guidance_rescale;
+    p.stg_scale = o->stg_scale;
+    p.stg_blocks = o->stg_blocks;
+    p.n_stg = o->n_stg_blocks;
+    p.ge_gamma = o->ge_gamma;
+    p.cond_latent = o->cond_latent;  // device variant: used as given; host variant: replaced by staged copies below
+    p.image_cond_noise_scale = o->image_cond_noise_scale;
+    p.cond_noise = o->cond_noise;
+    p.shard = o->shard;
+    if (sz >= offsetof(ltx_denoise_options, step_stats) + sizeof(o->step_stats)) p.step_stats = o->step_stats;
+}
+
+}  // namespace
+
+extern "C" {
+
+// ---- DiT ----
+int ltx_dit_load(ltx_ctx* ctx, const char* path, const ltx_transformer_config* cfg, int quant_bits, int group_size) {
+    if (!ctx || !path) return LTX_ERR_INVALID_CONFIGURATION;
+    return guarded(ctx, [&] {
+        LTX_REQUIRE(quant_bits == 16 || quant_bits == 0 || quant_bits == 8 || quant_bits == 4,
+                    "transformer quantization must be bf16 (16), qint8 (8) or int4 (4); got %d bits", quant_bits);
+        LTX_REQUIRE(quant_bits == 16 || quant_bits == 0 || group_size == 64, "quantization group size must be 64, got %d", group_size);
+        replace_model(ctx, &ctx->dit, [&] { return dit_create(to_cfg(cfg)); },
+                      [&](DiTModel* m) {
+                          dit_load_safetensors(ctx, m, path);
+                          if (quant_bits == 8 || quant_bits == 4) dit_quantize(ctx, m, quant_bits, 64);
+                      },
+                      dit_destroy);
+    });
+}
+
+int ltx_dit_init_synthetic(ltx_ctx* ctx, const ltx_transformer_config* cfg, uint64_t seed) {
+    return with_ctx(ctx, [&] {
+        replace_model(ctx, &ctx->dit, [&] { return dit_create(to_cfg(cfg)); }, [&](DiTModel* m) { dit_init_synthetic(ctx, m, seed); },
+                      dit_destroy);
+    });
+}
+
+int ltx_dit_quantize(ltx_ctx* ctx, int bits, int group_size) {
+    return with_ctx(ctx, [&] { dit_quantize(ctx, need(ctx->dit, kNoDit), bits, group_size); });
+}
+
+int ltx_dit_memory_info(ltx_ctx* ctx, long* bf16_weight_bytes, long* quantised_weight_bytes, long* scratch_bytes, long* other_bytes) {
+    return with_ctx(ctx, [&] {
+        DiTModel* m = need(ctx->dit, kNoDit);
+        if (bf16_weight_bytes) *bf16_weight_bytes = m->warena.buf.p ? (long)m->warena.buf.bytes : 0;
+        if (quantised_weight_bytes) *quantised_weight_bytes = m->qarena.buf.p ? (long)m->qarena.buf.bytes : 0;
+        if (scratch_bytes) *scratch_bytes = m->dq.buf.p ? (long)m->dq.buf.bytes : 0;
+        if (other_bytes) *other_bytes = m->arena.buf.p ? (long)m->arena.buf.bytes : 0;
+    });
+}
+
+int ltx_dit_fuse_lora(ltx_ctx* ctx, const char* path, float scale, int* n_fused) {
+    if (!ctx || !path) return LTX_ERR_INVALID_CONFIGURATION;
+    return guarded(ctx, [&] {
+        const int n = dit_fuse_lora(ctx, need(ctx->dit, kNoDitLora), path, scale);
+        if (n_fused) *n_fused = n;
+    });
+}
+
+int ltx_dit_unload(ltx_ctx* ctx) {
+    return with_ctx(ctx, [&] { unload_model(ctx, &ctx->dit, dit_destroy); });
+}
+
+int ltx_dit_forward_dev(ltx_ctx* ctx, const uint16_t* latent, const uint16_t* context, const float* timesteps,
+                        const int32_t* mask, int mask_all_ones, int B, int F, int H, int W, int S,
+                        uint64_t ctx_version, float* velocity) {
+    return with_ctx(ctx, [&] {
+        DiTModel* m = need(ctx->dit, kNoDit);
+        dit_forward(ctx, m, dit_args(latent, context, timesteps, mask, mask_all_ones, B, F, H, W, S, ctx_version, velocity));
+    });
+}
+
+int ltx_dit_forward_sp_dev(ltx_ctx* ctx, const uint16_t* latent, const uint16_t* context, const float* timesteps,
+                           const int32_t* mask, int mask_all_ones, int F, int H, int W, int S, uint64_t ctx_version,
+                           int sp_rank, int sp_world, ltx_allgather_fn gather, void* user, float* velocity) {
+    return with_ctx(ctx, [&] {
+        DiTModel* m = need(ctx->dit, kNoDit);
+        LTX_REQUIRE(sp_world >= 1 && (sp_world == 1 || gather || ctx->dist), "ltx_dit_forward_sp_dev: %d ranks need a gather callback or ltx_dist_init", sp_world);
+        DiTForwardArgs a = dit_args(latent, context, timesteps, mask, mask_all_ones, 1, F, H, W, S, ctx_version, velocity);
+        a.sp_rank = sp_rank;
+        a.sp_world = sp_world;
+        a.sp_gather = gather;
+        a.sp_user = user;
+        dit_forward(ctx, m, a);
+    });
+}
+
+int ltx_dit_forward(ltx_ctx* ctx, const uint16_t* latent, const uint16_t* context, const float* timesteps,
+                    const int32_t* mask, int B, int F, int H, int W, int S, float* velocity) {
+    return with_ctx(ctx, [&] {
+        DiTModel* m = need(ctx->dit, kNoDit);
+        LTX_REQUIRE(latent && context && timesteps && velocity && B >= 1 && F >= 1 && H >= 1 && W >= 1 && S >= 1, "ltx_dit_forward: bad arguments");
+        const long T = (long)F * H * W;
+        const size_t n_lat = (size_t)B * T * m->cfg.in_channels * 2;
+        const size_t n_ctx = (size_t)B * S * m->cfg.caption_channels * 2;
+        const size_t n_mask = (size_t)B * S * 4;
+        const size_t n_vel = (size_t)B * T * m->cfg.out_channels * 4;
+        DevBuf &d_lat = ctx->h2d[H2D_DIT_LATENT], &d_ctx = ctx->h2d[H2D_DIT_CONTEXT], &d_ts = ctx->h2d[H2D_DIT_TIMESTEPS],
+               &d_mask = ctx->h2d[H2D_DIT_MASK], &d_vel = ctx->h2d[H2D_DIT_VELOCITY];
+        d_ctx.ensure(n_ctx);
+        d_mask.ensure(n_mask);
+        d_vel.ensure(n_vel);
+        // the context is constant across denoise steps: upload + re-project it only when its bytes change
+        const ContextSignature sig = context_signature(context, n_ctx, mask, (long)B * S);
+        stage_in(ctx, d_lat, latent, n_lat);
+        bool cached = false;
+        for (auto* e : m->ctx_cache) cached = cached || (e->version == sig.version && e->kind == 0 && e->B == B && e->S == S);
+        if (!cached) {
+            stage_in(ctx, d_ctx, context, n_ctx);
+            if (mask) stage_in(ctx, d_mask, mask, n_mask);
+        }
+        stage_in(ctx, d_ts, timesteps, (size_t)B * 4);
+        dit_forward(ctx, m, dit_args(d_lat.as<bf16_t>(), d_ctx.as<bf16_t>(), d_ts.as<float>(), mask ? d_mask.as<int32_t>() : nullptr,
+                                     sig.all_ones, B, F, H, W, S, sig.version, d_vel.as<float>()));
+        stage_out(ctx, velocity, d_vel, n_vel);
+        stage_sync(ctx);
+    });
+}
+
+int ltx_dit_forward_tokens(ltx_ctx* ctx, const uint16_t* latent, const uint16_t* context, const float* token_timesteps,
+                           const int32_t* mask, int B, int F, int H, int W, int S, float* velocity) {
+    return with_ctx(ctx, [&] {
+        DiTModel* m = need(ctx->dit, kNoDit);
+        LTX_REQUIRE(latent && context && token_timesteps && velocity && B >= 1 && F >= 1 && H >= 1 && W >= 1 && S >= 1,
+                    "ltx_dit_forward_tokens: bad arguments");
+        const long T = (long)F * H * W;
+        // distinct timestep values per batch row -> groups (order of first appearance); G = the largest count
+        std::vector<std::vector<float>> uniq(B);
+        std::vector<int32_t> rowmap((size_t)B * T);
+        int G = 1;
+        for (int b = 0; b < B; ++b) {
+            for (long t = 0; t < T; ++t) {
+                const float v = token_timesteps[(size_t)b * T + t];
+                size_t g = 0;
+                while (g < uniq[b].size() && uniq[b][g] != v) ++g;
+                if (g == uniq[b].size()) uniq[b].push_back(v);
+                rowmap[(size_t)b * T + t] = (int32_t)g;
+                LTX_REQUIRE(uniq[b].size() <= 8, "ltx_dit_forward_tokens: more than 8 distinct timesteps in batch row %d", b);
+            }
+            G = std::max(G, (int)uniq[b].size());
+        }
+        LTX_REQUIRE(B * G <= 8, "ltx_dit_forward_tokens: batch x distinct timesteps = %d exceeds 8", B * G);
+        std::vector<float> ts((size_t)B * G);
+        for (int b = 0; b < B; ++b)
+            for (int g = 0; g < G; ++g) ts[(size_t)b * G + g] = uniq[b][g < (int)uniq[b].size() ? g : 0];
+        for (int b = 0; b < B; ++b)
+            for (long t = 0; t < T; ++t) rowmap[(size_t)b * T + t] += b * G;
+        const size_t n_lat = (size_t)B * T * m->cfg.in_channels * 2;
+        const size_t n_ctx = (size_t)B * S * m->cfg.caption_channels * 2;
+        const size_t n_mask = (size_t)B * S * 4;
+        const size_t n_vel = (size_t)B * T * m->cfg.out_channels * 4;
+        DevBuf &d_lat = ctx->h2d[H2D_DIT_LATENT], &d_ctx = ctx->h2d[H2D_DIT_CONTEXT], &d_ts = ctx->h2d[H2D_DIT_TIMESTEPS],
+               &d_mask = ctx->h2d[H2D_DIT_MASK], &d_vel = ctx->h2d[H2D_DIT_VELOCITY];
+        d_ts.ensure(8 * 4);
+        d_mask.ensure(n_mask);
+        d_vel.ensure(n_vel);
+        ctx->dn_rowmap.ensure(std::max((size_t)B * T * 4, (size_t)2 * T * 4));
+        // per-token timesteps are not cached by context version (0): only the mask scan is wanted
+        const ContextSignature sig = context_signature(nullptr, 0, mask, (long)B * S);
+        stage_in(ctx, d_lat, latent, n_lat);
+        stage_in(ctx, d_ctx, context, n_ctx);
+        if (mask) stage_in(ctx, d_mask, mask, n_mask);
+        stage_in(ctx, d_ts, ts.data(), ts.size() * 4);
+        stage_in(ctx, ctx->dn_rowmap, rowmap.data(), rowmap.size() * 4);
+        DiTForwardArgs a = dit_args(d_lat.as<bf16_t>(), d_ctx.as<bf16_t>(), d_ts.as<float>(), mask ? d_mask.as<int32_t>() : nullptr,
+                                    sig.all_ones, B, F, H, W, S, sig.version, d_vel.as<float>());
+        a.n_groups = G;
+        a.row_map = ctx->dn_rowmap.as<int32_t>();
+        dit_forward(ctx, m, a);
+        stage_out(ctx, velocity, d_vel, n_vel);
+        stage_sync(ctx);  // also keeps ts / rowmap alive until the copies are done
+    });
+}
+
+int ltx_dit_set_cross_attn_scale(ltx_ctx* ctx, float scale, int first_block, int last_block) {
+    return with_ctx(ctx, [&] {
+        DiTModel* m = need(ctx->dit, kNoDit);
+        if (last_block < 0) last_block = m->L - 1;
+        for (int i = first_block; i <= last_block; ++i)
+            if (i >= 0 && i < m->L) m->blocks[i].cross_scale = scale;
+    });
+}
+
+int ltx_dit_set_stg(ltx_ctx* ctx, const int* blocks, int n_blocks, int skip_attn, int skip_ff) {
+    return with_ctx(ctx, [&] {
+        DiTModel* m = need(ctx->dit, kNoDit);
+        for (int j = 0; j < n_blocks; ++j) {
+            const int i = blocks[j];
+            if (i < 0 || i >= m->L) continue;
+            m->blocks[i].skip_attn = skip_attn != 0;
+            m->blocks[i].skip_ff = skip_ff != 0;
+        }
+    });
+}
+
+int ltx_dit_clear_stg(ltx_ctx* ctx) {
+    return with_ctx(ctx, [&] {
+        DiTModel* m = need(ctx->dit, kNoDit);
+        for (auto& b : m->blocks) b.skip_attn = b.skip_ff = false;
+    });
+}
+
+// ---- VAE ----
+int ltx_vae_load(ltx_ctx* ctx, const char* path, const char* config_json) {
+    if (!ctx || !path) return LTX_ERR_INVALID_CONFIGURATION;
+    return guarded(ctx, [&] {
+        replace_model(ctx, &ctx->vae, vae_create,
+                      [&](VaeModel* m) { vae_load_safetensors(ctx, m, path, config_json ? config_json : ""); }, vae_destroy);
+    });
+}
+
+int ltx_vae_init_synthetic(ltx_ctx* ctx, uint64_t seed, int timestep_conditioning) {
+    return with_ctx(ctx, [&] {
+        replace_model(ctx, &ctx->vae, vae_create, [&](VaeModel* m) { vae_init_synthetic(ctx, m, seed, timestep_conditioning != 0); },
+                      vae_destroy);
+    });
+}
+
+int ltx_vae_unload(ltx_ctx* ctx) {
+    return with_ctx(ctx, [&] { unload_model(ctx, &ctx->vae, vae_destroy); });
+}
+
+int ltx_vae_timestep_conditioning(const ltx_ctx* ctx) {
+    if (!ctx || !ctx->vae) return -LTX_ERR_MODEL_NOT_LOADED;
+    return ctx->vae->timestep_conditioning ? 1 : 0;
+}
+
+int ltx_vae_decode_dev(ltx_ctx* ctx, const float* latent, int F, int H, int W, int has_timestep, float timestep,
+                       const float* noise, int tile, int overlap, float* frames_out, long frames_cap,
+                       int* n_frames_out) {
+    return with_ctx(ctx, [&] {
+        VaeModel* m = need(ctx->vae, kNoVae);
+        vae_decode(ctx, m, vae_args(latent, F, H, W, has_timestep, timestep, noise, tile, overlap, frames_out, frames_cap, n_frames_out));
+    });
+}
+
+int ltx_vae_decode_sharded_dev(ltx_ctx* ctx, const float* latent, int F, int H, int W, int has_timestep, float timestep,
+                               const float* noise, int tile, int overlap, float* frames_out, long frames_cap,
+                               int* n_frames_out) {
+    return with_ctx(ctx, [&] {
+        VaeModel* m = need(ctx->vae, kNoVae);
+        LTX_REQUIRE(ctx->dist, "ltx_vae_decode_sharded_dev: no group on this context (ltx_dist_init / ltx_dist_set_transport)");
+        VaeDecodeArgs a = vae_args(latent, F, H, W, has_timestep, timestep, noise, tile, overlap, frames_out, frames_cap, n_frames_out);
+        a.shard = 1;
+        vae_decode(ctx, m, a);
+    });
+}
+
+int ltx_vae_decode_gathered_dev(ltx_ctx* ctx, const float* latent, int F, int H, int W, int has_timestep, float timestep,
+                                const float* noise, int tile, int overlap, int root, float* frames_out, long frames_cap,
+                                int* n_frames_out) {
+    return with_ctx(ctx, [&] {
+        VaeModel* m = need(ctx->vae, kNoVae);
+        LTX_REQUIRE(ctx->dist, "ltx_vae_decode_gathered_dev: no group on this context (ltx_dist_init / ltx_dist_set_transport)");
+        VaeDecodeArgs a = vae_args(latent, F, H, W, has_timestep, timestep, noise, tile, overlap, frames_out, frames_cap, n_frames_out);
+        a.shard = 2;
+        a.root = root;
+        vae_decode(ctx, m, a);
+    });
+}
+
+int ltx_vae_decode_tile_dev(ltx_ctx* ctx, const float* latent, int F, int H, int W, int has_timestep, float timestep,
+                            const float* noise, int tile, int overlap, int tile_index, float* tile_out, long tile_cap,
+                            int* n_frames_out) {
+    return with_ctx(ctx, [&] {
+        VaeModel* m = need(ctx->vae, kNoVae);
+        vae_decode_tile(ctx, m, vae_args(latent, F, H, W, has_timestep, timestep, noise, tile, overlap, tile_out, tile_cap, n_frames_out),
+                        tile_index);
+    });
+}
+
+int ltx_vae_res_block_dev(ltx_ctx* ctx, int group, int block, float* x, int F, int H, int W) {
+    return with_ctx(ctx, [&] { vae_res_block(ctx, need(ctx->vae, kNoVae), group, block, x, F, H, W); });
+}
+
+int ltx_vae_upsample_dev(ltx_ctx* ctx, int group, const float* x, int F, int H, int W, float* out) {
+    return with_ctx(ctx, [&] { vae_upsample(ctx, need(ctx->vae, kNoVae), group, x, F, H, W, out); });
+}
+
+int ltx_vae_blend_tiles_dev(ltx_ctx* ctx, const float* const* tiles, const int* tile_frames, int n_tiles, int overlap, int H,
+                            int W, float* frames_out, long frames_cap, int* n_frames_out) {
+    return with_ctx(ctx, [&] {
+        LTX_REQUIRE(H >= 1 && W >= 1, "ltx_vae_blend_tiles_dev: bad latent size");
+        const int n = vae_blend_tiles(ctx, tiles, tile_frames, n_tiles, overlap, H, W, frames_out, frames_cap);
+        if (n_frames_out) *n_frames_out = n;
+    });
+}
+
+int ltx_vae_decode(ltx_ctx* ctx, const float* latent, int F, int H, int W, int has_timestep, float timestep,
+                   const float* noise, int tile, int overlap, float* frames_out, long frames_cap, int* n_frames_out) {
+    return with_ctx(ctx, [&] {
+        VaeModel* m = need(ctx->vae, kNoVae);
+        LTX_REQUIRE(latent && frames_out && F >= 1 && H >= 1 && W >= 1, "ltx_vae_decode: bad arguments");
+        const size_t n_lat = (size_t)128 * F * H * W * 4;
+        DevBuf dl, dn, df;  // per call, freed on return: the frame buffer is far too large to keep resident
+        const bool noisy = has_timestep && noise;
+        stage_in(ctx, dl, latent, n_lat);
+        if (noisy) stage_in(ctx, dn, noise, n_lat);
+        df.ensure((size_t)frames_cap * 4);
+        int nf = 0;
+        vae_decode(ctx, m, vae_args(dl.as<float>(), F, H, W, has_timestep, timestep, noisy ? dn.as<float>() : nullptr, tile, overlap,
+                                    df.as<float>(), frames_cap, &nf));
+        stage_out(ctx, frames_out, df, (size_t)nf * H * 32 * W * 32 * 3 * 4);
+        stage_sync(ctx);
+        if (n_frames_out) *n_frames_out = nf;
+    });
+}
+
+// ---- two-stage glue ----
+int ltx_upscaler_load(ltx_ctx* ctx, const char* path) {
+    if (!ctx || !path) return LTX_ERR_INVALID_CONFIGURATION;
+    return guarded(ctx, [&] {
+        // upscaler_load sizes the model from the file and returns it filled (or throws with nothing left behind)
+        replace_model(ctx, &ctx->upscaler, [&] { return upscaler_load(ctx, path); }, [](UpscalerModel*) {}, upscaler_destroy);
+    });
+}
+
+int ltx_upscaler_unload(ltx_ctx* ctx) {
+    return with_ctx(ctx, [&] { unload_model(ctx, &ctx->upscaler, upscaler_destroy); });
+}
+
+int ltx_upscale_latent_dev(ltx_ctx* ctx, const float* latent, int F, int H, int W, float* out) {
+    return with_ctx(ctx, [&] { upscale_body(ctx, latent, F, H, W, out); });
+}
+
+int ltx_upscale_latent(ltx_ctx* ctx, const float* latent, int F, int H, int W, float* out) {
+    return with_ctx(ctx, [&] {
+        need(ctx->upscaler, kNoUpscaler);  // a missing model is reported before a bad argument
+        need(ctx->vae, kNoVae);
+        LTX_REQUIRE(latent && out && F >= 1 && H >= 1 && W >= 1, "ltx_upscale_latent: bad arguments");
+        const size_t n_in = (size_t)128 * F * H * W * 4;
+        DevBuf di, dout;  // per call, freed on return
+        di.ensure(n_in);
+        dout.ensure(n_in * 4);
+        stage_in(ctx, di, latent, n_in);
+        upscale_body(ctx, di.as<float>(), F, H, W, dout.as<float>());
+        stage_out(ctx, out, dout, n_in * 4);
+        stage_sync(ctx);
+    });
+}
+
+int ltx_adain_filter_latent_dev(ltx_ctx* ctx, float* latent, long n, const float* reference, long n_ref, int channels,
+                                float factor) {
+    return with_ctx(ctx, [&] {
+        LTX_REQUIRE(latent && reference && n > 0 && n_ref > 0 && channels > 0, "adain: bad arguments");
+        if (factor <= 0.f) return;
+        adain_body(ctx, latent, n, reference, n_ref, channels, factor);
+    });
+}
+
+int ltx_adain_filter_latent(ltx_ctx* ctx, float* latent, long n, const float* reference, long n_ref, int channels,
+                            float factor) {
+    return with_ctx(ctx, [&] {
+        LTX_REQUIRE(latent && reference && n > 0 && n_ref > 0 && channels > 0, "adain: bad arguments");
+        if (factor <= 0.f) return;
+        const size_t n_lat = (size_t)n * channels * 4, n_reference = (size_t)n_ref * channels * 4;
+        DevBuf dl, dr;  // per call, freed on return
+        dl.ensure(n_lat);
+        dr.ensure(n_reference);
+        stage_in(ctx, dl, latent, n_lat);
+        stage_in(ctx, dr, reference, n_reference);
+        adain_body(ctx, dl.as<float>(), n, dr.as<float>(), n_ref, channels, factor);
+        stage_out(ctx, latent, dl, n_lat);
+        stage_sync(ctx);
+    });
+}
+
+int ltx_renoise_dev(ltx_ctx* ctx, float* latent, const float* noise, float sigma, long n) {
+    return with_ctx(ctx, [&] { launch_lincomb(noise, latent, sigma, 1.0f - sigma, latent, n, ctx->stream); });
+}
+
+// ---- denoise loop ----
+int ltx_denoise_dev(ltx_ctx* ctx, float* latent, int F, int H, int W, const float* sigmas, int n_sigmas,
+                    const uint16_t* context, const int32_t* mask, int mask_all_ones, int S, uint64_t ctx_version,
+                    const ltx_denoise_options* opt, ltx_progress_cb cb, void* user) {
+    return with_ctx(ctx, [&] {
+        DenoiseParams p;
+        p.latent = latent; p.F = F; p.H = H; p.W = W;
+        p.sigmas = sigmas; p.n_sigmas = n_sigmas;
+        p.context = context; p.mask = mask; p.mask_all_ones = mask_all_ones; p.S = S;
+        p.ctx_version = ctx_version;
+        fill_params(p, opt);
+        p.progress = cb; p.user = user;
+        denoise_run(ctx, p);
+    });
+}
+
+int ltx_denoise(ltx_ctx* ctx, float* latent, int F, int H, int W, const float* sigmas, int n_sigmas,
+                const uint16_t* context, const int32_t* mask, int S, const ltx_denoise_options* opt,
+                ltx_progress_cb cb, void* user) {
+    return with_ctx(ctx, [&] {
+        DiTModel* m = need(ctx->dit, kNoDit);
+        LTX_REQUIRE(latent && sigmas && context && F >= 1 && H >= 1 && W >= 1 && S >= 1 && n_sigmas >= 2, "ltx_denoise: bad arguments");
+        const int nb = (opt && opt->cfg_scale > 1.0f) ? 2 : 1;
+        const size_t n_lat = (size_t)m->cfg.in_channels * F * H * W * 4;
+        const size_t n_ctx = (size_t)nb * S * m->cfg.caption_channels * 2;
+        const size_t n_mask = (size_t)nb * S * 4;
+        DevBuf &d_lat = ctx->h2d[H2D_DENOISE_LATENT], &d_ctx = ctx->h2d[H2D_DENOISE_CONTEXT], &d_mask = ctx->h2d[H2D_DENOISE_MASK];
+        d_ctx.ensure(n_ctx);
+        d_mask.ensure(n_mask);
+        stage_in(ctx, d_lat, latent, n_lat);
+        stage_in(ctx, d_ctx, context, n_ctx);
+        if (mask) stage_in(ctx, d_mask, mask, n_mask);
+        const ContextSignature sig = context_signature(context, n_ctx, mask, (long)nb * S);
+        DenoiseParams p;
+        p.latent = d_lat.as<float>(); p.F = F; p.H = H; p.W = W;
+        p.sigmas = sigmas; p.n_sigmas = n_sigmas;
+        p.context = d_ctx.as<bf16_t>();
+        p.mask = mask ? d_mask.as<int32_t>() : nullptr;
+        p.mask_all_ones = sig.all_ones; p.S = S;
+        p.ctx_version = sig.version;
+        fill_params(p, opt);
+        if (opt && opt->cond_latent) {  // image-to-video: stage the image latent (and the re-noising draws) on the device
+            const size_t n_c = (size_t)m->cfg.in_channels * H * W * 4;
+            stage_in(ctx, ctx->i2v_cond, opt->cond_latent, n_c);
+            p.cond_latent = ctx->i2v_cond.as<float>();
+            if (opt->cond_noise) {
+                stage_in(ctx, ctx->i2v_noise, opt->cond_noise, n_c * (n_sigmas - 1));
+                p.cond_noise = ctx->i2v_noise.as<float>();
+            }
+        }
+        p.progress = cb; p.user = user;
+        denoise_run(ctx, p);
+        stage_out(ctx, latent, d_lat, n_lat);
+        stage_sync(ctx);
+    });
+}
+
+// ---- multi-GPU ----
+int ltx_dist_unique_id(void* id_out) {
+    if (!id_out) return LTX_ERR_INVALID_CONFIGURATION;
+    return guarded(nullptr, [&] { dist_unique_id(id_out); });
+}
+
+int ltx_dist_init(ltx_ctx* ctx, int rank, int world, const void* id) {
+    return with_ctx(ctx, [&] { dist_init_native(ctx, rank, world, id); });
+}
+
+int ltx_dist_set_transport(ltx_ctx* ctx, int rank, int world, ltx_allgather_fn gather, void* user) {
+    return with_ctx(ctx, [&] { dist_set_transport(ctx, rank, world, gather, user); });
+}
+
+int ltx_dist_shutdown(ltx_ctx* ctx) {
+    return with_ctx(ctx, [&] { dist_shutdown(ctx); });
+}
+
+int ltx_dist_info(const ltx_ctx* ctx, int* rank, int* world, int* native_transport, long* n_collectives) {
+    if (!ctx) return LTX_ERR_INVALID_CONFIGURATION;
+    if (rank) *rank = dist_rank(ctx);
+    if (world) *world = dist_world(ctx);
+    if (native_transport) *native_transport = (ctx->dist && ctx->dist->comm) ? 1 : 0;
+    if (n_collectives) *n_collectives = ctx->dist ? ctx->dist->n_collectives : 0;
+    return LTX_OK;
+}
+
+int ltx_dist_allgather_dev(ltx_ctx* ctx, const void* send, void* recv, long bytes) {
+    return with_ctx(ctx, [&] { dist_allgather(ctx, send, recv, bytes); });
+}
+
+int ltx_dist_broadcast_dev(ltx_ctx* ctx, void* buf, long bytes, int root) {
+    return with_ctx(ctx, [&] { dist_broadcast(ctx, buf, bytes, root); });
+}
+
+/* ---- text-embedding connector ---- */
+int ltx_connector_load(ltx_ctx* ctx, const char* path, const ltx_connector_config* cfg) {
+    if (!ctx || !path) return LTX_ERR_INVALID_CONFIGURATION;
+    return guarded(ctx, [&] {
+        replace_model(ctx, &ctx->connector, [&] { return connector_create(to_conn_cfg(cfg)); },
+                      [&](ConnectorModel* m) { connector_load_safetensors(ctx, m, path); }, connector_destroy);
+    });
+}
+
+int ltx_connector_init_synthetic(ltx_ctx* ctx, const ltx_connector_config* cfg, unsigned long seed) {
+    return with_ctx(ctx, [&] {
+        replace_model(ctx, &ctx->connector, [&] { return connector_create(to_conn_cfg(cfg)); },
+                      [&](ConnectorModel* m) { connector_init_synthetic(ctx, m, seed); }, connector_destroy);
+    });
+}
+
+int ltx_connector_unload(ltx_ctx* ctx) {
+    return with_ctx(ctx, [&] { unload_model(ctx, &ctx->connector, connector_destroy); });
+}
+
+int ltx_connector_encode_taps_dev(ltx_ctx* ctx, const uint16_t* hidden, const int32_t* attention_mask, int B, int T,
+                                  int padding_right, uint16_t* context, uint16_t* norm_concat, uint16_t* fe_out,
+                                  float* after_registers) {
+    return with_ctx(ctx, [&] {
+        ConnectorModel* m = need(ctx->connector, kNoConnector);
+        ConnectorArgs a;
+        a.hidden = hidden; a.mask = attention_mask; a.B = B; a.T = T; a.padding_right = padding_right;
+        a.out = context; a.dbg_nc = norm_concat; a.dbg_fe = fe_out; a.dbg_reg = after_registers;
+        connector_encode(ctx, m, a);
+    });
+}
+
+int ltx_connector_encode_dev(ltx_ctx* ctx, const uint16_t* hidden, const int32_t* attention_mask, int B, int T,
+                             int padding_right, uint16_t* context, int32_t* out_mask) {
+    return with_ctx(ctx, [&] {
+        ConnectorModel* m = need(ctx->connector, kNoConnector);
+        ConnectorArgs a;
+        a.hidden = hidden; a.mask = attention_mask; a.B = B; a.T = T; a.padding_right = padding_right;
+        a.out = context; a.out_mask = out_mask;
+        connector_encode(ctx, m, a);
+    });
+}
+
+int ltx_connector_encode(ltx_ctx* ctx, const uint16_t* hidden, const int32_t* attention_mask, int B, int T,
+                         int padding_right, uint16_t* context, int32_t* out_mask) {
+    return with_ctx(ctx, [&] {
+        ConnectorModel* m = need(ctx->connector, kNoConnector);
+        LTX_REQUIRE(hidden && attention_mask && context && B >= 1 && T >= 1, "connector_encode: bad arguments");
+        const ConnectorConfig& c = m->cfg;
+        const size_t hb = (size_t)c.states * B * T * c.dim * 2, mb = (size_t)B * T * 4, ob = (size_t)B * T * c.dim * 2;
+        DevBuf &d_hidden = ctx->h2d[H2D_CONN_HIDDEN], &d_mask = ctx->h2d[H2D_CONN_MASK], &d_context = ctx->h2d[H2D_CONN_CONTEXT],
+               &d_out_mask = ctx->h2d[H2D_CONN_OUT_MASK];
+        d_context.ensure(ob);
+        d_out_mask.ensure(mb);
+        stage_in(ctx, d_hidden, hidden, hb);
+        stage_in(ctx, d_mask, attention_mask, mb);
+        ConnectorArgs a;
+        a.hidden = d_hidden.as<bf16_t>(); a.mask = d_mask.as<int32_t>(); a.B = B; a.T = T; a.padding_right = padding_right;
+        a.out = d_context.as<bf16_t>(); a.out_mask = d_out_mask.as<int32_t>();
+        connector_encode(ctx, m, a);
+        stage_out(ctx, context, d_context, ob);
+        if (out_mask) stage_out(ctx, out_mask, d_out_mask, mb);
+        stage_sync(ctx);
+    });
+}
+
+/* ---- VAE encoder ---- */
+int ltx_vae_encoder_load(ltx_ctx* ctx, const char* path, int channel_base) {
+    if (!ctx || !path) return LTX_ERR_INVALID_CONFIGURATION;
+    return guarded(ctx, [&] {
+        replace_model(ctx, &ctx->vae_encoder, [&] { return vae_encoder_create(channel_base > 0 ? channel_base : 128); },
+                      [&](VaeEncoderModel* m) { vae_encoder_load_safetensors(ctx, m, path); }, vae_encoder_destroy);
+    });
+}
+
+int ltx_vae_encoder_init_synthetic(ltx_ctx* ctx, int channel_base, unsigned long seed) {
+    return with_ctx(ctx, [&] {
+        replace_model(ctx, &ctx->vae_encoder, [&] { return vae_encoder_create(channel_base > 0 ? channel_base : 128); },
+                      [&](VaeEncoderModel* m) { vae_encoder_init_synthetic(ctx, m, seed); }, vae_encoder_destroy);
+    });
+}
+
+int ltx_vae_encoder_unload(ltx_ctx* ctx) {
+    return with_ctx(ctx, [&] { unload_model(ctx, &ctx->vae_encoder, vae_encoder_destroy); });
+}
+
+int ltx_vae_encode_dev(ltx_ctx* ctx, const float* pixels, int T, int H, int W, int normalize, float* latent) {
+    return with_ctx(ctx, [&] { encode_body(ctx, pixels, T, H, W, normalize, latent); });
+}
+
+int ltx_vae_encode(ltx_ctx* ctx, const float* pixels, int T, int H, int W, int normalize, float* latent) {
+    return with_ctx(ctx, [&] {
+        LTX_REQUIRE(pixels && latent && T >= 1 && H >= 1 && W >= 1, "ltx_vae_encode: bad arguments");
+        const size_t nb_in = (size_t)3 * T * H * W * 4;
+        const size_t nb_out = (size_t)128 * vae_encoder_latent_frames(T) * (H / 32) * (W / 32) * 4;
+        DevBuf &d_pixels = ctx->h2d[H2D_IN], &d_latent = ctx->h2d[H2D_OUT];
+        d_latent.ensure(nb_out ? nb_out : 4);
+        stage_in(ctx, d_pixels, pixels, nb_in);
+        encode_body(ctx, d_pixels.as<float>(), T, H, W, normalize, d_latent.as<float>());
+        stage_out(ctx, latent, d_latent, nb_out);
+        stage_sync(ctx);
+    });
+}
+
+/* ---- audio decode leg (audio.h) ---- */
+int ltx_audio_vae_load(ltx_ctx* ctx, const char* path) {
+    if (!ctx || !path) return LTX_ERR_INVALID_CONFIGURATION;
+    return guarded(ctx, [&] {
+        replace_model(ctx, &ctx->audio_vae, audio_vae_create, [&](AudioVaeModel* m) { audio_vae_load(ctx, m, path); }, audio_vae_destroy);
+    });
+}
+int ltx_audio_vae_init_synthetic(ltx_ctx* ctx, int base_channels, uint64_t seed) {
+    return with_ctx(ctx, [&] {
+        replace_model(ctx, &ctx->audio_vae, audio_vae_create,
+                      [&](AudioVaeModel* m) { audio_vae_init_synthetic(ctx, m, base_channels > 0 ? base_channels : 128, seed); },
+                      audio_vae_destroy);
+    });
+}
+int ltx_audio_vae_unload(ltx_ctx* ctx) {
+    return with_ctx(ctx, [&] { unload_model(ctx, &ctx->audio_vae, audio_vae_destroy); });
+}
+int ltx_vocoder_load(ltx_ctx* ctx, const char* path) {
+    if (!ctx || !path) return LTX_ERR_INVALID_CONFIGURATION;
+    return guarded(ctx, [&] {
+        replace_model(ctx, &ctx->vocoder, vocoder_create, [&](VocoderModel* m) { vocoder_load(ctx, m, path); }, vocoder_destroy);
+    });
+}
+int ltx_vocoder_init_synthetic(ltx_ctx* ctx, int hidden_channels, uint64_t seed) {
+    return with_ctx(ctx, [&] {
+        replace_model(ctx, &ctx->vocoder, vocoder_create,
+                      [&](VocoderModel* m) { vocoder_init_synthetic(ctx, m, hidden_channels > 0 ? hidden_channels : 1024, seed); },
+                      vocoder_destroy);
+    });
+}
+int ltx_vocoder_unload(ltx_ctx* ctx) {
+    return with_ctx(ctx, [&] { unload_model(ctx, &ctx->vocoder, vocoder_destroy); });
+}
+
+int ltx_audio_vae_decode_dev(ltx_ctx* ctx, const float* latent, int T, float* mel) {
+    return with_ctx(ctx, [&] { audio_vae_decode(ctx, need(ctx->audio_vae, kNoAudioVae), latent, T, mel); });
+}
+int ltx_audio_vae_decode(ltx_ctx* ctx, const float* latent, int T, float* mel) {
+    return with_ctx(ctx, [&] {
+        AudioVaeModel* m = need(ctx->audio_vae, kNoAudioVae);
+        LTX_REQUIRE(T >= 1 && T <= 4096, "ltx_audio_vae_decode: T=%d", T);
+        const size_t n_mel = (size_t)2 * audio_mel_frames(T) * 64;
+        const float* d_latent = audio_stage_in(ctx, latent, (size_t)8 * T * 16, mel, n_mel);
+        audio_vae_decode(ctx, m, d_latent, T, ctx->h2d[H2D_OUT].as<float>());
+        audio_stage_out(ctx, mel, n_mel);
+    });
+}
+int ltx_vocoder_forward_dev(ltx_ctx* ctx, const float* mel, int T_mel, float* waveform) {
+    return with_ctx(ctx, [&] { vocoder_forward(ctx, need(ctx->vocoder, kNoVocoder), mel, T_mel, waveform); });
+}
+int ltx_vocoder_forward(ltx_ctx* ctx, const float* mel, int T_mel, float* waveform) {
+    return with_ctx(ctx, [&] {
+        VocoderModel* m = need(ctx->vocoder, kNoVocoder);
+        LTX_REQUIRE(T_mel >= 1 && T_mel <= 16384, "ltx_vocoder_forward: T_mel=%d", T_mel);
+        const size_t n_wave = (size_t)2 * 240 * T_mel;
+        const float* d_mel = audio_stage_in(ctx, mel, (size_t)2 * T_mel * 64, waveform, n_wave);
+        vocoder_forward(ctx, m, d_mel, T_mel, ctx->h2d[H2D_OUT].as<float>());
+        audio_stage_out(ctx, waveform, n_wave);
+    });
+}
+int ltx_audio_decode_dev(ltx_ctx* ctx, const float* latent, int T, float* waveform) {
+    return with_ctx(ctx, [&] { audio_decode_body(ctx, latent, T, waveform); });
+}
+int ltx_audio_decode(ltx_ctx* ctx, const float* latent, int T, float* waveform) {
+    return with_ctx(ctx, [&] {
+        need(ctx->audio_vae, kNoAudioVae);  // a missing model is reported before a bad argument
+        need(ctx->vocoder, kNoVocoder);
+        LTX_REQUIRE(T >= 1 && T <= 4096, "ltx_audio_decode: T=%d", T);
+        const size_t n_wave = (size_t)2 * 240 * audio_mel_frames(T);
+        const float* d_latent = audio_stage_in(ctx, latent, (size_t)8 * T * 16, waveform, n_wave);
+        audio_decode_body(ctx, d_latent, T, ctx->h2d[H2D_OUT].as<float>());
+        audio_stage_out(ctx, waveform, n_wave);
+    });
+}
+
+}  // extern "C"

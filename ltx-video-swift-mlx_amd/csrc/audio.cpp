@@ -178,6 +178,15 @@ std::vector<int> convt_phase_taps(int k, int s, int p, int r, std::vector<int>* 
     return js;
 }
 
+std::vector<float> convt_phase_slab(const float* w, int cin, int cout, int k, const std::vector<int>& js, int cin_pad) {
+    const size_t nt = js.size();
+    std::vector<float> slab((size_t)cout * nt * cin_pad, 0.f);
+    for (int o = 0; o < cout; ++o)
+        for (size_t t = 0; t < nt; ++t)
+            for (int c = 0; c < cin; ++c) slab[((size_t)o * nt + t) * cin_pad + c] = w[((size_t)c * cout + o) * k + js[t]];
+    return slab;
+}
+
 // ================================================================================================================
 // Audio VAE decoder
 // ================================================================================================================
@@ -405,12 +414,7 @@ static void vocoder_assemble(ltx_ctx* ctx, VocoderModel* m, const AHostWeights& 
         u.off.assign((size_t)u.stride, {});
         for (int r = 0; r < u.stride; ++r) {
             const std::vector<int> js = convt_phase_taps(u.k, u.stride, u.pad, r, &u.off[r]);
-            const int nt = (int)js.size();
-            std::vector<float> slab((size_t)u.cout * nt * u.cin_pad, 0.f);
-            for (int o = 0; o < u.cout; ++o)
-                for (int t = 0; t < nt; ++t)
-                    for (int c = 0; c < u.cin; ++c) slab[((size_t)o * nt + t) * u.cin_pad + c] = w->v[((size_t)c * u.cout + o) * u.k + js[t]];
-            as.push_bf16(&u.w[r], slab);
+            as.push_bf16(&u.w[r], convt_phase_slab(w->v.data(), u.cin, u.cout, u.k, js, u.cin_pad));
         }
         as.bias(p + ".bias", u.cout, &u.b);
         ch = u.cout;

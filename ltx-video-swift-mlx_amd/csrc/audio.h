@@ -107,6 +107,10 @@ struct VocoderModel {
 // taps of phase r of a transposed conv (kernel k, stride s, padding p): torch tap j contributes to output t*s + r from input row
 // t + (r + p - j) / s iff (r + p - j) % s == 0. Returns the js; offs gets the row offsets.
 std::vector<int> convt_phase_taps(int k, int s, int p, int r, std::vector<int>* offs);
+// weights of one phase in the kernel's order: PyTorch ConvTranspose1d weight w (cin, cout, k) -> [cout][js.size()][cin_pad], tap t of the
+// slab = torch tap js[t], input channels >= cin zero. The one [Cout][taps][Cin] reorder: the vocoder loader and the
+// ltx_op_conv_transpose1d test hook both build their slabs here.
+std::vector<float> convt_phase_slab(const float* w, int cin, int cout, int k, const std::vector<int>& js, int cin_pad);
 
 AudioVaeModel* audio_vae_create();
 void audio_vae_destroy(AudioVaeModel* m);

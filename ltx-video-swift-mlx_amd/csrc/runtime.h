@@ -126,6 +126,21 @@ struct ProfScope {
     }
 };
 
+// Staging buffers of the host-pointer entry points (ltx_ctx::h2d). They grow on demand and stay resident. Every host-pointer entry
+// point synchronises before it returns, so entry points may share a slot; none keeps data in one across calls (a context-cache hit
+// in ltx_dit_forward reads the cached projection, not H2D_DIT_CONTEXT).
+enum H2dSlot {
+    // ltx_dit_forward and ltx_dit_forward_tokens
+    H2D_DIT_LATENT = 0, H2D_DIT_CONTEXT = 1, H2D_DIT_TIMESTEPS = 2, H2D_DIT_MASK = 3, H2D_DIT_VELOCITY = 4,
+    // ltx_denoise: slots of its own
+    H2D_DENOISE_LATENT = 5, H2D_DENOISE_CONTEXT = 6, H2D_DENOISE_MASK = 7,
+    // ltx_connector_encode: shares 0-3 with the DiT forwards
+    H2D_CONN_HIDDEN = 0, H2D_CONN_MASK = 1, H2D_CONN_CONTEXT = 2, H2D_CONN_OUT_MASK = 3,
+    // one input, one output: ltx_vae_encode, ltx_audio_vae_decode, ltx_vocoder_forward, ltx_audio_decode (share 0-1 with the above)
+    H2D_IN = 0, H2D_OUT = 1,
+    H2D_COUNT = 8
+};
+
 struct ltx_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -140,8 +155,7 @@ struct ltx_ctx {
     AudioVaeModel* audio_vae = nullptr;  // audio decode leg (audio.h)
     VocoderModel* vocoder = nullptr;
     DevBuf audio_mel, audio_op[2];  // the mel between the two audio models; haloed operands of the audio conv test hooks
-    // staging buffers for host-pointer entry points
-    DevBuf h2d[8];
+    DevBuf h2d[H2D_COUNT];  // staging buffers of the host-pointer entry points, indexed by H2dSlot
     // load report of the last *_load call (mirrors the reference's "unmatched/missing" debug logs)
     int n_loaded = 0, n_missing = 0, n_unmatched = 0;
     Profiler prof;

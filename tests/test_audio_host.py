@@ -114,3 +114,28 @@ def test_audio_loaders_report(ltx, gpu_ctx, tmp_path):
     assert gpu_ctx.load_report() == {'loaded': len(wg) - 1, 'missing': 1, 'unmatched': 2}
     gpu_ctx.vocoder_unload()
     gpu_ctx.audio_vae_unload()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("k,s,p", [(16, 6, 5), (15, 5, 5), (8, 2, 3), (4, 2, 1)])
+def test_conv_transpose1d_phase_slabs_read_back(gpu_ctx, k, s, p):
+    """The [Cout][taps][Cin] phase slabs, read back element by element: unit impulses, one input channel per row block, make the
+    output of ltx_op_conv_transpose1d a copy of the weights in the order the phases placed them, and every weight is distinct from
+    its neighbours in all three indices. Same reference and same exact comparison as tests/test_audio_gpu.py
+    (torch conv_transpose1d, torch.equal). The hook builds its slabs with convt_phase_slab, the function the vocoder loader calls,
+    so this comparison and those of test_audio_gpu.py cover the loader's reorder too (needs a device to launch on)."""
+    import torch
+    import torch.nn.functional as F
+
+    cin, cout, gap = 64, 32, 8  # gap rows between impulses >= the k / s rows one impulse reaches
+    c, o, j = torch.meshgrid(torch.arange(cin), torch.arange(cout), torch.arange(k), indexing="ij")
+    w = ((c * 31 + o * 7 + j * 3) % 201 - 100).float()  # torch layout (in, out, k); integers, exact in bf16
+    x = torch.zeros((cin * gap, cin))
+    x[torch.arange(cin) * gap + 3, torch.arange(cin)] = 1.0
+    L = x.shape[0]
+    ref = F.conv_transpose1d(x.t()[None].double(), w.double(), None, stride=s, padding=p)[0].t().float()
+    assert ref.shape == (s * L, cout) and len(torch.unique(ref)) > 150
+    out = torch.full((s * L, cout), float("nan"), device="cuda")
+    gpu_ctx.op_conv_transpose1d(x.to(torch.bfloat16).cuda().contiguous(), w.to(torch.bfloat16).cuda().contiguous(), None, s, p, out_f32=out)
+    torch.cuda.synchronize()
+    assert torch.equal(out.cpu(), ref)
