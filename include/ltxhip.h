@@ -299,8 +299,8 @@ int ltx_map_vae_encoder_key(const char* file_key, char* out, int cap);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Audio decode leg (decodeAudio, Vocoder.swift:325-361): audio latent -> AudioVAE.decode -> stereo mel -> LTX2Vocoder -> 24 kHz
- * stereo waveform. The dual (video + audio) transformer that PRODUCES the audio latent is not part of this library yet: the latent
- * is an input. Precision: weights rounded to bf16 at load, bf16 conv operands, f32 accumulation, f32 residual streams.
+ * stereo waveform. The dual (video + audio) transformer that PRODUCES the audio latent is not part of this library yet (its attention
+ * module is: "Audio / cross-modal attention" below): the latent is an input. Precision: weights rounded to bf16 at load, bf16 conv operands, f32 accumulation, f32 residual streams.
  * ---------------------------------------------------------------------------------------------------------- */
 /* Replaces AudioVAE() + loadAudioVAEWeights / applyAudioVAEWeights (ModelDownloader.swift:1116-1158): keeps `decoder.*`, `latents_mean`
  * and `latents_std`, drops everything else; Conv2d weights are PyTorch (out, in, kh, kw) under `...conv.weight`. Channel counts come
@@ -338,6 +338,45 @@ int ltx_audio_sample_rate(void);
 /* AudioExporter.exportToWAV (AudioExporter.swift:19-92): waveform [2][n] f32 -> gain, clamp to [-1, 1], int16 by truncation toward
  * zero of x * 32767.0f, interleaved L/R behind the 44-byte PCM header. Pure host code. */
 int ltx_write_wav(const char* path, const float* waveform, long n, int sample_rate, float gain);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Audio / cross-modal attention: LTXAttention at 32 heads x 64 (LTXConfig.swift:134-135), the module the dual video + audio block
+ * adds four times to the video block - audio self-attention, audio text cross-attention, a2v and v2a cross-modal attention
+ * (LTX2TransformerBlock.swift:133-163,207-270) - with the RoPE tables of its real-valued 1-D positions. A context holds up to four
+ * modules, addressed by index 0 .. 3. The audio stream's adaLN embedders, the cross-modal scale-shift embedders, the block wiring and
+ * the joint denoise loop are not part of this library yet.
+ * ---------------------------------------------------------------------------------------------------------- */
+/* createAudioPositionGrid (LTXRoPE.swift:627-655; hop 160, rate 16000, scale 4, causal offset 1, f32 arithmetic): out[i] = seconds of
+ * the middle of audio latent frame i, i < T_a (0.005, 0.03, 0.07, ...). Pure host code. */
+int ltx_audio_positions(int T_a, float* out);
+/* The temporal coordinate of every video token in token order: row 0 of createPositionGrid (LTXRoPE.swift:552-610), which the
+ * cross-modal RoPE uses alone (LTX2Transformer.swift:205-209). out [F*H*W]. Pure host code. */
+int ltx_video_temporal_positions(int F, int H, int W, float fps, float* out);
+/* precomputeFreqsCis, f64 path, for ONE position dimension (LTXRoPE.swift:375-490 as LTX2Transformer.swift:176-184,210-233 call it):
+ * dim/2 frequencies theta^(i/(n-1)) * pi/2 times 2 * positions[t] / max_pos - 1 (max_pos 20 in the dual model); cos/sin [T][dim/2] f32,
+ * no padding slots. Head h of a 64-wide head owns columns 32h .. 32h+31. Pure host code. */
+int ltx_rope_tables_positions(const float* positions, int T, int dim, float theta, int max_pos, float* cos_out, float* sin_out);
+/* Random-init module (LTXAttention.init, LTXAttention.swift:130-158): to_q [heads*64][query_dim], to_k / to_v [heads*64][context_dim],
+ * to_out [query_dim][heads*64], biases, q_norm / k_norm [heads*64]. context_dim 0 = query_dim. Dims are multiples of 64. */
+int ltx_attn_module_init_synthetic(ltx_ctx* ctx, int index, int query_dim, int context_dim, int heads, uint64_t seed);
+/* Reads `<key_prefix>to_q.weight` ... from a safetensors file, e.g. key_prefix "transformer_blocks.0.audio_to_video_attn." (module
+ * names to_out / q_norm / k_norm or the checkpoint's to_out.0 / norm_q / norm_k, ModelDownloader.swift:756-803). query_dim and
+ * context_dim come from the file; heads * 64 must be the file's inner dim (LTX_ERR_INVALID_CONFIGURATION otherwise). */
+int ltx_attn_module_load(ltx_ctx* ctx, int index, const char* safetensors_path, const char* key_prefix, int heads);
+int ltx_attn_module_unload(ltx_ctx* ctx, int index);
+/* One resident parameter of module `index` as f32 ("to_q.weight", "to_q.bias", ..., "q_norm.weight", "k_norm.weight"): returns its
+ * element count (out NULL: the count only), or a negative ltx_status. Test seam, as ltx_dit_export_param. */
+long ltx_attn_module_export_param(ltx_ctx* ctx, int index, const char* name, float* out, long cap);
+/* Replaces LTXAttention.callAsFunction (LTXAttention.swift:160-218) at head dim 64. x [B][Tq][query_dim] f32; context
+ * [B][Tk][context_dim] f32, or bf16 with context_bf16 != 0 (the text context: K / V then round to bf16 as the reference's bf16
+ * Linears do), or NULL = self-attention (Tk == Tq). q_cos / q_sin [q_table_rows][heads*32] f32 rotate q; k_cos / k_sin
+ * [k_table_rows][heads*32] rotate k; with only the q tables given k is rotated with them (the reference's `kPe ?? pe`); all NULL = no
+ * RoPE. key_bias [B][Tk] f32 additive in the reference's units ((1 - mask) * -10000) or NULL. out [B][Tq][query_dim] f32. DEVICE
+ * pointers, asynchronous on the context stream. An empty index is LTX_ERR_MODEL_NOT_LOADED; tables with fewer rows than tokens are
+ * LTX_ERR_INVALID_CONFIGURATION; both are reported before any launch. */
+int ltx_attn_module_forward_dev(ltx_ctx* ctx, int index, const float* x, const void* context, int context_bf16, int B, int Tq, int Tk,
+                                const float* q_cos, const float* q_sin, int q_table_rows, const float* k_cos, const float* k_sin,
+                                int k_table_rows, const float* key_bias, float* out);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Text-embedding connector (VideoGemmaTextEncoderModel.encodeFromHiddenStates,
@@ -565,12 +604,25 @@ int ltx_op_attention(ltx_ctx* ctx, const uint16_t* Q, const uint16_t* K, const u
  * per (query block, head, key range) and a combine pass (attention.h, AttnArgs::split_ws). ltx_op_attention and the DiT forward
  * both lend that workspace. No reference counterpart: MLXFast.scaledDotProductAttention (LTXAttention.swift:209) is one call. */
 int ltx_attention_key_splits(int B, int H, int Tq, int Tk);
+/* ltx_op_attention with a head dim (64 or 128): at 128 it IS ltx_op_attention; at 64 (LTXAttention at 32 heads x 64,
+ * LTXAttention.swift:192-214) the layouts are Q / K / O [B][T][H*64], Vt [B][H*64][ldvt], and scale <= 0 means Q carries
+ * (1/sqrt(64)) * log2(e). Launches at head dim 64 are never key-split. */
+int ltx_op_attention_hd(ltx_ctx* ctx, const uint16_t* Q, const uint16_t* K, const uint16_t* Vt, long ldvt, const float* bias, int B, int H,
+                        int Tq, int Tk, int head_dim, float scale, uint16_t* O);
+/* Test seam: queries per workgroup the launcher picks for a head-dim-64 launch of this shape, 256, 128 or 64 by grid fill (0: not head
+ * dim 64), so that the tests can show they reach every instance of the kernel. No reference counterpart, as ltx_attention_key_splits. */
+int ltx_attention_hd_workgroup_queries(int B, int H, int Tq, int head_dim);
 /* adaLN: out = norm(x) * (1+scale) + shift -> bf16 ; norm_kind 0 RMS, 1 LayerNorm; scale/shift [D] or NULL */
 int ltx_op_norm_mod(ltx_ctx* ctx, const float* x, const float* scale, const float* shift, int rows, int D,
                     int norm_kind, float eps, int round_norm_bf16, uint16_t* out);
 /* q/k RMSNorm (weight w[D]) + split RoPE (cos/sin [T][D/2] or NULL) -> bf16 */
 int ltx_op_qknorm_rope(ltx_ctx* ctx, const float* x, long ldx, const float* w, const float* cos_t, const float* sin_t,
                        int T, int rows, int D, float eps, uint16_t* out);
+/* ltx_op_qknorm_rope with a head dim (64 or 128) and the folded output scale: head h of a row is columns h*head_dim .., rotated as its
+ * two halves with columns h*head_dim/2 .. of the cos/sin row [T][D/2] (applySplitRotaryEmb, LTXRoPE.swift:84-149); the norm is across
+ * the whole row (LTXAttention.swift:145-149,179-180); out_scale multiplies the row before its one rounding to bf16. */
+int ltx_op_qknorm_rope_hd(ltx_ctx* ctx, const float* x, long ldx, const float* w, const float* cos_t, const float* sin_t, int T, int rows,
+                          int D, int head_dim, float out_scale, float eps, uint16_t* out);
 /* ltx_op_norm_mod with every argument of the launcher (test seam: the shapes and strides the DiT passes select kernels the call above
  * cannot reach): x [rows][ldx] f32, out [rows][ldo] bf16, the modulation row of output row r is scale/shift + b * mod_bstride with
  * b = row_map ? row_map[r] : r / rows_per_batch (row_map: device int32 [rows] or NULL; per-token timestep groups of image-to-video). */

@@ -265,6 +265,32 @@ def rope_tables_1d(T, dim=3840, theta=10000.0, max_pos=4096):
     return cos, sin
 
 
+def audio_positions(T_a):
+    """``createAudioPositionGrid`` (LTXRoPE.swift:627-655): seconds of the middle of each audio latent frame, f32 [T_a]."""
+    out = np.empty(int(T_a), dtype=np.float32)
+    _check(lib.ltx_audio_positions(int(T_a), out.ctypes.data))
+    return out
+
+
+def video_temporal_positions(F, H, W, fps=24.0):
+    """Row 0 of ``createPositionGrid``: the temporal coordinate of every video token in token order, f32 [F*H*W]."""
+    out = np.empty(F * H * W, dtype=np.float32)
+    _check(lib.ltx_video_temporal_positions(F, H, W, float(fps), out.ctypes.data))
+    return out
+
+
+def rope_tables_positions(positions, dim, theta=10000.0, max_pos=20):
+    """``precomputeFreqsCis`` (f64 path) over one real-valued position per token: cos, sin [T][dim/2] f32."""
+    pos = np.ascontiguousarray(positions, dtype=np.float32)
+    cos = np.empty((pos.size, dim // 2), dtype=np.float32)
+    sin = np.empty((pos.size, dim // 2), dtype=np.float32)
+    _check(lib.ltx_rope_tables_positions(pos.ctypes.data, pos.size, dim, theta, max_pos, cos.ctypes.data, sin.ctypes.data))
+    return cos, sin
+
+
+ATTN_QUERY_PRESCALE_64 = float(np.float32(0.125) * np.float32(1.4426950408889634))  # csrc/attention.h kAttnQueryPrescale64
+
+
 # ---------------------------------------------------------------------------------------------------------------
 # device context
 # ---------------------------------------------------------------------------------------------------------------
@@ -798,6 +824,56 @@ class Context:
     def attention_key_splits(B, H, Tq, Tk):
         """Key ranges the attention launcher divides a launch of this shape into (1 = no split)."""
         return lib.ltx_attention_key_splits(B, H, Tq, Tk)
+
+    def op_attention_hd(self, Q, K, Vt, bias, H, O, head_dim, scale=None):
+        """``ltx_op_attention_hd``: Q / K / O [B][T][H*head_dim], Vt [B][H*head_dim][ldvt]; scale <= 0: Q is prescaled."""
+        B, Tq, _ = Q.shape
+        Tk = K.shape[1]
+        if scale is None:
+            scale = 1.0 / (float(head_dim) ** 0.5)
+        self._ck(lib.ltx_op_attention_hd(self._h, _ptr(Q), _ptr(K), _ptr(Vt), Vt.shape[2], _ptr(bias), B, H, Tq, Tk, head_dim, scale, _ptr(O)))
+
+    @staticmethod
+    def attention_hd_workgroup_queries(B, H, Tq, head_dim=64):
+        """Queries per workgroup the launcher picks for a head-dim-64 launch of this shape (256, 128 or 64)."""
+        return lib.ltx_attention_hd_workgroup_queries(B, H, Tq, head_dim)
+
+    def op_qknorm_rope_hd(self, x, w, cos, sin, T, out, head_dim, out_scale=1.0, eps=1e-6):
+        rows, D = out.shape
+        self._ck(lib.ltx_op_qknorm_rope_hd(self._h, _ptr(x), x.stride(0), _ptr(w), _ptr(cos), _ptr(sin), T, rows, D, head_dim, out_scale, eps,
+                                           _ptr(out)))
+
+    # ---- LTXAttention at head dim 64: the audio / cross-modal attention modules of the dual block ----
+    def attn_module_init_synthetic(self, index, query_dim, context_dim=0, heads=32, seed=4242):
+        self._ck(lib.ltx_attn_module_init_synthetic(self._h, index, query_dim, context_dim, heads, seed))
+
+    def attn_module_load(self, index, path, key_prefix, heads=32):
+        self._ck(lib.ltx_attn_module_load(self._h, index, str(path).encode(), key_prefix.encode(), heads))
+
+    def attn_module_unload(self, index):
+        self._ck(lib.ltx_attn_module_unload(self._h, index))
+
+    def attn_module_export_param(self, index, name):
+        """One resident parameter of module ``index`` as a flat f32 numpy array ("to_q.weight", ..., "k_norm.weight")."""
+        n = lib.ltx_attn_module_export_param(self._h, index, name.encode(), None, 0)
+        if n < 0:
+            raise LTXError(-n, lib.ltx_last_error(self._h).decode(errors="replace"))
+        out = np.empty(n, dtype=np.float32)
+        n2 = lib.ltx_attn_module_export_param(self._h, index, name.encode(), out.ctypes.data, n)
+        if n2 < 0:
+            raise LTXError(-n2, lib.ltx_last_error(self._h).decode(errors="replace"))
+        return out
+
+    def attn_module_forward_dev(self, index, x, out, context=None, q_tables=None, k_tables=None, key_bias=None):
+        """``ltx_attn_module_forward_dev``: x [B][Tq][Dq] f32, context [B][Tk][Dc] f32 or bf16 (None: self-attention), q_tables /
+        k_tables = (cos, sin) device tensors [rows][heads*32] f32 or None, key_bias [B][Tk] f32 or None, out [B][Tq][Dq] f32."""
+        B, Tq, _ = x.shape
+        Tk = Tq if context is None else context.shape[1]
+        qc, qs = q_tables if q_tables is not None else (None, None)
+        kc, ks = k_tables if k_tables is not None else (None, None)
+        self._ck(lib.ltx_attn_module_forward_dev(self._h, index, _ptr(x), _ptr(context), int(context is not None and context.element_size() == 2),
+                                                 B, Tq, Tk, _ptr(qc), _ptr(qs), 0 if qc is None else qc.shape[0], _ptr(kc), _ptr(ks),
+                                                 0 if kc is None else kc.shape[0], _ptr(key_bias), _ptr(out)))
 
     def op_norm_mod(self, x, scale, shift, out, norm_kind=0, eps=1e-6, round_norm_bf16=False):
         rows, D = x.shape

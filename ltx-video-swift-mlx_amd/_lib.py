@@ -195,6 +195,17 @@ SIGNATURES = {
     "ltx_audio_sample_count": (_l, [_i]),
     "ltx_audio_sample_rate": (_i, []),
     "ltx_write_wav": (_i, [C.c_char_p, _vp, _l, _i, _f]),
+    "ltx_audio_positions": (_i, [_i, _vp]),
+    "ltx_video_temporal_positions": (_i, [_i, _i, _i, _f, _vp]),
+    "ltx_rope_tables_positions": (_i, [_vp, _i, _i, _f, _i, _vp, _vp]),
+    "ltx_attn_module_init_synthetic": (_i, [_vp, _i, _i, _i, _i, _u64]),
+    "ltx_attn_module_load": (_i, [_vp, _i, C.c_char_p, C.c_char_p, _i]),
+    "ltx_attn_module_unload": (_i, [_vp, _i]),
+    "ltx_attn_module_export_param": (_l, [_vp, _i, C.c_char_p, _vp, _l]),
+    "ltx_attn_module_forward_dev": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp]),
+    "ltx_op_attention_hd": (_i, [_vp, _vp, _vp, _vp, _l, _vp, _i, _i, _i, _i, _i, _f, _vp]),
+    "ltx_attention_hd_workgroup_queries": (_i, [_i, _i, _i, _i]),
+    "ltx_op_qknorm_rope_hd": (_i, [_vp, _vp, _l, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _vp]),
     "ltx_op_conv1d": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _vp, _i, _f, _vp]),
     "ltx_op_conv_transpose1d": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _f, _vp]),
     "ltx_op_conv2d_causal": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp]),

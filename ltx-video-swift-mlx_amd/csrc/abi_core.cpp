@@ -4,6 +4,7 @@
 #include <vector>
 
 #include "abi_internal.h"
+#include "attn_module.h"
 #include "audio.h"
 #include "connector.h"
 #include "dist.h"
@@ -121,6 +122,7 @@ void ltx_ctx_destroy(ltx_ctx* ctx) {
     drop_model(&ctx->vae_encoder, vae_encoder_destroy);
     drop_model(&ctx->audio_vae, audio_vae_destroy);
     drop_model(&ctx->vocoder, vocoder_destroy);
+    for (AttnModule*& m : ctx->attn_modules) drop_model(&m, attn_module_destroy);
     if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
 }
@@ -193,6 +195,29 @@ int ltx_rope_tables_1d(int T, int dim, float theta, int max_pos, float* cos_out,
     if (!cos_out || !sin_out || T < 1 || dim < 2 || max_pos < 1) return LTX_ERR_INVALID_CONFIGURATION;
     std::vector<float> c, s;
     rope_tables_1d(T, dim, (double)theta, max_pos, &c, &s);
+    memcpy(cos_out, c.data(), c.size() * 4);
+    memcpy(sin_out, s.data(), s.size() * 4);
+    return LTX_OK;
+}
+
+int ltx_audio_positions(int T_a, float* out) {
+    if (!out || T_a < 1) return LTX_ERR_INVALID_CONFIGURATION;
+    const std::vector<float> p = audio_positions(T_a);
+    memcpy(out, p.data(), p.size() * 4);
+    return LTX_OK;
+}
+
+int ltx_video_temporal_positions(int F, int H, int W, float fps, float* out) {
+    if (!out || F < 1 || H < 1 || W < 1 || !(fps > 0.f)) return LTX_ERR_INVALID_CONFIGURATION;
+    const std::vector<float> p = video_temporal_positions(F, H, W, fps);
+    memcpy(out, p.data(), p.size() * 4);
+    return LTX_OK;
+}
+
+int ltx_rope_tables_positions(const float* positions, int T, int dim, float theta, int max_pos, float* cos_out, float* sin_out) {
+    if (!positions || !cos_out || !sin_out || T < 1 || dim < 2 || dim % 2 != 0 || max_pos < 1 || !(theta > 1.f)) return LTX_ERR_INVALID_CONFIGURATION;
+    std::vector<float> c, s;
+    rope_tables_positions(positions, T, dim, (double)theta, max_pos, &c, &s);
     memcpy(cos_out, c.data(), c.size() * 4);
     memcpy(sin_out, s.data(), s.size() * 4);
     return LTX_OK;

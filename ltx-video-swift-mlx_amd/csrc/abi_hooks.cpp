@@ -257,6 +257,30 @@ int ltx_op_attention(ltx_ctx* ctx, const uint16_t* Q, const uint16_t* K, const u
     });
 }
 
+int ltx_op_attention_hd(ltx_ctx* ctx, const uint16_t* Q, const uint16_t* K, const uint16_t* Vt, long ldvt, const float* bias, int B, int H,
+                        int Tq, int Tk, int head_dim, float scale, uint16_t* O) {
+    if (head_dim == 128) return ltx_op_attention(ctx, Q, K, Vt, ldvt, bias, B, H, Tq, Tk, scale, O);
+    return with_ctx(ctx, [&] {
+        LTX_REQUIRE(head_dim == 64, "ltx_op_attention_hd: head dim %d (64 or 128)", head_dim);
+        AttnArgs a;
+        const long D = (long)H * 64;
+        a.head_dim = 64;
+        a.Q = Q; a.ldq = D; a.q_bstride = (long)Tq * D;
+        a.K = K; a.ldk = D; a.k_bstride = (long)Tk * D;
+        a.Vt = Vt; a.ldvt = ldvt; a.vt_bstride = D * ldvt;
+        a.O = O; a.ldo = D; a.o_bstride = (long)Tq * D;
+        a.bias = bias; a.bias_bstride = Tk;
+        a.B = B; a.H = H; a.Tq = Tq; a.Tk = Tk; a.scale = scale;
+        a.q_prescaled = scale <= 0.f ? 1 : 0;
+        launch_attention(a, ctx->stream);
+    });
+}
+
+int ltx_attention_hd_workgroup_queries(int B, int H, int Tq, int head_dim) {
+    if (B < 1 || H < 1 || Tq < 1 || head_dim != 64) return 0;
+    return attn64_queries_per_workgroup(B, H, Tq);
+}
+
 int ltx_attention_key_splits(int B, int H, int Tq, int Tk) {
     if (B < 1 || H < 1 || Tq < 1 || Tk < 1) return 1;
     return attn_key_splits(B, H, Tq, Tk);
@@ -272,6 +296,11 @@ int ltx_op_norm_mod(ltx_ctx* ctx, const float* x, const float* scale, const floa
 int ltx_op_qknorm_rope(ltx_ctx* ctx, const float* x, long ldx, const float* w, const float* cos_t, const float* sin_t,
                        int T, int rows, int D, float eps, uint16_t* out) {
     return with_ctx(ctx, [&] { launch_qknorm_rope(x, ldx, w, cos_t, sin_t, T, out, D, rows, D, eps, ctx->stream); });
+}
+
+int ltx_op_qknorm_rope_hd(ltx_ctx* ctx, const float* x, long ldx, const float* w, const float* cos_t, const float* sin_t, int T, int rows,
+                          int D, int head_dim, float out_scale, float eps, uint16_t* out) {
+    return with_ctx(ctx, [&] { launch_qknorm_rope(x, ldx, w, cos_t, sin_t, T, out, D, rows, D, eps, ctx->stream, out_scale, false, head_dim); });
 }
 
 int ltx_op_norm_mod_ex(ltx_ctx* ctx, const float* x, long ldx, const float* scale, const float* shift, long mod_bstride,

@@ -7,6 +7,7 @@
 
 #include "abi_internal.h"
 #include "audio.h"
+#include "attn_module.h"
 #include "connector.h"
 #include "dist.h"
 #include "elementwise.h"
@@ -152,6 +153,12 @@ void fill_params(DenoiseParams& p, const ltx_denoise_options* o) {
     p.cond_noise = o->cond_noise;
     p.shard = o->shard;
     if (sz >= offsetof(ltx_denoise_options, step_stats) + sizeof(o->step_stats)) p.step_stats = o->step_stats;
+}
+
+// the context's slot of attention module `index` (attn_module.h)
+AttnModule** attn_slot(ltx_ctx* ctx, int index) {
+    LTX_REQUIRE(index >= 0 && index < kAttnModuleSlots, "attention module index %d outside 0 .. %d", index, kAttnModuleSlots - 1);
+    return &ctx->attn_modules[index];
 }
 
 }  // namespace
@@ -783,6 +790,58 @@ int ltx_audio_decode(ltx_ctx* ctx, const float* latent, int T, float* waveform) 
         const float* d_latent = audio_stage_in(ctx, latent, (size_t)8 * T * 16, waveform, n_wave);
         audio_decode_body(ctx, d_latent, T, ctx->h2d[H2D_OUT].as<float>());
         audio_stage_out(ctx, waveform, n_wave);
+    });
+}
+
+/* ---- LTXAttention at head dim 64: the audio / cross-modal attention modules of the dual block (attn_module.h) ---- */
+int ltx_attn_module_init_synthetic(ltx_ctx* ctx, int index, int query_dim, int context_dim, int heads, uint64_t seed) {
+    return with_ctx(ctx, [&] {
+        replace_model(ctx, attn_slot(ctx, index), [&] { return attn_module_create(query_dim, context_dim > 0 ? context_dim : query_dim, heads); },
+                      [&](AttnModule* m) { attn_module_init_synthetic(ctx, m, seed); }, attn_module_destroy);
+    });
+}
+int ltx_attn_module_load(ltx_ctx* ctx, int index, const char* path, const char* key_prefix, int heads) {
+    if (!ctx || !path || !key_prefix) return LTX_ERR_INVALID_CONFIGURATION;
+    return guarded(ctx, [&] {
+        AttnModule** slot = attn_slot(ctx, index);
+        int Dq = 0, Dc = 0, inner = 0;
+        attn_module_file_shape(path, key_prefix, &Dq, &Dc, &inner);
+        LTX_REQUIRE(heads >= 1 && (long)heads * 64 == inner, "ltx_attn_module_load: %d heads of 64 do not make the file's inner dim %d (%sto_q)", heads,
+                    inner, key_prefix);
+        replace_model(ctx, slot, [&] { return attn_module_create(Dq, Dc, heads); },
+                      [&](AttnModule* m) { attn_module_load(ctx, m, path, key_prefix); }, attn_module_destroy);
+    });
+}
+int ltx_attn_module_unload(ltx_ctx* ctx, int index) {
+    return with_ctx(ctx, [&] { unload_model(ctx, attn_slot(ctx, index), attn_module_destroy); });
+}
+long ltx_attn_module_export_param(ltx_ctx* ctx, int index, const char* name, float* out, long cap) {
+    if (!ctx || !name) return -LTX_ERR_INVALID_CONFIGURATION;
+    long n = 0;
+    const int rc = guarded(ctx, [&] {
+        AttnModule* m = need(*attn_slot(ctx, index), kNoAttnModule);
+        auto it = m->slots.find(name);
+        LTX_REQUIRE(it != m->slots.end(), "ltx_attn_module_export_param: no parameter '%s'", name);
+        n = it->second.numel;
+        if (!out) return;
+        LTX_REQUIRE(cap >= n, "ltx_attn_module_export_param: buffer too small (%ld < %ld)", cap, n);
+        attn_module_export(ctx, m, it->second, out);
+    });
+    return rc == 0 ? n : -rc;
+}
+int ltx_attn_module_forward_dev(ltx_ctx* ctx, int index, const float* x, const void* context, int context_bf16, int B, int Tq, int Tk,
+                                const float* q_cos, const float* q_sin, int q_table_rows, const float* k_cos, const float* k_sin,
+                                int k_table_rows, const float* key_bias, float* out) {
+    return with_ctx(ctx, [&] {
+        AttnModule* m = need(*attn_slot(ctx, index), kNoAttnModule);
+        AttnModuleArgs a;
+        a.x = x; a.context = context; a.context_bf16 = context_bf16;
+        a.B = B; a.Tq = Tq; a.Tk = Tk;
+        a.q_cos = q_cos; a.q_sin = q_sin; a.q_rows = q_table_rows;
+        a.k_cos = k_cos; a.k_sin = k_sin; a.k_rows = k_table_rows;
+        a.key_bias = key_bias;
+        a.out = out;
+        attn_module_forward(ctx, m, a);
     });
 }
 

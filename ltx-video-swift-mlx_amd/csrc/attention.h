@@ -3,7 +3,7 @@
 #include "common.h"
 
 struct AttnArgs {
-    const bf16_t* Q = nullptr;   // [B][Tq][ldq], head h occupies columns h*128 .. h*128+127
+    const bf16_t* Q = nullptr;   // [B][Tq][ldq], head h occupies columns h*128 .. h*128+127 (h*64 .. h*64+63 at head_dim 64)
     long ldq = 0, q_bstride = 0;
     const bf16_t* K = nullptr;   // [B][Tk][ldk]
     long ldk = 0, k_bstride = 0;
@@ -14,6 +14,10 @@ struct AttnArgs {
     const float* bias = nullptr;  // optional additive key mask [B][Tk] (reference: (1-m)*-10000, LTXTransformer.swift:141-156)
     long bias_bstride = 0;
     int B = 0, H = 0, Tq = 0, Tk = 0;
+    // 128: the kernels above all, unchanged. 64 (the LTX-2 audio / cross-modal attention, 32 heads x 64): attn64_fwd_kernel; the same
+    // layouts with 64 in place of 128 (Vt is [B][H*64][ldvt]), any Tq / Tk, bias and q_prescaled as at 128, never key-split (the
+    // workspace fields are ignored). The caller sets `scale` (1/8 at head dim 64).
+    int head_dim = 128;
     float scale = 0.08838834764831845f;  // 1/sqrt(128)
     // 1: Q already carries scale * log2(e) (written so by qknorm_rope's out_scale, one rounding to bf16): the scores ARE the base-2
     // exponents and `scale` is ignored. The assembly kernel then runs a stream without its 48 v_mul per key tile; the other
@@ -36,5 +40,10 @@ long attn_split_ws_bytes(int B, int H, int Tq, int Tk);
 int attn_key_splits(int B, int H, int Tq, int Tk);  // the number of key ranges (1 = no split)
 // what a producer multiplies q by for q_prescaled: (1 / sqrt(128)) * log2(e)
 constexpr float kAttnQueryPrescale = 0.08838834764831845f * 1.4426950408889634f;
+// the same for head dim 64: (1 / sqrt(64)) * log2(e)
+constexpr float kAttnQueryPrescale64 = 0.125f * 1.4426950408889634f;
+
+// head dim 64: queries per workgroup the launcher picks for a launch of this shape (256, 128 or 64)
+int attn64_queries_per_workgroup(int B, int H, int Tq);
 
 void launch_attention(const AttnArgs& args, hipStream_t stream);

@@ -1,4 +1,4 @@
-// attention.hip - flash-style non-causal attention forward for gfx950, head_dim = 128, bf16 in / f32 softmax.
+// attention.hip - flash-style non-causal attention forward for gfx950, head_dim = 128 (and 64: attn64_fwd_kernel), bf16 in / f32 softmax.
 //
 // Replaces the reference's MLXFast.scaledDotProductAttention call (LTXAttention.swift:207-211): self-attention
 // over the spatio-temporal video tokens and cross-attention over the projected caption keys with an additive
@@ -906,7 +906,266 @@ __global__ __launch_bounds__(256, 1) void attn_fwd_kernel_x32_asm(const AttnArgs
 
 #endif  // LTX_EXPERIMENTS
 
+// ---------------------------------------------------------------------------------------------------------------
+// Head dim 64 (LTXAttention at 32 heads x 64: the audio stream's self / text-cross attention and the two cross-modal attentions of the
+// dual block, LTXConfig.swift:134-135, LTX2TransformerBlock.swift:133-163). Plain HIP C++ on v_mfma_f32_16x16x32_bf16, the operand
+// mapping of the 48-query kernel above with half the head dim:
+//   S^T = K Q^T : key block kb (16 keys) x query block qb (16 queries), the head dim is TWO k-steps of 32
+//   O^T = Vt P^T: d-block db (16 of the 64 channels) x query block qb, a 64-key tile is two k-steps of 32
+// A/B lane (c16 = lane&15, g = lane>>4) holds k = 8g .. 8g+7 of row / column c16; C lane (c16, g) holds rows 4g .. 4g+3 of column c16.
+// MFMA row rho of key block kb reads tile key 32*(kb>>1) + 4*(kb&1) + 8*(rho>>2) + (rho&3), so a lane's 4 + 4 scores of blocks
+// (2i, 2i+1) are the 8 consecutive keys 32i + 8g .. +7: the B operand of the PV product's k-step i, P never leaves registers.
+// The PV accumulator is 4 d-blocks per query block (8 at head dim 128), so a wave carries NQB = 4 query blocks = 64 queries in the
+// registers the 48-query kernel needs for 48, 256 queries per workgroup: every K / Vt fragment read from LDS feeds four MFMAs.
+// Launches with few queries (the audio stream as the query side: a few dozen to 126 rows on 32 heads) take NQB = 1 or 2, more and
+// lighter workgroups, chosen by grid fill in launch_attention_d64.
+// LDS: K tile [64 keys][64 d] and Vt tile [64 d][64 keys] are both 64 rows of 128 B (two rows per 256-B bank row), staged by LDS-DMA
+// with the swizzle on the source address: physical 16-B chunk p of key k holds logical chunk p ^ (2*((k>>3)&3) | ((k>>1)&1)) - the key
+// bits that differ between the 16 rows of one fragment read besides the half-row bit - and of Vt row d chunk p ^ ((d>>1)&7). Both
+// fragment reads are conflict-free under the ds_read_b128 lane groups. Two stages of 16 KB, one barrier per key tile.
+// ---------------------------------------------------------------------------------------------------------------
+constexpr int D64_TILE_BYTES = 64 * 128;
+constexpr int D64_STAGE_BYTES = 2 * D64_TILE_BYTES;
+constexpr int D64_LDS = 2 * D64_STAGE_BYTES;
+LTX_DEVFN int d64_key_swizzle(int key) { return (((key >> 3) & 3) << 1) | ((key >> 1) & 1); }
+
+template <int NQB, bool HAS_BIAS>
+__global__ __launch_bounds__(256, NQB >= 4 ? 1 : 2) void attn64_fwd_kernel(const AttnArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int c16 = lane & 15, g = lane >> 4;
+    constexpr int WG_Q = 64 * NQB;
+    const AttnBlock blk = attn_block((a.Tq + WG_Q - 1) / WG_Q, a.H, a.B, a.plain_order);
+    const int head = blk.head, b = blk.b;
+    const bf16_t* Qb = a.Q + (long)b * a.q_bstride + head * 64;
+    const bf16_t* Kb = a.K + (long)b * a.k_bstride + head * 64;
+    const bf16_t* Vb = a.Vt + (long)b * a.vt_bstride + (long)head * 64 * a.ldvt;
+    const float* biasb = HAS_BIAS ? a.bias + (long)b * a.bias_bstride : nullptr;
+    const int q0 = blk.x * WG_Q + wave * 16 * NQB;
+
+    // Q fragments (B operand of S^T): lane (c16, g) holds Q[q = c16][d = 32*ks + 8g + j]; rows past Tq read row Tq-1 and are not stored
+    s16x8 qf[NQB][2];
+#pragma unroll
+    for (int qb = 0; qb < NQB; ++qb) {
+        const int qi = q0 + 16 * qb + c16;
+        const bf16_t* qrow = Qb + (long)(qi < a.Tq ? qi : a.Tq - 1) * a.ldq + g * 8;
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) qf[qb][ks] = *(const s16x8*)(qrow + ks * 32);
+    }
+
+    // staging: a tile is 8 wave-instructions of 1 KB (8 rows x 128 B); wave w issues pieces w and w + 4 of each operand. Keys past Tk
+    // read key Tk-1 (their scores are masked below); Vt columns up to roundup(Tk, 64) exist by the launcher's check.
+    const int st_row = lane >> 3, st_pch = lane & 7;
+    const bf16_t* v_src[2];
+    int k_row[2], k_col[2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const int row = (wave + 4 * i) * 8 + st_row;
+        k_row[i] = row;
+        k_col[i] = (st_pch ^ d64_key_swizzle(row)) << 3;
+        v_src[i] = Vb + (long)row * a.ldvt + ((st_pch ^ ((row >> 1) & 7)) << 3);
+    }
+    auto stage = [&](int s, int t) {
+        char* kbuf = smem + s * D64_STAGE_BYTES;
+        char* vbuf = kbuf + D64_TILE_BYTES;
+        const int k0 = t * KV_TILE;
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            int gk = k0 + k_row[i];
+            gk = gk < a.Tk ? gk : a.Tk - 1;
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(Kb + (long)gk * a.ldk + k_col[i]),
+                                             (__attribute__((address_space(3))) void*)(kbuf + (wave + 4 * i) * 1024), 16, 0, 0);
+        }
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(v_src[i] + k0),
+                                             (__attribute__((address_space(3))) void*)(vbuf + (wave + 4 * i) * 1024), 16, 0, 0);
+    };
+
+    // fragment addresses (block 0; blocks are compile-time offsets): K row of MFMA row c16, Vt row c16 of a 16-row d-block
+    const int kf_key = 8 * (c16 >> 2) + (c16 & 3);
+    const int kf_row = kf_key * 128, kf_sw = d64_key_swizzle(kf_key);
+    const int vf_row = c16 * 128, vf_sw = (c16 >> 1) & 7;
+
+    f32x4 o[4][NQB];
+#pragma unroll
+    for (int db = 0; db < 4; ++db)
+#pragma unroll
+        for (int qb = 0; qb < NQB; ++qb) o[db][qb] = f32x4{0.f, 0.f, 0.f, 0.f};
+    float m_run[NQB], l_run[NQB];
+#pragma unroll
+    for (int qb = 0; qb < NQB; ++qb) {
+        m_run[qb] = -INFINITY;
+        l_run[qb] = 0.f;
+    }
+    const float LOG2E = 1.4426950408889634f;
+    const float c = HAS_BIAS ? LOG2E : a.scale * LOG2E;  // masked: the scores are scaled when the bias is added (reference units)
+
+    const int nt = (a.Tk + KV_TILE - 1) / KV_TILE;
+    stage(0, 0);
+    __syncthreads();
+    for (int t = 0; t < nt; ++t) {
+        const int cur = t & 1;
+        if (t + 1 < nt) stage(cur ^ 1, t + 1);
+        const char* kbuf = smem + cur * D64_STAGE_BYTES;
+        const char* vbuf = kbuf + D64_TILE_BYTES;
+        const int k0 = t * KV_TILE;
+
+        // S^T = K Q^T: four 16-key blocks, two k-steps over the head dim
+        f32x4 s[4][NQB];
+#pragma unroll
+        for (int kb = 0; kb < 4; ++kb) {
+#pragma unroll
+            for (int qb = 0; qb < NQB; ++qb) s[kb][qb] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks) {
+                const s16x8 kf = *(const s16x8*)(kbuf + (32 * (kb >> 1) + 4 * (kb & 1)) * 128 + kf_row + ((((ks << 2) + g) ^ kf_sw) << 4));
+#pragma unroll
+                for (int qb = 0; qb < NQB; ++qb)
+                    s[kb][qb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, kf), __builtin_bit_cast(bf16x8_t, qf[qb][ks]),
+                                                                        s[kb][qb], 0, 0, 0);
+            }
+        }
+        // this lane's score (kb, j) is key k0 + 32*(kb>>1) + 4*(kb&1) + 8g + j, the same 16 keys for every query block
+        float bv[4][4];
+        if constexpr (HAS_BIAS) {
+#pragma unroll
+            for (int kb = 0; kb < 4; ++kb)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    int key = k0 + 32 * (kb >> 1) + 4 * (kb & 1) + 8 * g + j;
+                    key = key < a.Tk ? key : a.Tk - 1;
+                    bv[kb][j] = biasb[key];
+                }
+        }
+        const bool ragged = k0 + KV_TILE > a.Tk;
+        s16x8 pf[NQB][2];
+#pragma unroll
+        for (int qb = 0; qb < NQB; ++qb) {
+            if constexpr (HAS_BIAS) {
+#pragma unroll
+                for (int kb = 0; kb < 4; ++kb)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) s[kb][qb][j] = s[kb][qb][j] * a.scale + bv[kb][j];
+            }
+            if (ragged) {
+#pragma unroll
+                for (int kb = 0; kb < 4; ++kb)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+                        if (k0 + 32 * (kb >> 1) + 4 * (kb & 1) + 8 * g + j >= a.Tk) s[kb][qb][j] = -INFINITY;
+            }
+            float mloc = s[0][qb][0];
+#pragma unroll
+            for (int kb = 0; kb < 4; ++kb)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) mloc = fmaxf(mloc, s[kb][qb][j]);
+            mloc = fmaxf(mloc, __shfl_xor(mloc, 16, 64));
+            mloc = fmaxf(mloc, __shfl_xor(mloc, 32, 64));
+            // key 0 of every tile exists, so the column's maximum is finite from the first tile on
+            const float m_new = fmaxf(m_run[qb], mloc);
+            const float alpha = __builtin_amdgcn_exp2f((m_run[qb] - m_new) * c);
+            m_run[qb] = m_new;
+            const float nmc = -m_new * c;
+            float psum = 0.f;
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                s16x8 pk;
+#pragma unroll
+                for (int hh = 0; hh < 2; ++hh)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const float p = __builtin_amdgcn_exp2f(__builtin_fmaf(s[2 * i + hh][qb][j], c, nmc));
+                        psum += p;
+                        pk[4 * hh + j] = (short)f32_to_bf16(p);
+                    }
+                pf[qb][i] = pk;
+            }
+            l_run[qb] = l_run[qb] * alpha + psum;
+            if (__builtin_amdgcn_ballot_w64(alpha != 1.0f) != 0) {  // some column's maximum moved; skipped when none did, the common case after the first tiles
+#pragma unroll
+                for (int db = 0; db < 4; ++db) o[db][qb] *= alpha;
+            }
+        }
+        // O^T += Vt P^T: four 16-channel blocks, two k-steps of 32 keys
+#pragma unroll
+        for (int db = 0; db < 4; ++db)
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                const s16x8 vf = *(const s16x8*)(vbuf + db * 16 * 128 + vf_row + ((((i << 2) + g) ^ vf_sw) << 4));
+#pragma unroll
+                for (int qb = 0; qb < NQB; ++qb)
+                    o[db][qb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, vf), __builtin_bit_cast(bf16x8_t, pf[qb][i]),
+                                                                        o[db][qb], 0, 0, 0);
+            }
+        __syncthreads();
+    }
+
+    // epilogue: register j of o[db][qb] is channel 16*db + 4g + j of query q0 + 16*qb + c16; rows past Tq are not written
+#pragma unroll
+    for (int qb = 0; qb < NQB; ++qb) {
+        float l = l_run[qb];
+        l += __shfl_xor(l, 16, 64);
+        l += __shfl_xor(l, 32, 64);
+        const float inv = 1.0f / l;
+        const int qi = q0 + 16 * qb + c16;
+        if (qi < a.Tq) {
+            bf16_t* orow = a.O + (long)b * a.o_bstride + (long)qi * a.ldo + head * 64;
+#pragma unroll
+            for (int db = 0; db < 4; ++db) {
+                uint2 pk;
+                pk.x = pack_bf16x2(o[db][qb][0] * inv, o[db][qb][1] * inv);
+                pk.y = pack_bf16x2(o[db][qb][2] * inv, o[db][qb][3] * inv);
+                *(uint2*)(orow + db * 16 + g * 4) = pk;
+            }
+        }
+    }
+}
+
+template <int NQB>
+void launch_attn64(const AttnArgs& a, hipStream_t stream) {
+    static PerDeviceOnce attr_set;
+    attr_set.run([&] {
+        HIP_CHECK(hipFuncSetAttribute((const void*)attn64_fwd_kernel<NQB, false>, hipFuncAttributeMaxDynamicSharedMemorySize, D64_LDS));
+        HIP_CHECK(hipFuncSetAttribute((const void*)attn64_fwd_kernel<NQB, true>, hipFuncAttributeMaxDynamicSharedMemorySize, D64_LDS));
+    });
+    const dim3 grid(((a.Tq + 64 * NQB - 1) / (64 * NQB)) * a.H * a.B);
+    if (a.bias)
+        hipLaunchKernelGGL((attn64_fwd_kernel<NQB, true>), grid, dim3(256), D64_LDS, stream, a);
+    else
+        hipLaunchKernelGGL((attn64_fwd_kernel<NQB, false>), grid, dim3(256), D64_LDS, stream, a);
+    HIP_CHECK(hipGetLastError());
+}
+
 }  // namespace
+
+// Head dim 64: the workgroup size by grid fill. 256 queries per workgroup when that still gives every second CU a workgroup (the
+// a2v launch: 1536 video queries x 32 heads = 192 workgroups); otherwise 128, then 64 queries per workgroup, so that the launches
+// whose queries are the audio tokens (26 .. 126 rows x 32 heads against up to 1536 keys) become 32 .. 64 light workgroups instead
+// of 32 heavy ones. They are not key-split: see DESIGN.md, "audio / cross-modal attention".
+int attn64_queries_per_workgroup(int B, int H, int Tq) {
+    for (int nqb = 4; nqb > 1; nqb >>= 1)
+        if ((long)((Tq + 64 * nqb - 1) / (64 * nqb)) * H * B >= 128) return 64 * nqb;
+    return 64;
+}
+static void launch_attention_d64(AttnArgs a, hipStream_t stream) {
+    if (a.q_prescaled) a.scale = 0.6931471805599453f;  // as at head dim 128: exp2(score * scale * log2(e)) with the factor already in Q
+    if (ltx_opt(OPT_ATTN_PLAIN_ORDER) != 0) a.plain_order = 1;
+    LTX_REQUIRE(a.B > 0 && a.H > 0 && a.Tq > 0 && a.Tk > 0, "attention: empty problem");
+    LTX_REQUIRE(a.ldq % 8 == 0 && a.ldk % 8 == 0 && a.ldvt % 8 == 0 && a.ldo % 4 == 0, "attention: leading dims");
+    LTX_REQUIRE(a.ldq >= a.H * 64 && a.ldk >= a.H * 64 && a.ldo >= a.H * 64, "attention: row strides must cover %d heads of 64", a.H);
+    LTX_REQUIRE(a.ldvt >= ((a.Tk + 63) / 64) * 64, "attention: Vt row stride %ld must cover Tk=%d rounded up to 64", a.ldvt, a.Tk);
+    LTX_REQUIRE(((uintptr_t)a.Q & 15) == 0 && ((uintptr_t)a.K & 15) == 0 && ((uintptr_t)a.Vt & 15) == 0 && ((uintptr_t)a.O & 7) == 0,
+                "attention: pointer alignment");
+    LTX_REQUIRE(a.q_bstride % 8 == 0 && a.k_bstride % 8 == 0 && a.vt_bstride % 8 == 0 && a.o_bstride % 4 == 0, "attention: batch strides");
+    ProfScope prof(PROF_ATTN, 4.0 * a.B * a.H * (double)a.Tq * a.Tk * 64, stream);
+    switch (attn64_queries_per_workgroup(a.B, a.H, a.Tq)) {
+        case 256: launch_attn64<4>(a, stream); break;
+        case 128: launch_attn64<2>(a, stream); break;
+        default: launch_attn64<1>(a, stream); break;
+    }
+}
 
 // Key split of a launch of the 48-query kernel: only when its (query block, head, batch) workgroups leave most of the chip idle and
 // every range still has two key tiles; at most 8 ranges (attn_combine_kernel's register array), as many as fill 256 CUs.
@@ -935,6 +1194,8 @@ long attn_split_ws_bytes(int B, int H, int Tq, int Tk) { return attn_split_plan(
 int attn_key_splits(int B, int H, int Tq, int Tk) { return attn_split_plan(B, H, Tq, Tk).splits; }
 
 void launch_attention(const AttnArgs& a_in, hipStream_t stream) {
+    if (a_in.head_dim == 64) return launch_attention_d64(a_in, stream);
+    LTX_REQUIRE(a_in.head_dim == 128, "attention: head dim %d (64 or 128)", a_in.head_dim);
     AttnArgs a = a_in;
     // q_prescaled: every kernel but the prescaled assembly stream computes exp2(score * scale * log2(e)); with Q carrying
     // scale * log2(e) already that factor must be 1, i.e. scale = ln 2

@@ -1,0 +1,235 @@
+// attn_module.cpp - see attn_module.h.
+#include "attn_module.h"
+
+#include <vector>
+
+#include "attention.h"
+#include "elementwise.h"
+#include "gemm.h"
+#include "linear_ops.h"
+
+namespace {
+struct Pending {
+    const char* key;
+    void** dst;
+    int kind;
+    long rows, cols;
+};
+long slot_bytes(int kind, long numel) { return numel * (kind == SLOT_BF16 ? 2 : 4); }
+
+// the file's spelling of a module key (ModelDownloader.swift:756-803 maps the other way)
+std::string file_spelling(const std::string& key) {
+    if (key.compare(0, 7, "to_out.") == 0) return "to_out.0." + key.substr(7);
+    if (key.compare(0, 7, "q_norm.") == 0) return "norm_q." + key.substr(7);
+    if (key.compare(0, 7, "k_norm.") == 0) return "norm_k." + key.substr(7);
+    return key;
+}
+const StTensor* find_tensor(const SafeTensors& st, const std::string& prefix, const std::string& key) {
+    auto it = st.tensors.find(prefix + key);
+    if (it == st.tensors.end()) it = st.tensors.find(prefix + file_spelling(key));
+    return it == st.tensors.end() ? nullptr : &it->second;
+}
+}  // namespace
+
+AttnModule* attn_module_create(int query_dim, int context_dim, int heads) {
+    if (heads < 1 || heads > 128 || query_dim < 64 || context_dim < 64 || query_dim % 64 != 0 || context_dim % 64 != 0 || query_dim > 8192 ||
+        context_dim > 8192)
+        LTX_THROW(LTXS_INVALID_CONFIGURATION, "attention module: query_dim %d / context_dim %d must be multiples of 64 up to 8192, heads %d in 1 .. 128",
+                  query_dim, context_dim, heads);
+    AttnModule* m = new AttnModule();
+    m->heads = heads;
+    m->inner = heads * 64;
+    m->Dq = query_dim;
+    m->Dc = context_dim;
+    const long I = m->inner, Dq = query_dim, Dc = context_dim;
+    m->q.out = m->k.out = m->v.out = (int)I;
+    m->q.in = (int)Dq;
+    m->k.in = m->v.in = (int)Dc;
+    m->o.out = (int)Dq;
+    m->o.in = (int)I;
+    const Pending pend[] = {
+        {"to_q.weight", (void**)&m->q.w, SLOT_BF16, I, Dq},     {"to_q.bias", (void**)&m->q.b, SLOT_F32, I, 0},
+        {"to_k.weight", (void**)&m->k.w, SLOT_BF16, I, Dc},     {"to_k.bias", (void**)&m->k.b, SLOT_F32, I, 0},
+        {"to_v.weight", (void**)&m->v.w, SLOT_BF16, I, Dc},     {"to_v.bias", (void**)&m->v.b, SLOT_F32, I, 0},
+        {"to_out.weight", (void**)&m->o.w, SLOT_BF16, Dq, I},   {"to_out.bias", (void**)&m->o.b, SLOT_F32, Dq, 0},
+        {"q_norm.weight", (void**)&m->qn, SLOT_F32, I, 0},      {"k_norm.weight", (void**)&m->kn, SLOT_F32, I, 0},
+    };
+    size_t total = 0;
+    for (const Pending& p : pend) total += DeviceArena::padded(slot_bytes(p.kind, p.rows * (p.cols ? p.cols : 1)));
+    try {
+        m->arena.reserve(total + 256);
+        HIP_CHECK(hipMemset(m->arena.buf.p, 0, m->arena.buf.bytes));
+        for (const Pending& p : pend) {
+            ParamSlot s;
+            s.kind = p.kind;
+            s.rows = p.rows;
+            s.cols = p.cols;
+            s.numel = p.rows * (p.cols ? p.cols : 1);
+            s.dst = *p.dst = m->arena.take(slot_bytes(p.kind, s.numel));
+            m->slots[p.key] = s;
+        }
+    } catch (...) {
+        delete m;
+        throw;
+    }
+    return m;
+}
+
+void attn_module_destroy(AttnModule* m) { delete m; }
+
+void attn_module_init_synthetic(ltx_ctx* ctx, AttnModule* m, uint64_t seed) {
+    uint64_t k = 0;
+    for (auto& kv : m->slots) {
+        ParamSlot& s = kv.second;
+        const uint64_t sd = seed * 0x9E3779B97F4A7C15ull + (++k) * 0xD1B54A32D192ED03ull;
+        const bool is_norm = kv.first.find("_norm.") != std::string::npos;
+        if (s.kind == SLOT_BF16)
+            launch_fill_normal_bf16((bf16_t*)s.dst, s.numel, sd, 0.f, 0.02f, ctx->stream);
+        else
+            launch_fill_normal_f32((float*)s.dst, s.numel, sd, is_norm ? 1.0f : 0.f, is_norm ? 0.02f : 0.01f, 1, ctx->stream);
+        s.loaded = true;
+    }
+    HIP_CHECK(hipStreamSynchronize(ctx->stream));
+}
+
+void attn_module_file_shape(const std::string& path, const std::string& prefix, int* query_dim, int* context_dim, int* inner) {
+    SafeTensors st;
+    st.open(path);
+    const StTensor* wq = find_tensor(st, prefix, "to_q.weight");
+    const StTensor* wk = find_tensor(st, prefix, "to_k.weight");
+    if (!wq || !wk || wq->shape.size() != 2 || wk->shape.size() != 2)
+        LTX_THROW(LTXS_WEIGHT_LOADING_FAILED, "Failed to load weights: no attention module under '%s' in %s", prefix.c_str(), path.c_str());
+    if (wq->shape[0] != wk->shape[0] || wq->shape[0] > 8192 || wq->shape[1] > 8192 || wk->shape[1] > 8192)
+        LTX_THROW(LTXS_WEIGHT_LOADING_FAILED, "Failed to load weights: %sto_q [%ld, %ld] and to_k [%ld, %ld] do not form one module", prefix.c_str(),
+                  wq->shape[0], wq->shape[1], wk->shape[0], wk->shape[1]);
+    *inner = (int)wq->shape[0];
+    *query_dim = (int)wq->shape[1];
+    *context_dim = (int)wk->shape[1];
+}
+
+void attn_module_load(ltx_ctx* ctx, AttnModule* m, const std::string& path, const std::string& prefix) {
+    SafeTensors st;
+    st.open(path);
+    ctx->n_loaded = ctx->n_missing = ctx->n_unmatched = 0;
+    std::vector<uint8_t> staging;
+    for (auto& kv : m->slots) {
+        ParamSlot& s = kv.second;
+        s.loaded = false;
+        const StTensor* t = find_tensor(st, prefix, kv.first);
+        if (!t) LTX_THROW(LTXS_WEIGHT_LOADING_FAILED, "Failed to load weights: %s%s is not in %s", prefix.c_str(), kv.first.c_str(), path.c_str());
+        const bool shape_ok = s.cols ? (t->shape.size() == 2 && t->shape[0] == s.rows && t->shape[1] == s.cols) : t->numel() == s.numel;
+        if (!shape_ok)
+            LTX_THROW(LTXS_WEIGHT_LOADING_FAILED, "Failed to load weights: %s%s has %ld elements, expected [%ld, %ld]", prefix.c_str(), kv.first.c_str(),
+                      t->numel(), s.rows, s.cols);
+        if (s.kind == SLOT_BF16) {
+            staging.resize((size_t)s.numel * 2);
+            st_to_bf16(st, *t, (bf16_t*)staging.data());
+        } else {  // biases and norm weights are bf16 in the file: f32 copies of those values
+            staging.resize((size_t)s.numel * 4);
+            float* f = (float*)staging.data();
+            st_to_f32(st, *t, f);
+            for (long i = 0; i < s.numel; ++i) f[i] = host_bf16_to_f32(host_f32_to_bf16(f[i]));
+        }
+        HIP_CHECK(hipMemcpy(s.dst, staging.data(), staging.size(), hipMemcpyHostToDevice));
+        s.loaded = true;
+        ctx->n_loaded++;
+    }
+}
+
+void attn_module_export(ltx_ctx* ctx, AttnModule* m, const ParamSlot& s, float* out) {
+    (void)m;
+    HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    if (s.kind == SLOT_F32) {
+        HIP_CHECK(hipMemcpy(out, s.dst, (size_t)s.numel * 4, hipMemcpyDeviceToHost));
+        return;
+    }
+    std::vector<bf16_t> h((size_t)s.numel);
+    HIP_CHECK(hipMemcpy(h.data(), s.dst, (size_t)s.numel * 2, hipMemcpyDeviceToHost));
+    for (long i = 0; i < s.numel; ++i) out[i] = host_bf16_to_f32(h[i]);
+}
+
+void attn_module_forward(ltx_ctx* ctx, AttnModule* m, const AttnModuleArgs& a) {
+    // every check comes before the first launch
+    if (!a.x || !a.out || a.B < 1 || a.Tq < 1 || a.Tk < 1 || a.B > 64 || a.Tq > (1 << 20) || a.Tk > (1 << 20))
+        LTX_THROW(LTXS_INVALID_CONFIGURATION, "attention module: bad arguments (B=%d Tq=%d Tk=%d)", a.B, a.Tq, a.Tk);
+    if (!a.context && (a.Tk != a.Tq || m->Dc != m->Dq || a.context_bf16))
+        LTX_THROW(LTXS_INVALID_CONFIGURATION, "attention module: self-attention needs Tk == Tq (%d, %d), context_dim == query_dim (%d, %d) and f32 rows",
+                  a.Tk, a.Tq, m->Dc, m->Dq);
+    if ((a.q_cos == nullptr) != (a.q_sin == nullptr) || (a.k_cos == nullptr) != (a.k_sin == nullptr) || (a.k_cos && !a.q_cos))
+        LTX_THROW(LTXS_INVALID_CONFIGURATION, "attention module: cos and sin tables come in pairs, and key tables only with query tables");
+    if (a.q_cos && a.q_rows < a.Tq)
+        LTX_THROW(LTXS_INVALID_CONFIGURATION, "attention module: the query RoPE tables have %d rows for Tq = %d", a.q_rows, a.Tq);
+    if (a.q_cos && (a.k_cos ? a.k_rows : a.q_rows) < a.Tk)
+        LTX_THROW(LTXS_INVALID_CONFIGURATION, "attention module: the key RoPE tables have %d rows for Tk = %d", a.k_cos ? a.k_rows : a.q_rows, a.Tk);
+
+    hipStream_t st = ctx->stream;
+    const int I = m->inner, Dq = m->Dq, Dc = m->Dc, B = a.B, Tq = a.Tq, Tk = a.Tk;
+    const long qrows = (long)B * Tq, krows = (long)B * Tk;
+    const int Tpad = ((Tk + 63) / 64) * 64;
+    const bool kb = a.context_bf16 != 0;  // bf16 context: k leaves its projection in bf16
+    bool grew = false;
+    grew |= m->ws_xb.ensure((size_t)qrows * Dq * 2);
+    if (a.context && !kb) grew |= m->ws_cb.ensure((size_t)krows * Dc * 2);
+    grew |= m->ws_qraw.ensure((size_t)qrows * I * 4);
+    grew |= m->ws_kraw.ensure((size_t)krows * I * 4);
+    grew |= m->ws_q.ensure((size_t)qrows * I * 2);
+    grew |= m->ws_k.ensure((size_t)krows * I * 2);
+    grew |= m->ws_vt.ensure((size_t)B * I * Tpad * 2, true);  // zeroed: the pad columns of V^T must be finite
+    grew |= m->ws_ao.ensure((size_t)qrows * I * 2);
+    (void)grew;
+
+    bf16_t* xb = m->ws_xb.as<bf16_t>();
+    launch_cast_f32_bf16(a.x, xb, qrows * Dq, st);
+    const bf16_t* cb = xb;
+    if (a.context) {
+        if (kb) {
+            cb = (const bf16_t*)a.context;
+        } else {
+            launch_cast_f32_bf16((const float*)a.context, m->ws_cb.as<bf16_t>(), krows * Dc, st);
+            cb = m->ws_cb.as<bf16_t>();
+        }
+    }
+    float* qraw = m->ws_qraw.as<float>();
+    float* kraw = m->ws_kraw.as<float>();
+    bf16_t* q = m->ws_q.as<bf16_t>();
+    bf16_t* k = m->ws_k.as<bf16_t>();
+    bf16_t* vt = m->ws_vt.as<bf16_t>();
+    bf16_t* ao = m->ws_ao.as<bf16_t>();
+
+    GemmEpilogue eq;
+    eq.out_f32 = qraw;
+    eq.ld_f32 = I;
+    gemm_linear(xb, Dq, m->q, (int)qrows, eq, st);
+    GemmEpilogue ek;
+    if (kb) {
+        ek.out_bf16 = (bf16_t*)kraw;
+        ek.ld_bf16 = I;
+    } else {
+        ek.out_f32 = kraw;
+        ek.ld_f32 = I;
+    }
+    gemm_linear(cb, Dc, m->k, (int)krows, ek, st);
+    for (int b = 0; b < B; ++b) gemm_vt(cb + (size_t)b * Tk * Dc, Dc, Tk, m->v, vt + (size_t)b * I * Tpad, Tpad, st);
+
+    // q and k come from different inputs, token counts and tables: two one-job launches
+    launch_qknorm_rope(qraw, I, m->qn, a.q_cos, a.q_sin, Tq, q, I, (int)qrows, I, m->eps, st, kAttnQueryPrescale64, false, 64);
+    launch_qknorm_rope(kraw, I, m->kn, a.q_cos ? (a.k_cos ? a.k_cos : a.q_cos) : nullptr, a.q_cos ? (a.k_cos ? a.k_sin : a.q_sin) : nullptr, Tk, k,
+                       I, (int)krows, I, m->eps, st, 1.0f, kb, 64);
+
+    AttnArgs at;
+    at.head_dim = 64;
+    at.Q = q; at.ldq = I; at.q_bstride = (long)Tq * I;
+    at.K = k; at.ldk = I; at.k_bstride = (long)Tk * I;
+    at.Vt = vt; at.ldvt = Tpad; at.vt_bstride = (long)I * Tpad;
+    at.O = ao; at.ldo = I; at.o_bstride = (long)Tq * I;
+    at.bias = a.key_bias; at.bias_bstride = Tk;
+    at.B = B; at.H = m->heads; at.Tq = Tq; at.Tk = Tk;
+    at.scale = 0.125f;
+    at.q_prescaled = 1;
+    launch_attention(at, st);
+
+    GemmEpilogue eo;
+    eo.out_f32 = a.out;
+    eo.ld_f32 = Dq;
+    gemm_linear(ao, I, m->o, (int)qrows, eo, st);
+}

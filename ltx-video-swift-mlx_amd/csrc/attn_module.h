@@ -1,0 +1,62 @@
+// attn_module.h - LTXAttention at head dim 64 as a loadable unit (reference LTXAttention.swift:160-218 at 32 heads x 64,
+// LTXConfig.swift:134-135): the module the dual video+audio block adds four times to the video block - audio self-attention, audio
+// text cross-attention and the two cross-modal attentions a2v / v2a (LTX2TransformerBlock.swift:133-163,207-270).
+//
+// One module owns to_q [inner][Dq], to_k / to_v [inner][Dc], to_out [Dq][inner] (bf16, biases f32) and q_norm / k_norm [inner] (f32),
+// inner = heads x 64. Forward, in the reference's order, every step on the device:
+//   q = to_q(x), k = to_k(context ?? x), v = to_v(context ?? x)  ->  q_norm / k_norm across the whole row  ->  split RoPE on q with
+//   (q_cos, q_sin) and on k with (k_cos, k_sin), or with q's tables when only those are given (the reference's `kPe ?? pe`)  ->
+//   softmax(q k^T / 8 + key_bias) v per head  ->  to_out.
+//
+// Rounding points (the reference computes in f32 from f32 inputs, or in bf16 where the context is bf16):
+//   1. x [B][Tq][Dq] f32 and an f32 context are rounded to bf16 ONCE, as GEMM operands (as the DiT rounds its stream).
+//   2. q and k leave their projections in f32, are normed and rotated in f32 and rounded to bf16 once; q carries the folded softmax
+//      scale (1/8) log2(e) in that one rounding (kAttnQueryPrescale64).
+//   3. A bf16 context (the text cross-attention, whose K / V Linears are bf16 x bf16 in the reference): k is rounded to bf16 after
+//      the projection and again after the norm, as oracle.attention(kv_bf16=True) models it.
+//   4. v is rounded to bf16 by the projection's transposed store (V^T [inner][ldvt], what the attention kernel reads).
+//   5. Inside the attention kernel P is rounded to bf16 for the PV product (f32 accumulation); its output is bf16.
+//   6. to_out accumulates in f32 and writes f32 [B][Tq][Dq].
+// Scratch is owned by the module, grows to the largest shape seen and is reused: nothing is allocated per call.
+#pragma once
+#include <map>
+#include <string>
+
+#include "dit.h"
+#include "runtime.h"
+
+struct AttnModule {
+    int heads = 0, inner = 0, Dq = 0, Dc = 0;
+    float eps = 1e-6f;
+    DeviceArena arena;
+    LinearW q, k, v, o;
+    float* qn = nullptr;
+    float* kn = nullptr;
+    std::map<std::string, ParamSlot> slots;  // "to_q.weight", "to_q.bias", .., "q_norm.weight", "k_norm.weight"
+    DevBuf ws_xb, ws_cb, ws_qraw, ws_kraw, ws_q, ws_k, ws_vt, ws_ao;
+};
+
+AttnModule* attn_module_create(int query_dim, int context_dim, int heads);
+void attn_module_destroy(AttnModule* m);
+void attn_module_init_synthetic(ltx_ctx* ctx, AttnModule* m, uint64_t seed);
+// shapes of a module stored under `prefix` (e.g. "transformer_blocks.0.audio_to_video_attn.") in a safetensors file; the file's own
+// names (to_out.0, norm_q, norm_k) and the module's (to_out, q_norm, k_norm) are both accepted
+void attn_module_file_shape(const std::string& path, const std::string& prefix, int* query_dim, int* context_dim, int* inner);
+void attn_module_load(ltx_ctx* ctx, AttnModule* m, const std::string& path, const std::string& prefix);
+void attn_module_export(ltx_ctx* ctx, AttnModule* m, const ParamSlot& s, float* out);
+
+struct AttnModuleArgs {
+    const float* x = nullptr;        // [B][Tq][Dq] f32
+    const void* context = nullptr;   // [B][Tk][Dc] f32, or bf16 with context_bf16; null = self-attention (Tk == Tq)
+    int context_bf16 = 0;
+    int B = 1, Tq = 0, Tk = 0;
+    const float* q_cos = nullptr;    // [q_rows][inner/2] f32 or null (no RoPE at all)
+    const float* q_sin = nullptr;
+    int q_rows = 0;
+    const float* k_cos = nullptr;    // [k_rows][inner/2] f32; null with q_cos given: k is rotated with q's tables
+    const float* k_sin = nullptr;
+    int k_rows = 0;
+    const float* key_bias = nullptr; // [B][Tk] f32 additive, reference units ((1 - mask) * -10000), or null
+    float* out = nullptr;            // [B][Tq][Dq] f32
+};
+void attn_module_forward(ltx_ctx* ctx, AttnModule* m, const AttnModuleArgs& a);

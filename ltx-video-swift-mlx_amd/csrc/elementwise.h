@@ -18,15 +18,18 @@ void launch_norm_mod(const float* x, long ldx, const float* scale, const float* 
 // q/k RMSNorm across ALL heads with learnable weight, then split-RoPE per head (LTXAttention.swift:179-189,
 // LTXRoPE.swift:84-149). x: f32 [rows][ldx] (D valid columns), w: f32 [D], cos/sin: f32 [T][D/2] indexed by
 // (row % T) with per-head slices of 64 (nullable -> no RoPE, cross-attention). out: bf16 [rows][ldo].
+// head_dim (128, or 64 for the audio / cross-modal attention at 32 heads x 64): head h is columns h*head_dim .., rotated as its two
+// halves with columns h*head_dim/2 .. of the cos/sin row. The cross-modal q and k come from different inputs, token counts and tables:
+// two one-job launches.
 // q and k of a fused projection in ONE launch (job 1 optional: x1 == nullptr)
 void launch_qknorm_rope2(const float* x0, const float* w0, bf16_t* out0, const float* x1, const float* w1, bf16_t* out1,
                          long ldx, long ldo, const float* cosT, const float* sinT, int T, int rows, int D, float eps,
-                         hipStream_t stream, float out_scale0 = 1.0f, bool x_bf16 = false);
+                         hipStream_t stream, float out_scale0 = 1.0f, bool x_bf16 = false, int head_dim = 128);
 // out_scale0 / out_scale: multiplier applied to job 0's (the query's) normed + rotated row before its single rounding to bf16. The
 // DiT folds the softmax scale and log2(e) into it (kAttnQueryPrescale), so that the attention kernel's scores arrive as base-2
 // exponents: one rounding of q as before, and 48 multiplies per key tile less in the kernel (AttnArgs::q_prescaled).
 void launch_qknorm_rope(const float* x, long ldx, const float* w, const float* cosT, const float* sinT, int T,
-                        bf16_t* out, long ldo, int rows, int D, float eps, hipStream_t stream, float out_scale = 1.0f, bool x_bf16 = false);
+                        bf16_t* out, long ldo, int rows, int D, float eps, hipStream_t stream, float out_scale = 1.0f, bool x_bf16 = false, int head_dim = 128);
 
 // sequence-parallel self-attention: gathered V^T blocks [N][D][Tn] -> one V^T [D][ld] with rank r's keys at columns r*Tn ..
 void launch_sp_vt_interleave(const bf16_t* gathered, bf16_t* vt, int N, int D, int Tn, long ld, hipStream_t stream);

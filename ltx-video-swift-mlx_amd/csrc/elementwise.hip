@@ -274,6 +274,83 @@ __global__ __launch_bounds__(256) void qknorm_rope_kernel(QkJob j0, QkJob j1, co
     }
 }
 
+// The same kernel for heads of 64 (LTXAttention at 32 x 64, the audio / cross-modal attention of the dual block): head h of a row is
+// columns h*64 .. h*64+63, rotated as halves [0:32] / [32:64] with columns h*32 .. h*32+31 of the cos/sin row. The norm is still
+// across the whole row. A kernel of its own so that the head-dim-128 instantiations above stay as they are.
+template <int NP, bool XB = false>
+__global__ __launch_bounds__(256) void qknorm_rope64_kernel(QkJob j0, QkJob j1, const float* __restrict__ cosT,
+                                                          const float* __restrict__ sinT, int T, int D, float eps) {
+    __shared__ float red[4];
+    const QkJob job = blockIdx.y ? j1 : j0;
+    const int row = blockIdx.x;
+    const float* xr = XB ? (const float*)((const bf16_t*)job.x + (long)row * job.ldx) : job.x + (long)row * job.ldx;
+    // pair chunk p (0 .. D/8-1): head = p / 8, i4 = p % 8 ; a at head*64 + i4*4, b at +32
+    const int npair = D >> 3;
+    const int t = row % T;
+    f32x4 va[NP], vb[NP], wa[NP], wb[NP], c4[NP], s4[NP];
+#pragma unroll
+    for (int j = 0; j < NP; ++j) {
+        const int p = threadIdx.x + j * 256;
+        va[j] = vb[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (p < npair) {
+            const int col = (p >> 3) * 64 + (p & 7) * 4;
+            va[j] = qk_load4<XB>(xr, col);
+            vb[j] = qk_load4<XB>(xr, col + 32);
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < NP; ++j) {
+        const int p = threadIdx.x + j * 256;
+        if (p < npair) {
+            const int col = (p >> 3) * 64 + (p & 7) * 4;
+            wa[j] = *(const f32x4*)(job.w + col);
+            wb[j] = *(const f32x4*)(job.w + col + 32);
+            if (cosT) {
+                // cos/sin rows are [T][D/2]; head h uses columns h*32 .. h*32+31
+                const int fc = (p >> 3) * 32 + (p & 7) * 4;
+                c4[j] = *(const f32x4*)(cosT + (long)t * (D >> 1) + fc);
+                s4[j] = *(const f32x4*)(sinT + (long)t * (D >> 1) + fc);
+            }
+        }
+    }
+    float s2 = 0.f;
+#pragma unroll
+    for (int j = 0; j < NP; ++j)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) s2 += va[j][e] * va[j][e] + vb[j][e] * vb[j][e];
+    const float rstd = rsqrtf(block_reduce_sum(s2, red) / (float)D + eps);
+    const float osc = job.out_scale;
+    bf16_t* orow = job.out + (long)row * job.ldo;
+#pragma unroll
+    for (int j = 0; j < NP; ++j) {
+        const int p = threadIdx.x + j * 256;
+        if (p < npair) {
+            const int col = (p >> 3) * 64 + (p & 7) * 4;
+            f32x4 a, b;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                a[e] = va[j][e] * rstd * wa[j][e];
+                b[e] = vb[j][e] * rstd * wb[j][e];
+            }
+            if (cosT) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const float a0 = a[e], b0 = b[e];
+                    a[e] = a0 * c4[j][e] - b0 * s4[j][e];
+                    b[e] = b0 * c4[j][e] + a0 * s4[j][e];
+                }
+            }
+            uint2 pa, pb;
+            pa.x = pack_bf16x2(a[0] * osc, a[1] * osc);
+            pa.y = pack_bf16x2(a[2] * osc, a[3] * osc);
+            pb.x = pack_bf16x2(b[0] * osc, b[1] * osc);
+            pb.y = pack_bf16x2(b[2] * osc, b[3] * osc);
+            *(uint2*)(orow + col) = pa;
+            *(uint2*)(orow + col + 32) = pb;
+        }
+    }
+}
+
 __global__ void cast_f32_bf16_kernel(const float* __restrict__ x, bf16_t* __restrict__ out, long n) {
     long i = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
     const long stride = (long)gridDim.x * blockDim.x * 4;
@@ -834,10 +911,25 @@ __global__ __launch_bounds__(256) void qknorm_rope_pair_kernel(QkJob j0, QkJob j
 
 void launch_qknorm_rope2(const float* x0, const float* w0, bf16_t* out0, const float* x1, const float* w1, bf16_t* out1,
                          long ldx, long ldo, const float* cosT, const float* sinT, int T, int rows, int D, float eps,
-                         hipStream_t stream, float out_scale0, bool x_bf16) {
-    LTX_REQUIRE(D % 128 == 0 && D <= MAXV * 1024 && ldx % 4 == 0 && ldo % 4 == 0, "qknorm_rope: D=%d", D);
+                         hipStream_t stream, float out_scale0, bool x_bf16, int head_dim) {
+    LTX_REQUIRE(head_dim == 64 || head_dim == 128, "qknorm_rope: head dim %d (64 or 128)", head_dim);
+    LTX_REQUIRE(D % head_dim == 0 && D <= MAXV * 1024 && ldx % 4 == 0 && ldo % 4 == 0, "qknorm_rope: D=%d", D);
 
     const QkJob j0{x0, w0, out0, ldx, ldo, out_scale0}, j1{x1, w1, out1, ldx, ldo, 1.0f};
+    if (head_dim == 64) {
+        ProfScope prof(PROF_ELEM, (double)rows * D * (x1 ? 2 : 1) * ((x_bf16 ? 2 : 4) + 2 + (cosT ? 4 : 0)), stream);
+        const dim3 grid(rows, x1 ? 2 : 1);
+        const int t = T < 1 ? 1 : T;
+        if (x_bf16) {
+            if (D <= 2048) hipLaunchKernelGGL((qknorm_rope64_kernel<1, true>), grid, dim3(256), 0, stream, j0, j1, cosT, sinT, t, D, eps);
+            else if (D <= 4096) hipLaunchKernelGGL((qknorm_rope64_kernel<2, true>), grid, dim3(256), 0, stream, j0, j1, cosT, sinT, t, D, eps);
+            else hipLaunchKernelGGL((qknorm_rope64_kernel<4, true>), grid, dim3(256), 0, stream, j0, j1, cosT, sinT, t, D, eps);
+        } else if (D <= 2048) hipLaunchKernelGGL(qknorm_rope64_kernel<1>, grid, dim3(256), 0, stream, j0, j1, cosT, sinT, t, D, eps);
+        else if (D <= 4096) hipLaunchKernelGGL(qknorm_rope64_kernel<2>, grid, dim3(256), 0, stream, j0, j1, cosT, sinT, t, D, eps);
+        else hipLaunchKernelGGL(qknorm_rope64_kernel<4>, grid, dim3(256), 0, stream, j0, j1, cosT, sinT, t, D, eps);
+        HIP_CHECK(hipGetLastError());
+        return;
+    }
 #ifdef LTX_EXPERIMENTS  // timing ablation: LTX_ABL_ROWS bit 1 drops the q|k pass, bit 2 the cross-attention q pass, after two forwards' worth of calls
     { const int abl = ltx_opt(OPT_ABL_ROWS); static long c2 = 0, c1 = 0;
       if (x1 && (abl & 2) && ++c2 > 200) return; if (!x1 && (abl & 4) && ++c1 > 300) return; }
@@ -872,8 +964,8 @@ void launch_qknorm_rope2(const float* x0, const float* w0, bf16_t* out0, const f
 }
 
 void launch_qknorm_rope(const float* x, long ldx, const float* w, const float* cosT, const float* sinT, int T,
-                        bf16_t* out, long ldo, int rows, int D, float eps, hipStream_t stream, float out_scale, bool x_bf16) {
-    launch_qknorm_rope2(x, w, out, nullptr, nullptr, nullptr, ldx, ldo, cosT, sinT, T, rows, D, eps, stream, out_scale, x_bf16);
+                        bf16_t* out, long ldo, int rows, int D, float eps, hipStream_t stream, float out_scale, bool x_bf16, int head_dim) {
+    launch_qknorm_rope2(x, w, out, nullptr, nullptr, nullptr, ldx, ldo, cosT, sinT, T, rows, D, eps, stream, out_scale, x_bf16, head_dim);
 }
 
 void launch_cast_f32_bf16(const float* x, bf16_t* out, long n, hipStream_t stream) {

@@ -113,6 +113,16 @@ std::vector<float> compute_sigmas(bool distilled, int num_steps, int token_count
 // ---------------------------------------------------------------------------------------------------------------
 // R8 + R9: position grid and double-precision split-RoPE tables
 // ---------------------------------------------------------------------------------------------------------------
+// createPositionGrid's temporal coordinate of latent frame i: f32 pixel-space mid point with the causal fix, / fps
+static float video_temporal_coord(int i, float fps) {
+    const float tScale = 8.0f;
+    const float fi = (float)i;
+    float start = fi * tScale, end = (fi + 1) * tScale;
+    start = fmaxf(start + (1 - tScale), 0.0f);
+    end = fmaxf(end + (1 - tScale), 0.0f);
+    return ((start + end) / 2.0f) / fps;
+}
+
 void rope_tables(const TransformerConfig& cfg, int F, int H, int W, float fps, std::vector<float>* cos_out,
                  std::vector<float>* sin_out) {
     const int dim = cfg.inner_dim();
@@ -126,15 +136,9 @@ void rope_tables(const TransformerConfig& cfg, int F, int H, int W, float fps, s
     const long T = (long)F * H * W;
 
     // createPositionGrid: f32 pixel-space mid coordinates, temporal causal fix, /fps
-    const float tScale = 8.0f, sScale = 32.0f;
+    const float sScale = 32.0f;
     std::vector<float> tc(F), hc(H), wc(W);
-    for (int i = 0; i < F; ++i) {
-        const float fi = (float)i;
-        float start = fi * tScale, end = (fi + 1) * tScale;
-        start = fmaxf(start + (1 - tScale), 0.0f);
-        end = fmaxf(end + (1 - tScale), 0.0f);
-        tc[i] = ((start + end) / 2.0f) / fps;
-    }
+    for (int i = 0; i < F; ++i) tc[i] = video_temporal_coord(i, fps);
     for (int i = 0; i < H; ++i) hc[i] = (float)i * sScale + sScale / 2.0f;
     for (int i = 0; i < W; ++i) wc[i] = (float)i * sScale + sScale / 2.0f;
 
@@ -397,6 +401,49 @@ void rope_tables_1d(int T, int dim, double theta, int max_pos, std::vector<float
     }
 }
 
+
+// ---------------------------------------------------------------------------------------------------------------
+// audio / cross-modal RoPE: real-valued 1-D positions
+// ---------------------------------------------------------------------------------------------------------------
+std::vector<float> audio_positions(int T_a) {
+    const float scale = 4.0f, offset = 1.0f, hop = 160.0f, sr = 16000.0f;
+    std::vector<float> pos((size_t)(T_a > 0 ? T_a : 0));
+    for (int i = 0; i < T_a; ++i) {
+        const float fi = (float)i;
+        const float start = fmaxf(0.0f, fi * scale + offset - scale);
+        const float end = fmaxf(0.0f, (fi + 1) * scale + offset - scale);
+        pos[i] = (start + end) / 2.0f * hop / sr;
+    }
+    return pos;
+}
+
+std::vector<float> video_temporal_positions(int F, int H, int W, float fps) {
+    std::vector<float> pos;
+    pos.reserve((size_t)F * H * W);
+    for (int f = 0; f < F; ++f) pos.insert(pos.end(), (size_t)H * W, video_temporal_coord(f, fps));
+    return pos;
+}
+
+void rope_tables_positions(const float* pos, int T, int dim, double theta, int max_pos, std::vector<float>* cos_out,
+                           std::vector<float>* sin_out) {
+    const int n_idx = dim / 2 > 1 ? dim / 2 : 1;
+    const double log_start = log(1.0) / log(theta), log_end = log(theta) / log(theta);
+    std::vector<double> idx(n_idx);
+    for (int i = 0; i < n_idx; ++i) {
+        const double t = n_idx > 1 ? log_start + (log_end - log_start) * (double)i / (double)(n_idx - 1) : log_start;
+        idx[i] = pow(theta, t) * (M_PI / 2.0);
+    }
+    cos_out->assign((size_t)T * n_idx, 0.f);
+    sin_out->assign((size_t)T * n_idx, 0.f);
+    for (int t = 0; t < T; ++t) {
+        const double scaled = ((double)pos[t] / (double)max_pos) * 2.0 - 1.0;
+        for (int i = 0; i < n_idx; ++i) {
+            const double v = idx[i] * scaled;
+            (*cos_out)[(size_t)t * n_idx + i] = (float)cos(v);
+            (*sin_out)[(size_t)t * n_idx + i] = (float)sin(v);
+        }
+    }
+}
 
 bool map_vae_encoder_file_key(const std::string& file_key, std::string* module_key) {
     if (!starts_with(file_key, "encoder.")) return false;

@@ -63,6 +63,17 @@ bool map_text_encoder_file_key(const std::string& file_key, std::string* module_
 // LTXRoPE.swift:375-490). cos/sin [T][dim/2] f32 (no padding slots: one axis -> dim/2 frequencies).
 void rope_tables_1d(int T, int dim, double theta, int max_pos, std::vector<float>* cos_out, std::vector<float>* sin_out);
 
+// audio / cross-modal attention of the dual block (LTX2Transformer.swift:176-233): RoPE over ONE real-valued position per token.
+// createAudioPositionGrid (LTXRoPE.swift:627-655; hop 160, rate 16000, scale 4, causal offset 1, f32): seconds of the middle of
+// audio latent frame i.
+std::vector<float> audio_positions(int T_a);
+// temporal coordinate of every video token in token order: row 0 of the position grid rope_tables builds (LTX2Transformer.swift:205-209)
+std::vector<float> video_temporal_positions(int F, int H, int W, float fps);
+// precomputeFreqsCis, f64 path, one position dimension (LTXRoPE.swift:375-490): dim/2 frequencies theta^(i/(n-1)) * pi/2 times the
+// scaled position 2 * pos / max_pos - 1; cos/sin [T][dim/2] f32, no padding slots. max_pos = 20 in the dual model.
+void rope_tables_positions(const float* pos, int T, int dim, double theta, int max_pos, std::vector<float>* cos_out,
+                           std::vector<float>* sin_out);
+
 // MLX-compatible noise (R2: generateNoise = MLXRandom.seed(seed); MLXRandom.normal(shape, f32),
 // LatentUtils.swift:69-83). The arithmetic is mlx-swift 0.30.6's (absent from the reference tree), restated from its
 // published algorithm: threefry2x32-20 counter hash; key(seed) = {seed >> 32, seed & 0xffffffff}; every keyless draw first

@@ -89,6 +89,7 @@ struct VaeEncoderModel;
 struct UpscalerModel;
 struct AudioVaeModel;
 struct VocoderModel;
+struct AttnModule;
 struct DistState;
 
 // ---- live per-kernel timing (HIP events recorded on the launch stream around each launch of a kernel family) ----
@@ -141,6 +142,8 @@ enum H2dSlot {
     H2D_COUNT = 8
 };
 
+constexpr int kAttnModuleSlots = 4;  // attention modules a context holds: one dual block's worth
+
 struct ltx_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -154,6 +157,7 @@ struct ltx_ctx {
     DistState* dist = nullptr;  // multi-GPU state (dist.h); null = single GPU
     AudioVaeModel* audio_vae = nullptr;  // audio decode leg (audio.h)
     VocoderModel* vocoder = nullptr;
+    AttnModule* attn_modules[kAttnModuleSlots] = {};  // head-dim-64 attention modules by index (attn_module.h)
     DevBuf audio_mel, audio_op[2];  // the mel between the two audio models; haloed operands of the audio conv test hooks
     DevBuf h2d[H2D_COUNT];  // staging buffers of the host-pointer entry points, indexed by H2dSlot
     // load report of the last *_load call (mirrors the reference's "unmatched/missing" debug logs)
