@@ -343,8 +343,8 @@ int ltx_write_wav(const char* path, const float* waveform, long n, int sample_ra
  * Audio / cross-modal attention: LTXAttention at 32 heads x 64 (LTXConfig.swift:134-135), the module the dual video + audio block
  * adds four times to the video block - audio self-attention, audio text cross-attention, a2v and v2a cross-modal attention
  * (LTX2TransformerBlock.swift:133-163,207-270) - with the RoPE tables of its real-valued 1-D positions. A context holds up to four
- * modules, addressed by index 0 .. 3. The audio stream's adaLN embedders, the cross-modal scale-shift embedders, the block wiring and
- * the joint denoise loop are not part of this library yet.
+ * modules, addressed by index 0 .. 3. The block wiring is "Dual video + audio transformer blocks" below; the audio stream's adaLN
+ * embedders, the cross-modal scale-shift embedders and the joint denoise loop are not part of this library yet.
  * ---------------------------------------------------------------------------------------------------------- */
 /* createAudioPositionGrid (LTXRoPE.swift:627-655; hop 160, rate 16000, scale 4, causal offset 1, f32 arithmetic): out[i] = seconds of
  * the middle of audio latent frame i, i < T_a (0.005, 0.03, 0.07, ...). Pure host code. */
@@ -377,6 +377,92 @@ long ltx_attn_module_export_param(ltx_ctx* ctx, int index, const char* name, flo
 int ltx_attn_module_forward_dev(ltx_ctx* ctx, int index, const float* x, const void* context, int context_bf16, int B, int Tq, int Tk,
                                 const float* q_cos, const float* q_sin, int q_table_rows, const float* k_cos, const float* k_sin,
                                 int k_table_rows, const float* key_bias, float* out);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Dual video + audio transformer blocks: LTX2TransformerBlock (LTX2TransformerBlock.swift:174-297) as a loadable stack of L blocks
+ * with a forward of its own. It takes what LTX2Transformer.callAsFunction hands its blocks and returns both residual streams. The
+ * embedders that make the modulation rows (audio_adaln_single, av_ca_*), the patchify / output heads, the caption projections, the
+ * joint denoise loop and the CLI's --audio path are not part of this library yet. The modulation rows are one per batch element; the
+ * reference's per-token form (image-to-video, LTX2Transformer.swift:285-312) is not implemented. A context holds one stack.
+ * ---------------------------------------------------------------------------------------------------------- */
+typedef struct ltx_dual_block_config {
+    int num_layers;         /* 48 */
+    int video_heads;        /* 32 heads x 128 */
+    int video_dim;          /* 4096 = video_heads * 128 */
+    int audio_heads;        /* 32 heads x 64 */
+    int audio_dim;          /* 2048 = audio_heads * 64 */
+    int video_context_dim;  /* width of the video text context (videoCrossAttentionDim, 4096); a multiple of 64 */
+    int audio_context_dim;  /* width of the audio text context (audioCrossAttentionDim, 2048); a multiple of 64 */
+    float rope_theta;       /* 10000 */
+    int max_pos[3];         /* video 3-D RoPE: {20, 2048, 2048} */
+    int audio_max_pos;      /* audio and cross-modal 1-D RoPE: 20 */
+    float fps;              /* 24: temporal coordinates of the video tokens */
+    float norm_eps;         /* 1e-6 */
+} ltx_dual_block_config;
+/* Filled with the reference defaults (LTXConfig.swift:83-177 and its audio fields :126-140). */
+void ltx_dual_block_config_default(ltx_dual_block_config* cfg);
+/* Random-init stack (LTX2TransformerBlock.init, LTX2TransformerBlock.swift:98-170): Linear weights N(0, 0.02^2), biases N(0, 0.01^2),
+ * q / k norm weights 1 + N(0, 0.02^2), the four scale-shift tables N(0, 0.02^2), all bf16 values. video_dim != video_heads * 128 or
+ * audio_dim != audio_heads * 64: LTX_ERR_INVALID_CONFIGURATION. */
+int ltx_dual_blocks_init_synthetic(ltx_ctx* ctx, const ltx_dual_block_config* cfg, uint64_t seed);
+/* Replaces the block part of loadTransformerWeights(includeAudio: true) (ModelDownloader.swift:605-639): tensors under
+ * `transformer_blocks.{first_block + i}.` fill block i, i < num_blocks (cfg->num_layers is ignored). Keys in the module's spelling or
+ * the checkpoint's (to_out.0, norm_q / norm_k, ff.net.0.proj / ff.net.2, mapped as mapTransformerKey does, ModelDownloader.swift:
+ * 756-803; scale_shift_table_a2v_ca_video / _audio are spelled alike on both sides). ltx_load_report: tensors applied / 0 / tensors of
+ * those blocks that are no parameter (the RMSNorm weights: none is applied). A parameter the file lacks: LTX_ERR_WEIGHT_LOADING_FAILED,
+ * and the context holds no stack. */
+int ltx_dual_blocks_load(ltx_ctx* ctx, const char* safetensors_path, const ltx_dual_block_config* cfg, int first_block, int num_blocks);
+int ltx_dual_blocks_unload(ltx_ctx* ctx);
+/* One resident parameter as f32 by its module key with blocks numbered from 0 ("transformer_blocks.0.audio_attn1.to_q.weight",
+ * "transformer_blocks.1.scale_shift_table_a2v_ca_audio", ...): its element count (out NULL: the count only) or a negative ltx_status.
+ * Test seam, as ltx_dit_export_param. */
+long ltx_dual_blocks_export_param(ltx_ctx* ctx, const char* name, float* out, long cap);
+/* Arguments of ltx_dual_blocks_forward_dev; starts with its own size as ltx_denoise_options does (LTX_DUAL_FORWARD_ARGS_INIT). All
+ * pointers are DEVICE pointers. */
+typedef struct ltx_dual_forward_args {
+    uint32_t struct_size;          /* sizeof(ltx_dual_forward_args) in the caller's translation unit */
+    int B, F, H, W;                /* batch; latent frames / height / width: F*H*W video tokens in (f, h, w) order */
+    int T_a;                       /* audio tokens */
+    int S;                         /* text tokens of both contexts */
+    float* x_video;                /* [B][F*H*W][video_dim] f32, updated in place (TransformerArgs.x) */
+    float* x_audio;                /* [B][T_a][audio_dim] f32, updated in place (AudioTransformerArgs.x) */
+    const uint16_t* context_video; /* [B][S][video_context_dim] bf16 (TransformerArgs.context) */
+    const uint16_t* context_audio; /* [B][S][audio_context_dim] bf16 */
+    const float* key_bias_video;   /* [B][S] f32 additive, (1 - mask) * -10000, or NULL (contextMask) */
+    const float* key_bias_audio;
+    const float* temb_video;       /* [B][6][video_dim] f32 (TransformerArgs.timesteps) */
+    const float* temb_audio;       /* [B][6][audio_dim] f32 */
+    const float* cross_video_ss;   /* [B][5][video_dim] f32 (crossVideoScaleShift) */
+    const float* cross_audio_ss;   /* [B][5][audio_dim] f32 (crossAudioScaleShift) */
+    uint32_t phase_mask;           /* 0: all eight phases. Else bit p-1 runs phase p of every block alone - a measurement seam */
+} ltx_dual_forward_args;
+#define LTX_DUAL_FORWARD_ARGS_INIT {sizeof(ltx_dual_forward_args), 1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}
+/* Replaces the block loop of LTX2Transformer.callAsFunction: L x LTX2TransformerBlock.callAsFunction (LTX2TransformerBlock.swift:
+ * 174-297) on both streams in place. The four RoPE table sets (LTX2Transformer.swift:136-236) are made inside from (F, H, W) and T_a and
+ * cached. Asynchronous on the context stream. No stack: LTX_ERR_MODEL_NOT_LOADED; a struct_size that does not cover the fields up to
+ * cross_audio_ss, B outside 1 .. 8, a dimension < 1 or a NULL stream / context / modulation pointer: LTX_ERR_INVALID_CONFIGURATION. Every
+ * check comes before the first launch: a refused call writes nothing. */
+int ltx_dual_blocks_forward_dev(ltx_ctx* ctx, const ltx_dual_forward_args* args);
+/* One job of ltx_op_norm_mod2: rows f32 [rows][ldx] -> two bf16 outputs [rows][ldo]. */
+typedef struct ltx_norm_mod2_job {
+    const float* x;
+    long ldx;
+    const float* scale0; /* [B][mod_bstride] f32, row b = row / rows_per_batch; NULL with shift0 NULL: the plain norm */
+    const float* shift0;
+    const float* scale1;
+    const float* shift1;
+    long mod_bstride;
+    int rows_per_batch;
+    uint16_t* out0;
+    uint16_t* out1;
+    long ldo;
+    int rows; /* 0: the job is empty */
+    int D;    /* D % 4 == 0, <= 8192 */
+} ltx_norm_mod2_job;
+/* Kernel hook: the cross-modal norms of the dual block in one launch (audioToVideoNorm / videoToAudioNorm and their four modulations,
+ * LTX2TransformerBlock.swift:246-263). out0 = rmsnorm(x) * (1 + scale0) + shift0, out1 likewise with (scale1, shift1); each bit-equal
+ * to ltx_op_norm_mod_ex with the same operands. Either job may be NULL or empty. Bad arguments are refused before the launch. */
+int ltx_op_norm_mod2(ltx_ctx* ctx, const ltx_norm_mod2_job* video, const ltx_norm_mod2_job* audio, float eps);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Text-embedding connector (VideoGemmaTextEncoderModel.encodeFromHiddenStates,

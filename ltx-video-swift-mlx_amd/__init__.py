@@ -16,7 +16,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import (ALLGATHER_FN, DIST_ID_BYTES, SHARD_CFG, SHARD_NONE, SHARD_SEQUENCE, ConnectorConfig, PROGRESS_CB, DenoiseOptions,
-                   LTXError, TransformerConfig, lib)
+                   DualBlockConfig, DualForwardArgs, LTXError, NormMod2Job, TransformerConfig, lib)
 
 __version__ = lib.ltx_version().decode()
 
@@ -25,6 +25,31 @@ def _check(rc, ctx=None):
     if rc != 0:
         msg = lib.ltx_last_error(ctx).decode(errors="replace") if True else ""
         raise LTXError(rc, msg)
+
+
+def default_dual_block_config(**overrides):
+    """``ltx_dual_block_config`` with the reference defaults (48 blocks, video 32 x 128, audio 32 x 64), fields overridden by keyword.
+    ``video_heads`` / ``audio_heads`` given without their dims set ``video_dim`` = heads * 128 and ``audio_dim`` = heads * 64, and the
+    context dims follow the stream dims unless given."""
+    cfg = DualBlockConfig()
+    lib.ltx_dual_block_config_default(C.byref(cfg))
+    o = dict(overrides)
+    if "video_heads" in o:
+        o.setdefault("video_dim", o["video_heads"] * 128)
+    if "audio_heads" in o:
+        o.setdefault("audio_dim", o["audio_heads"] * 64)
+    if "video_dim" in o:
+        o.setdefault("video_context_dim", o["video_dim"])
+    if "audio_dim" in o:
+        o.setdefault("audio_context_dim", o["audio_dim"])
+    for k, v in o.items():
+        if k == "max_pos":
+            for i in range(3):
+                cfg.max_pos[i] = v[i]
+        else:
+            getattr(cfg, k)
+            setattr(cfg, k, v)
+    return cfg
 
 
 def default_transformer_config(**overrides):
@@ -874,6 +899,61 @@ class Context:
         self._ck(lib.ltx_attn_module_forward_dev(self._h, index, _ptr(x), _ptr(context), int(context is not None and context.element_size() == 2),
                                                  B, Tq, Tk, _ptr(qc), _ptr(qs), 0 if qc is None else qc.shape[0], _ptr(kc), _ptr(ks),
                                                  0 if kc is None else kc.shape[0], _ptr(key_bias), _ptr(out)))
+
+    # ---- LTX2TransformerBlock x L: the dual video + audio transformer blocks ----
+    def dual_blocks_init_synthetic(self, cfg, seed=4242):
+        self._ck(lib.ltx_dual_blocks_init_synthetic(self._h, C.byref(cfg), seed))
+
+    def dual_blocks_load(self, path, cfg, first_block=0, num_blocks=None):
+        self._ck(lib.ltx_dual_blocks_load(self._h, str(path).encode(), C.byref(cfg), first_block, cfg.num_layers if num_blocks is None else num_blocks))
+
+    def dual_blocks_unload(self):
+        self._ck(lib.ltx_dual_blocks_unload(self._h))
+
+    def dual_blocks_export_param(self, name):
+        """One resident parameter of the stack as a flat f32 numpy array ("transformer_blocks.0.attn1.to_q.weight", ...)."""
+        n = lib.ltx_dual_blocks_export_param(self._h, name.encode(), None, 0)
+        if n < 0:
+            raise LTXError(-n, lib.ltx_last_error(self._h).decode(errors="replace"))
+        out = np.empty(n, dtype=np.float32)
+        n2 = lib.ltx_dual_blocks_export_param(self._h, name.encode(), out.ctypes.data, n)
+        if n2 < 0:
+            raise LTXError(-n2, lib.ltx_last_error(self._h).decode(errors="replace"))
+        return out
+
+    def dual_blocks_forward_dev(self, x_video, x_audio, context_video, context_audio, temb_video, temb_audio, cross_video_ss, cross_audio_ss,
+                                F, H, W, key_bias_video=None, key_bias_audio=None, phase_mask=0, struct_size=None, T_a=None):
+        """``ltx_dual_blocks_forward_dev``: device tensors; x_video [B][F*H*W][Dv] and x_audio [B][T_a][Da] f32 are updated in place,
+        the contexts [B][S][.] are bf16, temb_* [B][6][D], cross_*_ss [B][5][D] f32, key biases [B][S] f32 or None."""
+        a = DualForwardArgs()
+        a.struct_size = C.sizeof(DualForwardArgs) if struct_size is None else struct_size
+        a.B, a.F, a.H, a.W = x_video.shape[0], F, H, W
+        a.T_a = x_audio.shape[1] if T_a is None else T_a
+        a.S = context_video.shape[1]
+        a.x_video, a.x_audio = _ptr(x_video), _ptr(x_audio)
+        a.context_video, a.context_audio = _ptr(context_video), _ptr(context_audio)
+        a.key_bias_video, a.key_bias_audio = _ptr(key_bias_video), _ptr(key_bias_audio)
+        a.temb_video, a.temb_audio = _ptr(temb_video), _ptr(temb_audio)
+        a.cross_video_ss, a.cross_audio_ss = _ptr(cross_video_ss), _ptr(cross_audio_ss)
+        a.phase_mask = phase_mask
+        self._ck(lib.ltx_dual_blocks_forward_dev(self._h, C.byref(a)))
+
+    def op_norm_mod2(self, video=None, audio=None, eps=1e-6):
+        """``ltx_op_norm_mod2``: each job is None or a dict(x=, out0=, out1= 2-D tensors whose row strides are ldx / ldo, rows=, D=,
+        scale0=, shift0=, scale1=, shift1= (tensors or None), mod_bstride=0, rows_per_batch=rows)."""
+        def job(j):
+            if j is None:
+                return None
+            o = NormMod2Job()
+            o.x, o.ldx = j["x"].data_ptr(), j["x"].stride(0)
+            for k in ("scale0", "shift0", "scale1", "shift1"):
+                setattr(o, k, _ptr(j.get(k)))
+            o.mod_bstride = j.get("mod_bstride", 0)
+            o.rows_per_batch = j.get("rows_per_batch", max(1, j["rows"]))
+            o.out0, o.out1, o.ldo = j["out0"].data_ptr(), j["out1"].data_ptr(), j["out0"].stride(0)
+            o.rows, o.D = j["rows"], j["D"]
+            return C.byref(o)
+        self._ck(lib.ltx_op_norm_mod2(self._h, job(video), job(audio), eps))
 
     def op_norm_mod(self, x, scale, shift, out, norm_kind=0, eps=1e-6, round_norm_bf16=False):
         rows, D = x.shape

@@ -60,6 +60,31 @@ class TransformerConfig(C.Structure):
     ]
 
 
+class DualBlockConfig(C.Structure):
+    """``ltx_dual_block_config``: the dual video + audio block stack (LTX2TransformerBlock.swift:98-170, LTXConfig.swift:83-177)."""
+
+    _fields_ = [("num_layers", C.c_int), ("video_heads", C.c_int), ("video_dim", C.c_int), ("audio_heads", C.c_int), ("audio_dim", C.c_int),
+                ("video_context_dim", C.c_int), ("audio_context_dim", C.c_int), ("rope_theta", C.c_float), ("max_pos", C.c_int * 3),
+                ("audio_max_pos", C.c_int), ("fps", C.c_float), ("norm_eps", C.c_float)]
+
+
+class DualForwardArgs(C.Structure):
+    """``ltx_dual_forward_args``: what LTX2Transformer.callAsFunction hands its blocks (LTX2TransformerBlock.swift:174-177)."""
+
+    _fields_ = [("struct_size", C.c_uint32), ("B", C.c_int), ("F", C.c_int), ("H", C.c_int), ("W", C.c_int), ("T_a", C.c_int), ("S", C.c_int),
+                ("x_video", C.c_void_p), ("x_audio", C.c_void_p), ("context_video", C.c_void_p), ("context_audio", C.c_void_p),
+                ("key_bias_video", C.c_void_p), ("key_bias_audio", C.c_void_p), ("temb_video", C.c_void_p), ("temb_audio", C.c_void_p),
+                ("cross_video_ss", C.c_void_p), ("cross_audio_ss", C.c_void_p), ("phase_mask", C.c_uint32)]
+
+
+class NormMod2Job(C.Structure):
+    """``ltx_norm_mod2_job``: one job of ``ltx_op_norm_mod2``."""
+
+    _fields_ = [("x", C.c_void_p), ("ldx", C.c_long), ("scale0", C.c_void_p), ("shift0", C.c_void_p), ("scale1", C.c_void_p),
+                ("shift1", C.c_void_p), ("mod_bstride", C.c_long), ("rows_per_batch", C.c_int), ("out0", C.c_void_p), ("out1", C.c_void_p),
+                ("ldo", C.c_long), ("rows", C.c_int), ("D", C.c_int)]
+
+
 def _load():
     if not os.path.exists(SO_PATH):
         raise ImportError(
@@ -203,6 +228,13 @@ SIGNATURES = {
     "ltx_attn_module_unload": (_i, [_vp, _i]),
     "ltx_attn_module_export_param": (_l, [_vp, _i, C.c_char_p, _vp, _l]),
     "ltx_attn_module_forward_dev": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp]),
+    "ltx_dual_block_config_default": (None, [C.POINTER(DualBlockConfig)]),
+    "ltx_dual_blocks_init_synthetic": (_i, [_vp, C.POINTER(DualBlockConfig), _u64]),
+    "ltx_dual_blocks_load": (_i, [_vp, C.c_char_p, C.POINTER(DualBlockConfig), _i, _i]),
+    "ltx_dual_blocks_unload": (_i, [_vp]),
+    "ltx_dual_blocks_export_param": (_l, [_vp, C.c_char_p, _vp, _l]),
+    "ltx_dual_blocks_forward_dev": (_i, [_vp, C.POINTER(DualForwardArgs)]),
+    "ltx_op_norm_mod2": (_i, [_vp, C.POINTER(NormMod2Job), C.POINTER(NormMod2Job), _f]),
     "ltx_op_attention_hd": (_i, [_vp, _vp, _vp, _vp, _l, _vp, _i, _i, _i, _i, _i, _f, _vp]),
     "ltx_attention_hd_workgroup_queries": (_i, [_i, _i, _i, _i]),
     "ltx_op_qknorm_rope_hd": (_i, [_vp, _vp, _l, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _vp]),

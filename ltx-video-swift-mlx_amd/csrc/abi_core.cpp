@@ -5,6 +5,7 @@
 
 #include "abi_internal.h"
 #include "attn_module.h"
+#include "dual_block.h"
 #include "audio.h"
 #include "connector.h"
 #include "dist.h"
@@ -123,6 +124,7 @@ void ltx_ctx_destroy(ltx_ctx* ctx) {
     drop_model(&ctx->audio_vae, audio_vae_destroy);
     drop_model(&ctx->vocoder, vocoder_destroy);
     for (AttnModule*& m : ctx->attn_modules) drop_model(&m, attn_module_destroy);
+    drop_model(&ctx->dual, dual_destroy);
     if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
 }

@@ -311,6 +311,22 @@ int ltx_op_norm_mod_ex(ltx_ctx* ctx, const float* x, long ldx, const float* scal
     });
 }
 
+int ltx_op_norm_mod2(ltx_ctx* ctx, const ltx_norm_mod2_job* video, const ltx_norm_mod2_job* audio, float eps) {
+    return with_ctx(ctx, [&] {
+        auto job = [](const ltx_norm_mod2_job* j) {
+            NormMod2Job o;
+            if (!j) return o;
+            o.x = j->x; o.ldx = j->ldx;
+            o.scale0 = j->scale0; o.shift0 = j->shift0; o.scale1 = j->scale1; o.shift1 = j->shift1;
+            o.mod_bstride = j->mod_bstride; o.rows_per_batch = j->rows_per_batch;
+            o.out0 = j->out0; o.out1 = j->out1; o.ldo = j->ldo;
+            o.rows = j->rows; o.D = j->D;
+            return o;
+        };
+        launch_norm_mod2(job(video), job(audio), eps, ctx->stream);
+    });
+}
+
 int ltx_op_qknorm_rope_pair(ltx_ctx* ctx, const void* x0, const float* w0, uint16_t* out0, const void* x1, const float* w1,
                             uint16_t* out1, long ldx, long ldo, const float* cos_t, const float* sin_t, int T, int rows, int D,
                             float eps, float out_scale0, int x_bf16) {

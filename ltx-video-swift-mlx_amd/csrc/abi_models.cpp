@@ -8,6 +8,7 @@
 #include "abi_internal.h"
 #include "audio.h"
 #include "attn_module.h"
+#include "dual_block.h"
 #include "connector.h"
 #include "dist.h"
 #include "elementwise.h"
@@ -159,6 +160,24 @@ void fill_params(DenoiseParams& p, const ltx_denoise_options* o) {
 AttnModule** attn_slot(ltx_ctx* ctx, int index) {
     LTX_REQUIRE(index >= 0 && index < kAttnModuleSlots, "attention module index %d outside 0 .. %d", index, kAttnModuleSlots - 1);
     return &ctx->attn_modules[index];
+}
+
+DualBlockConfig to_dual_cfg(const ltx_dual_block_config* c) {
+    DualBlockConfig t;
+    if (!c) return t;
+    t.num_layers = c->num_layers;
+    t.video_heads = c->video_heads;
+    t.video_dim = c->video_dim;
+    t.audio_heads = c->audio_heads;
+    t.audio_dim = c->audio_dim;
+    t.video_context_dim = c->video_context_dim;
+    t.audio_context_dim = c->audio_context_dim;
+    t.rope_theta = c->rope_theta;
+    for (int i = 0; i < 3; ++i) t.max_pos[i] = c->max_pos[i];
+    t.audio_max_pos = c->audio_max_pos;
+    t.fps = c->fps;
+    t.norm_eps = c->norm_eps;
+    return t;
 }
 
 }  // namespace
@@ -842,6 +861,76 @@ int ltx_attn_module_forward_dev(ltx_ctx* ctx, int index, const float* x, const v
         a.key_bias = key_bias;
         a.out = out;
         attn_module_forward(ctx, m, a);
+    });
+}
+
+/* ---- LTX2TransformerBlock x L: the dual video + audio transformer blocks (dual_block.h) ---- */
+void ltx_dual_block_config_default(ltx_dual_block_config* cfg) {
+    if (!cfg) return;
+    const DualBlockConfig d;
+    cfg->num_layers = d.num_layers;
+    cfg->video_heads = d.video_heads;
+    cfg->video_dim = d.video_dim;
+    cfg->audio_heads = d.audio_heads;
+    cfg->audio_dim = d.audio_dim;
+    cfg->video_context_dim = d.video_context_dim;
+    cfg->audio_context_dim = d.audio_context_dim;
+    cfg->rope_theta = d.rope_theta;
+    for (int i = 0; i < 3; ++i) cfg->max_pos[i] = d.max_pos[i];
+    cfg->audio_max_pos = d.audio_max_pos;
+    cfg->fps = d.fps;
+    cfg->norm_eps = d.norm_eps;
+}
+int ltx_dual_blocks_init_synthetic(ltx_ctx* ctx, const ltx_dual_block_config* cfg, uint64_t seed) {
+    return with_ctx(ctx, [&] {
+        replace_model(ctx, &ctx->dual, [&] { return dual_create(to_dual_cfg(cfg)); }, [&](DualStack* m) { dual_init_synthetic(ctx, m, seed); },
+                      dual_destroy);
+    });
+}
+int ltx_dual_blocks_load(ltx_ctx* ctx, const char* path, const ltx_dual_block_config* cfg, int first_block, int num_blocks) {
+    if (!ctx || !path) return LTX_ERR_INVALID_CONFIGURATION;
+    return guarded(ctx, [&] {
+        LTX_REQUIRE(first_block >= 0 && num_blocks >= 1, "ltx_dual_blocks_load: first_block %d, num_blocks %d", first_block, num_blocks);
+        DualBlockConfig c = to_dual_cfg(cfg);
+        c.num_layers = num_blocks;
+        replace_model(ctx, &ctx->dual, [&] { return dual_create(c); }, [&](DualStack* m) { dual_load(ctx, m, path, first_block); }, dual_destroy);
+    });
+}
+int ltx_dual_blocks_unload(ltx_ctx* ctx) {
+    return with_ctx(ctx, [&] { unload_model(ctx, &ctx->dual, dual_destroy); });
+}
+long ltx_dual_blocks_export_param(ltx_ctx* ctx, const char* name, float* out, long cap) {
+    if (!ctx || !name) return -LTX_ERR_INVALID_CONFIGURATION;
+    long n = 0;
+    const int rc = guarded(ctx, [&] {
+        DualStack* m = need(ctx->dual, kNoDualBlocks);
+        auto it = m->slots.find(name);
+        LTX_REQUIRE(it != m->slots.end(), "ltx_dual_blocks_export_param: no parameter '%s'", name);
+        n = it->second.numel;
+        if (!out) return;
+        LTX_REQUIRE(cap >= n, "ltx_dual_blocks_export_param: buffer too small (%ld < %ld)", cap, n);
+        dual_export(ctx, m, it->second, out);
+    });
+    return rc == 0 ? n : -rc;
+}
+int ltx_dual_blocks_forward_dev(ltx_ctx* ctx, const ltx_dual_forward_args* args) {
+    if (!ctx) return LTX_ERR_INVALID_CONFIGURATION;
+    return guarded(ctx, [&] {
+        LTX_REQUIRE(args != nullptr, "ltx_dual_blocks_forward_dev: null arguments");
+        const size_t sz = args->struct_size;
+        LTX_REQUIRE(sz >= offsetof(ltx_dual_forward_args, cross_audio_ss) + sizeof(args->cross_audio_ss) && sz <= 4096,
+                    "ltx_dual_forward_args.struct_size = %zu: set it to sizeof(ltx_dual_forward_args) (LTX_DUAL_FORWARD_ARGS_INIT); this library is ABI revision %d",
+                    sz, LTX_ABI_VERSION);
+        DualStack* m = need(ctx->dual, kNoDualBlocks);
+        DualForwardArgs a;
+        a.B = args->B; a.F = args->F; a.H = args->H; a.W = args->W; a.T_a = args->T_a; a.S = args->S;
+        a.x_video = args->x_video; a.x_audio = args->x_audio;
+        a.ctx_video = args->context_video; a.ctx_audio = args->context_audio;
+        a.bias_video = args->key_bias_video; a.bias_audio = args->key_bias_audio;
+        a.temb_video = args->temb_video; a.temb_audio = args->temb_audio;
+        a.cross_video_ss = args->cross_video_ss; a.cross_audio_ss = args->cross_audio_ss;
+        if (sz >= offsetof(ltx_dual_forward_args, phase_mask) + sizeof(args->phase_mask)) a.phase_mask = args->phase_mask;
+        dual_forward(ctx, m, a);
     });
 }
 

@@ -31,14 +31,20 @@ const StTensor* find_tensor(const SafeTensors& st, const std::string& prefix, co
 }
 }  // namespace
 
-AttnModule* attn_module_create(int query_dim, int context_dim, int heads) {
+AttnModule* attn_module_create(int query_dim, int context_dim, int heads) { return attn_module_create_ex(query_dim, context_dim, heads, 64, false); }
+
+AttnModule* attn_module_create_ex(int query_dim, int context_dim, int heads, int head_dim, bool fused_qk) {
     if (heads < 1 || heads > 128 || query_dim < 64 || context_dim < 64 || query_dim % 64 != 0 || context_dim % 64 != 0 || query_dim > 8192 ||
         context_dim > 8192)
         LTX_THROW(LTXS_INVALID_CONFIGURATION, "attention module: query_dim %d / context_dim %d must be multiples of 64 up to 8192, heads %d in 1 .. 128",
                   query_dim, context_dim, heads);
+    if ((head_dim != 64 && head_dim != 128) || (long)heads * head_dim > 8192 || (fused_qk && context_dim != query_dim))
+        LTX_THROW(LTXS_INVALID_CONFIGURATION, "attention module: head dim %d (64 or 128), inner dim up to 8192, fused q|k only for self-attention", head_dim);
     AttnModule* m = new AttnModule();
     m->heads = heads;
-    m->inner = heads * 64;
+    m->head_dim = head_dim;
+    m->fused_qk = fused_qk;
+    m->inner = heads * head_dim;
     m->Dq = query_dim;
     m->Dc = context_dim;
     const long I = m->inner, Dq = query_dim, Dc = context_dim;
@@ -47,19 +53,30 @@ AttnModule* attn_module_create(int query_dim, int context_dim, int heads) {
     m->k.in = m->v.in = (int)Dc;
     m->o.out = (int)Dq;
     m->o.in = (int)I;
-    const Pending pend[] = {
+    // fused: to_k directly behind to_q, weights and biases (every size here is a multiple of the arena's 256-byte grain)
+    const Pending plain[] = {
         {"to_q.weight", (void**)&m->q.w, SLOT_BF16, I, Dq},     {"to_q.bias", (void**)&m->q.b, SLOT_F32, I, 0},
         {"to_k.weight", (void**)&m->k.w, SLOT_BF16, I, Dc},     {"to_k.bias", (void**)&m->k.b, SLOT_F32, I, 0},
         {"to_v.weight", (void**)&m->v.w, SLOT_BF16, I, Dc},     {"to_v.bias", (void**)&m->v.b, SLOT_F32, I, 0},
         {"to_out.weight", (void**)&m->o.w, SLOT_BF16, Dq, I},   {"to_out.bias", (void**)&m->o.b, SLOT_F32, Dq, 0},
         {"q_norm.weight", (void**)&m->qn, SLOT_F32, I, 0},      {"k_norm.weight", (void**)&m->kn, SLOT_F32, I, 0},
     };
+    const Pending fused[] = {
+        {"to_q.weight", (void**)&m->q.w, SLOT_BF16, I, Dq},     {"to_k.weight", (void**)&m->k.w, SLOT_BF16, I, Dc},
+        {"to_q.bias", (void**)&m->q.b, SLOT_F32, I, 0},         {"to_k.bias", (void**)&m->k.b, SLOT_F32, I, 0},
+        {"to_v.weight", (void**)&m->v.w, SLOT_BF16, I, Dc},     {"to_v.bias", (void**)&m->v.b, SLOT_F32, I, 0},
+        {"to_out.weight", (void**)&m->o.w, SLOT_BF16, Dq, I},   {"to_out.bias", (void**)&m->o.b, SLOT_F32, Dq, 0},
+        {"q_norm.weight", (void**)&m->qn, SLOT_F32, I, 0},      {"k_norm.weight", (void**)&m->kn, SLOT_F32, I, 0},
+    };
+    const Pending* pend = fused_qk ? fused : plain;
+    const int npend = 10;
     size_t total = 0;
-    for (const Pending& p : pend) total += DeviceArena::padded(slot_bytes(p.kind, p.rows * (p.cols ? p.cols : 1)));
+    for (int i = 0; i < npend; ++i) total += DeviceArena::padded(slot_bytes(pend[i].kind, pend[i].rows * (pend[i].cols ? pend[i].cols : 1)));
     try {
         m->arena.reserve(total + 256);
         HIP_CHECK(hipMemset(m->arena.buf.p, 0, m->arena.buf.bytes));
-        for (const Pending& p : pend) {
+        for (int i = 0; i < npend; ++i) {
+            const Pending& p = pend[i];
             ParamSlot s;
             s.kind = p.kind;
             s.rows = p.rows;
@@ -68,6 +85,8 @@ AttnModule* attn_module_create(int query_dim, int context_dim, int heads) {
             s.dst = *p.dst = m->arena.take(slot_bytes(p.kind, s.numel));
             m->slots[p.key] = s;
         }
+        if (fused_qk && (m->k.w != m->q.w + I * Dq || m->k.b != m->q.b + I))
+            LTX_THROW(LTXS_GENERATION_FAILED, "attention module: the fused q|k rows are not contiguous");
     } catch (...) {
         delete m;
         throw;
@@ -232,4 +251,98 @@ void attn_module_forward(ltx_ctx* ctx, AttnModule* m, const AttnModuleArgs& a) {
     eo.out_f32 = a.out;
     eo.ld_f32 = Dq;
     gemm_linear(ao, I, m->o, (int)qrows, eo, st);
+}
+
+void attn_core_reserve(const AttnModule* m, AttnCoreScratch* ws, AttnVtSlot* vt, int B, int Tq, int Tk) {
+    const long I = m->inner, qrows = (long)B * Tq, krows = (long)B * Tk;
+    const int Tpad = ((Tk + 63) / 64) * 64;
+    ws->qraw.ensure((size_t)qrows * I * 4 * (m->fused_qk ? 2 : 1));
+    ws->kraw.ensure((size_t)krows * I * 4);
+    ws->q.ensure((size_t)qrows * I * 2);
+    ws->k.ensure((size_t)krows * I * 2);
+    ws->ao.ensure((size_t)qrows * I * 2);
+    if (m->head_dim == 128) {
+        const long need = attn_split_ws_bytes(B, m->heads, Tq, Tk);
+        if (need > 0) ws->attn_split.ensure((size_t)need);
+    }
+    if (vt->buf.ensure((size_t)B * I * Tpad * 2)) vt->inner = vt->Tpad = vt->B = 0;  // new memory: zeroed by the first launch sequence
+}
+
+void attn_module_core(ltx_ctx* ctx, AttnModule* m, const AttnCoreArgs& a, AttnCoreScratch* ws, AttnVtSlot* vs) {
+    hipStream_t st = ctx->stream;
+    const int I = m->inner, Dq = m->Dq, Dc = m->Dc, B = a.B, Tq = a.Tq, Tk = a.Tk, hd = m->head_dim;
+    const long qrows = (long)B * Tq, krows = (long)B * Tk;
+    const int Tpad = ((Tk + 63) / 64) * 64;
+    const SplitWs sk{a.split_ws, a.split_ws_elems};
+    if (vs->inner != I || vs->Tpad != Tpad || vs->B != B) {  // the pad columns of V^T must be finite
+        HIP_CHECK(hipMemsetAsync(vs->buf.p, 0, (size_t)B * I * Tpad * 2, st));
+        vs->inner = I;
+        vs->Tpad = Tpad;
+        vs->B = B;
+    }
+    const bf16_t* cb = a.ctx ? a.ctx : a.xq;
+    const bool kb = a.kv_bf16 != 0;
+    float* qraw = ws->qraw.as<float>();
+    float* kraw = ws->kraw.as<float>();
+    bf16_t* q = ws->q.as<bf16_t>();
+    bf16_t* k = ws->k.as<bf16_t>();
+    bf16_t* vt = vs->buf.as<bf16_t>();
+    bf16_t* ao = ws->ao.as<bf16_t>();
+    const float qscale = hd == 64 ? kAttnQueryPrescale64 : kAttnQueryPrescale;
+    const float* kc = a.q_cos ? (a.k_cos ? a.k_cos : a.q_cos) : nullptr;
+    const float* ks = a.q_cos ? (a.k_cos ? a.k_sin : a.q_sin) : nullptr;
+
+    if (m->fused_qk && !a.ctx) {
+        // q | k of the same rows: one GEMM over the [2 inner][Dq] matrix, one norm + RoPE launch with two jobs
+        LinearW qk = m->q;
+        qk.out = 2 * I;
+        GemmEpilogue e;
+        e.out_f32 = qraw;
+        e.ld_f32 = 2 * I;
+        gemm_linear(a.xq, Dq, qk, (int)qrows, e, st, sk);
+        launch_qknorm_rope2(qraw, m->qn, q, qraw + I, m->kn, k, 2 * I, I, a.q_cos, a.q_sin, Tq, (int)qrows, I, m->eps, st, qscale, false, hd);
+    } else {
+        GemmEpilogue eq;
+        eq.out_f32 = qraw;
+        eq.ld_f32 = I;
+        gemm_linear(a.xq, Dq, m->q, (int)qrows, eq, st, sk);
+        GemmEpilogue ek;
+        if (kb) {
+            ek.out_bf16 = (bf16_t*)kraw;
+            ek.ld_bf16 = I;
+        } else {
+            ek.out_f32 = kraw;
+            ek.ld_f32 = I;
+        }
+        gemm_linear(cb, Dc, m->k, (int)krows, ek, st, sk);
+        // q and k come from different inputs, token counts and tables: two one-job launches
+        launch_qknorm_rope(qraw, I, m->qn, a.q_cos, a.q_sin, Tq, q, I, (int)qrows, I, m->eps, st, qscale, false, hd);
+        launch_qknorm_rope(kraw, I, m->kn, kc, ks, Tk, k, I, (int)krows, I, m->eps, st, 1.0f, kb, hd);
+    }
+    for (int b = 0; b < B; ++b) gemm_vt(cb + (size_t)b * Tk * Dc, Dc, Tk, m->v, vt + (size_t)b * I * Tpad, Tpad, st, sk);
+
+    AttnArgs at;
+    at.head_dim = hd;
+    at.Q = q; at.ldq = I; at.q_bstride = (long)Tq * I;
+    at.K = k; at.ldk = I; at.k_bstride = (long)Tk * I;
+    at.Vt = vt; at.ldvt = Tpad; at.vt_bstride = (long)I * Tpad;
+    at.O = ao; at.ldo = I; at.o_bstride = (long)Tq * I;
+    at.bias = a.key_bias; at.bias_bstride = Tk;
+    at.B = B; at.H = m->heads; at.Tq = Tq; at.Tk = Tk;
+    if (hd == 64) at.scale = 0.125f;
+    at.q_prescaled = 1;
+    if (hd == 128) {
+        at.split_ws = ws->attn_split.p;
+        at.split_ws_bytes = (long)ws->attn_split.bytes;
+    }
+    launch_attention(at, st);
+
+    GemmEpilogue eo;
+    eo.out_f32 = a.x;
+    eo.ld_f32 = Dq;
+    eo.resid = 1;
+    eo.gate = a.gate;
+    eo.gate_bstride = a.gate_bstride;
+    eo.rows_per_batch = Tq;
+    gemm_linear(ao, I, m->o, (int)qrows, eo, st, sk);
 }

@@ -18,6 +18,12 @@
 //   5. Inside the attention kernel P is rounded to bf16 for the PV product (f32 accumulation); its output is bf16.
 //   6. to_out accumulates in f32 and writes f32 [B][Tq][Dq].
 // Scratch is owned by the module, grows to the largest shape seen and is reused: nothing is allocated per call.
+//
+// attn_module_core is the same sequence for a caller that is a block (dual_block.cpp): its query and context rows arrive as bf16,
+// already normed and modulated (rounding point 1 is the caller's), the scratch is the caller's, and to_out ends in the gated-residual
+// epilogue straight into the caller's f32 stream. A module made by attn_module_create_ex may have 128-wide heads (the video half of
+// the dual block) and, for self-attention, to_q and to_k stored as one [2 inner][Dq] matrix so that one GEMM feeds the norm + RoPE
+// pass (the DiT's layout). attn_module_forward takes neither: it is unchanged.
 #pragma once
 #include <map>
 #include <string>
@@ -27,6 +33,8 @@
 
 struct AttnModule {
     int heads = 0, inner = 0, Dq = 0, Dc = 0;
+    int head_dim = 64;      // 128: attn_module_create_ex only
+    bool fused_qk = false;  // to_q | to_k contiguous, q.w [2 inner][Dq] and q.b [2 inner] (attn_module_create_ex, Dc == Dq)
     float eps = 1e-6f;
     DeviceArena arena;
     LinearW q, k, v, o;
@@ -37,6 +45,7 @@ struct AttnModule {
 };
 
 AttnModule* attn_module_create(int query_dim, int context_dim, int heads);
+AttnModule* attn_module_create_ex(int query_dim, int context_dim, int heads, int head_dim, bool fused_qk);
 void attn_module_destroy(AttnModule* m);
 void attn_module_init_synthetic(ltx_ctx* ctx, AttnModule* m, uint64_t seed);
 // shapes of a module stored under `prefix` (e.g. "transformer_blocks.0.audio_to_video_attn.") in a safetensors file; the file's own
@@ -60,3 +69,35 @@ struct AttnModuleArgs {
     float* out = nullptr;            // [B][Tq][Dq] f32
 };
 void attn_module_forward(ltx_ctx* ctx, AttnModule* m, const AttnModuleArgs& a);
+
+// ---- the core a block calls ----
+// V^T of one attention of the caller: [B][inner][Tpad] bf16 whose pad columns must be finite. The slot remembers the layout it holds
+// and is zeroed (on the stream) when the layout changes.
+struct AttnVtSlot {
+    DevBuf buf;
+    int inner = 0, Tpad = 0, B = 0;
+};
+// scratch shared by the attentions of one caller, sized by attn_core_reserve for each of them before the first launch
+struct AttnCoreScratch {
+    DevBuf qraw, kraw, q, k, ao, attn_split;
+};
+struct AttnCoreArgs {
+    const bf16_t* xq = nullptr;    // [B][Tq][Dq] bf16: the normed (and modulated) query rows
+    const bf16_t* ctx = nullptr;   // [B][Tk][Dc] bf16 context rows; null = self-attention over xq (Tk == Tq)
+    int kv_bf16 = 0;               // text context: k is rounded to bf16 after its projection and after the norm (rounding point 3)
+    int B = 1, Tq = 0, Tk = 0;
+    const float* q_cos = nullptr;  // [>= Tq][inner/2]; null = no RoPE
+    const float* q_sin = nullptr;
+    const float* k_cos = nullptr;  // [>= Tk][inner/2]; null with q tables: k uses q's
+    const float* k_sin = nullptr;
+    const float* key_bias = nullptr;  // [B][Tk] f32 additive or null
+    float* x = nullptr;            // [B][Tq][Dq] f32 stream: x += gate * to_out(attention)
+    const float* gate = nullptr;   // [B][gate_bstride] rows, Dq valid columns; null = plain residual
+    long gate_bstride = 0;
+    float* split_ws = nullptr;     // optional split-K workspace of the GEMMs (floats)
+    long split_ws_elems = 0;
+};
+// grows the scratch for one attention of these shapes (no launch; may allocate)
+void attn_core_reserve(const AttnModule* m, AttnCoreScratch* ws, AttnVtSlot* vt, int B, int Tq, int Tk);
+// launches only: the caller has checked its arguments and reserved the scratch
+void attn_module_core(ltx_ctx* ctx, AttnModule* m, const AttnCoreArgs& a, AttnCoreScratch* ws, AttnVtSlot* vt);

@@ -1,0 +1,417 @@
+// dual_block.cpp - see dual_block.h. One forward = L x LTX2TransformerBlock.callAsFunction (LTX2TransformerBlock.swift:174-297).
+#include "dual_block.h"
+
+#include <string.h>
+
+#include <algorithm>
+
+#include "attention.h"
+#include "elementwise.h"
+#include "gemm.h"
+#include "linear_ops.h"
+
+namespace {
+
+long slot_bytes(int kind, long numel) { return numel * (kind == SLOT_BF16 ? 2 : 4); }
+
+struct Pending {
+    std::string key;
+    void** dst;
+    int kind;
+    long rows, cols;
+};
+
+// the module spelling of a checkpoint key (mapTransformerKey, ModelDownloader.swift:790-800; the scale_shift_table_a2v_ca_* names are
+// the same on both sides)
+std::string module_spelling(std::string k) {
+    auto sub = [&](const char* from, const char* to) {
+        const size_t n = strlen(from);
+        for (size_t at = k.find(from); at != std::string::npos; at = k.find(from, at + strlen(to))) k.replace(at, n, to);
+    };
+    sub(".norm_q.", ".q_norm.");
+    sub(".norm_k.", ".k_norm.");
+    sub(".to_out.0.", ".to_out.");
+    sub("ff.net.0.proj.", "ff.project_in.proj.");
+    sub("ff.net.2.", "ff.project_out.");
+    return k;
+}
+
+void destroy_blocks(DualStack* m) {
+    for (DualBlock& b : m->blocks)
+        for (AttnModule** a : {&b.attn1, &b.attn2, &b.audio_attn1, &b.audio_attn2, &b.a2v, &b.v2a}) {
+            if (*a) attn_module_destroy(*a);
+            *a = nullptr;
+        }
+}
+
+}  // namespace
+
+DualStack::~DualStack() { destroy_blocks(this); }
+
+DualStack* dual_create(const DualBlockConfig& cfg) {
+    if (cfg.num_layers < 1 || cfg.num_layers > 256 || cfg.video_heads < 1 || cfg.audio_heads < 1 || cfg.video_heads > 64 || cfg.audio_heads > 128)
+        LTX_THROW(LTXS_INVALID_CONFIGURATION, "dual blocks: %d layers, %d video heads, %d audio heads", cfg.num_layers, cfg.video_heads, cfg.audio_heads);
+    if (cfg.video_dim != cfg.video_heads * 128 || cfg.audio_dim != cfg.audio_heads * 64)
+        LTX_THROW(LTXS_INVALID_CONFIGURATION, "dual blocks: video_dim %d must be %d heads x 128 and audio_dim %d must be %d heads x 64", cfg.video_dim,
+                  cfg.video_heads, cfg.audio_dim, cfg.audio_heads);
+    if (cfg.video_context_dim < 64 || cfg.audio_context_dim < 64 || cfg.video_context_dim % 64 != 0 || cfg.audio_context_dim % 64 != 0 ||
+        cfg.video_context_dim > 8192 || cfg.audio_context_dim > 8192)
+        LTX_THROW(LTXS_INVALID_CONFIGURATION, "dual blocks: context dims %d / %d must be multiples of 64 up to 8192", cfg.video_context_dim,
+                  cfg.audio_context_dim);
+    if (!(cfg.norm_eps > 0.f) || !(cfg.rope_theta > 1.f) || cfg.audio_max_pos < 1 || cfg.max_pos[0] < 1 || cfg.max_pos[1] < 1 || cfg.max_pos[2] < 1 ||
+        !(cfg.fps > 0.f))
+        LTX_THROW(LTXS_INVALID_CONFIGURATION, "dual blocks: norm_eps, rope_theta, max_pos and fps must be positive");
+    DualStack* m = new DualStack();
+    try {
+        m->cfg = cfg;
+        m->L = cfg.num_layers;
+        const int L = m->L, Dv = m->Dv = cfg.video_dim, Da = m->Da = cfg.audio_dim;
+        m->blocks.resize(L);
+        std::vector<Pending> pend;
+        auto lin = [&](const std::string& name, LinearW& l, int out, int in) {
+            l.out = out;
+            l.in = in;
+            pend.push_back({name + ".weight", (void**)&l.w, SLOT_BF16, out, in});
+            pend.push_back({name + ".bias", (void**)&l.b, SLOT_F32, out, 0});
+        };
+        pend.push_back({"__sst_v", (void**)&m->sst_v, SLOT_F32, (long)L * 6, Dv});
+        pend.push_back({"__sst_a", (void**)&m->sst_a, SLOT_F32, (long)L * 6, Da});
+        pend.push_back({"__sst_ca_v", (void**)&m->sst_ca_v, SLOT_F32, (long)L * 5, Dv});
+        pend.push_back({"__sst_ca_a", (void**)&m->sst_ca_a, SLOT_F32, (long)L * 5, Da});
+        for (int i = 0; i < L; ++i) {
+            DualBlock& b = m->blocks[i];
+            const std::string p = "transformer_blocks." + std::to_string(i) + ".";
+            b.attn1 = attn_module_create_ex(Dv, Dv, cfg.video_heads, 128, true);
+            b.attn2 = attn_module_create_ex(Dv, cfg.video_context_dim, cfg.video_heads, 128, false);
+            b.audio_attn1 = attn_module_create_ex(Da, Da, cfg.audio_heads, 64, true);
+            b.audio_attn2 = attn_module_create_ex(Da, cfg.audio_context_dim, cfg.audio_heads, 64, false);
+            b.a2v = attn_module_create_ex(Dv, Da, cfg.audio_heads, 64, false);
+            b.v2a = attn_module_create_ex(Da, Dv, cfg.audio_heads, 64, false);
+            const std::pair<const char*, AttnModule*> mods[] = {{"attn1.", b.attn1},           {"attn2.", b.attn2},
+                                                                 {"audio_attn1.", b.audio_attn1}, {"audio_attn2.", b.audio_attn2},
+                                                                 {"audio_to_video_attn.", b.a2v}, {"video_to_audio_attn.", b.v2a}};
+            for (auto& mm : mods) {
+                mm.second->eps = cfg.norm_eps;
+                for (auto& kv : mm.second->slots) m->slots[p + mm.first + kv.first] = kv.second;
+            }
+            lin(p + "ff.project_in.proj", b.ff1, 4 * Dv, Dv);
+            lin(p + "ff.project_out", b.ff2, Dv, 4 * Dv);
+            lin(p + "audio_ff.project_in.proj", b.aff1, 4 * Da, Da);
+            lin(p + "audio_ff.project_out", b.aff2, Da, 4 * Da);
+        }
+        size_t total = 0, total_w = 0;
+        for (auto& q : pend) (q.kind == SLOT_BF16 ? total_w : total) += DeviceArena::padded(slot_bytes(q.kind, q.rows * (q.cols ? q.cols : 1)));
+        m->arena.reserve(total + 256);
+        m->warena.reserve(total_w + 256);
+        HIP_CHECK(hipMemset(m->arena.buf.p, 0, m->arena.buf.bytes));
+        HIP_CHECK(hipMemset(m->warena.buf.p, 0, m->warena.buf.bytes));
+        for (auto& q : pend) {
+            ParamSlot s;
+            s.kind = q.kind;
+            s.rows = q.rows;
+            s.cols = q.cols;
+            s.numel = q.rows * (q.cols ? q.cols : 1);
+            s.dst = *q.dst = (q.kind == SLOT_BF16 ? m->warena : m->arena).take(slot_bytes(q.kind, s.numel));
+            if (q.key.compare(0, 2, "__") != 0) m->slots[q.key] = s;
+        }
+        for (int i = 0; i < L; ++i) {  // per-block views into the four stacked tables
+            const std::string p = "transformer_blocks." + std::to_string(i) + ".";
+            auto view = [&](const char* key, float* dst, long rows, long cols) {
+                ParamSlot s;
+                s.dst = dst;
+                s.kind = SLOT_F32;
+                s.rows = rows;
+                s.cols = cols;
+                s.numel = rows * cols;
+                m->slots[p + key] = s;
+            };
+            view("scale_shift_table", m->sst_v + (long)i * 6 * Dv, 6, Dv);
+            view("audio_scale_shift_table", m->sst_a + (long)i * 6 * Da, 6, Da);
+            view("scale_shift_table_a2v_ca_video", m->sst_ca_v + (long)i * 5 * Dv, 5, Dv);
+            view("scale_shift_table_a2v_ca_audio", m->sst_ca_a + (long)i * 5 * Da, 5, Da);
+        }
+        HIP_CHECK(hipDeviceSynchronize());
+    } catch (...) {
+        delete m;
+        throw;
+    }
+    return m;
+}
+
+void dual_destroy(DualStack* m) { delete m; }
+
+void dual_init_synthetic(ltx_ctx* ctx, DualStack* m, uint64_t seed) {
+    // Linear weights N(0, 0.02^2), biases N(0, 0.01^2), q / k norm weights 1 + N(0, 0.02^2), scale-shift tables N(0, 0.02^2); bf16 values
+    uint64_t k = 0;
+    for (auto& kv : m->slots) {
+        ParamSlot& s = kv.second;
+        const uint64_t sd = seed * 0x9E3779B97F4A7C15ull + (++k) * 0xD1B54A32D192ED03ull;
+        const std::string& key = kv.first;
+        const bool is_bias = key.size() > 5 && key.compare(key.size() - 5, 5, ".bias") == 0;
+        const bool is_norm = key.find("_norm.weight") != std::string::npos;
+        if (s.kind == SLOT_BF16)
+            launch_fill_normal_bf16((bf16_t*)s.dst, s.numel, sd, 0.f, 0.02f, ctx->stream);
+        else
+            launch_fill_normal_f32((float*)s.dst, s.numel, sd, is_norm ? 1.0f : 0.f, is_bias ? 0.01f : 0.02f, 1, ctx->stream);
+        s.loaded = true;
+    }
+    HIP_CHECK(hipStreamSynchronize(ctx->stream));
+}
+
+void dual_load(ltx_ctx* ctx, DualStack* m, const std::string& path, int first_block) {
+    if (first_block < 0) LTX_THROW(LTXS_INVALID_CONFIGURATION, "dual blocks: first_block %d", first_block);
+    SafeTensors st;
+    st.open(path);
+    ctx->n_loaded = ctx->n_missing = ctx->n_unmatched = 0;
+    for (auto& kv : m->slots) kv.second.loaded = false;
+    std::vector<uint8_t> staging;
+    const std::string tb = "transformer_blocks.";
+    for (auto& kv : st.tensors) {
+        const std::string& fk = kv.first;
+        if (fk.compare(0, tb.size(), tb) != 0) continue;
+        const size_t dot = fk.find('.', tb.size());
+        if (dot == std::string::npos || dot == tb.size() || dot - tb.size() > 6) continue;
+        int idx = 0;
+        bool digits = true;
+        for (size_t i = tb.size(); i < dot; ++i) {
+            digits = digits && fk[i] >= '0' && fk[i] <= '9';
+            idx = idx * 10 + (fk[i] - '0');
+        }
+        if (!digits || idx < first_block || idx >= first_block + m->L) continue;  // another block of the file: not this stack's
+        const std::string mk = tb + std::to_string(idx - first_block) + module_spelling(fk.substr(dot));
+        auto it = m->slots.find(mk);
+        if (it == m->slots.end()) {
+            ctx->n_unmatched++;  // e.g. the weights of the eight RMSNorm modules: no weight is applied
+            continue;
+        }
+        ParamSlot& s = it->second;
+        const StTensor& t = kv.second;
+        const bool shape_ok = t.numel() == s.numel && (!(s.cols && t.shape.size() == 2) || (t.shape[0] == s.rows && t.shape[1] == s.cols));
+        if (!shape_ok)
+            LTX_THROW(LTXS_WEIGHT_LOADING_FAILED, "Failed to load weights: %s has %ld elements, expected [%ld, %ld]", fk.c_str(), t.numel(), s.rows, s.cols);
+        if (s.kind == SLOT_BF16) {
+            staging.resize((size_t)s.numel * 2);
+            st_to_bf16(st, t, (bf16_t*)staging.data());
+        } else {  // biases, norm weights and tables are bf16 in the file: f32 copies of those values
+            staging.resize((size_t)s.numel * 4);
+            float* f = (float*)staging.data();
+            st_to_f32(st, t, f);
+            for (long i = 0; i < s.numel; ++i) f[i] = host_bf16_to_f32(host_f32_to_bf16(f[i]));
+        }
+        HIP_CHECK(hipMemcpy(s.dst, staging.data(), staging.size(), hipMemcpyHostToDevice));
+        if (!s.loaded) ctx->n_loaded++;
+        s.loaded = true;
+    }
+    const std::string* first_missing = nullptr;
+    for (auto& kv : m->slots)
+        if (!kv.second.loaded) {
+            ctx->n_missing++;
+            if (!first_missing) first_missing = &kv.first;
+        }
+    if (first_missing)
+        LTX_THROW(LTXS_WEIGHT_LOADING_FAILED, "Failed to load weights: %s (block %d of the file) and %d more are not in %s", first_missing->c_str(),
+                  first_block, ctx->n_missing - 1, path.c_str());
+}
+
+void dual_export(ltx_ctx* ctx, DualStack* m, const ParamSlot& s, float* out) {
+    (void)m;
+    HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    if (s.kind == SLOT_F32) {
+        HIP_CHECK(hipMemcpy(out, s.dst, (size_t)s.numel * 4, hipMemcpyDeviceToHost));
+        return;
+    }
+    std::vector<bf16_t> h((size_t)s.numel);
+    HIP_CHECK(hipMemcpy(h.data(), s.dst, (size_t)s.numel * 2, hipMemcpyDeviceToHost));
+    for (long i = 0; i < s.numel; ++i) out[i] = host_bf16_to_f32(h[i]);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// forward
+// ---------------------------------------------------------------------------------------------------------------
+namespace {
+
+void upload(ltx_ctx* ctx, DevBuf& buf, const std::vector<float>& v) {
+    buf.ensure(v.size() * 4);
+    HIP_CHECK(hipMemcpyAsync(buf.p, v.data(), v.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+}
+
+void ensure_rope(ltx_ctx* ctx, DualStack* m, int F, int H, int W, int Ta) {
+    const DualBlockConfig& c = m->cfg;
+    const bool video = !(m->rope_F == F && m->rope_H == H && m->rope_W == W && m->rope_v_cos.p);
+    const bool audio = !(m->rope_Ta == Ta && m->rope_a_cos.p);
+    if (!video && !audio) return;
+    std::vector<float> vc, vs, cvc, cvs, ac, as, cac, cas;
+    const int Ia = m->Da;  // audio inner dim = audioCrossAttentionDim: the width of both cross-modal tables (LTX2Transformer.swift:210-233)
+    if (video) {
+        TransformerConfig tc;
+        tc.num_heads = c.video_heads;
+        tc.head_dim = 128;
+        tc.rope_theta = c.rope_theta;
+        for (int i = 0; i < 3; ++i) tc.max_pos[i] = c.max_pos[i];
+        rope_tables(tc, F, H, W, c.fps, &vc, &vs);
+        const std::vector<float> pos = video_temporal_positions(F, H, W, c.fps);
+        rope_tables_positions(pos.data(), (int)pos.size(), Ia, (double)c.rope_theta, c.audio_max_pos, &cvc, &cvs);
+        upload(ctx, m->rope_v_cos, vc);
+        upload(ctx, m->rope_v_sin, vs);
+        upload(ctx, m->rope_cv_cos, cvc);
+        upload(ctx, m->rope_cv_sin, cvs);
+    }
+    if (audio) {
+        const std::vector<float> pos = audio_positions(Ta);
+        rope_tables_positions(pos.data(), Ta, Ia, (double)c.rope_theta, c.audio_max_pos, &ac, &as);
+        rope_tables_positions(pos.data(), Ta, Ia, (double)c.rope_theta, c.audio_max_pos, &cac, &cas);
+        upload(ctx, m->rope_a_cos, ac);
+        upload(ctx, m->rope_a_sin, as);
+        upload(ctx, m->rope_ca_cos, cac);
+        upload(ctx, m->rope_ca_sin, cas);
+    }
+    HIP_CHECK(hipStreamSynchronize(ctx->stream));  // the host vectors go out of scope
+    if (video) {
+        m->rope_F = F;
+        m->rope_H = H;
+        m->rope_W = W;
+    }
+    if (audio) m->rope_Ta = Ta;
+}
+
+// adaLN / FFN phase of one stream (phases 7 and 8): x += gate * ff2(gelu(ff1(norm(x) * (1 + scale) + shift)))
+void ffn_phase(float* x, int D, int T, long rows, const float* mod, long mod_bs, const LinearW& ff1, const LinearW& ff2, bf16_t* xn, bf16_t* ffh,
+               float eps, const SplitWs& sk, hipStream_t st) {
+    launch_norm_mod(x, D, mod + 4L * D, mod + 3L * D, mod_bs, T, xn, D, (int)rows, D, LTX_NORM_RMS, eps, 0, st);
+    GemmEpilogue e1;
+    e1.out_bf16 = ffh;
+    e1.ld_bf16 = 4L * D;
+    e1.act = LTX_ACT_GELU_TANH;
+    gemm_linear(xn, D, ff1, (int)rows, e1, st, sk);
+    GemmEpilogue e2;
+    e2.out_f32 = x;
+    e2.ld_f32 = D;
+    e2.resid = 1;
+    e2.gate = mod + 5L * D;
+    e2.gate_bstride = mod_bs;
+    e2.rows_per_batch = T;
+    gemm_linear(ffh, 4L * D, ff2, (int)rows, e2, st, sk);
+}
+
+}  // namespace
+
+void dual_forward(ltx_ctx* ctx, DualStack* m, const DualForwardArgs& a) {
+    // every check comes before the first launch and before any allocation
+    const int L = m->L, Dv = m->Dv, Da = m->Da, B = a.B, S = a.S, Ta = a.T_a;
+    if (B < 1 || B > 8 || a.F < 1 || a.H < 1 || a.W < 1 || Ta < 1 || S < 1 || Ta > (1 << 20) || S > (1 << 20) || (long)a.F * a.H * a.W > (1 << 20))
+        LTX_THROW(LTXS_INVALID_CONFIGURATION, "dual blocks forward: bad shapes B=%d (1 .. 8) F=%d H=%d W=%d T_a=%d S=%d", B, a.F, a.H, a.W, Ta, S);
+    if (!a.x_video || !a.x_audio || !a.ctx_video || !a.ctx_audio || !a.temb_video || !a.temb_audio || !a.cross_video_ss || !a.cross_audio_ss)
+        LTX_THROW(LTXS_INVALID_CONFIGURATION, "dual blocks forward: null stream, context or modulation pointer");
+    if (a.phase_mask > 0xffu) LTX_THROW(LTXS_INVALID_CONFIGURATION, "dual blocks forward: phase_mask 0x%x has bits beyond the eight phases", a.phase_mask);
+    const unsigned phases = a.phase_mask ? a.phase_mask : 0xffu;
+    auto on = [&](int p) { return (phases >> (p - 1)) & 1u; };
+    const int Tv = a.F * a.H * a.W;
+    const long vrows = (long)B * Tv, arows = (long)B * Ta;
+    const float eps = m->cfg.norm_eps;
+    hipStream_t st = ctx->stream;
+
+    // scratch: grows to the largest shape seen
+    {
+        const DualBlock& b = m->blocks[0];  // every block has the same shapes: the V^T slots are shared by the blocks
+        attn_core_reserve(b.attn1, &m->attn_ws, &m->vt[0], B, Tv, Tv);
+        attn_core_reserve(b.audio_attn1, &m->attn_ws, &m->vt[1], B, Ta, Ta);
+        attn_core_reserve(b.attn2, &m->attn_ws, &m->vt[2], B, Tv, S);
+        attn_core_reserve(b.audio_attn2, &m->attn_ws, &m->vt[3], B, Ta, S);
+        attn_core_reserve(b.a2v, &m->attn_ws, &m->vt[4], B, Tv, Ta);
+        attn_core_reserve(b.v2a, &m->attn_ws, &m->vt[5], B, Ta, Tv);
+        m->ws_vn.ensure((size_t)vrows * Dv * 2);
+        m->ws_vn2.ensure((size_t)vrows * Dv * 2);
+        m->ws_an.ensure((size_t)arows * Da * 2);
+        m->ws_an2.ensure((size_t)arows * Da * 2);
+        m->ws_ffh.ensure((size_t)std::max(vrows * 4 * Dv, arows * 4 * Da) * 2);
+        m->ws_splitk.ensure((size_t)8 << 22);
+        if (!a.bias_video || !a.bias_audio) m->zero_bias.ensure((size_t)B * S * 4, true);  // a growing buffer is zeroed again
+        m->mod_v.ensure((size_t)B * L * 6 * Dv * 4);
+        m->mod_a.ensure((size_t)B * L * 6 * Da * 4);
+        m->mod_ca_v.ensure((size_t)B * L * 5 * Dv * 4);
+        m->mod_ca_a.ensure((size_t)B * L * 5 * Da * 4);
+    }
+    ensure_rope(ctx, m, a.F, a.H, a.W, Ta);
+
+    const SplitWs sk{m->ws_splitk.as<float>(), (long)(m->ws_splitk.bytes / 4)};
+    bf16_t* vn = m->ws_vn.as<bf16_t>();
+    bf16_t* vn2 = m->ws_vn2.as<bf16_t>();
+    bf16_t* an = m->ws_an.as<bf16_t>();
+    bf16_t* an2 = m->ws_an2.as<bf16_t>();
+    bf16_t* ffh = m->ws_ffh.as<bf16_t>();
+    float* xv = a.x_video;
+    float* xa = a.x_audio;
+    const float* bias_v = a.bias_video ? a.bias_video : m->zero_bias.as<float>();  // null = all zeros, bit for bit
+    const float* bias_a = a.bias_audio ? a.bias_audio : m->zero_bias.as<float>();
+
+    // mod[b][l][j][:] = table[l][j][:] + rows[b][j][:] for every block at once (the reference adds them per block: :182,195,229,230)
+    launch_make_mod(m->sst_v, a.temb_video, m->mod_v.as<float>(), B, L, 6, Dv, st);
+    launch_make_mod(m->sst_a, a.temb_audio, m->mod_a.as<float>(), B, L, 6, Da, st);
+    launch_make_mod(m->sst_ca_v, a.cross_video_ss, m->mod_ca_v.as<float>(), B, L, 5, Dv, st);
+    launch_make_mod(m->sst_ca_a, a.cross_audio_ss, m->mod_ca_a.as<float>(), B, L, 5, Da, st);
+    const long mv_bs = (long)L * 6 * Dv, ma_bs = (long)L * 6 * Da, cv_bs = (long)L * 5 * Dv, ca_bs = (long)L * 5 * Da;
+
+    auto core = [&](AttnModule* mod, AttnVtSlot* vt, const bf16_t* xq, const bf16_t* cx, int kvb, int Tq, int Tk, const float* qc, const float* qs,
+                    const float* kc, const float* ks, const float* bias, float* x, const float* gate, long gbs) {
+        AttnCoreArgs c;
+        c.xq = xq; c.ctx = cx; c.kv_bf16 = kvb;
+        c.B = B; c.Tq = Tq; c.Tk = Tk;
+        c.q_cos = qc; c.q_sin = qs; c.k_cos = kc; c.k_sin = ks;
+        c.key_bias = bias;
+        c.x = x; c.gate = gate; c.gate_bstride = gbs;
+        c.split_ws = sk.p; c.split_ws_elems = sk.elems;
+        attn_module_core(ctx, mod, c, &m->attn_ws, vt);
+    };
+    const float* rvc = m->rope_v_cos.as<float>();
+    const float* rvs = m->rope_v_sin.as<float>();
+    const float* rac = m->rope_a_cos.as<float>();
+    const float* ras = m->rope_a_sin.as<float>();
+    const float* cvc = m->rope_cv_cos.as<float>();
+    const float* cvs = m->rope_cv_sin.as<float>();
+    const float* cac = m->rope_ca_cos.as<float>();
+    const float* cas = m->rope_ca_sin.as<float>();
+
+    for (int l = 0; l < L; ++l) {
+        DualBlock& b = m->blocks[l];
+        const float* mv = m->mod_v.as<float>() + (long)l * 6 * Dv;     // rows: 0 shift_msa 1 scale_msa 2 gate_msa 3 shift_mlp 4 scale_mlp 5 gate_mlp
+        const float* ma = m->mod_a.as<float>() + (long)l * 6 * Da;
+        const float* cv = m->mod_ca_v.as<float>() + (long)l * 5 * Dv;  // rows: 0 a2v scale 1 a2v shift 2 v2a scale 3 v2a shift 4 gate
+        const float* ca = m->mod_ca_a.as<float>() + (long)l * 5 * Da;
+        if (on(1)) {  // video self-attention
+            launch_norm_mod(xv, Dv, mv + 1L * Dv, mv, mv_bs, Tv, vn, Dv, (int)vrows, Dv, LTX_NORM_RMS, eps, 0, st);
+            core(b.attn1, &m->vt[0], vn, nullptr, 0, Tv, Tv, rvc, rvs, nullptr, nullptr, nullptr, xv, mv + 2L * Dv, mv_bs);
+        }
+        if (on(2)) {  // audio self-attention
+            launch_norm_mod(xa, Da, ma + 1L * Da, ma, ma_bs, Ta, an, Da, (int)arows, Da, LTX_NORM_RMS, eps, 0, st);
+            core(b.audio_attn1, &m->vt[1], an, nullptr, 0, Ta, Ta, rac, ras, nullptr, nullptr, nullptr, xa, ma + 2L * Da, ma_bs);
+        }
+        if (on(3)) {  // video text cross-attention on norm2(x_v)
+            launch_norm_mod(xv, Dv, nullptr, nullptr, 0, Tv, vn, Dv, (int)vrows, Dv, LTX_NORM_RMS, eps, 0, st);
+            core(b.attn2, &m->vt[2], vn, a.ctx_video, 1, Tv, S, nullptr, nullptr, nullptr, nullptr, bias_v, xv, nullptr, 0);
+        }
+        if (on(4)) {  // audio text cross-attention on audio_norm2(x_a)
+            launch_norm_mod(xa, Da, nullptr, nullptr, 0, Ta, an, Da, (int)arows, Da, LTX_NORM_RMS, eps, 0, st);
+            core(b.audio_attn2, &m->vt[3], an, a.ctx_audio, 1, Ta, S, nullptr, nullptr, nullptr, nullptr, bias_a, xa, nullptr, 0);
+        }
+        if (on(5) || on(6)) {
+            // normVCA / normACA once, before either update; vn / an: the a2v operands, vn2 / an2: the v2a operands
+            if (m->use_norm_mod2) {
+                NormMod2Job jv, ja;
+                jv.x = xv; jv.ldx = Dv; jv.scale0 = cv; jv.shift0 = cv + 1L * Dv; jv.scale1 = cv + 2L * Dv; jv.shift1 = cv + 3L * Dv;
+                jv.mod_bstride = cv_bs; jv.rows_per_batch = Tv; jv.out0 = vn; jv.out1 = vn2; jv.ldo = Dv; jv.rows = (int)vrows; jv.D = Dv;
+                ja.x = xa; ja.ldx = Da; ja.scale0 = ca; ja.shift0 = ca + 1L * Da; ja.scale1 = ca + 2L * Da; ja.shift1 = ca + 3L * Da;
+                ja.mod_bstride = ca_bs; ja.rows_per_batch = Ta; ja.out0 = an; ja.out1 = an2; ja.ldo = Da; ja.rows = (int)arows; ja.D = Da;
+                launch_norm_mod2(jv, ja, eps, st);
+            } else {
+                launch_norm_mod(xv, Dv, cv, cv + 1L * Dv, cv_bs, Tv, vn, Dv, (int)vrows, Dv, LTX_NORM_RMS, eps, 0, st);
+                launch_norm_mod(xv, Dv, cv + 2L * Dv, cv + 3L * Dv, cv_bs, Tv, vn2, Dv, (int)vrows, Dv, LTX_NORM_RMS, eps, 0, st);
+                launch_norm_mod(xa, Da, ca, ca + 1L * Da, ca_bs, Ta, an, Da, (int)arows, Da, LTX_NORM_RMS, eps, 0, st);
+                launch_norm_mod(xa, Da, ca + 2L * Da, ca + 3L * Da, ca_bs, Ta, an2, Da, (int)arows, Da, LTX_NORM_RMS, eps, 0, st);
+            }
+            if (on(5)) core(b.a2v, &m->vt[4], vn, an, 0, Tv, Ta, cvc, cvs, cac, cas, nullptr, xv, cv + 4L * Dv, cv_bs);
+            if (on(6)) core(b.v2a, &m->vt[5], an2, vn2, 0, Ta, Tv, cac, cas, cvc, cvs, nullptr, xa, ca + 4L * Da, ca_bs);
+        }
+        if (on(7)) ffn_phase(xv, Dv, Tv, vrows, mv, mv_bs, b.ff1, b.ff2, vn, ffh, eps, sk, st);
+        if (on(8)) ffn_phase(xa, Da, Ta, arows, ma, ma_bs, b.aff1, b.aff2, an, ffh, eps, sk, st);
+    }
+}

@@ -15,6 +15,29 @@ void launch_norm_mod(const float* x, long ldx, const float* scale, const float* 
                      int rows_per_batch, bf16_t* out, long ldo, int rows, int D, int norm_kind, float eps,
                      int round_norm_bf16, hipStream_t stream, const int32_t* row_map = nullptr);
 
+// The cross-modal norms of the dual video + audio block (LTX2TransformerBlock.swift:246-263): audio_to_video_norm(x_v) and
+// video_to_audio_norm(x_a) are each computed ONCE and modulated twice - a2v query / v2a key rows of the video stream, a2v key / v2a
+// query rows of the audio stream. One launch, two jobs (video rows at Dv, audio rows at Da; rows == 0: the job is empty): every f32 row
+// is read once, RMS-normed once and written twice as bf16, out0 = norm * (1 + scale0[b]) + shift0[b] and out1 likewise with
+// (scale1, shift1), b = row / rows_per_batch. A null (scale, shift) pair writes the plain norm. D % 4 == 0 up to 8192, ldx / ldo >= D
+// and multiples of 4. Reduction order of norm_mod_kernel (wave sums added in wave order): each output is bit-equal to the
+// launch_norm_mod call (LTX_NORM_RMS, round_norm_bf16 = 0) it replaces. Every check comes before the launch.
+struct NormMod2Job {
+    const float* x = nullptr;       // [rows][ldx] f32
+    long ldx = 0;
+    const float* scale0 = nullptr;  // [B][mod_bstride] f32 rows, D valid columns
+    const float* shift0 = nullptr;
+    const float* scale1 = nullptr;
+    const float* shift1 = nullptr;
+    long mod_bstride = 0;
+    int rows_per_batch = 1;
+    bf16_t* out0 = nullptr;         // [rows][ldo] bf16
+    bf16_t* out1 = nullptr;
+    long ldo = 0;
+    int rows = 0, D = 0;
+};
+void launch_norm_mod2(const NormMod2Job& video, const NormMod2Job& audio, float eps, hipStream_t stream);
+
 // q/k RMSNorm across ALL heads with learnable weight, then split-RoPE per head (LTXAttention.swift:179-189,
 // LTXRoPE.swift:84-149). x: f32 [rows][ldx] (D valid columns), w: f32 [D], cos/sin: f32 [T][D/2] indexed by
 // (row % T) with per-head slices of 64 (nullable -> no RoPE, cross-attention). out: bf16 [rows][ldo].

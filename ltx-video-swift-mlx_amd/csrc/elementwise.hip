@@ -177,6 +177,88 @@ __global__ __launch_bounds__(256) void norm_mod_rows_kernel(const float* __restr
     }
 }
 
+// norm_mod_kernel for the cross-modal norms of the dual block (elementwise.h, NormMod2Job): one workgroup per row of either job
+// (workgroups 0 .. j0.rows-1 take job 0, the rest job 1; the choice is uniform per workgroup). The row and both pairs of modulation
+// vectors are fetched before the reduction, as norm_mod_kernel fetches its one pair; the row is normed once and stored twice. Same
+// per-thread chunk assignment, same sum of squares per thread, same block_reduce_sum: out0 and out1 carry norm_mod_kernel's bits.
+template <int NV>
+__global__ __launch_bounds__(256) void norm_mod2_kernel(const NormMod2Job j0, const NormMod2Job j1, float eps) {
+    __shared__ float red[4];
+    constexpr bool EARLY = NV <= 4;  // NV = 8 (D > 4096) would hold 5 x 32 row registers across the barrier: it fetches the vectors after it
+    const bool second = (int)blockIdx.x >= j0.rows;
+    const int row = second ? (int)blockIdx.x - j0.rows : (int)blockIdx.x;
+    const int D = second ? j1.D : j0.D;
+    const long ldx = second ? j1.ldx : j0.ldx, ldo = second ? j1.ldo : j0.ldo, mbs = second ? j1.mod_bstride : j0.mod_bstride;
+    const float* xr = (second ? j1.x : j0.x) + (long)row * ldx;
+    const long moff = (long)(row / (second ? j1.rows_per_batch : j0.rows_per_batch)) * mbs;
+    const float* sc0 = second ? j1.scale0 : j0.scale0;
+    const float* sh0 = second ? j1.shift0 : j0.shift0;
+    const float* sc1 = second ? j1.scale1 : j0.scale1;
+    const float* sh1 = second ? j1.shift1 : j0.shift1;
+    f32x4 v[NV], s0[NV], h0[NV], s1[NV], h1[NV];
+    const int nchunk = D >> 2;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        const int c = threadIdx.x + i * 256;
+        v[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (c < nchunk) v[i] = *(const f32x4*)(xr + c * 4);
+    }
+    auto fetch = [&](int i) {
+        const int c = threadIdx.x + i * 256;
+        if (c < nchunk) {
+            if (sc0) {
+                s0[i] = *(const f32x4*)(sc0 + moff + c * 4);
+                h0[i] = *(const f32x4*)(sh0 + moff + c * 4);
+            }
+            if (sc1) {
+                s1[i] = *(const f32x4*)(sc1 + moff + c * 4);
+                h1[i] = *(const f32x4*)(sh1 + moff + c * 4);
+            }
+        }
+    };
+    if constexpr (EARLY) {
+#pragma unroll
+        for (int i = 0; i < NV; ++i) fetch(i);
+    }
+    float s2 = 0.f;
+#pragma unroll
+    for (int i = 0; i < NV; ++i)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) s2 += v[i][e] * v[i][e];
+    const float ms = block_reduce_sum(s2, red) / (float)D;
+    const float rstd = rsqrtf(ms + eps);
+    bf16_t* o0 = (second ? j1.out0 : j0.out0) + (long)row * ldo;
+    bf16_t* o1 = (second ? j1.out1 : j0.out1) + (long)row * ldo;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        const int c = threadIdx.x + i * 256;
+        if (c < nchunk) {
+            if constexpr (!EARLY) fetch(i);
+            f32x4 y, ya, yb;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                y[e] = v[i][e] * rstd;
+                ya[e] = yb[e] = y[e];
+            }
+            if (sc0) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) ya[e] = y[e] * (1.0f + s0[i][e]) + h0[i][e];
+            }
+            if (sc1) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) yb[e] = y[e] * (1.0f + s1[i][e]) + h1[i][e];
+            }
+            uint2 pa, pb;
+            pa.x = pack_bf16x2(ya[0], ya[1]);
+            pa.y = pack_bf16x2(ya[2], ya[3]);
+            pb.x = pack_bf16x2(yb[0], yb[1]);
+            pb.y = pack_bf16x2(yb[2], yb[3]);
+            *(uint2*)(o0 + c * 4) = pa;
+            *(uint2*)(o1 + c * 4) = pb;
+        }
+    }
+}
+
 // one workgroup per row; thread handles float4 chunks of the first half `a` of a head and the matching `b` chunk.
 // blockIdx.y selects the job (q or k of the fused projection): one launch normalises and rotates both. The weight and
 // cos/sin chunks are fetched with the row, before the reduction (same reason as norm_mod_kernel).
@@ -717,6 +799,35 @@ void launch_norm_mod(const float* x, long ldx, const float* scale, const float* 
     else if (D <= 4096) LTX_NORM_LAUNCH(4);
     else LTX_NORM_LAUNCH(8);
 #undef LTX_NORM_LAUNCH
+    HIP_CHECK(hipGetLastError());
+}
+
+void launch_norm_mod2(const NormMod2Job& video, const NormMod2Job& audio, float eps, hipStream_t stream) {
+    int maxD = 0;
+    for (const NormMod2Job* j : {&video, &audio}) {
+        LTX_REQUIRE(j->rows >= 0, "norm_mod2: rows=%d", j->rows);
+        if (j->rows == 0) continue;
+        LTX_REQUIRE(j->x && j->out0 && j->out1, "norm_mod2: null row or output pointer");
+        LTX_REQUIRE(j->D >= 4 && j->D % 4 == 0 && j->D <= MAXV * 1024 && j->ldx % 4 == 0 && j->ldo % 4 == 0 && j->ldx >= j->D && j->ldo >= j->D,
+                    "norm_mod2: D=%d ldx=%ld ldo=%ld", j->D, j->ldx, j->ldo);
+        LTX_REQUIRE((j->scale0 == nullptr) == (j->shift0 == nullptr) && (j->scale1 == nullptr) == (j->shift1 == nullptr),
+                    "norm_mod2: scale/shift must both be set or both null");
+        LTX_REQUIRE(j->rows_per_batch >= 1 && j->mod_bstride >= 0, "norm_mod2: rows_per_batch=%d mod_bstride=%ld", j->rows_per_batch, j->mod_bstride);
+        if (j->D > maxD) maxD = j->D;
+    }
+    const long total = (long)video.rows + audio.rows;
+    LTX_REQUIRE(total <= 0x7fffffffL, "norm_mod2: %ld rows", total);
+    if (total == 0) return;
+    ProfScope prof(PROF_ELEM, ((double)video.rows * video.D + (double)audio.rows * audio.D) * (4 + 2 + 2), stream);  // f32 row in, two bf16 rows out
+    NormMod2Job j0 = video, j1 = audio;
+    if (j0.rows_per_batch < 1) j0.rows_per_batch = 1;  // an empty job is never indexed, but never divided by zero either
+    if (j1.rows_per_batch < 1) j1.rows_per_batch = 1;
+#define LTX_NORM2_LAUNCH(NV) hipLaunchKernelGGL(norm_mod2_kernel<NV>, dim3((unsigned)total), dim3(256), 0, stream, j0, j1, eps)
+    if (maxD <= 1024) LTX_NORM2_LAUNCH(1);
+    else if (maxD <= 2048) LTX_NORM2_LAUNCH(2);
+    else if (maxD <= 4096) LTX_NORM2_LAUNCH(4);
+    else LTX_NORM2_LAUNCH(8);
+#undef LTX_NORM2_LAUNCH
     HIP_CHECK(hipGetLastError());
 }
 

@@ -90,6 +90,7 @@ struct UpscalerModel;
 struct AudioVaeModel;
 struct VocoderModel;
 struct AttnModule;
+struct DualStack;
 struct DistState;
 
 // ---- live per-kernel timing (HIP events recorded on the launch stream around each launch of a kernel family) ----
@@ -158,6 +159,7 @@ struct ltx_ctx {
     AudioVaeModel* audio_vae = nullptr;  // audio decode leg (audio.h)
     VocoderModel* vocoder = nullptr;
     AttnModule* attn_modules[kAttnModuleSlots] = {};  // head-dim-64 attention modules by index (attn_module.h)
+    DualStack* dual = nullptr;  // dual video + audio transformer blocks (dual_block.h)
     DevBuf audio_mel, audio_op[2];  // the mel between the two audio models; haloed operands of the audio conv test hooks
     DevBuf h2d[H2D_COUNT];  // staging buffers of the host-pointer entry points, indexed by H2dSlot
     // load report of the last *_load call (mirrors the reference's "unmatched/missing" debug logs)
