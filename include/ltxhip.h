@@ -682,7 +682,8 @@ int ltx_op_gemv_f32(ltx_ctx* ctx, const float* a, long lda, const uint16_t* W, l
 /* O = softmax(Q K^T * scale + bias) V ; Q [B][Tq][H*128], K [B][Tk][H*128], Vt [B][H*128][ldvt] (keys contiguous,
  * ldvt >= roundup(Tk,64)), bias [B][Tk] f32 or NULL, O [B][Tq][H*128] ; all bf16. scale <= 0: Q already carries
  * (1/sqrt(128)) * log2(e) - what the DiT's q-norm + RoPE pass writes, one rounding to bf16 - and the scores are base-2 exponents:
- * O = softmax_2(Q K^T + bias * log2(e)) V. */
+ * O = softmax_2(Q K^T + bias * log2(e)) V: the bias is in the reference's units (added after the scale) in both modes.
+ * Columns Tk..ldvt-1 of Vt are read and must hold finite values (they are multiplied by P = 0); here and in ltx_op_attention_hd. */
 int ltx_op_attention(ltx_ctx* ctx, const uint16_t* Q, const uint16_t* K, const uint16_t* Vt, long ldvt,
                      const float* bias, int B, int H, int Tq, int Tk, float scale, uint16_t* O);
 /* Number of key ranges the attention launcher divides a launch of this shape into when it has a workspace (1 = it does not): few

@@ -1,6 +1,7 @@
 """CPU tests of the host side of the audio / cross-modal attention: the 1-D position grids, the RoPE tables over real-valued
 positions, and the ABI surface of the new entries."""
 import ctypes
+import math
 import os
 import re
 import sys
@@ -107,3 +108,67 @@ def test_head_dim_64_attention_kernels_have_no_scratch(tmp_path):
     assert len(seen) == 6, [k[0] for k in kernels]
     for name, scratch, sspill, vspill in seen:
         assert int(scratch) == 0 and int(sspill) == 0 and int(vspill) == 0, f"{name}: private segment {scratch} B, spills {sspill} / {vspill}"
+
+
+# ---- the attention kernel's stress inputs, without a GPU: a numpy replay of the kernel's rounding points (attn64_ref.attention_replay)
+# meets, on every input of tests/test_attention_d64_stress_gpu.py, the bounds that file holds the kernel to ----
+def test_stress_and_edge_shapes_reach_the_instance_they_name(ltx):
+    q = ltx.Context.attention_hd_workgroup_queries
+    for instance, shape in ref.INSTANCE_SHAPES.items():
+        assert q(*shape) == instance, shape
+    for instance, B, H, Tq in ref.EDGE_SHAPES:
+        assert q(B, H, Tq) == instance, (B, H, Tq)
+    # 128 queries per workgroup are never chosen for Tq <= 128 (the reason EDGE_SHAPES starts that instance at 129)
+    assert all(q(B, H, Tq) != 128 for B in (1, 2, 3) for H in range(1, 130) for Tq in (1, 64, 127, 128))
+
+
+@pytest.mark.parametrize("case", ref.STRESS_CASES + ref.SOFT_BIAS_CASES, ids=ref.case_id)
+def test_kernel_replay_meets_the_bounds_on_the_stress_inputs(case):
+    builder, args = case
+    c = builder(*args)
+    want = c.reference()
+    got = c.replay()
+    err, rel = ref.attention_errors(got, want)
+    print(f"{c.name}: replay max abs {err:.3e} rel-L2 {rel:.3e}")
+    assert np.isfinite(got).all() and np.isfinite(want).all()
+    assert err <= c.bounds[0] and rel <= c.bounds[1], (err, rel)
+
+
+@pytest.mark.parametrize("case", ref.SOFT_BIAS_CASES, ids=ref.case_id)
+@pytest.mark.parametrize("factor", [0.125, 1.4426950408889634], ids=["bias_over_8", "bias_times_log2e"])
+def test_soft_bias_in_other_units_is_outside_the_bounds(case, factor):
+    """The soft-bias case discriminates: the reference with the bias in a wrong unit misses both bounds."""
+    builder, args = case
+    c = builder(*args)
+    err, rel = ref.attention_errors(c.reference(factor), c.reference())
+    print(f"{c.name} bias x {factor}: max abs {err:.3e} rel-L2 {rel:.3e}")
+    assert err > c.bounds[0] and rel > c.bounds[1], (err, rel)
+
+
+def test_soft_bias_at_head_dim_128_discriminates_too():
+    c = ref.soft_bias_case(64, False, heads=2, head_dim=128)
+    for factor in (1.0 / math.sqrt(128.0), 1.4426950408889634):
+        err, rel = ref.attention_errors(c.reference(factor), c.reference())
+        assert err > c.bounds[0] and rel > c.bounds[1], (factor, err, rel)
+
+
+@pytest.mark.parametrize("instance", [64, 128, 256])
+def test_masking_the_dominant_key_changes_the_reference(instance):
+    """reference_maximum, masked: the two batch elements differ only in the dominant key's bias, and their references differ at its
+    query by far more than the bound, so a kernel that ignored the bias there (or applied element 0's to both) cannot pass."""
+    c = ref.reference_maximum_case(instance, True)
+    want = c.reference()
+    row = want[:, ref.DOMINANT_QUERY, :64]
+    assert np.abs(row[0] - row[1]).max() > 10 * c.bounds[0]
+    plain = ref.reference_maximum_case(instance, False).reference()
+    assert np.array_equal(plain[0], plain[1])
+
+
+def test_one_hot_inputs_select_what_they_promise():
+    rng = np.random.default_rng(0)
+    for Tk in ref.EDGE_TK:
+        q, k, v, sel = ref.one_hot_case(rng, 2, 3, 63, Tk)
+        hit = set(sel.ravel().tolist())
+        assert {0, Tk - 1} <= hit and set(range(64 * ((Tk - 1) // 64), Tk)) <= hit, Tk
+        got = ref.attention_f64(q, k, v, 3, ref.SCALE)
+        assert np.abs(got - ref.one_hot_expected(v, sel, 3)).max() <= 1e-3, Tk

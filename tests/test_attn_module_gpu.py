@@ -115,6 +115,29 @@ def test_full_width_a2v_routes_the_real_gemm_shapes(gpu_ctx, ltx):
         gpu_ctx.attn_module_unload(0)
 
 
+@pytest.mark.parametrize("fhw,instance", [((4, 10, 20), 256), ((2, 10, 20), 128)])
+def test_full_width_cross_attention_on_the_larger_kernel_instances(gpu_ctx, ltx, fhw, instance):
+    """800 and 400 video-side queries on 32 heads against 26 keys with a key bias: 4 x 32 workgroups of 256 queries, and 4 x 32 of
+    128 - the two instances of the attention kernel that the cases above (at most 192 queries) do not launch from the module."""
+    heads, Dq, Dc = 32, 4096, 2048
+    Tq = fhw[0] * fhw[1] * fhw[2]
+    assert gpu_ctx.attention_hd_workgroup_queries(1, heads, Tq) == instance
+    gpu_ctx.attn_module_init_synthetic(0, Dq, Dc, heads, seed=22)
+    try:
+        qt = ltx.rope_tables_positions(ltx.video_temporal_positions(*fhw), heads * 64)
+        kt = ltx.rope_tables_positions(ltx.audio_positions(T_A), heads * 64)
+        rng = np.random.default_rng(8 + instance)
+        x = rng.standard_normal((1, Tq, Dq)).astype(np.float32)
+        context = rng.standard_normal((1, T_A, Dc)).astype(np.float32)
+        m = (rng.random((1, T_A)) >= 1.0 / 3.0).astype(np.float32)
+        m[:, 0] = 1
+        bias = ((1 - m) * np.float32(-10000.0)).astype(np.float32)
+        got = run(gpu_ctx, 0, x, context=context, q_tables=tuple(dev(t) for t in qt), k_tables=tuple(dev(t) for t in kt), bias=bias)
+        check(got, ref.module_forward(weights(gpu_ctx, 0, heads, Dq, Dc), x, heads, context=context, q_tables=qt, k_tables=kt, bias=bias))
+    finally:
+        gpu_ctx.attn_module_unload(0)
+
+
 def test_key_tables_default_to_the_query_tables(gpu_ctx, tables):
     """`kPe ?? pe`: only q tables = the same tables for q and k, bit for bit; different key tables change the result."""
     gpu_ctx.attn_module_init_synthetic(0, 256, 0, HEADS, seed=11)
