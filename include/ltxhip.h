@@ -299,8 +299,8 @@ int ltx_map_vae_encoder_key(const char* file_key, char* out, int cap);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Audio decode leg (decodeAudio, Vocoder.swift:325-361): audio latent -> AudioVAE.decode -> stereo mel -> LTX2Vocoder -> 24 kHz
- * stereo waveform. The dual (video + audio) transformer that PRODUCES the audio latent is not part of this library yet (its attention
- * module is: "Audio / cross-modal attention" below): the latent is an input. Precision: weights rounded to bf16 at load, bf16 conv operands, f32 accumulation, f32 residual streams.
+ * stereo waveform. The dual (video + audio) transformer that PRODUCES the audio latent is "Dual video + audio model" below; the joint
+ * denoise loop around it is not part of this library yet: the latent is an input. Precision: weights rounded to bf16 at load, bf16 conv operands, f32 accumulation, f32 residual streams.
  * ---------------------------------------------------------------------------------------------------------- */
 /* Replaces AudioVAE() + loadAudioVAEWeights / applyAudioVAEWeights (ModelDownloader.swift:1116-1158): keeps `decoder.*`, `latents_mean`
  * and `latents_std`, drops everything else; Conv2d weights are PyTorch (out, in, kh, kw) under `...conv.weight`. Channel counts come
@@ -381,8 +381,9 @@ int ltx_attn_module_forward_dev(ltx_ctx* ctx, int index, const float* x, const v
 /* ------------------------------------------------------------------------------------------------------------
  * Dual video + audio transformer blocks: LTX2TransformerBlock (LTX2TransformerBlock.swift:174-297) as a loadable stack of L blocks
  * with a forward of its own. It takes what LTX2Transformer.callAsFunction hands its blocks and returns both residual streams. The
- * embedders that make the modulation rows (audio_adaln_single, av_ca_*), the patchify / output heads, the caption projections, the
- * joint denoise loop and the CLI's --audio path are not part of this library yet. The modulation rows are one per batch element; the
+ * embedders that make the modulation rows (audio_adaln_single, av_ca_*), the patchify / output heads and the caption projections are
+ * "Dual video + audio model" below, which owns a stack of its own; the joint denoise loop and the CLI's --audio path are not part of
+ * this library yet. The modulation rows are one per batch element; the
  * reference's per-token form (image-to-video, LTX2Transformer.swift:285-312) is not implemented. A context holds one stack.
  * ---------------------------------------------------------------------------------------------------------- */
 typedef struct ltx_dual_block_config {
@@ -463,6 +464,75 @@ typedef struct ltx_norm_mod2_job {
  * LTX2TransformerBlock.swift:246-263). out0 = rmsnorm(x) * (1 + scale0) + shift0, out1 likewise with (scale1, shift1); each bit-equal
  * to ltx_op_norm_mod_ex with the same operands. Either job may be NULL or empty. Bad arguments are refused before the launch. */
 int ltx_op_norm_mod2(ltx_ctx* ctx, const ltx_norm_mod2_job* video, const ltx_norm_mod2_job* audio, float eps);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Dual video + audio model: LTX2Transformer.callAsFunction (LTX2Transformer.swift:254-392) - two latents, two text contexts and two
+ * timestep vectors in, two velocities out. The model owns a block stack of its own (as "Dual video + audio transformer blocks" above)
+ * and the top-level modules of LTX2Transformer.swift:28-48: the two patchify Linears, the six AdaLayerNormSingle embedders, the two
+ * caption projections, the two output tables and the two output Linears. A context holds one model, in a slot of its own: loading it
+ * does not disturb the ltx_dual_blocks_* stack, and the reverse. Timesteps are one value per batch element and stream; the reference's
+ * per-token form (image-to-video, LTX2Transformer.swift:285-312) is not implemented. The joint denoise loop, a text K / V^T cache across
+ * steps and the CLI's --audio path are not part of this library yet.
+ * ---------------------------------------------------------------------------------------------------------- */
+typedef struct ltx_dual_model_config {
+    ltx_dual_block_config blocks;     /* video_context_dim == video_dim, audio_context_dim == audio_dim */
+    int in_channels;                  /* 128 */
+    int out_channels;                 /* 128 */
+    int audio_in_channels;            /* 128 */
+    int audio_out_channels;           /* 128 */
+    int caption_channels;             /* 3840 */
+    float timestep_scale_multiplier;  /* 1000 */
+} ltx_dual_model_config;
+/* Filled with the reference defaults (LTXConfig.swift:83-177). */
+void ltx_dual_model_config_default(ltx_dual_model_config* cfg);
+/* Random-init model (LTX2Transformer.init, LTX2Transformer.swift:59-121) with the distributions of ltx_dual_blocks_init_synthetic for
+ * the blocks and the top-level parameters alike (the output tables N(0, 0.02^2) rather than the reference's zeros, so that a test sees
+ * them). A bad configuration: LTX_ERR_INVALID_CONFIGURATION. */
+int ltx_dual_model_init_synthetic(ltx_ctx* ctx, const ltx_dual_model_config* cfg, uint64_t seed);
+/* Replaces loadTransformerWeights(includeAudio: true) (ModelDownloader.swift:605-639). Keys in the module's spelling or in any spelling
+ * mapTransformerKey(includeAudio: true) maps onto it (ModelDownloader.swift:756-803): proj_in., time_embed.emb.timestep_embedder.,
+ * time_embed.linear., the general .emb.timestep_embedder. flattening, and the block spellings of ltx_dual_blocks_load.
+ * ltx_load_report: tensors applied / 0 / tensors that are no parameter. A parameter the file lacks: LTX_ERR_WEIGHT_LOADING_FAILED, and
+ * the context holds no model. */
+int ltx_dual_model_load(ltx_ctx* ctx, const char* safetensors_path, const ltx_dual_model_config* cfg);
+int ltx_dual_model_unload(ltx_ctx* ctx);
+/* One resident parameter as f32 by its module key ("adaln_single.emb.linear_1.weight", "audio_scale_shift_table", ...; block
+ * parameters under "transformer_blocks.{i}." as ltx_dual_blocks_export_param names them): its element count (out NULL: the count only)
+ * or a negative ltx_status. Test seam, as ltx_dit_export_param. */
+long ltx_dual_model_export_param(ltx_ctx* ctx, const char* name, float* out, long cap);
+/* Arguments of ltx_dual_model_forward_dev; starts with its own size (LTX_DUAL_MODEL_FORWARD_ARGS_INIT). All pointers are DEVICE
+ * pointers. */
+typedef struct ltx_dual_model_forward_args {
+    uint32_t struct_size;            /* sizeof(ltx_dual_model_forward_args) in the caller's translation unit */
+    int B, F, H, W;                  /* batch; latent frames / height / width: F*H*W video tokens in (f, h, w) order */
+    int T_a;                         /* audio tokens */
+    int S;                           /* text tokens of both contexts */
+    const uint16_t* video_latent;    /* [B][F*H*W][in_channels] bf16 */
+    const uint16_t* audio_latent;    /* [B][T_a][audio_in_channels] bf16 */
+    const uint16_t* video_context;   /* [B][S][caption_channels] bf16 */
+    const uint16_t* audio_context;   /* [B][S][caption_channels] bf16 */
+    const float* video_timesteps;    /* [B] f32, sigma (unscaled) */
+    const float* audio_timesteps;    /* [B] f32 */
+    const int32_t* video_mask;       /* [B][S] int32 or NULL (videoContextMask) */
+    const int32_t* audio_mask;       /* [B][S] int32 or NULL */
+    float* video_velocity;           /* [B][F*H*W][out_channels] f32 */
+    float* audio_velocity;           /* [B][T_a][audio_out_channels] f32 */
+    int ungrouped;                   /* measurement seam: non-zero runs the timestep path as 18 ltx_op_gemv_f32-style launches instead of
+                                        three grouped ones; the same bits */
+} ltx_dual_model_forward_args;
+#define LTX_DUAL_MODEL_FORWARD_ARGS_INIT {sizeof(ltx_dual_model_forward_args), 1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}
+/* Replaces LTX2Transformer.callAsFunction (LTX2Transformer.swift:254-392). Asynchronous on the context stream. No model:
+ * LTX_ERR_MODEL_NOT_LOADED; a struct_size that does not cover the fields up to audio_velocity, B outside 1 .. 8, a dimension < 1 or a
+ * NULL latent / context / timestep / velocity pointer: LTX_ERR_INVALID_CONFIGURATION. Every check comes before the first launch: a
+ * refused call writes nothing. */
+int ltx_dual_model_forward_dev(ltx_ctx* ctx, const ltx_dual_model_forward_args* args);
+/* The timestep path of the forward alone (LTX2Transformer.swift:272-312), into caller buffers: temb_v [B][6][video_dim], temb_a
+ * [B][6][audio_dim], cross_v [B][5][video_dim], cross_a [B][5][audio_dim] (rows 0-3 from the scale-shift embedder, row 4 from the
+ * gate embedder), embts_v [B][video_dim], embts_a [B][audio_dim] (the embedded timesteps of the output heads), all f32 DEVICE
+ * pointers; video_timesteps / audio_timesteps [B] f32. `ungrouped` as in the forward. Test and measurement seam, as
+ * ltx_dit_export_param is one. B outside 1 .. 8 or a NULL pointer: LTX_ERR_INVALID_CONFIGURATION, nothing written. */
+int ltx_dual_model_embed_dev(ltx_ctx* ctx, const float* video_timesteps, const float* audio_timesteps, int B, int ungrouped,
+                             float* temb_v, float* temb_a, float* cross_v, float* cross_a, float* embts_v, float* embts_a);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Text-embedding connector (VideoGemmaTextEncoderModel.encodeFromHiddenStates,
@@ -679,6 +749,24 @@ int ltx_op_gemm_bf16_gated_residual_norm(ltx_ctx* ctx, const uint16_t* A, long l
 /* out[m][n] = sum_k in_act(a[m][k]) W[n][k] + bias[n], f32 x bf16 -> f32, M <= 8 */
 int ltx_op_gemv_f32(ltx_ctx* ctx, const float* a, long lda, const uint16_t* W, long ldw, const float* bias, float* out,
                     long ldo, int M, int N, int K, int in_act);
+/* One job of ltx_op_gemv_group: the operands of ltx_op_gemv_f32 without M. */
+typedef struct ltx_gemv_job {
+    const float* a; /* [M][lda] f32 */
+    long lda;       /* lda % 4 == 0 */
+    const uint16_t* W; /* [N][ldw] bf16 */
+    long ldw;       /* ldw % 8 == 0 */
+    const float* bias; /* [N] f32 or NULL */
+    float* out;     /* [M][ldo] f32; may point into the middle of a wider row */
+    long ldo;
+    int N;          /* 0: the job is skipped */
+    int K;          /* K % 8 == 0 */
+    int in_act;     /* 0 none, 2 SiLU on the activations */
+} ltx_gemv_job;
+/* Up to 8 ltx_op_gemv_f32 jobs that share M in ONE launch, as the dual model's timestep path runs the six AdaLayerNormSingle embedders
+ * of LTX2Transformer.swift:272-312 (one launch per stage). Jobs may differ in N, K and activation. Every job is bit-equal to
+ * ltx_op_gemv_f32 on its operands. n_jobs outside 1 .. 8, M outside 1 .. 8, a K / lda / ldw that ltx_op_gemv_f32 refuses, or a NULL
+ * a / W / out with N > 0: LTX_ERR_INVALID_CONFIGURATION. Every check comes before the launch: a refused call writes nothing. */
+int ltx_op_gemv_group(ltx_ctx* ctx, const ltx_gemv_job* jobs, int n_jobs, int M);
 /* O = softmax(Q K^T * scale + bias) V ; Q [B][Tq][H*128], K [B][Tk][H*128], Vt [B][H*128][ldvt] (keys contiguous,
  * ldvt >= roundup(Tk,64)), bias [B][Tk] f32 or NULL, O [B][Tq][H*128] ; all bf16. scale <= 0: Q already carries
  * (1/sqrt(128)) * log2(e) - what the DiT's q-norm + RoPE pass writes, one rounding to bf16 - and the scores are base-2 exponents:

@@ -16,7 +16,8 @@ import numpy as np
 
 from . import _lib
 from ._lib import (ALLGATHER_FN, DIST_ID_BYTES, SHARD_CFG, SHARD_NONE, SHARD_SEQUENCE, ConnectorConfig, PROGRESS_CB, DenoiseOptions,
-                   DualBlockConfig, DualForwardArgs, LTXError, NormMod2Job, TransformerConfig, lib)
+                   DualBlockConfig, DualForwardArgs, DualModelConfig, DualModelForwardArgs, GemvJob, LTXError, NormMod2Job,
+                   TransformerConfig, lib)
 
 __version__ = lib.ltx_version().decode()
 
@@ -47,6 +48,20 @@ def default_dual_block_config(**overrides):
             for i in range(3):
                 cfg.max_pos[i] = v[i]
         else:
+            getattr(cfg, k)
+            setattr(cfg, k, v)
+    return cfg
+
+
+def default_dual_model_config(**overrides):
+    """``ltx_dual_model_config`` with the reference defaults. Keywords that name a field of the block config (``num_layers``,
+    ``video_heads``, ...) go to ``default_dual_block_config``; the others (``in_channels``, ``caption_channels``, ...) are set here."""
+    cfg = DualModelConfig()
+    lib.ltx_dual_model_config_default(C.byref(cfg))
+    block_fields = {f[0] for f in DualBlockConfig._fields_}
+    cfg.blocks = default_dual_block_config(**{k: v for k, v in overrides.items() if k in block_fields})
+    for k, v in overrides.items():
+        if k not in block_fields:
             getattr(cfg, k)
             setattr(cfg, k, v)
     return cfg
@@ -937,6 +952,68 @@ class Context:
         a.cross_video_ss, a.cross_audio_ss = _ptr(cross_video_ss), _ptr(cross_audio_ss)
         a.phase_mask = phase_mask
         self._ck(lib.ltx_dual_blocks_forward_dev(self._h, C.byref(a)))
+
+    # ---- LTX2Transformer: the dual video + audio model ----
+    def dual_model_init_synthetic(self, cfg, seed=4242):
+        self._ck(lib.ltx_dual_model_init_synthetic(self._h, C.byref(cfg), seed))
+
+    def dual_model_load(self, path, cfg):
+        self._ck(lib.ltx_dual_model_load(self._h, str(path).encode(), C.byref(cfg)))
+
+    def dual_model_unload(self):
+        self._ck(lib.ltx_dual_model_unload(self._h))
+
+    def dual_model_export_param(self, name):
+        """One resident parameter of the model as a flat f32 numpy array ("adaln_single.linear.weight", "transformer_blocks.0. ...")."""
+        n = lib.ltx_dual_model_export_param(self._h, name.encode(), None, 0)
+        if n < 0:
+            raise LTXError(-n, lib.ltx_last_error(self._h).decode(errors="replace"))
+        out = np.empty(n, dtype=np.float32)
+        n2 = lib.ltx_dual_model_export_param(self._h, name.encode(), out.ctypes.data, n)
+        if n2 < 0:
+            raise LTXError(-n2, lib.ltx_last_error(self._h).decode(errors="replace"))
+        return out
+
+    def dual_model_forward_dev(self, video_latent, audio_latent, video_context, audio_context, video_timesteps, audio_timesteps,
+                               video_velocity, audio_velocity, F, H, W, video_mask=None, audio_mask=None, ungrouped=False, struct_size=None,
+                               T_a=None):
+        """``ltx_dual_model_forward_dev``: device tensors; latents [B][T][C] and contexts [B][S][caption_channels] bf16, timesteps [B] f32
+        (sigma), masks [B][S] int32 or None; the velocities [B][F*H*W][out_channels] / [B][T_a][audio_out_channels] f32 are written."""
+        a = DualModelForwardArgs()
+        a.struct_size = C.sizeof(DualModelForwardArgs) if struct_size is None else struct_size
+        a.B, a.F, a.H, a.W = video_latent.shape[0], F, H, W
+        a.T_a = audio_latent.shape[1] if T_a is None else T_a
+        a.S = video_context.shape[1]
+        a.video_latent, a.audio_latent = _ptr(video_latent), _ptr(audio_latent)
+        a.video_context, a.audio_context = _ptr(video_context), _ptr(audio_context)
+        a.video_timesteps, a.audio_timesteps = _ptr(video_timesteps), _ptr(audio_timesteps)
+        a.video_mask, a.audio_mask = _ptr(video_mask), _ptr(audio_mask)
+        a.video_velocity, a.audio_velocity = _ptr(video_velocity), _ptr(audio_velocity)
+        a.ungrouped = int(ungrouped)
+        self._ck(lib.ltx_dual_model_forward_dev(self._h, C.byref(a)))
+
+    def dual_model_embed_dev(self, video_timesteps, audio_timesteps, temb_v, temb_a, cross_v, cross_a, embts_v, embts_a, ungrouped=False, B=None):
+        """``ltx_dual_model_embed_dev``: the timestep path alone into caller tensors (f32, device)."""
+        self._ck(lib.ltx_dual_model_embed_dev(self._h, _ptr(video_timesteps), _ptr(audio_timesteps),
+                                              video_timesteps.shape[0] if B is None else B, int(ungrouped), _ptr(temb_v), _ptr(temb_a),
+                                              _ptr(cross_v), _ptr(cross_a), _ptr(embts_v), _ptr(embts_a)))
+
+    def op_gemv_group(self, jobs, M=None, n_jobs=None):
+        """``ltx_op_gemv_group``: each job is a dict(a= [M][K] f32, W= [N][K] bf16, out= a 2-D f32 view whose row stride is ldo, bias=
+        tensor or None, in_act=0); N / K default to W's shape and may be given (N=0 skips the job; a / W / out may then be None)."""
+        arr = (GemvJob * max(1, len(jobs)))()
+        for o, j in zip(arr, jobs):
+            a, W, out = j.get("a"), j.get("W"), j.get("out")
+            o.a, o.lda = (a.data_ptr(), j.get("lda", a.stride(0))) if a is not None else (None, j.get("lda", 0))
+            o.W, o.ldw = (W.data_ptr(), j.get("ldw", W.stride(0))) if W is not None else (None, j.get("ldw", 0))
+            o.out, o.ldo = (out.data_ptr(), out.stride(0)) if out is not None else (None, 0)
+            o.bias = _ptr(j.get("bias"))
+            o.N = j["N"] if "N" in j else W.shape[0]
+            o.K = j["K"] if "K" in j else W.shape[1]
+            o.in_act = j.get("in_act", 0)
+        if M is None:
+            M = jobs[0]["a"].shape[0]
+        self._ck(lib.ltx_op_gemv_group(self._h, arr, len(jobs) if n_jobs is None else n_jobs, M))
 
     def op_norm_mod2(self, video=None, audio=None, eps=1e-6):
         """``ltx_op_norm_mod2``: each job is None or a dict(x=, out0=, out1= 2-D tensors whose row strides are ldx / ldo, rows=, D=,

@@ -77,6 +77,29 @@ class DualForwardArgs(C.Structure):
                 ("cross_video_ss", C.c_void_p), ("cross_audio_ss", C.c_void_p), ("phase_mask", C.c_uint32)]
 
 
+class GemvJob(C.Structure):
+    """``ltx_gemv_job``: one job of ``ltx_op_gemv_group`` (the operands of ``ltx_op_gemv_f32`` without M)."""
+
+    _fields_ = [("a", C.c_void_p), ("lda", C.c_long), ("W", C.c_void_p), ("ldw", C.c_long), ("bias", C.c_void_p), ("out", C.c_void_p),
+                ("ldo", C.c_long), ("N", C.c_int), ("K", C.c_int), ("in_act", C.c_int)]
+
+
+class DualModelConfig(C.Structure):
+    """``ltx_dual_model_config``: the block config plus the top-level widths of LTX2Transformer (LTXConfig.swift:83-177)."""
+
+    _fields_ = [("blocks", DualBlockConfig), ("in_channels", C.c_int), ("out_channels", C.c_int), ("audio_in_channels", C.c_int),
+                ("audio_out_channels", C.c_int), ("caption_channels", C.c_int), ("timestep_scale_multiplier", C.c_float)]
+
+
+class DualModelForwardArgs(C.Structure):
+    """``ltx_dual_model_forward_args``: the arguments of LTX2Transformer.callAsFunction (LTX2Transformer.swift:254-265)."""
+
+    _fields_ = [("struct_size", C.c_uint32), ("B", C.c_int), ("F", C.c_int), ("H", C.c_int), ("W", C.c_int), ("T_a", C.c_int), ("S", C.c_int),
+                ("video_latent", C.c_void_p), ("audio_latent", C.c_void_p), ("video_context", C.c_void_p), ("audio_context", C.c_void_p),
+                ("video_timesteps", C.c_void_p), ("audio_timesteps", C.c_void_p), ("video_mask", C.c_void_p), ("audio_mask", C.c_void_p),
+                ("video_velocity", C.c_void_p), ("audio_velocity", C.c_void_p), ("ungrouped", C.c_int)]
+
+
 class NormMod2Job(C.Structure):
     """``ltx_norm_mod2_job``: one job of ``ltx_op_norm_mod2``."""
 
@@ -235,6 +258,14 @@ SIGNATURES = {
     "ltx_dual_blocks_export_param": (_l, [_vp, C.c_char_p, _vp, _l]),
     "ltx_dual_blocks_forward_dev": (_i, [_vp, C.POINTER(DualForwardArgs)]),
     "ltx_op_norm_mod2": (_i, [_vp, C.POINTER(NormMod2Job), C.POINTER(NormMod2Job), _f]),
+    "ltx_op_gemv_group": (_i, [_vp, C.POINTER(GemvJob), _i, _i]),
+    "ltx_dual_model_config_default": (None, [C.POINTER(DualModelConfig)]),
+    "ltx_dual_model_init_synthetic": (_i, [_vp, C.POINTER(DualModelConfig), _u64]),
+    "ltx_dual_model_load": (_i, [_vp, C.c_char_p, C.POINTER(DualModelConfig)]),
+    "ltx_dual_model_unload": (_i, [_vp]),
+    "ltx_dual_model_export_param": (_l, [_vp, C.c_char_p, _vp, _l]),
+    "ltx_dual_model_forward_dev": (_i, [_vp, C.POINTER(DualModelForwardArgs)]),
+    "ltx_dual_model_embed_dev": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ltx_op_attention_hd": (_i, [_vp, _vp, _vp, _vp, _l, _vp, _i, _i, _i, _i, _i, _f, _vp]),
     "ltx_attention_hd_workgroup_queries": (_i, [_i, _i, _i, _i]),
     "ltx_op_qknorm_rope_hd": (_i, [_vp, _vp, _l, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _vp]),

@@ -6,6 +6,7 @@
 #include "abi_internal.h"
 #include "attn_module.h"
 #include "dual_block.h"
+#include "dual_model.h"
 #include "audio.h"
 #include "connector.h"
 #include "dist.h"
@@ -125,6 +126,7 @@ void ltx_ctx_destroy(ltx_ctx* ctx) {
     drop_model(&ctx->vocoder, vocoder_destroy);
     for (AttnModule*& m : ctx->attn_modules) drop_model(&m, attn_module_destroy);
     drop_model(&ctx->dual, dual_destroy);
+    drop_model(&ctx->dual_model, dual_model_destroy);
     if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
 }

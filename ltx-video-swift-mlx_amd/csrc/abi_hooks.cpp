@@ -207,6 +207,19 @@ int ltx_op_gemv_f32(ltx_ctx* ctx, const float* a, long lda, const uint16_t* W, l
     return with_ctx(ctx, [&] { launch_gemv_f32(a, lda, W, ldw, bias, out, ldo, M, N, K, in_act, ctx->stream); });
 }
 
+int ltx_op_gemv_group(ltx_ctx* ctx, const ltx_gemv_job* jobs, int n_jobs, int M) {
+    return with_ctx(ctx, [&] {
+        LTX_REQUIRE(jobs && n_jobs >= 1 && n_jobs <= 8, "ltx_op_gemv_group: %d jobs out of range (1..8)", n_jobs);
+        GemvJob g[8];
+        for (int j = 0; j < n_jobs; ++j) {
+            const ltx_gemv_job& q = jobs[j];
+            g[j].a = q.a; g[j].lda = q.lda; g[j].W = q.W; g[j].ldw = q.ldw; g[j].bias = q.bias;
+            g[j].out = q.out; g[j].ldo = q.ldo; g[j].N = q.N; g[j].K = q.K; g[j].in_act = q.in_act;
+        }
+        launch_gemv_group(g, n_jobs, M, ctx->stream);
+    });
+}
+
 int ltx_op_conv3d(ltx_ctx* ctx, const uint16_t* x, int F, int H, int W, int Cin, const uint16_t* w, const float* bias,
                   int Cout, int causal, float* out) {
     return with_ctx(ctx, [&] {

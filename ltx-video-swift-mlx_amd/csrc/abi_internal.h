@@ -63,7 +63,7 @@ inline TransformerConfig to_cfg(const ltx_transformer_config* c) {
 }
 
 // ---- model slots: the pointer members of ltx_ctx that hold a component (dit, vae, upscaler, connector, vae_encoder, audio_vae,
-// vocoder, each attn_modules[i], dual). A slot is either null or a fully built model; nothing else is ever published. ----
+// vocoder, each attn_modules[i], dual, dual_model). A slot is either null or a fully built model; nothing else is ever published. ----
 
 // Destroy and null. The caller has made the GPU idle (ltx_ctx_destroy, after its device-wide synchronise).
 template <class M, class Destroy>
@@ -112,6 +112,7 @@ constexpr const char* kNoAudioVae = "Model not loaded: audio VAE not loaded";
 constexpr const char* kNoVocoder = "Model not loaded: vocoder not loaded";
 constexpr const char* kNoAttnModule = "Model not loaded: attention module not loaded at this index";
 constexpr const char* kNoDualBlocks = "Model not loaded: dual transformer blocks not loaded";
+constexpr const char* kNoDualModel = "Model not loaded: dual transformer model not loaded";
 
 // ---- staging for host-pointer entry points: stage_in* / run the _dev body / stage_out* / stage_sync, all on the context's stream.
 // The DevBuf is the caller's choice and decides what stays resident: a ctx->h2d slot (runtime.h, H2dSlot) is kept for the next call,

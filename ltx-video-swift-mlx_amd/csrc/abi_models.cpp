@@ -9,6 +9,7 @@
 #include "audio.h"
 #include "attn_module.h"
 #include "dual_block.h"
+#include "dual_model.h"
 #include "connector.h"
 #include "dist.h"
 #include "elementwise.h"
@@ -177,6 +178,19 @@ DualBlockConfig to_dual_cfg(const ltx_dual_block_config* c) {
     t.audio_max_pos = c->audio_max_pos;
     t.fps = c->fps;
     t.norm_eps = c->norm_eps;
+    return t;
+}
+
+DualModelConfig to_dual_model_cfg(const ltx_dual_model_config* c) {
+    DualModelConfig t;
+    if (!c) return t;
+    t.blocks = to_dual_cfg(&c->blocks);
+    t.in_channels = c->in_channels;
+    t.out_channels = c->out_channels;
+    t.audio_in_channels = c->audio_in_channels;
+    t.audio_out_channels = c->audio_out_channels;
+    t.caption_channels = c->caption_channels;
+    t.timestep_scale_multiplier = c->timestep_scale_multiplier;
     return t;
 }
 
@@ -931,6 +945,78 @@ int ltx_dual_blocks_forward_dev(ltx_ctx* ctx, const ltx_dual_forward_args* args)
         a.cross_video_ss = args->cross_video_ss; a.cross_audio_ss = args->cross_audio_ss;
         if (sz >= offsetof(ltx_dual_forward_args, phase_mask) + sizeof(args->phase_mask)) a.phase_mask = args->phase_mask;
         dual_forward(ctx, m, a);
+    });
+}
+
+/* ---- LTX2Transformer: the dual video + audio model (dual_model.h) ---- */
+void ltx_dual_model_config_default(ltx_dual_model_config* cfg) {
+    if (!cfg) return;
+    const DualModelConfig d;
+    ltx_dual_block_config_default(&cfg->blocks);
+    cfg->in_channels = d.in_channels;
+    cfg->out_channels = d.out_channels;
+    cfg->audio_in_channels = d.audio_in_channels;
+    cfg->audio_out_channels = d.audio_out_channels;
+    cfg->caption_channels = d.caption_channels;
+    cfg->timestep_scale_multiplier = d.timestep_scale_multiplier;
+}
+int ltx_dual_model_init_synthetic(ltx_ctx* ctx, const ltx_dual_model_config* cfg, uint64_t seed) {
+    return with_ctx(ctx, [&] {
+        replace_model(ctx, &ctx->dual_model, [&] { return dual_model_create(to_dual_model_cfg(cfg)); },
+                      [&](DualModel* m) { dual_model_init_synthetic(ctx, m, seed); }, dual_model_destroy);
+    });
+}
+int ltx_dual_model_load(ltx_ctx* ctx, const char* path, const ltx_dual_model_config* cfg) {
+    if (!ctx || !path) return LTX_ERR_INVALID_CONFIGURATION;
+    return guarded(ctx, [&] {
+        replace_model(ctx, &ctx->dual_model, [&] { return dual_model_create(to_dual_model_cfg(cfg)); },
+                      [&](DualModel* m) { dual_model_load(ctx, m, path); }, dual_model_destroy);
+    });
+}
+int ltx_dual_model_unload(ltx_ctx* ctx) {
+    return with_ctx(ctx, [&] { unload_model(ctx, &ctx->dual_model, dual_model_destroy); });
+}
+long ltx_dual_model_export_param(ltx_ctx* ctx, const char* name, float* out, long cap) {
+    if (!ctx || !name) return -LTX_ERR_INVALID_CONFIGURATION;
+    long n = 0;
+    const int rc = guarded(ctx, [&] {
+        DualModel* m = need(ctx->dual_model, kNoDualModel);
+        const ParamSlot* s = dual_model_find(m, name);
+        LTX_REQUIRE(s != nullptr, "ltx_dual_model_export_param: no parameter '%s'", name);
+        n = s->numel;
+        if (!out) return;
+        LTX_REQUIRE(cap >= n, "ltx_dual_model_export_param: buffer too small (%ld < %ld)", cap, n);
+        dual_export(ctx, m->stack, *s, out);
+    });
+    return rc == 0 ? n : -rc;
+}
+int ltx_dual_model_forward_dev(ltx_ctx* ctx, const ltx_dual_model_forward_args* args) {
+    if (!ctx) return LTX_ERR_INVALID_CONFIGURATION;
+    return guarded(ctx, [&] {
+        LTX_REQUIRE(args != nullptr, "ltx_dual_model_forward_dev: null arguments");
+        const size_t sz = args->struct_size;
+        LTX_REQUIRE(sz >= offsetof(ltx_dual_model_forward_args, audio_velocity) + sizeof(args->audio_velocity) && sz <= 4096,
+                    "ltx_dual_model_forward_args.struct_size = %zu: set it to sizeof(ltx_dual_model_forward_args) (LTX_DUAL_MODEL_FORWARD_ARGS_INIT); this library is ABI revision %d",
+                    sz, LTX_ABI_VERSION);
+        DualModel* m = need(ctx->dual_model, kNoDualModel);
+        DualModelForwardArgs a;
+        a.B = args->B; a.F = args->F; a.H = args->H; a.W = args->W; a.T_a = args->T_a; a.S = args->S;
+        a.video_latent = args->video_latent; a.audio_latent = args->audio_latent;
+        a.video_context = args->video_context; a.audio_context = args->audio_context;
+        a.video_timesteps = args->video_timesteps; a.audio_timesteps = args->audio_timesteps;
+        a.video_mask = args->video_mask; a.audio_mask = args->audio_mask;
+        a.video_velocity = args->video_velocity; a.audio_velocity = args->audio_velocity;
+        if (sz >= offsetof(ltx_dual_model_forward_args, ungrouped) + sizeof(args->ungrouped)) a.ungrouped = args->ungrouped;
+        dual_model_forward(ctx, m, a);
+    });
+}
+int ltx_dual_model_embed_dev(ltx_ctx* ctx, const float* video_timesteps, const float* audio_timesteps, int B, int ungrouped,
+                             float* temb_v, float* temb_a, float* cross_v, float* cross_a, float* embts_v, float* embts_a) {
+    return with_ctx(ctx, [&] {
+        DualModel* m = need(ctx->dual_model, kNoDualModel);
+        DualEmbedOut o;
+        o.temb_v = temb_v; o.temb_a = temb_a; o.cross_v = cross_v; o.cross_a = cross_a; o.embts_v = embts_v; o.embts_a = embts_a;
+        dual_model_embed(ctx, m, video_timesteps, audio_timesteps, B, ungrouped != 0, o);
     });
 }
 

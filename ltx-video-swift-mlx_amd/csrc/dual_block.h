@@ -1,11 +1,12 @@
 // dual_block.h - LTX2TransformerBlock, the dual video + audio block of the reference (LTX2TransformerBlock.swift:174-297), as a
 // loadable stack of L blocks with a forward of its own. It takes what LTX2Transformer.callAsFunction hands its blocks - the two
 // residual streams, the two text contexts, the adaLN rows of both streams and the cross-modal scale-shift rows - and returns both
-// streams. The embedders that produce those rows (audio_adaln_single, av_ca_*), the patchify / output heads, the caption projections,
-// the joint denoise loop and the CLI's --audio path are not here.
+// streams. The embedders that produce those rows (audio_adaln_single, av_ca_*), the patchify / output heads and the caption projections
+// are dual_model.h, which owns a DualStack and calls dual_forward; the joint denoise loop and the CLI's --audio path are not built.
 //
 // Modulation inputs are ONE ROW PER BATCH ELEMENT: temb_v [B][6][Dv], temb_a [B][6][Da], cross_video_ss [B][5][Dv], cross_audio_ss
-// [B][5][Da]. The reference's per-token form (image-to-video, LTX2Transformer.swift:285-312) is not implemented.
+// [B][5][Da]. The reference's per-token form (image-to-video, LTX2Transformer.swift:285-312) is not implemented, here or in
+// dual_model.h, whose timesteps are one value per batch element and stream.
 //
 // The eight phases of one block, in the reference's order (x_v [B][Tv][Dv], x_a [B][Ta][Da], both f32, updated in place):
 //   1. video self-attention: adaLN rows 0 (shift) / 1 (scale), gate row 2 of scale_shift_table [6][Dv] + temb_v; heads x 128, 3-D RoPE

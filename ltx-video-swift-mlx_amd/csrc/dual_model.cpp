@@ -1,0 +1,342 @@
+// dual_model.cpp - see dual_model.h. One forward = LTX2Transformer.callAsFunction (LTX2Transformer.swift:254-392).
+#include "dual_model.h"
+
+#include <string.h>
+
+#include <algorithm>
+#include <vector>
+
+#include "elementwise.h"
+#include "gemm.h"
+#include "linear_ops.h"
+
+namespace {
+
+struct Pending {
+    std::string key;
+    void** dst;
+    int kind;
+    long rows, cols;
+};
+
+// the module spelling of a top-level checkpoint key (mapTransformerKey(includeAudio: true), ModelDownloader.swift:772-788)
+std::string module_spelling(std::string k) {
+    auto starts = [&](const char* p) { return k.compare(0, strlen(p), p) == 0; };
+    if (starts("proj_in.")) k = "patchify_proj." + k.substr(strlen("proj_in."));
+    if (starts("time_embed.emb.timestep_embedder."))
+        k = "adaln_single.emb." + k.substr(strlen("time_embed.emb.timestep_embedder."));
+    else if (starts("time_embed.linear."))
+        k = "adaln_single." + k.substr(strlen("time_embed."));
+    const char* from = ".emb.timestep_embedder.";
+    const char* to = ".emb.";
+    for (size_t at = k.find(from); at != std::string::npos; at = k.find(from, at + strlen(to))) k.replace(at, strlen(from), to);
+    return k;
+}
+
+// offsets (in floats) of embedder j's [B][D] rows inside ws_h1 / ws_h2
+long stage_offset(const DualModel* m, int j, int B) {
+    long off = 0;
+    for (int i = 0; i < j; ++i) off += (long)B * (m->emb[i].audio ? m->Da : m->Dv);
+    return off;
+}
+
+void ensure_embed_scratch(DualModel* m, int B) {
+    m->ws_emb256.ensure((size_t)2 * B * 256 * 4);
+    const size_t stage = (size_t)stage_offset(m, kDualEmbedders, B) * 4;
+    m->ws_h1.ensure(stage);
+    m->ws_h2.ensure(stage);
+}
+
+// The timestep path (LTX2Transformer.swift:272-312). No check and no allocation in here: the callers have done both.
+void embed_launches(ltx_ctx* ctx, DualModel* m, const float* video_ts, const float* audio_ts, int B, bool ungrouped, const DualEmbedOut& o) {
+    hipStream_t st = ctx->stream;
+    const int Dv = m->Dv, Da = m->Da;
+    float* emb_v = m->ws_emb256.as<float>();
+    float* emb_a = emb_v + (long)B * 256;
+    launch_timestep_embedding(video_ts, m->cfg.timestep_scale_multiplier, emb_v, B, 256, st);
+    launch_timestep_embedding(audio_ts, m->cfg.timestep_scale_multiplier, emb_a, B, 256, st);
+    // stage 3 destinations: the four modulation tensors; the gate embedders write row 4 of the 5-row tensors
+    float* dst3[kDualEmbedders] = {o.temb_v, o.temb_a, o.cross_v, o.cross_v + 4L * Dv, o.cross_a, o.cross_a + 4L * Da};
+    const long ldo3[kDualEmbedders] = {6L * Dv, 6L * Da, 5L * Dv, 5L * Dv, 5L * Da, 5L * Da};
+    GemvJob s1[kDualEmbedders], s2[kDualEmbedders], s3[kDualEmbedders];
+    for (int j = 0; j < kDualEmbedders; ++j) {
+        const DualEmbedder& e = m->emb[j];
+        const int D = e.audio ? Da : Dv;
+        float* h1 = m->ws_h1.as<float>() + stage_offset(m, j, B);
+        // the stage-2 outputs of adaln_single / audio_adaln_single are the embedded timesteps
+        float* h2 = j == 0 ? o.embts_v : j == 1 ? o.embts_a : m->ws_h2.as<float>() + stage_offset(m, j, B);
+        s1[j].a = e.audio ? emb_a : emb_v; s1[j].lda = 256; s1[j].W = e.l1.w; s1[j].ldw = 256; s1[j].bias = e.l1.b;
+        s1[j].out = h1; s1[j].ldo = D; s1[j].N = D; s1[j].K = 256; s1[j].in_act = LTX_ACT_NONE;
+        s2[j].a = h1; s2[j].lda = D; s2[j].W = e.l2.w; s2[j].ldw = D; s2[j].bias = e.l2.b;
+        s2[j].out = h2; s2[j].ldo = D; s2[j].N = D; s2[j].K = D; s2[j].in_act = LTX_ACT_SILU;
+        s3[j].a = h2; s3[j].lda = D; s3[j].W = e.lin.w; s3[j].ldw = D; s3[j].bias = e.lin.b;
+        s3[j].out = dst3[j]; s3[j].ldo = ldo3[j]; s3[j].N = e.n * D; s3[j].K = D; s3[j].in_act = LTX_ACT_SILU;
+    }
+    if (!ungrouped) {
+        launch_gemv_group(s1, kDualEmbedders, B, st);
+        launch_gemv_group(s2, kDualEmbedders, B, st);
+        launch_gemv_group(s3, kDualEmbedders, B, st);
+        return;
+    }
+    for (const GemvJob* s : {s1, s2, s3})
+        for (int j = 0; j < kDualEmbedders; ++j)
+            launch_gemv_f32(s[j].a, s[j].lda, s[j].W, s[j].ldw, s[j].bias, s[j].out, s[j].ldo, B, s[j].N, s[j].K, s[j].in_act, st);
+}
+
+}  // namespace
+
+DualModel::~DualModel() {
+    if (stack) dual_destroy(stack);
+}
+
+DualModel* dual_model_create(const DualModelConfig& cfg) {
+    const DualBlockConfig& bc = cfg.blocks;
+    if (bc.video_context_dim != bc.video_dim || bc.audio_context_dim != bc.audio_dim)
+        LTX_THROW(LTXS_INVALID_CONFIGURATION, "dual model: context dims %d / %d must equal the stream dims %d / %d (the caption projections' widths)",
+                  bc.video_context_dim, bc.audio_context_dim, bc.video_dim, bc.audio_dim);
+    for (int c : {cfg.in_channels, cfg.out_channels, cfg.audio_in_channels, cfg.audio_out_channels, cfg.caption_channels})
+        if (c < 64 || c > 16384 || c % 64 != 0)
+            LTX_THROW(LTXS_INVALID_CONFIGURATION, "dual model: channel count %d must be a multiple of 64 up to 16384", c);
+    if (!(cfg.timestep_scale_multiplier > 0.f)) LTX_THROW(LTXS_INVALID_CONFIGURATION, "dual model: timestep_scale_multiplier must be positive");
+    DualModel* m = new DualModel();
+    try {
+        m->stack = dual_create(bc);  // validates the block config
+        m->cfg = cfg;
+        const int Dv = m->Dv = bc.video_dim, Da = m->Da = bc.audio_dim;
+        std::vector<Pending> pend;
+        auto lin = [&](const std::string& name, LinearW& l, int out, int in) {
+            l.out = out;
+            l.in = in;
+            pend.push_back({name + ".weight", (void**)&l.w, SLOT_BF16, out, in});
+            pend.push_back({name + ".bias", (void**)&l.b, SLOT_F32, out, 0});
+        };
+        lin("patchify_proj", m->patchify, Dv, cfg.in_channels);
+        lin("audio_patchify_proj", m->audio_patchify, Da, cfg.audio_in_channels);
+        const struct { const char* name; int n; bool audio; } embs[kDualEmbedders] = {
+            {"adaln_single", 6, false},
+            {"audio_adaln_single", 6, true},
+            {"av_ca_video_scale_shift_adaln_single", 4, false},
+            {"av_ca_a2v_gate_adaln_single", 1, false},
+            {"av_ca_audio_scale_shift_adaln_single", 4, true},
+            {"av_ca_v2a_gate_adaln_single", 1, true}};
+        for (int j = 0; j < kDualEmbedders; ++j) {
+            DualEmbedder& e = m->emb[j];
+            e.name = embs[j].name;
+            e.n = embs[j].n;
+            e.audio = embs[j].audio;
+            const int D = e.audio ? Da : Dv;
+            lin(std::string(e.name) + ".emb.linear_1", e.l1, D, 256);
+            lin(std::string(e.name) + ".emb.linear_2", e.l2, D, D);
+            lin(std::string(e.name) + ".linear", e.lin, e.n * D, D);
+        }
+        lin("caption_projection.linear_1", m->cap1, Dv, cfg.caption_channels);
+        lin("caption_projection.linear_2", m->cap2, Dv, Dv);
+        lin("audio_caption_projection.linear_1", m->acap1, Da, cfg.caption_channels);
+        lin("audio_caption_projection.linear_2", m->acap2, Da, Da);
+        pend.push_back({"scale_shift_table", (void**)&m->sst_out_v, SLOT_F32, 2, Dv});
+        pend.push_back({"audio_scale_shift_table", (void**)&m->sst_out_a, SLOT_F32, 2, Da});
+        lin("proj_out", m->proj_out, cfg.out_channels, Dv);
+        lin("audio_proj_out", m->audio_proj_out, cfg.audio_out_channels, Da);
+        size_t total = 0, total_w = 0;
+        for (auto& q : pend) (q.kind == SLOT_BF16 ? total_w : total) += DeviceArena::padded((q.kind == SLOT_BF16 ? 2 : 4) * q.rows * (q.cols ? q.cols : 1));
+        m->arena.reserve(total + 256);
+        m->warena.reserve(total_w + 256);
+        HIP_CHECK(hipMemset(m->arena.buf.p, 0, m->arena.buf.bytes));
+        HIP_CHECK(hipMemset(m->warena.buf.p, 0, m->warena.buf.bytes));
+        for (auto& q : pend) {
+            ParamSlot s;
+            s.kind = q.kind;
+            s.rows = q.rows;
+            s.cols = q.cols;
+            s.numel = q.rows * (q.cols ? q.cols : 1);
+            s.dst = *q.dst = (q.kind == SLOT_BF16 ? m->warena : m->arena).take((q.kind == SLOT_BF16 ? 2 : 4) * s.numel);
+            m->slots[q.key] = s;
+        }
+        HIP_CHECK(hipDeviceSynchronize());
+    } catch (...) {
+        delete m;
+        throw;
+    }
+    return m;
+}
+
+void dual_model_destroy(DualModel* m) { delete m; }
+
+void dual_model_init_synthetic(ltx_ctx* ctx, DualModel* m, uint64_t seed) {
+    dual_init_synthetic(ctx, m->stack, seed);
+    // the stack's distributions: Linear weights N(0, 0.02^2), biases N(0, 0.01^2), tables N(0, 0.02^2); bf16 values. A stream of seeds of
+    // its own (the stack counts its slots from 1)
+    uint64_t k = 1u << 20;
+    for (auto& kv : m->slots) {
+        ParamSlot& s = kv.second;
+        const uint64_t sd = seed * 0x9E3779B97F4A7C15ull + (++k) * 0xD1B54A32D192ED03ull;
+        const std::string& key = kv.first;
+        const bool is_bias = key.size() > 5 && key.compare(key.size() - 5, 5, ".bias") == 0;
+        if (s.kind == SLOT_BF16)
+            launch_fill_normal_bf16((bf16_t*)s.dst, s.numel, sd, 0.f, 0.02f, ctx->stream);
+        else
+            launch_fill_normal_f32((float*)s.dst, s.numel, sd, 0.f, is_bias ? 0.01f : 0.02f, 1, ctx->stream);
+        s.loaded = true;
+    }
+    HIP_CHECK(hipStreamSynchronize(ctx->stream));
+}
+
+void dual_model_load(ltx_ctx* ctx, DualModel* m, const std::string& path) {
+    dual_load(ctx, m->stack, path, 0);  // the blocks; starts the load report; throws on a missing block parameter
+    SafeTensors st;
+    st.open(path);
+    for (auto& kv : m->slots) kv.second.loaded = false;
+    std::vector<uint8_t> staging;
+    const std::string tb = "transformer_blocks.";
+    for (auto& kv : st.tensors) {
+        const std::string& fk = kv.first;
+        if (fk.compare(0, tb.size(), tb) == 0) continue;  // dual_load has seen it
+        // a file that holds two spellings of one parameter (proj_in.weight and patchify_proj.weight) is accepted, the later key in
+        // map order wins and the parameter counts once: the reference's mapped dictionary behaves the same way
+        auto it = m->slots.find(module_spelling(fk));
+        if (it == m->slots.end()) {
+            ctx->n_unmatched++;  // e.g. norm_out.weight: LayerNorm(affine: false) has none
+            continue;
+        }
+        ParamSlot& s = it->second;
+        const StTensor& t = kv.second;
+        const bool shape_ok = t.numel() == s.numel && (!(s.cols && t.shape.size() == 2) || (t.shape[0] == s.rows && t.shape[1] == s.cols));
+        if (!shape_ok)
+            LTX_THROW(LTXS_WEIGHT_LOADING_FAILED, "Failed to load weights: %s has %ld elements, expected [%ld, %ld]", fk.c_str(), t.numel(), s.rows, s.cols);
+        if (s.kind == SLOT_BF16) {
+            staging.resize((size_t)s.numel * 2);
+            st_to_bf16(st, t, (bf16_t*)staging.data());
+        } else {  // biases and tables are bf16 in the file: f32 copies of those values
+            staging.resize((size_t)s.numel * 4);
+            float* f = (float*)staging.data();
+            st_to_f32(st, t, f);
+            for (long i = 0; i < s.numel; ++i) f[i] = host_bf16_to_f32(host_f32_to_bf16(f[i]));
+        }
+        HIP_CHECK(hipMemcpy(s.dst, staging.data(), staging.size(), hipMemcpyHostToDevice));
+        if (!s.loaded) ctx->n_loaded++;
+        s.loaded = true;
+    }
+    const std::string* first_missing = nullptr;
+    for (auto& kv : m->slots)
+        if (!kv.second.loaded) {
+            ctx->n_missing++;
+            if (!first_missing) first_missing = &kv.first;
+        }
+    if (first_missing)
+        LTX_THROW(LTXS_WEIGHT_LOADING_FAILED, "Failed to load weights: %s and %d more are not in %s", first_missing->c_str(), ctx->n_missing - 1,
+                  path.c_str());
+}
+
+const ParamSlot* dual_model_find(const DualModel* m, const std::string& name) {
+    auto it = m->slots.find(name);
+    if (it != m->slots.end()) return &it->second;
+    auto ib = m->stack->slots.find(name);
+    return ib != m->stack->slots.end() ? &ib->second : nullptr;
+}
+
+void dual_model_embed(ltx_ctx* ctx, DualModel* m, const float* video_ts, const float* audio_ts, int B, bool ungrouped, const DualEmbedOut& o) {
+    if (B < 1 || B > 8) LTX_THROW(LTXS_INVALID_CONFIGURATION, "dual model embed: B=%d (1 .. 8)", B);
+    if (!video_ts || !audio_ts || !o.temb_v || !o.temb_a || !o.cross_v || !o.cross_a || !o.embts_v || !o.embts_a)
+        LTX_THROW(LTXS_INVALID_CONFIGURATION, "dual model embed: null timestep or output pointer");
+    ensure_embed_scratch(m, B);
+    embed_launches(ctx, m, video_ts, audio_ts, B, ungrouped, o);
+}
+
+void dual_model_forward(ltx_ctx* ctx, DualModel* m, const DualModelForwardArgs& a) {
+    // every check comes before the first launch and before any allocation; the shape rules are dual_forward's, so that it cannot refuse
+    // the call after the launches in front of it
+    const int Dv = m->Dv, Da = m->Da, B = a.B, S = a.S, Ta = a.T_a;
+    if (B < 1 || B > 8 || a.F < 1 || a.H < 1 || a.W < 1 || Ta < 1 || S < 1 || Ta > (1 << 20) || S > (1 << 20) || (long)a.F * a.H * a.W > (1 << 20))
+        LTX_THROW(LTXS_INVALID_CONFIGURATION, "dual model forward: bad shapes B=%d (1 .. 8) F=%d H=%d W=%d T_a=%d S=%d", B, a.F, a.H, a.W, Ta, S);
+    if (!a.video_latent || !a.audio_latent || !a.video_context || !a.audio_context || !a.video_timesteps || !a.audio_timesteps ||
+        !a.video_velocity || !a.audio_velocity)
+        LTX_THROW(LTXS_INVALID_CONFIGURATION, "dual model forward: null latent, context, timestep or velocity pointer");
+    const int Tv = a.F * a.H * a.W;
+    const long vrows = (long)B * Tv, arows = (long)B * Ta, crows = (long)B * S;
+    const float eps = m->cfg.blocks.norm_eps;
+    hipStream_t st = ctx->stream;
+
+    // scratch: grows to the largest shape seen
+    m->ws_xv.ensure((size_t)vrows * Dv * 4);
+    m->ws_xa.ensure((size_t)arows * Da * 4);
+    m->ws_ctx_v.ensure((size_t)crows * Dv * 2);
+    m->ws_ctx_a.ensure((size_t)crows * Da * 2);
+    m->ws_cap_h.ensure((size_t)crows * std::max(Dv, Da) * 2);  // shared by both caption projections; audio_dim may exceed video_dim
+    if (a.video_mask) m->ws_bias_v.ensure((size_t)crows * 4);
+    if (a.audio_mask) m->ws_bias_a.ensure((size_t)crows * 4);
+    ensure_embed_scratch(m, B);
+    m->ws_temb_v.ensure((size_t)B * 6 * Dv * 4);
+    m->ws_temb_a.ensure((size_t)B * 6 * Da * 4);
+    m->ws_cross_v.ensure((size_t)B * 5 * Dv * 4);
+    m->ws_cross_a.ensure((size_t)B * 5 * Da * 4);
+    m->ws_modout_v.ensure((size_t)B * 2 * Dv * 4);
+    m->ws_modout_a.ensure((size_t)B * 2 * Da * 4);
+    m->ws_xn.ensure((size_t)std::max(vrows * Dv, arows * Da) * 2);
+    m->ws_splitk.ensure((size_t)8 << 22);
+    const SplitWs sk{m->ws_splitk.as<float>(), (long)(m->ws_splitk.bytes / 4)};
+    float* xv = m->ws_xv.as<float>();
+    float* xa = m->ws_xa.as<float>();
+
+    // 1. patchify (LTX2Transformer.swift:271,278): the streams start as the bf16 value of the projection (dual_model.h, rounding point 1)
+    {
+        GemmEpilogue e;
+        e.out_f32 = xv;
+        e.ld_f32 = Dv;
+        e.round_bf16 = 1;
+        gemm_linear(a.video_latent, m->cfg.in_channels, m->patchify, (int)vrows, e, st, sk);
+        e.out_f32 = xa;
+        e.ld_f32 = Da;
+        gemm_linear(a.audio_latent, m->cfg.audio_in_channels, m->audio_patchify, (int)arows, e, st, sk);
+    }
+    // 2. timestep path (:272-312). The embedded timesteps live in the first two [B][D] blocks of ws_h2.
+    DualEmbedOut eo;
+    eo.temb_v = m->ws_temb_v.as<float>();
+    eo.temb_a = m->ws_temb_a.as<float>();
+    eo.cross_v = m->ws_cross_v.as<float>();
+    eo.cross_a = m->ws_cross_a.as<float>();
+    eo.embts_v = m->ws_h2.as<float>() + stage_offset(m, 0, B);
+    eo.embts_a = m->ws_h2.as<float>() + stage_offset(m, 1, B);
+    embed_launches(ctx, m, a.video_timesteps, a.audio_timesteps, B, a.ungrouped != 0, eo);
+    // 3. text (:275,282,315-316)
+    auto caption = [&](const bf16_t* context, const LinearW& l1, const LinearW& l2, int D, bf16_t* out) {
+        GemmEpilogue e1;
+        e1.out_bf16 = m->ws_cap_h.as<bf16_t>();
+        e1.ld_bf16 = D;
+        e1.act = LTX_ACT_GELU_TANH;
+        gemm_linear(context, m->cfg.caption_channels, l1, (int)crows, e1, st, sk);
+        GemmEpilogue e2;
+        e2.out_bf16 = out;
+        e2.ld_bf16 = D;
+        gemm_linear(m->ws_cap_h.as<bf16_t>(), D, l2, (int)crows, e2, st, sk);
+    };
+    caption(a.video_context, m->cap1, m->cap2, Dv, m->ws_ctx_v.as<bf16_t>());
+    caption(a.audio_context, m->acap1, m->acap2, Da, m->ws_ctx_a.as<bf16_t>());
+    if (a.video_mask) launch_mask_to_bias(a.video_mask, m->ws_bias_v.as<float>(), crows, st);
+    if (a.audio_mask) launch_mask_to_bias(a.audio_mask, m->ws_bias_a.as<float>(), crows, st);
+    // 4. the blocks (:361-372)
+    DualForwardArgs f;
+    f.x_video = xv;
+    f.x_audio = xa;
+    f.ctx_video = m->ws_ctx_v.as<bf16_t>();
+    f.ctx_audio = m->ws_ctx_a.as<bf16_t>();
+    f.bias_video = a.video_mask ? m->ws_bias_v.as<float>() : nullptr;
+    f.bias_audio = a.audio_mask ? m->ws_bias_a.as<float>() : nullptr;
+    f.temb_video = eo.temb_v;
+    f.temb_audio = eo.temb_a;
+    f.cross_video_ss = eo.cross_v;
+    f.cross_audio_ss = eo.cross_a;
+    f.B = B; f.F = a.F; f.H = a.H; f.W = a.W; f.T_a = Ta; f.S = S;
+    dual_forward(ctx, m->stack, f);
+    // 5. heads (:375-389): mod[b][j][:] = table[j][:] + embedded_ts[b][:], j = 0 shift, 1 scale - launch_make_mod with the table's two
+    // rows as its "layers" and one row per batch element
+    auto head = [&](const float* x, int D, int T, long rows, const float* table, const float* embts, float* mod, const LinearW& proj, float* out) {
+        launch_make_mod(table, embts, mod, B, 2, 1, D, st);
+        launch_norm_mod(x, D, mod + D, mod, 2L * D, T, m->ws_xn.as<bf16_t>(), D, (int)rows, D, LTX_NORM_LAYER, eps, 0, st);
+        GemmEpilogue e;
+        e.out_f32 = out;
+        e.ld_f32 = proj.out;
+        gemm_linear(m->ws_xn.as<bf16_t>(), D, proj, (int)rows, e, st, sk);
+    };
+    head(xv, Dv, Tv, vrows, m->sst_out_v, eo.embts_v, m->ws_modout_v.as<float>(), m->proj_out, a.video_velocity);
+    head(xa, Da, Ta, arows, m->sst_out_a, eo.embts_a, m->ws_modout_a.as<float>(), m->audio_proj_out, a.audio_velocity);
+}

@@ -156,3 +156,28 @@ void launch_gemm_bf16_cfg(const GemmArgs& args, int cfg, hipStream_t stream);
 // weights -> f32, exactly the reference's promotion on the timestep path.
 void launch_gemv_f32(const float* a, long lda, const bf16_t* W, long ldw, const float* bias, float* out, long ldo,
                      int M, int N, int K, int in_act, hipStream_t stream);
+
+// Up to 8 launch_gemv_f32 jobs that share M, in ONE launch (the timestep path of the dual model: one launch per stage of its six
+// embedders). Field meanings are launch_gemv_f32's; jobs may differ in N, K and activation, and out / ldo may point into the middle of
+// a wider row. One workgroup of 4 waves per 4 output columns of each job, laid end to end; a job with N = 0 is skipped. Every job
+// is bit-equal to launch_gemv_f32 on its operands (same lane -> k mapping, fma chain, reduction and bias add); the weight vectors of
+// up to eight trips are fetched before the first fma. Throws before the launch on n_jobs outside 1 .. 8, M outside 1 .. 8, a K / lda /
+// ldw that launch_gemv_f32 refuses, or a null a / W / out with N > 0.
+struct GemvJob {
+    const float* a = nullptr;
+    long lda = 0;
+    const bf16_t* W = nullptr;
+    long ldw = 0;
+    const float* bias = nullptr;
+    float* out = nullptr;
+    long ldo = 0;
+    int N = 0, K = 0;
+    int in_act = 0;
+};
+struct GemvGroup {  // the kernel's argument: the jobs by value and the prefix table of their workgroups
+    GemvJob job[8];
+    int wg_end[8];
+    int n_jobs;
+    int M;
+};
+void launch_gemv_group(const GemvJob* jobs, int n_jobs, int M, hipStream_t stream);

@@ -1776,6 +1776,87 @@ __global__ __launch_bounds__(256) void gemv_f32_kernel(const float* __restrict__
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// grouped small-M path: up to 8 gemv_f32 jobs of one M in one launch (the six AdaLayerNormSingle embedders of the dual model, one
+// launch per stage). Each job's arithmetic is gemv_f32_kernel's - the same lane -> k mapping (lane * 8 + 512 * trip), the same
+// explicit fma chain in the same order, the same wave reduction and bias add - so every job is bit-equal to launch_gemv_f32 on its
+// operands. What differs is when the weights are fetched: the 16-byte weight vectors of up to eight trips (4096 k, 32 VGPRs) are
+// loaded straight to registers before the first fma of the chunk.
+// ---------------------------------------------------------------------------------------------------------------
+// one trip of gemv_f32_kernel's loop body: lane's 8 weights at k against rows 0 .. M-1
+template <int MMAX>
+LTX_DEVFN void gemv_trip(const float* __restrict__ a, long lda, const s16x8 wv, int k, int M, int in_act, float (&accv)[MMAX]) {
+    float wf[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) wf[e] = bf16_to_f32((bf16_t)wv[e]);
+#pragma unroll
+    for (int m = 0; m < MMAX; ++m) {
+        if (m < M) {
+            const f32x4 a0 = *(const f32x4*)(a + (long)m * lda + k);
+            const f32x4 a1 = *(const f32x4*)(a + (long)m * lda + k + 4);
+            float av[8] = {a0[0], a0[1], a0[2], a0[3], a1[0], a1[1], a1[2], a1[3]};
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                float x = av[e];
+                if (in_act == LTX_ACT_SILU) x = silu_f(x);
+                accv[m] = __builtin_fmaf(x, wf[e], accv[m]);  // explicit, as in gemv_f32_kernel
+            }
+        }
+    }
+}
+// UN whole trips starting at the lane's k: every weight load is issued before the first fma; the fmas run in trip order
+template <int MMAX, int UN>
+LTX_DEVFN void gemv_chunk(const float* __restrict__ a, long lda, const bf16_t* __restrict__ wrow, int k, int M, int in_act, float (&accv)[MMAX]) {
+    s16x8 wv[UN];
+#pragma unroll
+    for (int i = 0; i < UN; ++i) wv[i] = *(const s16x8*)(wrow + k + 512 * i);
+#pragma unroll
+    for (int i = 0; i < UN; ++i) gemv_trip<MMAX>(a, lda, wv[i], k + 512 * i, M, in_act, accv);
+}
+
+template <int MMAX>
+__global__ __launch_bounds__(256) void gemv_group_kernel(const GemvGroup g) {
+    // the job of this workgroup: uniform, from the prefix table (a job with N = 0 owns no workgroup and is stepped over)
+    int j = 0;
+    while (j < g.n_jobs - 1 && (int)blockIdx.x >= g.wg_end[j]) ++j;
+    const GemvJob& job = g.job[j];
+    const int wg0 = j ? g.wg_end[j - 1] : 0;
+    const int lane = threadIdx.x & 63;
+    const int n = ((int)blockIdx.x - wg0) * 4 + (threadIdx.x >> 6);
+    const int M = g.M, N = job.N, K = job.K, in_act = job.in_act;
+    if (n >= N) return;
+    const float* __restrict__ a = job.a;
+    const long lda = job.lda;
+    float accv[MMAX];
+#pragma unroll
+    for (int m = 0; m < MMAX; ++m) accv[m] = 0.f;
+    const bf16_t* wrow = job.W + (long)n * job.ldw;
+    // whole chunks need no lane predicate: kb is uniform and every lane's k of the chunk is below K
+    int kb = 0;
+    for (; kb + 4096 <= K; kb += 4096) gemv_chunk<MMAX, 8>(a, lda, wrow, kb + lane * 8, M, in_act, accv);
+    if (kb + 2048 <= K) {
+        gemv_chunk<MMAX, 4>(a, lda, wrow, kb + lane * 8, M, in_act, accv);
+        kb += 2048;
+    }
+    if (kb + 1024 <= K) {
+        gemv_chunk<MMAX, 2>(a, lda, wrow, kb + lane * 8, M, in_act, accv);
+        kb += 1024;
+    }
+    if (kb + 512 <= K) {
+        gemv_chunk<MMAX, 1>(a, lda, wrow, kb + lane * 8, M, in_act, accv);
+        kb += 512;
+    }
+    if (kb + lane * 8 < K) gemv_chunk<MMAX, 1>(a, lda, wrow, kb + lane * 8, M, in_act, accv);  // the partly filled last trip
+    const float* bias = job.bias;
+    float* out = job.out;
+    const long ldo = job.ldo;
+#pragma unroll
+    for (int m = 0; m < MMAX; ++m) {
+        const float s = wave_reduce_sum(accv[m]);
+        if (lane == 0 && m < M) out[(long)m * ldo + n] = s + (bias ? bias[n] : 0.f);
+    }
+}
+
 #ifdef LTX_EXPERIMENTS
 #define LTX_GEMM_EXPERIMENTS_PART 1
 #include "gemm_experiments.inc"
@@ -2840,5 +2921,31 @@ void launch_gemv_f32(const float* a, long lda, const bf16_t* W, long ldw, const 
         hipLaunchKernelGGL((gemv_f32_kernel<2>), dim3(grid), dim3(256), 0, stream, a, lda, W, ldw, bias, out, ldo, M, N, K, in_act);
     else
         hipLaunchKernelGGL((gemv_f32_kernel<8>), dim3(grid), dim3(256), 0, stream, a, lda, W, ldw, bias, out, ldo, M, N, K, in_act);
+    HIP_CHECK(hipGetLastError());
+}
+
+void launch_gemv_group(const GemvJob* jobs, int n_jobs, int M, hipStream_t stream) {
+    // every check comes before the launch: a refused call writes nothing
+    LTX_REQUIRE(jobs && n_jobs >= 1 && n_jobs <= 8, "gemv group: %d jobs out of range (1..8)", n_jobs);
+    LTX_REQUIRE(M >= 1 && M <= 8, "gemv group: M=%d out of range (1..8)", M);
+    GemvGroup g;
+    g.n_jobs = n_jobs;
+    g.M = M;
+    long wgs = 0;
+    for (int j = 0; j < 8; ++j) {
+        g.job[j] = j < n_jobs ? jobs[j] : GemvJob{};
+        const GemvJob& q = g.job[j];
+        LTX_REQUIRE(q.N >= 0 && q.K >= 0 && q.K % 8 == 0 && q.lda % 4 == 0 && q.ldw % 8 == 0, "gemv group: job %d N=%d K=%d lda=%ld ldw=%ld alignment",
+                    j, q.N, q.K, q.lda, q.ldw);
+        LTX_REQUIRE(q.N == 0 || (q.a && q.W && q.out), "gemv group: job %d has a null a / W / out", j);
+        wgs += (q.N + 3) / 4;
+        LTX_REQUIRE(wgs < (1L << 30), "gemv group: too many output columns");
+        g.wg_end[j] = (int)wgs;
+    }
+    if (wgs == 0) return;
+    if (M <= 2)
+        hipLaunchKernelGGL((gemv_group_kernel<2>), dim3((unsigned)wgs), dim3(256), 0, stream, g);
+    else
+        hipLaunchKernelGGL((gemv_group_kernel<8>), dim3((unsigned)wgs), dim3(256), 0, stream, g);
     HIP_CHECK(hipGetLastError());
 }

@@ -91,6 +91,7 @@ struct AudioVaeModel;
 struct VocoderModel;
 struct AttnModule;
 struct DualStack;
+struct DualModel;
 struct DistState;
 
 // ---- live per-kernel timing (HIP events recorded on the launch stream around each launch of a kernel family) ----
@@ -160,6 +161,7 @@ struct ltx_ctx {
     VocoderModel* vocoder = nullptr;
     AttnModule* attn_modules[kAttnModuleSlots] = {};  // head-dim-64 attention modules by index (attn_module.h)
     DualStack* dual = nullptr;  // dual video + audio transformer blocks (dual_block.h)
+    DualModel* dual_model = nullptr;  // the dual model: its own blocks + embedders, caption projections and heads (dual_model.h)
     DevBuf audio_mel, audio_op[2];  // the mel between the two audio models; haloed operands of the audio conv test hooks
     DevBuf h2d[H2D_COUNT];  // staging buffers of the host-pointer entry points, indexed by H2dSlot
     // load report of the last *_load call (mirrors the reference's "unmatched/missing" debug logs)
