@@ -299,8 +299,8 @@ int ltx_map_vae_encoder_key(const char* file_key, char* out, int cap);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Audio decode leg (decodeAudio, Vocoder.swift:325-361): audio latent -> AudioVAE.decode -> stereo mel -> LTX2Vocoder -> 24 kHz
- * stereo waveform. The dual (video + audio) transformer that PRODUCES the audio latent is "Dual video + audio model" below; the joint
- * denoise loop around it is not part of this library yet: the latent is an input. Precision: weights rounded to bf16 at load, bf16 conv operands, f32 accumulation, f32 residual streams.
+ * stereo waveform. The dual (video + audio) transformer that PRODUCES the audio latent is "Dual video + audio model" below, and
+ * ltx_dual_denoise is the joint loop around it: its audio latent is this leg's input. Precision: weights rounded to bf16 at load, bf16 conv operands, f32 accumulation, f32 residual streams.
  * ---------------------------------------------------------------------------------------------------------- */
 /* Replaces AudioVAE() + loadAudioVAEWeights / applyAudioVAEWeights (ModelDownloader.swift:1116-1158): keeps `decoder.*`, `latents_mean`
  * and `latents_std`, drops everything else; Conv2d weights are PyTorch (out, in, kh, kw) under `...conv.weight`. Channel counts come
@@ -344,7 +344,7 @@ int ltx_write_wav(const char* path, const float* waveform, long n, int sample_ra
  * adds four times to the video block - audio self-attention, audio text cross-attention, a2v and v2a cross-modal attention
  * (LTX2TransformerBlock.swift:133-163,207-270) - with the RoPE tables of its real-valued 1-D positions. A context holds up to four
  * modules, addressed by index 0 .. 3. The block wiring is "Dual video + audio transformer blocks" below; the audio stream's adaLN
- * embedders, the cross-modal scale-shift embedders and the joint denoise loop are not part of this library yet.
+ * embedders and the cross-modal scale-shift embedders are "Dual video + audio model", the joint denoise loop is ltx_dual_denoise.
  * ---------------------------------------------------------------------------------------------------------- */
 /* createAudioPositionGrid (LTXRoPE.swift:627-655; hop 160, rate 16000, scale 4, causal offset 1, f32 arithmetic): out[i] = seconds of
  * the middle of audio latent frame i, i < T_a (0.005, 0.03, 0.07, ...). Pure host code. */
@@ -382,8 +382,8 @@ int ltx_attn_module_forward_dev(ltx_ctx* ctx, int index, const float* x, const v
  * Dual video + audio transformer blocks: LTX2TransformerBlock (LTX2TransformerBlock.swift:174-297) as a loadable stack of L blocks
  * with a forward of its own. It takes what LTX2Transformer.callAsFunction hands its blocks and returns both residual streams. The
  * embedders that make the modulation rows (audio_adaln_single, av_ca_*), the patchify / output heads and the caption projections are
- * "Dual video + audio model" below, which owns a stack of its own; the joint denoise loop and the CLI's --audio path are not part of
- * this library yet. The modulation rows are one per batch element; the
+ * "Dual video + audio model" below, which owns a stack of its own; the joint denoise loop is ltx_dual_denoise; the CLI's --audio path
+ * is not part of this library yet. The modulation rows are one per batch element; the
  * reference's per-token form (image-to-video, LTX2Transformer.swift:285-312) is not implemented. A context holds one stack.
  * ---------------------------------------------------------------------------------------------------------- */
 typedef struct ltx_dual_block_config {
@@ -471,8 +471,10 @@ int ltx_op_norm_mod2(ltx_ctx* ctx, const ltx_norm_mod2_job* video, const ltx_nor
  * and the top-level modules of LTX2Transformer.swift:28-48: the two patchify Linears, the six AdaLayerNormSingle embedders, the two
  * caption projections, the two output tables and the two output Linears. A context holds one model, in a slot of its own: loading it
  * does not disturb the ltx_dual_blocks_* stack, and the reverse. Timesteps are one value per batch element and stream; the reference's
- * per-token form (image-to-video, LTX2Transformer.swift:285-312) is not implemented. The joint denoise loop, a text K / V^T cache across
- * steps and the CLI's --audio path are not part of this library yet.
+ * per-token form (image-to-video, LTX2Transformer.swift:285-312) is not implemented, and the CLI's --audio path is not part of this
+ * library yet. Within one prompt the text side of a forward does not change: ltx_dual_model_prepare_text_dev computes it once (both
+ * caption projections, both mask biases and, for every block, the normed K and the V^T of the two text cross-attentions) and a forward
+ * with text_cache != 0 reads it. The joint denoise loop is ltx_dual_denoise below.
  * ---------------------------------------------------------------------------------------------------------- */
 typedef struct ltx_dual_model_config {
     ltx_dual_block_config blocks;     /* video_context_dim == video_dim, audio_context_dim == audio_dim */
@@ -519,12 +521,15 @@ typedef struct ltx_dual_model_forward_args {
     float* audio_velocity;           /* [B][T_a][audio_out_channels] f32 */
     int ungrouped;                   /* measurement seam: non-zero runs the timestep path as 18 ltx_op_gemv_f32-style launches instead of
                                         three grouped ones; the same bits */
+    int text_cache;                  /* non-zero: read the text side from the cache ltx_dual_model_prepare_text_dev filled; the context
+                                        and mask pointers are not read (they may be NULL). The same bits as 0, which recomputes it */
 } ltx_dual_model_forward_args;
-#define LTX_DUAL_MODEL_FORWARD_ARGS_INIT {sizeof(ltx_dual_model_forward_args), 1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}
+#define LTX_DUAL_MODEL_FORWARD_ARGS_INIT {sizeof(ltx_dual_model_forward_args), 1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}
 /* Replaces LTX2Transformer.callAsFunction (LTX2Transformer.swift:254-392). Asynchronous on the context stream. No model:
  * LTX_ERR_MODEL_NOT_LOADED; a struct_size that does not cover the fields up to audio_velocity, B outside 1 .. 8, a dimension < 1 or a
- * NULL latent / context / timestep / velocity pointer: LTX_ERR_INVALID_CONFIGURATION. Every check comes before the first launch: a
- * refused call writes nothing. */
+ * NULL latent / context / timestep / velocity pointer: LTX_ERR_INVALID_CONFIGURATION. text_cache (read only when struct_size covers
+ * it) without a cache of this call's (B, S): LTX_ERR_INVALID_CONFIGURATION. Every check comes before the first launch: a refused call
+ * writes nothing. */
 int ltx_dual_model_forward_dev(ltx_ctx* ctx, const ltx_dual_model_forward_args* args);
 /* The timestep path of the forward alone (LTX2Transformer.swift:272-312), into caller buffers: temb_v [B][6][video_dim], temb_a
  * [B][6][audio_dim], cross_v [B][5][video_dim], cross_a [B][5][audio_dim] (rows 0-3 from the scale-shift embedder, row 4 from the
@@ -533,6 +538,34 @@ int ltx_dual_model_forward_dev(ltx_ctx* ctx, const ltx_dual_model_forward_args* 
  * ltx_dit_export_param is one. B outside 1 .. 8 or a NULL pointer: LTX_ERR_INVALID_CONFIGURATION, nothing written. */
 int ltx_dual_model_embed_dev(ltx_ctx* ctx, const float* video_timesteps, const float* audio_timesteps, int B, int ungrouped,
                              float* temb_v, float* temb_a, float* cross_v, float* cross_a, float* embts_v, float* embts_a);
+/* The text side of a forward, once per prompt: caption_projection / audio_caption_projection of the two contexts [B][S][caption_channels]
+ * bf16, the two mask biases (a NULL mask is a null bias, as in the forward) and, for every block, K (normed) and V^T of attn2 and
+ * audio_attn2 - the same launches with the same operands as a forward with text_cache = 0 runs, so the cached operands carry the same
+ * bits. The cache is ONE allocation of L * B * (S + ceil64(S)) * (video_dim + audio_dim) * 2 bytes (2.4 GB at L 48, B 2, S 1024), owned
+ * by the model; ltx_dual_model_load / _init_synthetic / _unload drop it. DEVICE pointers, asynchronous on the context stream. */
+int ltx_dual_model_prepare_text_dev(ltx_ctx* ctx, const uint16_t* video_context, const uint16_t* audio_context, const int32_t* video_mask,
+                                    const int32_t* audio_mask, int B, int S);
+/* What the text cache holds: its (B, S) (0, 0: none), its bytes, and how many times prepare_text has filled it since the model was
+ * loaded. Any output pointer may be NULL. */
+int ltx_dual_model_text_cache_info(ltx_ctx* ctx, int* B, int* S, long* bytes, long* builds);
+
+/* One job of ltx_op_dual_step: one stream's share of the work between two forwards of the joint loop. */
+typedef struct ltx_dual_step_job {
+    float* latent;         /* [n] f32, in / out, TOKEN layout [T][C] */
+    const float* v_cond;   /* [n] f32 */
+    const float* v_uncond; /* [n] f32, or NULL: no CFG */
+    float cfg_scale;
+    int form;              /* 0: the scheduler's Euler form (LTXScheduler.swift:305-327); 1: x + (sigma_next - sigma) * v (LTXPipeline.swift:1402) */
+    uint16_t* tokens;      /* [copies][n] bf16: the next forward's operand */
+    int copies;            /* 1 or 2 (a B = 2 CFG forward reads the same tokens twice) */
+    float* v_out;          /* [n] f32 or NULL: the guided velocity; may alias v_cond */
+    long n;                /* elements; n % 4 == 0; 0: the job is empty */
+} ltx_dual_step_job;
+/* Kernel hook: CFG (LatentUtils.swift:131-141), the Euler step and the bf16 cast of both streams in one launch. Every operation is
+ * rounded on its own (no fused multiply-add, correctly rounded division), as the reference's separate array ops are: latent and v_out
+ * are bit-equal to a float32 replay of those ops. Either job may be NULL or empty. n % 4 != 0, copies outside 1 .. 2, form outside
+ * 0 .. 1, a NULL latent / v_cond / tokens with n > 0, or sigma <= 0: LTX_ERR_INVALID_CONFIGURATION before the launch, nothing written. */
+int ltx_op_dual_step(ltx_ctx* ctx, const ltx_dual_step_job* video, const ltx_dual_step_job* audio, float sigma, float sigma_next);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Text-embedding connector (VideoGemmaTextEncoderModel.encodeFromHiddenStates,
@@ -638,6 +671,38 @@ int ltx_denoise(ltx_ctx* ctx, float* latent, int F, int H, int W, const float* s
 int ltx_denoise_dev(ltx_ctx* ctx, float* latent, int F, int H, int W, const float* sigmas, int n_sigmas,
                     const uint16_t* context, const int32_t* mask, int mask_all_ones, int S, uint64_t ctx_version,
                     const ltx_denoise_options* opt, ltx_progress_cb cb, void* user);
+
+/* Arguments of ltx_dual_denoise(_dev); starts with its own size (LTX_DUAL_DENOISE_ARGS_INIT). */
+typedef struct ltx_dual_denoise_args {
+    uint32_t struct_size;          /* sizeof(ltx_dual_denoise_args) in the caller's translation unit */
+    int F, H, W;                   /* latent frames / height / width */
+    int T_a;                       /* audio latent frames */
+    int S;                         /* text tokens */
+    float* video_latent;           /* [1][in_channels][F][H][W] f32, in / out, already scaled by sigmas[0]: ltx_denoise's and ltx_vae_decode's layout */
+    float* audio_latent;           /* [1][8][T_a][16] f32, in / out, scaled: the layout ltx_audio_decode takes */
+    const float* sigmas;           /* HOST, n_sigmas values: one schedule for both streams (the reference builds two identical schedulers) */
+    int n_sigmas;
+    const uint16_t* video_context; /* [nb][S][caption_channels] bf16, nb = 2 ([negative, positive]) iff cfg_scale > 1 */
+    const uint16_t* audio_context; /* the same shape, or NULL: the video context (audioEncoding ?? videoEncoding) */
+    const int32_t* mask;           /* [nb][S] int32 or NULL; both streams use it (LTXPipeline.swift:1322-1323) */
+    float cfg_scale;
+    float guidance_rescale;        /* > 0 (needs cfg_scale > 1): applied to the VIDEO velocity only (LTXPipeline.swift:1352-1359) */
+    int text_cache;                /* non-zero (default): the text side is computed once; 0 recomputes it every step. The same bits */
+    float* step_stats;             /* HOST, 8 * (n_sigmas - 1) floats or NULL: per step mean and std of the video velocity, the video
+                                      latent, the audio velocity and the audio latent. Non-NULL makes the _dev call synchronous */
+} ltx_dual_denoise_args;
+#define LTX_DUAL_DENOISE_ARGS_INIT {(uint32_t)sizeof(ltx_dual_denoise_args), 0, 0, 0, 0, 0, NULL, NULL, NULL, 0, NULL, NULL, NULL, 1.0f, 0.0f, 1, NULL}
+/* Replaces the denoise loop of generateVideoWithAudio (LTXPipeline.swift:1276-1417), text-to-video+audio: per step the progress
+ * callback, ONE dual-model forward (B = 2 on [negative, positive] with CFG), optional guidance rescale of the video velocity, and ONE
+ * launch for CFG + both Euler steps + the next forward's tokens (ltx_op_dual_step; video form 0, audio form 1). Both latents are held in
+ * token layout for the whole loop and transposed once at entry and once at exit. Noise is the caller's (video first, then audio,
+ * :1229-1236). Image-to-video, STG, GE, the two-stage path and sharding are not implemented here. DEVICE pointers except sigmas and
+ * step_stats; asynchronous on the context stream unless step_stats is set. No dual model: LTX_ERR_MODEL_NOT_LOADED; a short struct_size,
+ * n_sigmas < 2, a dimension < 1, a NULL latent / sigmas / video_context, a sigma <= 0 before the last, or guidance_rescale > 0 without
+ * CFG: LTX_ERR_INVALID_CONFIGURATION. Every check comes before the first launch: a refused call leaves both latents untouched. */
+int ltx_dual_denoise_dev(ltx_ctx* ctx, const ltx_dual_denoise_args* args, ltx_progress_cb cb, void* user);
+/* The same with HOST pointers throughout; staged through the context's staging buffers, synchronous. */
+int ltx_dual_denoise(ltx_ctx* ctx, const ltx_dual_denoise_args* args, ltx_progress_cb cb, void* user);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Multi-GPU: one process per GPU, one ltx_ctx per process, RCCL over xGMI called by the library itself (librccl is loaded

@@ -16,8 +16,8 @@ import numpy as np
 
 from . import _lib
 from ._lib import (ALLGATHER_FN, DIST_ID_BYTES, SHARD_CFG, SHARD_NONE, SHARD_SEQUENCE, ConnectorConfig, PROGRESS_CB, DenoiseOptions,
-                   DualBlockConfig, DualForwardArgs, DualModelConfig, DualModelForwardArgs, GemvJob, LTXError, NormMod2Job,
-                   TransformerConfig, lib)
+                   DualBlockConfig, DualDenoiseArgs, DualForwardArgs, DualModelConfig, DualModelForwardArgs, DualStepJob, GemvJob,
+                   LTXError, NormMod2Job, TransformerConfig, lib)
 
 __version__ = lib.ltx_version().decode()
 
@@ -976,14 +976,16 @@ class Context:
 
     def dual_model_forward_dev(self, video_latent, audio_latent, video_context, audio_context, video_timesteps, audio_timesteps,
                                video_velocity, audio_velocity, F, H, W, video_mask=None, audio_mask=None, ungrouped=False, struct_size=None,
-                               T_a=None):
+                               T_a=None, text_cache=0, S=None):
         """``ltx_dual_model_forward_dev``: device tensors; latents [B][T][C] and contexts [B][S][caption_channels] bf16, timesteps [B] f32
-        (sigma), masks [B][S] int32 or None; the velocities [B][F*H*W][out_channels] / [B][T_a][audio_out_channels] f32 are written."""
+        (sigma), masks [B][S] int32 or None; the velocities [B][F*H*W][out_channels] / [B][T_a][audio_out_channels] f32 are written.
+        ``text_cache`` non-zero reads the text side from ``dual_model_prepare_text``: the contexts and masks may be None (give ``S``)."""
         a = DualModelForwardArgs()
         a.struct_size = C.sizeof(DualModelForwardArgs) if struct_size is None else struct_size
         a.B, a.F, a.H, a.W = video_latent.shape[0], F, H, W
         a.T_a = audio_latent.shape[1] if T_a is None else T_a
-        a.S = video_context.shape[1]
+        a.S = video_context.shape[1] if S is None else S
+        a.text_cache = int(text_cache)
         a.video_latent, a.audio_latent = _ptr(video_latent), _ptr(audio_latent)
         a.video_context, a.audio_context = _ptr(video_context), _ptr(audio_context)
         a.video_timesteps, a.audio_timesteps = _ptr(video_timesteps), _ptr(audio_timesteps)
@@ -997,6 +999,76 @@ class Context:
         self._ck(lib.ltx_dual_model_embed_dev(self._h, _ptr(video_timesteps), _ptr(audio_timesteps),
                                               video_timesteps.shape[0] if B is None else B, int(ungrouped), _ptr(temb_v), _ptr(temb_a),
                                               _ptr(cross_v), _ptr(cross_a), _ptr(embts_v), _ptr(embts_a)))
+
+    def dual_model_prepare_text(self, video_context, audio_context, video_mask=None, audio_mask=None, B=None, S=None):
+        """``ltx_dual_model_prepare_text_dev``: the text side of the forwards of one prompt, once (contexts [B][S][caption_channels] bf16,
+        masks [B][S] int32 or None; device tensors)."""
+        self._ck(lib.ltx_dual_model_prepare_text_dev(self._h, _ptr(video_context), _ptr(audio_context), _ptr(video_mask), _ptr(audio_mask),
+                                                     video_context.shape[0] if B is None else B, video_context.shape[1] if S is None else S))
+
+    def dual_model_text_cache_info(self):
+        """``ltx_dual_model_text_cache_info`` as a dict(B=, S=, bytes=, builds=)."""
+        B, S, nb, builds = C.c_int(), C.c_int(), C.c_long(), C.c_long()
+        self._ck(lib.ltx_dual_model_text_cache_info(self._h, C.byref(B), C.byref(S), C.byref(nb), C.byref(builds)))
+        return {"B": B.value, "S": S.value, "bytes": nb.value, "builds": builds.value}
+
+    @staticmethod
+    def _dual_denoise_args(video_latent, audio_latent, sg, video_context, audio_context, mask, F, H, W, T_a, S, cfg_scale, guidance_rescale,
+                           text_cache, stats, struct_size):
+        a = DualDenoiseArgs()
+        a.struct_size = C.sizeof(DualDenoiseArgs) if struct_size is None else struct_size
+        a.F, a.H, a.W, a.T_a, a.S = F, H, W, T_a, S
+        a.video_latent, a.audio_latent = _ptr(video_latent), _ptr(audio_latent)
+        a.sigmas, a.n_sigmas = sg.ctypes.data_as(C.POINTER(C.c_float)), len(sg)
+        a.video_context, a.audio_context, a.mask = _ptr(video_context), _ptr(audio_context), _ptr(mask)
+        a.cfg_scale, a.guidance_rescale, a.text_cache = cfg_scale, guidance_rescale, int(text_cache)
+        a.step_stats = None if stats is None else stats.ctypes.data
+        return a
+
+    def dual_denoise_dev(self, video_latent, audio_latent, sigmas_, video_context, F, H, W, audio_context=None, mask=None, cfg_scale=1.0,
+                         guidance_rescale=0.0, text_cache=1, step_stats=False, on_progress=None, T_a=None, S=None, struct_size=None):
+        """``ltx_dual_denoise_dev``: the joint loop on device tensors, in place. video_latent [1][C][F][H][W] f32 and audio_latent
+        [1][8][T_a][16] f32, scaled by sigmas[0]; contexts [nb][S][caption_channels] bf16, nb = 2 ([negative, positive]) iff cfg_scale > 1;
+        mask [nb][S] int32 or None. Returns the step statistics [steps][8] when ``step_stats``, else None."""
+        sg = np.ascontiguousarray(sigmas_, dtype=np.float32)
+        cb = PROGRESS_CB(on_progress if on_progress else (lambda s, t, sig, u: None))
+        stats = np.zeros((max(len(sg) - 1, 0), 8), np.float32) if step_stats else None
+        a = self._dual_denoise_args(video_latent, audio_latent, sg, video_context, audio_context, mask, F, H, W,
+                                    audio_latent.shape[2] if T_a is None else T_a, video_context.shape[1] if S is None else S, cfg_scale,
+                                    guidance_rescale, text_cache, stats, struct_size)
+        self._ck(lib.ltx_dual_denoise_dev(self._h, C.byref(a), cb, None))
+        return stats
+
+    def dual_denoise(self, video_latent, audio_latent, sigmas_, video_context_bf16, F, H, W, audio_context_bf16=None, mask=None, cfg_scale=1.0,
+                     guidance_rescale=0.0, text_cache=1, step_stats=False, on_progress=None):
+        """``ltx_dual_denoise``: the same with host arrays (contexts as bf16 bit patterns, uint16). Returns (video_latent, audio_latent)
+        or, with ``step_stats``, (video_latent, audio_latent, stats)."""
+        v = np.ascontiguousarray(video_latent, dtype=np.float32).copy()
+        au = np.ascontiguousarray(audio_latent, dtype=np.float32).copy()
+        sg = np.ascontiguousarray(sigmas_, dtype=np.float32)
+        cv = np.ascontiguousarray(video_context_bf16)
+        ca = None if audio_context_bf16 is None else np.ascontiguousarray(audio_context_bf16)
+        mk = None if mask is None else np.ascontiguousarray(mask, dtype=np.int32)
+        cb = PROGRESS_CB(on_progress if on_progress else (lambda s, t, sig, u: None))
+        stats = np.zeros((max(len(sg) - 1, 0), 8), np.float32) if step_stats else None
+        a = self._dual_denoise_args(v, au, sg, cv, ca, mk, F, H, W, au.shape[2], cv.shape[1], cfg_scale, guidance_rescale, text_cache, stats, None)
+        self._ck(lib.ltx_dual_denoise(self._h, C.byref(a), cb, None))
+        return (v, au, stats) if step_stats else (v, au)
+
+    def op_dual_step(self, video=None, audio=None, sigma=1.0, sigma_next=0.0):
+        """``ltx_op_dual_step``: each job is None or a dict(latent=, v_cond=, tokens= tensors, v_uncond=None, v_out=None, cfg_scale=1.0,
+        form=0, copies=1, n= latent.numel())."""
+        def job(j):
+            if j is None:
+                return None
+            o = DualStepJob()
+            for k in ("latent", "v_cond", "v_uncond", "tokens", "v_out"):
+                t = j.get(k)
+                setattr(o, k, None if t is None else t.data_ptr())
+            o.cfg_scale, o.form, o.copies = j.get("cfg_scale", 1.0), j.get("form", 0), j.get("copies", 1)
+            o.n = j["n"] if "n" in j else j["latent"].numel()
+            return C.byref(o)
+        self._ck(lib.ltx_op_dual_step(self._h, job(video), job(audio), sigma, sigma_next))
 
     def op_gemv_group(self, jobs, M=None, n_jobs=None):
         """``ltx_op_gemv_group``: each job is a dict(a= [M][K] f32, W= [N][K] bf16, out= a 2-D f32 view whose row stride is ldo, bias=

@@ -97,7 +97,7 @@ class DualModelForwardArgs(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("B", C.c_int), ("F", C.c_int), ("H", C.c_int), ("W", C.c_int), ("T_a", C.c_int), ("S", C.c_int),
                 ("video_latent", C.c_void_p), ("audio_latent", C.c_void_p), ("video_context", C.c_void_p), ("audio_context", C.c_void_p),
                 ("video_timesteps", C.c_void_p), ("audio_timesteps", C.c_void_p), ("video_mask", C.c_void_p), ("audio_mask", C.c_void_p),
-                ("video_velocity", C.c_void_p), ("audio_velocity", C.c_void_p), ("ungrouped", C.c_int)]
+                ("video_velocity", C.c_void_p), ("audio_velocity", C.c_void_p), ("ungrouped", C.c_int), ("text_cache", C.c_int)]
 
 
 class NormMod2Job(C.Structure):
@@ -106,6 +106,22 @@ class NormMod2Job(C.Structure):
     _fields_ = [("x", C.c_void_p), ("ldx", C.c_long), ("scale0", C.c_void_p), ("shift0", C.c_void_p), ("scale1", C.c_void_p),
                 ("shift1", C.c_void_p), ("mod_bstride", C.c_long), ("rows_per_batch", C.c_int), ("out0", C.c_void_p), ("out1", C.c_void_p),
                 ("ldo", C.c_long), ("rows", C.c_int), ("D", C.c_int)]
+
+
+class DualStepJob(C.Structure):
+    """``ltx_dual_step_job``: one job of ``ltx_op_dual_step``."""
+
+    _fields_ = [("latent", C.c_void_p), ("v_cond", C.c_void_p), ("v_uncond", C.c_void_p), ("cfg_scale", C.c_float), ("form", C.c_int),
+                ("tokens", C.c_void_p), ("copies", C.c_int), ("v_out", C.c_void_p), ("n", C.c_long)]
+
+
+class DualDenoiseArgs(C.Structure):
+    """``ltx_dual_denoise_args``: the joint video + audio loop of generateVideoWithAudio (LTXPipeline.swift:1276-1417)."""
+
+    _fields_ = [("struct_size", C.c_uint32), ("F", C.c_int), ("H", C.c_int), ("W", C.c_int), ("T_a", C.c_int), ("S", C.c_int),
+                ("video_latent", C.c_void_p), ("audio_latent", C.c_void_p), ("sigmas", C.POINTER(C.c_float)), ("n_sigmas", C.c_int),
+                ("video_context", C.c_void_p), ("audio_context", C.c_void_p), ("mask", C.c_void_p), ("cfg_scale", C.c_float),
+                ("guidance_rescale", C.c_float), ("text_cache", C.c_int), ("step_stats", C.c_void_p)]
 
 
 def _load():
@@ -266,6 +282,11 @@ SIGNATURES = {
     "ltx_dual_model_export_param": (_l, [_vp, C.c_char_p, _vp, _l]),
     "ltx_dual_model_forward_dev": (_i, [_vp, C.POINTER(DualModelForwardArgs)]),
     "ltx_dual_model_embed_dev": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ltx_dual_model_prepare_text_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i]),
+    "ltx_dual_model_text_cache_info": (_i, [_vp, _ip, _ip, C.POINTER(_l), C.POINTER(_l)]),
+    "ltx_op_dual_step": (_i, [_vp, C.POINTER(DualStepJob), C.POINTER(DualStepJob), _f, _f]),
+    "ltx_dual_denoise_dev": (_i, [_vp, C.POINTER(DualDenoiseArgs), PROGRESS_CB, _vp]),
+    "ltx_dual_denoise": (_i, [_vp, C.POINTER(DualDenoiseArgs), PROGRESS_CB, _vp]),
     "ltx_op_attention_hd": (_i, [_vp, _vp, _vp, _vp, _l, _vp, _i, _i, _i, _i, _i, _f, _vp]),
     "ltx_attention_hd_workgroup_queries": (_i, [_i, _i, _i, _i]),
     "ltx_op_qknorm_rope_hd": (_i, [_vp, _vp, _l, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _vp]),

@@ -340,6 +340,20 @@ int ltx_op_norm_mod2(ltx_ctx* ctx, const ltx_norm_mod2_job* video, const ltx_nor
     });
 }
 
+int ltx_op_dual_step(ltx_ctx* ctx, const ltx_dual_step_job* video, const ltx_dual_step_job* audio, float sigma, float sigma_next) {
+    return with_ctx(ctx, [&] {
+        auto job = [](const ltx_dual_step_job* j) {
+            DualStepJob o;
+            if (!j) return o;
+            o.latent = j->latent; o.v_cond = j->v_cond; o.v_uncond = j->v_uncond;
+            o.cfg_scale = j->cfg_scale; o.form = j->form;
+            o.tokens = j->tokens; o.copies = j->copies; o.v_out = j->v_out; o.n = j->n;
+            return o;
+        };
+        launch_dual_step(job(video), job(audio), sigma, sigma_next, ctx->stream);
+    });
+}
+
 int ltx_op_qknorm_rope_pair(ltx_ctx* ctx, const void* x0, const float* w0, uint16_t* out0, const void* x1, const float* w1,
                             uint16_t* out1, long ldx, long ldo, const float* cos_t, const float* sin_t, int T, int rows, int D,
                             float eps, float out_scale0, int x_bf16) {

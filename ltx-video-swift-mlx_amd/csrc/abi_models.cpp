@@ -9,6 +9,7 @@
 #include "audio.h"
 #include "attn_module.h"
 #include "dual_block.h"
+#include "dual_denoise.h"
 #include "dual_model.h"
 #include "connector.h"
 #include "dist.h"
@@ -1007,6 +1008,7 @@ int ltx_dual_model_forward_dev(ltx_ctx* ctx, const ltx_dual_model_forward_args* 
         a.video_mask = args->video_mask; a.audio_mask = args->audio_mask;
         a.video_velocity = args->video_velocity; a.audio_velocity = args->audio_velocity;
         if (sz >= offsetof(ltx_dual_model_forward_args, ungrouped) + sizeof(args->ungrouped)) a.ungrouped = args->ungrouped;
+        if (sz >= offsetof(ltx_dual_model_forward_args, text_cache) + sizeof(args->text_cache)) a.text_cache = args->text_cache;
         dual_model_forward(ctx, m, a);
     });
 }
@@ -1017,6 +1019,83 @@ int ltx_dual_model_embed_dev(ltx_ctx* ctx, const float* video_timesteps, const f
         DualEmbedOut o;
         o.temb_v = temb_v; o.temb_a = temb_a; o.cross_v = cross_v; o.cross_a = cross_a; o.embts_v = embts_v; o.embts_a = embts_a;
         dual_model_embed(ctx, m, video_timesteps, audio_timesteps, B, ungrouped != 0, o);
+    });
+}
+int ltx_dual_model_prepare_text_dev(ltx_ctx* ctx, const uint16_t* video_context, const uint16_t* audio_context, const int32_t* video_mask,
+                                    const int32_t* audio_mask, int B, int S) {
+    return with_ctx(ctx, [&] {
+        DualModel* m = need(ctx->dual_model, kNoDualModel);
+        dual_model_prepare_text(ctx, m, video_context, audio_context, video_mask, audio_mask, B, S);
+    });
+}
+int ltx_dual_model_text_cache_info(ltx_ctx* ctx, int* B, int* S, long* bytes, long* builds) {
+    return with_ctx(ctx, [&] {
+        const DualTextCache& c = need(ctx->dual_model, kNoDualModel)->stack->text_cache;
+        if (B) *B = c.B;
+        if (S) *S = c.S;
+        if (bytes) *bytes = c.bytes;
+        if (builds) *builds = c.builds;
+    });
+}
+
+/* ---- the joint video + audio denoise loop (dual_denoise.h) ---- */
+namespace {
+void dual_denoise_params(ltx_ctx* ctx, const ltx_dual_denoise_args* args, ltx_progress_cb cb, void* user, const char* who, DualDenoiseParams& p) {
+    need(ctx->dual_model, kNoDualModel);
+    LTX_REQUIRE(args != nullptr, "%s: null arguments", who);
+    const size_t sz = args->struct_size;
+    LTX_REQUIRE(sz >= offsetof(ltx_dual_denoise_args, step_stats) + sizeof(args->step_stats) && sz <= 4096,
+                "ltx_dual_denoise_args.struct_size = %zu: set it to sizeof(ltx_dual_denoise_args) (LTX_DUAL_DENOISE_ARGS_INIT); this library is ABI revision %d",
+                sz, LTX_ABI_VERSION);
+    p.F = args->F; p.H = args->H; p.W = args->W; p.T_a = args->T_a; p.S = args->S;
+    p.video_latent = args->video_latent; p.audio_latent = args->audio_latent;
+    p.sigmas = args->sigmas; p.n_sigmas = args->n_sigmas;
+    p.video_context = args->video_context; p.audio_context = args->audio_context; p.mask = args->mask;
+    p.cfg_scale = args->cfg_scale; p.guidance_rescale = args->guidance_rescale;
+    p.text_cache = args->text_cache; p.step_stats = args->step_stats;
+    p.progress = cb; p.user = user;
+}
+}  // namespace
+
+int ltx_dual_denoise_dev(ltx_ctx* ctx, const ltx_dual_denoise_args* args, ltx_progress_cb cb, void* user) {
+    return with_ctx(ctx, [&] {
+        DualDenoiseParams p;
+        dual_denoise_params(ctx, args, cb, user, "ltx_dual_denoise_dev", p);
+        dual_denoise_run(ctx, p);
+    });
+}
+
+int ltx_dual_denoise(ltx_ctx* ctx, const ltx_dual_denoise_args* args, ltx_progress_cb cb, void* user) {
+    return with_ctx(ctx, [&] {
+        DualDenoiseParams p;
+        dual_denoise_params(ctx, args, cb, user, "ltx_dual_denoise", p);
+        const DualModel* m = ctx->dual_model;
+        // what staging needs; dual_denoise_run repeats these checks among its own
+        LTX_REQUIRE(p.video_latent && p.audio_latent && p.video_context && p.F >= 1 && p.H >= 1 && p.W >= 1 && p.T_a >= 1 && p.S >= 1 &&
+                        p.T_a <= (1 << 20) && p.S <= (1 << 20) && (long)p.F * p.H * p.W <= (1 << 20) && p.n_sigmas >= 2 && p.sigmas,
+                    "ltx_dual_denoise: bad arguments");
+        LTX_REQUIRE(!(p.guidance_rescale > 0.f) || p.cfg_scale > 1.0f, "ltx_dual_denoise: guidance_rescale needs cfg_scale > 1");
+        for (int i = 0; i + 1 < p.n_sigmas; ++i) LTX_REQUIRE(p.sigmas[i] > 0.f, "ltx_dual_denoise: sigmas[%d] must be positive", i);
+        const int nb = p.cfg_scale > 1.0f ? 2 : 1;
+        const size_t n_v = (size_t)m->cfg.in_channels * p.F * p.H * p.W * 4, n_a = (size_t)128 * p.T_a * 4;
+        const size_t n_ctx = (size_t)nb * p.S * m->cfg.caption_channels * 2, n_mask = (size_t)nb * p.S * 4;
+        DevBuf &d_v = ctx->h2d[H2D_DENOISE_LATENT], &d_a = ctx->h2d[H2D_DUAL_AUDIO_LATENT], &d_cv = ctx->h2d[H2D_DENOISE_CONTEXT],
+               &d_ca = ctx->h2d[H2D_DUAL_AUDIO_CONTEXT], &d_mask = ctx->h2d[H2D_DENOISE_MASK];
+        float* host_v = p.video_latent;
+        float* host_a = p.audio_latent;
+        stage_in(ctx, d_v, host_v, n_v);
+        stage_in(ctx, d_a, host_a, n_a);
+        stage_in(ctx, d_cv, p.video_context, n_ctx);
+        if (p.audio_context) stage_in(ctx, d_ca, p.audio_context, n_ctx);
+        if (p.mask) stage_in(ctx, d_mask, p.mask, n_mask);
+        p.video_latent = d_v.as<float>(); p.audio_latent = d_a.as<float>();
+        p.video_context = d_cv.as<bf16_t>();
+        p.audio_context = p.audio_context ? d_ca.as<bf16_t>() : nullptr;
+        p.mask = p.mask ? d_mask.as<int32_t>() : nullptr;
+        dual_denoise_run(ctx, p);
+        stage_out(ctx, host_v, d_v, n_v);
+        stage_out(ctx, host_a, d_a, n_a);
+        stage_sync(ctx);
     });
 }
 

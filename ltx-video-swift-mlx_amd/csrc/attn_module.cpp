@@ -268,13 +268,49 @@ void attn_core_reserve(const AttnModule* m, AttnCoreScratch* ws, AttnVtSlot* vt,
     if (vt->buf.ensure((size_t)B * I * Tpad * 2)) vt->inner = vt->Tpad = vt->B = 0;  // new memory: zeroed by the first launch sequence
 }
 
+namespace {
+// the key side of attn_module_core when q and k are separate projections: k GEMM, k norm + RoPE, V^T per batch element
+void launch_k_gemm(AttnModule* m, const bf16_t* cb, bool kb, long krows, float* kraw, hipStream_t st, const SplitWs& sk) {
+    GemmEpilogue ek;
+    if (kb) {
+        ek.out_bf16 = (bf16_t*)kraw;
+        ek.ld_bf16 = m->inner;
+    } else {
+        ek.out_f32 = kraw;
+        ek.ld_f32 = m->inner;
+    }
+    gemm_linear(cb, m->Dc, m->k, (int)krows, ek, st, sk);
+}
+void launch_k_norm(AttnModule* m, const float* kraw, const float* kc, const float* ks, int Tk, bf16_t* k, long krows, bool kb, hipStream_t st) {
+    launch_qknorm_rope(kraw, m->inner, m->kn, kc, ks, Tk, k, m->inner, (int)krows, m->inner, m->eps, st, 1.0f, kb, m->head_dim);
+}
+void launch_vt(AttnModule* m, const bf16_t* cb, int B, int Tk, int Tpad, bf16_t* vt, hipStream_t st, const SplitWs& sk) {
+    for (int b = 0; b < B; ++b) gemm_vt(cb + (size_t)b * Tk * m->Dc, m->Dc, Tk, m->v, vt + (size_t)b * m->inner * Tpad, Tpad, st, sk);
+}
+}  // namespace
+
+void attn_module_build_kv(ltx_ctx* ctx, AttnModule* m, const AttnCoreArgs& a, AttnCoreScratch* ws, bf16_t* k_out, bf16_t* vt_out) {
+    hipStream_t st = ctx->stream;
+    const long krows = (long)a.B * a.Tk;
+    const int Tpad = ((a.Tk + 63) / 64) * 64;
+    const SplitWs sk{a.split_ws, a.split_ws_elems};
+    const bool kb = a.kv_bf16 != 0;
+    const float* kc = a.q_cos ? (a.k_cos ? a.k_cos : a.q_cos) : nullptr;
+    const float* ks = a.q_cos ? (a.k_cos ? a.k_sin : a.q_sin) : nullptr;
+    float* kraw = ws->kraw.as<float>();
+    launch_k_gemm(m, a.ctx, kb, krows, kraw, st, sk);
+    launch_k_norm(m, kraw, kc, ks, a.Tk, k_out, krows, kb, st);
+    launch_vt(m, a.ctx, a.B, a.Tk, Tpad, vt_out, st, sk);
+}
+
 void attn_module_core(ltx_ctx* ctx, AttnModule* m, const AttnCoreArgs& a, AttnCoreScratch* ws, AttnVtSlot* vs) {
     hipStream_t st = ctx->stream;
     const int I = m->inner, Dq = m->Dq, Dc = m->Dc, B = a.B, Tq = a.Tq, Tk = a.Tk, hd = m->head_dim;
     const long qrows = (long)B * Tq, krows = (long)B * Tk;
     const int Tpad = ((Tk + 63) / 64) * 64;
     const SplitWs sk{a.split_ws, a.split_ws_elems};
-    if (vs->inner != I || vs->Tpad != Tpad || vs->B != B) {  // the pad columns of V^T must be finite
+    const bool cached = a.cached_k && a.cached_vt;
+    if (!cached && (vs->inner != I || vs->Tpad != Tpad || vs->B != B)) {  // the pad columns of V^T must be finite
         HIP_CHECK(hipMemsetAsync(vs->buf.p, 0, (size_t)B * I * Tpad * 2, st));
         vs->inner = I;
         vs->Tpad = Tpad;
@@ -285,8 +321,8 @@ void attn_module_core(ltx_ctx* ctx, AttnModule* m, const AttnCoreArgs& a, AttnCo
     float* qraw = ws->qraw.as<float>();
     float* kraw = ws->kraw.as<float>();
     bf16_t* q = ws->q.as<bf16_t>();
-    bf16_t* k = ws->k.as<bf16_t>();
-    bf16_t* vt = vs->buf.as<bf16_t>();
+    const bf16_t* k = cached ? a.cached_k : ws->k.as<bf16_t>();
+    const bf16_t* vt = cached ? a.cached_vt : vs->buf.as<bf16_t>();
     bf16_t* ao = ws->ao.as<bf16_t>();
     const float qscale = hd == 64 ? kAttnQueryPrescale64 : kAttnQueryPrescale;
     const float* kc = a.q_cos ? (a.k_cos ? a.k_cos : a.q_cos) : nullptr;
@@ -300,26 +336,19 @@ void attn_module_core(ltx_ctx* ctx, AttnModule* m, const AttnCoreArgs& a, AttnCo
         e.out_f32 = qraw;
         e.ld_f32 = 2 * I;
         gemm_linear(a.xq, Dq, qk, (int)qrows, e, st, sk);
-        launch_qknorm_rope2(qraw, m->qn, q, qraw + I, m->kn, k, 2 * I, I, a.q_cos, a.q_sin, Tq, (int)qrows, I, m->eps, st, qscale, false, hd);
+        launch_qknorm_rope2(qraw, m->qn, q, qraw + I, m->kn, ws->k.as<bf16_t>(), 2 * I, I, a.q_cos, a.q_sin, Tq, (int)qrows, I, m->eps, st, qscale,
+                            false, hd);
     } else {
         GemmEpilogue eq;
         eq.out_f32 = qraw;
         eq.ld_f32 = I;
         gemm_linear(a.xq, Dq, m->q, (int)qrows, eq, st, sk);
-        GemmEpilogue ek;
-        if (kb) {
-            ek.out_bf16 = (bf16_t*)kraw;
-            ek.ld_bf16 = I;
-        } else {
-            ek.out_f32 = kraw;
-            ek.ld_f32 = I;
-        }
-        gemm_linear(cb, Dc, m->k, (int)krows, ek, st, sk);
+        if (!cached) launch_k_gemm(m, cb, kb, krows, kraw, st, sk);
         // q and k come from different inputs, token counts and tables: two one-job launches
         launch_qknorm_rope(qraw, I, m->qn, a.q_cos, a.q_sin, Tq, q, I, (int)qrows, I, m->eps, st, qscale, false, hd);
-        launch_qknorm_rope(kraw, I, m->kn, kc, ks, Tk, k, I, (int)krows, I, m->eps, st, 1.0f, kb, hd);
+        if (!cached) launch_k_norm(m, kraw, kc, ks, Tk, ws->k.as<bf16_t>(), krows, kb, st);
     }
-    for (int b = 0; b < B; ++b) gemm_vt(cb + (size_t)b * Tk * Dc, Dc, Tk, m->v, vt + (size_t)b * I * Tpad, Tpad, st, sk);
+    if (!cached) launch_vt(m, cb, B, Tk, Tpad, vs->buf.as<bf16_t>(), st, sk);
 
     AttnArgs at;
     at.head_dim = hd;

@@ -96,8 +96,17 @@ struct AttnCoreArgs {
     long gate_bstride = 0;
     float* split_ws = nullptr;     // optional split-K workspace of the GEMMs (floats)
     long split_ws_elems = 0;
+    // K and V^T of a context that does not change between calls (attn_module_build_kv made them): both set = the k GEMM, k's norm pass
+    // and the V^T GEMMs are skipped and the attention reads these. ctx / kv_bf16 / the key tables are then not read.
+    const bf16_t* cached_k = nullptr;   // [B][Tk][inner] bf16, normed
+    const bf16_t* cached_vt = nullptr;  // [B][inner][ceil64(Tk)] bf16, pad columns finite
 };
 // grows the scratch for one attention of these shapes (no launch; may allocate)
 void attn_core_reserve(const AttnModule* m, AttnCoreScratch* ws, AttnVtSlot* vt, int B, int Tq, int Tk);
 // launches only: the caller has checked its arguments and reserved the scratch
 void attn_module_core(ltx_ctx* ctx, AttnModule* m, const AttnCoreArgs& a, AttnCoreScratch* ws, AttnVtSlot* vt);
+// K and V^T of one context into caller memory (k_out [B][Tk][inner], vt_out [B][inner][ceil64(Tk)] whose pad columns the caller has made
+// finite): exactly the launches attn_module_core runs for them when nothing is cached - the k GEMM into ws->kraw, k's norm (+ RoPE)
+// pass, one V^T GEMM per batch element - with the same operands, a.kv_bf16 and the split-K workspace included, so the outputs carry the
+// same bits. Reads a.ctx, a.kv_bf16, a.B, a.Tk, the key tables and a.split_ws; not for a fused q|k module. ws->kraw is reserved.
+void attn_module_build_kv(ltx_ctx* ctx, AttnModule* m, const AttnCoreArgs& a, AttnCoreScratch* ws, bf16_t* k_out, bf16_t* vt_out);

@@ -293,15 +293,57 @@ void ffn_phase(float* x, int D, int T, long rows, const float* mod, long mod_bs,
     gemm_linear(ffh, 4L * D, ff2, (int)rows, e2, st, sk);
 }
 
+// where block l's four cached tensors start (elements of bf16)
+struct TextCacheSlices {
+    bf16_t *k_v, *vt_v, *k_a, *vt_a;
+};
+TextCacheSlices text_cache_slices(const DualTextCache& c, int l, int Dv, int Da) {
+    const long B = c.B, S = c.S, Sp = c.Spad;
+    const long kv = B * S * Dv, vv = B * Dv * Sp, ka = B * S * Da, va = B * Da * Sp;
+    bf16_t* base = c.buf.as<bf16_t>() + (long)l * (kv + vv + ka + va);
+    return {base, base + kv, base + kv + vv, base + kv + vv + ka};
+}
+
 }  // namespace
+
+void dual_prepare_text(ltx_ctx* ctx, DualStack* m, const bf16_t* ctx_video, const bf16_t* ctx_audio, int B, int S) {
+    const int L = m->L, Dv = m->Dv, Da = m->Da;
+    if (B < 1 || B > 8 || S < 1 || S > (1 << 20)) LTX_THROW(LTXS_INVALID_CONFIGURATION, "dual prepare text: bad shapes B=%d (1 .. 8) S=%d", B, S);
+    if (!ctx_video || !ctx_audio) LTX_THROW(LTXS_INVALID_CONFIGURATION, "dual prepare text: null context pointer");
+    hipStream_t st = ctx->stream;
+    DualTextCache& c = m->text_cache;
+    const int Spad = ((S + 63) / 64) * 64;
+    const long bytes = (long)L * B * (S + Spad) * (Dv + Da) * 2;
+    m->attn_ws.kraw.ensure((size_t)B * S * std::max(Dv, Da) * 4);
+    m->ws_splitk.ensure((size_t)8 << 22);
+    const bool fresh = c.buf.ensure((size_t)bytes);
+    if (fresh || c.B != B || c.S != S) HIP_CHECK(hipMemsetAsync(c.buf.p, 0, (size_t)bytes, st));  // the pad columns of V^T must be finite
+    c.B = B; c.S = S; c.Spad = Spad; c.bytes = bytes;
+    const SplitWs sk{m->ws_splitk.as<float>(), (long)(m->ws_splitk.bytes / 4)};
+    for (int l = 0; l < L; ++l) {
+        DualBlock& b = m->blocks[l];
+        const TextCacheSlices t = text_cache_slices(c, l, Dv, Da);
+        AttnCoreArgs k;  // what phases 3 and 4 hand attn_module_core for the key side
+        k.kv_bf16 = 1; k.B = B; k.Tk = S;
+        k.split_ws = sk.p; k.split_ws_elems = sk.elems;
+        k.ctx = ctx_video;
+        attn_module_build_kv(ctx, b.attn2, k, &m->attn_ws, t.k_v, t.vt_v);
+        k.ctx = ctx_audio;
+        attn_module_build_kv(ctx, b.audio_attn2, k, &m->attn_ws, t.k_a, t.vt_a);
+    }
+    c.builds++;
+}
 
 void dual_forward(ltx_ctx* ctx, DualStack* m, const DualForwardArgs& a) {
     // every check comes before the first launch and before any allocation
     const int L = m->L, Dv = m->Dv, Da = m->Da, B = a.B, S = a.S, Ta = a.T_a;
     if (B < 1 || B > 8 || a.F < 1 || a.H < 1 || a.W < 1 || Ta < 1 || S < 1 || Ta > (1 << 20) || S > (1 << 20) || (long)a.F * a.H * a.W > (1 << 20))
         LTX_THROW(LTXS_INVALID_CONFIGURATION, "dual blocks forward: bad shapes B=%d (1 .. 8) F=%d H=%d W=%d T_a=%d S=%d", B, a.F, a.H, a.W, Ta, S);
-    if (!a.x_video || !a.x_audio || !a.ctx_video || !a.ctx_audio || !a.temb_video || !a.temb_audio || !a.cross_video_ss || !a.cross_audio_ss)
+    const DualTextCache* tc = a.text_cache;
+    if (!a.x_video || !a.x_audio || (!tc && (!a.ctx_video || !a.ctx_audio)) || !a.temb_video || !a.temb_audio || !a.cross_video_ss || !a.cross_audio_ss)
         LTX_THROW(LTXS_INVALID_CONFIGURATION, "dual blocks forward: null stream, context or modulation pointer");
+    if (tc && (tc->B != B || tc->S != S || !tc->buf.p))
+        LTX_THROW(LTXS_INVALID_CONFIGURATION, "dual blocks forward: the text cache holds B=%d S=%d, the call has B=%d S=%d", tc->B, tc->S, B, S);
     if (a.phase_mask > 0xffu) LTX_THROW(LTXS_INVALID_CONFIGURATION, "dual blocks forward: phase_mask 0x%x has bits beyond the eight phases", a.phase_mask);
     const unsigned phases = a.phase_mask ? a.phase_mask : 0xffu;
     auto on = [&](int p) { return (phases >> (p - 1)) & 1u; };
@@ -352,8 +394,10 @@ void dual_forward(ltx_ctx* ctx, DualStack* m, const DualForwardArgs& a) {
     const long mv_bs = (long)L * 6 * Dv, ma_bs = (long)L * 6 * Da, cv_bs = (long)L * 5 * Dv, ca_bs = (long)L * 5 * Da;
 
     auto core = [&](AttnModule* mod, AttnVtSlot* vt, const bf16_t* xq, const bf16_t* cx, int kvb, int Tq, int Tk, const float* qc, const float* qs,
-                    const float* kc, const float* ks, const float* bias, float* x, const float* gate, long gbs) {
+                    const float* kc, const float* ks, const float* bias, float* x, const float* gate, long gbs, const bf16_t* ck = nullptr,
+                    const bf16_t* cvt = nullptr) {
         AttnCoreArgs c;
+        c.cached_k = ck; c.cached_vt = cvt;
         c.xq = xq; c.ctx = cx; c.kv_bf16 = kvb;
         c.B = B; c.Tq = Tq; c.Tk = Tk;
         c.q_cos = qc; c.q_sin = qs; c.k_cos = kc; c.k_sin = ks;
@@ -373,6 +417,7 @@ void dual_forward(ltx_ctx* ctx, DualStack* m, const DualForwardArgs& a) {
 
     for (int l = 0; l < L; ++l) {
         DualBlock& b = m->blocks[l];
+        const TextCacheSlices tcs = tc ? text_cache_slices(*tc, l, Dv, Da) : TextCacheSlices{nullptr, nullptr, nullptr, nullptr};
         const float* mv = m->mod_v.as<float>() + (long)l * 6 * Dv;     // rows: 0 shift_msa 1 scale_msa 2 gate_msa 3 shift_mlp 4 scale_mlp 5 gate_mlp
         const float* ma = m->mod_a.as<float>() + (long)l * 6 * Da;
         const float* cv = m->mod_ca_v.as<float>() + (long)l * 5 * Dv;  // rows: 0 a2v scale 1 a2v shift 2 v2a scale 3 v2a shift 4 gate
@@ -387,11 +432,11 @@ void dual_forward(ltx_ctx* ctx, DualStack* m, const DualForwardArgs& a) {
         }
         if (on(3)) {  // video text cross-attention on norm2(x_v)
             launch_norm_mod(xv, Dv, nullptr, nullptr, 0, Tv, vn, Dv, (int)vrows, Dv, LTX_NORM_RMS, eps, 0, st);
-            core(b.attn2, &m->vt[2], vn, a.ctx_video, 1, Tv, S, nullptr, nullptr, nullptr, nullptr, bias_v, xv, nullptr, 0);
+            core(b.attn2, &m->vt[2], vn, a.ctx_video, 1, Tv, S, nullptr, nullptr, nullptr, nullptr, bias_v, xv, nullptr, 0, tcs.k_v, tcs.vt_v);
         }
         if (on(4)) {  // audio text cross-attention on audio_norm2(x_a)
             launch_norm_mod(xa, Da, nullptr, nullptr, 0, Ta, an, Da, (int)arows, Da, LTX_NORM_RMS, eps, 0, st);
-            core(b.audio_attn2, &m->vt[3], an, a.ctx_audio, 1, Ta, S, nullptr, nullptr, nullptr, nullptr, bias_a, xa, nullptr, 0);
+            core(b.audio_attn2, &m->vt[3], an, a.ctx_audio, 1, Ta, S, nullptr, nullptr, nullptr, nullptr, bias_a, xa, nullptr, 0, tcs.k_a, tcs.vt_a);
         }
         if (on(5) || on(6)) {
             // normVCA / normACA once, before either update; vn / an: the a2v operands, vn2 / an2: the v2a operands

@@ -2,7 +2,7 @@
 // loadable stack of L blocks with a forward of its own. It takes what LTX2Transformer.callAsFunction hands its blocks - the two
 // residual streams, the two text contexts, the adaLN rows of both streams and the cross-modal scale-shift rows - and returns both
 // streams. The embedders that produce those rows (audio_adaln_single, av_ca_*), the patchify / output heads and the caption projections
-// are dual_model.h, which owns a DualStack and calls dual_forward; the joint denoise loop and the CLI's --audio path are not built.
+// are dual_model.h, which owns a DualStack and calls dual_forward; the joint loop is dual_denoise.h; the CLI's --audio path is not built.
 //
 // Modulation inputs are ONE ROW PER BATCH ELEMENT: temb_v [B][6][Dv], temb_a [B][6][Da], cross_video_ss [B][5][Dv], cross_audio_ss
 // [B][5][Da]. The reference's per-token form (image-to-video, LTX2Transformer.swift:285-312) is not implemented, here or in
@@ -30,7 +30,8 @@
 //   2. q and k leave their projections in f32, are normed and rotated in f32 and rounded to bf16 once; q carries the folded softmax
 //      scale (1/sqrt(head dim)) log2(e) in that one rounding.
 //   3. The text contexts are bf16: k is rounded to bf16 after its projection and again after the norm (oracle.attention(kv_bf16=True)).
-//      Text-context K / V^T are computed per forward, per block (caching them across steps belongs with the joint loop).
+//      Text-context K / V^T are computed per forward, per block, unless the caller hands in a DualTextCache (below): the same
+//      launches run once per prompt by dual_prepare_text, the same bits.
 //   4. v is rounded to bf16 by the projection's transposed store; P is rounded to bf16 for the PV product; attention output is bf16.
 //   5. The FFN's hidden activation (GELU-tanh) is rounded to bf16, as the DiT rounds it.
 //   6. to_out / FFN-down accumulate in f32 and add gate * (acc + bias) to the f32 stream in the GEMM's epilogue. The streams stay f32.
@@ -78,6 +79,17 @@ struct DualBlock {
     LinearW ff1, ff2, aff1, aff2;
 };
 
+// K (normed) and V^T of the two text cross-attentions of every block, for contexts that do not change between forwards (one prompt):
+// ONE allocation, per block [K attn2 [B][S][Dv]] [V^T attn2 [B][Dv][Spad]] [K audio_attn2 [B][S][Da]] [V^T audio_attn2 [B][Da][Spad]],
+// Spad = ceil64(S), L * B * (S + Spad) * (Dv + Da) * 2 bytes (2.4 GB at L 48, B 2, S 1024). The pad columns of V^T are zeroed when
+// the layout changes. dual_prepare_text fills it; B == 0: empty.
+struct DualTextCache {
+    DevBuf buf;
+    int B = 0, S = 0, Spad = 0;
+    long bytes = 0;   // of the layout held (buf may be larger)
+    long builds = 0;  // fills since the stack was created
+};
+
 struct DualStack {
     DualBlockConfig cfg;
     int L = 0, Dv = 0, Da = 0;
@@ -100,6 +112,7 @@ struct DualStack {
     DevBuf ws_vn, ws_vn2, ws_an, ws_an2, ws_ffh, ws_splitk;
     DevBuf mod_v, mod_a, mod_ca_v, mod_ca_a;  // [B][L][6|5][D] f32
     DevBuf zero_bias;  // [B][S] f32 zeros: what a null key bias reads (allocated zeroed, never written)
+    DualTextCache text_cache;
     bool use_norm_mod2 = true;  // false: phases 5 / 6 run the four launch_norm_mod passes (bit-equal; tools/bench_dual_block.py A/B)
 
     ~DualStack();
@@ -127,5 +140,11 @@ struct DualForwardArgs {
     const float* cross_audio_ss = nullptr; // [B][5][Da]
     int B = 1, F = 0, H = 0, W = 0, T_a = 0, S = 0;
     unsigned phase_mask = 0;  // measurement seam (tools/bench_dual_block.py): bit p-1 set = run phase p; 0 = all eight
+    // optional: phases 3 and 4 read K / V^T from here and skip their k GEMM, k norm and V^T GEMMs; ctx_video / ctx_audio are then not
+    // read (they may be null). Its (B, S) must be the call's, or the forward is refused before the first launch.
+    const DualTextCache* text_cache = nullptr;
 };
 void dual_forward(ltx_ctx* ctx, DualStack* m, const DualForwardArgs& a);
+// Fills m->text_cache from the two projected contexts (ctx_video [B][S][video_context_dim], ctx_audio [B][S][audio_context_dim], bf16):
+// per block the launches phases 3 and 4 would run for K and V^T (attn_module_build_kv). Every check comes before the first launch.
+void dual_prepare_text(ltx_ctx* ctx, DualStack* m, const bf16_t* ctx_video, const bf16_t* ctx_audio, int B, int S);

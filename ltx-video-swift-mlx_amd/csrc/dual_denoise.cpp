@@ -1,0 +1,126 @@
+// dual_denoise.cpp - see dual_denoise.h.
+#include "dual_denoise.h"
+
+#include <math.h>
+
+#include "dual_model.h"
+#include "elementwise.h"
+
+namespace {
+constexpr int kAudioChannels = 8, kAudioMelBins = 16;  // audioLatentChannels x audioLatentMelBins = the 128 audio token channels
+
+// (8, T_a, 16) <-> (T_a, 128): token t holds channel c's 16 bins at columns 16 c .. (packAudioLatents / unpackAudioLatents)
+void pack_audio(float* planes, float* tokens, int Ta, bool unpack, hipStream_t st) {
+    const size_t row = kAudioMelBins * 4, tok_row = (size_t)kAudioChannels * kAudioMelBins * 4;
+    for (int c = 0; c < kAudioChannels; ++c) {
+        float* pl = planes + (size_t)c * Ta * kAudioMelBins;
+        float* tk = tokens + c * kAudioMelBins;
+        if (unpack)
+            HIP_CHECK(hipMemcpy2DAsync(pl, row, tk, tok_row, row, Ta, hipMemcpyDeviceToDevice, st));
+        else
+            HIP_CHECK(hipMemcpy2DAsync(tk, tok_row, pl, row, row, Ta, hipMemcpyDeviceToDevice, st));
+    }
+}
+}  // namespace
+
+void dual_denoise_run(ltx_ctx* ctx, const DualDenoiseParams& p) {
+    DualModel* m = ctx->dual_model;
+    if (!m) LTX_THROW(LTXS_MODEL_NOT_LOADED, "Model not loaded: dual transformer model not loaded");
+    // every check comes before the first launch, the forward's and the step's included
+    LTX_REQUIRE(p.n_sigmas >= 2 && p.sigmas, "dual denoise: %d sigmas (at least 2)", p.n_sigmas);
+    LTX_REQUIRE(p.F >= 1 && p.H >= 1 && p.W >= 1 && p.T_a >= 1 && p.S >= 1 && p.T_a <= (1 << 20) && p.S <= (1 << 20) && (long)p.F * p.H * p.W <= (1 << 20),
+                "dual denoise: bad shapes F=%d H=%d W=%d T_a=%d S=%d", p.F, p.H, p.W, p.T_a, p.S);
+    LTX_REQUIRE(p.video_latent && p.audio_latent && p.video_context, "dual denoise: null latent or context pointer");
+    const bool use_cfg = p.cfg_scale > 1.0f;
+    LTX_REQUIRE(!(p.guidance_rescale > 0.f) || use_cfg, "dual denoise: guidance_rescale %g needs cfg_scale > 1 (got %g)", (double)p.guidance_rescale,
+                (double)p.cfg_scale);
+    const int steps = p.n_sigmas - 1;
+    for (int i = 0; i < steps; ++i) LTX_REQUIRE(p.sigmas[i] > 0.f, "dual denoise: sigmas[%d] = %g must be positive", i, (double)p.sigmas[i]);
+    const int C = m->cfg.in_channels, Ca = kAudioChannels * kAudioMelBins;
+    LTX_REQUIRE(m->cfg.out_channels == C && C % 4 == 0, "dual denoise: video in / out channels differ");
+    LTX_REQUIRE(m->cfg.audio_in_channels == Ca && m->cfg.audio_out_channels == Ca, "dual denoise: the audio stream must have %d channels", Ca);
+    const int Tv = p.F * p.H * p.W, Ta = p.T_a, B = use_cfg ? 2 : 1;
+    const long nv = (long)Tv * C, na = (long)Ta * Ca;
+    hipStream_t st = ctx->stream;
+
+    // one allocation, carved: [xv][xa][vel_v B][vel_a B][guided v][tok_v B][tok_a B][ts 4][rescale stats 4][step stats 8 steps]
+    size_t off = 0;
+    auto carve = [&](size_t bytes) {
+        const size_t at = off;
+        off = (off + bytes + 255) & ~(size_t)255;
+        return at;
+    };
+    const size_t o_xv = carve(nv * 4), o_xa = carve(na * 4), o_vv = carve(B * nv * 4), o_va = carve(B * na * 4), o_vg = carve(nv * 4),
+                 o_tv = carve(B * nv * 2), o_ta = carve(B * na * 2), o_ts = carve(16), o_rs = carve(16), o_ss = carve((size_t)steps * 32);
+    ctx->dual_dn.ensure(off);
+    char* base = (char*)ctx->dual_dn.p;
+    float *xv = (float*)(base + o_xv), *xa = (float*)(base + o_xa), *vel_v = (float*)(base + o_vv), *vel_a = (float*)(base + o_va),
+          *vg = (float*)(base + o_vg), *ts = (float*)(base + o_ts), *rs = (float*)(base + o_rs), *ss = (float*)(base + o_ss);
+    bf16_t *tok_v = (bf16_t*)(base + o_tv), *tok_a = (bf16_t*)(base + o_ta);
+
+    const bf16_t* actx = p.audio_context ? p.audio_context : p.video_context;  // audioEncoding ?? videoEncoding
+
+    // entry: token layout, first tokens, the text side
+    launch_unpatchify_f32(p.video_latent, xv, 1, Tv, C, st);  // [C][Tv] -> [Tv][C]: the transpose with the roles of C and T exchanged
+    pack_audio(p.audio_latent, xa, Ta, false, st);
+    launch_cast_f32_bf16(xv, tok_v, nv, st);
+    launch_cast_f32_bf16(xa, tok_a, na, st);
+    if (B == 2) {
+        HIP_CHECK(hipMemcpyAsync(tok_v + nv, tok_v, (size_t)nv * 2, hipMemcpyDeviceToDevice, st));
+        HIP_CHECK(hipMemcpyAsync(tok_a + na, tok_a, (size_t)na * 2, hipMemcpyDeviceToDevice, st));
+    }
+    if (p.text_cache) dual_model_prepare_text(ctx, m, p.video_context, actx, p.mask, p.mask, B, p.S);
+
+    for (int step = 0; step < steps; ++step) {
+        const float sigma = p.sigmas[step], sigma_next = p.sigmas[step + 1];
+        if (p.progress) p.progress(step, steps, sigma, p.user);  // before the forward (:1285-1287)
+        launch_fill_const_f32(ts, 4, sigma, st);                 // [video B][audio B]
+        DualModelForwardArgs f;
+        f.video_latent = tok_v; f.audio_latent = tok_a;
+        f.video_timesteps = ts; f.audio_timesteps = ts + 2;
+        f.B = B; f.F = p.F; f.H = p.H; f.W = p.W; f.T_a = Ta; f.S = p.S;
+        f.video_velocity = vel_v; f.audio_velocity = vel_a;
+        f.text_cache = p.text_cache;
+        if (!p.text_cache) {
+            f.video_context = p.video_context; f.audio_context = actx;
+            f.video_mask = p.mask; f.audio_mask = p.mask;  // one mask, both streams (:1322-1323)
+        }
+        dual_model_forward(ctx, m, f);
+
+        // batch order [negative, positive]
+        DualStepJob jv, ja;
+        jv.latent = xv; jv.v_cond = vel_v + (B - 1) * nv; jv.v_uncond = use_cfg ? vel_v : nullptr; jv.cfg_scale = p.cfg_scale;
+        jv.form = 0; jv.tokens = tok_v; jv.copies = B; jv.n = nv;
+        ja.latent = xa; ja.v_cond = vel_a + (B - 1) * na; ja.v_uncond = use_cfg ? vel_a : nullptr; ja.cfg_scale = p.cfg_scale;
+        ja.form = 1; ja.tokens = tok_a; ja.copies = B; ja.n = na;
+        if (p.guidance_rescale > 0.f) {  // video only (:1352-1359); the step then takes the guided velocity as it is
+            launch_cfg_combine(jv.v_uncond, jv.v_cond, p.cfg_scale, vg, nv, st);
+            launch_mean_var(vg, nv, 1, rs, st);
+            launch_mean_var(jv.v_cond, nv, 1, rs + 2, st);
+            launch_guidance_rescale(vg, rs, rs + 2, p.guidance_rescale, nv, 1, st);
+            jv.v_cond = vg;
+            jv.v_uncond = nullptr;
+        }
+        if (p.step_stats) {  // the guided velocities, in place of the conditional ones
+            jv.v_out = (float*)jv.v_cond;
+            ja.v_out = (float*)ja.v_cond;
+        }
+        launch_dual_step(jv, ja, sigma, sigma_next, st);
+        if (p.step_stats) {  // the diagnostics of :1407-1413
+            float* s8 = ss + 8 * step;
+            launch_mean_var(jv.v_out, nv, 1, s8, st);
+            launch_mean_var(xv, nv, 1, s8 + 2, st);
+            launch_mean_var(ja.v_out, na, 1, s8 + 4, st);
+            launch_mean_var(xa, na, 1, s8 + 6, st);
+        }
+    }
+
+    // exit: back to the caller's layouts
+    launch_unpatchify_f32(xv, p.video_latent, 1, C, Tv, st);
+    pack_audio(p.audio_latent, xa, Ta, true, st);
+    if (p.step_stats) {
+        HIP_CHECK(hipMemcpyAsync(p.step_stats, ss, (size_t)steps * 32, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        for (int i = 0; i < 4 * steps; ++i) p.step_stats[2 * i + 1] = sqrtf(p.step_stats[2 * i + 1]);  // variance -> standard deviation
+    }
+}

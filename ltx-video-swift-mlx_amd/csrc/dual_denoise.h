@@ -1,0 +1,36 @@
+// dual_denoise.h - the denoise loop of generateVideoWithAudio (LTXPipeline.swift:1276-1417), text-to-video+audio, around the dual model
+// (dual_model.h). One schedule for both streams. The graph:
+//   entry     video [C][Tv] f32 -> token layout [Tv][C] (launch_unpatchify_f32 with the roles of C and T exchanged); audio (8, T_a, 16) ->
+//             (T_a, 128) (packAudioLatents, :540-544: eight strided 2-D copies); two launch_cast_f32_bf16 write the first tokens;
+//             dual_model_prepare_text once (text_cache)
+//   per step  progress callback; both timestep vectors = sigma; ONE dual_model_forward (B = 2 on duplicated tokens and contexts
+//             [negative, positive] with CFG, else B = 1); with guidance_rescale > 0 launch_cfg_combine + 2 x launch_mean_var +
+//             launch_guidance_rescale on the VIDEO velocity (:1352-1359); ONE launch_dual_step (video: the scheduler's form, audio: the
+//             plain form) = CFG, both Euler steps and the next forward's tokens; with step_stats four launch_mean_var
+//   exit      the inverse transposes into the caller's buffers
+// Both latents stay in token layout for the whole loop, which is what makes the step elementwise: the per-step patchify, unpatchify,
+// cast and copy passes of denoise_run (pipeline.cpp) have no counterpart here. No new rounding point: the step is f32, every operation
+// rounded on its own as the reference's array ops are (elementwise.h, DualStepJob); the tokens are the one bf16 rounding of :1306-1307.
+// Every check comes before the first launch: a refused call leaves both latents untouched. Image-to-video (per-token timesteps), STG,
+// GE, the two-stage path and sharding are not implemented.
+#pragma once
+#include "../../include/ltxhip.h"
+#include "runtime.h"
+
+struct DualDenoiseParams {
+    int F = 0, H = 0, W = 0, T_a = 0, S = 0;
+    float* video_latent = nullptr;          // device [1][C][F][H][W] f32, in / out, scaled by sigmas[0]
+    float* audio_latent = nullptr;          // device [1][8][T_a][16] f32, in / out
+    const float* sigmas = nullptr;          // host [n_sigmas]
+    int n_sigmas = 0;
+    const bf16_t* video_context = nullptr;  // device [nb][S][caption_channels] bf16, nb = 2 ([negative, positive]) iff cfg_scale > 1
+    const bf16_t* audio_context = nullptr;  // the same shape; null = the video context
+    const int32_t* mask = nullptr;          // device [nb][S] or null; both streams
+    float cfg_scale = 1.0f;
+    float guidance_rescale = 0.0f;          // video velocity only
+    int text_cache = 1;
+    float* step_stats = nullptr;            // host [n_sigmas - 1][8] or null: mean, std of video velocity, video latent, audio velocity, audio latent
+    ltx_progress_cb progress = nullptr;
+    void* user = nullptr;
+};
+void dual_denoise_run(ltx_ctx* ctx, const DualDenoiseParams& p);

@@ -83,6 +83,21 @@ void embed_launches(ltx_ctx* ctx, DualModel* m, const float* video_ts, const flo
             launch_gemv_f32(s[j].a, s[j].lda, s[j].W, s[j].ldw, s[j].bias, s[j].out, s[j].ldo, B, s[j].N, s[j].K, s[j].in_act, st);
 }
 
+// PixArtAlphaTextProjection of one context (LTX2Transformer.swift:275,282): Linear, GELU-tanh, Linear; the hidden activation goes
+// through ws_cap_h (dual_model.h, rounding point 3)
+void caption_launches(DualModel* m, const bf16_t* context, const LinearW& l1, const LinearW& l2, int D, long crows, bf16_t* out, hipStream_t st,
+                      const SplitWs& sk) {
+    GemmEpilogue e1;
+    e1.out_bf16 = m->ws_cap_h.as<bf16_t>();
+    e1.ld_bf16 = D;
+    e1.act = LTX_ACT_GELU_TANH;
+    gemm_linear(context, m->cfg.caption_channels, l1, (int)crows, e1, st, sk);
+    GemmEpilogue e2;
+    e2.out_bf16 = out;
+    e2.ld_bf16 = D;
+    gemm_linear(m->ws_cap_h.as<bf16_t>(), D, l2, (int)crows, e2, st, sk);
+}
+
 }  // namespace
 
 DualModel::~DualModel() {
@@ -248,9 +263,14 @@ void dual_model_forward(ltx_ctx* ctx, DualModel* m, const DualModelForwardArgs& 
     const int Dv = m->Dv, Da = m->Da, B = a.B, S = a.S, Ta = a.T_a;
     if (B < 1 || B > 8 || a.F < 1 || a.H < 1 || a.W < 1 || Ta < 1 || S < 1 || Ta > (1 << 20) || S > (1 << 20) || (long)a.F * a.H * a.W > (1 << 20))
         LTX_THROW(LTXS_INVALID_CONFIGURATION, "dual model forward: bad shapes B=%d (1 .. 8) F=%d H=%d W=%d T_a=%d S=%d", B, a.F, a.H, a.W, Ta, S);
-    if (!a.video_latent || !a.audio_latent || !a.video_context || !a.audio_context || !a.video_timesteps || !a.audio_timesteps ||
+    const bool cached = a.text_cache != 0;
+    if (!a.video_latent || !a.audio_latent || (!cached && (!a.video_context || !a.audio_context)) || !a.video_timesteps || !a.audio_timesteps ||
         !a.video_velocity || !a.audio_velocity)
         LTX_THROW(LTXS_INVALID_CONFIGURATION, "dual model forward: null latent, context, timestep or velocity pointer");
+    const DualTextCache& tc = m->stack->text_cache;
+    if (cached && (tc.B != B || tc.S != S || !tc.buf.p))
+        LTX_THROW(LTXS_INVALID_CONFIGURATION, "dual model forward: text_cache needs dual_model_prepare_text at B=%d S=%d (the cache holds B=%d S=%d)", B,
+                  S, tc.B, tc.S);
     const int Tv = a.F * a.H * a.W;
     const long vrows = (long)B * Tv, arows = (long)B * Ta, crows = (long)B * S;
     const float eps = m->cfg.blocks.norm_eps;
@@ -259,11 +279,13 @@ void dual_model_forward(ltx_ctx* ctx, DualModel* m, const DualModelForwardArgs& 
     // scratch: grows to the largest shape seen
     m->ws_xv.ensure((size_t)vrows * Dv * 4);
     m->ws_xa.ensure((size_t)arows * Da * 4);
-    m->ws_ctx_v.ensure((size_t)crows * Dv * 2);
-    m->ws_ctx_a.ensure((size_t)crows * Da * 2);
-    m->ws_cap_h.ensure((size_t)crows * std::max(Dv, Da) * 2);  // shared by both caption projections; audio_dim may exceed video_dim
-    if (a.video_mask) m->ws_bias_v.ensure((size_t)crows * 4);
-    if (a.audio_mask) m->ws_bias_a.ensure((size_t)crows * 4);
+    if (!cached) {
+        m->ws_ctx_v.ensure((size_t)crows * Dv * 2);
+        m->ws_ctx_a.ensure((size_t)crows * Da * 2);
+        m->ws_cap_h.ensure((size_t)crows * std::max(Dv, Da) * 2);  // shared by both caption projections; audio_dim may exceed video_dim
+        if (a.video_mask) m->ws_bias_v.ensure((size_t)crows * 4);
+        if (a.audio_mask) m->ws_bias_a.ensure((size_t)crows * 4);
+    }
     ensure_embed_scratch(m, B);
     m->ws_temb_v.ensure((size_t)B * 6 * Dv * 4);
     m->ws_temb_a.ensure((size_t)B * 6 * Da * 4);
@@ -297,30 +319,27 @@ void dual_model_forward(ltx_ctx* ctx, DualModel* m, const DualModelForwardArgs& 
     eo.embts_v = m->ws_h2.as<float>() + stage_offset(m, 0, B);
     eo.embts_a = m->ws_h2.as<float>() + stage_offset(m, 1, B);
     embed_launches(ctx, m, a.video_timesteps, a.audio_timesteps, B, a.ungrouped != 0, eo);
-    // 3. text (:275,282,315-316)
-    auto caption = [&](const bf16_t* context, const LinearW& l1, const LinearW& l2, int D, bf16_t* out) {
-        GemmEpilogue e1;
-        e1.out_bf16 = m->ws_cap_h.as<bf16_t>();
-        e1.ld_bf16 = D;
-        e1.act = LTX_ACT_GELU_TANH;
-        gemm_linear(context, m->cfg.caption_channels, l1, (int)crows, e1, st, sk);
-        GemmEpilogue e2;
-        e2.out_bf16 = out;
-        e2.ld_bf16 = D;
-        gemm_linear(m->ws_cap_h.as<bf16_t>(), D, l2, (int)crows, e2, st, sk);
-    };
-    caption(a.video_context, m->cap1, m->cap2, Dv, m->ws_ctx_v.as<bf16_t>());
-    caption(a.audio_context, m->acap1, m->acap2, Da, m->ws_ctx_a.as<bf16_t>());
-    if (a.video_mask) launch_mask_to_bias(a.video_mask, m->ws_bias_v.as<float>(), crows, st);
-    if (a.audio_mask) launch_mask_to_bias(a.audio_mask, m->ws_bias_a.as<float>(), crows, st);
+    // 3. text (:275,282,315-316); a cached forward reads what dual_model_prepare_text left
+    if (!cached) {
+        caption_launches(m, a.video_context, m->cap1, m->cap2, Dv, crows, m->ws_ctx_v.as<bf16_t>(), st, sk);
+        caption_launches(m, a.audio_context, m->acap1, m->acap2, Da, crows, m->ws_ctx_a.as<bf16_t>(), st, sk);
+        if (a.video_mask) launch_mask_to_bias(a.video_mask, m->ws_bias_v.as<float>(), crows, st);
+        if (a.audio_mask) launch_mask_to_bias(a.audio_mask, m->ws_bias_a.as<float>(), crows, st);
+    }
     // 4. the blocks (:361-372)
     DualForwardArgs f;
     f.x_video = xv;
     f.x_audio = xa;
-    f.ctx_video = m->ws_ctx_v.as<bf16_t>();
-    f.ctx_audio = m->ws_ctx_a.as<bf16_t>();
-    f.bias_video = a.video_mask ? m->ws_bias_v.as<float>() : nullptr;
-    f.bias_audio = a.audio_mask ? m->ws_bias_a.as<float>() : nullptr;
+    if (cached) {
+        f.text_cache = &tc;
+        f.bias_video = m->tc_has_bias_v ? m->tc_bias_v.as<float>() : nullptr;
+        f.bias_audio = m->tc_has_bias_a ? m->tc_bias_a.as<float>() : nullptr;
+    } else {
+        f.ctx_video = m->ws_ctx_v.as<bf16_t>();
+        f.ctx_audio = m->ws_ctx_a.as<bf16_t>();
+        f.bias_video = a.video_mask ? m->ws_bias_v.as<float>() : nullptr;
+        f.bias_audio = a.audio_mask ? m->ws_bias_a.as<float>() : nullptr;
+    }
     f.temb_video = eo.temb_v;
     f.temb_audio = eo.temb_a;
     f.cross_video_ss = eo.cross_v;
@@ -339,4 +358,28 @@ void dual_model_forward(ltx_ctx* ctx, DualModel* m, const DualModelForwardArgs& 
     };
     head(xv, Dv, Tv, vrows, m->sst_out_v, eo.embts_v, m->ws_modout_v.as<float>(), m->proj_out, a.video_velocity);
     head(xa, Da, Ta, arows, m->sst_out_a, eo.embts_a, m->ws_modout_a.as<float>(), m->audio_proj_out, a.audio_velocity);
+}
+
+void dual_model_prepare_text(ltx_ctx* ctx, DualModel* m, const bf16_t* video_context, const bf16_t* audio_context, const int32_t* video_mask,
+                             const int32_t* audio_mask, int B, int S) {
+    // the checks of dual_prepare_text, before any launch or allocation
+    if (B < 1 || B > 8 || S < 1 || S > (1 << 20)) LTX_THROW(LTXS_INVALID_CONFIGURATION, "dual model prepare text: bad shapes B=%d (1 .. 8) S=%d", B, S);
+    if (!video_context || !audio_context) LTX_THROW(LTXS_INVALID_CONFIGURATION, "dual model prepare text: null context pointer");
+    const int Dv = m->Dv, Da = m->Da;
+    const long crows = (long)B * S;
+    hipStream_t st = ctx->stream;
+    m->tc_ctx_v.ensure((size_t)crows * Dv * 2);
+    m->tc_ctx_a.ensure((size_t)crows * Da * 2);
+    m->ws_cap_h.ensure((size_t)crows * std::max(Dv, Da) * 2);
+    if (video_mask) m->tc_bias_v.ensure((size_t)crows * 4);
+    if (audio_mask) m->tc_bias_a.ensure((size_t)crows * 4);
+    m->ws_splitk.ensure((size_t)8 << 22);
+    const SplitWs sk{m->ws_splitk.as<float>(), (long)(m->ws_splitk.bytes / 4)};
+    caption_launches(m, video_context, m->cap1, m->cap2, Dv, crows, m->tc_ctx_v.as<bf16_t>(), st, sk);
+    caption_launches(m, audio_context, m->acap1, m->acap2, Da, crows, m->tc_ctx_a.as<bf16_t>(), st, sk);
+    if (video_mask) launch_mask_to_bias(video_mask, m->tc_bias_v.as<float>(), crows, st);
+    if (audio_mask) launch_mask_to_bias(audio_mask, m->tc_bias_a.as<float>(), crows, st);
+    m->tc_has_bias_v = video_mask != nullptr;
+    m->tc_has_bias_a = audio_mask != nullptr;
+    dual_prepare_text(ctx, m->stack, m->tc_ctx_v.as<bf16_t>(), m->tc_ctx_a.as<bf16_t>(), B, S);
 }

@@ -4,7 +4,11 @@
 // parameters of LTX2Transformer.swift:28-48: patchify_proj / audio_patchify_proj, the six AdaLayerNormSingle embedders (each
 // emb.linear_1, emb.linear_2, linear), caption_projection / audio_caption_projection (linear_1, linear_2), scale_shift_table [2][Dv] /
 // audio_scale_shift_table [2][Da], proj_out / audio_proj_out. norm_out / audio_norm_out are LayerNorm(affine: false): no weight.
-// The joint denoise loop, a text K / V^T cache across steps, per-token timesteps and the CLI's --audio path are not here.
+// The joint denoise loop is dual_denoise.h; per-token timesteps and the CLI's --audio path are not here.
+//
+// The text side of a forward (step 3 below and the K / V^T of the blocks' text cross-attentions) does not change within a prompt:
+// dual_model_prepare_text runs it once into model-owned buffers and the stack's DualTextCache, and a forward with text_cache set reads
+// those instead. Same launches, same operands, same bits as the forward that recomputes them.
 //
 // Timesteps are ONE VALUE PER BATCH ELEMENT per stream (video_timesteps [B], audio_timesteps [B], sigma unscaled), so every modulation
 // row is one row per batch element, as dual_block.h takes them. The reference's per-token form (image-to-video,
@@ -83,6 +87,10 @@ struct DualModel {
     DevBuf ws_modout_v, ws_modout_a;                  // [B][2][D]
     DevBuf ws_xn;                                     // head operand (bf16)
     DevBuf ws_splitk;
+    // what dual_model_prepare_text keeps for the cached forwards (never the per-forward scratch above): the projected contexts it
+    // built the stack's K / V^T from, and the mask biases
+    DevBuf tc_ctx_v, tc_ctx_a, tc_bias_v, tc_bias_a;
+    bool tc_has_bias_v = false, tc_has_bias_a = false;
 
     ~DualModel();
 };
@@ -125,5 +133,10 @@ struct DualModelForwardArgs {
     float* audio_velocity = nullptr;        // [B][T_a][audio_out_channels] f32
     int ungrouped = 0;                      // non-zero: 18 launch_gemv_f32 launches instead of the three grouped ones (bit-equal); the
                                             // grouped path is the default because it measured faster (profiles/dual_model_bench.txt)
+    int text_cache = 0;                     // non-zero: the text side comes from dual_model_prepare_text; contexts and masks are not read
 };
 void dual_model_forward(ltx_ctx* ctx, DualModel* m, const DualModelForwardArgs& a);
+// Both caption projections and both launch_mask_to_bias passes (a null mask is a null bias) into model-owned buffers, then
+// dual_prepare_text on the owned stack. Contexts [B][S][caption_channels] bf16, masks [B][S] int32 or null; device pointers.
+void dual_model_prepare_text(ltx_ctx* ctx, DualModel* m, const bf16_t* video_context, const bf16_t* audio_context, const int32_t* video_mask,
+                             const int32_t* audio_mask, int B, int S);

@@ -82,6 +82,28 @@ void launch_euler_step(float* latent, const float* velocity, float sigma, float 
 void launch_set_frame0(float* latent, const float* cond, const float* noise, float scale, float sigma2, int C, int F, int HW,
                        hipStream_t stream);
 void launch_i2v_rowmap(int32_t* row_map, int B, int T, int first, int G, hipStream_t stream);
+// Everything between two forwards of the joint video + audio loop (generateVideoWithAudio, LTXPipeline.swift:1276-1417) in ONE launch:
+// CFG, the Euler step and the next forward's bf16 operand, for both streams. Two jobs share one grid (video, audio; n == 0: the job is
+// empty). Per element, every operation rounded on its own as the reference's separate array ops round (no contraction, correctly
+// rounded division), so the f32 outputs are bit-equal to a numpy float32 replay:
+//   v  = v_uncond ? v_cond + (cfg_scale - 1) * (v_cond - v_uncond) : v_cond                    (LatentUtils.swift:131-141)
+//   form 0 (the scheduler's, LTXScheduler.swift:305-327): den = x - sigma * v; x' = sigma_next > 0 ? den + sigma_next * (x - den) / sigma : den
+//   form 1 (the audio line, LTXPipeline.swift:1402):      x' = x + (sigma_next - sigma) * v
+//   tokens[c] = bf16(x'), c < copies (round to nearest even, :1306-1307): a B = 2 CFG forward reads both copies, no copy launch
+// The two forms are NOT one formula: they differ in about half of the f32 results. Latents stay in TOKEN layout [T][C], which is what
+// makes the step elementwise. n % 4 == 0, copies 1 .. 2, form 0 .. 1, sigma > 0; every check comes before the launch.
+struct DualStepJob {
+    float* latent = nullptr;          // [n] f32, in / out
+    const float* v_cond = nullptr;    // [n] f32
+    const float* v_uncond = nullptr;  // [n] f32 or null (no CFG)
+    float cfg_scale = 1.0f;
+    int form = 0;
+    bf16_t* tokens = nullptr;         // [copies][n] bf16
+    int copies = 1;
+    float* v_out = nullptr;           // [n] f32 or null: the guided velocity; may alias v_cond
+    long n = 0;
+};
+void launch_dual_step(const DualStepJob& video, const DualStepJob& audio, float sigma, float sigma_next, hipStream_t stream);
 // CFG combine v = cond + (scale-1)*(cond-uncond) (LatentUtils.swift:131-141)
 void launch_cfg_combine(const float* uncond, const float* cond, float scale, float* out, long n, hipStream_t stream);
 // out = a + s*(a - b)   (STG: LTXPipeline.swift:920) ; out = g*(a-b)+b (GE: :924-927) share one kernel

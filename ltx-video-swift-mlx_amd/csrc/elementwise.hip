@@ -5,6 +5,8 @@
 
 #include <stdlib.h>
 
+#include <algorithm>
+
 #include "options.h"
 #include "runtime.h"
 
@@ -530,6 +532,69 @@ __global__ void euler_step_kernel(float* __restrict__ latent, const float* __res
     const float x = latent[i];
     const float den = x - sigma * vel[i];
     latent[i] = (sigma_next > 0.f) ? den + sigma_next * (x - den) / sigma : den;
+}
+// CFG + Euler step + the next forward's bf16 tokens for both streams of the joint loop (elementwise.h, DualStepJob). Workgroups
+// 0 .. wgs0-1 take job 0, the rest job 1 (uniform per workgroup); each job's workgroups stride over its own n. 16-byte loads and
+// stores of f32, 8-byte stores of bf16; no LDS. Contraction is off for the whole body and the division is the correctly rounded one:
+// every operation rounds on its own, as the reference's separate array ops do.
+__global__ __launch_bounds__(256) void dual_step_kernel(const DualStepJob j0, const DualStepJob j1, int wgs0, float sigma, float sigma_next) {
+#pragma clang fp contract(off)
+    const bool second = (int)blockIdx.x >= wgs0;
+    const int wg = second ? (int)blockIdx.x - wgs0 : (int)blockIdx.x;
+    const int nwg = second ? (int)gridDim.x - wgs0 : wgs0;
+    float* __restrict__ lat = second ? j1.latent : j0.latent;
+    const float* vc = second ? j1.v_cond : j0.v_cond;  // may alias v_out: no __restrict__
+    const float* __restrict__ vu = second ? j1.v_uncond : j0.v_uncond;
+    float* vo = second ? j1.v_out : j0.v_out;
+    bf16_t* __restrict__ tok = second ? j1.tokens : j0.tokens;
+    const float sm1 = (second ? j1.cfg_scale : j0.cfg_scale) - 1.0f;
+    const int form = second ? j1.form : j0.form;
+    const int copies = second ? j1.copies : j0.copies;
+    const long n = second ? j1.n : j0.n;
+    const float ds = sigma_next - sigma;
+    const long stride = (long)nwg * 256 * 4;
+    for (long i = ((long)wg * 256 + threadIdx.x) * 4; i < n; i += stride) {  // n % 4 == 0: whole vectors only
+        const f32x4 x = *(const f32x4*)(lat + i);
+        f32x4 v = *(const f32x4*)(vc + i);
+        if (vu) {
+            const f32x4 u = *(const f32x4*)(vu + i);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const float d = v[e] - u[e];
+                const float g = sm1 * d;
+                v[e] = v[e] + g;
+            }
+        }
+        if (vo) *(f32x4*)(vo + i) = v;
+        f32x4 y;
+        if (form == 0) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const float sv = sigma * v[e];
+                const float den = x[e] - sv;
+                if (sigma_next > 0.f) {
+                    const float back = x[e] - den;
+                    const float num = sigma_next * back;
+                    const float q = __fdiv_rn(num, sigma);
+                    y[e] = den + q;
+                } else {
+                    y[e] = den;
+                }
+            }
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const float dv = ds * v[e];
+                y[e] = x[e] + dv;
+            }
+        }
+        *(f32x4*)(lat + i) = y;
+        uint2 pk;
+        pk.x = pack_bf16x2(y[0], y[1]);
+        pk.y = pack_bf16x2(y[2], y[3]);
+        *(uint2*)(tok + i) = pk;
+        if (copies == 2) *(uint2*)(tok + n + i) = pk;
+    }
 }
 __global__ void cfg_combine_kernel(const float* __restrict__ uncond, const float* __restrict__ cond, float sm1,
                                    float* __restrict__ out, long n) {
@@ -1176,6 +1241,26 @@ void launch_i2v_rowmap(int32_t* row_map, int B, int T, int first, int G, hipStre
 }
 void launch_cfg_combine(const float* uncond, const float* cond, float scale, float* out, long n, hipStream_t stream) {
     hipLaunchKernelGGL(cfg_combine_kernel, dim3(cdiv(n, 256)), dim3(256), 0, stream, uncond, cond, scale - 1.0f, out, n);
+    HIP_CHECK(hipGetLastError());
+}
+void launch_dual_step(const DualStepJob& video, const DualStepJob& audio, float sigma, float sigma_next, hipStream_t stream) {
+    LTX_REQUIRE(sigma > 0.f, "dual_step: sigma=%g must be positive", (double)sigma);
+    long bytes = 0;
+    for (const DualStepJob* j : {&video, &audio}) {
+        LTX_REQUIRE(j->n >= 0 && j->n % 4 == 0, "dual_step: n=%ld must be a multiple of 4", j->n);
+        if (j->n == 0) continue;
+        LTX_REQUIRE(j->latent && j->v_cond && j->tokens, "dual_step: null latent, velocity or token pointer");
+        LTX_REQUIRE(j->copies >= 1 && j->copies <= 2, "dual_step: copies=%d (1 .. 2)", j->copies);
+        LTX_REQUIRE(j->form >= 0 && j->form <= 1, "dual_step: form=%d (0 .. 1)", j->form);
+        bytes += j->n * (4 + 4 + (j->v_uncond ? 4 : 0) + 4 + (j->v_out ? 4 : 0) + 2 * j->copies);
+    }
+    // per job: one workgroup per 1024 elements, at most kMaxWgs (half the CUs each; the loop strides over the rest)
+    constexpr long kMaxWgs = 128;
+    auto wgs = [=](long n) { return (int)std::min<long>(cdiv(n, 4 * 256), kMaxWgs); };
+    const int w0 = wgs(video.n), w1 = wgs(audio.n);
+    if (w0 + w1 == 0) return;
+    ProfScope prof(PROF_ELEM, (double)bytes, stream);
+    hipLaunchKernelGGL(dual_step_kernel, dim3((unsigned)(w0 + w1)), dim3(256), 0, stream, video, audio, w0, sigma, sigma_next);
     HIP_CHECK(hipGetLastError());
 }
 void launch_axpby(const float* a, const float* b, float ca, float cb, float* out, long n, hipStream_t stream) {

@@ -141,6 +141,8 @@ enum H2dSlot {
     H2D_CONN_HIDDEN = 0, H2D_CONN_MASK = 1, H2D_CONN_CONTEXT = 2, H2D_CONN_OUT_MASK = 3,
     // one input, one output: ltx_vae_encode, ltx_audio_vae_decode, ltx_vocoder_forward, ltx_audio_decode (share 0-1 with the above)
     H2D_IN = 0, H2D_OUT = 1,
+    // ltx_dual_denoise: video latent / video context / mask in ltx_denoise's slots, the audio latent and context in 0-1
+    H2D_DUAL_AUDIO_LATENT = 0, H2D_DUAL_AUDIO_CONTEXT = 1,
     H2D_COUNT = 8
 };
 
@@ -173,6 +175,7 @@ struct ltx_ctx {
     DevBuf dn_vel_slice;  // sequence-sharded loop: this rank's [T/N][C] velocity rows before the all-gather
     DevBuf i2v_cond, i2v_noise;  // staged image latent / re-noising draws of the host-pointer denoise entry
     DevBuf op_ws;  // split-K workspace of the kernel-level test hook
+    DevBuf dual_dn;  // joint video + audio loop (dual_denoise.h): token-layout latents, velocities, tokens, timesteps, statistics
 };
 
 // synthetic weights (bench / property tests): counter-based normal fill on device
