@@ -799,6 +799,14 @@ int ltx_op_gemm_q8(ltx_ctx* ctx, const uint16_t* A, long lda, const uint8_t* cod
  * (to_v of LTXAttention.swift:100-104 followed by the head split; columns t >= tokens of vt are left untouched), ldvt % 4 == 0 */
 int ltx_op_value_projection_t(ltx_ctx* ctx, const uint16_t* X, long ldx, int tokens, const uint16_t* W, const float* bias, int out_features,
                               int in_features, uint16_t* vt, long ldvt);
+/* The self-attention projections of a DiT block from the same rows X[rows][K]: qk_out[m][n] = bf16(X[m] . Wqk[n] + bqk[n]) for the
+ * fused to_q|to_k Linear Wqk [2 D][K], and V^T per batch element b = m / rows_per_batch in the layout the attention op takes:
+ * vt_out[(b * D + d) * ldvt + m % rows_per_batch] = bf16(X[m] . Wv[d] + bv[d]), Wv [D][K]; everything else of vt_out / qk_out is left
+ * untouched. fused != 0: ONE launch of 192 x 384 tiles (an error unless rows and rows_per_batch are multiples of 192, D of 128, K of
+ * 64, ldx and ld_qk of 8, ldvt of 4); fused == 0: the q|k Linear and one V^T launch per batch element. Both give the same bits. */
+int ltx_op_qkv_projection(ltx_ctx* ctx, const uint16_t* X, long ldx, int rows, int rows_per_batch, const uint16_t* Wqk, const float* bqk,
+                          const uint16_t* Wv, const float* bv, int D, int K, uint16_t* qk_out, long ld_qk, uint16_t* vt_out, long ldvt,
+                          int fused);
 /* x[m][n] += gate[n] * (A.B^T + bias) in place on an f32 stream, optional bf16 mirror of the result */
 int ltx_op_gemm_bf16_gated_residual(ltx_ctx* ctx, const uint16_t* A, long lda, const uint16_t* B, long ldb,
                                     const float* bias, const float* gate, float gate_scalar, int M, int N, int K,

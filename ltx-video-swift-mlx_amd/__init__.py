@@ -833,6 +833,17 @@ class Context:
         tokens, K = X.shape
         self._ck(lib.ltx_op_value_projection_t(self._h, _ptr(X), X.stride(0), tokens, _ptr(W), _ptr(bias), W.shape[0], K, _ptr(vt), vt.stride(0)))
 
+    def op_qkv_projection(self, X, Wqk, bqk, Wv, bv, qk_out, vt_out, rows=None, rows_per_batch=None, fused=True):
+        """qk_out[:rows, :2 D] bf16 = X[:rows, :K] . Wqk^T + bqk; V^T per batch element b of rows_per_batch rows in the attention op's
+        layout: row b * D + d of vt_out (any shape with rows of ldvt = vt_out.stride(-2) elements) holds (X . Wv^T + bv)[:, d] of that
+        element's rows. Wqk [2 D][K] and Wv [D][K] dense; X, qk_out and vt_out may have wider rows than they use. fused: one launch of
+        192 x 384 tiles (an error on a shape it does not take), else the two-launch path. Same bits either way."""
+        D, K = Wv.shape
+        rows = X.shape[0] if rows is None else rows
+        self._ck(lib.ltx_op_qkv_projection(self._h, _ptr(X), X.stride(0), rows, rows if rows_per_batch is None else rows_per_batch, _ptr(Wqk),
+                                           _ptr(bqk), _ptr(Wv), _ptr(bv), D, K, _ptr(qk_out), qk_out.stride(0), _ptr(vt_out), vt_out.stride(-2),
+                                           int(fused)))
+
     def op_gemm_gated_residual(self, A, B, bias, gate, gate_scalar, x, mirror=None):
         M, K = A.shape
         N = B.shape[0]

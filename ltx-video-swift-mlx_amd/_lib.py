@@ -232,6 +232,7 @@ SIGNATURES = {
     "ltx_prof_collect": (_i, [_vp, _i, C.POINTER(C.c_double), C.POINTER(C.c_long), C.POINTER(C.c_double), _i]),
     "ltx_op_gemm_bf16": (_i, [_vp, _vp, _l, _vp, _l, _vp, _i, _i, _i, _i, _i, _vp, _l, _vp, _l]),
     "ltx_op_value_projection_t": (_i, [_vp, _vp, _l, _i, _vp, _vp, _i, _i, _vp, _l]),
+    "ltx_op_qkv_projection": (_i, [_vp, _vp, _l, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _l, _vp, _l, _i]),
     "ltx_op_gemm_bf16_gated_residual": (_i, [_vp, _vp, _l, _vp, _l, _vp, _vp, _f, _i, _i, _i, _vp, _l, _vp, _l]),
     "ltx_op_gemm_bf16_gated_residual_norm": (_i, [_vp, _vp, _l, _vp, _l, _vp, _vp, _f, _i, _i, _i, _vp, _l, _vp, _vp, _f, _vp, _l, _i]),
     "ltx_op_gemv_f32": (_i, [_vp, _vp, _l, _vp, _l, _vp, _vp, _l, _i, _i, _i, _i]),

@@ -158,6 +158,23 @@ int ltx_op_value_projection_t(ltx_ctx* ctx, const uint16_t* X, long ldx, int tok
     });
 }
 
+int ltx_op_qkv_projection(ltx_ctx* ctx, const uint16_t* X, long ldx, int rows, int rows_per_batch, const uint16_t* Wqk, const float* bqk,
+                          const uint16_t* Wv, const float* bv, int D, int K, uint16_t* qk_out, long ld_qk, uint16_t* vt_out, long ldvt, int fused) {
+    return with_ctx(ctx, [&] {
+        LTX_REQUIRE(X && Wqk && Wv && qk_out && vt_out && rows > 0 && rows_per_batch > 0 && rows % rows_per_batch == 0 && D > 0 && K > 0,
+                    "ltx_op_qkv_projection: null argument or rows not a multiple of rows_per_batch");
+        LinearW wqk, wv;
+        wqk.w = (bf16_t*)Wqk;
+        wqk.b = (float*)bqk;
+        wqk.out = 2 * D;
+        wv.w = (bf16_t*)Wv;
+        wv.b = (float*)bv;
+        wv.out = D;
+        wqk.in = wv.in = K;
+        gemm_qkv(X, ldx, rows, rows_per_batch, wqk, wv, qk_out, ld_qk, vt_out, ldvt, (long)D * ldvt, fused != 0, ctx->stream);
+    });
+}
+
 int ltx_op_gemm_bf16_gated_residual(ltx_ctx* ctx, const uint16_t* A, long lda, const uint16_t* B, long ldb,
                                     const float* bias, const float* gate, float gate_scalar, int M, int N, int K,
                                     float* x, long ldx, uint16_t* mirror, long ld_mirror) {

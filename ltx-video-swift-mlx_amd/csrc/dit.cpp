@@ -446,6 +446,7 @@ void dit_forward(ltx_ctx* ctx, DiTModel* m, const DiTForwardArgs& a) {
     }
     const long mod_bs = (long)L * 6 * D;  // batch stride of mod
 
+    const bool qkv_fused_on = ltx_opt(OPT_QKV_FUSED) != 0;  // read once per forward
     bool xn_ready = false;  // the previous block's last GEMM launch already wrote this block's first adaLN rows (NormAfter)
     for (int l = 0; l < L; ++l) {
         const DiTBlock& blk = m->blocks[l];
@@ -479,13 +480,23 @@ void dit_forward(ltx_ctx* ctx, DiTModel* m, const DiTForwardArgs& a) {
                 eqk.out_f32 = qk;
                 eqk.ld_f32 = 2 * D;
             }
-            gemm_linear(xn, D, blk.qk1, (int)rows, eqk, st, sk);
+            // one launch for q|k and V^T where the 192 x 384 kernel takes the shape (dense weights, bf16 q|k store, no sequence parallelism)
+            const bool qkv_fused = qkv_fused_on && !sp && qkb &&
+                                   gemm_qkv_fused_takes(gemm_qkv_args(xn, D, (int)rows, T, blk.qk1, blk.v1, (bf16_t*)qk, 2 * D, vt, Tpad, (long)D * Tpad),
+                                                        blk.qk1, blk.v1, sk.p != nullptr);
+            if (qkv_fused) {
+                gemm_qkv(xn, D, (int)rows, T, blk.qk1, blk.v1, (bf16_t*)qk, 2 * D, vt, Tpad, (long)D * Tpad, true, st);
+            } else {
+                gemm_linear(xn, D, blk.qk1, (int)rows, eqk, st, sk);
+            }
             if (qkb) launch_qknorm_rope2(qk, blk.qn1, q, (const float*)((const bf16_t*)qk + D), blk.kn1, k, 2 * D, D, rope_c, rope_s, T, (int)rows, D, eps, st, kAttnQueryPrescale, true);
             else
             launch_qknorm_rope2(qk, blk.qn1, q, qk + D, blk.kn1, k, 2 * D, D, rope_c, rope_s, T, (int)rows, D, eps, st, kAttnQueryPrescale);
             AttnArgs at;
             if (!sp) {
-                for (int b = 0; b < B; ++b) gemm_vt(xn + (size_t)b * T * D, D, T, blk.v1, vt + (size_t)b * D * Tpad, Tpad, st, sk);
+                if (!qkv_fused) {  // (the fused launch wrote every batch element's V^T slab)
+                    for (int b = 0; b < B; ++b) gemm_vt(xn + (size_t)b * T * D, D, T, blk.v1, vt + (size_t)b * D * Tpad, Tpad, st, sk);
+                }
                 at.Vt = vt; at.ldvt = Tpad; at.vt_bstride = (long)D * Tpad;
                 at.K = k; at.k_bstride = (long)T * D;
                 at.Tk = T;

@@ -152,6 +152,33 @@ bool gemm_fewrow_takes(int M, int N, int K, int splits);
 // used by tests/bench sweeps.
 void launch_gemm_bf16_cfg(const GemmArgs& args, int cfg, hipStream_t stream);
 
+// The self-attention projections of a DiT block in ONE launch of 192 x 384 tiles (gemm_bf16_kernel_qkv): both read the rows X.
+//   qk[m][n]                  = bf16(X[m][:] . Wqk[n][:] + bias_qk[n])   n < Nqk (the fused q|k Linear), row-major
+//   vt[m / rpb][d][m % rpb]   = bf16(X[m][:] . Wv[d][:]  + bias_v[d])    d < Nqk / 2, transposed per batch element (rpb = rows_per_batch)
+// Column tile tn takes weight rows [256 tn, 256 tn + 256) of Wqk and [128 tn, 128 tn + 128) of Wv through two buffer descriptors: the
+// weights stay where they are. Bit-identical to launch_gemm_bf16 of the two Linears (one f32 accumulator chain per element, K
+// ascending). gemm_qkv_takes is the launcher's own rule; launch_gemm_qkv throws on a shape it does not take.
+struct GemmQkvArgs {
+    const bf16_t* X = nullptr;
+    long ldx = 0;
+    int M = 0, rows_per_batch = 0;
+    const bf16_t* Wqk = nullptr;  // [Nqk][ldwqk]
+    long ldwqk = 0;
+    const float* bias_qk = nullptr;
+    const bf16_t* Wv = nullptr;   // [Nqk / 2][ldwv]
+    long ldwv = 0;
+    const float* bias_v = nullptr;
+    int Nqk = 0, K = 0;
+    bf16_t* qk = nullptr;  // [M][ld_qk]
+    long ld_qk = 0;
+    bf16_t* vt = nullptr;  // [M / rows_per_batch] slabs of [Nqk / 2][ldvt], vt_bstride elements apart
+    long ldvt = 0;
+    long vt_bstride = 0;
+    int group_m = 4;       // GemmArgs::group_m
+};
+bool gemm_qkv_takes(const GemmQkvArgs& args);
+void launch_gemm_qkv(const GemmQkvArgs& args, hipStream_t stream);
+
 // Small-M path (M <= 8): out[m][n] = act_out( sum_k in_act(a[m][k]) * W[n][k] + bias[n] ), f32 activations x bf16
 // weights -> f32, exactly the reference's promotion on the timestep path.
 void launch_gemv_f32(const float* a, long lda, const bf16_t* W, long ldw, const float* bias, float* out, long ldo,

@@ -72,18 +72,20 @@ LTX_DEVFN int conv_block_order(int L, int F, int RG) {
     return (f0 + fo) * RG + rbi * RB + ro;
 }
 
-LTX_DEVFN void tile_coords(const GemmArgs& g, int bid, int tiles_m, int BN_, int& tm, int& tn) {
-    if (g.group_m > 0 && g.group_m < tiles_m) {
-        const int tiles_n = (g.N + BN_ - 1) / BN_;
-        const int per = g.group_m * tiles_n;
+LTX_DEVFN void tile_coords(int group_m, int tiles_n, int bid, int tiles_m, int& tm, int& tn) {
+    if (group_m > 0 && group_m < tiles_m) {
+        const int per = group_m * tiles_n;
         const int grp = bid / per, rem = bid - grp * per;
-        const int gm = (tiles_m - grp * g.group_m) < g.group_m ? (tiles_m - grp * g.group_m) : g.group_m;
+        const int gm = (tiles_m - grp * group_m) < group_m ? (tiles_m - grp * group_m) : group_m;
         tn = rem / gm;
-        tm = grp * g.group_m + (rem - tn * gm);
+        tm = grp * group_m + (rem - tn * gm);
     } else {
         tm = bid % tiles_m;
         tn = bid / tiles_m;
     }
+}
+LTX_DEVFN void tile_coords(const GemmArgs& g, int bid, int tiles_m, int BN_, int& tm, int& tn) {
+    tile_coords(g.group_m, (g.N + BN_ - 1) / BN_, bid, tiles_m, tm, tn);
 }
 
 // ---- epilogue: per-wave LDS transpose (16 rows at a time), then 16-B row-contiguous global accesses ----
@@ -841,7 +843,7 @@ LTX_DEVFN void wait_vmcnt_barrier() {
 // 128-B line, to hide the HBM latency of the once-streamed DiT weights. Same-process A/B on MI355X: 779 vs 963 TFLOP/s
 // cold and 932 vs 1040 warm at 1536x8192x4096 - every touched line crosses the CU's vector L1, +40 % bytes through the
 // texture path that this loop already saturates. The ring depth stays the only latency cover.)
-#if defined(GEMM_ASM_STAMPS) || defined(GEMM_V2_STAMPS) || defined(DTL_STAMPS)
+#if defined(GEMM_ASM_STAMPS) || defined(GEMM_V2_STAMPS) || defined(DTL_STAMPS) || defined(QKV_STAMPS)
 __device__ unsigned long long g_gemm_stamps[5][8];  // diagnostic builds only (tools/ubench/gemm_stamps.hip)
 #endif
 // QB (few-row launches on a quantised Linear, round 3): B arrives as 8-bit codes + bf16 scale / bias per 64-wide group (one group =
@@ -2236,6 +2238,130 @@ __global__ __launch_bounds__(256, 1) void gemm_bf16_kernel_dtl(const GemmArgs g)
     });
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// 192 x 384 tile for the self-attention projections of a DiT block: 256 columns of the fused q|k matrix and 128 columns of V in ONE
+// launch (both read the same adaLN rows), assembly main loop generated by tools/gen_gemm_asm_qkv.py (LDS layout of the two weight
+// sources, schedule, register map and the static proof of its LDS-DMA / ds_read ordering are in that script). 1536 tokens x
+// (8192 + 4096) columns are exactly one round of 256 tiles where the two launches it replaces ran a round each. One wave per SIMD,
+// wave tile 96 x 192: columns 0..127 of a wave are q|k (bias, row-major bf16 store through the LDS scratch, as the 192 x 256 kernel),
+// columns 128..191 are V (bias, transposed bf16 store straight from the accumulator layout, as gemm_epilogue_with's out_bf16_t form).
+// Same accumulator chain per output element as either of those kernels: the results are bit-identical to the two launches.
+// ---------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256, 1) void gemm_bf16_kernel_qkv(const GemmQkvArgs g) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    constexpr int BM = 192, WM = 96, WNQ = 128, WNV = 64;
+    constexpr int A_BYTES = BM * ROW_BYTES;
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wr = wave / 2, wc = wave % 2;
+    const int tiles_m = g.M / BM;
+    const int bid = xcd_remap(blockIdx.x, gridDim.x);
+    int tm, tn;
+    tile_coords(g.group_m, g.Nqk / 256, bid, tiles_m, tm, tn);
+    const int m0 = tm * BM;
+    // piece i of this wave = LDS rows (wave + 4 i) * 8 .. +7 of the tile: the per-lane part of its source address (row inside the piece,
+    // swizzled 16-byte chunk) does not depend on i, the i part (and which weight matrix it comes from) is in the stream
+    const int srow = lane >> 3, pch = lane & 7;
+    const int row0 = wave * 8 + srow;
+    const int sw = (pch ^ ((row0 >> 1) & 7)) << 3;
+    const int ao = (row0 * (int)g.ldx + sw) * 2;
+    const int bo = (row0 * (int)g.ldwqk + sw) * 2;
+    const int vo = (row0 * (int)g.ldwv + sw) * 2;
+    const uint32_t sa = (uint32_t)(32 * g.ldx * 2), sb = (uint32_t)(32 * g.ldwqk * 2), sv = (uint32_t)(32 * g.ldwv * 2);
+    const int nkt = g.K / BK;
+    const bf16_t* At = g.X + (long)m0 * g.ldx;
+    const bf16_t* Bt = g.Wqk + (long)tn * 256 * g.ldwqk;
+    const bf16_t* Vt = g.Wv + (long)tn * 128 * g.ldwv;
+    const uint32_t alo = (uint32_t)(uintptr_t)At, ahi = (uint32_t)((uintptr_t)At >> 32);
+    const uint32_t blo = (uint32_t)(uintptr_t)Bt, bhi = (uint32_t)((uintptr_t)Bt >> 32);
+    const uint32_t vlo = (uint32_t)(uintptr_t)Vt, vhi = (uint32_t)((uintptr_t)Vt >> 32);
+    const uint32_t arec = (uint32_t)(((long)(BM - 1) * g.ldx + g.K) * 2), brec = (uint32_t)(((long)255 * g.ldwqk + g.K) * 2),
+                   vrec = (uint32_t)(((long)127 * g.ldwv + g.K) * 2);
+    const uint32_t nk = (uint32_t)nkt;
+    const uint32_t wlds = (uint32_t)wave * 1024u;
+    const int frow = lane & 15, fsw = (lane >> 1) & 7;
+    const int foff0 = frow * ROW_BYTES + ((((lane >> 4) + 0) ^ fsw) << 4);
+    const int foff1 = frow * ROW_BYTES + ((((lane >> 4) + 4) ^ fsw) << 4);
+    // LDS: [A slot 0][A slot 1][B slot 0][B slot 1]; a B slot holds [q|k 0..127][V 0..63][q|k 128..255][V 64..127]
+    const int a_wave_off = (wr * WM) * ROW_BYTES, b_wave_off = 2 * A_BYTES + (wc * (WNQ + WNV)) * ROW_BYTES;
+    const int fa0 = a_wave_off + foff0, fa1 = a_wave_off + foff1, fb0 = b_wave_off + foff0, fb1 = b_wave_off + foff1;
+    // where the stream leaves the eight V accumulators it keeps in VGPRs: behind the q|k scratch of the epilogue, 8 KB per wave
+    constexpr int SPILL0 = 4 * 32 * WNQ * 4;
+    const int sp = SPILL0 + wave * 8192 + lane * 16;
+#ifdef QKV_STAMPS  // tools/ubench/gemm_qkv_stamps.hip
+    unsigned long long* dbg = (blockIdx.x == 7) ? &g_gemm_stamps[wave][0] : &g_gemm_stamps[4][0];
+#endif
+    asm volatile(
+#ifdef QKV_STAMPS
+#include "gemm_qkv_192x384_stamps.inc"
+#else
+#include "gemm_qkv_192x384.inc"
+#endif
+        :
+        : [alo] "s"(alo), [ahi] "s"(ahi), [arec] "s"(arec), [blo] "s"(blo), [bhi] "s"(bhi), [brec] "s"(brec), [vlo] "s"(vlo), [vhi] "s"(vhi),
+          [vrec] "s"(vrec), [nk] "s"(nk), [sa] "s"(sa), [sb] "s"(sb), [sv] "s"(sv), [wlds] "s"(wlds), [ao] "v"(ao), [bo] "v"(bo), [vo] "v"(vo),
+          [fa0] "v"(fa0), [fa1] "v"(fa1), [fb0] "v"(fb0), [fb1] "v"(fb1), [sp] "v"(sp)
+#ifdef QKV_STAMPS
+          , [dbg] "s"(dbg)
+#endif
+        :
+#include "gemm_qkv_192x384_clobbers.inc"
+    );
+    // (the stream ends behind a barrier: every wave is done with the K-tile slots, and its VGPR-held accumulators are in LDS)
+    // V epilogue: fragment vf = 4 mi + nv holds C[16 mi + 4 (lane >> 4) + r][16 nv + (lane & 15)], r = 0..3, of the wave's 96 x 64 V
+    // tile: four consecutive tokens of one channel = 8 contiguous bytes of V^T. The tile's rows lie in one batch element.
+    {
+        const int bi = m0 / g.rows_per_batch;
+        const int tok0 = m0 - bi * g.rows_per_batch + wr * WM + (lane >> 4) * 4;
+        const int d0 = tn * 128 + wc * WNV + (lane & 15);
+        bf16_t* vbase = g.vt + (long)bi * g.vt_bstride + tok0;
+        float bv[4];
+#pragma unroll
+        for (int nv = 0; nv < 4; ++nv) bv[nv] = g.bias_v ? g.bias_v[d0 + nv * 16] : 0.f;
+        static_for<0, 24>([&](auto vf_c) {
+            constexpr int vf = decltype(vf_c)::value;
+            constexpr int mi = vf / 4, nv = vf % 4;
+            float f0, f1, f2, f3;
+            if constexpr (vf < 16) {
+#include "gemm_qkv_192x384_vread.inc"
+            } else {
+                const f32x4 t = *(const f32x4*)(smem + SPILL0 + wave * 8192 + (vf - 16) * 1024 + lane * 16);
+                f0 = t[0], f1 = t[1], f2 = t[2], f3 = t[3];
+            }
+            const float bn = bv[nv];
+            uint2 pk;
+            pk.x = pack_bf16x2(f0 + bn, f1 + bn);
+            pk.y = pack_bf16x2(f2 + bn, f3 + bn);
+            *(uint2*)(vbase + (long)(d0 + nv * 16) * g.ldvt + mi * 16) = pk;
+        });
+    }
+    // q|k epilogue: 32 rows x 128 columns at a time through the wave's LDS scratch (a[0:191] in the 192 x 256 kernel's map: its dump),
+    // the 16 scratch reads of a group issued together
+    constexpr int WN = WNQ, LPR = WN / 4, RPI = 64 / LPR, NITG = 32 / RPI;
+    float* scr = (float*)(smem + wave * (32 * WN * 4));
+    const unsigned scr_lane = (unsigned)(wave * (32 * WN * 4) + ((((lane >> 4) * 4) * WN + (lane & 15)) * 4));
+    const int gn = tn * 256 + wc * WN + (lane % LPR) * 4;
+    const f32x4 bias = g.bias_qk ? *(const f32x4*)(g.bias_qk + gn) : f32x4{0.f, 0.f, 0.f, 0.f};
+    static_for<0, 3>([&](auto grp_c) {
+        constexpr int grp = decltype(grp_c)::value;
+#include "gemm_asm_192x256_dump.inc"
+        f32x4 vv[NITG];
+#pragma unroll
+        for (int it = 0; it < NITG; ++it) vv[it] = *(const f32x4*)(scr + (it * RPI + lane / LPR) * WN + (lane % LPR) * 4);
+#pragma unroll
+        for (int it = 0; it < NITG; ++it) {
+            const int gm = m0 + wr * WM + grp * 32 + it * RPI + lane / LPR;
+            const f32x4 v = vv[it] + bias;
+            uint2 pk;
+            pk.x = pack_bf16x2(v[0], v[1]);
+            pk.y = pack_bf16x2(v[2], v[3]);
+            *(uint2*)(g.qk + (long)gm * g.ld_qk + gn) = pk;
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the scratch is rewritten by the next dump
+    });
+}
+
 #ifdef LTX_EXPERIMENTS
 template <int BM, int BN, int NSTAGE>
 void launch_m32(const GemmArgs& a, hipStream_t stream) {
@@ -2410,6 +2536,31 @@ static void launch_dtl(const GemmArgs& a, hipStream_t stream, const NormAfter* n
     } else {
         LTX_REQUIRE(!na, "gemm: a norm pass can only ride on a split-K finish");
     }
+}
+
+// ---- fused q|k + V projection (gemm_bf16_kernel_qkv) ----
+bool gemm_qkv_takes(const GemmQkvArgs& a) {
+    // ld % 8: the LDS-DMA pieces are 16-byte loads, the q|k store is 8-byte; ldvt % 4: 8-byte V^T stores; rows_per_batch % 192: a row tile
+    // lies in one V^T slab; the 1 << 22 bound keeps every 32-bit buffer offset of a 256-row tile positive
+    const long ldmax = 1L << 22;
+    return a.X && a.Wqk && a.Wv && a.qk && a.vt && a.M > 0 && a.M % 192 == 0 && a.rows_per_batch > 0 && a.rows_per_batch % 192 == 0 &&
+           a.M % a.rows_per_batch == 0 && a.Nqk > 0 && a.Nqk % 256 == 0 && a.K >= 64 && a.K % 64 == 0 && a.ldx % 8 == 0 && a.ldwqk % 8 == 0 &&
+           a.ldwv % 8 == 0 && a.ld_qk % 8 == 0 && a.ldvt % 4 == 0 && a.ldx >= a.K && a.ldwqk >= a.K && a.ldwv >= a.K && a.ld_qk >= a.Nqk &&
+           a.ldvt >= a.rows_per_batch && a.ldx < ldmax && a.ldwqk < ldmax && a.ldwv < ldmax && a.vt_bstride % 4 == 0 &&
+           ((uintptr_t)a.X | (uintptr_t)a.Wqk | (uintptr_t)a.Wv) % 16 == 0 && ((uintptr_t)a.qk | (uintptr_t)a.vt) % 8 == 0 &&
+           (!a.bias_qk || (uintptr_t)a.bias_qk % 16 == 0);
+}
+void launch_gemm_qkv(const GemmQkvArgs& a, hipStream_t stream) {
+    LTX_REQUIRE(gemm_qkv_takes(a),
+                "gemm: the fused q|k + V kernel needs M %% 192 == 0, rows per batch %% 192 == 0, N_qk %% 256 == 0, K %% 64 == 0, leading dimensions %% 8 == 0 "
+                "and ldvt %% 4 == 0 (M=%d rows_per_batch=%d N_qk=%d K=%d ldx=%ld ld_qk=%ld ldvt=%ld)",
+                a.M, a.rows_per_batch, a.Nqk, a.K, a.ldx, a.ld_qk, a.ldvt);
+    ProfScope prof(PROF_GEMM, 2.0 * a.M * ((double)a.Nqk + a.Nqk / 2) * a.K, stream);
+    constexpr int smem = (2 * 192 + 2 * 384) * ROW_BYTES;  // two activation slots, two weight slots
+    static PerDeviceOnce attr_set;
+    attr_set.run([&] { HIP_CHECK(hipFuncSetAttribute((const void*)gemm_bf16_kernel_qkv, hipFuncAttributeMaxDynamicSharedMemorySize, smem)); });
+    hipLaunchKernelGGL(gemm_bf16_kernel_qkv, dim3((a.M / 192) * (a.Nqk / 256)), dim3(256), smem, stream, a);
+    HIP_CHECK(hipGetLastError());
 }
 
 #ifdef LTX_EXPERIMENTS

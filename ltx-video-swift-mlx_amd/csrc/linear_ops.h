@@ -109,3 +109,53 @@ inline void gemm_vt(const bf16_t* X, long ldx, int tokens, const LinearW& wv, bf
     }
     launch_gemm_bf16(g, s);
 }
+
+// q|k (row-major bf16, ld_qk) and V^T (per batch element: vt + b * vt_bstride, [wv.out][ldvt]) of a block's self-attention from the same
+// rows X. gemm_qkv_fused_takes: can the pair run as ONE launch of 192 x 384 tiles (launch_gemm_qkv)? Dense resident weights only - a
+// quantised Linear's scratch matrix cannot hold both Linears at once. The results equal the two launches' bit for bit.
+inline GemmQkvArgs gemm_qkv_args(const bf16_t* X, long ldx, int rows, int rows_per_batch, const LinearW& wqk, const LinearW& wv, bf16_t* qk, long ld_qk,
+                                 bf16_t* vt, long ldvt, long vt_bstride) {
+    GemmQkvArgs g;
+    g.X = X;
+    g.ldx = ldx;
+    g.M = rows;
+    g.rows_per_batch = rows_per_batch;
+    g.Wqk = wqk.w;
+    g.ldwqk = wqk.in;
+    g.bias_qk = wqk.b;
+    g.Wv = wv.w;
+    g.ldwv = wv.in;
+    g.bias_v = wv.b;
+    g.Nqk = wqk.out;
+    g.K = wqk.in;
+    g.qk = qk;
+    g.ld_qk = ld_qk;
+    g.vt = vt;
+    g.ldvt = ldvt;
+    g.vt_bstride = vt_bstride;
+    return g;
+}
+// may_split: the two launches would be given a split-K workspace. Where either of them would then split its reduction (few output tiles
+// or a long K: gemm_suggest_split_k, the 192x256 kernel's K ranges) the sums differ from one accumulator chain, so those shapes keep
+// the two launches.
+inline bool gemm_qkv_fused_takes(const GemmQkvArgs& g, const LinearW& wqk, const LinearW& wv, bool may_split) {
+    if (!(wqk.w && wv.w && wv.out * 2 == wqk.out && wv.in == wqk.in && gemm_qkv_takes(g))) return false;
+    return !may_split || (gemm_suggest_split_k(g.M, wqk.out, g.K) <= 1 && gemm_suggest_split_k(g.rows_per_batch, wv.out, g.K) <= 1 &&
+                          g.K < 2 * ltx_opt(OPT_DTL_SPLITK_MINK));
+}
+// fused: one launch (throws on a shape gemm_qkv_fused_takes refuses); else the q|k Linear and one V^T launch per batch element
+inline void gemm_qkv(const bf16_t* X, long ldx, int rows, int rows_per_batch, const LinearW& wqk, const LinearW& wv, bf16_t* qk, long ld_qk, bf16_t* vt,
+                     long ldvt, long vt_bstride, bool fused, hipStream_t s, SplitWs ws = {}) {
+    if (fused) {
+        const GemmQkvArgs g = gemm_qkv_args(X, ldx, rows, rows_per_batch, wqk, wv, qk, ld_qk, vt, ldvt, vt_bstride);
+        LTX_REQUIRE(wqk.w && wv.w && wv.out * 2 == wqk.out && wv.in == wqk.in,
+                    "gemm_qkv: the fused launch needs resident bf16 weights of a [2D][K] q|k and a [D][K] V Linear");
+        launch_gemm_qkv(g, s);
+        return;
+    }
+    GemmEpilogue e;
+    e.out_bf16 = qk;
+    e.ld_bf16 = ld_qk;
+    gemm_linear(X, ldx, wqk, rows, e, s, ws);
+    for (int b = 0; b < rows / rows_per_batch; ++b) gemm_vt(X + (size_t)b * rows_per_batch * ldx, ldx, rows_per_batch, wv, vt + (size_t)b * vt_bstride, ldvt, s, ws);
+}
