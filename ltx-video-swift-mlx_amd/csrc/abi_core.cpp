@@ -22,6 +22,24 @@ std::string& noctx_error() {
     return e;
 }
 
+long export_param_body(ltx_ctx* ctx, const char* who, const char* name, float* out, long cap, const std::function<const ParamSlot*()>& find,
+                       const std::function<void(const ParamSlot&, float*)>& export_slot) {
+    if (!ctx || !name) return -LTX_ERR_INVALID_CONFIGURATION;
+    long n = 0;
+    const int rc = guarded(ctx, [&] {
+        const ParamSlot* s = find();
+        LTX_REQUIRE(s != nullptr, "%s: no parameter '%s'", who, name);
+        n = s->numel;
+        if (!out) return;
+        LTX_REQUIRE(cap >= n, "%s: buffer too small (%ld < %ld)", who, cap, n);
+        if (export_slot)
+            export_slot(*s, out);
+        else
+            param_export(ctx, *s, out);
+    });
+    return rc == 0 ? n : -rc;
+}
+
 extern "C" {
 
 const char* ltx_version(void) { return "0.1.0"; }

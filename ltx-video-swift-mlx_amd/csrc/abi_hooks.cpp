@@ -53,20 +53,9 @@ void audio_op_epilogue(AConvArgs& a, const float* resid, int f32_act, int transp
 extern "C" {
 
 long ltx_dit_export_param(ltx_ctx* ctx, const char* module_key, float* out, long cap) {
-    if (!ctx || !module_key) return -LTX_ERR_INVALID_CONFIGURATION;
-    long n = 0;
-    const int rc = guarded(ctx, [&] {
-        DiTModel* m = need(ctx->dit, kNoDit);
-        auto it = m->slots.find(module_key);
-        LTX_REQUIRE(it != m->slots.end(), "ltx_dit_export_param: no parameter '%s'", module_key);
-        const ParamSlot& sl = it->second;
-        n = sl.numel;
-        if (!out) return;
-        LTX_REQUIRE(cap >= n, "ltx_dit_export_param: buffer too small (%ld < %ld)", cap, n);
-        HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        dit_export_slot(ctx, m, sl, out);
-    });
-    return rc == 0 ? n : -rc;
+    return export_param_body(
+        ctx, "ltx_dit_export_param", module_key, out, cap, [&] { return need(ctx->dit, kNoDit)->params.find(module_key); },
+        [&](const ParamSlot& s, float* o) { dit_export_slot(ctx, ctx->dit, s, o); });
 }
 
 int ltx_prof_enable(ltx_ctx* ctx, int on) {

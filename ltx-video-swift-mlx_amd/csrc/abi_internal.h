@@ -6,6 +6,7 @@
 #include <stddef.h>
 #include <string.h>
 
+#include <functional>
 #include <string>
 
 #include "../../include/ltxhip.h"
@@ -99,6 +100,11 @@ M* need(M* model, const char* message) {
     if (!model) LTX_THROW(LTXS_MODEL_NOT_LOADED, "%s", message);
     return model;
 }
+
+// The body of every ltx_*_export_param: the element count, and the values when `out` is given. `find` names the model's parameter (null:
+// no such parameter) and throws the model's not-loaded error itself; `export_slot` replaces param_export (the DiT's also de-quantises).
+long export_param_body(ltx_ctx* ctx, const char* who, const char* name, float* out, long cap, const std::function<const ParamSlot*()>& find,
+                       const std::function<void(const ParamSlot&, float*)>& export_slot = nullptr);
 
 // the not-loaded texts; callers and the mirrors may match on them
 constexpr const char* kNoDit = "Model component not loaded: transformer";

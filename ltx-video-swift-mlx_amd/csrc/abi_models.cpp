@@ -229,10 +229,10 @@ int ltx_dit_quantize(ltx_ctx* ctx, int bits, int group_size) {
 int ltx_dit_memory_info(ltx_ctx* ctx, long* bf16_weight_bytes, long* quantised_weight_bytes, long* scratch_bytes, long* other_bytes) {
     return with_ctx(ctx, [&] {
         DiTModel* m = need(ctx->dit, kNoDit);
-        if (bf16_weight_bytes) *bf16_weight_bytes = m->warena.buf.p ? (long)m->warena.buf.bytes : 0;
+        if (bf16_weight_bytes) *bf16_weight_bytes = m->params.warena.buf.p ? (long)m->params.warena.buf.bytes : 0;
         if (quantised_weight_bytes) *quantised_weight_bytes = m->qarena.buf.p ? (long)m->qarena.buf.bytes : 0;
         if (scratch_bytes) *scratch_bytes = m->dq.buf.p ? (long)m->dq.buf.bytes : 0;
-        if (other_bytes) *other_bytes = m->arena.buf.p ? (long)m->arena.buf.bytes : 0;
+        if (other_bytes) *other_bytes = m->params.arena.buf.p ? (long)m->params.arena.buf.bytes : 0;
     });
 }
 
@@ -850,18 +850,8 @@ int ltx_attn_module_unload(ltx_ctx* ctx, int index) {
     return with_ctx(ctx, [&] { unload_model(ctx, attn_slot(ctx, index), attn_module_destroy); });
 }
 long ltx_attn_module_export_param(ltx_ctx* ctx, int index, const char* name, float* out, long cap) {
-    if (!ctx || !name) return -LTX_ERR_INVALID_CONFIGURATION;
-    long n = 0;
-    const int rc = guarded(ctx, [&] {
-        AttnModule* m = need(*attn_slot(ctx, index), kNoAttnModule);
-        auto it = m->slots.find(name);
-        LTX_REQUIRE(it != m->slots.end(), "ltx_attn_module_export_param: no parameter '%s'", name);
-        n = it->second.numel;
-        if (!out) return;
-        LTX_REQUIRE(cap >= n, "ltx_attn_module_export_param: buffer too small (%ld < %ld)", cap, n);
-        attn_module_export(ctx, m, it->second, out);
-    });
-    return rc == 0 ? n : -rc;
+    return export_param_body(ctx, "ltx_attn_module_export_param", name, out, cap,
+                             [&] { return need(*attn_slot(ctx, index), kNoAttnModule)->params.find(name); });
 }
 int ltx_attn_module_forward_dev(ltx_ctx* ctx, int index, const float* x, const void* context, int context_bf16, int B, int Tq, int Tk,
                                 const float* q_cos, const float* q_sin, int q_table_rows, const float* k_cos, const float* k_sin,
@@ -915,18 +905,7 @@ int ltx_dual_blocks_unload(ltx_ctx* ctx) {
     return with_ctx(ctx, [&] { unload_model(ctx, &ctx->dual, dual_destroy); });
 }
 long ltx_dual_blocks_export_param(ltx_ctx* ctx, const char* name, float* out, long cap) {
-    if (!ctx || !name) return -LTX_ERR_INVALID_CONFIGURATION;
-    long n = 0;
-    const int rc = guarded(ctx, [&] {
-        DualStack* m = need(ctx->dual, kNoDualBlocks);
-        auto it = m->slots.find(name);
-        LTX_REQUIRE(it != m->slots.end(), "ltx_dual_blocks_export_param: no parameter '%s'", name);
-        n = it->second.numel;
-        if (!out) return;
-        LTX_REQUIRE(cap >= n, "ltx_dual_blocks_export_param: buffer too small (%ld < %ld)", cap, n);
-        dual_export(ctx, m, it->second, out);
-    });
-    return rc == 0 ? n : -rc;
+    return export_param_body(ctx, "ltx_dual_blocks_export_param", name, out, cap, [&] { return need(ctx->dual, kNoDualBlocks)->params.find(name); });
 }
 int ltx_dual_blocks_forward_dev(ltx_ctx* ctx, const ltx_dual_forward_args* args) {
     if (!ctx) return LTX_ERR_INVALID_CONFIGURATION;
@@ -978,18 +957,8 @@ int ltx_dual_model_unload(ltx_ctx* ctx) {
     return with_ctx(ctx, [&] { unload_model(ctx, &ctx->dual_model, dual_model_destroy); });
 }
 long ltx_dual_model_export_param(ltx_ctx* ctx, const char* name, float* out, long cap) {
-    if (!ctx || !name) return -LTX_ERR_INVALID_CONFIGURATION;
-    long n = 0;
-    const int rc = guarded(ctx, [&] {
-        DualModel* m = need(ctx->dual_model, kNoDualModel);
-        const ParamSlot* s = dual_model_find(m, name);
-        LTX_REQUIRE(s != nullptr, "ltx_dual_model_export_param: no parameter '%s'", name);
-        n = s->numel;
-        if (!out) return;
-        LTX_REQUIRE(cap >= n, "ltx_dual_model_export_param: buffer too small (%ld < %ld)", cap, n);
-        dual_export(ctx, m->stack, *s, out);
-    });
-    return rc == 0 ? n : -rc;
+    return export_param_body(ctx, "ltx_dual_model_export_param", name, out, cap,
+                             [&] { return dual_model_find(need(ctx->dual_model, kNoDualModel), name); });
 }
 int ltx_dual_model_forward_dev(ltx_ctx* ctx, const ltx_dual_model_forward_args* args) {
     if (!ctx) return LTX_ERR_INVALID_CONFIGURATION;

@@ -9,14 +9,6 @@
 #include "linear_ops.h"
 
 namespace {
-struct Pending {
-    const char* key;
-    void** dst;
-    int kind;
-    long rows, cols;
-};
-long slot_bytes(int kind, long numel) { return numel * (kind == SLOT_BF16 ? 2 : 4); }
-
 // the file's spelling of a module key (ModelDownloader.swift:756-803 maps the other way)
 std::string file_spelling(const std::string& key) {
     if (key.compare(0, 7, "to_out.") == 0) return "to_out.0." + key.substr(7);
@@ -53,38 +45,23 @@ AttnModule* attn_module_create_ex(int query_dim, int context_dim, int heads, int
     m->k.in = m->v.in = (int)Dc;
     m->o.out = (int)Dq;
     m->o.in = (int)I;
-    // fused: to_k directly behind to_q, weights and biases (every size here is a multiple of the arena's 256-byte grain)
-    const Pending plain[] = {
-        {"to_q.weight", (void**)&m->q.w, SLOT_BF16, I, Dq},     {"to_q.bias", (void**)&m->q.b, SLOT_F32, I, 0},
-        {"to_k.weight", (void**)&m->k.w, SLOT_BF16, I, Dc},     {"to_k.bias", (void**)&m->k.b, SLOT_F32, I, 0},
-        {"to_v.weight", (void**)&m->v.w, SLOT_BF16, I, Dc},     {"to_v.bias", (void**)&m->v.b, SLOT_F32, I, 0},
-        {"to_out.weight", (void**)&m->o.w, SLOT_BF16, Dq, I},   {"to_out.bias", (void**)&m->o.b, SLOT_F32, Dq, 0},
-        {"q_norm.weight", (void**)&m->qn, SLOT_F32, I, 0},      {"k_norm.weight", (void**)&m->kn, SLOT_F32, I, 0},
-    };
-    const Pending fused[] = {
-        {"to_q.weight", (void**)&m->q.w, SLOT_BF16, I, Dq},     {"to_k.weight", (void**)&m->k.w, SLOT_BF16, I, Dc},
-        {"to_q.bias", (void**)&m->q.b, SLOT_F32, I, 0},         {"to_k.bias", (void**)&m->k.b, SLOT_F32, I, 0},
-        {"to_v.weight", (void**)&m->v.w, SLOT_BF16, I, Dc},     {"to_v.bias", (void**)&m->v.b, SLOT_F32, I, 0},
-        {"to_out.weight", (void**)&m->o.w, SLOT_BF16, Dq, I},   {"to_out.bias", (void**)&m->o.b, SLOT_F32, Dq, 0},
-        {"q_norm.weight", (void**)&m->qn, SLOT_F32, I, 0},      {"k_norm.weight", (void**)&m->kn, SLOT_F32, I, 0},
-    };
-    const Pending* pend = fused_qk ? fused : plain;
-    const int npend = 10;
-    size_t total = 0;
-    for (int i = 0; i < npend; ++i) total += DeviceArena::padded(slot_bytes(pend[i].kind, pend[i].rows * (pend[i].cols ? pend[i].cols : 1)));
     try {
-        m->arena.reserve(total + 256);
-        HIP_CHECK(hipMemset(m->arena.buf.p, 0, m->arena.buf.bytes));
-        for (int i = 0; i < npend; ++i) {
-            const Pending& p = pend[i];
-            ParamSlot s;
-            s.kind = p.kind;
-            s.rows = p.rows;
-            s.cols = p.cols;
-            s.numel = p.rows * (p.cols ? p.cols : 1);
-            s.dst = *p.dst = m->arena.take(slot_bytes(p.kind, s.numel));
-            m->slots[p.key] = s;
+        ParamTable& pt = m->params;
+        if (fused_qk) {
+            // to_k directly behind to_q, weights and biases (every size here is a multiple of the arena's 256-byte grain)
+            pt.add("to_q.weight", (void**)&m->q.w, SLOT_BF16, I, Dq);
+            pt.add("to_k.weight", (void**)&m->k.w, SLOT_BF16, I, Dc);
+            pt.add("to_q.bias", (void**)&m->q.b, SLOT_F32, I, 0);
+            pt.add("to_k.bias", (void**)&m->k.b, SLOT_F32, I, 0);
+        } else {
+            pt.add_linear("to_q", m->q, (int)I, (int)Dq);
+            pt.add_linear("to_k", m->k, (int)I, (int)Dc);
         }
+        pt.add_linear("to_v", m->v, (int)I, (int)Dc);
+        pt.add_linear("to_out", m->o, (int)Dq, (int)I);
+        pt.add("q_norm.weight", (void**)&m->qn, SLOT_F32, I, 0);
+        pt.add("k_norm.weight", (void**)&m->kn, SLOT_F32, I, 0);
+        pt.place(false);
         if (fused_qk && (m->k.w != m->q.w + I * Dq || m->k.b != m->q.b + I))
             LTX_THROW(LTXS_GENERATION_FAILED, "attention module: the fused q|k rows are not contiguous");
     } catch (...) {
@@ -97,18 +74,8 @@ AttnModule* attn_module_create_ex(int query_dim, int context_dim, int heads, int
 void attn_module_destroy(AttnModule* m) { delete m; }
 
 void attn_module_init_synthetic(ltx_ctx* ctx, AttnModule* m, uint64_t seed) {
-    uint64_t k = 0;
-    for (auto& kv : m->slots) {
-        ParamSlot& s = kv.second;
-        const uint64_t sd = seed * 0x9E3779B97F4A7C15ull + (++k) * 0xD1B54A32D192ED03ull;
-        const bool is_norm = kv.first.find("_norm.") != std::string::npos;
-        if (s.kind == SLOT_BF16)
-            launch_fill_normal_bf16((bf16_t*)s.dst, s.numel, sd, 0.f, 0.02f, ctx->stream);
-        else
-            launch_fill_normal_f32((float*)s.dst, s.numel, sd, is_norm ? 1.0f : 0.f, is_norm ? 0.02f : 0.01f, 1, ctx->stream);
-        s.loaded = true;
-    }
-    HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    // Linear weights N(0, 0.02^2), biases N(0, 0.01^2), q / k norm weights 1 + N(0, 0.02^2)
+    param_table_fill_synthetic(ctx, m->params, seed, 0, param_fill_rule_default);
 }
 
 void attn_module_file_shape(const std::string& path, const std::string& prefix, int* query_dim, int* context_dim, int* inner) {
@@ -131,40 +98,16 @@ void attn_module_load(ltx_ctx* ctx, AttnModule* m, const std::string& path, cons
     st.open(path);
     ctx->n_loaded = ctx->n_missing = ctx->n_unmatched = 0;
     std::vector<uint8_t> staging;
-    for (auto& kv : m->slots) {
+    for (auto& kv : m->params.slots) {
         ParamSlot& s = kv.second;
         s.loaded = false;
         const StTensor* t = find_tensor(st, prefix, kv.first);
         if (!t) LTX_THROW(LTXS_WEIGHT_LOADING_FAILED, "Failed to load weights: %s%s is not in %s", prefix.c_str(), kv.first.c_str(), path.c_str());
-        const bool shape_ok = s.cols ? (t->shape.size() == 2 && t->shape[0] == s.rows && t->shape[1] == s.cols) : t->numel() == s.numel;
-        if (!shape_ok)
-            LTX_THROW(LTXS_WEIGHT_LOADING_FAILED, "Failed to load weights: %s%s has %ld elements, expected [%ld, %ld]", prefix.c_str(), kv.first.c_str(),
-                      t->numel(), s.rows, s.cols);
-        if (s.kind == SLOT_BF16) {
-            staging.resize((size_t)s.numel * 2);
-            st_to_bf16(st, *t, (bf16_t*)staging.data());
-        } else {  // biases and norm weights are bf16 in the file: f32 copies of those values
-            staging.resize((size_t)s.numel * 4);
-            float* f = (float*)staging.data();
-            st_to_f32(st, *t, f);
-            for (long i = 0; i < s.numel; ++i) f[i] = host_bf16_to_f32(host_f32_to_bf16(f[i]));
-        }
-        HIP_CHECK(hipMemcpy(s.dst, staging.data(), staging.size(), hipMemcpyHostToDevice));
+        param_check_shape(prefix + kv.first, *t, s);
+        param_upload(st, *t, s, &staging);
         s.loaded = true;
         ctx->n_loaded++;
     }
-}
-
-void attn_module_export(ltx_ctx* ctx, AttnModule* m, const ParamSlot& s, float* out) {
-    (void)m;
-    HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    if (s.kind == SLOT_F32) {
-        HIP_CHECK(hipMemcpy(out, s.dst, (size_t)s.numel * 4, hipMemcpyDeviceToHost));
-        return;
-    }
-    std::vector<bf16_t> h((size_t)s.numel);
-    HIP_CHECK(hipMemcpy(h.data(), s.dst, (size_t)s.numel * 2, hipMemcpyDeviceToHost));
-    for (long i = 0; i < s.numel; ++i) out[i] = host_bf16_to_f32(h[i]);
 }
 
 void attn_module_forward(ltx_ctx* ctx, AttnModule* m, const AttnModuleArgs& a) {

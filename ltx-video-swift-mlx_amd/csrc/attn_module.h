@@ -36,11 +36,10 @@ struct AttnModule {
     int head_dim = 64;      // 128: attn_module_create_ex only
     bool fused_qk = false;  // to_q | to_k contiguous, q.w [2 inner][Dq] and q.b [2 inner] (attn_module_create_ex, Dc == Dq)
     float eps = 1e-6f;
-    DeviceArena arena;
     LinearW q, k, v, o;
     float* qn = nullptr;
     float* kn = nullptr;
-    std::map<std::string, ParamSlot> slots;  // "to_q.weight", "to_q.bias", .., "q_norm.weight", "k_norm.weight"
+    ParamTable params;  // one arena; "to_q.weight", "to_q.bias", .., "q_norm.weight", "k_norm.weight"
     DevBuf ws_xb, ws_cb, ws_qraw, ws_kraw, ws_q, ws_k, ws_vt, ws_ao;
 };
 
@@ -52,7 +51,6 @@ void attn_module_init_synthetic(ltx_ctx* ctx, AttnModule* m, uint64_t seed);
 // names (to_out.0, norm_q, norm_k) and the module's (to_out, q_norm, k_norm) are both accepted
 void attn_module_file_shape(const std::string& path, const std::string& prefix, int* query_dim, int* context_dim, int* inner);
 void attn_module_load(ltx_ctx* ctx, AttnModule* m, const std::string& path, const std::string& prefix);
-void attn_module_export(ltx_ctx* ctx, AttnModule* m, const ParamSlot& s, float* out);
 
 struct AttnModuleArgs {
     const float* x = nullptr;        // [B][Tq][Dq] f32

@@ -9,17 +9,6 @@
 #include "hostmath.h"
 #include "linear_ops.h"
 
-namespace {
-struct Pending {
-    std::string key;
-    void** dst;
-    int kind;
-    long rows, cols;
-    int init;
-};
-long slot_bytes(int kind, long numel) { return numel * (kind == SLOT_BF16 ? 2 : 4); }
-}  // namespace
-
 ConnectorModel* connector_create(const ConnectorConfig& cfg) {
     LTX_REQUIRE(cfg.dim == cfg.heads * 128, "connector: dim %d must be heads (%d) x 128", cfg.dim, cfg.heads);
     LTX_REQUIRE(cfg.dim % 64 == 0 && cfg.dim <= 8192, "connector: dim %d must be a multiple of 64 and <= 8192", cfg.dim);
@@ -28,70 +17,34 @@ ConnectorModel* connector_create(const ConnectorConfig& cfg) {
     m->cfg = cfg;
     m->blocks.resize(cfg.layers);
     const int D = cfg.dim;
-    std::vector<Pending> pend;
-    auto lin = [&](const std::string& name, LinearW& l, int out, int in) {
-        l.out = out;
-        l.in = in;
-        pend.push_back({name + ".weight", (void**)&l.w, SLOT_BF16, out, in, 0});
-        pend.push_back({name + ".bias", (void**)&l.b, SLOT_F32, out, 0, 0});
-    };
+    ParamTable& pt = m->params;
     m->fe.out = D;
     m->fe.in = D * cfg.states;
-    pend.push_back({"feature_extractor.aggregate_embed.weight", (void**)&m->fe.w, SLOT_BF16, D, (long)D * cfg.states, 0});
-    pend.push_back({"embeddings_connector.learnable_registers", (void**)&m->registers, SLOT_F32, cfg.registers, D, 0});
+    pt.add("feature_extractor.aggregate_embed.weight", (void**)&m->fe.w, SLOT_BF16, D, (long)D * cfg.states);
+    pt.add("embeddings_connector.learnable_registers", (void**)&m->registers, SLOT_F32, cfg.registers, D);
     for (int i = 0; i < cfg.layers; ++i) {
         ConnBlock& b = m->blocks[i];
         const std::string p = "embeddings_connector.transformer_1d_blocks." + std::to_string(i) + ".";
         b.qk.out = 2 * D;
         b.qk.in = D;
-        pend.push_back({p + "attn1.__qk.weight", (void**)&b.qk.w, SLOT_BF16, 2 * D, D, 0});
-        pend.push_back({p + "attn1.__qk.bias", (void**)&b.qk.b, SLOT_F32, 2 * D, 0, 0});
-        lin(p + "attn1.to_v", b.v, D, D);
-        lin(p + "attn1.to_out", b.o, D, D);
-        pend.push_back({p + "attn1.q_norm.weight", (void**)&b.qn, SLOT_F32, D, 0, 1});
-        pend.push_back({p + "attn1.k_norm.weight", (void**)&b.kn, SLOT_F32, D, 0, 1});
-        lin(p + "ff.project_in.proj", b.ff1, 4 * D, D);
-        lin(p + "ff.project_out", b.ff2, D, 4 * D);
+        pt.add_hidden((void**)&b.qk.w, SLOT_BF16, 2 * D, D);
+        pt.add_hidden((void**)&b.qk.b, SLOT_F32, 2 * D, 0);
+        pt.add_linear(p + "attn1.to_v", b.v, D, D);
+        pt.add_linear(p + "attn1.to_out", b.o, D, D);
+        pt.add(p + "attn1.q_norm.weight", (void**)&b.qn, SLOT_F32, D, 0, 1);
+        pt.add(p + "attn1.k_norm.weight", (void**)&b.kn, SLOT_F32, D, 0, 1);
+        pt.add_linear(p + "ff.project_in.proj", b.ff1, 4 * D, D);
+        pt.add_linear(p + "ff.project_out", b.ff2, D, 4 * D);
     }
-    size_t total = 0;
-    for (auto& q : pend) total += DeviceArena::padded(slot_bytes(q.kind, q.rows * (q.cols ? q.cols : 1)));
-    m->weight_bytes = total;
-    m->arena.reserve(total + 256);
-    HIP_CHECK(hipMemset(m->arena.buf.p, 0, m->arena.buf.bytes));
-    for (auto& q : pend) {
-        const long numel = q.rows * (q.cols ? q.cols : 1);
-        *q.dst = m->arena.take(slot_bytes(q.kind, numel));
-        ParamSlot s;
-        s.dst = *q.dst;
-        s.kind = q.kind;
-        s.numel = numel;
-        s.rows = q.rows;
-        s.cols = q.cols;
-        s.init = q.init;
-        m->slots[q.key] = s;
-    }
+    m->weight_bytes = pt.place(false);
     for (int i = 0; i < cfg.layers; ++i) {
         ConnBlock& b = m->blocks[i];
         const std::string p = "embeddings_connector.transformer_1d_blocks." + std::to_string(i) + ".";
-        auto view = [&](const std::string& key, void* dst, int kind, long rows, long cols) {
-            ParamSlot s;
-            s.dst = dst;
-            s.kind = kind;
-            s.rows = rows;
-            s.cols = cols;
-            s.numel = rows * (cols ? cols : 1);
-            m->slots[key] = s;
-        };
-        view(p + "attn1.to_q.weight", b.qk.w, SLOT_BF16, D, D);
-        view(p + "attn1.to_k.weight", b.qk.w + (long)D * D, SLOT_BF16, D, D);
-        view(p + "attn1.to_q.bias", b.qk.b, SLOT_F32, D, 0);
-        view(p + "attn1.to_k.bias", b.qk.b + D, SLOT_F32, D, 0);
-        m->slots.erase(p + "attn1.__qk.weight");
-        m->slots.erase(p + "attn1.__qk.bias");
+        pt.view(p + "attn1.to_q.weight", b.qk.w, SLOT_BF16, D, D);
+        pt.view(p + "attn1.to_k.weight", b.qk.w + (long)D * D, SLOT_BF16, D, D);
+        pt.view(p + "attn1.to_q.bias", b.qk.b, SLOT_F32, D, 0);
+        pt.view(p + "attn1.to_k.bias", b.qk.b + D, SLOT_F32, D, 0);
     }
-    for (auto& kv : m->slots)
-        if (kv.second.init == 1) launch_fill_const_f32((float*)kv.second.dst, kv.second.numel, 1.0f, nullptr);
-    HIP_CHECK(hipDeviceSynchronize());
     return m;
 }
 
@@ -100,58 +53,19 @@ void connector_destroy(ConnectorModel* m) { delete m; }
 void connector_load_safetensors(ltx_ctx* ctx, ConnectorModel* m, const std::string& path) {
     SafeTensors st;
     st.open(path);
-    ctx->n_loaded = ctx->n_missing = ctx->n_unmatched = 0;
-    for (auto& kv : m->slots) kv.second.loaded = false;
-    std::vector<uint8_t> staging;
-    for (auto& kv : st.tensors) {
-        std::string mk;
-        if (!map_text_encoder_file_key(kv.first, &mk)) continue;  // DiT / VAE / audio tensors of a unified file
-        if (mk.compare(0, 26, "audio_embeddings_connector") == 0) continue;
-        auto it = m->slots.find(mk);
-        if (it == m->slots.end()) {
-            ctx->n_unmatched++;
-            continue;
-        }
-        ParamSlot& s = it->second;
-        const StTensor& t = kv.second;
-        if (t.numel() != s.numel)
-            LTX_THROW(LTXS_WEIGHT_LOADING_FAILED, "Failed to load weights: %s has %ld elements, expected %ld", kv.first.c_str(), t.numel(), s.numel);
-        if (s.kind == SLOT_BF16) {
-            staging.resize((size_t)s.numel * 2);
-            st_to_bf16(st, t, (bf16_t*)staging.data());
-        } else {
-            staging.resize((size_t)s.numel * 4);
-            float* f = (float*)staging.data();
-            st_to_f32(st, t, f);
-            for (long i = 0; i < s.numel; ++i) f[i] = host_bf16_to_f32(host_f32_to_bf16(f[i]));
-        }
-        HIP_CHECK(hipMemcpy(s.dst, staging.data(), staging.size(), hipMemcpyHostToDevice));
-        s.loaded = true;
-        ctx->n_loaded++;
-    }
-    for (auto& kv : m->slots)
-        if (!kv.second.loaded) ctx->n_missing++;
+    param_table_load(ctx, m->params, st, [](const std::string& fk, std::string* mk) {
+        // false: DiT / VAE / audio tensors of a unified file, and the audio connector's
+        return map_text_encoder_file_key(fk, mk) && mk->compare(0, 26, "audio_embeddings_connector") != 0;
+    });
 }
 
 void connector_init_synthetic(ltx_ctx* ctx, ConnectorModel* m, uint64_t seed) {
-    uint64_t k = 0;
-    for (auto& kv : m->slots) {
-        ParamSlot& s = kv.second;
-        const uint64_t sd = seed * 0x9E3779B97F4A7C15ull + (++k) * 0xD1B54A32D192ED03ull;
-        const std::string& key = kv.first;
-        const bool is_bias = key.size() > 5 && key.compare(key.size() - 5, 5, ".bias") == 0;
-        const bool is_norm = key.find("_norm.weight") != std::string::npos;
-        const bool is_reg = key.find("learnable_registers") != std::string::npos;
-        const bool is_fe = key.find("aggregate_embed") != std::string::npos;
-        if (s.kind == SLOT_BF16)
-            launch_fill_normal_bf16((bf16_t*)s.dst, s.numel, sd, 0.f, is_fe ? 1.0f / sqrtf((float)m->fe.in) : 0.02f, ctx->stream);
-        else if (is_norm)
-            launch_fill_normal_f32((float*)s.dst, s.numel, sd, 1.0f, 0.02f, 1, ctx->stream);
-        else
-            launch_fill_normal_f32((float*)s.dst, s.numel, sd, 0.f, is_reg ? 0.5f : (is_bias ? 0.01f : 0.02f), 1, ctx->stream);
-        s.loaded = true;
-    }
-    HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    const float fe_std = 1.0f / sqrtf((float)m->fe.in);
+    param_table_fill_synthetic(ctx, m->params, seed, 0, [&](const std::string& key, const ParamSlot& s) -> std::pair<float, float> {
+        if (key.find("aggregate_embed") != std::string::npos) return {0.f, fe_std};
+        if (key.find("learnable_registers") != std::string::npos) return {0.f, 0.5f};
+        return param_fill_rule_default(key, s);
+    });
 }
 
 void connector_encode(ltx_ctx* ctx, ConnectorModel* m, const ConnectorArgs& a) {

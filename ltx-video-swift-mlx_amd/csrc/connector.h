@@ -28,11 +28,10 @@ struct ConnBlock {
 
 struct ConnectorModel {
     ConnectorConfig cfg;
-    DeviceArena arena;
+    ParamTable params;           // one arena
     LinearW fe;                  // aggregate_embed [D][D*states], no bias
     float* registers = nullptr;  // [R][D] f32 (bf16-representable)
     std::vector<ConnBlock> blocks;
-    std::map<std::string, ParamSlot> slots;
     size_t weight_bytes = 0;
     DevBuf rope_cos, rope_sin;  // [T][D/2] f32, values rounded to bf16 (LTXTextEncoder.swift:498)
     int rope_T = 0;

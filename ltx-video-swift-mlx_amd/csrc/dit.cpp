@@ -11,20 +11,6 @@
 #include "linear_ops.h"
 #include "options.h"
 
-namespace {
-
-struct Pending {
-    std::string key;
-    void** dst;
-    int kind;
-    long rows, cols;
-    int init;
-};
-
-long slot_bytes(int kind, long numel) { return numel * (kind == SLOT_BF16 ? 2 : 4); }
-
-}  // namespace
-
 DiTModel* dit_create(const TransformerConfig& cfg) {
     LTX_REQUIRE(cfg.head_dim == 128, "DiT: attention_head_dim must be 128 (got %d)", cfg.head_dim);
     LTX_REQUIRE(cfg.num_layers >= 1 && cfg.num_heads >= 1, "DiT: empty model");
@@ -39,95 +25,49 @@ DiTModel* dit_create(const TransformerConfig& cfg) {
     m->blocks.resize(m->L);
     const int D = m->D;
 
-    std::vector<Pending> pend;
-    auto lin = [&](const std::string& name, LinearW& l, int out, int in, bool fused_rows = false) {
-        l.out = out;
-        l.in = in;
-        if (!fused_rows) {
-            pend.push_back({name + ".weight", (void**)&l.w, SLOT_BF16, out, in, 0});
-            pend.push_back({name + ".bias", (void**)&l.b, SLOT_F32, out, 0, 0});
-        }
-    };
-    auto vec = [&](const std::string& name, float*& p, long rows, long cols, int init) {
-        pend.push_back({name, (void**)&p, SLOT_F32, rows, cols, init});
-    };
-    lin("patchify_proj", m->patchify, D, cfg.in_channels);
-    lin("adaln_single.emb.linear_1", m->ada_l1, D, 256);
-    lin("adaln_single.emb.linear_2", m->ada_l2, D, D);
-    lin("adaln_single.linear", m->ada_lin, 6 * D, D);
-    lin("caption_projection.linear_1", m->cap_l1, D, cfg.caption_channels);
-    lin("caption_projection.linear_2", m->cap_l2, D, D);
-    lin("proj_out", m->proj_out, cfg.out_channels, D);
-    vec("scale_shift_table", m->sst_out, 2, D, 0);
+    ParamTable& pt = m->params;
+    pt.add_linear("patchify_proj", m->patchify, D, cfg.in_channels);
+    pt.add_linear("adaln_single.emb.linear_1", m->ada_l1, D, 256);
+    pt.add_linear("adaln_single.emb.linear_2", m->ada_l2, D, D);
+    pt.add_linear("adaln_single.linear", m->ada_lin, 6 * D, D);
+    pt.add_linear("caption_projection.linear_1", m->cap_l1, D, cfg.caption_channels);
+    pt.add_linear("caption_projection.linear_2", m->cap_l2, D, D);
+    pt.add_linear("proj_out", m->proj_out, cfg.out_channels, D);
+    pt.add("scale_shift_table", (void**)&m->sst_out, SLOT_F32, 2, D);
     // all per-block scale-shift tables live in one [L][6][D] tensor so one kernel builds every layer's modulation
-    pend.push_back({"__sst_blocks", (void**)&m->sst_blocks, SLOT_F32, (long)m->L * 6, D, 0});
+    pt.add_hidden((void**)&m->sst_blocks, SLOT_F32, (long)m->L * 6, D);
     for (int i = 0; i < m->L; ++i) {
         DiTBlock& b = m->blocks[i];
         const std::string p = "transformer_blocks." + std::to_string(i) + ".";
         // attn1: to_q and to_k rows fused into one [2D][D] matrix (+ [2D] bias)
         b.qk1.out = 2 * D;
         b.qk1.in = D;
-        pend.push_back({p + "attn1.__qk.weight", (void**)&b.qk1.w, SLOT_BF16, 2 * D, D, 0});
-        pend.push_back({p + "attn1.__qk.bias", (void**)&b.qk1.b, SLOT_F32, 2 * D, 0, 0});
-        lin(p + "attn1.to_v", b.v1, D, D);
-        lin(p + "attn1.to_out", b.o1, D, D);
-        vec(p + "attn1.q_norm.weight", b.qn1, D, 0, 1);
-        vec(p + "attn1.k_norm.weight", b.kn1, D, 0, 1);
-        lin(p + "attn2.to_q", b.q2, D, D);
-        lin(p + "attn2.to_k", b.k2, D, cfg.cross_attention_dim);
-        lin(p + "attn2.to_v", b.v2, D, cfg.cross_attention_dim);
-        lin(p + "attn2.to_out", b.o2, D, D);
-        vec(p + "attn2.q_norm.weight", b.qn2, D, 0, 1);
-        vec(p + "attn2.k_norm.weight", b.kn2, D, 0, 1);
-        lin(p + "ff.project_in.proj", b.ff1, 4 * D, D);
-        lin(p + "ff.project_out", b.ff2, D, 4 * D);
+        pt.add_hidden((void**)&b.qk1.w, SLOT_BF16, 2 * D, D);
+        pt.add_hidden((void**)&b.qk1.b, SLOT_F32, 2 * D, 0);
+        pt.add_linear(p + "attn1.to_v", b.v1, D, D);
+        pt.add_linear(p + "attn1.to_out", b.o1, D, D);
+        pt.add(p + "attn1.q_norm.weight", (void**)&b.qn1, SLOT_F32, D, 0, 1);
+        pt.add(p + "attn1.k_norm.weight", (void**)&b.kn1, SLOT_F32, D, 0, 1);
+        pt.add_linear(p + "attn2.to_q", b.q2, D, D);
+        pt.add_linear(p + "attn2.to_k", b.k2, D, cfg.cross_attention_dim);
+        pt.add_linear(p + "attn2.to_v", b.v2, D, cfg.cross_attention_dim);
+        pt.add_linear(p + "attn2.to_out", b.o2, D, D);
+        pt.add(p + "attn2.q_norm.weight", (void**)&b.qn2, SLOT_F32, D, 0, 1);
+        pt.add(p + "attn2.k_norm.weight", (void**)&b.kn2, SLOT_F32, D, 0, 1);
+        pt.add_linear(p + "ff.project_in.proj", b.ff1, 4 * D, D);
+        pt.add_linear(p + "ff.project_out", b.ff2, D, 4 * D);
     }
-    size_t total = 0, total_w = 0;
-    for (auto& q : pend) (q.kind == SLOT_BF16 ? total_w : total) += DeviceArena::padded(slot_bytes(q.kind, q.rows * (q.cols ? q.cols : 1)));
-    m->weight_bytes = total + total_w;
-    m->arena.reserve(total + 256);
-    m->warena.reserve(total_w + 256);   // the Linear weights on their own: dit_quantize releases exactly these
-    HIP_CHECK(hipMemset(m->arena.buf.p, 0, m->arena.buf.bytes));
-    HIP_CHECK(hipMemset(m->warena.buf.p, 0, m->warena.buf.bytes));
-    for (auto& q : pend) {
-        const long numel = q.rows * (q.cols ? q.cols : 1);
-        *q.dst = (q.kind == SLOT_BF16 ? m->warena : m->arena).take(slot_bytes(q.kind, numel));
-        ParamSlot s;
-        s.dst = *q.dst;
-        s.kind = q.kind;
-        s.numel = numel;
-        s.rows = q.rows;
-        s.cols = q.cols;
-        s.init = q.init;
-        m->slots[q.key] = s;
-    }
+    m->weight_bytes = pt.place(true);
     // module-key views into the fused tensors (these are the keys files actually carry)
     for (int i = 0; i < m->L; ++i) {
         DiTBlock& b = m->blocks[i];
         const std::string p = "transformer_blocks." + std::to_string(i) + ".";
-        auto view = [&](const std::string& key, void* dst, int kind, long rows, long cols, int init) {
-            ParamSlot s;
-            s.dst = dst;
-            s.kind = kind;
-            s.rows = rows;
-            s.cols = cols;
-            s.numel = rows * (cols ? cols : 1);
-            s.init = init;
-            m->slots[key] = s;
-        };
-        view(p + "attn1.to_q.weight", b.qk1.w, SLOT_BF16, D, D, 0);
-        view(p + "attn1.to_k.weight", b.qk1.w + (long)D * D, SLOT_BF16, D, D, 0);
-        view(p + "attn1.to_q.bias", b.qk1.b, SLOT_F32, D, 0, 0);
-        view(p + "attn1.to_k.bias", b.qk1.b + D, SLOT_F32, D, 0, 0);
-        view(p + "scale_shift_table", m->sst_blocks + (long)i * 6 * D, SLOT_F32, 6, D, 0);
-        m->slots.erase(p + "attn1.__qk.weight");
-        m->slots.erase(p + "attn1.__qk.bias");
+        pt.view(p + "attn1.to_q.weight", b.qk1.w, SLOT_BF16, D, D);
+        pt.view(p + "attn1.to_k.weight", b.qk1.w + (long)D * D, SLOT_BF16, D, D);
+        pt.view(p + "attn1.to_q.bias", b.qk1.b, SLOT_F32, D, 0);
+        pt.view(p + "attn1.to_k.bias", b.qk1.b + D, SLOT_F32, D, 0);
+        pt.view(p + "scale_shift_table", m->sst_blocks + (long)i * 6 * D, SLOT_F32, 6, D);
     }
-    m->slots.erase("__sst_blocks");
-    // reference initialisers for parameters a file may omit: RMSNorm weights = 1 (LTXAttention.swift:18)
-    for (auto& kv : m->slots)
-        if (kv.second.init == 1) launch_fill_const_f32((float*)kv.second.dst, kv.second.numel, 1.0f, nullptr);
-    HIP_CHECK(hipDeviceSynchronize());
     return m;
 }
 
@@ -137,61 +77,14 @@ void dit_load_safetensors(ltx_ctx* ctx, DiTModel* m, const std::string& path) {
     LTX_REQUIRE(m->quant_bits == 16, "weights cannot be loaded into a quantised model");
     SafeTensors st;
     st.open(path);
-    ctx->n_loaded = ctx->n_missing = ctx->n_unmatched = 0;
-    for (auto& kv : m->slots) kv.second.loaded = false;
-    std::vector<uint8_t> staging;
-    for (auto& kv : st.tensors) {
-        std::string mk;
-        if (!map_transformer_file_key(kv.first, &mk)) continue;
-        auto it = m->slots.find(mk);
-        if (it == m->slots.end()) {
-            ctx->n_unmatched++;  // silently dropped by the reference (ModelDownloader.swift:992-1003)
-            continue;
-        }
-        ParamSlot& s = it->second;
-        const StTensor& t = kv.second;
-        if (t.numel() != s.numel)
-            LTX_THROW(LTXS_WEIGHT_LOADING_FAILED, "Failed to load weights: %s has %ld elements, expected %ld", kv.first.c_str(), t.numel(), s.numel);
-        if (s.kind == SLOT_BF16) {
-            staging.resize((size_t)s.numel * 2);
-            st_to_bf16(st, t, (bf16_t*)staging.data());
-        } else {
-            // every f32 parameter is cast to bf16 when applied (ModelDownloader.swift:1005-1012); keep the
-            // bf16-rounded value in an f32 container
-            staging.resize((size_t)s.numel * 4);
-            float* f = (float*)staging.data();
-            st_to_f32(st, t, f);
-            for (long i = 0; i < s.numel; ++i) f[i] = host_bf16_to_f32(host_f32_to_bf16(f[i]));
-        }
-        HIP_CHECK(hipMemcpy(s.dst, staging.data(), staging.size(), hipMemcpyHostToDevice));
-        s.loaded = true;
-        ctx->n_loaded++;
-    }
-    for (auto& kv : m->slots)
-        if (!kv.second.loaded) ctx->n_missing++;
+    param_table_load(ctx, m->params, st, map_transformer_file_key);  // missing parameters keep their initialisers: ltx_load_report
     for (auto* c : m->ctx_cache) c->version = 0;
 }
 
 void dit_init_synthetic(ltx_ctx* ctx, DiTModel* m, uint64_t seed) {
     // Linear weights N(0,0.02^2), biases N(0,0.01^2), q/k norm weights 1+N(0,0.02^2),
     // scale-shift tables N(0,0.02^2); everything rounded to bf16 once.
-    uint64_t k = 0;
-    for (auto& kv : m->slots) {
-        ParamSlot& s = kv.second;
-        const uint64_t sd = seed * 0x9E3779B97F4A7C15ull + (++k) * 0xD1B54A32D192ED03ull;
-        const std::string& key = kv.first;
-        const bool is_bias = key.size() > 5 && key.compare(key.size() - 5, 5, ".bias") == 0;
-        const bool is_norm = key.find("_norm.weight") != std::string::npos;
-        if (s.kind == SLOT_BF16) {
-            launch_fill_normal_bf16((bf16_t*)s.dst, s.numel, sd, 0.f, 0.02f, ctx->stream);
-        } else if (is_norm) {
-            launch_fill_normal_f32((float*)s.dst, s.numel, sd, 1.0f, 0.02f, 1, ctx->stream);
-        } else {
-            launch_fill_normal_f32((float*)s.dst, s.numel, sd, 0.f, is_bias ? 0.01f : 0.02f, 1, ctx->stream);
-        }
-        s.loaded = true;
-    }
-    HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    param_table_fill_synthetic(ctx, m->params, seed, 0, param_fill_rule_default);
     for (auto* c : m->ctx_cache) c->version = 0;
 }
 
@@ -200,19 +93,13 @@ void dit_export_slot(ltx_ctx* ctx, DiTModel* m, const ParamSlot& s, float* out) 
         DevBuf tmp;
         tmp.ensure((size_t)s.numel * 2);
         launch_dequant(s.q, s.qs, s.qb, s.rows, s.cols, m->quant_bits, tmp.as<bf16_t>(), ctx->stream);
-        HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        std::vector<bf16_t> h((size_t)s.numel);
-        HIP_CHECK(hipMemcpy(h.data(), tmp.p, (size_t)s.numel * 2, hipMemcpyDeviceToHost));
-        for (long i = 0; i < s.numel; ++i) out[i] = host_bf16_to_f32(h[i]);
+        ParamSlot d;
+        d.dst = tmp.p;
+        d.numel = s.numel;
+        param_export(ctx, d, out);
         return;
     }
-    if (s.kind == SLOT_F32) {
-        HIP_CHECK(hipMemcpy(out, s.dst, (size_t)s.numel * 4, hipMemcpyDeviceToHost));
-        return;
-    }
-    std::vector<bf16_t> h((size_t)s.numel);
-    HIP_CHECK(hipMemcpy(h.data(), s.dst, (size_t)s.numel * 2, hipMemcpyDeviceToHost));
-    for (long i = 0; i < s.numel; ++i) out[i] = host_bf16_to_f32(h[i]);
+    param_export(ctx, s, out);
 }
 
 // ---------------------------------------------------------------------------------------------------------------

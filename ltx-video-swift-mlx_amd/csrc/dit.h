@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "hostmath.h"
+#include "params.h"
 #include "runtime.h"
 
 // One scratch matrix for the weights of the GEMM that is about to run on a quantised model (largest Linear: 16384 x 4096 bf16).
@@ -42,33 +43,16 @@ struct DiTBlock {
     bool skip_ff = false;
 };
 
-enum SlotKind { SLOT_BF16 = 0, SLOT_F32 = 1 };
-struct ParamSlot {
-    // quantised model: the slot of a Linear weight points at its codes / scales / biases instead of dst (rows of a fused matrix
-    // are row offsets into all three)
-    uint8_t* q = nullptr;
-    bf16_t* qs = nullptr;
-    bf16_t* qb = nullptr;
-    void* dst = nullptr;
-    int kind = SLOT_BF16;
-    long numel = 0;
-    long rows = 0, cols = 0;  // expected shape (cols = 0 -> vector)
-    int init = 0;             // 0: zeros, 1: ones (reference initialisers for parameters absent from the file)
-    bool loaded = false;
-};
-
 struct DiTModel {
     TransformerConfig cfg;
     int D = 0, L = 0;
-    DeviceArena arena;    // biases, norm weights, scale-shift tables (f32)
-    DeviceArena warena;   // Linear weights, bf16 (26.07 GB at the reference architecture); released by dit_quantize
+    ParamTable params;    // module key -> destination; params.warena: the Linear weights, bf16 (26.07 GB at the reference architecture)
     DeviceArena qarena;   // after dit_quantize: codes + group scales / biases (13.9 GB at 8 bits, 7.3 GB at 4)
     DequantScratch dq;
     LinearW patchify, ada_l1, ada_l2, ada_lin, cap_l1, cap_l2, proj_out;
     float* sst_blocks = nullptr;  // [L][6][D]
     float* sst_out = nullptr;     // [2][D]
     std::vector<DiTBlock> blocks;
-    std::map<std::string, ParamSlot> slots;  // module key -> destination
     size_t weight_bytes = 0;
     int quant_bits = 16;  // 16 (bf16), 8 or 4 after dit_quantize
 

@@ -12,30 +12,6 @@
 
 namespace {
 
-long slot_bytes(int kind, long numel) { return numel * (kind == SLOT_BF16 ? 2 : 4); }
-
-struct Pending {
-    std::string key;
-    void** dst;
-    int kind;
-    long rows, cols;
-};
-
-// the module spelling of a checkpoint key (mapTransformerKey, ModelDownloader.swift:790-800; the scale_shift_table_a2v_ca_* names are
-// the same on both sides)
-std::string module_spelling(std::string k) {
-    auto sub = [&](const char* from, const char* to) {
-        const size_t n = strlen(from);
-        for (size_t at = k.find(from); at != std::string::npos; at = k.find(from, at + strlen(to))) k.replace(at, n, to);
-    };
-    sub(".norm_q.", ".q_norm.");
-    sub(".norm_k.", ".k_norm.");
-    sub(".to_out.0.", ".to_out.");
-    sub("ff.net.0.proj.", "ff.project_in.proj.");
-    sub("ff.net.2.", "ff.project_out.");
-    return k;
-}
-
 void destroy_blocks(DualStack* m) {
     for (DualBlock& b : m->blocks)
         for (AttnModule** a : {&b.attn1, &b.attn2, &b.audio_attn1, &b.audio_attn2, &b.a2v, &b.v2a}) {
@@ -67,17 +43,11 @@ DualStack* dual_create(const DualBlockConfig& cfg) {
         m->L = cfg.num_layers;
         const int L = m->L, Dv = m->Dv = cfg.video_dim, Da = m->Da = cfg.audio_dim;
         m->blocks.resize(L);
-        std::vector<Pending> pend;
-        auto lin = [&](const std::string& name, LinearW& l, int out, int in) {
-            l.out = out;
-            l.in = in;
-            pend.push_back({name + ".weight", (void**)&l.w, SLOT_BF16, out, in});
-            pend.push_back({name + ".bias", (void**)&l.b, SLOT_F32, out, 0});
-        };
-        pend.push_back({"__sst_v", (void**)&m->sst_v, SLOT_F32, (long)L * 6, Dv});
-        pend.push_back({"__sst_a", (void**)&m->sst_a, SLOT_F32, (long)L * 6, Da});
-        pend.push_back({"__sst_ca_v", (void**)&m->sst_ca_v, SLOT_F32, (long)L * 5, Dv});
-        pend.push_back({"__sst_ca_a", (void**)&m->sst_ca_a, SLOT_F32, (long)L * 5, Da});
+        ParamTable& pt = m->params;
+        pt.add_hidden((void**)&m->sst_v, SLOT_F32, (long)L * 6, Dv);
+        pt.add_hidden((void**)&m->sst_a, SLOT_F32, (long)L * 6, Da);
+        pt.add_hidden((void**)&m->sst_ca_v, SLOT_F32, (long)L * 5, Dv);
+        pt.add_hidden((void**)&m->sst_ca_a, SLOT_F32, (long)L * 5, Da);
         for (int i = 0; i < L; ++i) {
             DualBlock& b = m->blocks[i];
             const std::string p = "transformer_blocks." + std::to_string(i) + ".";
@@ -92,45 +62,21 @@ DualStack* dual_create(const DualBlockConfig& cfg) {
                                                                  {"audio_to_video_attn.", b.a2v}, {"video_to_audio_attn.", b.v2a}};
             for (auto& mm : mods) {
                 mm.second->eps = cfg.norm_eps;
-                for (auto& kv : mm.second->slots) m->slots[p + mm.first + kv.first] = kv.second;
+                for (auto& kv : mm.second->params.slots) pt.slots[p + mm.first + kv.first] = kv.second;
             }
-            lin(p + "ff.project_in.proj", b.ff1, 4 * Dv, Dv);
-            lin(p + "ff.project_out", b.ff2, Dv, 4 * Dv);
-            lin(p + "audio_ff.project_in.proj", b.aff1, 4 * Da, Da);
-            lin(p + "audio_ff.project_out", b.aff2, Da, 4 * Da);
+            pt.add_linear(p + "ff.project_in.proj", b.ff1, 4 * Dv, Dv);
+            pt.add_linear(p + "ff.project_out", b.ff2, Dv, 4 * Dv);
+            pt.add_linear(p + "audio_ff.project_in.proj", b.aff1, 4 * Da, Da);
+            pt.add_linear(p + "audio_ff.project_out", b.aff2, Da, 4 * Da);
         }
-        size_t total = 0, total_w = 0;
-        for (auto& q : pend) (q.kind == SLOT_BF16 ? total_w : total) += DeviceArena::padded(slot_bytes(q.kind, q.rows * (q.cols ? q.cols : 1)));
-        m->arena.reserve(total + 256);
-        m->warena.reserve(total_w + 256);
-        HIP_CHECK(hipMemset(m->arena.buf.p, 0, m->arena.buf.bytes));
-        HIP_CHECK(hipMemset(m->warena.buf.p, 0, m->warena.buf.bytes));
-        for (auto& q : pend) {
-            ParamSlot s;
-            s.kind = q.kind;
-            s.rows = q.rows;
-            s.cols = q.cols;
-            s.numel = q.rows * (q.cols ? q.cols : 1);
-            s.dst = *q.dst = (q.kind == SLOT_BF16 ? m->warena : m->arena).take(slot_bytes(q.kind, s.numel));
-            if (q.key.compare(0, 2, "__") != 0) m->slots[q.key] = s;
-        }
+        pt.place(true);
         for (int i = 0; i < L; ++i) {  // per-block views into the four stacked tables
             const std::string p = "transformer_blocks." + std::to_string(i) + ".";
-            auto view = [&](const char* key, float* dst, long rows, long cols) {
-                ParamSlot s;
-                s.dst = dst;
-                s.kind = SLOT_F32;
-                s.rows = rows;
-                s.cols = cols;
-                s.numel = rows * cols;
-                m->slots[p + key] = s;
-            };
-            view("scale_shift_table", m->sst_v + (long)i * 6 * Dv, 6, Dv);
-            view("audio_scale_shift_table", m->sst_a + (long)i * 6 * Da, 6, Da);
-            view("scale_shift_table_a2v_ca_video", m->sst_ca_v + (long)i * 5 * Dv, 5, Dv);
-            view("scale_shift_table_a2v_ca_audio", m->sst_ca_a + (long)i * 5 * Da, 5, Da);
+            pt.view(p + "scale_shift_table", m->sst_v + (long)i * 6 * Dv, SLOT_F32, 6, Dv);
+            pt.view(p + "audio_scale_shift_table", m->sst_a + (long)i * 6 * Da, SLOT_F32, 6, Da);
+            pt.view(p + "scale_shift_table_a2v_ca_video", m->sst_ca_v + (long)i * 5 * Dv, SLOT_F32, 5, Dv);
+            pt.view(p + "scale_shift_table_a2v_ca_audio", m->sst_ca_a + (long)i * 5 * Da, SLOT_F32, 5, Da);
         }
-        HIP_CHECK(hipDeviceSynchronize());
     } catch (...) {
         delete m;
         throw;
@@ -142,87 +88,32 @@ void dual_destroy(DualStack* m) { delete m; }
 
 void dual_init_synthetic(ltx_ctx* ctx, DualStack* m, uint64_t seed) {
     // Linear weights N(0, 0.02^2), biases N(0, 0.01^2), q / k norm weights 1 + N(0, 0.02^2), scale-shift tables N(0, 0.02^2); bf16 values
-    uint64_t k = 0;
-    for (auto& kv : m->slots) {
-        ParamSlot& s = kv.second;
-        const uint64_t sd = seed * 0x9E3779B97F4A7C15ull + (++k) * 0xD1B54A32D192ED03ull;
-        const std::string& key = kv.first;
-        const bool is_bias = key.size() > 5 && key.compare(key.size() - 5, 5, ".bias") == 0;
-        const bool is_norm = key.find("_norm.weight") != std::string::npos;
-        if (s.kind == SLOT_BF16)
-            launch_fill_normal_bf16((bf16_t*)s.dst, s.numel, sd, 0.f, 0.02f, ctx->stream);
-        else
-            launch_fill_normal_f32((float*)s.dst, s.numel, sd, is_norm ? 1.0f : 0.f, is_bias ? 0.01f : 0.02f, 1, ctx->stream);
-        s.loaded = true;
-    }
-    HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    param_table_fill_synthetic(ctx, m->params, seed, 0, param_fill_rule_default);
 }
 
 void dual_load(ltx_ctx* ctx, DualStack* m, const std::string& path, int first_block) {
     if (first_block < 0) LTX_THROW(LTXS_INVALID_CONFIGURATION, "dual blocks: first_block %d", first_block);
     SafeTensors st;
     st.open(path);
-    ctx->n_loaded = ctx->n_missing = ctx->n_unmatched = 0;
-    for (auto& kv : m->slots) kv.second.loaded = false;
-    std::vector<uint8_t> staging;
     const std::string tb = "transformer_blocks.";
-    for (auto& kv : st.tensors) {
-        const std::string& fk = kv.first;
-        if (fk.compare(0, tb.size(), tb) != 0) continue;
+    // "transformer_blocks.{first_block + i}.x" of the file is block i of this stack; other blocks and top-level keys are not its own
+    const std::string first_missing = param_table_load(ctx, m->params, st, [&](const std::string& fk, std::string* mk) {
+        if (fk.compare(0, tb.size(), tb) != 0) return false;
         const size_t dot = fk.find('.', tb.size());
-        if (dot == std::string::npos || dot == tb.size() || dot - tb.size() > 6) continue;
+        if (dot == std::string::npos || dot == tb.size() || dot - tb.size() > 6) return false;
         int idx = 0;
         bool digits = true;
         for (size_t i = tb.size(); i < dot; ++i) {
             digits = digits && fk[i] >= '0' && fk[i] <= '9';
             idx = idx * 10 + (fk[i] - '0');
         }
-        if (!digits || idx < first_block || idx >= first_block + m->L) continue;  // another block of the file: not this stack's
-        const std::string mk = tb + std::to_string(idx - first_block) + module_spelling(fk.substr(dot));
-        auto it = m->slots.find(mk);
-        if (it == m->slots.end()) {
-            ctx->n_unmatched++;  // e.g. the weights of the eight RMSNorm modules: no weight is applied
-            continue;
-        }
-        ParamSlot& s = it->second;
-        const StTensor& t = kv.second;
-        const bool shape_ok = t.numel() == s.numel && (!(s.cols && t.shape.size() == 2) || (t.shape[0] == s.rows && t.shape[1] == s.cols));
-        if (!shape_ok)
-            LTX_THROW(LTXS_WEIGHT_LOADING_FAILED, "Failed to load weights: %s has %ld elements, expected [%ld, %ld]", fk.c_str(), t.numel(), s.rows, s.cols);
-        if (s.kind == SLOT_BF16) {
-            staging.resize((size_t)s.numel * 2);
-            st_to_bf16(st, t, (bf16_t*)staging.data());
-        } else {  // biases, norm weights and tables are bf16 in the file: f32 copies of those values
-            staging.resize((size_t)s.numel * 4);
-            float* f = (float*)staging.data();
-            st_to_f32(st, t, f);
-            for (long i = 0; i < s.numel; ++i) f[i] = host_bf16_to_f32(host_f32_to_bf16(f[i]));
-        }
-        HIP_CHECK(hipMemcpy(s.dst, staging.data(), staging.size(), hipMemcpyHostToDevice));
-        if (!s.loaded) ctx->n_loaded++;
-        s.loaded = true;
-    }
-    const std::string* first_missing = nullptr;
-    for (auto& kv : m->slots)
-        if (!kv.second.loaded) {
-            ctx->n_missing++;
-            if (!first_missing) first_missing = &kv.first;
-        }
-    if (first_missing)
-        LTX_THROW(LTXS_WEIGHT_LOADING_FAILED, "Failed to load weights: %s (block %d of the file) and %d more are not in %s", first_missing->c_str(),
+        if (!digits || idx < first_block || idx >= first_block + m->L) return false;
+        *mk = tb + std::to_string(idx - first_block) + transformer_module_spelling(fk.substr(dot));
+        return true;
+    });
+    if (!first_missing.empty())
+        LTX_THROW(LTXS_WEIGHT_LOADING_FAILED, "Failed to load weights: %s (block %d of the file) and %d more are not in %s", first_missing.c_str(),
                   first_block, ctx->n_missing - 1, path.c_str());
-}
-
-void dual_export(ltx_ctx* ctx, DualStack* m, const ParamSlot& s, float* out) {
-    (void)m;
-    HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    if (s.kind == SLOT_F32) {
-        HIP_CHECK(hipMemcpy(out, s.dst, (size_t)s.numel * 4, hipMemcpyDeviceToHost));
-        return;
-    }
-    std::vector<bf16_t> h((size_t)s.numel);
-    HIP_CHECK(hipMemcpy(h.data(), s.dst, (size_t)s.numel * 2, hipMemcpyDeviceToHost));
-    for (long i = 0; i < s.numel; ++i) out[i] = host_bf16_to_f32(h[i]);
 }
 
 // ---------------------------------------------------------------------------------------------------------------

@@ -93,15 +93,14 @@ struct DualTextCache {
 struct DualStack {
     DualBlockConfig cfg;
     int L = 0, Dv = 0, Da = 0;
-    DeviceArena arena;   // FFN biases and the four scale-shift tables (f32)
-    DeviceArena warena;  // FFN weights (bf16)
     // [L][6][Dv], [L][6][Da], [L][5][Dv], [L][5][Da]: one tensor per kind so that one launch builds every block's modulation rows
     float* sst_v = nullptr;
     float* sst_a = nullptr;
     float* sst_ca_v = nullptr;
     float* sst_ca_a = nullptr;
     std::vector<DualBlock> blocks;
-    std::map<std::string, ParamSlot> slots;  // "transformer_blocks.{i}.attn1.to_q.weight", ... (module spelling, i from 0)
+    // params.arena: FFN biases and the four scale-shift tables (f32); params.warena: FFN weights (bf16); the attention modules own theirs
+    ParamTable params;  // "transformer_blocks.{i}.attn1.to_q.weight", ... (module spelling, i from 0)
 
     // RoPE tables, cached per (F, H, W) / T_a
     DevBuf rope_v_cos, rope_v_sin, rope_a_cos, rope_a_sin, rope_cv_cos, rope_cv_sin, rope_ca_cos, rope_ca_sin;
@@ -125,7 +124,6 @@ void dual_init_synthetic(ltx_ctx* ctx, DualStack* m, uint64_t seed);
 // both accepted (to_out.0, norm_q / norm_k, ff.net.0.proj / ff.net.2: ModelDownloader.swift:756-803). Fills the load report; a tensor
 // the stack needs and the file lacks is weightLoadingFailed.
 void dual_load(ltx_ctx* ctx, DualStack* m, const std::string& path, int first_block);
-void dual_export(ltx_ctx* ctx, DualStack* m, const ParamSlot& s, float* out);
 
 struct DualForwardArgs {
     float* x_video = nullptr;              // [B][F*H*W][Dv] f32, in place

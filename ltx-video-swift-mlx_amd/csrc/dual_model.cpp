@@ -12,27 +12,6 @@
 
 namespace {
 
-struct Pending {
-    std::string key;
-    void** dst;
-    int kind;
-    long rows, cols;
-};
-
-// the module spelling of a top-level checkpoint key (mapTransformerKey(includeAudio: true), ModelDownloader.swift:772-788)
-std::string module_spelling(std::string k) {
-    auto starts = [&](const char* p) { return k.compare(0, strlen(p), p) == 0; };
-    if (starts("proj_in.")) k = "patchify_proj." + k.substr(strlen("proj_in."));
-    if (starts("time_embed.emb.timestep_embedder."))
-        k = "adaln_single.emb." + k.substr(strlen("time_embed.emb.timestep_embedder."));
-    else if (starts("time_embed.linear."))
-        k = "adaln_single." + k.substr(strlen("time_embed."));
-    const char* from = ".emb.timestep_embedder.";
-    const char* to = ".emb.";
-    for (size_t at = k.find(from); at != std::string::npos; at = k.find(from, at + strlen(to))) k.replace(at, strlen(from), to);
-    return k;
-}
-
 // offsets (in floats) of embedder j's [B][D] rows inside ws_h1 / ws_h2
 long stage_offset(const DualModel* m, int j, int B) {
     long off = 0;
@@ -118,15 +97,9 @@ DualModel* dual_model_create(const DualModelConfig& cfg) {
         m->stack = dual_create(bc);  // validates the block config
         m->cfg = cfg;
         const int Dv = m->Dv = bc.video_dim, Da = m->Da = bc.audio_dim;
-        std::vector<Pending> pend;
-        auto lin = [&](const std::string& name, LinearW& l, int out, int in) {
-            l.out = out;
-            l.in = in;
-            pend.push_back({name + ".weight", (void**)&l.w, SLOT_BF16, out, in});
-            pend.push_back({name + ".bias", (void**)&l.b, SLOT_F32, out, 0});
-        };
-        lin("patchify_proj", m->patchify, Dv, cfg.in_channels);
-        lin("audio_patchify_proj", m->audio_patchify, Da, cfg.audio_in_channels);
+        ParamTable& pt = m->params;
+        pt.add_linear("patchify_proj", m->patchify, Dv, cfg.in_channels);
+        pt.add_linear("audio_patchify_proj", m->audio_patchify, Da, cfg.audio_in_channels);
         const struct { const char* name; int n; bool audio; } embs[kDualEmbedders] = {
             {"adaln_single", 6, false},
             {"audio_adaln_single", 6, true},
@@ -140,34 +113,19 @@ DualModel* dual_model_create(const DualModelConfig& cfg) {
             e.n = embs[j].n;
             e.audio = embs[j].audio;
             const int D = e.audio ? Da : Dv;
-            lin(std::string(e.name) + ".emb.linear_1", e.l1, D, 256);
-            lin(std::string(e.name) + ".emb.linear_2", e.l2, D, D);
-            lin(std::string(e.name) + ".linear", e.lin, e.n * D, D);
+            pt.add_linear(std::string(e.name) + ".emb.linear_1", e.l1, D, 256);
+            pt.add_linear(std::string(e.name) + ".emb.linear_2", e.l2, D, D);
+            pt.add_linear(std::string(e.name) + ".linear", e.lin, e.n * D, D);
         }
-        lin("caption_projection.linear_1", m->cap1, Dv, cfg.caption_channels);
-        lin("caption_projection.linear_2", m->cap2, Dv, Dv);
-        lin("audio_caption_projection.linear_1", m->acap1, Da, cfg.caption_channels);
-        lin("audio_caption_projection.linear_2", m->acap2, Da, Da);
-        pend.push_back({"scale_shift_table", (void**)&m->sst_out_v, SLOT_F32, 2, Dv});
-        pend.push_back({"audio_scale_shift_table", (void**)&m->sst_out_a, SLOT_F32, 2, Da});
-        lin("proj_out", m->proj_out, cfg.out_channels, Dv);
-        lin("audio_proj_out", m->audio_proj_out, cfg.audio_out_channels, Da);
-        size_t total = 0, total_w = 0;
-        for (auto& q : pend) (q.kind == SLOT_BF16 ? total_w : total) += DeviceArena::padded((q.kind == SLOT_BF16 ? 2 : 4) * q.rows * (q.cols ? q.cols : 1));
-        m->arena.reserve(total + 256);
-        m->warena.reserve(total_w + 256);
-        HIP_CHECK(hipMemset(m->arena.buf.p, 0, m->arena.buf.bytes));
-        HIP_CHECK(hipMemset(m->warena.buf.p, 0, m->warena.buf.bytes));
-        for (auto& q : pend) {
-            ParamSlot s;
-            s.kind = q.kind;
-            s.rows = q.rows;
-            s.cols = q.cols;
-            s.numel = q.rows * (q.cols ? q.cols : 1);
-            s.dst = *q.dst = (q.kind == SLOT_BF16 ? m->warena : m->arena).take((q.kind == SLOT_BF16 ? 2 : 4) * s.numel);
-            m->slots[q.key] = s;
-        }
-        HIP_CHECK(hipDeviceSynchronize());
+        pt.add_linear("caption_projection.linear_1", m->cap1, Dv, cfg.caption_channels);
+        pt.add_linear("caption_projection.linear_2", m->cap2, Dv, Dv);
+        pt.add_linear("audio_caption_projection.linear_1", m->acap1, Da, cfg.caption_channels);
+        pt.add_linear("audio_caption_projection.linear_2", m->acap2, Da, Da);
+        pt.add("scale_shift_table", (void**)&m->sst_out_v, SLOT_F32, 2, Dv);
+        pt.add("audio_scale_shift_table", (void**)&m->sst_out_a, SLOT_F32, 2, Da);
+        pt.add_linear("proj_out", m->proj_out, cfg.out_channels, Dv);
+        pt.add_linear("audio_proj_out", m->audio_proj_out, cfg.audio_out_channels, Da);
+        pt.place(true);
     } catch (...) {
         delete m;
         throw;
@@ -181,72 +139,31 @@ void dual_model_init_synthetic(ltx_ctx* ctx, DualModel* m, uint64_t seed) {
     dual_init_synthetic(ctx, m->stack, seed);
     // the stack's distributions: Linear weights N(0, 0.02^2), biases N(0, 0.01^2), tables N(0, 0.02^2); bf16 values. A stream of seeds of
     // its own (the stack counts its slots from 1)
-    uint64_t k = 1u << 20;
-    for (auto& kv : m->slots) {
-        ParamSlot& s = kv.second;
-        const uint64_t sd = seed * 0x9E3779B97F4A7C15ull + (++k) * 0xD1B54A32D192ED03ull;
-        const std::string& key = kv.first;
-        const bool is_bias = key.size() > 5 && key.compare(key.size() - 5, 5, ".bias") == 0;
-        if (s.kind == SLOT_BF16)
-            launch_fill_normal_bf16((bf16_t*)s.dst, s.numel, sd, 0.f, 0.02f, ctx->stream);
-        else
-            launch_fill_normal_f32((float*)s.dst, s.numel, sd, 0.f, is_bias ? 0.01f : 0.02f, 1, ctx->stream);
-        s.loaded = true;
-    }
-    HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    param_table_fill_synthetic(ctx, m->params, seed, 1u << 20, param_fill_rule_default);
 }
 
 void dual_model_load(ltx_ctx* ctx, DualModel* m, const std::string& path) {
     dual_load(ctx, m->stack, path, 0);  // the blocks; starts the load report; throws on a missing block parameter
     SafeTensors st;
     st.open(path);
-    for (auto& kv : m->slots) kv.second.loaded = false;
-    std::vector<uint8_t> staging;
-    const std::string tb = "transformer_blocks.";
-    for (auto& kv : st.tensors) {
-        const std::string& fk = kv.first;
-        if (fk.compare(0, tb.size(), tb) == 0) continue;  // dual_load has seen it
-        // a file that holds two spellings of one parameter (proj_in.weight and patchify_proj.weight) is accepted, the later key in
-        // map order wins and the parameter counts once: the reference's mapped dictionary behaves the same way
-        auto it = m->slots.find(module_spelling(fk));
-        if (it == m->slots.end()) {
-            ctx->n_unmatched++;  // e.g. norm_out.weight: LayerNorm(affine: false) has none
-            continue;
-        }
-        ParamSlot& s = it->second;
-        const StTensor& t = kv.second;
-        const bool shape_ok = t.numel() == s.numel && (!(s.cols && t.shape.size() == 2) || (t.shape[0] == s.rows && t.shape[1] == s.cols));
-        if (!shape_ok)
-            LTX_THROW(LTXS_WEIGHT_LOADING_FAILED, "Failed to load weights: %s has %ld elements, expected [%ld, %ld]", fk.c_str(), t.numel(), s.rows, s.cols);
-        if (s.kind == SLOT_BF16) {
-            staging.resize((size_t)s.numel * 2);
-            st_to_bf16(st, t, (bf16_t*)staging.data());
-        } else {  // biases and tables are bf16 in the file: f32 copies of those values
-            staging.resize((size_t)s.numel * 4);
-            float* f = (float*)staging.data();
-            st_to_f32(st, t, f);
-            for (long i = 0; i < s.numel; ++i) f[i] = host_bf16_to_f32(host_f32_to_bf16(f[i]));
-        }
-        HIP_CHECK(hipMemcpy(s.dst, staging.data(), staging.size(), hipMemcpyHostToDevice));
-        if (!s.loaded) ctx->n_loaded++;
-        s.loaded = true;
-    }
-    const std::string* first_missing = nullptr;
-    for (auto& kv : m->slots)
-        if (!kv.second.loaded) {
-            ctx->n_missing++;
-            if (!first_missing) first_missing = &kv.first;
-        }
-    if (first_missing)
-        LTX_THROW(LTXS_WEIGHT_LOADING_FAILED, "Failed to load weights: %s and %d more are not in %s", first_missing->c_str(), ctx->n_missing - 1,
+    // a file that holds two spellings of one parameter (proj_in.weight and patchify_proj.weight) is accepted, the later key in
+    // map order wins and the parameter counts once: the reference's mapped dictionary behaves the same way
+    const std::string first_missing = param_table_load(
+        ctx, m->params, st,
+        [](const std::string& fk, std::string* mk) {
+            if (fk.compare(0, 19, "transformer_blocks.") == 0) return false;  // dual_load has seen it
+            *mk = transformer_module_spelling(fk);
+            return true;
+        },
+        true);
+    if (!first_missing.empty())
+        LTX_THROW(LTXS_WEIGHT_LOADING_FAILED, "Failed to load weights: %s and %d more are not in %s", first_missing.c_str(), ctx->n_missing - 1,
                   path.c_str());
 }
 
 const ParamSlot* dual_model_find(const DualModel* m, const std::string& name) {
-    auto it = m->slots.find(name);
-    if (it != m->slots.end()) return &it->second;
-    auto ib = m->stack->slots.find(name);
-    return ib != m->stack->slots.end() ? &ib->second : nullptr;
+    const ParamSlot* s = m->params.find(name);
+    return s ? s : m->stack->params.find(name);
 }
 
 void dual_model_embed(ltx_ctx* ctx, DualModel* m, const float* video_ts, const float* audio_ts, int B, bool ungrouped, const DualEmbedOut& o) {

@@ -70,13 +70,11 @@ struct DualModel {
     DualModelConfig cfg;
     int Dv = 0, Da = 0;
     DualStack* stack = nullptr;
-    DeviceArena arena;   // biases and the two output tables (f32)
-    DeviceArena warena;  // Linear weights (bf16)
     LinearW patchify, audio_patchify, cap1, cap2, acap1, acap2, proj_out, audio_proj_out;
     DualEmbedder emb[kDualEmbedders];  // adaln_single, audio_adaln_single, av_ca_video_scale_shift, av_ca_a2v_gate, av_ca_audio_scale_shift, av_ca_v2a_gate
     float* sst_out_v = nullptr;  // [2][Dv]: row 0 shift, row 1 scale
     float* sst_out_a = nullptr;  // [2][Da]
-    std::map<std::string, ParamSlot> slots;  // the top-level parameters by module key; the blocks' are stack->slots
+    ParamTable params;  // the top-level parameters by module key (arena: biases and the two output tables; warena: Linear weights); the blocks' are stack->params
 
     // scratch
     DevBuf ws_xv, ws_xa;                              // f32 residual streams

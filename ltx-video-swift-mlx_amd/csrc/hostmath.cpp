@@ -231,20 +231,7 @@ void replace_all(std::string& s, const char* from, const char* to) {
 }
 }  // namespace
 
-bool map_transformer_file_key(const std::string& key, std::string* out) {
-    // loadTransformerWeights filters (ModelDownloader.swift:617-629)
-    if (has_suffix(key, ".weight_scale") || has_suffix(key, ".input_scale")) return false;
-    if (contains(key, "audio") || has_prefix(key, "vocoder") || contains(key, "av_ca_")) return false;
-    const char* diffusion = "model.diffusion_model.";
-    if (!has_prefix(key, diffusion)) return false;
-    if (has_prefix(key, "model.diffusion_model.video_embeddings_connector.")) return false;
-    if (has_prefix(key, "model.diffusion_model.audio_embeddings_connector.")) return false;
-    std::string k = key.substr(strlen(diffusion));
-    // mapTransformerKey (ModelDownloader.swift:756-803)
-    if (has_prefix(k, "audio_") || contains(k, ".audio_") || has_prefix(k, "av_cross_attn_") ||
-        contains(k, "video_to_audio") || contains(k, "video_a2v") || contains(k, "a2v_ca") ||
-        contains(k, "scale_shift_table_a2v"))
-        return false;
+std::string transformer_module_spelling(std::string k) {
     if (has_prefix(k, "proj_in.")) k = "patchify_proj." + k.substr(strlen("proj_in."));
     if (has_prefix(k, "time_embed.emb.timestep_embedder."))
         k = "adaln_single.emb." + k.substr(strlen("time_embed.emb.timestep_embedder."));
@@ -258,7 +245,24 @@ bool map_transformer_file_key(const std::string& key, std::string* out) {
     replace_all(k, ".to_out.0.", ".to_out.");
     replace_all(k, "ff.net.0.proj.", "ff.project_in.proj.");
     replace_all(k, "ff.net.2.", "ff.project_out.");
-    *out = k;
+    return k;
+}
+
+bool map_transformer_file_key(const std::string& key, std::string* out) {
+    // loadTransformerWeights filters (ModelDownloader.swift:617-629)
+    if (has_suffix(key, ".weight_scale") || has_suffix(key, ".input_scale")) return false;
+    if (contains(key, "audio") || has_prefix(key, "vocoder") || contains(key, "av_ca_")) return false;
+    const char* diffusion = "model.diffusion_model.";
+    if (!has_prefix(key, diffusion)) return false;
+    if (has_prefix(key, "model.diffusion_model.video_embeddings_connector.")) return false;
+    if (has_prefix(key, "model.diffusion_model.audio_embeddings_connector.")) return false;
+    const std::string k = key.substr(strlen(diffusion));
+    // mapTransformerKey (ModelDownloader.swift:756-803): the video-only model drops the audio side, then renames
+    if (has_prefix(k, "audio_") || contains(k, ".audio_") || has_prefix(k, "av_cross_attn_") ||
+        contains(k, "video_to_audio") || contains(k, "video_a2v") || contains(k, "a2v_ca") ||
+        contains(k, "scale_shift_table_a2v"))
+        return false;
+    *out = transformer_module_spelling(k);
     return true;
 }
 

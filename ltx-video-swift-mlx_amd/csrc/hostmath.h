@@ -50,6 +50,10 @@ TilePlan vae_tile_plan(int latent_frames, int tile, int overlap);
 // mapTransformerKey / loadTransformerWeights filters (ModelDownloader.swift:605-639,756-803).
 // `file_key` is the raw safetensors key. Returns false when the key is skipped.
 bool map_transformer_file_key(const std::string& file_key, std::string* module_key);
+// The rename half of mapTransformerKey (ModelDownloader.swift:772-800): checkpoint spelling -> module spelling of a key that has no
+// "model.diffusion_model." prefix (proj_in, time_embed, .emb.timestep_embedder., norm_q / norm_k, to_out.0, ff.net.0.proj, ff.net.2).
+// The dual model's loaders use it directly: they keep the audio keys that map_transformer_file_key drops.
+std::string transformer_module_spelling(std::string key);
 // mapVAEWeights (ModelDownloader.swift:808-899). Accepts keys with or without the unified file's "vae." prefix.
 bool map_vae_file_key(const std::string& file_key, std::string* module_key);
 // LoRA key -> module weight key (LoRALoader.swift:209-243)

@@ -170,7 +170,7 @@ void dit_quantize(ltx_ctx* ctx, DiTModel* m, int bits, int group) {
         by_w[l->w] = l;
     }
     // parameter slots of the weights (incl. the to_q / to_k row views of the fused matrix) now name codes / scales / biases
-    for (auto& kv : m->slots) {
+    for (auto& kv : m->params.slots) {
         ParamSlot& sl = kv.second;
         if (sl.kind != SLOT_BF16) continue;
         auto it = by_w.upper_bound((const bf16_t*)sl.dst);
@@ -186,7 +186,7 @@ void dit_quantize(ltx_ctx* ctx, DiTModel* m, int bits, int group) {
     }
     HIP_CHECK(hipStreamSynchronize(ctx->stream));
     for (LinearW* l : lins) l->w = nullptr;
-    m->warena.buf.release();   // the bf16 weights are gone: 26 GB -> 13.9 GB (8 bits) / 7.3 GB (4 bits) resident
+    m->params.warena.buf.release();   // the bf16 weights are gone: 26 GB -> 13.9 GB (8 bits) / 7.3 GB (4 bits) resident
     m->quant_bits = bits;
     for (auto* c : m->ctx_cache) c->version = 0;
 }
@@ -236,8 +236,8 @@ int dit_fuse_lora(ltx_ctx* ctx, DiTModel* m, const std::string& path, float scal
         }
         std::string mk;
         map_lora_key(base, &mk);
-        auto sit = m->slots.find(mk);
-        if (sit == m->slots.end()) continue;  // "no model weight for ..., skipping" (LoRAAdapter.swift:136-139)
+        auto sit = m->params.slots.find(mk);
+        if (sit == m->params.slots.end()) continue;  // "no model weight for ..., skipping" (LoRAAdapter.swift:136-139)
         ParamSlot& slot = sit->second;
         if (slot.kind != SLOT_BF16 || slot.rows != out || slot.cols != in)
             LTX_THROW(LTXS_INVALID_LORA, "Invalid LoRA: %s is [%d,%d] but the layer is [%ld,%ld]", base.c_str(), out, in, slot.rows, slot.cols);

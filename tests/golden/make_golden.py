@@ -5,6 +5,7 @@ fixture is additionally recomputed with a torch re-implementation of the attenti
 text-embedding connector and the VAE encoder fixtures are cross-checked the same way).
 
     python tests/golden/make_golden.py
+    python tests/golden/make_golden.py --synthetic-digests    # only synthetic_param_digests.json; needs the built library and a GPU
 """
 import math
 import os
@@ -205,7 +206,31 @@ def make_vae_encoder_fixture():
     np.savez_compressed(os.path.join(HERE, "vae_encoder_tiny.npz"), seed=seed, base=base, pixels=px, latent=z.astype(np.float32))
 
 
+def make_synthetic_param_digests():
+    """synthetic_param_digests.json: what *_init_synthetic(seed) leaves resident (tests/helpers/synthetic_params.py). Unlike the
+    other fixtures this records the library itself, so it needs the built library and a GPU, and is rewritten only when the synthetic
+    weights are meant to change."""
+    import importlib
+    import json
+
+    sys.path.insert(0, os.path.join(HERE, "..", ".."))
+    sys.path.insert(0, os.path.join(HERE, "..", "helpers"))
+    import synthetic_params as sp
+
+    ltx = importlib.import_module("ltx-video-swift-mlx_amd")
+    ctx = ltx.Context(0)
+    d = sp.digests(ltx, o, ctx)
+    assert d == sp.digests(ltx, o, ctx), "the synthetic weights or the connector encode differ between two runs"
+    ctx.close()
+    with open(os.path.join(HERE, "synthetic_param_digests.json"), "w") as f:
+        json.dump({"seed": sp.SEED, "models": d}, f, indent=0, sort_keys=True)
+        f.write("\n")
+    print("synthetic parameter digests:", {k: len(v) for k, v in d.items()})
+
+
 def main():
+    if "--synthetic-digests" in sys.argv[1:]:
+        return make_synthetic_param_digests()
     seed, layers, heads, caption = 11, 2, 2, 128
     cfg = o.DiTConfig(num_layers=layers, num_heads=heads, caption_channels=caption)
     w = o.synth_dit_weights(cfg, seed=seed)

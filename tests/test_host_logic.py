@@ -238,6 +238,17 @@ KEY_KATS = {
     "model.diffusion_model.transformer_blocks.0.ff.net.0.proj.weight": "transformer_blocks.0.ff.project_in.proj.weight",
     "model.diffusion_model.transformer_blocks.0.ff.net.2.bias": "transformer_blocks.0.ff.project_out.bias",
     "model.diffusion_model.transformer_blocks.0.scale_shift_table": "transformer_blocks.0.scale_shift_table",
+    # the dual model's loaders rename through the same function (transformer_module_spelling): one dual-block checkpoint key per rule ...
+    "model.diffusion_model.transformer_blocks.1.attn2.norm_q.weight": "transformer_blocks.1.attn2.q_norm.weight",
+    "model.diffusion_model.transformer_blocks.1.attn1.norm_k.weight": "transformer_blocks.1.attn1.k_norm.weight",
+    "model.diffusion_model.transformer_blocks.1.attn1.to_out.0.weight": "transformer_blocks.1.attn1.to_out.weight",
+    "model.diffusion_model.transformer_blocks.1.ff.net.0.proj.bias": "transformer_blocks.1.ff.project_in.proj.bias",
+    "model.diffusion_model.transformer_blocks.1.ff.net.2.weight": "transformer_blocks.1.ff.project_out.weight",
+    # ... and one top-level dual key per rule
+    "model.diffusion_model.proj_in.bias": "patchify_proj.bias",
+    "model.diffusion_model.time_embed.emb.timestep_embedder.linear_1.weight": "adaln_single.emb.linear_1.weight",
+    "model.diffusion_model.time_embed.linear.bias": "adaln_single.linear.bias",
+    "model.diffusion_model.adaln_single.emb.timestep_embedder.linear_2.bias": "adaln_single.emb.linear_2.bias",
     # skipped
     "model.diffusion_model.transformer_blocks.0.attn1.to_q.weight_scale": None,
     "model.diffusion_model.transformer_blocks.0.audio_attn1.to_q.weight": None,
@@ -284,6 +295,30 @@ def test_key_mapping_kats(ltx, oracle):
         assert ltx.map_vae_key(k) == v == oracle.map_vae_key(k), k
     for k, v in LORA_KATS.items():
         assert ltx.map_lora_key(k) == v == oracle.map_lora_key(k), k
+
+
+def test_dual_checkpoint_keys_map_back_through_the_shared_rename(ltx):
+    """Every video-side key of the dual model in its checkpoint spelling comes back as its module key, and no rename rule fires on a
+    key it was not written for: the block rules leave the top-level keys alone and the top-level rules leave the block keys alone.
+    (ltx_map_transformer_key drops the audio side, which goes through the same renames under an "audio_" name.)"""
+    import sys
+
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
+    import dual_block_ref
+    import dual_model_ref
+
+    keys = list(dual_model_ref.param_shapes(2, 1, 1))
+    assert not [k for k in dual_block_ref.param_shapes(2, 1, 1) if k.startswith("proj_in.") or ".emb.timestep_embedder." in k]
+    top = dual_model_ref.top_shapes(1, 1)
+    for k in top:
+        ck = dual_model_ref.checkpoint_spelling(k)
+        assert not any(r in ck for r in (".norm_q.", ".norm_k.", ".to_out.0.", "ff.net.")), ck
+    video = [k for k in keys if ltx.map_transformer_key("model.diffusion_model." + k) is not None]
+    assert len(video) > len(keys) // 4 and any(k in top for k in video) and any(k.startswith("transformer_blocks.1.") for k in video)
+    for k in video:
+        assert ltx.map_transformer_key("model.diffusion_model." + dual_model_ref.checkpoint_spelling(k)) == k, k
+    for k in keys:  # the Python restatement the GPU round-trip tests write their files with agrees on every key, audio included
+        assert dual_model_ref.module_spelling(dual_model_ref.checkpoint_spelling(k)) == k, k
 
 
 def test_key_mapping_roundtrip_covers_all_params(ltx, oracle):
