@@ -888,6 +888,11 @@ int ltx_op_qknorm_rope_pair(ltx_ctx* ctx, const void* x0, const float* w0, uint1
  * launcher's own rule, which the decoder asks; options "conv_halo" and the 32-bit offset limits of the halo-staged kernels enter it),
  * 0 when that PixelNorm runs as a row pass. Host-side, no device. */
 int ltx_conv_takes_d2s_pn(int F, int H, int W, int C);
+/* The tile configuration the GEMM launcher picks for a dense launch C[M][N] = A[M][K] . B[N][K]^T (+ bias_n, activation `act`)
+ * without split-K on a device of `ncu` CUs: 21 = 192x128 ring, 1 = 192x128 two-stage, 75 = 192x256, 76 = 384x256, ... flags: 1 f32
+ * output, 2 bf16 output, 4 gated residual, 8 transposed bf16 output, 16 per-row bias. Reads option "gemm_tall". -1 on a shape no
+ * launch takes. Host-side, no device. */
+int ltx_gemm_dense_tile_cfg(int M, int N, int K, int act, int flags, int ncu);
 /* The audio leg's convolutions (csrc/audio_conv.hip), one launch family: x channels-last bf16, f32 accumulation. tile: -1 auto, else
  * the instance by output-channel width (128, 64, 32). Cin must be a multiple of 32. Epilogue arguments as the launcher takes them:
  * resid f32 (same layout as out_f32) is added; f32_act 0 none / 2 tanh; transposed != 0 stores out_f32 as [Cout][rows]; out_bf16

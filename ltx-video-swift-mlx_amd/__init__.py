@@ -181,6 +181,11 @@ def conv_takes_d2s_pn(F, H, W, C):
     return bool(lib.ltx_conv_takes_d2s_pn(F, H, W, C))
 
 
+def gemm_dense_tile_cfg(M, N, K, act=0, flags=2, ncu=256):
+    """``ltx_gemm_dense_tile_cfg``: the tile configuration the launcher picks for a dense GEMM launch on a device of ``ncu`` CUs."""
+    return lib.ltx_gemm_dense_tile_cfg(M, N, K, act, flags, ncu)
+
+
 def option_table():
     """[(name, default, min, max, numerics, doc)] of every switch (``ltx_option_info``)."""
     n = lib.ltx_option_info(-1, None, None, None, None, None, None)

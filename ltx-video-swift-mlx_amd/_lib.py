@@ -243,6 +243,7 @@ SIGNATURES = {
     "ltx_op_norm_mod_ex": (_i, [_vp, _vp, _l, _vp, _vp, _l, _i, _vp, _i, _i, _i, _f, _i, _vp, _l]),
     "ltx_op_qknorm_rope_pair": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _l, _l, _vp, _vp, _i, _i, _i, _f, _f, _i]),
     "ltx_conv_takes_d2s_pn": (_i, [_i, _i, _i, _i]),
+    "ltx_gemm_dense_tile_cfg": (_i, [_i, _i, _i, _i, _i, _i]),
     "ltx_audio_vae_load": (_i, [_vp, C.c_char_p]),
     "ltx_audio_vae_init_synthetic": (_i, [_vp, _i, _u64]),
     "ltx_audio_vae_unload": (_i, [_vp]),

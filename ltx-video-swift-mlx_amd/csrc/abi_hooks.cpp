@@ -253,6 +253,22 @@ int ltx_conv_takes_d2s_pn(int F, int H, int W, int C) {
     return (long)F * H * W <= 0x7fffffffL && gemm_conv_takes_d2s_pn(g) ? 1 : 0;
 }
 
+int ltx_gemm_dense_tile_cfg(int M, int N, int K, int act, int flags, int ncu) {
+    if (M < 1 || N < 1 || K < 64 || K % 64 != 0 || ncu < 1) return -1;
+    // the launch as ltx_op_gemm_bf16 forms it; the pointers only say which operands and outputs exist and are never followed
+    static const uintptr_t present = 256;
+    GemmArgs g;
+    g.A = (const bf16_t*)present; g.lda = K; g.B = (const bf16_t*)present; g.ldb = K; g.M = M; g.N = N; g.K = K;
+    g.ep.bias_n = (const float*)present;
+    g.ep.act = act;
+    if (flags & 1) { g.ep.out_f32 = (float*)present; g.ep.ld_f32 = N; }
+    if (flags & 2) { g.ep.out_bf16 = (bf16_t*)present; g.ep.ld_bf16 = N; }
+    if (flags & 4) { g.ep.resid = 1; g.ep.gate = (const float*)present; g.ep.rows_per_batch = M; }
+    if (flags & 8) { g.ep.out_bf16_t = (bf16_t*)present; g.ep.ld_bf16_t = M; }
+    if (flags & 16) g.ep.bias_m = (const float*)present;
+    return gemm_dense_cfg(g, ncu);
+}
+
 // ---- attention and row kernels ----
 int ltx_op_attention(ltx_ctx* ctx, const uint16_t* Q, const uint16_t* K, const uint16_t* Vt, long ldvt,
                      const float* bias, int B, int H, int Tq, int Tk, float scale, uint16_t* O) {

@@ -148,7 +148,13 @@ bool gemm_conv_takes_d2s_pn(const GemmArgs& args);
 // can a launch of this shape take B as 8-bit codes (GemmArgs::Bq)?
 bool gemm_takes_codes(int M, int N, int K);
 bool gemm_fewrow_takes(int M, int N, int K, int splits);
-// Force a tile config (v1: 0 128x128, 1 192x128, 3 96x128, 4 128x96; v2 ring: 21 192x128, 23 256x128, 25 128x192) -
+// Does launch_gemm_bf16 send this dense launch to the 384 x 256 kernel (tile_cfg 76) on a device of `ncu` CUs? Whole tiles, a
+// plain-store epilogue (bias_n, activation, round_bf16, f32 / bf16 output), no split-K, and a whole number of rounds of tiles.
+bool gemm_tall_takes(const GemmArgs& args, int ncu);
+// The tile cfg launch_gemm_bf16 picks for a dense launch without split-K, as a pure function of the launch and the CU count
+// (option "gemm_tall" is read once per call; no device is touched).
+int gemm_dense_cfg(const GemmArgs& args, int ncu);
+// Force a tile config (v1: 0 128x128, 1 192x128, 3 96x128, 4 128x96; v2 ring: 21 192x128, 23 256x128, 25 128x192; 75 192x256; 76 384x256) -
 // used by tests/bench sweeps.
 void launch_gemm_bf16_cfg(const GemmArgs& args, int cfg, hipStream_t stream);
 

@@ -843,7 +843,7 @@ LTX_DEVFN void wait_vmcnt_barrier() {
 // 128-B line, to hide the HBM latency of the once-streamed DiT weights. Same-process A/B on MI355X: 779 vs 963 TFLOP/s
 // cold and 932 vs 1040 warm at 1536x8192x4096 - every touched line crosses the CU's vector L1, +40 % bytes through the
 // texture path that this loop already saturates. The ring depth stays the only latency cover.)
-#if defined(GEMM_ASM_STAMPS) || defined(GEMM_V2_STAMPS) || defined(DTL_STAMPS) || defined(QKV_STAMPS)
+#if defined(GEMM_ASM_STAMPS) || defined(GEMM_V2_STAMPS) || defined(DTL_STAMPS) || defined(QKV_STAMPS) || defined(TALL_STAMPS)
 __device__ unsigned long long g_gemm_stamps[5][8];  // diagnostic builds only (tools/ubench/gemm_stamps.hip)
 #endif
 // QB (few-row launches on a quantised Linear, round 3): B arrives as 8-bit codes + bf16 scale / bias per 64-wide group (one group =
@@ -2362,6 +2362,114 @@ __global__ __launch_bounds__(256, 1) void gemm_bf16_kernel_qkv(const GemmQkvArgs
     });
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// 384 x 256 tile, ONE wave per SIMD, assembly main loop generated by tools/gen_gemm_asm_tall.py (schedule, register map and the static
+// proofs of its LDS-DMA / ds_read ordering and of every MFMA's operands are in that script). The DiT's FFN-up projection at 1536 tokens
+// (1536 x 16384) is exactly ONE round of 256 such tiles where the 192 x 256 kernel runs two, and per MFMA the tile stages 29 % fewer
+// bytes. Two activation slots (48 KB) and two weight slots (32 KB) are the whole 160 KB of LDS: no static LDS in this kernel. Wave
+// tile 192 x 128: the accumulators of its first 128 rows are left in a[0:255] (the 192 x 256 kernel's map, one 32-row group longer),
+// those of rows 128..191 were in VGPRs and are left in LDS in the layout of the epilogue scratch. Dense A.B^T with plain stores only
+// (gemm_tall_takes); same arithmetic in the same order as the plain-store epilogue of gemm_bf16_kernel_dtl: bit-identical outputs.
+// ---------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256, 1) void gemm_bf16_kernel_tall(const GemmArgs g) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    constexpr int BM = 384, BN = 256, WGN = 2;
+    constexpr int WM = 192, WN = 128;
+    constexpr int A_BYTES = BM * ROW_BYTES;
+    constexpr int WAVE_LDS = 2 * 32 * WN * 4;  // the epilogue's share of LDS per wave: two 32-row groups of f32
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wr = wave / WGN, wc = wave % WGN;
+    const int tiles_m = g.M / BM;
+    const int bid = xcd_remap(blockIdx.x, gridDim.x);
+    int tm, tn;
+    tile_coords(g, bid, tiles_m, BN, tm, tn);
+    const int m0 = tm * BM, n0 = tn * BN;
+    // piece i of this wave = rows (wave + 4 i) * 8 .. +7 of the tile (as gemm_bf16_kernel_dtl): the i part is a scalar offset
+    const int srow = lane >> 3, pch = lane & 7;
+    const int row0 = wave * 8 + srow;
+    const int ao = (row0 * (int)g.lda + ((pch ^ ((row0 >> 1) & 7)) << 3)) * 2;
+    const int bo = (row0 * (int)g.ldb + ((pch ^ ((row0 >> 1) & 7)) << 3)) * 2;
+    const uint32_t sa = (uint32_t)(32 * g.lda * 2), sb = (uint32_t)(32 * g.ldb * 2);
+    const int nkt = g.K / BK;
+    const bf16_t* At = g.A + (long)m0 * g.lda;
+    const bf16_t* Bt = g.B + (long)n0 * g.ldb;
+    const uint32_t alo = (uint32_t)(uintptr_t)At, ahi = (uint32_t)((uintptr_t)At >> 32);
+    const uint32_t blo = (uint32_t)(uintptr_t)Bt, bhi = (uint32_t)((uintptr_t)Bt >> 32);
+    const uint32_t arec = (uint32_t)(((long)(BM - 1) * g.lda + (long)nkt * BK) * 2), brec = (uint32_t)(((long)(BN - 1) * g.ldb + (long)nkt * BK) * 2);
+    const uint32_t nk = (uint32_t)nkt;
+    const uint32_t wlds = (uint32_t)wave * 1024u;
+    const int frow = lane & 15, fsw = (lane >> 1) & 7;
+    const int foff0 = frow * ROW_BYTES + ((((lane >> 4) + 0) ^ fsw) << 4);
+    const int foff1 = frow * ROW_BYTES + ((((lane >> 4) + 4) ^ fsw) << 4);
+    // LDS: [A slot 0][A slot 1][B slot 0][B slot 1] (tools/gen_gemm_asm_tall.py)
+    const int a_wave_off = (wr * WM) * ROW_BYTES, b_wave_off = 2 * A_BYTES + (wc * WN) * ROW_BYTES;
+    const int fa0 = a_wave_off + foff0, fa1 = a_wave_off + foff1, fb0 = b_wave_off + foff0, fb1 = b_wave_off + foff1;
+    // where the stream leaves the accumulators of rows 128..191: this lane's first element of the wave's two scratch groups
+    const int sp = wave * WAVE_LDS + ((((lane >> 4) * 4) * WN + (lane & 15)) * 4);
+#ifdef TALL_STAMPS  // tools/ubench/gemm_tall_stamps.hip
+    unsigned long long* dbg = (blockIdx.x == 7) ? &g_gemm_stamps[wave][0] : &g_gemm_stamps[4][0];
+#endif
+    asm volatile(
+#ifdef TALL_STAMPS
+#include "gemm_tall_384x256_stamps.inc"
+#else
+#include "gemm_tall_384x256.inc"
+#endif
+        :
+        : [alo] "s"(alo), [ahi] "s"(ahi), [arec] "s"(arec), [blo] "s"(blo), [bhi] "s"(bhi), [brec] "s"(brec), [nk] "s"(nk), [sa] "s"(sa),
+          [sb] "s"(sb), [wlds] "s"(wlds), [ao] "v"(ao), [bo] "v"(bo), [fa0] "v"(fa0), [fa1] "v"(fa1), [fb0] "v"(fb0), [fb1] "v"(fb1), [sp] "v"(sp)
+#ifdef TALL_STAMPS
+          , [dbg] "s"(dbg)
+#endif
+        :
+#include "gemm_tall_384x256_clobbers.inc"
+    );
+    // (the stream ends behind a barrier: every wave is done with the K-tile slots. From here on a wave touches its own WAVE_LDS bytes only.)
+    // Epilogue: 32 rows x 128 columns at a time. Groups 4, 5 (rows 128..191) lie in the wave's LDS already and go first; groups 0..3
+    // are then dumped from a[0:255] over them, one at a time. The 16 scratch reads of a group are issued together.
+    constexpr int LPR = WN / 4, RPI = 64 / LPR, NITG = 32 / RPI;  // lanes per row, rows per iteration, iterations per group
+    const unsigned scr_lane = (unsigned)(wave * WAVE_LDS + ((((lane >> 4) * 4) * WN + (lane & 15)) * 4));
+    const int gn = n0 + wc * WN + (lane % LPR) * 4;
+    const GemmEpilogue& ep = g.ep;
+    const f32x4 bias = ep.bias_n ? *(const f32x4*)(ep.bias_n + gn) : f32x4{0.f, 0.f, 0.f, 0.f};
+    static_for<0, 6>([&](auto ord_c) {
+        constexpr int grp = (decltype(ord_c)::value + 4) % 6;  // 4, 5, 0, 1, 2, 3
+        const float* scr = (const float*)(smem + wave * WAVE_LDS + (grp == 5 ? 32 * WN * 4 : 0));
+        if constexpr (grp < 4) {
+#include "gemm_tall_384x256_dump.inc"
+        }
+        f32x4 vv[NITG];
+#pragma unroll
+        for (int it = 0; it < NITG; ++it) vv[it] = *(const f32x4*)(scr + (it * RPI + lane / LPR) * WN + (lane % LPR) * 4);
+#pragma unroll
+        for (int it = 0; it < NITG; ++it) {
+            const int gm = m0 + wr * WM + grp * 32 + it * RPI + lane / LPR;
+            f32x4 v = vv[it] + bias;
+            if (ep.act == LTX_ACT_GELU_TANH) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[e] = gelu_tanh(v[e]);
+            } else if (ep.act == LTX_ACT_SILU) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[e] = silu_f(v[e]);
+            }
+            if (ep.round_bf16) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[e] = bf16_to_f32(f32_to_bf16(v[e]));
+            }
+            if (ep.out_f32) *(f32x4*)(ep.out_f32 + (long)gm * ep.ld_f32 + gn) = v;
+            if (ep.out_bf16) {
+                uint2 pk;
+                pk.x = pack_bf16x2(v[0], v[1]);
+                pk.y = pack_bf16x2(v[2], v[3]);
+                *(uint2*)(ep.out_bf16 + (long)gm * ep.ld_bf16 + gn) = pk;
+            }
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the scratch is rewritten by the next dump
+    });
+}
+
 #ifdef LTX_EXPERIMENTS
 template <int BM, int BN, int NSTAGE>
 void launch_m32(const GemmArgs& a, hipStream_t stream) {
@@ -2536,6 +2644,35 @@ static void launch_dtl(const GemmArgs& a, hipStream_t stream, const NormAfter* n
     } else {
         LTX_REQUIRE(!na, "gemm: a norm pass can only ride on a split-K finish");
     }
+}
+
+// ---- 384 x 256 tiles (gemm_bf16_kernel_tall, tile_cfg 76) ----
+// What the kernel can run: a dense A.B^T of whole tiles with bias_n / activation / round_bf16 and plain f32 and/or bf16 stores. The
+// 1 << 22 bound keeps every 32-bit buffer offset of a 384-row tile positive.
+static bool gemm_tall_fits(const GemmArgs& a) {
+    const GemmEpilogue& e = a.ep;
+    const long ldmax = 1L << 22;
+    return !a.conv && !a.Bq && a.B && a.M > 0 && a.M % 384 == 0 && a.N > 0 && a.N % 256 == 0 && a.K >= 64 && a.K % 64 == 0 && a.lda % 8 == 0 &&
+           a.ldb % 8 == 0 && a.lda >= a.K && a.ldb >= a.K && a.lda < ldmax && a.ldb < ldmax && a.split_k <= 1 && a.tile_count == 0 &&
+           a.win_rows == 0 && (e.out_f32 || e.out_bf16) && !e.out_bf16_t && !e.bias_m && !e.resid && !e.gate && !e.gate_rowmap &&
+           !e.resid_src && !e.d2s && !e.clip01 && !e.pn_out;
+}
+// ... and what launch_gemm_bf16 sends there instead of the 192 x 256 kernel: launches that are a whole number of rounds of these tiles
+// on `ncu` CUs (the FFN-up projection at 1536 / 3072 / 6144 tokens). A ragged round of tiles twice as tall would cost what it saves.
+bool gemm_tall_takes(const GemmArgs& a, int ncu) {
+    if (!gemm_tall_fits(a) || ncu <= 0) return false;
+    const long tiles = (long)(a.M / 384) * (a.N / 256);
+    return tiles > 0 && tiles % ncu == 0;
+}
+static void launch_tall(const GemmArgs& a, hipStream_t stream) {
+    LTX_REQUIRE(gemm_tall_fits(a),
+                "gemm: the 384x256 kernel needs a dense A.B^T with M %% 384 == 0, N %% 256 == 0, K %% 64 == 0, no split-K and a plain-store "
+                "epilogue (bias_n, activation, f32 / bf16 output) (M=%d N=%d K=%d)", a.M, a.N, a.K);
+    constexpr int smem = (2 * 384 + 2 * 256) * ROW_BYTES;  // two activation slots, two weight slots: all 160 KB
+    static PerDeviceOnce attr_set;
+    attr_set.run([&] { HIP_CHECK(hipFuncSetAttribute((const void*)gemm_bf16_kernel_tall, hipFuncAttributeMaxDynamicSharedMemorySize, smem)); });
+    hipLaunchKernelGGL(gemm_bf16_kernel_tall, dim3((a.M / 384) * (a.N / 256)), dim3(256), smem, stream, a);
+    HIP_CHECK(hipGetLastError());
 }
 
 // ---- fused q|k + V projection (gemm_bf16_kernel_qkv) ----
@@ -2762,6 +2899,7 @@ void launch_gemm_bf16_cfg(const GemmArgs& a, int cfg, hipStream_t stream) {
                 break;
 #endif
             case 75: launch_dtl(a, stream); break;  // 192x256, one wave per SIMD, fragments of a whole K-tile in registers, 2 + 3 LDS slots
+            case 76: launch_tall(a, stream); break;  // 384x256, one wave per SIMD, B fragments of a K-tile in registers, A through a ring, 2 + 2 LDS slots
 #ifdef LTX_EXPERIMENTS  // measured, not selected (gemm_experiments.inc)
             case 31: launch_m32<192, 128, 4>(a, stream); break;  // the 192x128 ring tile on 32x32x16 MFMAs (2 x 4 waves of 96 x 32): 951 vs 1021 TFLOP/s
             case 90: launch_stream(a, stream); break;  // weight-streaming kernel for M <= 128 (bf16 weights or 8-bit codes): 1.4x slower than the ring split-K path
@@ -2817,6 +2955,31 @@ static int dtl_split_for(const GemmArgs& a) {
     return gemm_dtl_takes(b) ? (int)s : 0;
 }
 
+// The tile choice of a dense launch without split-K as a pure function of the launch and the CU count: no device is touched
+// (ltx_gemm_dense_tile_cfg pins the table in a CPU test). launch_gemm_bf16 may still split a ragged 192x256 launch by rows.
+int gemm_dense_cfg(const GemmArgs& a, int ncu) {
+    struct Cand { int cfg, bm, bn, slots; double f; };
+    //   cfg 75: 192x256 tile, one wave per SIMD, assembly main loop (tools/gen_gemm_asm_dtl.py): half the rounds of a 192x128 tile.
+    //   Same measurement, round 2 (profiles/r02_gemm_microbench.txt): N=8192: cfg75 1165 | library GEMM 1116 | cfg1 936 | cfg21 959;
+    //   N=16384: 1274 | 1294 | 1054 | 1009; 6144x4096x4096: 1290 | 1325 | 1093 | 1033; 1536x4096x4096 (128 tiles): 740 -> not chosen.
+    static const Cand cands[] = {{75, 192, 256, 256, 1.22}, {1, 192, 128, 512, 1.00}, {21, 192, 128, 256, 0.95}, {25, 128, 192, 256, 0.90},
+                                 {0, 128, 128, 512, 0.80},  {3, 96, 128, 512, 0.72},  {4, 128, 96, 512, 0.72}};
+    int best = 0;
+    double be = -1;
+    for (const Cand& c : cands) {
+        if (c.cfg == 75 && !gemm_dtl_takes(a)) continue;
+        const long tiles = (long)((a.M + c.bm - 1) / c.bm) * ((a.N + c.bn - 1) / c.bn);
+        const long rounds = (tiles + c.slots - 1) / c.slots;
+        const double fill = ((double)a.M * a.N) / ((double)tiles * c.bm * c.bn);  // ragged edges waste MFMA work
+        const double e = (double)tiles / (double)(rounds * c.slots) * c.f * fill;
+        if (e > be + 1e-9) { be = e; best = c.cfg; }
+    }
+    // cfg 76: where the 192x256 kernel would run an even number of rounds, tiles twice as tall run half as many, each staging 29 % fewer
+    // bytes per MFMA (the FFN-up projection, N = 16384). Option "gemm_tall" = 0 = off (A/B); bit-neutral. Read once per decision.
+    if (best == 75 && ltx_opt(OPT_GEMM_TALL) != 0 && gemm_tall_takes(a, ncu)) best = 76;
+    return best;
+}
+
 void launch_gemm_bf16(const GemmArgs& a, hipStream_t stream, const NormAfter* na) {
     LTX_REQUIRE(na && a.ep.out_f32 && !a.conv, "gemm: norm_after needs a dense launch with an f32 output");
     const bool fuse_on = ltx_opt(OPT_FINISH_NORM) != 0;  // A/B option "finish_norm"
@@ -2858,12 +3021,7 @@ void launch_gemm_bf16(const GemmArgs& a_in, hipStream_t stream) {
     // Measured on MI355X, HBM-cold B operand, random data (tools/bench_gemm.py --cold), TFLOP/s:
     //   M=1536 N=4096 K=4096 : cfg21 944 | cfg0 754 | cfg1 608      N=8192: cfg1 1026 | cfg21 949
     //   N=16384: cfg1 1049 | cfg21 991         K=16384: cfg21 1094 | cfg0 864       M=4096 N=1536: cfg25 876 | cfg0 629
-    struct Cand { int cfg, bm, bn, slots; double f; };
-    //   cfg 75: 192x256 tile, one wave per SIMD, assembly main loop (tools/gen_gemm_asm_dtl.py): half the rounds of a 192x128 tile.
-    //   Same measurement, round 2 (profiles/r02_gemm_microbench.txt): N=8192: cfg75 1165 | library GEMM 1116 | cfg1 936 | cfg21 959;
-    //   N=16384: 1274 | 1294 | 1054 | 1009; 6144x4096x4096: 1290 | 1325 | 1093 | 1033; 1536x4096x4096 (128 tiles): 740 -> not chosen.
-    static const Cand cands[] = {{75, 192, 256, 256, 1.22}, {1, 192, 128, 512, 1.00}, {21, 192, 128, 256, 0.95}, {25, 128, 192, 256, 0.90},
-                                 {0, 128, 128, 512, 0.80},  {3, 96, 128, 512, 0.72},  {4, 128, 96, 512, 0.72}};
+    // (the candidates and their factors: gemm_dense_cfg)
     if (a.conv) {
         // implicit-GEMM convs: the per-tap gather arithmetic must hide under MFMAs (8-wave ring kernels interleave it;
         // the two-stage 4-wave kernel serialises it and ran the 256-channel VAE stage at 150 TFLOP/s). M is huge, so
@@ -3013,16 +3171,8 @@ void launch_gemm_bf16(const GemmArgs& a_in, hipStream_t stream) {
         }
     }
 #endif
-    int best = 0;
-    double be = -1;
-    for (const Cand& c : cands) {
-        if (c.cfg == 75 && !gemm_dtl_takes(a)) continue;
-        const long tiles = (long)((a.M + c.bm - 1) / c.bm) * ((a.N + c.bn - 1) / c.bn);
-        const long rounds = (tiles + c.slots - 1) / c.slots;
-        const double fill = ((double)a.M * a.N) / ((double)tiles * c.bm * c.bn);  // ragged edges waste MFMA work
-        const double e = (double)tiles / (double)(rounds * c.slots) * c.f * fill;
-        if (e > be + 1e-9) { be = e; best = c.cfg; }
-    }
+    const int ncu = device_cu_count();
+    const int best = gemm_dense_cfg(a, ncu);
     // Ragged last round of the 192x256 kernel (round 4). With T = 9984 tokens the N = 4096 launches are 52 x 16 = 832 tiles = 3.25 rounds:
     // the fourth round runs 64 workgroups, K-long, on a quarter of the chip (19 % of the launch). Rows are independent, so such a launch is
     // split by rows into a head whose tiles are a whole number of rounds (48 row tiles = 768 tiles) and a tail (4 row tiles = 768 rows)
@@ -3030,7 +3180,6 @@ void launch_gemm_bf16(const GemmArgs& a_in, hipStream_t stream) {
     // round. Same kernels per output element as an unsplit launch of each part: bit-identical to those; option "gemm_rowsplit" = 0 = off (A/B).
     const bool rowsplit_on = ltx_opt(OPT_GEMM_ROWSPLIT) != 0;
     if (best == 75 && rowsplit_on && !a.ep.out_bf16_t && !a.ep.bias_m && a.split_k <= 1) {
-        const int ncu = device_cu_count();
         const int tm = a.M / 192, tn = a.N / 256;
         const long tiles = (long)tm * tn;
         const long rem = tiles % ncu;

@@ -35,6 +35,7 @@ const LtxOptInfo kInfo[OPT_COUNT] = {
     {"conv_stagger", 1, 0, 1, 0, "0: both waves of a SIMD issue their LDS-DMA pieces at the same point of the halo conv kernel's K loop"},
     {"b_nt", -1, -1, 1, 0, "-1: launcher's choice; 0 / 1: non-temporal weight loads of the few-row GEMM off / on"},
     {"qkv_fused", 1, 0, 1, 0, "0: the q|k and V projections of a DiT block's self-attention as two GEMM launches; 1: as one launch of 192 x 384 tiles where the shape allows (dense weights, 192-row multiples, no split-K)"},
+    {"gemm_tall", 1, 0, 1, 0, "0: dense launches that are whole rounds of 384 x 256 tiles (the FFN-up projection) on 192 x 256 tiles; 1: on the 384 x 256 kernel (plain-store epilogues, no split-K)"},
     {"attn_plain_order", 0, 0, 1, 0, "1: (query block, head, batch) workgroup order"},
     {"sp_overlap", 0, 0, 1, 0, "1: sequence-parallel V^T gather on a side stream"},
     {"sp_selftest", 0, 0, 1, 0, "1: one-rank self-test of the sequence-parallel side-stream branch"},

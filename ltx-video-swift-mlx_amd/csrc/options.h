@@ -38,6 +38,7 @@ enum LtxOpt {
     OPT_CONV_STAGGER,     // 0 = both waves of a SIMD issue their LDS-DMA pieces at the same point of the halo kernel's K loop (as before round 5)
     OPT_B_NT,             // -1 = launcher's choice; 0 / 1 = non-temporal weight loads of the few-row GEMM off / on
     OPT_QKV_FUSED,        // 0 = q|k and V projections of a DiT block as two launches (default 1: one launch of 192 x 384 tiles where gemm_qkv_takes)
+    OPT_GEMM_TALL,        // 0 = the FFN-up projection on 192 x 256 tiles (default 1: one round of 384 x 256 tiles where gemm_tall_takes)
     OPT_ATTN_PLAIN_ORDER, // 1 = (query block, head, batch) workgroup order as before round 3
     OPT_SP_OVERLAP,       // 1 = sequence-parallel V^T gather on a side stream (opt-in until a >= 2-rank RCCL run exists)
     OPT_SP_SELFTEST,      // 1 = one-rank self-test of the side-stream branch

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Micro-benchmark of the GEMM tile configurations on the DiT / VAE shapes (interleaved rounds in one process,
-random data - guide rule 24/25). Usage: python tools/bench_gemm.py [--rounds 5]"""
+random data - guide rule 24/25). Usage: python tools/bench_gemm.py [--rounds 5] [--cold] [--cfgs 21,75,76] [--shapes ff1]
+(cfgs: -1 library GEMM, -2 the launcher's choice, 21 192x128 ring, 75 192x256, 76 384x256 - whole 384 x 256 tiles only, n/a elsewhere)"""
 import argparse
 import importlib
 import os
@@ -28,10 +29,14 @@ def main():
     ap.add_argument("--cfgs", type=str, default="0,1,2,10,11,12,13,14")
     ap.add_argument("--cold", action="store_true", help="cycle through >512 MB of distinct weight matrices (HBM-cold B operand, as in the DiT)")
     ap.add_argument("--f32out", action="store_true")
+    ap.add_argument("--shapes", type=str, default="", help="comma-separated name prefixes of SHAPES (default: all)")
     args = ap.parse_args()
     cfgs = [int(c) for c in args.cfgs.split(",")]
     ctx = ltx.Context(0)
-    for name, M, N, K in SHAPES:
+    pick = [p for p in args.shapes.split(",") if p]
+    for name, M, N, K in SHAPES + [("ff1x2 3072x16384x4096", 3072, 16384, 4096)]:
+        if pick and not any(name.startswith(p) for p in pick):
+            continue
         A = torch.randn(M, K, device="cuda").to(torch.bfloat16)
         nb = max(1, (640 * 2 ** 20) // (N * K * 2)) if args.cold else 1
         Bs = [(torch.randn(N, K, device="cuda") / K ** 0.5).to(torch.bfloat16) for _ in range(nb)]
@@ -76,8 +81,8 @@ def main():
                 continue
             v = sorted(best[c])
             med = v[len(v) // 2]
-            line += f" | c{c}: {fl / med / 1e9:6.0f}"
-        print(line + "  (TFLOP/s, median)", flush=True)
+            line += f" | c{c}: {fl / med / 1e9:6.0f} ({med * 1e3:6.1f} us, {v[0] * 1e3:.1f} .. {v[-1] * 1e3:.1f})"
+        print(line + "  (TFLOP/s, median; us per launch median, min .. max)", flush=True)
     ctx.close()
 
 
