@@ -6,6 +6,7 @@ text-embedding connector and the VAE encoder fixtures are cross-checked the same
 
     python tests/golden/make_golden.py
     python tests/golden/make_golden.py --synthetic-digests    # only synthetic_param_digests.json; needs the built library and a GPU
+    python tests/golden/make_golden.py --gemm-asm-family-digests    # only gemm_asm_family_digests.json; the same needs
 """
 import math
 import os
@@ -228,9 +229,47 @@ def make_synthetic_param_digests():
     print("synthetic parameter digests:", {k: len(v) for k, v in d.items()})
 
 
+def make_gemm_asm_family_digests():
+    """gemm_asm_family_digests.json: the output bits of the assembly-loop GEMM kernels (tests/helpers/gemm_asm_family.py). It records
+    the library itself, so it is run on a build of the commit whose bits are to be kept, and rewritten only when they are meant to
+    change. Every case runs twice; one whose two runs differ cannot be pinned and stops the recording."""
+    import importlib
+    import json
+
+    sys.path.insert(0, os.path.join(HERE, "..", ".."))
+    sys.path.insert(0, os.path.join(HERE, "..", "helpers"))
+    import gemm_asm_family as fam
+
+    ltx = importlib.import_module("ltx-video-swift-mlx_amd")
+    assert fam.resid_tile_cfg(ltx) == 75, "the residual case would not run the 192 x 256 kernel on this device"
+
+    def once():
+        ctx, d = ltx.Context(0), {}
+        d.update(fam.gemm_cases(ltx, ctx, 75, fam.DTL_SHAPES))
+        d.update(fam.gemm_cases(ltx, ctx, 76, fam.TALL_SHAPES))
+        d.update(fam.qkv_cases(ctx))
+        d.update(fam.resid_case(ltx, ctx))
+        ctx.close()
+        model = fam.two_layer_context(ltx)
+        d.update(fam.forward_case(model))
+        model.close()
+        return d
+
+    d, again = once(), once()
+    unstable = sorted(k for k in d if d[k] != again[k])
+    assert not unstable, f"not reproducible between two runs: {unstable}"
+    assert sorted(d) == fam.expected_keys()
+    with open(os.path.join(HERE, "gemm_asm_family_digests.json"), "w") as f:
+        json.dump({"seed": fam.SEED, "digests": d}, f, indent=0, sort_keys=True)
+        f.write("\n")
+    print("assembly-loop GEMM digests:", len(d))
+
+
 def main():
     if "--synthetic-digests" in sys.argv[1:]:
         return make_synthetic_param_digests()
+    if "--gemm-asm-family-digests" in sys.argv[1:]:
+        return make_gemm_asm_family_digests()
     seed, layers, heads, caption = 11, 2, 2, 128
     cfg = o.DiTConfig(num_layers=layers, num_heads=heads, caption_channels=caption)
     w = o.synth_dit_weights(cfg, seed=seed)

@@ -16,7 +16,7 @@ DTL = os.path.join(ROOT, "tools", "gen_gemm_asm_dtl.py")
 
 def test_qkv_stream_is_proven_and_matches_the_committed_files():
     r = subprocess.run([sys.executable, QKV, "--check"], capture_output=True, text=True)
-    assert r.returncode == 0 and "wait coverage ok" in r.stdout and "match" in r.stdout and "DIFFER" not in r.stdout, r.stdout + r.stderr
+    assert r.returncode == 0 and "wait coverage ok" in r.stdout and "matches" in r.stdout and "DIFFER" not in r.stdout, r.stdout + r.stderr
 
 
 @pytest.mark.parametrize("flag,kind", [("--inject-raw-race", "RAW"), ("--inject-war-race", "WAR")])

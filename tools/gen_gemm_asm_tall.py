@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Generates ltx-video-swift-mlx_amd/csrc/gemm_tall_384x256.inc (+ _clobbers.inc, _dump.inc): the gfx950 assembly main loop of
-gemm_bf16_kernel_tall (gemm.hip, tile_cfg 76). The generated files are committed; the build does not run this script. Sibling of
+gemm_bf16_kernel_tall (gemm_asm_tiles.inc, tile_cfg 76). The generated files are committed; the build does not run this script. Sibling of
 tools/gen_gemm_asm_dtl.py (the 192 x 256 stream) and tools/gen_gemm_asm_qkv.py (192 x 384), whose outputs this script never touches.
 
 C[M][N] = A[M][K] . B[N][K]^T, bf16 in, f32 accumulate. Workgroup tile 384 x 256: the DiT's FFN-up projection at 1536 tokens
@@ -24,7 +24,8 @@ static LDS and the epilogue reuses the slots):
       MFMA 169..192  the reads of tile t+1's k-step-0 B fragments and first A fragments; the first ATAIL pieces of A(t+2)
     A(t+1) is always issued before B(t+2), so the counted wait leaves exactly the 8 newer weight pieces in flight. Two barriers and
     no VALU instruction per K-tile; the loop body is two tiles long, left after either. Every wait is derived from the issue order;
-    check_wait_coverage() proves both hazards and check_products() the operand of every MFMA on the emitted text before it is written.
+    check_wait_coverage() (tools/gemm_asm_common.py, shared with the 192 x 256 and 192 x 384 streams) proves both hazards and
+    check_products() the operand of every MFMA on the emitted text before it is written.
   * one accumulator chain per output element, K ascending, A = activations, B = weights: bit-identical to the 192 x 256 stream and to
     the 192 x 128 ring kernel on the same operands.
 
@@ -41,13 +42,14 @@ import os
 import re
 import sys
 
+from gemm_asm_common import Slots, Stream, WaitCoverageError, check_wait_coverage, clobbers_inc, emit, finish, knobs, read_slot_from, vr, walk
+
 MI, NI = 12, 8
 MI_AGPR = 8                   # row fragments 0..7 accumulate in AGPRs, 8..11 in VGPRs
 NA, NB = 12, 8                # LDS-DMA pieces per wave and K-tile
 A_BYTES = 384 * 128           # 49152 per A slot
 B_BYTES = 256 * 128           # 32768 per B slot
-A_SLOTS, B_SLOTS = 2, 2
-B_BASE = A_SLOTS * A_BYTES    # LDS: [A0][A1][B0][B1] = 163840 bytes
+A_SLOTS, B_SLOTS = 2, 2       # LDS: [A0][A1][B0][B1] = 163840 bytes
 BSET = (0, 32)                # B fragments of the two k-steps
 ARING = 64
 VACC = 80
@@ -67,29 +69,12 @@ NEXT_FIRST, NEXT_EVERY = 169, 2
 TDMA_FIRST, TDMA_EVERY = 170, 6
 STAMPS = "--stamps" in sys.argv   # diagnostic build (tools/ubench/gemm_tall_stamps.hip): s_memtime at the phase boundaries of body 0
 # schedule knobs for A/B builds: TALL_KNOBS="ring=4,bar1=16,atail=4,adma0=2,admae=3,bdma0=26,bdmae=4,bar2=168,next=169,nexte=2,tdma0=170,tdmae=6"
-for _kv in filter(None, os.environ.get("TALL_KNOBS", "").split(",")):
-    _k, _v = _kv.split("=")
-    _v = int(_v)
-    if _k == "ring": RING = _v
-    elif _k == "b1": B1_FIRST = _v
-    elif _k == "b1e": B1_EVERY = _v
-    elif _k == "bar1": BAR1_AFTER = _v
-    elif _k == "atail": ATAIL = _v
-    elif _k == "adma0": ADMA_FIRST = _v
-    elif _k == "admae": ADMA_EVERY = _v
-    elif _k == "bdma0": BDMA_FIRST = _v
-    elif _k == "bdmae": BDMA_EVERY = _v
-    elif _k == "bar2": BAR2_AFTER = _v
-    elif _k == "next": NEXT_FIRST = _v
-    elif _k == "nexte": NEXT_EVERY = _v
-    elif _k == "tdma0": TDMA_FIRST = _v
-    elif _k == "tdmae": TDMA_EVERY = _v
-    else: raise SystemExit(f"unknown knob {_k}")
+globals().update(knobs("TALL_KNOBS", {"ring": "RING", "b1": "B1_FIRST", "b1e": "B1_EVERY", "bar1": "BAR1_AFTER", "atail": "ATAIL",
+                                      "adma0": "ADMA_FIRST", "admae": "ADMA_EVERY", "bdma0": "BDMA_FIRST", "bdmae": "BDMA_EVERY", "bar2": "BAR2_AFTER",
+                                      "next": "NEXT_FIRST", "nexte": "NEXT_EVERY", "tdma0": "TDMA_FIRST", "tdmae": "TDMA_EVERY"}))
 assert RING in (3, 4) and 0 <= ATAIL <= NA
-
-
-def vr(b, n=4):
-    return f"v[{b}:{b + n - 1}]"
+read_slot = read_slot_from(S1)
+SLOTS = Slots(A_SLOTS, A_BYTES, B_SLOTS, B_BYTES, read_slot)
 
 
 def acc(mi, ni):
@@ -126,13 +111,9 @@ def actions(m):
     return out
 
 
-class Gen:
-    def __init__(self):
-        self.lines = []
-        self.pending = []   # names of LDS reads in issue order (they return in order)
-
-    def e(self, s):
-        self.lines.append(s)
+class Gen(Stream):
+    A_SLOTS, A_BYTES, B_SLOTS, B_BYTES = A_SLOTS, A_BYTES, B_SLOTS, B_BYTES
+    SOFF_A, SOFF_B, STAMP0 = SA, SB, STAMP0
 
     def addr(self, slot, kind, ks):
         if slot == 0:
@@ -147,32 +128,6 @@ class Gen:
     def read_b(self, t, ks, ni):
         self.e(f"ds_read_b128 {vr(BSET[ks] + 4 * ni)}, {self.addr(t % B_SLOTS, 'B', ks)} offset:{ni * 2048}")
         self.pending.append(("B", ks, ni))
-
-    def wait_reads(self, idx):
-        """counted wait: pending[idx] (and every older read) has returned"""
-        n = len(self.pending) - 1 - idx
-        self.e(f"s_waitcnt lgkmcnt({min(n, 15)})")   # 4-bit field: a smaller count waits for more, never for less
-        self.pending = self.pending[idx + 1:] if n <= 15 else self.pending[len(self.pending) - 15:]
-
-    def need(self, name):
-        if name in self.pending:
-            self.wait_reads(len(self.pending) - 1 - self.pending[::-1].index(name))
-
-    def dma_a(self, t, i):
-        dst = (t % A_SLOTS) * A_BYTES + i * 4096
-        return [f"s_add_u32 m0, %[wlds], {dst}", "s_nop 0", f"buffer_load_dwordx4 %[ao], s[36:39], s{SA + i} offen lds"]
-
-    def dma_b(self, t, i):
-        dst = B_BASE + (t % B_SLOTS) * B_BYTES + i * 4096
-        return [f"s_add_u32 m0, %[wlds], {dst}", "s_nop 0", f"buffer_load_dwordx4 %[bo], s[40:43], s{SB + i} offen lds"]
-
-    def advance(self, first, n):
-        for i in range(n):
-            self.e(f"s_add_u32 s{first + i}, s{first + i}, 128")
-
-    def stamp(self, i, p):
-        if STAMPS and p == 0:
-            self.e(f"s_memtime s[{STAMP0 + 2 * i}:{STAMP0 + 1 + 2 * i}]")
 
     def body(self, p):
         """K-tile t with t % 2 == p."""
@@ -215,13 +170,11 @@ class Gen:
                     else:
                         assert done["bar2"]
                         done["tdma"] += 1
-                    for ins in self.dma_a(p + act[1], act[2]):
-                        e(ins)
+                    self.emit_all([self.dma_a(p + act[1], act[2])])
                 elif act[0] == "bdma":
                     assert done["bar1"] and done["adma"] == NA - ATAIL and not done["bar2"]
                     done["bdma"] += 1
-                    for ins in self.dma_b(p + 2, act[2]):
-                        e(ins)
+                    self.emit_all([self.dma_b(p + 2, act[2])])
                 elif act[0] == "bar2":
                     assert done["bdma"] == NB and done["adma"] == NA - ATAIL
                     self.advance(SA, NA)
@@ -238,26 +191,17 @@ class Gen:
 
     def build(self):
         e = self.e
-        for a, b in (("s36", "%[alo]"), ("s37", "%[ahi]"), ("s38", "%[arec]"), ("s39", "0x00020000"), ("s40", "%[blo]"),
-                     ("s41", "%[bhi]"), ("s42", "%[brec]"), ("s43", "0x00020000"), ("s46", "%[nk]")):
-            e(f"s_mov_b32 {a}, {b}")
-        for first, n, step in ((SA, NA, "%[sa]"), (SB, NB, "%[sb]")):
-            e(f"s_mov_b32 s{first}, 0")
-            for i in range(1, n):
-                e(f"s_add_u32 s{first + i}, s{first + i - 1}, {step}")
+        self.descriptors((("s36", "%[alo]"), ("s37", "%[ahi]"), ("s38", "%[arec]"), ("s39", "0x00020000"), ("s40", "%[blo]"),
+                          ("s41", "%[bhi]"), ("s42", "%[brec]"), ("s43", "0x00020000"), ("s46", "%[nk]")))
+        self.piece_offsets(SA, NA, "%[sa]")
+        self.piece_offsets(SB, NB, "%[sb]")
         # issue order A0 B0 B1 + the first ATAIL pieces of A1: the same in-order history the loop's counted wait assumes
-        for i in range(NA):
-            for ins in self.dma_a(0, i):
-                e(ins)
+        self.emit_all(self.dma_a(0, i) for i in range(NA))
         self.advance(SA, NA)
         for t in (0, 1):
-            for i in range(NB):
-                for ins in self.dma_b(t, i):
-                    e(ins)
+            self.emit_all(self.dma_b(t, i) for i in range(NB))
             self.advance(SB, NB)
-        for i in range(ATAIL):
-            for ins in self.dma_a(1, i):
-                e(ins)
+        self.emit_all(self.dma_a(1, i) for i in range(ATAIL))
         for ks in range(2):
             e(f"v_add_u32 v{S1 + ks}, {A_BYTES}, %[fa{ks}]")
             e(f"v_add_u32 v{S1 + 2 + ks}, {B_BYTES}, %[fb{ks}]")
@@ -274,17 +218,7 @@ class Gen:
                     self.read_a(0, act[2])
                 elif act[0] == "bread" and act[1] == 1:
                     self.read_b(0, act[2], act[3])
-        entry = list(self.pending)
-        e("10:")
-        for p in range(2):
-            self.pending = list(entry)
-            self.body(p)
-            assert self.pending == entry, "the loop body must leave the entry state it assumes"
-            e("s_sub_u32 s46, s46, 1")
-            e("s_cmp_eq_u32 s46, 0")
-            e("s_cbranch_scc1 20f")
-        e("s_branch 10b")
-        e("20:")
+        self.loop(2, 46, list(self.pending))
         e("s_waitcnt vmcnt(0) lgkmcnt(0)")   # nothing of this wave may land in LDS after the epilogue takes it over
         e("s_nop 7")                          # the last MFMAs' results are read by ds_write / v_accvgpr_read next
         e("s_nop 7")
@@ -296,104 +230,8 @@ class Gen:
                 for r in range(4):   # the layout gemm_tall_384x256_dump.inc gives a 32-row group, 16 KB per group
                     e(f"ds_write_b32 %[sp], v{VACC + ((mi - MI_AGPR) * NI + ni) * 4 + r} offset:{grp * 16384 + ((half * 16 + r) * (16 * NI) + ni * 16) * 4}")
         e("s_waitcnt lgkmcnt(0)")
-        if STAMPS:   # lane 0 of every wave writes its 8 stamps of the last pass through body 0: dbg[8] u64
-            for i in range(16):
-                e(f"v_mov_b32 v{i}, s{STAMP0 + i}")
-            e("v_mov_b32 v16, 0")
-            for i in range(8):
-                e(f"global_store_dwordx2 v16, v[{2 * i}:{2 * i + 1}], %[dbg] offset:{i * 8}")
-            e("s_waitcnt vmcnt(0)")
+        self.store_stamps()
         return self.lines
-
-
-class WaitCoverageError(AssertionError):
-    pass
-
-
-def read_slot(a):
-    """address operand of a ds_read -> (kind, slot, k-step)"""
-    if a.startswith("%[fa"):
-        return "A", 0, int(a[4])
-    if a.startswith("%[fb"):
-        return "B", 0, int(a[4])
-    r = int(a[1:]) - S1
-    return ("A", 1, r) if r < 2 else ("B", 1, r - 2)
-
-
-def walk(lines, iterations):
-    i10, ibr = lines.index("10:"), lines.index("s_branch 10b")
-    return lines[:i10] + lines[i10 + 1:ibr] * iterations + lines[ibr + 1:]
-
-
-def check_wait_coverage(lines, iterations=3):
-    """Static proof of the LDS-DMA / ds_read ordering of the emitted stream (same rules as tools/gen_gemm_asm_dtl.py):
-      RAW  a ds_read of slot s needs every LDS-DMA issued into s to be retired by a counted vmcnt wait that is followed by a barrier;
-      WAR  an LDS-DMA into slot s needs every earlier ds_read of s to be retired by an lgkmcnt wait that is followed by a barrier.
-    Walks prologue + iterations x loop body + exit with branches not taken."""
-    seq = walk(lines, iterations)
-    regions = [("A", i) for i in range(A_SLOTS)] + [("B", i) for i in range(B_SLOTS)]
-    vm, lg, fills, reads = [], [], {r: [] for r in regions}, {r: [] for r in regions}
-    m0 = None
-    n_reads = n_dma = 0
-    for pos, ins in enumerate(seq):
-        mm = re.match(r"s_add_u32 m0, %\[wlds\], (\d+)", ins)
-        if mm:
-            m0 = int(mm.group(1))
-            continue
-        if ins.startswith("buffer_load_dwordx4") and ins.endswith("lds"):
-            slot = ("A", m0 // A_BYTES) if m0 < B_BASE else ("B", (m0 - B_BASE) // B_BYTES)
-            for r in reads[slot]:
-                if r["state"] != "fenced":
-                    raise WaitCoverageError(f"WAR: LDS-DMA into slot {slot} at {pos} while the ds_read at {r['pos']} is only '{r['state']}'")
-            reads[slot] = []
-            op = {"state": "inflight", "pos": pos}
-            vm.append(op)
-            fills[slot].append(op)
-            n_dma += 1
-            m0 = None
-            continue
-        mm = re.match(r"ds_read_b128 v\[\d+:\d+\], (\S+) offset:(\d+)", ins)
-        if mm:
-            slot = read_slot(mm.group(1))[:2]
-            if not fills[slot]:
-                raise WaitCoverageError(f"RAW: ds_read of slot {slot} at {pos} before anything was staged")
-            for f in fills[slot]:
-                if f["state"] != "visible":
-                    raise WaitCoverageError(f"RAW: ds_read of slot {slot} at {pos} ({ins}) while the LDS-DMA at {f['pos']} is only '{f['state']}'")
-            op = {"state": "issued", "pos": pos}
-            lg.append(op)
-            reads[slot].append(op)
-            n_reads += 1
-            continue
-        if ins.startswith("ds_write"):   # the accumulators that leave through LDS: every slot must be quiet
-            for s in regions:
-                if any(f["state"] != "visible" for f in fills[s]) or any(r["state"] != "fenced" for r in reads[s]):
-                    raise WaitCoverageError(f"WAR: ds_write at {pos} while slot {s} is still in use")
-            continue
-        if ins.startswith("s_waitcnt"):
-            mv, ml = re.search(r"vmcnt\((\d+)\)", ins), re.search(r"lgkmcnt\((\d+)\)", ins)
-            if mv:
-                keep = int(mv.group(1))
-                done, vm = (vm[:len(vm) - keep], vm[len(vm) - keep:]) if keep < len(vm) else ([], vm)
-                for op in done:
-                    op["state"] = "retired"
-            if ml:
-                keep = int(ml.group(1))
-                done, lg = (lg[:len(lg) - keep], lg[len(lg) - keep:]) if keep < len(lg) else ([], lg)
-                for op in done:
-                    op["state"] = "done"
-            continue
-        if ins == "s_barrier":
-            for s in regions:
-                for op in fills[s]:
-                    if op["state"] == "retired":
-                        op["state"] = "visible"
-                for op in reads[s]:
-                    if op["state"] == "done":
-                        op["state"] = "fenced"
-    if not n_reads or not n_dma:
-        raise WaitCoverageError("checker saw no LDS traffic - the stream format changed")
-    return {"reads": n_reads, "fills": n_dma, "instructions": len(seq)}
 
 
 def check_products(lines, iterations=3):
@@ -464,44 +302,12 @@ def dump_inc():
 
 
 def main():
-    g = Gen()
-    lines = g.build()
-    # m0 (the LDS-DMA destination) is a reserved register: the block saves it in an SGPR of its own and restores it on the way out,
-    # so the surrounding HIP code sees m0 unchanged and the clobber list does not name it
-    lines = [f"s_mov_b32 s{SAVE_M0}, m0"] + lines + [f"s_mov_b32 m0, s{SAVE_M0}"]
-    if "--inject-raw-race" in sys.argv:   # checker self-test: the second barrier's wait leaves the activations of tile t+1 in flight
-        k = lines.index(f"s_waitcnt vmcnt({NB}) lgkmcnt(0)", lines.index("10:"))
-        lines[k] = f"s_waitcnt vmcnt({NB + 1}) lgkmcnt(0)"
-    if "--inject-war-race" in sys.argv:   # checker self-test: the first barrier is dropped
-        k = lines.index("s_barrier", lines.index("10:"))
-        del lines[k]
-    stats = check_wait_coverage(lines)
+    # --inject-raw-race: the second barrier's wait leaves the activations of tile t+1 in flight
+    lines = finish(Gen(STAMPS).build(), SAVE_M0, (f"s_waitcnt vmcnt({NB}) lgkmcnt(0)", f"s_waitcnt vmcnt({NB + 1}) lgkmcnt(0)"))
+    stats = check_wait_coverage(lines, SLOTS)
     check_products(lines)
-    here = os.path.dirname(os.path.abspath(__file__))
-    d = os.path.join(here, "..", "ltx-video-swift-mlx_amd", "csrc")
-    body = ["// GENERATED by tools/gen_gemm_asm_tall.py - do not edit. gfx950 assembly main loop of gemm_bf16_kernel_tall (gemm.hip).\n"]
-    body += ['"' + ln + '\\n\\t"\n' for ln in lines]
-    diag = STAMPS or os.environ.get("TALL_KNOBS")
-    path = os.path.join(d, "gemm_tall_384x256_stamps.inc" if diag else "gemm_tall_384x256.inc")
-    clob = [f"v{i}" for i in range(NV)] + [f"a{i}" for i in range(256)] + [f"s{i}" for i in range(36, SAVE_M0 + 1)] + ["vcc", "scc", "memory"]
-    clob_text = "// GENERATED by tools/gen_gemm_asm_tall.py - do not edit. Registers the assembly main loop assigns by hand.\n"
-    for i in range(0, len(clob), 12):
-        clob_text += ", ".join('"' + c + '"' for c in clob[i:i + 12]) + ("," if i + 12 < len(clob) else "") + "\n"
-    others = ((os.path.join(d, "gemm_tall_384x256_clobbers.inc"), clob_text), (os.path.join(d, "gemm_tall_384x256_dump.inc"), dump_inc()))
-    if "--check" in sys.argv:
-        same = os.path.exists(path) and open(path).read() == "".join(body)
-        same = same and all(os.path.exists(p) and open(p).read() == t for p, t in others)
-        print(f"wait coverage ok: {stats}; committed files {'match' if same else 'DIFFER'}")
-        sys.exit(0 if same else 4)
-    with open(path, "w") as f:
-        f.write("".join(body))
-    if diag:
-        print(f"{len(lines)} lines -> {os.path.normpath(path)}; {stats}")
-        return
-    for p, t in others:
-        with open(p, "w") as f:
-            f.write(t)
-    print(f"{len(lines)} lines, {sum(1 for ln in lines if 'v_mfma' in ln)} MFMAs; {stats}")
+    emit("gen_gemm_asm_tall.py", "gemm_bf16_kernel_tall", "gemm_tall_384x256", STAMPS or os.environ.get("TALL_KNOBS"), lines, stats,
+         {"gemm_tall_384x256_clobbers.inc": clobbers_inc("gen_gemm_asm_tall.py", NV, 256, SAVE_M0), "gemm_tall_384x256_dump.inc": dump_inc()})
 
 
 if __name__ == "__main__":
