@@ -224,10 +224,7 @@ DiTModel::CtxCache* prepare_context(ltx_ctx* ctx, DiTModel* m, const DiTForwardA
 // measured cost - the 48-layer headline forward sits 2.419e-3 from the oracle against 2.416e-3 with the f32 store, the 8-step loops move in
 // the fourth digit ("extra roundings") - and option "qk_f32" = 1 (ltx_ctx_set_option) restores the f32 store. The
 // choice depends on nothing but that option, so sequence-parallel ranks and single-GPU runs round alike. The f32 workspaces (ws_qk, ws_qc)
-// are reused at half their size.
-static bool qk_store_bf16() {
-    return ltx_opt(OPT_QK_F32) == 0;
-}
+// are reused at half their size. dit_forward reads the option once, with its other two.
 
 void dit_forward(ltx_ctx* ctx, DiTModel* m, const DiTForwardArgs& a) {
     const int D = m->D, L = m->L, B = a.B;
@@ -333,7 +330,10 @@ void dit_forward(ltx_ctx* ctx, DiTModel* m, const DiTForwardArgs& a) {
     }
     const long mod_bs = (long)L * 6 * D;  // batch stride of mod
 
-    const bool qkv_fused_on = ltx_opt(OPT_QKV_FUSED) != 0;  // read once per forward
+    // the options of a forward, read once: every block sees the same values
+    const bool qkv_fused_on = ltx_opt(OPT_QKV_FUSED) != 0;
+    const bool qk_bf16 = ltx_opt(OPT_QK_F32) == 0;  // the q|k and cross-q stores (comment above dit_forward)
+    const bool sp_overlap_on = ltx_opt(OPT_SP_OVERLAP) != 0;
     bool xn_ready = false;  // the previous block's last GEMM launch already wrote this block's first adaLN rows (NormAfter)
     for (int l = 0; l < L; ++l) {
         const DiTBlock& blk = m->blocks[l];
@@ -347,7 +347,6 @@ void dit_forward(ltx_ctx* ctx, DiTModel* m, const DiTForwardArgs& a) {
             // Opt-in (option "sp_overlap" = 1) until a run on two or more GPUs has confirmed it: the side-stream gather shares ONE RCCL
             // communicator with the K gather on the context's stream, and no box reachable so far could execute that with two ranks
             // (round-3 advice). The self-test hook always takes the branch - that is what it is for.
-            const bool sp_overlap_on = ltx_opt(OPT_SP_OVERLAP) != 0;
             const bool overlap = sp && !a.sp_gather && dist_can_overlap(ctx) && (sp_overlap_on || sp_selftest);
             if (sp) {
                 gemm_vt(xn, D, T, blk.v1, vt, T, st, sk);  // V^T of the local tokens, dense [D][T]
@@ -358,7 +357,7 @@ void dit_forward(ltx_ctx* ctx, DiTModel* m, const DiTForwardArgs& a) {
                     launch_sp_vt_interleave(m->ws_sp_vtg.as<bf16_t>(), vt_full, NW, D, T, TfullPad, side);
                 }
             }
-            const bool qkb = qk_store_bf16();
+            const bool qkb = qk_bf16;
             GemmEpilogue eqk;
             if (qkb) {
                 eqk.out_bf16 = (bf16_t*)qk;
@@ -427,7 +426,7 @@ void dit_forward(ltx_ctx* ctx, DiTModel* m, const DiTForwardArgs& a) {
             GemmEpilogue eq;
             eq.out_f32 = qc;
             eq.ld_f32 = D;
-            const bool q2b = qk_store_bf16();
+            const bool q2b = qk_bf16;
             if (q2b) {
                 eq.out_f32 = nullptr;
                 eq.out_bf16 = (bf16_t*)qc;

@@ -1288,451 +1288,6 @@ __global__ __launch_bounds__(WGM * WGN * 64) void gemm_bf16_kernel_v2(const Gemm
 #include "conv_halo.inc"
 #include "conv_halo2.inc"
 
-#ifdef LTX_EXPERIMENTS
-// ---------------------------------------------------------------------------------------------------------------
-// Few-row launches (M <= 128: the DiT at 256x256x9 = 128 tokens), round 3. Such a GEMM streams its weights once and is bound by
-// how many bytes a CU keeps in flight against the HBM latency, not by MFMAs (16 per wave and K-tile). The ring kernel above stages
-// activations and weights through ONE ring with one in-order counter: three K-tiles = 72 KB in flight, two thirds of them the
-// activation tile, which comes from L2 and needs no such cover. Here the two operands have rings of their own and waves of their own:
-//   waves 0, 1 stage the activation tile (128 x 64 bf16 = 16 pieces) two K-tiles ahead: 3 slots, 48 KB;
-//   waves 2, 3 stage the weights in MACRO-tiles of four K-tiles, two macro-tiles ahead: a piece is 2 rows x 512 contiguous bytes
-//              (8 rows x 128 B pieces fetch a quarter of a DRAM page per row visit: the ring kernel streams weights at ~3 TB/s);
-//              3 slots of 32 KB - or, QB, the 8-bit codes of a quantised Linear: pieces of 4 rows x 256 B, 4 slots of 16 KB, three
-//              macro-tiles ahead, plus the group scales / biases of the macro-tile (two dwords per row and wave);
-// each role waits on its own vmcnt (the counter is per wave), one workgroup barrier per K-tile publishes both. All four waves run the
-// MFMAs (wave tile 64 x 32). QB: the codes of tile t+1 are converted to the bf16 image (two slots) during K-tile t, w' = bf16(q * scale
-// + bias) - quant_decode_kernel's arithmetic, bit-identical to the scratch path - so a quantised few-row GEMM reads half the bytes.
-// Split-K (grid.y) and the epilogue are the ring kernel's.
-// MEASURED, NOT SELECTED (tile_cfg 30, experiments build): bit-exact (tests/test_experiments_gpu.py), and 9 % SLOWER than the 128x64
-// ring kernel at 128 tokens - 22.9 / 25.9 / 45.0 us against 20.95 / 23.3 / 41.1 us for the N = 4096 / 8192 / 16384 launches of a block
-// (rocprofv3, profiles/r03_config1_fewrow.txt); forward 12.7 against 11.9 ms. Both kernels stream the weights at ~3 TB/s whatever the
-// run length per DRAM row (128 B or 512 B). The activation tile's re-fetch (16 KB per K-tile from L2 beside 8 KB of weights) was this
-// kernel's premise and is NOT the bound: 16-row launches of the ring kernel are only 7 % faster than 128-row ones
-// (profiles/r03_fewrow_bounds.txt); a six-slot ring there gained 5 % and is what the product now runs.
-// ---------------------------------------------------------------------------------------------------------------
-template <int N>
-LTX_DEVFN void wait_vmcnt_only() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-// s_waitcnt vmcnt(n) for a run-time n (immediates only): n is wave-uniform, <= 45
-LTX_DEVFN void wait_vmcnt_dyn(int n) {
-    switch (n) {
-#define LTX_W(K) case K: wait_vmcnt_only<K>(); break;
-        LTX_W(0) LTX_W(1) LTX_W(2) LTX_W(3) LTX_W(4) LTX_W(5) LTX_W(6) LTX_W(7) LTX_W(8) LTX_W(9) LTX_W(10) LTX_W(11) LTX_W(12) LTX_W(13) LTX_W(14)
-        LTX_W(15) LTX_W(16) LTX_W(17) LTX_W(18) LTX_W(19) LTX_W(20) LTX_W(21) LTX_W(22) LTX_W(23) LTX_W(24) LTX_W(25) LTX_W(26) LTX_W(27) LTX_W(28)
-        LTX_W(29) LTX_W(30) LTX_W(31) LTX_W(32) LTX_W(33) LTX_W(34) LTX_W(35) LTX_W(36) LTX_W(37) LTX_W(38) LTX_W(39) LTX_W(40) LTX_W(41) LTX_W(42)
-        LTX_W(43) LTX_W(44) LTX_W(45)
-#undef LTX_W
-        default: wait_vmcnt_only<0>(); break;
-    }
-}
-
-template <bool QB>
-__global__ __launch_bounds__(256, 1) void gemm_fewrow_kernel(const GemmArgs g) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int BM = 128, BN = 64, WGM = 2, WGN = 2, WM = 64, WN = 32, MI = 4, NI = 2;
-    constexpr int A_BYTES = BM * ROW_BYTES, B_BYTES = BN * ROW_BYTES;
-    constexpr int NA = 3, PA = NA - 1;                       // activation ring (K-tiles)
-    constexpr int MT = 4;                                    // K-tiles per weight macro-tile: 256 elements = 512 B (256 B of codes) of a row
-    constexpr int NBM = QB ? 4 : 3, PBM = NBM - 1;           // weight ring (macro-tiles)
-    constexpr int BM_BYTES = QB ? BN * MT * 64 : BN * MT * ROW_BYTES;   // 16 KB of codes / 32 KB of bf16 weights
-    constexpr int SB_BYTES = 1024;                           // QB: [scale dword 0][scale dword 1][bias dword 0][bias dword 1] x 64 rows
-    constexpr int A_OFF = 0, B_OFF = NA * A_BYTES;           // bf16 macro ring, or (QB) the two-slot bf16 image of single K-tiles
-    constexpr int Q_OFF = B_OFF + 2 * B_BYTES, SB_OFF = Q_OFF + NBM * BM_BYTES;
-    constexpr int APW = 8;                                   // LDS-DMA pieces per K-tile of an activation wave
-    constexpr int BPW = QB ? 10 : 16;                        // ... per MACRO-tile of a weight wave
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wr = wave / WGN, wc = wave % WGN;
-    const bool a_role = wave < 2;
-    const int bid = xcd_remap(blockIdx.x, gridDim.x);
-    const int n0 = bid * BN, m0 = 0;
-    int nk = g.K / BK, kt0 = 0;
-    const int groups = g.K / BK;
-    if (g.split_k > 1) {  // the launcher guarantees whole macro-tiles per split
-        const int z = blockIdx.y;
-        kt0 = (int)((long)nk * z / g.split_k);
-        nk = (int)((long)nk * (z + 1) / g.split_k) - kt0;
-    }
-    const int nm = nk / MT;  // macro-tiles of this workgroup
-    // ---- staging sources ----
-    const bf16_t* asrc[APW];
-    const char* bsrc = nullptr;   // weight wave: this lane's 16 bytes of piece 0 of macro-tile 0; piece i is `bstep` rows further down
-    long bstep = 0;
-    const bf16_t* sbsrc = nullptr;
-    if (a_role) {
-        const int srow = lane >> 3, pch = lane & 7;
-#pragma unroll
-        for (int i = 0; i < APW; ++i) {
-            const int row = (wave + 2 * i) * 8 + srow;
-            const int gm = row < g.M ? row : g.M - 1;
-            asrc[i] = g.A + (long)gm * g.lda + (pch ^ ((row >> 1) & 7)) * 8;
-        }
-    } else {
-#pragma unroll
-        for (int i = 0; i < APW; ++i) asrc[i] = nullptr;
-        if constexpr (QB) {
-            // piece = 4 rows x 256 B of codes; wave w-2 takes pieces (w-2), (w-2)+2, ...: rows 4 piece + lane / 16, chunk lane % 16
-            const int row = (wave - 2) * 4 + (lane >> 4);
-            int gn = n0 + row;
-            gn = gn < g.N ? gn : g.N - 1;
-            bsrc = (const char*)(g.Bq + (long)gn * g.K + (long)kt0 * BK + (lane & 15) * 16);
-            bstep = 8L * g.K;   // two pieces = 8 rows further (ragged N is handled by the caller: N % 64 == 0 for this instance)
-            int gs = n0 + lane;
-            gs = gs < g.N ? gs : g.N - 1;
-            sbsrc = (wave == 2 ? g.Bqs : g.Bqb) + (long)gs * groups + kt0;
-        } else {
-            // piece = 2 rows x 512 B; physical chunk p of row r holds logical chunk p ^ (r & 15) (fragment reads: 16 rows, one chunk);
-            // the source addresses are formed in stage_b
-        }
-    }
-    auto stage_a = [&](int j) {  // relative K-tile j -> activation slot j % NA
-        char* base = smem + A_OFF + (j % NA) * A_BYTES;
-#pragma unroll
-        for (int i = 0; i < APW; ++i)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(asrc[i] + (long)(kt0 + j) * BK),
-                                             (__attribute__((address_space(3))) void*)(base + (wave + 2 * i) * 1024), 16, 0, 0);
-    };
-    auto stage_b = [&](int m) {  // relative macro-tile m -> weight slot m % NBM
-        if constexpr (QB) {
-            char* base = smem + Q_OFF + (m % NBM) * BM_BYTES;
-#pragma unroll
-            for (int i = 0; i < 8; ++i)
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(bsrc + i * bstep + (long)m * MT * BK),
-                                                 (__attribute__((address_space(3))) void*)(base + ((wave - 2) + 2 * i) * 1024), 16, 0, 0);
-            char* sb = smem + SB_OFF + (m % NBM) * SB_BYTES + (wave - 2) * 512;
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(sbsrc + m * MT + 2 * i),
-                                                 (__attribute__((address_space(3))) void*)(sb + i * 256), 4, 0, 0);
-        } else {
-            char* base = smem + B_OFF + (m % NBM) * BM_BYTES;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                // piece (wave - 2) + 2 i = rows 2 piece, 2 piece + 1; the swizzle term (row & 15) changes from piece to piece
-                const int row = ((wave - 2) + 2 * i) * 2 + (lane >> 5);
-                const bf16_t* src = g.B + (long)(n0 + row) * g.ldb + (long)(kt0 + m * MT) * BK + (((lane & 31) ^ (row & 15)) * 8);
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                                 (__attribute__((address_space(3))) void*)(base + ((wave - 2) + 2 * i) * 1024), 16, 0, 0);
-            }
-        }
-    };
-    // QB: codes of relative K-tile j -> bf16 image slot j & 1. Thread = (row tid / 4, 16 codes tid % 4).
-    auto convert_q = [&](int j) {
-        if constexpr (QB) {
-            const int row = tid >> 2, c4 = tid & 3;
-            const int m = j / MT, sub = j % MT;
-            const uint4 raw = *(const uint4*)(smem + Q_OFF + (m % NBM) * BM_BYTES + row * 256 + sub * 64 + c4 * 16);
-            const char* sbp = smem + SB_OFF + (m % NBM) * SB_BYTES + (sub >> 1) * 256 + row * 4;
-            const uint32_t sw_ = *(const uint32_t*)sbp, bw_ = *(const uint32_t*)(sbp + 512);
-            const float scale = bf16_to_f32((bf16_t)((sub & 1) ? (sw_ >> 16) : (sw_ & 0xffffu)));
-            const float bias = bf16_to_f32((bf16_t)((sub & 1) ? (bw_ >> 16) : (bw_ & 0xffffu)));
-            const uint32_t wd[4] = {raw.x, raw.y, raw.z, raw.w};
-            uint32_t out[8];
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int jj = 0; jj < 2; ++jj) {
-                    const float q0 = (float)((wd[i] >> (16 * jj)) & 0xffu), q1 = (float)((wd[i] >> (16 * jj + 8)) & 0xffu);
-                    out[i * 2 + jj] = pack_bf16x2(q0 * scale + bias, q1 * scale + bias);
-                }
-            char* brow = smem + B_OFF + (j & 1) * B_BYTES + row * ROW_BYTES;
-            const int sw = (row >> 1) & 7;
-            *(uint4*)(brow + (((2 * c4) ^ sw) << 4)) = uint4{out[0], out[1], out[2], out[3]};
-            *(uint4*)(brow + (((2 * c4 + 1) ^ sw) << 4)) = uint4{out[4], out[5], out[6], out[7]};
-        }
-    };
-    auto role_wait = [&](int need_through, int issued_through, int per) {
-        int keep = issued_through - need_through;
-        keep = keep < 0 ? 0 : keep;
-        wait_vmcnt_dyn(keep * per);
-    };
-
-    const int frow = lane & 15;
-    const int fsw = (lane >> 1) & 7;
-    const int foff0 = frow * ROW_BYTES + ((((lane >> 4) + 0) ^ fsw) << 4);
-    const int foff1 = frow * ROW_BYTES + ((((lane >> 4) + 4) ^ fsw) << 4);
-    const int a_wave_off = (wr * WM) * ROW_BYTES;
-    f32x4 acc[MI][NI];
-#pragma unroll
-    for (int i = 0; i < MI; ++i)
-#pragma unroll
-        for (int j = 0; j < NI; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    // ---- prologue ----
-    int a_issued = -1, b_issued = -1;  // last relative K-tile / macro-tile this role has staged
-    if (a_role) {
-        for (int j = 0; j < PA && j < nk; ++j) { stage_a(j); a_issued = j; }
-    } else {
-        for (int m = 0; m < PBM && m < nm; ++m) { stage_b(m); b_issued = m; }
-    }
-    if constexpr (QB) {  // the first tile's image needs a barrier of its own
-        if (!a_role) role_wait(0, b_issued, BPW);
-        raw_barrier();
-        convert_q(0);
-        wait_lgkm_barrier();
-    }
-    ResidualTile<BM, BN, WGM, WGN> rt;
-    for (int t = 0; t < nk; ++t) {
-        const int m = t / MT, sub = t % MT;
-        // K-tile t of the activations and macro-tile m of the weights (QB: the macro-tile of K-tile t+1, converted below) must have landed
-        if (a_role) role_wait(t, a_issued, APW);
-        else role_wait(QB ? ((t + 1 < nk ? t + 1 : t) / MT) : m, b_issued, BPW);
-        if constexpr (QB) wait_lgkm_barrier(); else raw_barrier();   // QB: also publishes the image converted during K-tile t-1
-        // refill what K-tile t-1 / macro-tile m-1 occupied: every wave is past its reads (QB: past the conversion of its last K-tile)
-        if (a_role) {
-            if (t + PA < nk) { stage_a(t + PA); a_issued = t + PA; }
-        } else if (sub == (QB ? 1 : 0)) {
-            if (m + PBM < nm) { stage_b(m + PBM); b_issued = m + PBM; }
-        }
-        if (t == nk - 1 && !g.ep.d2s && g.split_k <= 1 && n0 + BN <= g.N) {  // residual / bias under the last tile's MFMAs
-            gemm_bias_prefetch(g, n0, wc, lane, rt);
-            if (g.ep.resid) gemm_residual_prefetch(g, m0, n0, wr, wc, lane, rt);
-        }
-        const char* abase = smem + A_OFF + (t % NA) * A_BYTES + a_wave_off;
-        s16x8 fa[2][MI], fb[2][NI];
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-#pragma unroll
-            for (int i = 0; i < MI; ++i) fa[k][i] = *(const s16x8*)(abase + i * 16 * ROW_BYTES + (k ? foff1 : foff0));
-#pragma unroll
-            for (int j = 0; j < NI; ++j) {
-                if constexpr (QB) {
-                    fb[k][j] = *(const s16x8*)(smem + B_OFF + (t & 1) * B_BYTES + (wc * WN + j * 16) * ROW_BYTES + (k ? foff1 : foff0));
-                } else {
-                    // macro image: row stride 512 B, logical chunk sub*8 + 4k + (lane >> 4) at physical chunk ^ (row & 15)
-                    const int row = wc * WN + j * 16 + frow;
-                    fb[k][j] = *(const s16x8*)(smem + B_OFF + (m % NBM) * BM_BYTES + row * (MT * ROW_BYTES) +
-                                               (((sub * 8 + 4 * k + (lane >> 4)) ^ frow) << 4));
-                }
-            }
-        }
-        if constexpr (QB) {
-            if (t + 1 < nk) convert_q(t + 1);
-        }
-#pragma unroll
-        for (int k = 0; k < 2; ++k)
-#pragma unroll
-            for (int i = 0; i < MI; ++i)
-#pragma unroll
-                for (int j = 0; j < NI; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, fa[k][i]), __builtin_bit_cast(bf16x8_t, fb[k][j]),
-                                                                        acc[i][j], 0, 0, 0);
-    }
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");  // the epilogue reuses the LDS
-    if (g.split_k > 1) {
-        GemmArgs gs = g;  // raw partial tile -> workspace slice of this split
-        gs.ep = GemmEpilogue{};
-        gs.ep.out_f32 = g.split_ws + (long)blockIdx.y * g.M * g.N;
-        gs.ep.ld_f32 = g.N;
-        gemm_epilogue<BM, BN, WGM, WGN>(acc, gs, m0, n0, wr, wc, lane, wave, smem);
-        return;
-    }
-    gemm_epilogue<BM, BN, WGM, WGN>(acc, g, m0, n0, wr, wc, lane, wave, smem, &rt);
-}
-#endif  // LTX_EXPERIMENTS (few-row kernel)
-
-#ifdef LTX_EXPERIMENTS
-// ---------------------------------------------------------------------------------------------------------------
-// The ring kernel on v_mfma_f32_32x32x16_bf16 (dense launches). Same LDS ring, counted waits and skewed fragment pipeline as _v2;
-// what changes is the issue budget: an MFMA holds the SIMD's vector issue port for 8 cycles whether it computes for 16 or for 32
-// (MI355X_MICROARCH.md, 'vector-instruction ISSUE cost'), so the 12 MFMAs of a K-tile leave 24 free cycles per gap where the 24 of
-// the 16x16x32 form leave 8 - and the LDS-DMA pieces and fragment reads that the 16x16x32 loop cannot hide fit. Waves 2 x 4, per
-// wave 96 x 32 = 3 x 1 blocks of 32 x 32 (48 accumulator registers, as before).
-// MEASURED, NOT SELECTED (tile_cfg 31, experiments build): bit-identical to the 16x16x32 ring kernel on integer data, and slower -
-// 1536x4096x4096 951 against 1021 TFLOP/s, K = 16384 1083 against 1178 (HBM-cold weights, same process): a 96 x 32 wave tile reads
-// 16 KB of fragments per K-tile where 48 x 64 reads 14, and the compiler bunches the LDS-DMA pieces in one gap.
-//   operands: lane l holds row (l & 31), k = 8 (l >> 5) .. +7 of the 16-deep k-step  -> one ds_read_b128 per block and k-step
-//   result:   lane l holds column (l & 31), rows 8 (v / 4) + 4 (l >> 5) + (v % 4), v = 0..15
-// ---------------------------------------------------------------------------------------------------------------
-template <int BM, int BN, int NSTAGE>
-__global__ __launch_bounds__(512) void gemm_bf16_kernel_m32(const GemmArgs g) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int WGM = 2, WGN = 4, NW = 8;
-    constexpr int WM = BM / WGM, WN = BN / WGN, MI = WM / 32, NI = WN / 32;
-    static_assert(WM % 32 == 0 && WN % 32 == 0, "32x32 blocks");
-    constexpr int A_BYTES = BM * ROW_BYTES, B_BYTES = BN * ROW_BYTES, STAGE = A_BYTES + B_BYTES;
-    constexpr int A_PER_WAVE = BM / 8 / NW, B_PER_WAVE = BN / 8 / NW;
-    static_assert(A_PER_WAVE * 8 * NW == BM && B_PER_WAVE * 8 * NW == BN, "tile rows must split evenly over the waves");
-    constexpr int LPT = A_PER_WAVE + B_PER_WAVE;
-    constexpr int PD = NSTAGE - 1;
-    constexpr int NF = 2 * (MI + NI);  // fragment reads per half K-tile (two 16-deep k-steps)
-    constexpr int NM = 2 * MI * NI;    // MFMAs per half K-tile
-    static_assert(NSTAGE >= 3, "ring needs >= 3 slots");
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wr = wave / WGN, wc = wave % WGN;
-    const int tiles_m = (g.M + BM - 1) / BM;
-    const int bid = xcd_remap(blockIdx.x, gridDim.x) + g.tile0;
-    int tm, tn;
-    tile_coords(g, bid, tiles_m, BN, tm, tn);
-    const int m0 = tm * BM, n0 = tn * BN;
-
-    const int srow = lane >> 3, pch = lane & 7;
-    const bf16_t* a_src[A_PER_WAVE];
-    const bf16_t* b_src[B_PER_WAVE];
-#pragma unroll
-    for (int i = 0; i < A_PER_WAVE; ++i) {
-        const int row = (wave + NW * i) * 8 + srow;
-        int gm = m0 + row;
-        gm = gm < g.M ? gm : g.M - 1;
-        a_src[i] = g.A + (long)gm * g.lda + (pch ^ ((row >> 1) & 7)) * 8;
-    }
-#pragma unroll
-    for (int i = 0; i < B_PER_WAVE; ++i) {
-        const int row = (wave + NW * i) * 8 + srow;
-        int gn = n0 + row;
-        gn = gn < g.N ? gn : g.N - 1;
-        b_src[i] = g.B + (long)gn * g.ldb + (pch ^ ((row >> 1) & 7)) * 8;
-    }
-    int nk = g.K / BK, kt0 = 0;
-    if (g.split_k > 1) {
-        const int z = blockIdx.y;
-        kt0 = (int)((long)nk * z / g.split_k);
-        nk = (int)((long)nk * (z + 1) / g.split_k) - kt0;
-    }
-    auto stage = [&](int slot, int kt) {
-        char* base = smem + slot * STAGE;
-#pragma unroll
-        for (int i = 0; i < A_PER_WAVE; ++i)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(a_src[i] + (long)kt * BK),
-                                             (__attribute__((address_space(3))) void*)(base + (wave + NW * i) * 1024), 16, 0, 0);
-#pragma unroll
-        for (int i = 0; i < B_PER_WAVE; ++i)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(b_src[i] + (long)kt * BK),
-                                             (__attribute__((address_space(3))) void*)(base + A_BYTES + (wave + NW * i) * 1024), 16, 0, 0);
-    };
-
-    // fragment read offsets: row (lane & 31) of a 32-row block, 16-byte chunk (lane >> 5) + 2 ks of the row, XOR-swizzled by the row
-    const int frow = lane & 31;
-    const int fsw = (lane >> 1) & 7;  // ((row >> 1) & 7) for row = 32 k + (lane & 31)
-    int foff[4];
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) foff[ks] = frow * ROW_BYTES + ((((lane >> 5) + 2 * ks) ^ fsw) << 4);
-    const int a_wave_off = (wr * WM) * ROW_BYTES;
-    const int b_wave_off = A_BYTES + (wc * WN) * ROW_BYTES;
-
-    f32x16 acc[MI][NI];
-#pragma unroll
-    for (int i = 0; i < MI; ++i)
-#pragma unroll
-        for (int j = 0; j < NI; ++j)
-#pragma unroll
-            for (int v = 0; v < 16; ++v) acc[i][j][v] = 0.f;
-
-    // two fragment sets (a half K-tile each = two k-steps): [k-step within the half][block]
-    s16x8 fa0[2][MI], fb0[2][NI], fa1[2][MI], fb1[2][NI];
-    auto load_frags = [&](int slot, int half, s16x8(&fa)[2][MI], s16x8(&fb)[2][NI]) {
-        const char* base = smem + slot * STAGE;
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-#pragma unroll
-            for (int i = 0; i < MI; ++i) fa[k][i] = *(const s16x8*)(base + a_wave_off + i * 32 * ROW_BYTES + foff[2 * half + k]);
-#pragma unroll
-            for (int j = 0; j < NI; ++j) fb[k][j] = *(const s16x8*)(base + b_wave_off + j * 32 * ROW_BYTES + foff[2 * half + k]);
-        }
-    };
-    auto mfma_one = [&](const s16x8(&fa)[2][MI], const s16x8(&fb)[2][NI], int k, int i, int j) {
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, fa[k][i]), __builtin_bit_cast(bf16x8_t, fb[k][j]),
-                                                            acc[i][j], 0, 0, 0);
-    };
-    auto mfma_first = [&](const s16x8(&fa)[2][MI], const s16x8(&fb)[2][NI]) { mfma_one(fa, fb, 0, 0, 0); };
-    auto mfma_rest = [&](const s16x8(&fa)[2][MI], const s16x8(&fb)[2][NI]) {
-#pragma unroll
-        for (int k = 0; k < 2; ++k)
-#pragma unroll
-            for (int i = 0; i < MI; ++i)
-#pragma unroll
-                for (int j = 0; j < NI; ++j)
-                    if (k + i + j > 0) mfma_one(fa, fb, k, i, j);
-    };
-
-#pragma unroll
-    for (int s = 0; s < PD; ++s)
-        if (s < nk) stage(s, kt0 + s);
-    if (nk >= PD) wait_vmcnt_barrier<(PD - 1) * LPT>(); else wait_vmcnt_barrier<0>();
-    load_frags(0, 0, fa0, fb0);
-
-    int slot = 0;
-    bool drained = false;
-    auto ktile = [&](int kt, auto steady_tag) {
-        constexpr bool STEADY = decltype(steady_tag)::value;
-        int nslot = slot + 1;
-        nslot = nslot == NSTAGE ? 0 : nslot;
-        int pslot = slot - 1;
-        pslot = pslot < 0 ? NSTAGE - 1 : pslot;
-        // ---- first half: MFMAs of k-steps 0, 1; the fragment reads of k-steps 2, 3 go two per MFMA gap
-        mfma_first(fa0, fb0);
-        __builtin_amdgcn_sched_barrier(0);
-        load_frags(slot, 1, fa1, fb1);
-        mfma_rest(fa0, fb0);
-#pragma unroll
-        for (int q = 0; q < (NF + 1) / 2; ++q) {
-            __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);  // two ds_reads
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // one MFMA
-        }
-        __builtin_amdgcn_sched_group_barrier(0x008, NM - 1 - (NF + 1) / 2, 0);
-        if constexpr (STEADY) wait_vmcnt_barrier<(PD - 2) * LPT>(); else if (!drained) wait_vmcnt_barrier<0>();
-        // ---- second half
-        mfma_first(fa1, fb1);
-        __builtin_amdgcn_sched_barrier(0);
-        if constexpr (STEADY) {
-            stage(pslot, kt0 + kt + PD);
-            load_frags(nslot, 0, fa0, fb0);
-            mfma_rest(fa1, fb1);
-            // five MFMAs to go: each gap takes one LDS-DMA piece and two of the next tile's fragment reads
-#pragma unroll
-            for (int q = 0; q < NM - 1; ++q) {
-                __builtin_amdgcn_sched_group_barrier(0x020, (LPT + NM - 2) / (NM - 1), 1);
-                __builtin_amdgcn_sched_group_barrier(0x100, (NF + NM - 2) / (NM - 1), 1);
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 1);
-            }
-        } else {
-            if (kt + 1 < nk) load_frags(nslot, 0, fa0, fb0);
-            mfma_rest(fa1, fb1);
-        }
-        slot = nslot;
-    };
-    int kt = 0;
-    for (; kt < nk - PD; ++kt) ktile(kt, std::true_type{});
-    ResidualTile<BM, BN, WGM, WGN> rt;
-    if (kt < nk) {
-        ktile(kt, std::false_type{});
-        ++kt;
-        drained = true;
-        if (!g.ep.d2s && g.split_k <= 1 && n0 + BN <= g.N && kt < nk) {
-            gemm_bias_prefetch(g, n0, wc, lane, rt);
-            if (g.ep.resid) gemm_residual_prefetch(g, m0, n0, wr, wc, lane, rt);
-        }
-    }
-    for (; kt < nk; ++kt) ktile(kt, std::false_type{});
-    __syncthreads();
-    // the 16-row slab s of this wave's tile = half (s & 1) of block s / 2: values v = 8 (s & 1) + t, t = 0..7, at row
-    // 8 (t / 4) + 4 (lane >> 5) + (t % 4) of the slab, column 32 j + (lane & 31)
-    auto put = [&](auto s_c, float* scr) {
-        constexpr int sidx = decltype(s_c)::value;
-        constexpr int blk = sidx / 2, h = sidx % 2;
-#pragma unroll
-        for (int j = 0; j < NI; ++j)
-#pragma unroll
-            for (int t = 0; t < 8; ++t)
-                scr[(8 * (t / 4) + 4 * (lane >> 5) + (t % 4)) * WN + 32 * j + (lane & 31)] = acc[blk][j][8 * h + t];
-    };
-    if (g.split_k > 1) {
-        GemmArgs gs = g;
-        gs.ep = GemmEpilogue{};
-        gs.ep.out_f32 = g.split_ws + ((long)blockIdx.y * (g.win_rows ? g.win_rows : g.M) - g.win_row0) * g.N;
-        gs.ep.ld_f32 = g.N;
-        gemm_epilogue_with<BM, BN, WGM, WGN, false, true>(put, gs, m0, n0, wr, wc, lane, wave, smem);
-        return;
-    }
-    gemm_epilogue_with<BM, BN, WGM, WGN, false, true>(put, g, m0, n0, wr, wc, lane, wave, smem, &rt);
-}
-
-#endif  // LTX_EXPERIMENTS
 
 // ---------------------------------------------------------------------------------------------------------------
 // small-M path: one wave per output column, f32 activations x bf16 weights
@@ -1859,7 +1414,7 @@ __global__ __launch_bounds__(256) void gemv_group_kernel(const GemvGroup g) {
     }
 }
 
-#ifdef LTX_EXPERIMENTS
+#ifdef LTX_EXPERIMENTS  // the kernels that were measured and not selected
 #define LTX_GEMM_EXPERIMENTS_PART 1
 #include "gemm_experiments.inc"
 #endif
@@ -2012,6 +1567,37 @@ static bool finish_takes_norm(const GemmArgs& a, const NormAfter& na) {
            !e.pn_out && na.norm_kind == 0 && na.scale && na.shift && !na.row_map && na.out && na.ldo % 4 == 0 && e.ld_f32 % 4 == 0 &&
            na.rows_per_batch % 2 == 0 && (!e.gate || e.rows_per_batch % 2 == 0) && a.M % 2 == 0;
 }
+// the finish pass of a split-K launch over `rows` rows of the workspace (a row window passes its own rows and an epilogue that starts there)
+void launch_splitk_finish(const GemmArgs& a, int rows, const GemmEpilogue& e, int ws_bf16, hipStream_t stream) {
+    const long total = (long)rows * (a.N / 4);
+    const int grid = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
+    hipLaunchKernelGGL(splitk_finish_kernel, dim3(grid), dim3(256), 0, stream, a.split_ws, a.split_k, rows, a.N, e, ws_bf16);
+    HIP_CHECK(hipGetLastError());
+}
+
+// The options (options.h) the launchers below read, by value: every public entry takes ONE snapshot and hands it down, so the rules that
+// route a launch and the launcher it is routed to see the same values whatever ltx_ctx_set_option does on another thread meanwhile.
+struct GemmOpts {
+    int conv_halo, conv_tall, conv_persist, conv_stagger, gemm_stagger, conv_cfg, conv_no_tail, smallm_cfg, b_nt, dtl_splitk, dtl_splitk_mink,
+        split_f32, finish_norm, finish_rows, gemm_rowsplit, gemm_tall;
+};
+GemmOpts gemm_opts() {
+    return {ltx_opt(OPT_CONV_HALO),  ltx_opt(OPT_CONV_TALL),    ltx_opt(OPT_CONV_PERSIST),  ltx_opt(OPT_CONV_STAGGER),
+            ltx_opt(OPT_GEMM_STAGGER), ltx_opt(OPT_CONV_CFG),   ltx_opt(OPT_CONV_NO_TAIL),  ltx_opt(OPT_SMALLM_CFG),
+            ltx_opt(OPT_B_NT),       ltx_opt(OPT_DTL_SPLITK),   ltx_opt(OPT_DTL_SPLITK_MINK), ltx_opt(OPT_SPLIT_F32),
+            ltx_opt(OPT_FINISH_NORM), ltx_opt(OPT_FINISH_ROWS), ltx_opt(OPT_GEMM_ROWSPLIT), ltx_opt(OPT_GEMM_TALL)};
+}
+
+// Split count that fills the chip: 256 / tiles ranges of K, at most `cap` and at most one per eight K-tiles, shrunk until the partial
+// slices (`slice` elements each) fit `ws_elems`. Each caller counts tiles of its own kernel and passes its own cap.
+int fill_split_k(long tiles, int nk, int cap, long slice, long ws_elems) {
+    long s = 256 / tiles;
+    if (s > cap) s = cap;
+    if (s > nk / 8) s = nk / 8;
+    if (s < 1) s = 1;
+    while (s > 1 && s * slice > ws_elems) --s;
+    return (int)s;
+}
 
 template <int BM, int BN, bool CONV>
 void launch_one(const GemmArgs& a, hipStream_t stream) {
@@ -2026,32 +1612,8 @@ void launch_one(const GemmArgs& a, hipStream_t stream) {
     HIP_CHECK(hipGetLastError());
 }
 
-#ifdef LTX_EXPERIMENTS
-template <int BM, int BN, int NSTAGE>
-void launch_m32(const GemmArgs& a, hipStream_t stream) {
-    constexpr int smem = NSTAGE * (BM + BN) * ROW_BYTES;
-    static PerDeviceOnce attr_set;
-    attr_set.run([&] {
-        HIP_CHECK(hipFuncSetAttribute((const void*)gemm_bf16_kernel_m32<BM, BN, NSTAGE>, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-    });
-    LTX_REQUIRE(!a.conv && !a.ep.out_bf16_t && !a.ep.pn_out && !a.tile_count, "gemm: the 32x32x16 ring kernel takes dense launches without a transposed output");
-    const int tiles = ((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN);
-    if (a.split_k > 1) {
-        LTX_REQUIRE(a.split_ws && a.N % 4 == 0 && !a.ep.d2s && a.split_k <= a.K / BK, "gemm split-K: workspace, N %% 4 == 0, no depth-to-space");
-    }
-    hipLaunchKernelGGL((gemm_bf16_kernel_m32<BM, BN, NSTAGE>), dim3(tiles, a.split_k > 1 ? a.split_k : 1), dim3(512), smem, stream, a);
-    HIP_CHECK(hipGetLastError());
-    if (a.split_k > 1) {
-        const long total = (long)a.M * (a.N / 4);
-        const int grid = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
-        hipLaunchKernelGGL(splitk_finish_kernel, dim3(grid), dim3(256), 0, stream, a.split_ws, a.split_k, a.M, a.N, a.ep, 0);
-        HIP_CHECK(hipGetLastError());
-    }
-}
-#endif
-
 template <int BM, int BN, int NSTAGE, bool CONV, int WGM = 2, int WGN = 2, bool QB = false>
-void launch_v2(const GemmArgs& a, hipStream_t stream) {
+void launch_v2(const GemmArgs& a, const GemmOpts& o, hipStream_t stream) {
     constexpr int smem = NSTAGE * (BM + BN) * ROW_BYTES + (QB ? (NSTAGE + 1) * (BN * 64 + WGM * WGN * 256) : 0);
     static PerDeviceOnce attr_set;
     attr_set.run([&] {
@@ -2070,7 +1632,7 @@ void launch_v2(const GemmArgs& a, hipStream_t stream) {
                     "gemm split-K: a row window takes neither per-row gates / biases nor the transposed output");
     }
     GemmArgs ab = a;
-    ab.conv_stagger = ltx_opt(CONV ? OPT_CONV_STAGGER : OPT_GEMM_STAGGER) != 0;
+    ab.conv_stagger = (CONV ? o.conv_stagger : o.gemm_stagger) != 0;
     hipLaunchKernelGGL((gemm_bf16_kernel_v2<BM, BN, NSTAGE, CONV, WGM, WGN, QB>), dim3(tiles, a.split_k > 1 ? a.split_k : 1),
                        dim3(WGM * WGN * 64), smem, stream, ab);
     HIP_CHECK(hipGetLastError());
@@ -2082,35 +1644,9 @@ void launch_v2(const GemmArgs& a, hipStream_t stream) {
             if (e.out_bf16) e.out_bf16 += (long)a.win_row0 * e.ld_bf16;
             if (e.resid_src) e.resid_src += (long)a.win_row0 * e.ld_resid;
         }
-        const long total = (long)rows * (a.N / 4);
-        const int grid = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
-        hipLaunchKernelGGL(splitk_finish_kernel, dim3(grid), dim3(256), 0, stream, a.split_ws, a.split_k, rows, a.N, e, 0);
-        HIP_CHECK(hipGetLastError());
+        launch_splitk_finish(a, rows, e, 0, stream);
     }
 }
-
-#ifdef LTX_EXPERIMENTS
-template <bool QB>
-void launch_fewrow(const GemmArgs& a, hipStream_t stream) {
-    constexpr int smem = 3 * 128 * ROW_BYTES + (QB ? 2 * 64 * ROW_BYTES + 4 * (64 * 256 + 1024) : 3 * 64 * 4 * ROW_BYTES);
-    static PerDeviceOnce attr_set;
-    attr_set.run([&] { HIP_CHECK(hipFuncSetAttribute((const void*)gemm_fewrow_kernel<QB>, hipFuncAttributeMaxDynamicSharedMemorySize, smem)); });
-    LTX_REQUIRE(QB == (a.Bq != nullptr), "gemm: quantised codes need the de-quantising instance of the few-row kernel");
-    LTX_REQUIRE(gemm_fewrow_takes(a.M, a.N, a.K, a.split_k) && !a.conv && !a.tile_count && !a.win_rows && !a.ep.d2s && !a.ep.pn_out,
-                "gemm: the few-row kernel takes dense launches with M <= 128, N %% 64 == 0 and whole 256-wide macro-tiles of K per split "
-                "(M=%d N=%d K=%d splits=%d)", a.M, a.N, a.K, a.split_k);
-    const int tiles = (a.N + 63) / 64;
-    if (a.split_k > 1) LTX_REQUIRE(a.split_ws && a.N % 4 == 0 && a.split_k <= a.K / BK, "gemm split-K: needs a workspace and N %% 4 == 0");
-    hipLaunchKernelGGL(gemm_fewrow_kernel<QB>, dim3(tiles, a.split_k > 1 ? a.split_k : 1), dim3(256), smem, stream, a);
-    HIP_CHECK(hipGetLastError());
-    if (a.split_k > 1) {
-        const long total = (long)a.M * (a.N / 4);
-        const int grid = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
-        hipLaunchKernelGGL(splitk_finish_kernel, dim3(grid), dim3(256), 0, stream, a.split_ws, a.split_k, a.M, a.N, a.ep, 0);
-        HIP_CHECK(hipGetLastError());
-    }
-}
-#endif
 
 void validate(const GemmArgs& a) {
     LTX_REQUIRE(a.M > 0 && a.N > 0 && a.K > 0, "gemm: empty problem M=%d N=%d K=%d", a.M, a.N, a.K);
@@ -2144,75 +1680,13 @@ void validate(const GemmArgs& a) {
 
 }  // namespace
 
-#ifdef LTX_EXPERIMENTS
-template <int BN>
-static bool gemm_asm_takes(const GemmArgs& a) {
-    return !a.conv && a.split_k <= 1 && a.M % 192 == 0 && a.N % BN == 0 && a.K % 64 == 0 && a.K >= 64 && !a.ep.d2s;
-}
-template <int BN, int RING = 0>
-static void launch_asm(const GemmArgs& a, hipStream_t stream) {
-    LTX_REQUIRE(gemm_asm_takes<BN>(a), "gemm: the assembly kernel needs a dense A.B^T with M %% 192 == 0, N %% %d == 0, K %% 64 == 0 (M=%d N=%d K=%d)",
-                BN, a.M, a.N, a.K);
-    constexpr int smem = RING == 2 ? 4 * 192 * ROW_BYTES : (RING ? 4 : 2) * (192 + BN) * ROW_BYTES;
-    static PerDeviceOnce attr_set;
-    attr_set.run([&] {
-        HIP_CHECK(hipFuncSetAttribute((const void*)gemm_bf16_kernel_asm<BN, RING>, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-    });
-    hipLaunchKernelGGL((gemm_bf16_kernel_asm<BN, RING>), dim3((a.M / 192) * (a.N / BN)), dim3(256), smem, stream, a);
-    HIP_CHECK(hipGetLastError());
-}
-
-#endif
 
 // the 192 x 256, 192 x 384 (q|k|v) and 384 x 256 kernels with a generated main loop, their predicates and launchers
 #include "gemm_asm_tiles.inc"
 
-#ifdef LTX_EXPERIMENTS
-bool gemm_stream_takes(const GemmArgs& a) {
-    const GemmEpilogue& e = a.ep;
-    return !a.conv && a.M >= 1 && a.M <= 128 && a.K % 64 == 0 && a.K >= 64 && a.N >= 16 && a.N % 4 == 0 && !e.d2s && a.lda % 8 == 0 &&
-           (a.Bq ? a.ldb % 16 == 0 : a.ldb % 8 == 0);
-}
-// K split of the weight-streaming kernel: aim at one to two workgroups per CU, each wave with >= 4 K-tiles
-static int stream_split_k(const GemmArgs& a) {
-    const int tiles_n = (a.N + 63) / 64, nk = a.K / BK;
-    int s = 1;
-    while (tiles_n * s * 2 <= 512 && nk / (s * 2) >= 16 && s < 8) s *= 2;
-    return s;
-}
-static void launch_stream(const GemmArgs& a_in, hipStream_t stream) {
-    GemmArgs a = a_in;
-    LTX_REQUIRE(gemm_stream_takes(a), "gemm: the weight-streaming kernel needs M <= 128, K %% 64 == 0, N %% 4 == 0 (M=%d N=%d K=%d)", a.M, a.N, a.K);
-    if (a.split_k == 0) {  // workspace given, split left to the launcher
-        a.split_k = stream_split_k(a);
-        while (a.split_k > 1 && (long)a.split_k * a.M * a.N > a.split_ws_elems) a.split_k /= 2;
-    }
-    if (a.split_k < 1 || !a.split_ws) a.split_k = 1;
-    constexpr int smem = 4 * 8 * 4 * 64 * 16;  // the four waves' 128 x 64 f32 tiles
-    static PerDeviceOnce attr_set;
-    attr_set.run([&] {
-        HIP_CHECK(hipFuncSetAttribute((const void*)gemm_stream_kernel<16>, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-        HIP_CHECK(hipFuncSetAttribute((const void*)gemm_stream_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-    });
-    const dim3 grid((a.N + 63) / 64, a.split_k);
-    if (a.Bq)
-        hipLaunchKernelGGL(gemm_stream_kernel<8>, grid, dim3(256), smem, stream, a);
-    else
-        hipLaunchKernelGGL(gemm_stream_kernel<16>, grid, dim3(256), smem, stream, a);
-    HIP_CHECK(hipGetLastError());
-    if (a.split_k > 1) {
-        const long total = (long)a.M * (a.N / 4);
-        const int fgrid = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
-        hipLaunchKernelGGL(splitk_finish_kernel, dim3(fgrid), dim3(256), 0, stream, a.split_ws, a.split_k, a.M, a.N, a.ep, 0);
-        HIP_CHECK(hipGetLastError());
-    }
-}
-
-#endif
-
 // conv_halo.inc: which conv launches the halo-staged kernel takes (everything else stays on the ring kernel)
-static bool conv_halo_takes(const GemmArgs& a) {
-    const bool off = ltx_opt(OPT_CONV_HALO) == 0;  // A/B option "conv_halo"
+static bool conv_halo_takes(const GemmArgs& a, const GemmOpts& o) {
+    const bool off = o.conv_halo == 0;  // A/B option "conv_halo"
     const Conv3dGeom& q = a.geom;
     // (win_rows on a launch without split-K is work accounting only: the head launch of a window pair)
     if (off || !a.conv || q.kt != 3 || !(q.pad_mode == 0 || q.pad_mode == 2) || q.C % 64 != 0 || a.split_k > 1 || a.tile0 != 0) return false;
@@ -2223,12 +1697,12 @@ static bool conv_halo_takes(const GemmArgs& a) {
     return w_ok && !a.ep.out_bf16_t && !a.ep.gate;  // (its epilogue is the scalar-gate form)
 }
 template <int BN>
-static void launch_conv_halo(const GemmArgs& a, hipStream_t stream);
+static void launch_conv_halo(const GemmArgs& a, const GemmOpts& o, hipStream_t stream);
 // conv_halo2.inc: the 384 x 128 tile of NRT image rows -> 0 = not this launch, else NRT (1: W == 384, 2: W == 192, 4: W == 96)
-static int conv_halo2_takes(const GemmArgs& a) {
-    if (ltx_opt(OPT_CONV_TALL) == 0 || !conv_halo_takes(a)) return 0;
+static int conv_halo2_takes(const GemmArgs& a, const GemmOpts& o) {
+    if (o.conv_tall == 0 || !conv_halo_takes(a, o)) return 0;
     const Conv3dGeom& q = a.geom;
-    const int nrt = (q.W == 384 && ltx_opt(OPT_CONV_TALL) != 2) ? 1 : (q.W == 192 ? 2 : (q.W == 96 ? 4 : 0));  // (2: A/B without the W == 384 instance)
+    const int nrt = (q.W == 384 && o.conv_tall != 2) ? 1 : (q.W == 192 ? 2 : (q.W == 96 ? 4 : 0));  // (2: A/B without the W == 384 instance)
     if (!nrt || q.H % nrt != 0 || a.N % 128 != 0 || a.M % 384 != 0 || a.tile_count != 0 || a.tile0 != 0 || a.ldb % 8 != 0) return 0;
     if (nrt == 4 && q.C % 128 != 0) return 0;                       // (the row-slot rotation must come back to slot 0 or 4 at a tile boundary)
     if (a.ep.d2s != 0 && a.ep.d2s != 1) return 0;                   // plain / fused-PixelNorm / depth-to-space epilogues (conv_out's d2s == 3 has N = 48)
@@ -2236,11 +1710,11 @@ static int conv_halo2_takes(const GemmArgs& a) {
     if ((long)q.F * q.H * q.W * q.C >= (1L << 31) || (long)a.N * a.ldb >= (1L << 31)) return 0;  // 32-bit element offsets
     // A tall tile is two 192-row tiles on ONE CU: a launch whose tall tiles cover at most half the chip finishes sooner as 192-row tiles
     // on twice the CUs (small clips; the stages of a 256 x 256 decode). Option value 3 takes the tall kernel regardless (tests of small shapes).
-    if (ltx_opt(OPT_CONV_TALL) != 3 && 2L * (a.M / 384) * (a.N / 128) <= device_cu_count()) return 0;
+    if (o.conv_tall != 3 && 2L * (a.M / 384) * (a.N / 128) <= device_cu_count()) return 0;
     return nrt;
 }
 template <int NRT>
-static void launch_conv_halo2_nrt(const GemmArgs& a, hipStream_t stream) {
+static void launch_conv_halo2_nrt(const GemmArgs& a, const GemmOpts& o, hipStream_t stream) {
     constexpr int RSP = (384 / NRT + 2 + 7) / 8, NS = NRT == 1 ? 2 : (NRT == 2 ? 4 : 8);
     constexpr int smem = NS * RSP * 1024 + 1024 + 3 * 128 * ROW_BYTES;
     static PerDeviceOnce attr_set;
@@ -2266,23 +1740,24 @@ static void launch_conv_halo2_nrt(const GemmArgs& a, hipStream_t stream) {
         GemmArgs t = a;
         t.tile0 = 2 * (main_tiles / tiles_n) * tiles_n;  // 192-row tiles in front of the window (conv_halo.inc's order: supertiles of group_m row tiles)
         t.tile_count = 2 * rows_t * tiles_n - t.tile0;
-        launch_conv_halo<128>(t, stream);
+        launch_conv_halo<128>(t, o, stream);
     }
 }
-static void launch_conv_halo2(const GemmArgs& a, hipStream_t stream) {
-    const int nrt = conv_halo2_takes(a);
-    if (nrt == 1) launch_conv_halo2_nrt<1>(a, stream);
-    else if (nrt == 2) launch_conv_halo2_nrt<2>(a, stream);
+// nrt = what conv_halo2_takes said of this launch
+static void launch_conv_halo2(const GemmArgs& a, int nrt, const GemmOpts& o, hipStream_t stream) {
+    if (nrt == 1) launch_conv_halo2_nrt<1>(a, o, stream);
+    else if (nrt == 2) launch_conv_halo2_nrt<2>(a, o, stream);
     else {
         LTX_REQUIRE(nrt == 4, "conv halo2: the launch is not one the tall kernel takes (W=%d H=%d N=%d M=%d)", a.geom.W, a.geom.H, a.N, a.M);
-        launch_conv_halo2_nrt<4>(a, stream);
+        launch_conv_halo2_nrt<4>(a, o, stream);
     }
 }
 // Both halo-staged kernels carry the depth-to-space + PixelNorm epilogue, and conv_halo2_takes is a subset of conv_halo_takes (it starts
 // with it), so the wider rule decides; it reads no device property and can be asked without one.
-bool gemm_conv_takes_d2s_pn(const GemmArgs& a) { return a.ep.d2s == 1 && a.N == 8 * 128 && a.split_k <= 1 && conv_halo_takes(a); }
+static bool conv_takes_d2s_pn(const GemmArgs& a, const GemmOpts& o) { return a.ep.d2s == 1 && a.N == 8 * 128 && a.split_k <= 1 && conv_halo_takes(a, o); }
+bool gemm_conv_takes_d2s_pn(const GemmArgs& a) { return conv_takes_d2s_pn(a, gemm_opts()); }
 template <int BN>
-static void launch_conv_halo(const GemmArgs& a, hipStream_t stream) {
+static void launch_conv_halo(const GemmArgs& a, const GemmOpts& o, hipStream_t stream) {
     constexpr int smem = 2 * 32 * 1024 + 6 * BN * ROW_BYTES;
     static PerDeviceOnce attr_set;
     attr_set.run([&] { HIP_CHECK(hipFuncSetAttribute((const void*)conv3d_halo_kernel<BN>, hipFuncAttributeMaxDynamicSharedMemorySize, smem)); });
@@ -2292,16 +1767,30 @@ static void launch_conv_halo(const GemmArgs& a, hipStream_t stream) {
     LTX_REQUIRE(a.tile0 >= 0 && a.tile0 + tiles <= all_tiles, "conv halo: tile window [%d, %d) outside %d", a.tile0, a.tile0 + tiles, all_tiles);
     // persistent above one round: one workgroup per CU walks the tiles of its XCD's chunk and requests the next tile's first operands
     // before the epilogue of the current one (conv_halo.inc); option "conv_persist" = 0 restores one workgroup per tile (A/B)
-    const bool persist = ltx_opt(OPT_CONV_PERSIST) != 0;
+    const bool persist = o.conv_persist != 0;
     const int ncu = device_cu_count() & ~7;
     const int grid = (persist && tiles > ncu && ncu >= 8) ? ncu : tiles;
     GemmArgs b = a;
-    b.conv_stagger = ltx_opt(OPT_CONV_STAGGER) != 0;
+    b.conv_stagger = o.conv_stagger != 0;
     hipLaunchKernelGGL(conv3d_halo_kernel<BN>, dim3(grid), dim3(512), smem, stream, b);
     HIP_CHECK(hipGetLastError());
 }
 
-void launch_gemm_bf16_cfg(const GemmArgs& a, int cfg, hipStream_t stream) {
+// One launch on tile cfg `cfg`. nrt = conv_halo2_takes of a conv launch (read by cfg 21 only; 0 for a dense one).
+static void launch_cfg(const GemmArgs& a, int cfg, const GemmOpts& o, int nrt, hipStream_t stream);
+
+// The launchers of the experiments build and its hooks into the flow below: gemm_experiments_cfg runs a tile cfg that only that build knows,
+// gemm_experiments_forced a dense launch whose cfg its environment forces (true = launched); gemm_experiments_group_m overrides group_m.
+#ifdef LTX_EXPERIMENTS
+#define LTX_GEMM_EXPERIMENTS_PART 2
+#include "gemm_experiments.inc"
+#else
+static bool gemm_experiments_cfg(const GemmArgs&, int, const GemmOpts&, hipStream_t) { return false; }
+static bool gemm_experiments_forced(const GemmArgs&, const GemmOpts&, hipStream_t) { return false; }
+static void gemm_experiments_group_m(GemmArgs&) {}
+#endif
+
+static void launch_cfg(const GemmArgs& a, int cfg, const GemmOpts& o, int nrt, hipStream_t stream) {
     if (a.ep.out_bf16_t) {
         const GemmEpilogue& e = a.ep;
         LTX_REQUIRE(!e.out_f32 && !e.out_bf16 && !e.resid && !e.d2s && !e.bias_m && e.act == LTX_ACT_NONE && !e.round_bf16 &&
@@ -2316,22 +1805,15 @@ void launch_gemm_bf16_cfg(const GemmArgs& a, int cfg, hipStream_t stream) {
     if (a.conv) {
         switch (cfg) {
             case 21:  // 8 waves (4x2), per-wave 48x64: the halo-staged kernel where it applies (its tall form where THAT applies), else the 4-slot ring
-                if (conv_halo2_takes(a)) launch_conv_halo2(a, stream);
-                else if (conv_halo_takes(a)) launch_conv_halo<128>(a, stream);
-                else launch_v2<192, 128, 4, true, 4, 2>(a, stream);
+                if (nrt) launch_conv_halo2(a, nrt, o, stream);
+                else if (conv_halo_takes(a, o)) launch_conv_halo<128>(a, o, stream);
+                else launch_v2<192, 128, 4, true, 4, 2>(a, o, stream);
                 break;
-#ifdef LTX_EXPERIMENTS  // measured, not selected for convs (VAE decode 19.4 ms with the 256x128 ring, 22.8 with the two-stage kernel, against 17.0)
-            case 0: launch_one<128, 128, true>(a, stream); break;
-            case 1: launch_one<192, 128, true>(a, stream); break;
-            case 3: launch_one<96, 128, true>(a, stream); break;
-            case 4: launch_one<128, 96, true>(a, stream); break;
-            case 23: launch_v2<256, 128, 3, true, 4, 2>(a, stream); break;  // 8 waves, per-wave 64x64
-            case 25: launch_v2<128, 192, 4, true, 2, 4>(a, stream); break;
-#endif
             case 27:  // narrow outputs (the VAE's 128 -> 48 conv_out): the halo-staged kernel's 192x64 instance, else the 256x64 ring (per-wave 64x32)
-                if (a.N <= 64 && conv_halo_takes(a)) launch_conv_halo<64>(a, stream); else launch_v2<256, 64, 4, true, 4, 2>(a, stream);
+                if (a.N <= 64 && conv_halo_takes(a, o)) launch_conv_halo<64>(a, o, stream); else launch_v2<256, 64, 4, true, 4, 2>(a, o, stream);
                 break;
-            default: LTX_THROW(LTXS_INVALID_CONFIGURATION, "gemm: unknown tile cfg %d", cfg);
+            default:
+                if (!gemm_experiments_cfg(a, cfg, o, stream)) LTX_THROW(LTXS_INVALID_CONFIGURATION, "gemm: unknown tile cfg %d", cfg);
         }
     } else {
         switch (cfg) {
@@ -2339,47 +1821,36 @@ void launch_gemm_bf16_cfg(const GemmArgs& a, int cfg, hipStream_t stream) {
             case 1: launch_one<192, 128, false>(a, stream); break;
             case 3: launch_one<96, 128, false>(a, stream); break;
             case 4: launch_one<128, 96, false>(a, stream); break;
-            case 21: launch_v2<192, 128, 4, false, 4, 2>(a, stream); break;  // 8 waves (4x2), per-wave 48x64, 4-slot ring
-            case 22: { GemmArgs b = a; b.group_m = 0; launch_v2<192, 128, 4, false, 4, 2>(b, stream); break; }  // A/B: column-major order
-            case 23: launch_v2<256, 128, 3, false, 4, 2>(a, stream); break;  // 8 waves, per-wave 64x64
-            case 25: launch_v2<128, 192, 4, false, 2, 4>(a, stream); break;
+            case 21: launch_v2<192, 128, 4, false, 4, 2>(a, o, stream); break;  // 8 waves (4x2), per-wave 48x64, 4-slot ring
+            case 22: { GemmArgs b = a; b.group_m = 0; launch_v2<192, 128, 4, false, 4, 2>(b, o, stream); break; }  // A/B: column-major order
+            case 23: launch_v2<256, 128, 3, false, 4, 2>(a, o, stream); break;  // 8 waves, per-wave 64x64
+            case 25: launch_v2<128, 192, 4, false, 2, 4>(a, o, stream); break;
             case 29:  // few rows: narrow column tiles, 4 waves, one workgroup per CU; 8-bit codes de-quantised in the B stage.
                       // bf16 weights: SIX ring slots (144 KB) - five K-tiles of weights in flight per CU instead of three: the
                       // weight stream of a 128-token launch goes from 3.45 to 3.65 TB/s (same-box A/B, tools/fewrow_stride.py)
                 if (a.Bq) {
-                    launch_v2<128, 64, 4, false, 2, 2, true>(a, stream);
+                    launch_v2<128, 64, 4, false, 2, 2, true>(a, o, stream);
                 } else {
-                    const int nt_env = ltx_opt(OPT_B_NT);  // A/B option "b_nt": 0 / 1 overrides the launcher
+                    const int nt_env = o.b_nt;  // A/B option "b_nt": 0 / 1 overrides the launcher
                     if (nt_env >= 0 && a.b_nt != nt_env) {
                         GemmArgs b = a;
                         b.b_nt = nt_env;
-                        launch_v2<128, 64, 6, false, 2, 2>(b, stream);
+                        launch_v2<128, 64, 6, false, 2, 2>(b, o, stream);
                     } else {
-                        launch_v2<128, 64, 6, false, 2, 2>(a, stream);
+                        launch_v2<128, 64, 6, false, 2, 2>(a, o, stream);
                     }
                 }
                 break;
-#ifdef LTX_EXPERIMENTS
-            case 28: launch_v2<128, 64, 4, false, 2, 2>(a, stream); break;  // cfg 29 with the 4-slot ring it had until round 3 (A/B)
-            case 30:  // few rows (M <= 128), operand rings of their own, weights in macro-tiles: measured, not selected
-                if (a.Bq) launch_fewrow<true>(a, stream); else launch_fewrow<false>(a, stream);
-                break;
-#endif
-            case 75: launch_dtl(a, stream); break;  // 192x256, one wave per SIMD, fragments of a whole K-tile in registers, 2 + 3 LDS slots
+            case 75: launch_dtl(a, o, stream); break;  // 192x256, one wave per SIMD, fragments of a whole K-tile in registers, 2 + 3 LDS slots
             case 76: launch_tall(a, stream); break;  // 384x256, one wave per SIMD, B fragments of a K-tile in registers, A through a ring, 2 + 2 LDS slots
-#ifdef LTX_EXPERIMENTS  // measured, not selected (gemm_experiments.inc)
-            case 31: launch_m32<192, 128, 4>(a, stream); break;  // the 192x128 ring tile on 32x32x16 MFMAs (2 x 4 waves of 96 x 32): 951 vs 1021 TFLOP/s
-            case 90: launch_stream(a, stream); break;  // weight-streaming kernel for M <= 128 (bf16 weights or 8-bit codes): 1.4x slower than the ring split-K path
-            case 71: launch_asm<256>(a, stream); break;      // one wave per SIMD, assembly main loop, 192x256
-            case 72: launch_asm<128>(a, stream); break;      // the same, 192x128
-            case 73: launch_asm<128, 1>(a, stream); break;  // 192x128, one wave per SIMD, LDS-DMA ring of four slots
-            case 74: launch_asm<128, 2>(a, stream); break;  // the same with B as fragment-layout loads straight to registers
-            case 41: launch_v4<192, 256>(a, stream); break;  // ping-pong, 8 waves (2x4), per-wave 96x64
-            case 42: launch_v4<256, 256>(a, stream); break;  // ping-pong, per-wave 128x64
-#endif
-            default: LTX_THROW(LTXS_INVALID_CONFIGURATION, "gemm: unknown tile cfg %d", cfg);
+            default:
+                if (!gemm_experiments_cfg(a, cfg, o, stream)) LTX_THROW(LTXS_INVALID_CONFIGURATION, "gemm: unknown tile cfg %d", cfg);
         }
     }
+}
+void launch_gemm_bf16_cfg(const GemmArgs& a, int cfg, hipStream_t stream) {
+    const GemmOpts o = gemm_opts();
+    launch_cfg(a, cfg, o, (a.conv && cfg == 21) ? conv_halo2_takes(a, o) : 0, stream);
 }
 
 bool gemm_takes_codes(int M, int N, int K) { return M >= 1 && M <= 256 && K % BK == 0 && K >= 4 * BK && N % 4 == 0; }
@@ -2393,10 +1864,7 @@ int gemm_suggest_split_k(int M, int N, int K) {
     const long tiles = (long)((M + 191) / 192) * ((N + 127) / 128);  // the 192x128 ring kernel's tiles
     const int nk = K / BK;
     if (tiles >= 160 || nk < 32) return 1;
-    long s = 256 / tiles;
-    if (s > 8) s = 8;
-    if (s > nk / 8) s = nk / 8;
-    return s < 1 ? 1 : (int)s;
+    return fill_split_k(tiles, nk, 8, 0, 0);
 }
 
 // At most one round of 192x128 ring tiles with a long reduction (the FFN's second GEMM at 1536 tokens: 256 tiles, K = 16384) runs as K
@@ -2405,10 +1873,10 @@ int gemm_suggest_split_k(int M, int N, int K) {
 // (8192; with 2048 the three K = 4096 launches of a block split too and the step LOSES 1.3 ms).
 // Partial tiles of such a launch cross the workspace as bf16 ONLY when the caller asked for it (GemmArgs::split_bf16 - the DiT sets it for
 // its FFN-down Linear, nothing else does: a generic or ABI launch keeps f32 partials, round-4 advice) and option "split_f32" is 0.
-static int dtl_split_bf16(const GemmArgs& a) { return a.split_bf16 && ltx_opt(OPT_SPLIT_F32) == 0; }
-static int dtl_split_for(const GemmArgs& a) {
-    const bool dtl_split = ltx_opt(OPT_DTL_SPLITK) != 0;
-    const int dtl_mink = ltx_opt(OPT_DTL_SPLITK_MINK);
+static int dtl_split_bf16(const GemmArgs& a, const GemmOpts& o) { return a.split_bf16 && o.split_f32 == 0; }
+static int dtl_split_for(const GemmArgs& a, const GemmOpts& o) {
+    const bool dtl_split = o.dtl_splitk != 0;
+    const int dtl_mink = o.dtl_splitk_mink;
     if (!dtl_split || dtl_mink < 64 || a.conv || a.Bq || !a.split_ws || a.split_k != 0 || a.M % 192 != 0 || a.N % 256 != 0 || a.ep.d2s) return 0;
     if (gemm_suggest_split_k(a.M, a.N, a.K) > 1) return 0;  // fewer than 160 ring tiles: the ring kernel's own split-K
     const long t1 = (long)(a.M / 192) * (a.N / 256);
@@ -2423,8 +1891,8 @@ static int dtl_split_for(const GemmArgs& a) {
 }
 
 // The tile choice of a dense launch without split-K as a pure function of the launch and the CU count: no device is touched
-// (ltx_gemm_dense_tile_cfg pins the table in a CPU test). launch_gemm_bf16 may still split a ragged 192x256 launch by rows.
-int gemm_dense_cfg(const GemmArgs& a, int ncu) {
+// (ltx_gemm_dense_tile_cfg pins the table in a CPU test). launch_dense may still split a ragged 192x256 launch by rows.
+static int dense_cfg(const GemmArgs& a, int ncu, const GemmOpts& o) {
     struct Cand { int cfg, bm, bn, slots; double f; };
     //   cfg 75: 192x256 tile, one wave per SIMD, assembly main loop (tools/gen_gemm_asm_dtl.py): half the rounds of a 192x128 tile.
     //   Same measurement, round 2 (profiles/r02_gemm_microbench.txt): N=8192: cfg75 1165 | library GEMM 1116 | cfg1 936 | cfg21 959;
@@ -2442,210 +1910,136 @@ int gemm_dense_cfg(const GemmArgs& a, int ncu) {
         if (e > be + 1e-9) { be = e; best = c.cfg; }
     }
     // cfg 76: where the 192x256 kernel would run an even number of rounds, tiles twice as tall run half as many, each staging 29 % fewer
-    // bytes per MFMA (the FFN-up projection, N = 16384). Option "gemm_tall" = 0 = off (A/B); bit-neutral. Read once per decision.
-    if (best == 75 && ltx_opt(OPT_GEMM_TALL) != 0 && gemm_tall_takes(a, ncu)) best = 76;
+    // bytes per MFMA (the FFN-up projection, N = 16384). Option "gemm_tall" = 0 = off (A/B); bit-neutral.
+    if (best == 75 && o.gemm_tall != 0 && gemm_tall_takes(a, ncu)) best = 76;
     return best;
 }
+int gemm_dense_cfg(const GemmArgs& a, int ncu) { return dense_cfg(a, ncu, gemm_opts()); }
 
-void launch_gemm_bf16(const GemmArgs& a, hipStream_t stream, const NormAfter* na) {
-    LTX_REQUIRE(na && a.ep.out_f32 && !a.conv, "gemm: norm_after needs a dense launch with an f32 output");
-    const bool fuse_on = ltx_opt(OPT_FINISH_NORM) != 0;  // A/B option "finish_norm"
-    const int s2 = (fuse_on && finish_takes_norm(a, *na)) ? dtl_split_for(a) : 0;
-    if (s2) {
-        GemmArgs b = a;
-        b.split_k = s2;
-        b.split_bf16 = dtl_split_bf16(a);
-        validate(b);
-        ProfScope prof(PROF_GEMM, 2.0 * a.M * a.N * a.K, stream);
-        launch_dtl(b, stream, na);
-        return;
-    }
-    launch_gemm_bf16(a, stream);
-    launch_norm_mod(a.ep.out_f32, a.ep.ld_f32, na->scale, na->shift, na->mod_bstride, na->rows_per_batch, na->out, na->ldo, a.M, a.N, na->norm_kind,
-                    na->eps, na->round_norm_bf16, stream, na->row_map);
-}
+// ---- launch_gemm_bf16: a conv, a dense launch whose split count is left to the launcher, or a plain dense launch ----
+// Tile choice = workgroup-count quantisation x structure efficiency. Two structures:
+//   v1 (cfg 0,1,3,4): 4 waves, 2 LDS stages, TWO workgroups resident per CU (512 slots) - two waves per SIMD from
+//       co-residency; best when a launch has >= 512 tiles. Its single-tile prefetch exposes HBM latency on
+//       weights that are streamed once (the DiT case), hence the lower factor for the small tiles.
+//   v2 (cfg 21,23,25): 8 waves (two per SIMD inside ONE workgroup per CU, 256 slots), 3/4-slot LDS ring filled
+//       2-3 K-tiles ahead with counted vmcnt - HBM-cold weights cost nothing; best at exactly k*256 tiles.
+// Measured on MI355X, HBM-cold B operand, random data (tools/bench_gemm.py --cold), TFLOP/s:
+//   M=1536 N=4096 K=4096 : cfg21 944 | cfg0 754 | cfg1 608      N=8192: cfg1 1026 | cfg21 949
+//   N=16384: cfg1 1049 | cfg21 991         K=16384: cfg21 1094 | cfg0 864       M=4096 N=1536: cfg25 876 | cfg0 629
+// (the candidates and their factors: dense_cfg)
 
-void launch_gemm_bf16(const GemmArgs& a_in, hipStream_t stream) {
-    // A/B hook: LTX_GEMM_GROUP_M="N:g,..." overrides the supertile height of dense launches with that N (tile_coords)
-    GemmArgs a = a_in;
-#ifdef LTX_EXPERIMENTS  // string-valued tile experiments stay environment hooks of the experiments build only
-    if (const char* f = getenv("LTX_GEMM_GROUP_M")) {
-        for (const char* q = f; *q;) {
-            const long n = strtol(q, (char**)&q, 10);
-            if (*q != ':') break;
-            const long gm = strtol(q + 1, (char**)&q, 10);
-            if (n == a.N && !a.conv) a.group_m = (int)gm;
-            if (*q == ',') ++q;
-        }
-    }
-#endif
-    // Tile choice = workgroup-count quantisation x structure efficiency. Two structures:
-    //   v1 (cfg 0,1,3,4): 4 waves, 2 LDS stages, TWO workgroups resident per CU (512 slots) - two waves per SIMD from
-    //       co-residency; best when a launch has >= 512 tiles. Its single-tile prefetch exposes HBM latency on
-    //       weights that are streamed once (the DiT case), hence the lower factor for the small tiles.
-    //   v2 (cfg 21,23,25): 8 waves (two per SIMD inside ONE workgroup per CU, 256 slots), 3/4-slot LDS ring filled
-    //       2-3 K-tiles ahead with counted vmcnt - HBM-cold weights cost nothing; best at exactly k*256 tiles.
-    // Measured on MI355X, HBM-cold B operand, random data (tools/bench_gemm.py --cold), TFLOP/s:
-    //   M=1536 N=4096 K=4096 : cfg21 944 | cfg0 754 | cfg1 608      N=8192: cfg1 1026 | cfg21 949
-    //   N=16384: cfg1 1049 | cfg21 991         K=16384: cfg21 1094 | cfg0 864       M=4096 N=1536: cfg25 876 | cfg0 629
-    // (the candidates and their factors: gemm_dense_cfg)
-    if (a.conv) {
-        // implicit-GEMM convs: the per-tap gather arithmetic must hide under MFMAs (8-wave ring kernels interleave it;
-        // the two-stage 4-wave kernel serialises it and ran the 256-channel VAE stage at 150 TFLOP/s). M is huge, so
-        // tile-count quantisation does not matter; N <= 128 wants the 192x128 tile, wide N the same (B re-use).
-        const int cc_opt = ltx_opt(OPT_CONV_CFG);  // A/B option "conv_cfg" for tile experiments (21 = 192x128 ring; 23 = 256x128 ring in the experiments build)
-        const bool cc = cc_opt != 0;
-        // N <= 64 (the decoder's conv_out, 128 -> 48 channels): a 192x128 tile spends 62 % of its MFMAs on padding columns
-        const int conv_default = (a.N <= 64 && a.split_k <= 1) ? 27 : 21;
-        if (a.ep.pn_out) {
-            // the fused PixelNorm output needs every channel of a row in ONE 128-column tile and the epilogue in the GEMM launch
-            // (round 5: or, with the depth-to-space store of an upsampler, N == 8 x 128: a tile is one sub-position's 128 channels; only the
-            // halo-staged kernels carry that epilogue)
-            LTX_REQUIRE(((a.N == 128 && !a.ep.d2s) || gemm_conv_takes_d2s_pn(a)) && a.split_k <= 1 &&
-                            (a.ep.pn_scale == nullptr) == (a.ep.pn_shift == nullptr),
-                        "gemm: fused PixelNorm output needs N == 128 (got %d; 1024 with a depth-to-space store on a halo-staged launch) and no split-K", a.N);
-            // (A last partial round - the 128-channel stage at 768x512 is 3200 tiles = 12.5 rounds - is NOT worth a launch of its own here:
-            // running the 128 remaining tiles as 256 half-height tiles behind the whole rounds measured +0.28 ms per decode, round 3.
-            // Tiles are dispatched as CUs free up, so the ragged end costs half a tile, less than a launch boundary.)
-            launch_gemm_bf16_cfg(a, 21, stream);
-            return;
-        }
-        // Last partial round: T tiles = q full rounds of 256 + r. With r <= 128 the r tiles of the last round would run K-long on
-        // r CUs while the others idle (the VAE's 256-channel stage: 832 tiles = 3.25 rounds, 19 % of every conv). Run the full
-        // rounds as one launch and the remainder as a split-K launch over all CUs (window fields of GemmArgs).
-        const bool no_tail = ltx_opt(OPT_CONV_NO_TAIL) != 0;  // A/B option "conv_no_tail"
-        if (!cc && conv_default == 21 && conv_halo2_takes(a)) {  // the tall kernel balances its own last round (launch_conv_halo2)
-            launch_gemm_bf16_cfg(a, 21, stream);
-            return;
-        }
-        if (!no_tail && !cc && conv_default == 21 && a.split_k <= 1 && a.split_ws && !a.ep.d2s && a.N % 4 == 0 && !a.ep.gate && !a.ep.bias_m &&
-            !a.ep.out_bf16_t && a.group_m > 0) {
-            const int tiles_m = (a.M + 191) / 192, tiles_n = (a.N + 127) / 128, tiles = tiles_m * tiles_n;
-            const int full = tiles / 256 * 256, tail = tiles - full, per = a.group_m * tiles_n, nk = a.K / BK;
-            if (full >= 512 && tail > 0 && tail <= 128 && full % per == 0) {
-                const int row0 = full / per * a.group_m * 192;  // whole supertiles before the window: it covers complete rows
-                int sk = 256 / tail;
-                if (sk > 8) sk = 8;
-                if (sk > nk / 8) sk = nk / 8;
-                while (sk > 1 && (long)sk * (a.M - row0) * a.N > a.split_ws_elems) --sk;
-                if (sk > 1) {
-                    GemmArgs head = a, rest = a;
-                    head.tile_count = full;
-                    head.win_rows = row0;  // rows [0, row0): only the work accounting reads it on a launch without split-K
-                    head.split_ws = nullptr;
-                    rest.tile0 = full;
-                    rest.tile_count = tail;
-                    rest.split_k = sk;
-                    rest.win_row0 = row0;
-                    rest.win_rows = a.M - row0;
-                    launch_gemm_bf16_cfg(head, 21, stream);
-                    launch_gemm_bf16_cfg(rest, 21, stream);
-                    return;
-                }
-            }
-        }
-        launch_gemm_bf16_cfg(a, (cc && a.split_k <= 1) ? cc_opt : conv_default, stream);
+// implicit-GEMM convs: the per-tap gather arithmetic must hide under MFMAs (8-wave ring kernels interleave it;
+// the two-stage 4-wave kernel serialises it and ran the 256-channel VAE stage at 150 TFLOP/s). M is huge, so
+// tile-count quantisation does not matter; N <= 128 wants the 192x128 tile, wide N the same (B re-use).
+static void launch_conv(const GemmArgs& a, const GemmOpts& o, hipStream_t stream) {
+    const int cc_opt = o.conv_cfg;  // A/B option "conv_cfg" for tile experiments (21 = 192x128 ring; 23 = 256x128 ring in the experiments build)
+    const bool cc = cc_opt != 0;
+    // N <= 64 (the decoder's conv_out, 128 -> 48 channels): a 192x128 tile spends 62 % of its MFMAs on padding columns
+    const int conv_default = (a.N <= 64 && a.split_k <= 1) ? 27 : 21;
+    const int nrt = conv_halo2_takes(a, o);  // the tall kernel's say on THIS launch, asked once (the head / tail launches below are not its)
+    if (a.ep.pn_out) {
+        // the fused PixelNorm output needs every channel of a row in ONE 128-column tile and the epilogue in the GEMM launch
+        // (round 5: or, with the depth-to-space store of an upsampler, N == 8 x 128: a tile is one sub-position's 128 channels; only the
+        // halo-staged kernels carry that epilogue)
+        LTX_REQUIRE(((a.N == 128 && !a.ep.d2s) || conv_takes_d2s_pn(a, o)) && a.split_k <= 1 &&
+                        (a.ep.pn_scale == nullptr) == (a.ep.pn_shift == nullptr),
+                    "gemm: fused PixelNorm output needs N == 128 (got %d; 1024 with a depth-to-space store on a halo-staged launch) and no split-K", a.N);
+        // (A last partial round - the 128-channel stage at 768x512 is 3200 tiles = 12.5 rounds - is NOT worth a launch of its own here:
+        // running the 128 remaining tiles as 256 half-height tiles behind the whole rounds measured +0.28 ms per decode, round 3.
+        // Tiles are dispatched as CUs free up, so the ragged end costs half a tile, less than a launch boundary.)
+        launch_cfg(a, 21, o, nrt, stream);
         return;
     }
-    LTX_REQUIRE(!a.ep.pn_out, "gemm: the fused PixelNorm output exists for conv launches only");
-    LTX_REQUIRE(!a.Bq || (gemm_takes_codes(a.M, a.N, a.K) && a.split_ws && a.split_k == 0),
-                "gemm: 8-bit codes are de-quantised in the B stage of few-row launches only (M=%d N=%d K=%d)", a.M, a.N, a.K);
-    if (a.split_ws && a.split_k == 0) {
-        // caller-provided workspace, split count left to the launcher: few output tiles and a long reduction (the DiT at
-        // small token counts, e.g. 256x256x9 -> 128 tokens: 32 tiles of weights to stream with 256 CUs) -> split K over the idle CUs
-        GemmArgs b = a;
-        b.split_k = gemm_suggest_split_k(a.M, a.N, a.K);
-        // few rows (<= 128, e.g. 256x256x9): narrow 128x64 ring tiles - 64 column tiles at N = 4096, so 4 splits fill the chip and
-        // the partial slices are a quarter of the weights (128x192 tiles needed 16 splits: as many partial bytes as weight bytes),
-        // and the FFN's first GEMM (256 column tiles) needs no split at all. Config 1: 12.04 ms per forward against 12.25 (cfg 25).
-        const int smallm_cfg = ltx_opt(OPT_SMALLM_CFG);  // 30 (experiments build): the few-row kernel, 9 % slower
-        // codes in the B stage exist only in the 128x64 ring (29) and the experiments build's few-row kernel (30): the hook cannot move a
-        // quantised launch anywhere else
-        const int smallm_q = (smallm_cfg == 29 || smallm_cfg == 30) ? smallm_cfg : 29;
-        int cfg = a.Bq ? (a.M <= 128 ? smallm_q : 29) : ((a.M <= 128 && b.split_k > 1) ? smallm_cfg : 21);
-        if (cfg == 29 || cfg == 30) {
-            const long tiles = (long)((a.N + 63) / 64);
-            long sk = 256 / tiles;
-            const int nk = a.K / BK;
-            if (sk > 16) sk = 16;
-            if (sk > nk / 8) sk = nk / 8;
-            b.split_k = sk < 1 ? 1 : (int)sk;
-            while (b.split_k > 1 && (long)b.split_k * a.M * a.N > a.split_ws_elems) --b.split_k;
-            if (cfg == 30 && !gemm_fewrow_takes(a.M, a.N, a.K, b.split_k)) cfg = 29;
-            // once-read weights, non-temporal - from 64 MB up: the q|k, FFN-up and FFN-down launches gain 3-6 %, the 33.5 MB ones
-            // (N = K = 4096, four splits) LOSE 12 % with it (profiles/r03_fewrow_bounds.txt)
-            b.b_nt = (long)a.N * a.K >= (32L << 20) ? 1 : 0;
-        }
-        if (cfg == 25) {
-            const long tiles = (long)((a.N + 191) / 192);
-            long sk = 256 / tiles;
-            const int nk = a.K / BK;
-            if (sk > 16) sk = 16;
-            if (sk > nk / 8) sk = nk / 8;
-            b.split_k = sk < 1 ? 1 : (int)sk;
-        }
-        while (b.split_k > 1 && (long)b.split_k * a.M * a.N > a.split_ws_elems) --b.split_k;
-        LTX_REQUIRE(!a.Bq || (a.N % 4 == 0 && !a.ep.d2s), "gemm: quantised few-row launch with N %% 4 != 0");
-        if ((b.split_k > 1 || cfg == 29 || cfg == 30) && a.N % 4 == 0 && !a.ep.d2s) {
-            if (b.split_k <= 1) {
-                b.split_k = 1;  // enough column tiles to fill the chip without a split (the FFN's first GEMM)
-                b.split_ws = nullptr;
-            }
-            launch_gemm_bf16_cfg(b, cfg, stream);
-            return;
-        }
-        if (const int s2 = dtl_split_for(a)) {
-            b.split_k = s2;
-            b.split_bf16 = dtl_split_bf16(a);
-            launch_gemm_bf16_cfg(b, 75, stream);
-            return;
-        }
-        b.split_k = 1;
-        b.split_ws = nullptr;
-        launch_gemm_bf16(b, stream);
+    if (!cc && conv_default == 21 && nrt) {  // the tall kernel balances its own last round (launch_conv_halo2_nrt)
+        launch_cfg(a, 21, o, nrt, stream);
         return;
     }
-#ifdef LTX_EXPERIMENTS
-    // The assembly kernel (tile_cfg 71: 192 x 256 tile, one wave per SIMD, generated main loop) is NOT in the default choice.
-    // Measured on MI355X, HBM-cold weights, random data, same process (tools/bench_gemm.py --cold --cfgs=-1,21,1,71), TFLOP/s:
-    // 1536x16384x4096 1057 vs 1009 (two-stage) / 987 (ring); 6144x4096x4096 1069 vs 1053 / 1015; 1536x8192x4096 895 vs 930 (ring);
-    // but inside the DiT step (same-box A/B of bench.py) routing the FFN's first GEMM to it costs 0.3 ms per step (41.6 vs 41.3).
-    // Its loop runs 2380 cycles per K-tile against 1730 of MFMA issue (14 buffer loads + 14 ds_write_b128 per wave and tile are
-    // not free) and its epilogue (10 us for 50 MB of output, every workgroup at the same time) is exposed once per launch.
-    // LTX_GEMM_ASM=1 opts in for launches that fill the chip at least twice with 192x256 tiles (A/B runs).
-    static const bool asm_on = getenv("LTX_GEMM_ASM") && getenv("LTX_GEMM_ASM")[0] == '1';
-    if (asm_on && gemm_asm_takes<256>(a)) {
-        const long tiles_asm = (long)(a.M / 192) * (a.N / 256);
-        if (tiles_asm >= 512 && tiles_asm % 256 == 0 && a.K <= 8192) {
-            launch_gemm_bf16_cfg(a, 71, stream);
-            return;
-        }
-    }
-#endif
-#ifdef LTX_EXPERIMENTS
-    // A/B hook for in-pipeline tile experiments (experiments build only): LTX_GEMM_FORCE="8192:21,16384:21" forces a tile cfg for dense launches by N
-    if (const char* f = getenv("LTX_GEMM_FORCE")) {
-        for (const char* q = f; *q;) {
-            const long n = strtol(q, (char**)&q, 10);
-            if (*q != ':') break;
-            const long c = strtol(q + 1, (char**)&q, 10);
-            const bool takes = c == 71 ? gemm_asm_takes<256>(a) : (c >= 72 && c <= 74) ? gemm_asm_takes<128>(a) : c == 75 ? gemm_dtl_takes(a) : true;
-            if (n == a.N && takes) {
-                launch_gemm_bf16_cfg(a, (int)c, stream);
+    // Last partial round: T tiles = q full rounds of 256 + r. With r <= 128 the r tiles of the last round would run K-long on
+    // r CUs while the others idle (the VAE's 256-channel stage: 832 tiles = 3.25 rounds, 19 % of every conv). Run the full
+    // rounds as one launch and the remainder as a split-K launch over all CUs (window fields of GemmArgs).
+    const bool no_tail = o.conv_no_tail != 0;  // A/B option "conv_no_tail"
+    if (!no_tail && !cc && conv_default == 21 && a.split_k <= 1 && a.split_ws && !a.ep.d2s && a.N % 4 == 0 && !a.ep.gate && !a.ep.bias_m &&
+        !a.ep.out_bf16_t && a.group_m > 0) {
+        const int tiles_m = (a.M + 191) / 192, tiles_n = (a.N + 127) / 128, tiles = tiles_m * tiles_n;
+        const int full = tiles / 256 * 256, tail = tiles - full, per = a.group_m * tiles_n, nk = a.K / BK;
+        if (full >= 512 && tail > 0 && tail <= 128 && full % per == 0) {
+            const int row0 = full / per * a.group_m * 192;  // whole supertiles before the window: it covers complete rows
+            const int sk = fill_split_k(tail, nk, 8, (long)(a.M - row0) * a.N, a.split_ws_elems);
+            if (sk > 1) {
+                GemmArgs head = a, rest = a;
+                head.tile_count = full;
+                head.win_rows = row0;  // rows [0, row0): only the work accounting reads it on a launch without split-K
+                head.split_ws = nullptr;
+                rest.tile0 = full;
+                rest.tile_count = tail;
+                rest.split_k = sk;
+                rest.win_row0 = row0;
+                rest.win_rows = a.M - row0;
+                launch_cfg(head, 21, o, 0, stream);
+                launch_cfg(rest, 21, o, 0, stream);
                 return;
             }
-            if (*q == ',') ++q;
         }
     }
-#endif
+    launch_cfg(a, (cc && a.split_k <= 1) ? cc_opt : conv_default, o, nrt, stream);
+}
+
+static void launch_dense(const GemmArgs& a, const GemmOpts& o, hipStream_t stream);
+
+// caller-provided workspace, split count left to the launcher: few output tiles and a long reduction (the DiT at
+// small token counts, e.g. 256x256x9 -> 128 tokens: 32 tiles of weights to stream with 256 CUs) -> split K over the idle CUs
+static void launch_dense_ws(const GemmArgs& a, const GemmOpts& o, hipStream_t stream) {
+    GemmArgs b = a;
+    b.split_k = gemm_suggest_split_k(a.M, a.N, a.K);
+    // few rows (<= 128, e.g. 256x256x9): narrow 128x64 ring tiles - 64 column tiles at N = 4096, so 4 splits fill the chip and
+    // the partial slices are a quarter of the weights (128x192 tiles needed 16 splits: as many partial bytes as weight bytes),
+    // and the FFN's first GEMM (256 column tiles) needs no split at all. Config 1: 12.04 ms per forward against 12.25 (cfg 25).
+    const int smallm_cfg = o.smallm_cfg;  // 30 (experiments build): the few-row kernel, 9 % slower
+    // codes in the B stage exist only in the 128x64 ring (29) and the experiments build's few-row kernel (30): the hook cannot move a
+    // quantised launch anywhere else
+    const int smallm_q = (smallm_cfg == 29 || smallm_cfg == 30) ? smallm_cfg : 29;
+    int cfg = a.Bq ? (a.M <= 128 ? smallm_q : 29) : ((a.M <= 128 && b.split_k > 1) ? smallm_cfg : 21);
+    if (cfg == 29 || cfg == 30 || cfg == 25) {  // one row tile: column tiles of 64 (29, 30) or 192 (25) x up to 16 splits fill the chip
+        const int bn = cfg == 25 ? 192 : 64;
+        b.split_k = fill_split_k((a.N + bn - 1) / bn, a.K / BK, 16, (long)a.M * a.N, a.split_ws_elems);
+    }
+    if (cfg == 29 || cfg == 30) {
+        if (cfg == 30 && !gemm_fewrow_takes(a.M, a.N, a.K, b.split_k)) cfg = 29;
+        // once-read weights, non-temporal - from 64 MB up: the q|k, FFN-up and FFN-down launches gain 3-6 %, the 33.5 MB ones
+        // (N = K = 4096, four splits) LOSE 12 % with it (profiles/r03_fewrow_bounds.txt)
+        b.b_nt = (long)a.N * a.K >= (32L << 20) ? 1 : 0;
+    }
+    while (b.split_k > 1 && (long)b.split_k * a.M * a.N > a.split_ws_elems) --b.split_k;  // (the ring kernel's own count)
+    LTX_REQUIRE(!a.Bq || (a.N % 4 == 0 && !a.ep.d2s), "gemm: quantised few-row launch with N %% 4 != 0");
+    if ((b.split_k > 1 || cfg == 29 || cfg == 30) && a.N % 4 == 0 && !a.ep.d2s) {
+        if (b.split_k <= 1) {
+            b.split_k = 1;  // enough column tiles to fill the chip without a split (the FFN's first GEMM)
+            b.split_ws = nullptr;
+        }
+        launch_cfg(b, cfg, o, 0, stream);
+        return;
+    }
+    if (const int s2 = dtl_split_for(a, o)) {
+        b.split_k = s2;
+        b.split_bf16 = dtl_split_bf16(a, o);
+        launch_cfg(b, 75, o, 0, stream);
+        return;
+    }
+    b.split_k = 1;
+    b.split_ws = nullptr;
+    launch_dense(b, o, stream);
+}
+
+static void launch_dense(const GemmArgs& a, const GemmOpts& o, hipStream_t stream) {
+    if (gemm_experiments_forced(a, o, stream)) return;
     const int ncu = device_cu_count();
-    const int best = gemm_dense_cfg(a, ncu);
+    const int best = dense_cfg(a, ncu, o);
     // Ragged last round of the 192x256 kernel (round 4). With T = 9984 tokens the N = 4096 launches are 52 x 16 = 832 tiles = 3.25 rounds:
     // the fourth round runs 64 workgroups, K-long, on a quarter of the chip (19 % of the launch). Rows are independent, so such a launch is
     // split by rows into a head whose tiles are a whole number of rounds (48 row tiles = 768 tiles) and a tail (4 row tiles = 768 rows)
     // that goes through this function again - as 128 tiles of 192x128 on the ring kernel it takes half the time of the K-long quarter
     // round. Same kernels per output element as an unsplit launch of each part: bit-identical to those; option "gemm_rowsplit" = 0 = off (A/B).
-    const bool rowsplit_on = ltx_opt(OPT_GEMM_ROWSPLIT) != 0;
+    const bool rowsplit_on = o.gemm_rowsplit != 0;
     if (best == 75 && rowsplit_on && !a.ep.out_bf16_t && !a.ep.bias_m && a.split_k <= 1) {
         const int tm = a.M / 192, tn = a.N / 256;
         const long tiles = (long)tm * tn;
@@ -2670,13 +2064,44 @@ void launch_gemm_bf16(const GemmArgs& a_in, hipStream_t stream) {
                     if (e.gate_rowmap) e.gate_rowmap += row0;
                     return s;
                 };
-                launch_gemm_bf16_cfg(rows(0, tm_head * 192), 75, stream);
-                launch_gemm_bf16(rows(tm_head * 192, a.M - tm_head * 192), stream);
+                launch_cfg(rows(0, tm_head * 192), 75, o, 0, stream);
+                launch_dense(rows(tm_head * 192, a.M - tm_head * 192), o, stream);
                 return;
             }
         }
     }
-    launch_gemm_bf16_cfg(a, best, stream);
+    launch_cfg(a, best, o, 0, stream);
+}
+
+static void launch_gemm(const GemmArgs& a_in, const GemmOpts& o, hipStream_t stream) {
+    if (a_in.conv) return launch_conv(a_in, o, stream);
+    GemmArgs a = a_in;
+    gemm_experiments_group_m(a);
+    LTX_REQUIRE(!a.ep.pn_out, "gemm: the fused PixelNorm output exists for conv launches only");
+    LTX_REQUIRE(!a.Bq || (gemm_takes_codes(a.M, a.N, a.K) && a.split_ws && a.split_k == 0),
+                "gemm: 8-bit codes are de-quantised in the B stage of few-row launches only (M=%d N=%d K=%d)", a.M, a.N, a.K);
+    if (a.split_ws && a.split_k == 0) launch_dense_ws(a, o, stream);
+    else launch_dense(a, o, stream);
+}
+void launch_gemm_bf16(const GemmArgs& a, hipStream_t stream) { launch_gemm(a, gemm_opts(), stream); }
+
+void launch_gemm_bf16(const GemmArgs& a, hipStream_t stream, const NormAfter* na) {
+    LTX_REQUIRE(na && a.ep.out_f32 && !a.conv, "gemm: norm_after needs a dense launch with an f32 output");
+    const GemmOpts o = gemm_opts();
+    const bool fuse_on = o.finish_norm != 0;  // A/B option "finish_norm"
+    const int s2 = (fuse_on && finish_takes_norm(a, *na)) ? dtl_split_for(a, o) : 0;
+    if (s2) {
+        GemmArgs b = a;
+        b.split_k = s2;
+        b.split_bf16 = dtl_split_bf16(a, o);
+        validate(b);
+        ProfScope prof(PROF_GEMM, 2.0 * a.M * a.N * a.K, stream);
+        launch_dtl(b, o, stream, na);
+        return;
+    }
+    launch_gemm(a, o, stream);
+    launch_norm_mod(a.ep.out_f32, a.ep.ld_f32, na->scale, na->shift, na->mod_bstride, na->rows_per_batch, na->out, na->ldo, a.M, a.N, na->norm_kind,
+                    na->eps, na->round_norm_bf16, stream, na->row_map);
 }
 
 void launch_gemv_f32(const float* a, long lda, const bf16_t* W, long ldw, const float* bias, float* out, long ldo,

@@ -7,6 +7,7 @@ text-embedding connector and the VAE encoder fixtures are cross-checked the same
     python tests/golden/make_golden.py
     python tests/golden/make_golden.py --synthetic-digests    # only synthetic_param_digests.json; needs the built library and a GPU
     python tests/golden/make_golden.py --gemm-asm-family-digests    # only gemm_asm_family_digests.json; the same needs
+    python tests/golden/make_golden.py --gemm-launcher-paths-digests    # only gemm_launcher_paths_digests.json; the same needs, 256 CUs
 """
 import math
 import os
@@ -265,7 +266,43 @@ def make_gemm_asm_family_digests():
     print("assembly-loop GEMM digests:", len(d))
 
 
+def make_gemm_launcher_paths_digests():
+    """gemm_launcher_paths_digests.json: the output bits of launch_gemm_bf16's multi-launch and split-count branches
+    (tests/helpers/gemm_launcher_paths.py). Like the recorder above it records the library itself (LTX_LIB may name a build of the commit
+    whose bits are to be kept) and runs every case twice."""
+    import importlib
+    import json
+
+    import torch
+
+    sys.path.insert(0, os.path.join(HERE, "..", ".."))
+    sys.path.insert(0, os.path.join(HERE, "..", "helpers"))
+    import gemm_launcher_paths as paths
+
+    ltx = importlib.import_module("ltx-video-swift-mlx_amd")
+    ncu = torch.cuda.get_device_properties(0).multi_processor_count
+    assert ncu == paths.NCU, f"the cases are the launcher's branches on {paths.NCU} CUs; this device has {ncu}"
+    assert paths.rowsplit_tile_cfg(ltx) == 75, "the row-split case would not run the 192 x 256 kernel"
+
+    def once():
+        ctx = ltx.Context(0)
+        d = paths.all_cases(ltx, ctx)
+        ctx.close()
+        return d
+
+    d, again = once(), once()
+    unstable = sorted(k for k in d if d[k] != again[k])
+    assert not unstable, f"not reproducible between two runs: {unstable}"
+    assert sorted(d) == paths.expected_keys()
+    with open(os.path.join(HERE, "gemm_launcher_paths_digests.json"), "w") as f:
+        json.dump({"seed": paths.SEED, "digests": d}, f, indent=0, sort_keys=True)
+        f.write("\n")
+    print("launcher path digests:", len(d))
+
+
 def main():
+    if "--gemm-launcher-paths-digests" in sys.argv[1:]:
+        return make_gemm_launcher_paths_digests()
     if "--synthetic-digests" in sys.argv[1:]:
         return make_synthetic_param_digests()
     if "--gemm-asm-family-digests" in sys.argv[1:]:

@@ -66,7 +66,7 @@ int main() {
     (void)hipEventRecord(e1);
     (void)hipDeviceSynchronize();
     float ms; (void)hipEventElapsedTime(&ms, e0, e1);
-    const bool tall = conv_halo2_takes(g) != 0;  // (option conv_tall, CONV_TALL=0 turns it off): 384-row tiles, stamps of the main launch only
+    const bool tall = conv_halo2_takes(g, gemm_opts()) != 0;  // (option conv_tall, CONV_TALL=0 turns it off): 384-row tiles, stamps of the main launch only
     const int tiles = tall ? (int)(P / 384) * (N / 128) / 256 * 256 : (int)((P + 191) / 192) * ((N + 127) / 128);
     if (tiles > 16383) printf("(more tiles than stamp slots: statistics over the first 16383)\n");
     printf("conv %d -> %d at %dx%dx%d: %d tiles, %.1f us per launch, %.0f TFLOP/s\n", C, N, F, H, W, tiles, ms * 1e3 / reps, 2.0 * P * N * 27 * C / (ms / reps * 1e-3) / 1e12);
