@@ -819,6 +819,40 @@ int ltx_op_gemm_bf16_gated_residual_norm(ltx_ctx* ctx, const uint16_t* A, long l
                                          const float* bias, const float* gate, float gate_scalar, int M, int N, int K,
                                          float* x, long ldx, const float* scale, const float* shift, float eps,
                                          uint16_t* xn, long ldxn, int fused);
+/* One launch of the 192 x 256 (tile_cfg 75) or the 384 x 256 (tile_cfg 76) GEMM kernel with any epilogue it has, for the tests that pin
+ * every form of their store: v = act(A.B^T + bias_n[n] + bias_m[m]), rounded through bf16 when round_bf16; stored to out_f32 and / or
+ * out_bf16, or, with resid, out_f32[m][n] = (resid_src ? resid_src : out_f32)[m][n] + gate(m, n) * v (and its bf16 copy), gate(m, n) =
+ * gate ? gate[(gate_rowmap ? gate_rowmap[m] : m / rows_per_batch) * gate_bstride + n] : gate_scalar. split_k > 1 (tile_cfg 75): that many
+ * K ranges through the context's workspace, as f32 or (split_bf16) bf16 partial tiles, and the finish pass. An error for a launch the
+ * kernel does not take (whole tiles, K % 64 == 0, leading dimensions % 8 == 0; 76: plain stores only). */
+typedef struct ltx_gemm_tile_launch {
+    uint32_t struct_size; /* sizeof(ltx_gemm_tile_launch) */
+    int tile_cfg;
+    const uint16_t* A; /* [M][lda] bf16 */
+    long lda;
+    const uint16_t* B; /* [N][ldb] bf16 */
+    long ldb;
+    int M, N, K;
+    int split_k;       /* >= 1 */
+    int split_bf16;
+    int act;           /* 0 none, 1 gelu-tanh, 2 silu */
+    int round_bf16;
+    int resid;
+    const float* bias_n; /* [N] or NULL */
+    const float* bias_m; /* [M] or NULL */
+    float* out_f32;      /* [M][ld_f32] or NULL */
+    long ld_f32;
+    uint16_t* out_bf16;  /* [M][ld_bf16] or NULL */
+    long ld_bf16;
+    const float* resid_src; /* [M][ld_resid] or NULL: in place on out_f32 */
+    long ld_resid;
+    const float* gate;      /* or NULL: gate_scalar */
+    long gate_bstride;
+    const int32_t* gate_rowmap; /* [M] or NULL */
+    int rows_per_batch;     /* 0: M */
+    float gate_scalar;
+} ltx_gemm_tile_launch;
+int ltx_op_gemm_tile(ltx_ctx* ctx, const ltx_gemm_tile_launch* launch);
 /* out[m][n] = sum_k in_act(a[m][k]) W[n][k] + bias[n], f32 x bf16 -> f32, M <= 8 */
 int ltx_op_gemv_f32(ltx_ctx* ctx, const float* a, long lda, const uint16_t* W, long ldw, const float* bias, float* out,
                     long ldo, int M, int N, int K, int in_act);

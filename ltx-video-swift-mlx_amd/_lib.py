@@ -84,6 +84,17 @@ class GemvJob(C.Structure):
                 ("ldo", C.c_long), ("N", C.c_int), ("K", C.c_int), ("in_act", C.c_int)]
 
 
+class GemmTileLaunch(C.Structure):
+    """``ltx_gemm_tile_launch``: one launch of the 192 x 256 / 384 x 256 GEMM kernel with any epilogue it has (``ltx_op_gemm_tile``)."""
+
+    _fields_ = [("struct_size", C.c_uint32), ("tile_cfg", C.c_int), ("A", C.c_void_p), ("lda", C.c_long), ("B", C.c_void_p), ("ldb", C.c_long),
+                ("M", C.c_int), ("N", C.c_int), ("K", C.c_int), ("split_k", C.c_int), ("split_bf16", C.c_int), ("act", C.c_int),
+                ("round_bf16", C.c_int), ("resid", C.c_int), ("bias_n", C.c_void_p), ("bias_m", C.c_void_p), ("out_f32", C.c_void_p),
+                ("ld_f32", C.c_long), ("out_bf16", C.c_void_p), ("ld_bf16", C.c_long), ("resid_src", C.c_void_p), ("ld_resid", C.c_long),
+                ("gate", C.c_void_p), ("gate_bstride", C.c_long), ("gate_rowmap", C.c_void_p), ("rows_per_batch", C.c_int),
+                ("gate_scalar", C.c_float)]
+
+
 class DualModelConfig(C.Structure):
     """``ltx_dual_model_config``: the block config plus the top-level widths of LTX2Transformer (LTXConfig.swift:83-177)."""
 
@@ -277,6 +288,7 @@ SIGNATURES = {
     "ltx_dual_blocks_forward_dev": (_i, [_vp, C.POINTER(DualForwardArgs)]),
     "ltx_op_norm_mod2": (_i, [_vp, C.POINTER(NormMod2Job), C.POINTER(NormMod2Job), _f]),
     "ltx_op_gemv_group": (_i, [_vp, C.POINTER(GemvJob), _i, _i]),
+    "ltx_op_gemm_tile": (_i, [_vp, C.POINTER(GemmTileLaunch)]),
     "ltx_dual_model_config_default": (None, [C.POINTER(DualModelConfig)]),
     "ltx_dual_model_init_synthetic": (_i, [_vp, C.POINTER(DualModelConfig), _u64]),
     "ltx_dual_model_load": (_i, [_vp, C.c_char_p, C.POINTER(DualModelConfig)]),

@@ -208,6 +208,30 @@ int ltx_op_gemm_bf16_gated_residual_norm(ltx_ctx* ctx, const uint16_t* A, long l
     });
 }
 
+int ltx_op_gemm_tile(ltx_ctx* ctx, const ltx_gemm_tile_launch* l) {
+    return with_ctx(ctx, [&] {
+        LTX_REQUIRE(l && l->struct_size == sizeof(ltx_gemm_tile_launch), "ltx_op_gemm_tile: null argument or a struct_size of another ABI");
+        LTX_REQUIRE(l->tile_cfg == 75 || l->tile_cfg == 76, "ltx_op_gemm_tile: tile_cfg %d is neither 75 (192x256) nor 76 (384x256)", l->tile_cfg);
+        LTX_REQUIRE(l->A && l->B && l->split_k >= 1, "ltx_op_gemm_tile: null operand or split_k < 1");
+        GemmArgs g;
+        g.A = l->A; g.lda = l->lda; g.B = l->B; g.ldb = l->ldb; g.M = l->M; g.N = l->N; g.K = l->K;
+        GemmEpilogue& e = g.ep;
+        e.bias_n = l->bias_n; e.bias_m = l->bias_m; e.act = l->act; e.round_bf16 = l->round_bf16;
+        e.out_f32 = l->out_f32; e.ld_f32 = l->ld_f32; e.out_bf16 = l->out_bf16; e.ld_bf16 = l->ld_bf16;
+        e.resid = l->resid; e.resid_src = l->resid_src; e.ld_resid = l->ld_resid;
+        e.gate = l->gate; e.gate_bstride = l->gate_bstride; e.gate_rowmap = l->gate_rowmap; e.gate_scalar = l->gate_scalar;
+        e.rows_per_batch = l->rows_per_batch > 0 ? l->rows_per_batch : l->M;
+        if (l->split_k > 1) {
+            g.split_k = l->split_k;
+            g.split_bf16 = l->split_bf16;
+            op_workspace(ctx, (size_t)g.split_k * l->M * l->N * 4);
+            g.split_ws = ctx->op_ws.as<float>();
+            g.split_ws_elems = (long)(ctx->op_ws.bytes / 4);
+        }
+        launch_gemm_bf16_cfg(g, l->tile_cfg, ctx->stream);
+    });
+}
+
 int ltx_op_gemv_f32(ltx_ctx* ctx, const float* a, long lda, const uint16_t* W, long ldw, const float* bias, float* out,
                     long ldo, int M, int N, int K, int in_act) {
     return with_ctx(ctx, [&] { launch_gemv_f32(a, lda, W, ldw, bias, out, ldo, M, N, K, in_act, ctx->stream); });

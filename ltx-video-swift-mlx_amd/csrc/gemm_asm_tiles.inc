@@ -14,8 +14,10 @@
 //   * C++ prepares those offsets, the fragment read addresses of slot 0 and the buffer descriptors, the stream runs the whole K loop
 //     and leaves the accumulators of the first rows in AGPRs in the map a[(mi * 8 + ni) * 4 ..] (tools/gen_gemm_asm.py's dump reads it);
 //   * the plain-store epilogue: 32 rows x 128 columns at a time through the wave's LDS scratch, the 16 scratch reads of a group issued
-//     together, one 16-byte column group per lane (asm_store_group). One accumulator chain per output element, K ascending, and one
-//     copy of the epilogue arithmetic: the kernels give the same bits on the same operands.
+//     together, one 16-byte column group per lane. The form of the store is picked once per launch (asm_plain_variant: four
+//     instantiated variants through per-lane row pointers, asm_store_rows + AsmRowStore; anything else through the generic
+//     asm_store_group). One accumulator chain per output element, K ascending, and the same epilogue operations in the same order in
+//     every form: the kernels give the same bits on the same operands.
 //   * one launcher helper (launch_asm_tile): the dynamic-LDS attribute once per device, then the launch.
 namespace {
 
@@ -63,6 +65,23 @@ LTX_DEVFN int asm_scratch_lane(int lane) { return (((lane >> 4) * 4) * WN + (lan
 
 #if defined(DTL_STAMPS) || defined(QKV_STAMPS) || defined(TALL_STAMPS)  // tools/ubench/gemm_{dtl,qkv,tall}_stamps.hip
 LTX_DEVFN unsigned long long* asm_stamp_slot(int wave) { return (blockIdx.x == 7) ? &g_gemm_stamps[wave][0] : &g_gemm_stamps[4][0]; }
+// Epilogue stamps of the same builds, shader-clock cycles per wave of workgroup 7: [0] the stream has been left; per row group in the
+// order it is stored [1 + 2 i] its dump is in LDS (for a group the stream left there: the group before it is done) and [2 + 2 i] its
+// scratch reads have landed and its last store is issued; [1 + 2 groups] the final vmcnt(0). The indices are constants: registers.
+__device__ unsigned long long g_gemm_epi_stamps[5][16];
+#define ASM_EPI_STAMPS unsigned long long epi_ts[16] = {}
+#define ASM_EPI_STAMP(i) epi_ts[i] = __builtin_readcyclecounter()
+#define ASM_EPI_STAMPS_FLUSH(n)                                                               \
+    do {                                                                                      \
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                      \
+        ASM_EPI_STAMP(n);                                                                     \
+        if (lane == 0)                                                                        \
+            for (int i_ = 0; i_ <= (n); ++i_) g_gemm_epi_stamps[blockIdx.x == 7 ? wave : 4][i_] = epi_ts[i_]; \
+    } while (0)
+#else
+#define ASM_EPI_STAMPS
+#define ASM_EPI_STAMP(i)
+#define ASM_EPI_STAMPS_FLUSH(n)
 #endif
 
 // ---- the plain-store epilogue ----
@@ -126,6 +145,96 @@ LTX_DEVFN void asm_store_group(const float* scr, int lane, int gm0, int gn, cons
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 }
 
+// ---- the plain-store epilogue, one variant per launch ----
+// These launches are one round with one wave per SIMD: nothing overlaps the epilogue, so it costs the sum of its issue slots. The
+// generic body above tests ep.act / round_bf16 / out_f32 / out_bf16 in every 4-element step and rebuilds (long)gm * ld + gn for every
+// store. The forms the launchers really send are therefore picked ONCE per kernel (asm_plain_variant, wave-uniform) and instantiated
+// with the activation and the outputs as template arguments: a step is then arithmetic, a pack and a store through a per-lane row
+// pointer that advances by a wave-uniform stride. Same operations in the same order per element as asm_activate + asm_store: same bits.
+typedef __attribute__((ext_vector_type(2))) float f32x2;
+typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
+
+// the two store dwords of four values: two v_cvt_pk_bf16_f32 (round-to-nearest-even, as f32_to_bf16) and nothing else
+LTX_DEVFN uint2 asm_pack_bf16x4(const f32x4& v) {
+    const bf16x2_t lo = __builtin_convertvector(f32x2{v[0], v[1]}, bf16x2_t);
+    const bf16x2_t hi = __builtin_convertvector(f32x2{v[2], v[3]}, bf16x2_t);
+    return uint2{__builtin_bit_cast(uint32_t, lo), __builtin_bit_cast(uint32_t, hi)};
+}
+// gelu_tanh (common.h) on a pair: the same multiplies, fma and add per element, issued as v_pk_mul_f32 / v_pk_fma_f32 / v_pk_add_f32
+LTX_DEVFN f32x2 asm_gelu_tanh2(f32x2 x) {
+    const float c0 = -2.0f * 0.7978845608028654f * 1.4426950408889634f;
+    const float c1 = c0 * 0.044715f;
+    const f32x2 t = x * __builtin_elementwise_fma(f32x2{c1, c1}, x * x, f32x2{c0, c0});
+    const f32x2 d = f32x2{1.0f, 1.0f} + f32x2{__builtin_amdgcn_exp2f(t[0]), __builtin_amdgcn_exp2f(t[1])};
+    return x * f32x2{__builtin_amdgcn_rcpf(d[0]), __builtin_amdgcn_rcpf(d[1])};
+}
+
+enum { ASM_OUT_BF16 = 1, ASM_OUT_F32 = 2 };
+// Row stores of one lane: pb / pf point at this lane's four columns of the row its next step stores, sb / sf are the elements from
+// one step's row to the next's (RPI rows). ACT is LTX_ACT_NONE or LTX_ACT_GELU_TANH, OUTS a mask of ASM_OUT_*; BIAS adds the column
+// bias (the split-K partial tiles are stored raw: adding a zero bias would turn -0 into +0).
+template <int ACT, int OUTS, bool BIAS>
+struct AsmRowStore {
+    bf16_t* pb;
+    float* pf;
+    long sb, sf;
+    f32x4 bias;
+    LTX_DEVFN AsmRowStore after(int steps) const { return {pb + steps * sb, pf + steps * sf, sb, sf, bias}; }  // wave-uniform offset
+    LTX_DEVFN void operator()(f32x4 v) {
+        if constexpr (BIAS) v += bias;
+        if constexpr (ACT == LTX_ACT_GELU_TANH) {
+            const f32x2 lo = asm_gelu_tanh2(f32x2{v[0], v[1]}), hi = asm_gelu_tanh2(f32x2{v[2], v[3]});
+            v = f32x4{lo[0], lo[1], hi[0], hi[1]};
+        }
+        if constexpr ((OUTS & ASM_OUT_F32) != 0) {
+            *(f32x4*)pf = v;
+            pf += sf;
+        }
+        if constexpr ((OUTS & ASM_OUT_BF16) != 0) {
+            *(uint2*)pb = asm_pack_bf16x4(v);
+            pb += sb;
+        }
+    }
+};
+// the store of rows row0 + lane / LPR + RPI * step, this lane's columns gn .. gn + 3: the only per-lane address arithmetic of a kernel
+template <int WN, int ACT, int OUTS, bool BIAS>
+LTX_DEVFN AsmRowStore<ACT, OUTS, BIAS> asm_row_store(bf16_t* out_bf16, long ld_bf16, float* out_f32, long ld_f32, int lane, int row0, int gn, const f32x4& bias) {
+    using G = AsmGroup<WN>;
+    const int row = row0 + lane / G::LPR;
+    return {out_bf16 + (long)row * ld_bf16 + gn, out_f32 + (long)row * ld_f32 + gn, G::RPI * ld_bf16, G::RPI * ld_f32, bias};
+}
+// asm_store_group for a row store: the group's scratch reads issued together, then its steps in row order
+template <int WN, class Put>
+LTX_DEVFN void asm_store_rows(const float* scr, int lane, Put put) {
+    using G = AsmGroup<WN>;
+    f32x4 vv[G::NITG];
+#pragma unroll
+    for (int it = 0; it < G::NITG; ++it) vv[it] = *(const f32x4*)(scr + (it * G::RPI + lane / G::LPR) * WN + (lane % G::LPR) * 4);
+#pragma unroll
+    for (int it = 0; it < G::NITG; ++it) put(vv[it]);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+}
+// The variant of a plain-store launch: 0 = the generic body, 1 .. 4 = the forms asm_plain_dispatch lists. round_bf16 changes nothing when
+// only bf16 is stored (rounding twice is rounding once); a per-row bias or SiLU stays generic (no launcher sends them to these kernels
+// on a hot path).
+LTX_DEVFN int asm_plain_variant(const GemmEpilogue& ep) {
+    if (ep.bias_m || (ep.round_bf16 && ep.out_f32)) return 0;
+    if (ep.act == LTX_ACT_NONE) return ep.out_f32 ? (ep.out_bf16 ? 4 : 3) : 1;
+    if (ep.act == LTX_ACT_GELU_TANH && !ep.out_f32) return 2;
+    return 0;
+}
+// body(act, outs) with both as integral constants for variants 1 .. 4; false for variant 0
+template <class Body>
+LTX_DEVFN bool asm_plain_dispatch(int variant, Body&& body) {
+    using std::integral_constant;
+    if (variant == 1) body(integral_constant<int, LTX_ACT_NONE>{}, integral_constant<int, ASM_OUT_BF16>{});
+    else if (variant == 2) body(integral_constant<int, LTX_ACT_GELU_TANH>{}, integral_constant<int, ASM_OUT_BF16>{});
+    else if (variant == 3) body(integral_constant<int, LTX_ACT_NONE>{}, integral_constant<int, ASM_OUT_F32>{});
+    else if (variant == 4) body(integral_constant<int, LTX_ACT_NONE>{}, integral_constant<int, ASM_OUT_F32 | ASM_OUT_BF16>{});
+    else return false;
+    return true;
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // 192 x 256 tile. The wide DiT GEMMs (fused q|k: N = 8192, FFN up: N = 16384) at 1536 tokens are exactly one / two rounds of 256 such
 // tiles, where 192 x 128 tiles need two / four rounds and pay the fixed cost of a round (ring fill, epilogue with every workgroup
@@ -179,6 +288,8 @@ __global__ __launch_bounds__(256, 1) void gemm_bf16_kernel_dtl(const GemmArgs g)
 #include "gemm_dtl_192x256_clobbers.inc"
     );
     __syncthreads();  // every wave is done with the K-tile slots before the epilogue scratch reuses them
+    ASM_EPI_STAMPS;
+    ASM_EPI_STAMP(0);
     // Epilogue: three groups of 32 rows, each dumped from a[0:191] into the wave's LDS scratch (assembly dump shared with
     // tools/gen_gemm_asm.py: same accumulator map)
     constexpr int LPR = AsmGroup<WN>::LPR, RPI = AsmGroup<WN>::RPI, NITG = AsmGroup<WN>::NITG;
@@ -186,21 +297,23 @@ __global__ __launch_bounds__(256, 1) void gemm_bf16_kernel_dtl(const GemmArgs g)
     // LDS byte address of this lane's first scratch element (the dynamic LDS of this kernel starts at 0, as the main loop assumes)
     const unsigned scr_lane = (unsigned)(wave * (32 * WN * 4) + asm_scratch_lane<WN>(lane));
     const int gn = n0 + wc * WN + (lane % LPR) * 4;
-    if (g.split_k > 1) {  // raw partial tile -> this K range's slice of the workspace: a rolled loop, no bias
+    if (g.split_k > 1) {  // raw partial tile -> this K range's slice of the workspace: no bias
         float* ws = g.split_ws + (long)blockIdx.y * g.M * g.N;
         bf16_t* wsb = (bf16_t*)g.split_ws + (long)blockIdx.y * g.M * g.N;
-        static_for<0, 3>([&](auto grp_c) {
-            constexpr int grp = decltype(grp_c)::value;
+        auto partial = [&](auto outs_c) {  // the form of the store is picked once, not per step
+            constexpr int outs = decltype(outs_c)::value;
+            const auto st = asm_row_store<WN, LTX_ACT_NONE, outs, false>(wsb, g.N, ws, g.N, lane, m0 + wr * WM, gn, f32x4{});
+            static_for<0, 3>([&](auto grp_c) {
+                constexpr int grp = decltype(grp_c)::value;
 #include "gemm_asm_192x256_dump.inc"
-#pragma unroll 4
-            for (int it = 0; it < 32 / RPI; ++it) {
-                const int row = it * RPI + lane / LPR;
-                const f32x4 v = *(const f32x4*)(scr + row * WN + (lane % LPR) * 4);
-                if (g.split_bf16) asm_store_bf16(wsb, g.N, m0 + wr * WM + grp * 32 + row, gn, v);
-                else *(f32x4*)(ws + (long)(m0 + wr * WM + grp * 32 + row) * g.N + gn) = v;
-            }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        });
+                ASM_EPI_STAMP(1 + 2 * grp);
+                asm_store_rows<WN>(scr, lane, st.after(grp * NITG));
+                ASM_EPI_STAMP(2 + 2 * grp);
+            });
+        };
+        if (g.split_bf16) partial(std::integral_constant<int, ASM_OUT_BF16>{});
+        else partial(std::integral_constant<int, ASM_OUT_F32>{});
+        ASM_EPI_STAMPS_FLUSH(7);
         return;
     }
     const GemmEpilogue& ep = g.ep;
@@ -217,45 +330,83 @@ __global__ __launch_bounds__(256, 1) void gemm_bf16_kernel_dtl(const GemmArgs g)
         const bool gate_uniform = ep.gate && !ep.gate_rowmap && row_lo / ep.rows_per_batch == row_hi / ep.rows_per_batch;
         f32x4 gtu = f32x4{ep.gate_scalar, ep.gate_scalar, ep.gate_scalar, ep.gate_scalar};
         if (gate_uniform) gtu = *(const f32x4*)(ep.gate + (long)(row_lo / ep.rows_per_batch) * ep.gate_bstride + gn);
-        f32x4 rs[2][NITG];
-        auto fetch = [&](auto grp_c, auto buf_c) {
-            constexpr int grp = decltype(grp_c)::value, buf = decltype(buf_c)::value;
+        // The form is picked once, like the plain stores: FAST is what the DiT sends (no row bias, activation or rounding, an f32 stream
+        // with or without its bf16 copy) and stores through row pointers; GATE_ROWS loads the gate per row (row map, or a wave whose rows
+        // span two batch elements). Anything else keeps the generic step. The residual rows are read through a row pointer in every form.
+        auto resid_body = [&](auto fast_c, auto mirror_c, auto gate_rows_c) {
+            constexpr bool FAST = decltype(fast_c)::value, MIRROR = decltype(mirror_c)::value, GATE_ROWS = decltype(gate_rows_c)::value;
+            const float* rp = rbase + (long)(row_lo + lane / LPR) * rld + gn;
+            const long rstep = RPI * rld;
+            auto st = asm_row_store<WN, LTX_ACT_NONE, ASM_OUT_F32 | (MIRROR ? ASM_OUT_BF16 : 0), false>(ep.out_bf16, ep.ld_bf16, ep.out_f32, ep.ld_f32, lane, row_lo,
+                                                                                                     gn, f32x4{});
+            f32x4 rs[2][NITG];
+            auto fetch = [&](auto grp_c, auto buf_c) {
+                constexpr int grp = decltype(grp_c)::value, buf = decltype(buf_c)::value;
 #pragma unroll
-            for (int it = 0; it < NITG; ++it) rs[buf][it] = *(const f32x4*)(rbase + (long)(m0 + wr * WM + grp * 32 + it * RPI + lane / LPR) * rld + gn);
-        };
-        fetch(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{});
-        static_for<0, 3>([&](auto grp_c) {
-            constexpr int grp = decltype(grp_c)::value;
-            constexpr int buf = grp & 1;
-            if constexpr (grp + 1 < 3) fetch(std::integral_constant<int, grp + 1>{}, std::integral_constant<int, (grp + 1) & 1>{});
+                for (int it = 0; it < NITG; ++it) rs[buf][it] = *(const f32x4*)(rp + (grp * NITG + it) * rstep);
+            };
+            fetch(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{});
+            static_for<0, 3>([&](auto grp_c) {
+                constexpr int grp = decltype(grp_c)::value;
+                constexpr int buf = grp & 1;
+                if constexpr (grp + 1 < 3) fetch(std::integral_constant<int, grp + 1>{}, std::integral_constant<int, (grp + 1) & 1>{});
 #include "gemm_asm_192x256_dump.inc"
-            static_for<0, 2>([&](auto half_c) {
-                constexpr int half = decltype(half_c)::value;
-                f32x4 vv[NITG / 2];  // the scratch reads of eight two-row steps issued together
+                static_for<0, 2>([&](auto half_c) {
+                    constexpr int half = decltype(half_c)::value;
+                    f32x4 vv[NITG / 2];  // the scratch reads of eight two-row steps issued together
 #pragma unroll
-                for (int i2 = 0; i2 < NITG / 2; ++i2) vv[i2] = *(const f32x4*)(scr + ((half * (NITG / 2) + i2) * RPI + lane / LPR) * WN + (lane % LPR) * 4);
+                    for (int i2 = 0; i2 < NITG / 2; ++i2) vv[i2] = *(const f32x4*)(scr + ((half * (NITG / 2) + i2) * RPI + lane / LPR) * WN + (lane % LPR) * 4);
 #pragma unroll
-                for (int i2 = 0; i2 < NITG / 2; ++i2) {
-                    const int it = half * (NITG / 2) + i2;
-                    const int gm = m0 + wr * WM + grp * 32 + it * RPI + lane / LPR;
-                    f32x4 v = asm_activate<true>(ep, vv[i2] + bias, gm);
-                    f32x4 gt = gtu;
-                    if (ep.gate && !gate_uniform)
-                        gt = *(const f32x4*)(ep.gate + (long)(ep.gate_rowmap ? ep.gate_rowmap[gm] : gm / ep.rows_per_batch) * ep.gate_bstride + gn);
+                    for (int i2 = 0; i2 < NITG / 2; ++i2) {
+                        const int it = half * (NITG / 2) + i2;
+                        const int gm = row_lo + grp * 32 + it * RPI + lane / LPR;
+                        f32x4 v = vv[i2] + bias;
+                        if constexpr (!FAST) v = asm_activate<true>(ep, v, gm);
+                        f32x4 gt = gtu;
+                        if constexpr (!FAST) {
+                            if (ep.gate && !gate_uniform)
+                                gt = *(const f32x4*)(ep.gate + (long)(ep.gate_rowmap ? ep.gate_rowmap[gm] : gm / ep.rows_per_batch) * ep.gate_bstride + gn);
+                        } else if constexpr (GATE_ROWS) {
+                            gt = *(const f32x4*)(ep.gate + (long)(ep.gate_rowmap ? ep.gate_rowmap[gm] : gm / ep.rows_per_batch) * ep.gate_bstride + gn);
+                        }
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = rs[buf][it][e] + gt[e] * v[e];
-                    asm_store(ep, gm, gn, v);
-                }
+                        for (int e = 0; e < 4; ++e) v[e] = rs[buf][it][e] + gt[e] * v[e];
+                        if constexpr (FAST) st(v);  // the steps come in row order
+                        else asm_store(ep, gm, gn, v);
+                    }
+                });
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the scratch is rewritten by the next dump
             });
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the scratch is rewritten by the next dump
-        });
+        };
+        using std::false_type;
+        using std::true_type;
+        const bool fast = !ep.bias_m && ep.act == LTX_ACT_NONE && !ep.round_bf16 && ep.out_f32;
+        const bool gate_rows = ep.gate && !gate_uniform;
+        if (!fast) resid_body(false_type{}, false_type{}, false_type{});
+        else if (gate_rows) ep.out_bf16 ? resid_body(true_type{}, true_type{}, true_type{}) : resid_body(true_type{}, false_type{}, true_type{});
+        else ep.out_bf16 ? resid_body(true_type{}, true_type{}, false_type{}) : resid_body(true_type{}, false_type{}, false_type{});
         return;
     }
-    static_for<0, 3>([&](auto grp_c) {
-        constexpr int grp = decltype(grp_c)::value;
+    const bool specialised = asm_plain_dispatch(__builtin_amdgcn_readfirstlane(asm_plain_variant(ep)), [&](auto act_c, auto outs_c) {
+        const auto st = asm_row_store<WN, decltype(act_c)::value, decltype(outs_c)::value, true>(ep.out_bf16, ep.ld_bf16, ep.out_f32, ep.ld_f32, lane,
+                                                                                                 m0 + wr * WM, gn, bias);
+        static_for<0, 3>([&](auto grp_c) {
+            constexpr int grp = decltype(grp_c)::value;
 #include "gemm_asm_192x256_dump.inc"
-        asm_store_group<WN>(scr, lane, m0 + wr * WM + grp * 32, gn, bias, AsmPlainStore<true>{ep});
+            ASM_EPI_STAMP(1 + 2 * grp);
+            asm_store_rows<WN>(scr, lane, st.after(grp * NITG));
+            ASM_EPI_STAMP(2 + 2 * grp);
+        });
     });
+    if (!specialised)
+        static_for<0, 3>([&](auto grp_c) {
+            constexpr int grp = decltype(grp_c)::value;
+#include "gemm_asm_192x256_dump.inc"
+            ASM_EPI_STAMP(1 + 2 * grp);
+            asm_store_group<WN>(scr, lane, m0 + wr * WM + grp * 32, gn, bias, AsmPlainStore<true>{ep});
+            ASM_EPI_STAMP(2 + 2 * grp);
+        });
+    ASM_EPI_STAMPS_FLUSH(7);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -312,6 +463,8 @@ __global__ __launch_bounds__(256, 1) void gemm_bf16_kernel_qkv(const GemmQkvArgs
 #include "gemm_qkv_192x384_clobbers.inc"
     );
     // (the stream ends behind a barrier: every wave is done with the K-tile slots, and its VGPR-held accumulators are in LDS)
+    ASM_EPI_STAMPS;
+    ASM_EPI_STAMP(0);
     // V epilogue: fragment vf = 4 mi + nv holds C[16 mi + 4 (lane >> 4) + r][16 nv + (lane & 15)], r = 0..3, of the wave's 96 x 64 V
     // tile: four consecutive tokens of one channel = 8 contiguous bytes of V^T. The tile's rows lie in one batch element.
     {
@@ -320,8 +473,12 @@ __global__ __launch_bounds__(256, 1) void gemm_bf16_kernel_qkv(const GemmQkvArgs
         const int d0 = tn * 128 + wc * WNV + (lane & 15);
         bf16_t* vbase = g.vt + (long)bi * g.vt_bstride + tok0;
         float bv[4];
+        bf16_t* vrow[4];  // this lane's four V^T rows (channels d0 + 16 nv): a fragment's store is a constant offset from one of them
 #pragma unroll
-        for (int nv = 0; nv < 4; ++nv) bv[nv] = g.bias_v ? g.bias_v[d0 + nv * 16] : 0.f;
+        for (int nv = 0; nv < 4; ++nv) {
+            bv[nv] = g.bias_v ? g.bias_v[d0 + nv * 16] : 0.f;
+            vrow[nv] = vbase + (long)(d0 + nv * 16) * g.ldvt;
+        }
         static_for<0, 24>([&](auto vf_c) {
             constexpr int vf = decltype(vf_c)::value;
             constexpr int mi = vf / 4, nv = vf % 4;
@@ -333,24 +490,25 @@ __global__ __launch_bounds__(256, 1) void gemm_bf16_kernel_qkv(const GemmQkvArgs
                 f0 = t[0], f1 = t[1], f2 = t[2], f3 = t[3];
             }
             const float bn = bv[nv];
-            uint2 pk;
-            pk.x = pack_bf16x2(f0 + bn, f1 + bn);
-            pk.y = pack_bf16x2(f2 + bn, f3 + bn);
-            *(uint2*)(vbase + (long)(d0 + nv * 16) * g.ldvt + mi * 16) = pk;
+            *(uint2*)(vrow[nv] + mi * 16) = asm_pack_bf16x4(f32x4{f0 + bn, f1 + bn, f2 + bn, f3 + bn});
         });
     }
+    ASM_EPI_STAMP(1);
     // q|k epilogue: three groups of 32 rows, each dumped from a[0:191] into the wave's LDS scratch
     constexpr int WN = WNQ;
     float* scr = (float*)(smem + wave * (32 * WN * 4));
     const unsigned scr_lane = (unsigned)(wave * (32 * WN * 4) + asm_scratch_lane<WN>(lane));
     const int gn = tn * 256 + wc * WN + (lane % AsmGroup<WN>::LPR) * 4;
     const f32x4 bias = asm_column_bias(g.bias_qk, gn);
+    const auto qk_store = asm_row_store<WN, LTX_ACT_NONE, ASM_OUT_BF16, true>(g.qk, g.ld_qk, nullptr, 0, lane, m0 + wr * WM, gn, bias);
     static_for<0, 3>([&](auto grp_c) {
         constexpr int grp = decltype(grp_c)::value;
 #include "gemm_asm_192x256_dump.inc"
-        asm_store_group<WN>(scr, lane, m0 + wr * WM + grp * 32, gn, bias,
-                            [&](int gm, int gn_, const f32x4& val) { asm_store_bf16(g.qk, g.ld_qk, gm, gn_, val); });
+        ASM_EPI_STAMP(2 + 2 * grp);
+        asm_store_rows<WN>(scr, lane, qk_store.after(grp * AsmGroup<WN>::NITG));
+        ASM_EPI_STAMP(3 + 2 * grp);
     });
+    ASM_EPI_STAMPS_FLUSH(8);  // [1]: the V^T stores are issued; q|k groups from [2]
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -402,18 +560,38 @@ __global__ __launch_bounds__(256, 1) void gemm_bf16_kernel_tall(const GemmArgs g
 #include "gemm_tall_384x256_clobbers.inc"
     );
     // (the stream ends behind a barrier: every wave is done with the K-tile slots. From here on a wave touches its own WAVE_LDS bytes only.)
+    ASM_EPI_STAMPS;
+    ASM_EPI_STAMP(0);
     const unsigned scr_lane = (unsigned)(wave * WAVE_LDS + asm_scratch_lane<WN>(lane));
     const int gn = n0 + wc * WN + (lane % AsmGroup<WN>::LPR) * 4;
     const GemmEpilogue& ep = g.ep;
     const f32x4 bias = asm_column_bias(ep.bias_n, gn);
-    static_for<0, 6>([&](auto ord_c) {
-        constexpr int grp = (decltype(ord_c)::value + 4) % 6;  // 4, 5, 0, 1, 2, 3
-        const float* scr = (const float*)(smem + wave * WAVE_LDS + (grp == 5 ? 32 * WN * 4 : 0));
-        if constexpr (grp < 4) {
+    const bool specialised = asm_plain_dispatch(__builtin_amdgcn_readfirstlane(asm_plain_variant(ep)), [&](auto act_c, auto outs_c) {
+        const auto st = asm_row_store<WN, decltype(act_c)::value, decltype(outs_c)::value, true>(ep.out_bf16, ep.ld_bf16, ep.out_f32, ep.ld_f32, lane,
+                                                                                                 m0 + wr * WM, gn, bias);
+        static_for<0, 6>([&](auto ord_c) {
+            constexpr int grp = (decltype(ord_c)::value + 4) % 6;  // 4, 5, 0, 1, 2, 3
+            const float* scr = (const float*)(smem + wave * WAVE_LDS + (grp == 5 ? 32 * WN * 4 : 0));
+            if constexpr (grp < 4) {
 #include "gemm_tall_384x256_dump.inc"
-        }
-        asm_store_group<WN>(scr, lane, m0 + wr * WM + grp * 32, gn, bias, AsmPlainStore<false>{ep});
+            }
+            ASM_EPI_STAMP(1 + 2 * decltype(ord_c)::value);
+            asm_store_rows<WN>(scr, lane, st.after(grp * AsmGroup<WN>::NITG));
+            ASM_EPI_STAMP(2 + 2 * decltype(ord_c)::value);
+        });
     });
+    if (!specialised)
+        static_for<0, 6>([&](auto ord_c) {
+            constexpr int grp = (decltype(ord_c)::value + 4) % 6;  // 4, 5, 0, 1, 2, 3
+            const float* scr = (const float*)(smem + wave * WAVE_LDS + (grp == 5 ? 32 * WN * 4 : 0));
+            if constexpr (grp < 4) {
+#include "gemm_tall_384x256_dump.inc"
+            }
+            ASM_EPI_STAMP(1 + 2 * decltype(ord_c)::value);
+            asm_store_group<WN>(scr, lane, m0 + wr * WM + grp * 32, gn, bias, AsmPlainStore<false>{ep});
+            ASM_EPI_STAMP(2 + 2 * decltype(ord_c)::value);
+        });
+    ASM_EPI_STAMPS_FLUSH(13);
 }
 
 }  // namespace

@@ -49,5 +49,14 @@ int main() {
     for (int w = 0; w < 4; ++w)
         printf("  %d  | %12llu %16llu %10llu %18llu %18llu %10llu %18llu          | %llu\n", w, st[w][1] - st[w][0], st[w][2] - st[w][1], st[w][3] - st[w][2],
                st[w][4] - st[w][3], st[w][5] - st[w][4], st[w][6] - st[w][5], st[w][7] - st[w][6], st[w][7] - st[w][0]);
+    // the epilogue of the same launch (bias-free bf16 store): ASM_EPI_STAMP points of gemm_asm_tiles.inc
+    unsigned long long ep[5][16];
+    (void)hipMemcpyFromSymbol(ep, HIP_SYMBOL(g_gemm_epi_stamps), sizeof(ep));
+    printf("epilogue, cycles from the barrier behind the stream: [dump done | last store issued] x 3 groups, final vmcnt(0)\n");
+    for (int w = 0; w < 4; ++w) {
+        printf("  %d  |", w);
+        for (int i = 1; i <= 7; ++i) printf(" %6llu%s", ep[w][i] - ep[w][0], (i & 1) ? "" : " |");
+        printf("\n");
+    }
     return 0;
 }

@@ -88,5 +88,18 @@ int main() {
     const double cyc = (double)(st[0][7] - st[0][0]);
     printf("wave 0: %.0f cycles per K-tile, MFMA duty %.1f %% (192 MFMAs x 16 issue cycles = 3072), clock in the loop %.0f MHz (%.3f us per K-tile)\n", cyc,
            100.0 * 3072 / cyc, tile_us > 0 ? cyc / tile_us : 0.0, tile_us);
+    // the epilogue of the same launch (GELU-tanh -> bf16, the FFN-up form): ASM_EPI_STAMP points of gemm_asm_tiles.inc
+    unsigned long long ep[5][16];
+    (void)hipMemcpyFromSymbol(ep, HIP_SYMBOL(g_gemm_epi_stamps), sizeof(ep));
+    printf("epilogue, cycles from the stream's exit; groups in store order 4 5 0 1 2 3: [dump done | last store issued] x 6, final vmcnt(0)\n");
+    for (int w = 0; w < 4; ++w) {
+        printf("  %d  |", w);
+        for (int i = 1; i <= 13; ++i) printf(" %6llu%s", ep[w][i] - ep[w][0], (i & 1) ? "" : " |");
+        printf("\n");
+    }
+    double dump = 0, store = 0;
+    for (int i = 0; i < 6; ++i) { dump += (double)(ep[0][1 + 2 * i] - ep[0][2 * i]); store += (double)(ep[0][2 + 2 * i] - ep[0][1 + 2 * i]); }
+    printf("wave 0: dumps %.0f cycles, reads + arithmetic + store issue %.0f, drain %.0f, epilogue %.0f\n", dump, store, (double)(ep[0][13] - ep[0][12]),
+           (double)(ep[0][13] - ep[0][0]));
     return 0;
 }
