@@ -203,7 +203,10 @@ int ltx_op_gemm_bf16_gated_residual_norm(ltx_ctx* ctx, const uint16_t* A, long l
             launch_gemm_bf16(g, ctx->stream, &na);
         } else {
             launch_gemm_bf16(g, ctx->stream);
-            launch_norm_mod(x, ldx, scale, shift, 0, M, xn, ldxn, M, N, LTX_NORM_RMS, eps, 0, ctx->stream);
+            NormModArgs n;
+            n.x = x; n.ldx = ldx; n.scale = scale; n.shift = shift; n.rows_per_batch = M;
+            n.out = xn; n.ldo = ldxn; n.rows = M; n.D = N; n.eps = eps;
+            launch_norm_mod(n, ctx->stream);
         }
     });
 }
@@ -348,25 +351,39 @@ int ltx_attention_key_splits(int B, int H, int Tq, int Tk) {
 int ltx_op_norm_mod(ltx_ctx* ctx, const float* x, const float* scale, const float* shift, int rows, int D,
                     int norm_kind, float eps, int round_norm_bf16, uint16_t* out) {
     return with_ctx(ctx, [&] {
-        launch_norm_mod(x, D, scale, shift, 0, rows, out, D, rows, D, norm_kind, eps, round_norm_bf16, ctx->stream);
+        NormModArgs n;
+        n.x = x; n.ldx = D; n.scale = scale; n.shift = shift; n.rows_per_batch = rows;
+        n.out = out; n.ldo = D; n.rows = rows; n.D = D;
+        n.norm_kind = norm_kind; n.eps = eps; n.round_norm_bf16 = round_norm_bf16;
+        launch_norm_mod(n, ctx->stream);
     });
 }
 
 int ltx_op_qknorm_rope(ltx_ctx* ctx, const float* x, long ldx, const float* w, const float* cos_t, const float* sin_t,
                        int T, int rows, int D, float eps, uint16_t* out) {
-    return with_ctx(ctx, [&] { launch_qknorm_rope(x, ldx, w, cos_t, sin_t, T, out, D, rows, D, eps, ctx->stream); });
+    return ltx_op_qknorm_rope_hd(ctx, x, ldx, w, cos_t, sin_t, T, rows, D, 128, 1.0f, eps, out);
 }
 
 int ltx_op_qknorm_rope_hd(ltx_ctx* ctx, const float* x, long ldx, const float* w, const float* cos_t, const float* sin_t, int T, int rows,
                           int D, int head_dim, float out_scale, float eps, uint16_t* out) {
-    return with_ctx(ctx, [&] { launch_qknorm_rope(x, ldx, w, cos_t, sin_t, T, out, D, rows, D, eps, ctx->stream, out_scale, false, head_dim); });
+    return with_ctx(ctx, [&] {
+        QkNormRopeArgs n;
+        n.job[0].x = x; n.job[0].w = w; n.job[0].out = out; n.job[0].out_scale = out_scale;
+        n.ldx = ldx; n.ldo = D; n.cos = cos_t; n.sin = sin_t;
+        n.T = T; n.rows = rows; n.D = D; n.eps = eps; n.head_dim = head_dim;
+        launch_qknorm_rope(n, ctx->stream);
+    });
 }
 
 int ltx_op_norm_mod_ex(ltx_ctx* ctx, const float* x, long ldx, const float* scale, const float* shift, long mod_bstride,
                        int rows_per_batch, const int32_t* row_map, int rows, int D, int norm_kind, float eps,
                        int round_norm_bf16, uint16_t* out, long ldo) {
     return with_ctx(ctx, [&] {
-        launch_norm_mod(x, ldx, scale, shift, mod_bstride, rows_per_batch, out, ldo, rows, D, norm_kind, eps, round_norm_bf16, ctx->stream, row_map);
+        NormModArgs n;
+        n.x = x; n.ldx = ldx; n.scale = scale; n.shift = shift; n.mod_bstride = mod_bstride; n.rows_per_batch = rows_per_batch;
+        n.row_map = row_map; n.out = out; n.ldo = ldo; n.rows = rows; n.D = D;
+        n.norm_kind = norm_kind; n.eps = eps; n.round_norm_bf16 = round_norm_bf16;
+        launch_norm_mod(n, ctx->stream);
     });
 }
 
@@ -404,8 +421,12 @@ int ltx_op_qknorm_rope_pair(ltx_ctx* ctx, const void* x0, const float* w0, uint1
                             uint16_t* out1, long ldx, long ldo, const float* cos_t, const float* sin_t, int T, int rows, int D,
                             float eps, float out_scale0, int x_bf16) {
     return with_ctx(ctx, [&] {
-        launch_qknorm_rope2((const float*)x0, w0, out0, (const float*)x1, w1, out1, ldx, ldo, cos_t, sin_t, T, rows, D, eps, ctx->stream,
-                            out_scale0, x_bf16 != 0);
+        QkNormRopeArgs n;
+        n.job[0].x = x0; n.job[0].w = w0; n.job[0].out = out0; n.job[0].out_scale = out_scale0;
+        n.job[1].x = x1; n.job[1].w = w1; n.job[1].out = out1;
+        n.ldx = ldx; n.ldo = ldo; n.cos = cos_t; n.sin = sin_t;
+        n.T = T; n.rows = rows; n.D = D; n.eps = eps; n.x_bf16 = x_bf16 != 0;
+        launch_qknorm_rope(n, ctx->stream);
     });
 }
 

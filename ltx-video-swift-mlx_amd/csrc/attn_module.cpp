@@ -174,9 +174,16 @@ void attn_module_forward(ltx_ctx* ctx, AttnModule* m, const AttnModuleArgs& a) {
     for (int b = 0; b < B; ++b) gemm_vt(cb + (size_t)b * Tk * Dc, Dc, Tk, m->v, vt + (size_t)b * I * Tpad, Tpad, st);
 
     // q and k come from different inputs, token counts and tables: two one-job launches
-    launch_qknorm_rope(qraw, I, m->qn, a.q_cos, a.q_sin, Tq, q, I, (int)qrows, I, m->eps, st, kAttnQueryPrescale64, false, 64);
-    launch_qknorm_rope(kraw, I, m->kn, a.q_cos ? (a.k_cos ? a.k_cos : a.q_cos) : nullptr, a.q_cos ? (a.k_cos ? a.k_sin : a.q_sin) : nullptr, Tk, k,
-                       I, (int)krows, I, m->eps, st, 1.0f, kb, 64);
+    QkNormRopeArgs n;
+    n.job[0].x = qraw; n.job[0].w = m->qn; n.job[0].out = q; n.job[0].out_scale = kAttnQueryPrescale64;
+    n.ldx = n.ldo = I;
+    n.cos = a.q_cos; n.sin = a.q_sin;
+    n.T = Tq; n.rows = (int)qrows; n.D = I; n.eps = m->eps; n.head_dim = 64;
+    launch_qknorm_rope(n, st);
+    n.job[0].x = kraw; n.job[0].w = m->kn; n.job[0].out = k; n.job[0].out_scale = 1.0f;
+    n.cos = a.q_cos ? (a.k_cos ? a.k_cos : a.q_cos) : nullptr; n.sin = a.q_cos ? (a.k_cos ? a.k_sin : a.q_sin) : nullptr;
+    n.T = Tk; n.rows = (int)krows; n.x_bf16 = kb;
+    launch_qknorm_rope(n, st);
 
     AttnArgs at;
     at.head_dim = 64;
@@ -225,7 +232,12 @@ void launch_k_gemm(AttnModule* m, const bf16_t* cb, bool kb, long krows, float* 
     gemm_linear(cb, m->Dc, m->k, (int)krows, ek, st, sk);
 }
 void launch_k_norm(AttnModule* m, const float* kraw, const float* kc, const float* ks, int Tk, bf16_t* k, long krows, bool kb, hipStream_t st) {
-    launch_qknorm_rope(kraw, m->inner, m->kn, kc, ks, Tk, k, m->inner, (int)krows, m->inner, m->eps, st, 1.0f, kb, m->head_dim);
+    QkNormRopeArgs n;
+    n.job[0].x = kraw; n.job[0].w = m->kn; n.job[0].out = k;
+    n.ldx = n.ldo = m->inner;
+    n.cos = kc; n.sin = ks;
+    n.T = Tk; n.rows = (int)krows; n.D = m->inner; n.eps = m->eps; n.x_bf16 = kb; n.head_dim = m->head_dim;
+    launch_qknorm_rope(n, st);
 }
 void launch_vt(AttnModule* m, const bf16_t* cb, int B, int Tk, int Tpad, bf16_t* vt, hipStream_t st, const SplitWs& sk) {
     for (int b = 0; b < B; ++b) gemm_vt(cb + (size_t)b * Tk * m->Dc, m->Dc, Tk, m->v, vt + (size_t)b * m->inner * Tpad, Tpad, st, sk);
@@ -271,6 +283,11 @@ void attn_module_core(ltx_ctx* ctx, AttnModule* m, const AttnCoreArgs& a, AttnCo
     const float* kc = a.q_cos ? (a.k_cos ? a.k_cos : a.q_cos) : nullptr;
     const float* ks = a.q_cos ? (a.k_cos ? a.k_sin : a.q_sin) : nullptr;
 
+    QkNormRopeArgs qn;  // the query's pass; q | k of the same rows: k rides as a second job
+    qn.job[0].x = qraw; qn.job[0].w = m->qn; qn.job[0].out = q; qn.job[0].out_scale = qscale;
+    qn.ldx = qn.ldo = I;
+    qn.cos = a.q_cos; qn.sin = a.q_sin;
+    qn.T = Tq; qn.rows = (int)qrows; qn.D = I; qn.eps = m->eps; qn.head_dim = hd;
     if (m->fused_qk && !a.ctx) {
         // q | k of the same rows: one GEMM over the [2 inner][Dq] matrix, one norm + RoPE launch with two jobs
         LinearW qk = m->q;
@@ -279,8 +296,9 @@ void attn_module_core(ltx_ctx* ctx, AttnModule* m, const AttnCoreArgs& a, AttnCo
         e.out_f32 = qraw;
         e.ld_f32 = 2 * I;
         gemm_linear(a.xq, Dq, qk, (int)qrows, e, st, sk);
-        launch_qknorm_rope2(qraw, m->qn, q, qraw + I, m->kn, ws->k.as<bf16_t>(), 2 * I, I, a.q_cos, a.q_sin, Tq, (int)qrows, I, m->eps, st, qscale,
-                            false, hd);
+        qn.job[1].x = qraw + I; qn.job[1].w = m->kn; qn.job[1].out = ws->k.as<bf16_t>();
+        qn.ldx = 2 * I;
+        launch_qknorm_rope(qn, st);
     } else {
         GemmEpilogue eq;
         eq.out_f32 = qraw;
@@ -288,7 +306,7 @@ void attn_module_core(ltx_ctx* ctx, AttnModule* m, const AttnCoreArgs& a, AttnCo
         gemm_linear(a.xq, Dq, m->q, (int)qrows, eq, st, sk);
         if (!cached) launch_k_gemm(m, cb, kb, krows, kraw, st, sk);
         // q and k come from different inputs, token counts and tables: two one-job launches
-        launch_qknorm_rope(qraw, I, m->qn, a.q_cos, a.q_sin, Tq, q, I, (int)qrows, I, m->eps, st, qscale, false, hd);
+        launch_qknorm_rope(qn, st);
         if (!cached) launch_k_norm(m, kraw, kc, ks, Tk, ws->k.as<bf16_t>(), krows, kb, st);
     }
     if (!cached) launch_vt(m, cb, B, Tk, Tpad, vs->buf.as<bf16_t>(), st, sk);

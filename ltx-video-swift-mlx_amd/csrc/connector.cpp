@@ -132,15 +132,25 @@ void connector_encode(ltx_ctx* ctx, ConnectorModel* m, const ConnectorArgs& a) {
     launch_register_gather(enc, m->registers, m->ws_src.as<int32_t>(), B, T, D, c.registers, x, st);
     if (a.dbg_reg) HIP_CHECK(hipMemcpyAsync(a.dbg_reg, x, (size_t)rows * D * 4, hipMemcpyDeviceToDevice, st));
 
+    NormModArgs nm;  // the plain RMS norms of the stream, x -> xn (the last one -> a.out)
+    nm.x = x; nm.ldx = D; nm.rows_per_batch = T;
+    nm.out = xn; nm.ldo = D;
+    nm.rows = (int)rows; nm.D = D; nm.eps = c.eps;
+    QkNormRopeArgs qkn;  // q and k of the fused projection, two jobs
+    qkn.job[0].x = qk; qkn.job[0].out = q;
+    qkn.job[1].x = qk + D; qkn.job[1].out = k;
+    qkn.ldx = 2 * D; qkn.ldo = D;
+    qkn.cos = m->rope_cos.as<float>(); qkn.sin = m->rope_sin.as<float>();
+    qkn.T = T; qkn.rows = (int)rows; qkn.D = D; qkn.eps = c.eps;
     for (int l = 0; l < c.layers; ++l) {
         const ConnBlock& blk = m->blocks[l];
-        launch_norm_mod(x, D, nullptr, nullptr, 0, T, xn, D, (int)rows, D, LTX_NORM_RMS, c.eps, 0, st);
+        launch_norm_mod(nm, st);
         GemmEpilogue eqk;
         eqk.out_f32 = qk;
         eqk.ld_f32 = 2 * D;
         gemm_linear(xn, D, blk.qk, (int)rows, eqk, st);
-        launch_qknorm_rope2(qk, blk.qn, q, qk + D, blk.kn, k, 2 * D, D, m->rope_cos.as<float>(), m->rope_sin.as<float>(), T, (int)rows, D,
-                            c.eps, st);
+        qkn.job[0].w = blk.qn; qkn.job[1].w = blk.kn;
+        launch_qknorm_rope(qkn, st);
         for (int b = 0; b < B; ++b) gemm_vt(xn + (size_t)b * T * D, D, T, blk.v, vt + (size_t)b * D * Tpad, Tpad, st);
         AttnArgs at;
         at.Q = q; at.ldq = D; at.q_bstride = (long)T * D;
@@ -155,7 +165,7 @@ void connector_encode(ltx_ctx* ctx, ConnectorModel* m, const ConnectorArgs& a) {
         eo.resid = 1;
         eo.gate_scalar = 1.0f;
         gemm_linear(ao, D, blk.o, (int)rows, eo, st);
-        launch_norm_mod(x, D, nullptr, nullptr, 0, T, xn, D, (int)rows, D, LTX_NORM_RMS, c.eps, 0, st);
+        launch_norm_mod(nm, st);
         GemmEpilogue e1;
         e1.out_bf16 = ffh;
         e1.ld_bf16 = 4 * D;
@@ -168,7 +178,8 @@ void connector_encode(ltx_ctx* ctx, ConnectorModel* m, const ConnectorArgs& a) {
         e2.gate_scalar = 1.0f;
         gemm_linear(ffh, 4 * D, blk.ff2, (int)rows, e2, st);
     }
-    launch_norm_mod(x, D, nullptr, nullptr, 0, T, a.out, D, (int)rows, D, LTX_NORM_RMS, c.eps, 0, st);
+    nm.out = a.out;
+    launch_norm_mod(nm, st);
     // after the register replacement every position is valid: the mask the loop receives is all ones (:466-468, :622-626)
     if (a.out_mask) launch_fill_const_i32(a.out_mask, rows, 1, st);
 }

@@ -200,8 +200,11 @@ DiTModel::CtxCache* prepare_context(ltx_ctx* ctx, DiTModel* m, const DiTForwardA
         ek.ld_f32 = D;
         ek.round_bf16 = 1;  // the reference's K projection runs bf16 x bf16 -> bf16 (SURVEY R5/R11 dtype notes)
         gemm_linear(c->proj.as<bf16_t>(), D, blk.k2, (int)rows, ek, st, sk);
-        launch_qknorm_rope(m->ctx_tmp_kraw.as<float>(), D, blk.kn2, nullptr, nullptr, S,
-                           c->k.as<bf16_t>() + (size_t)l * rows * D, D, (int)rows, D, m->cfg.norm_eps, st);
+        QkNormRopeArgs kn;  // one job, no RoPE
+        kn.job[0].x = m->ctx_tmp_kraw.as<float>(); kn.job[0].w = blk.kn2; kn.job[0].out = c->k.as<bf16_t>() + (size_t)l * rows * D;
+        kn.ldx = kn.ldo = D;
+        kn.T = S; kn.rows = (int)rows; kn.D = D; kn.eps = m->cfg.norm_eps;
+        launch_qknorm_rope(kn, st);
         for (int b = 0; b < B; ++b)
             gemm_vt(c->proj.as<bf16_t>() + (size_t)b * S * D, D, S, blk.v2,
                     c->vt.as<bf16_t>() + ((size_t)l * B + b) * D * Spad, Spad, st, sk);
@@ -335,11 +338,28 @@ void dit_forward(ltx_ctx* ctx, DiTModel* m, const DiTForwardArgs& a) {
     const bool qk_bf16 = ltx_opt(OPT_QK_F32) == 0;  // the q|k and cross-q stores (comment above dit_forward)
     const bool sp_overlap_on = ltx_opt(OPT_SP_OVERLAP) != 0;
     bool xn_ready = false;  // the previous block's last GEMM launch already wrote this block's first adaLN rows (NormAfter)
+    // the adaLN passes of the forward, x -> xn: every launch sets its scale / shift rows (and what else differs) and leaves the rest
+    NormModArgs nm;
+    nm.x = x; nm.ldx = D;
+    nm.mod_bstride = mod_bs; nm.rows_per_batch = T; nm.row_map = rmap;
+    nm.out = xn; nm.ldo = D;
+    nm.rows = (int)rows; nm.D = D; nm.eps = eps;
+    // the q/k norm + RoPE passes: q|k of the self-attention as two jobs, the cross-attention query as one
+    QkNormRopeArgs qkn;
+    qkn.job[0].out = q; qkn.job[0].out_scale = kAttnQueryPrescale;
+    qkn.ldo = D;
+    qkn.T = T; qkn.rows = (int)rows; qkn.D = D; qkn.eps = eps;
+    qkn.x_bf16 = qk_bf16;
     for (int l = 0; l < L; ++l) {
         const DiTBlock& blk = m->blocks[l];
         const float* ml = mod + (long)l * 6 * D;  // rows: 0 shift_msa 1 scale_msa 2 gate_msa 3 shift_mlp 4 scale_mlp 5 gate_mlp
         if (!blk.skip_attn) {
-            if (!xn_ready) launch_norm_mod(x, D, ml + 1 * D, ml + 0 * D, mod_bs, T, xn, D, (int)rows, D, LTX_NORM_RMS, eps, l == 0 ? 1 : 0, st, rmap);
+            if (!xn_ready) {
+                nm.scale = ml + 1 * D; nm.shift = ml + 0 * D;
+                nm.round_norm_bf16 = l == 0 ? 1 : 0;
+                launch_norm_mod(nm, st);
+                nm.round_norm_bf16 = 0;
+            }
             xn_ready = false;
             // Sequence parallelism on the native transport: the V^T gather (and its interleave) runs on the side stream under
             // the q|k projection and its norm + RoPE pass; only the K gather stays on the critical path. Same kernels, same
@@ -375,9 +395,11 @@ void dit_forward(ltx_ctx* ctx, DiTModel* m, const DiTForwardArgs& a) {
             } else {
                 gemm_linear(xn, D, blk.qk1, (int)rows, eqk, st, sk);
             }
-            if (qkb) launch_qknorm_rope2(qk, blk.qn1, q, (const float*)((const bf16_t*)qk + D), blk.kn1, k, 2 * D, D, rope_c, rope_s, T, (int)rows, D, eps, st, kAttnQueryPrescale, true);
-            else
-            launch_qknorm_rope2(qk, blk.qn1, q, qk + D, blk.kn1, k, 2 * D, D, rope_c, rope_s, T, (int)rows, D, eps, st, kAttnQueryPrescale);
+            qkn.job[0].x = qk; qkn.job[0].w = blk.qn1;
+            qkn.job[1].x = qkb ? (const void*)((const bf16_t*)qk + D) : (const void*)(qk + D); qkn.job[1].w = blk.kn1; qkn.job[1].out = k;
+            qkn.ldx = 2 * D;
+            qkn.cos = rope_c; qkn.sin = rope_s;
+            launch_qknorm_rope(qkn, st);
             AttnArgs at;
             if (!sp) {
                 if (!qkv_fused) {  // (the fused launch wrote every batch element's V^T slab)
@@ -433,7 +455,11 @@ void dit_forward(ltx_ctx* ctx, DiTModel* m, const DiTForwardArgs& a) {
                 eq.ld_bf16 = D;
             }
             gemm_linear(xb, D, blk.q2, (int)rows, eq, st, sk);
-            launch_qknorm_rope(qc, D, blk.qn2, nullptr, nullptr, T, q, D, (int)rows, D, eps, st, kAttnQueryPrescale, q2b);
+            qkn.job[0].x = qc; qkn.job[0].w = blk.qn2;
+            qkn.job[1] = {};
+            qkn.ldx = D;
+            qkn.cos = qkn.sin = nullptr;
+            launch_qknorm_rope(qkn, st);
             AttnArgs at;
             at.Q = q; at.ldq = D; at.q_bstride = (long)T * D;
             at.K = cc->k.as<bf16_t>() + (size_t)l * B * S * D; at.ldk = D; at.k_bstride = (long)S * D;
@@ -454,7 +480,8 @@ void dit_forward(ltx_ctx* ctx, DiTModel* m, const DiTForwardArgs& a) {
             gemm_linear(ao, D, blk.o2, (int)rows, eo, st, sk);
         }
         if (!blk.skip_ff) {
-            launch_norm_mod(x, D, ml + 4 * D, ml + 3 * D, mod_bs, T, xn, D, (int)rows, D, LTX_NORM_RMS, eps, 0, st, rmap);
+            nm.scale = ml + 4 * D; nm.shift = ml + 3 * D;
+            launch_norm_mod(nm, st);
             GemmEpilogue e1;
             e1.out_bf16 = ffh;
             e1.ld_bf16 = 4 * D;
@@ -493,7 +520,10 @@ void dit_forward(ltx_ctx* ctx, DiTModel* m, const DiTForwardArgs& a) {
     // 6. output head: LayerNorm (no affine) * (1+scale) + shift -> proj_out (LTXTransformer.swift:208-224)
     {
         const float* mo = m->ws_modout.as<float>();
-        launch_norm_mod(x, D, mo + D, mo, 2L * D, T, xn, D, (int)rows, D, LTX_NORM_LAYER, eps, 0, st, rmap);
+        nm.scale = mo + D; nm.shift = mo;
+        nm.mod_bstride = 2L * D;
+        nm.norm_kind = LTX_NORM_LAYER;
+        launch_norm_mod(nm, st);
         GemmEpilogue e;
         e.out_f32 = a.velocity;
         e.ld_f32 = m->cfg.out_channels;

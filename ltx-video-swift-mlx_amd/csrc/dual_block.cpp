@@ -168,7 +168,12 @@ void ensure_rope(ltx_ctx* ctx, DualStack* m, int F, int H, int W, int Ta) {
 // adaLN / FFN phase of one stream (phases 7 and 8): x += gate * ff2(gelu(ff1(norm(x) * (1 + scale) + shift)))
 void ffn_phase(float* x, int D, int T, long rows, const float* mod, long mod_bs, const LinearW& ff1, const LinearW& ff2, bf16_t* xn, bf16_t* ffh,
                float eps, const SplitWs& sk, hipStream_t st) {
-    launch_norm_mod(x, D, mod + 4L * D, mod + 3L * D, mod_bs, T, xn, D, (int)rows, D, LTX_NORM_RMS, eps, 0, st);
+    NormModArgs n;
+    n.x = x; n.ldx = D;
+    n.scale = mod + 4L * D; n.shift = mod + 3L * D; n.mod_bstride = mod_bs; n.rows_per_batch = T;
+    n.out = xn; n.ldo = D;
+    n.rows = (int)rows; n.D = D; n.eps = eps;
+    launch_norm_mod(n, st);
     GemmEpilogue e1;
     e1.out_bf16 = ffh;
     e1.ld_bf16 = 4L * D;
@@ -306,6 +311,15 @@ void dual_forward(ltx_ctx* ctx, DualStack* m, const DualForwardArgs& a) {
     const float* cac = m->rope_ca_cos.as<float>();
     const float* cas = m->rope_ca_sin.as<float>();
 
+    // the RMS norm (+ modulation) passes of the two streams: a launch sets its scale / shift rows, their batch stride and its output
+    NormModArgs nv, na;
+    nv.x = xv; nv.ldx = nv.ldo = Dv; nv.rows_per_batch = Tv; nv.rows = (int)vrows; nv.D = Dv; nv.eps = eps;
+    na.x = xa; na.ldx = na.ldo = Da; na.rows_per_batch = Ta; na.rows = (int)arows; na.D = Da; na.eps = eps;
+    auto norm = [st](NormModArgs n, const float* scale, const float* shift, long mod_bs, bf16_t* out) {
+        n.scale = scale; n.shift = shift; n.mod_bstride = mod_bs; n.out = out;
+        launch_norm_mod(n, st);
+    };
+
     for (int l = 0; l < L; ++l) {
         DualBlock& b = m->blocks[l];
         const TextCacheSlices tcs = tc ? text_cache_slices(*tc, l, Dv, Da) : TextCacheSlices{nullptr, nullptr, nullptr, nullptr};
@@ -314,19 +328,19 @@ void dual_forward(ltx_ctx* ctx, DualStack* m, const DualForwardArgs& a) {
         const float* cv = m->mod_ca_v.as<float>() + (long)l * 5 * Dv;  // rows: 0 a2v scale 1 a2v shift 2 v2a scale 3 v2a shift 4 gate
         const float* ca = m->mod_ca_a.as<float>() + (long)l * 5 * Da;
         if (on(1)) {  // video self-attention
-            launch_norm_mod(xv, Dv, mv + 1L * Dv, mv, mv_bs, Tv, vn, Dv, (int)vrows, Dv, LTX_NORM_RMS, eps, 0, st);
+            norm(nv, mv + 1L * Dv, mv, mv_bs, vn);
             core(b.attn1, &m->vt[0], vn, nullptr, 0, Tv, Tv, rvc, rvs, nullptr, nullptr, nullptr, xv, mv + 2L * Dv, mv_bs);
         }
         if (on(2)) {  // audio self-attention
-            launch_norm_mod(xa, Da, ma + 1L * Da, ma, ma_bs, Ta, an, Da, (int)arows, Da, LTX_NORM_RMS, eps, 0, st);
+            norm(na, ma + 1L * Da, ma, ma_bs, an);
             core(b.audio_attn1, &m->vt[1], an, nullptr, 0, Ta, Ta, rac, ras, nullptr, nullptr, nullptr, xa, ma + 2L * Da, ma_bs);
         }
         if (on(3)) {  // video text cross-attention on norm2(x_v)
-            launch_norm_mod(xv, Dv, nullptr, nullptr, 0, Tv, vn, Dv, (int)vrows, Dv, LTX_NORM_RMS, eps, 0, st);
+            norm(nv, nullptr, nullptr, 0, vn);
             core(b.attn2, &m->vt[2], vn, a.ctx_video, 1, Tv, S, nullptr, nullptr, nullptr, nullptr, bias_v, xv, nullptr, 0, tcs.k_v, tcs.vt_v);
         }
         if (on(4)) {  // audio text cross-attention on audio_norm2(x_a)
-            launch_norm_mod(xa, Da, nullptr, nullptr, 0, Ta, an, Da, (int)arows, Da, LTX_NORM_RMS, eps, 0, st);
+            norm(na, nullptr, nullptr, 0, an);
             core(b.audio_attn2, &m->vt[3], an, a.ctx_audio, 1, Ta, S, nullptr, nullptr, nullptr, nullptr, bias_a, xa, nullptr, 0, tcs.k_a, tcs.vt_a);
         }
         if (on(5) || on(6)) {
@@ -339,10 +353,10 @@ void dual_forward(ltx_ctx* ctx, DualStack* m, const DualForwardArgs& a) {
                 ja.mod_bstride = ca_bs; ja.rows_per_batch = Ta; ja.out0 = an; ja.out1 = an2; ja.ldo = Da; ja.rows = (int)arows; ja.D = Da;
                 launch_norm_mod2(jv, ja, eps, st);
             } else {
-                launch_norm_mod(xv, Dv, cv, cv + 1L * Dv, cv_bs, Tv, vn, Dv, (int)vrows, Dv, LTX_NORM_RMS, eps, 0, st);
-                launch_norm_mod(xv, Dv, cv + 2L * Dv, cv + 3L * Dv, cv_bs, Tv, vn2, Dv, (int)vrows, Dv, LTX_NORM_RMS, eps, 0, st);
-                launch_norm_mod(xa, Da, ca, ca + 1L * Da, ca_bs, Ta, an, Da, (int)arows, Da, LTX_NORM_RMS, eps, 0, st);
-                launch_norm_mod(xa, Da, ca + 2L * Da, ca + 3L * Da, ca_bs, Ta, an2, Da, (int)arows, Da, LTX_NORM_RMS, eps, 0, st);
+                norm(nv, cv, cv + 1L * Dv, cv_bs, vn);
+                norm(nv, cv + 2L * Dv, cv + 3L * Dv, cv_bs, vn2);
+                norm(na, ca, ca + 1L * Da, ca_bs, an);
+                norm(na, ca + 2L * Da, ca + 3L * Da, ca_bs, an2);
             }
             if (on(5)) core(b.a2v, &m->vt[4], vn, an, 0, Tv, Ta, cvc, cvs, cac, cas, nullptr, xv, cv + 4L * Dv, cv_bs);
             if (on(6)) core(b.v2a, &m->vt[5], an2, vn2, 0, Ta, Tv, cac, cas, cvc, cvs, nullptr, xa, ca + 4L * Da, ca_bs);

@@ -267,7 +267,12 @@ void dual_model_forward(ltx_ctx* ctx, DualModel* m, const DualModelForwardArgs& 
     // rows as its "layers" and one row per batch element
     auto head = [&](const float* x, int D, int T, long rows, const float* table, const float* embts, float* mod, const LinearW& proj, float* out) {
         launch_make_mod(table, embts, mod, B, 2, 1, D, st);
-        launch_norm_mod(x, D, mod + D, mod, 2L * D, T, m->ws_xn.as<bf16_t>(), D, (int)rows, D, LTX_NORM_LAYER, eps, 0, st);
+        NormModArgs n;
+        n.x = x; n.ldx = D;
+        n.scale = mod + D; n.shift = mod; n.mod_bstride = 2L * D; n.rows_per_batch = T;
+        n.out = m->ws_xn.as<bf16_t>(); n.ldo = D;
+        n.rows = (int)rows; n.D = D; n.norm_kind = LTX_NORM_LAYER; n.eps = eps;
+        launch_norm_mod(n, st);
         GemmEpilogue e;
         e.out_f32 = out;
         e.ld_f32 = proj.out;

@@ -8,12 +8,24 @@ enum { LTX_NORM_RMS = 0, LTX_NORM_LAYER = 1 };
 
 // y = norm(x) * (1 + scale[b]) + shift[b]  -> bf16            (adaLN: LTXTransformerBlock.swift:72-83;
 //                                                              final head: LTXTransformer.swift:208-224)
-// x: f32 [rows][D]; scale/shift: f32 [B][mod_bstride] rows (b = row / rows_per_batch), nullable (plain norm).
-// round_norm_bf16: round norm(x) to bf16 before the modulation (block 0 sees a bf16 residual stream in the
-// reference, so MLXFast.rmsNorm returns bf16 there - SURVEY R10 dtype column).
-void launch_norm_mod(const float* x, long ldx, const float* scale, const float* shift, long mod_bstride,
-                     int rows_per_batch, bf16_t* out, long ldo, int rows, int D, int norm_kind, float eps,
-                     int round_norm_bf16, hipStream_t stream, const int32_t* row_map = nullptr);
+struct NormModArgs {
+    const float* x = nullptr;          // [rows][ldx] f32, D valid columns
+    long ldx = 0;
+    const float* scale = nullptr;      // [B][mod_bstride] f32 rows; scale and shift null together: plain norm
+    const float* shift = nullptr;
+    long mod_bstride = 0;
+    int rows_per_batch = 1;            // modulation row b = row / rows_per_batch ...
+    const int32_t* row_map = nullptr;  // ... or row_map[row] (per-token timestep groups: image-to-video)
+    bf16_t* out = nullptr;             // [rows][ldo] bf16
+    long ldo = 0;
+    int rows = 0, D = 0;
+    int norm_kind = LTX_NORM_RMS;
+    float eps = 1e-6f;
+    // round norm(x) to bf16 before the modulation (block 0 sees a bf16 residual stream in the reference, so MLXFast.rmsNorm returns
+    // bf16 there - SURVEY R10 dtype column)
+    int round_norm_bf16 = 0;
+};
+void launch_norm_mod(const NormModArgs& args, hipStream_t stream);
 
 // The cross-modal norms of the dual video + audio block (LTX2TransformerBlock.swift:246-263): audio_to_video_norm(x_v) and
 // video_to_audio_norm(x_a) are each computed ONCE and modulated twice - a2v query / v2a key rows of the video stream, a2v key / v2a
@@ -39,20 +51,30 @@ struct NormMod2Job {
 void launch_norm_mod2(const NormMod2Job& video, const NormMod2Job& audio, float eps, hipStream_t stream);
 
 // q/k RMSNorm across ALL heads with learnable weight, then split-RoPE per head (LTXAttention.swift:179-189,
-// LTXRoPE.swift:84-149). x: f32 [rows][ldx] (D valid columns), w: f32 [D], cos/sin: f32 [T][D/2] indexed by
-// (row % T) with per-head slices of 64 (nullable -> no RoPE, cross-attention). out: bf16 [rows][ldo].
-// head_dim (128, or 64 for the audio / cross-modal attention at 32 heads x 64): head h is columns h*head_dim .., rotated as its two
-// halves with columns h*head_dim/2 .. of the cos/sin row. The cross-modal q and k come from different inputs, token counts and tables:
-// two one-job launches.
-// q and k of a fused projection in ONE launch (job 1 optional: x1 == nullptr)
-void launch_qknorm_rope2(const float* x0, const float* w0, bf16_t* out0, const float* x1, const float* w1, bf16_t* out1,
-                         long ldx, long ldo, const float* cosT, const float* sinT, int T, int rows, int D, float eps,
-                         hipStream_t stream, float out_scale0 = 1.0f, bool x_bf16 = false, int head_dim = 128);
-// out_scale0 / out_scale: multiplier applied to job 0's (the query's) normed + rotated row before its single rounding to bf16. The
-// DiT folds the softmax scale and log2(e) into it (kAttnQueryPrescale), so that the attention kernel's scores arrive as base-2
-// exponents: one rounding of q as before, and 48 multiplies per key tile less in the kernel (AttnArgs::q_prescaled).
-void launch_qknorm_rope(const float* x, long ldx, const float* w, const float* cosT, const float* sinT, int T,
-                        bf16_t* out, long ldo, int rows, int D, float eps, hipStream_t stream, float out_scale = 1.0f, bool x_bf16 = false, int head_dim = 128);
+// LTXRoPE.swift:84-149). One launch runs one job or two: q and k of a fused projection share strides, tables and rows (job[1].x ==
+// nullptr: a one-job launch). The cross-modal q and k come from different inputs, token counts and tables: two one-job launches.
+struct QkNormRopeArgs {
+    struct Job {
+        const void* x = nullptr;   // [rows][ldx] f32, or bf16 (x_bf16) with ldx counted in bf16 elements; D valid columns
+        const float* w = nullptr;  // [D] f32 norm weight
+        bf16_t* out = nullptr;     // [rows][ldo] bf16
+        // multiplier applied to the normed + rotated row before its single rounding to bf16. The DiT folds the softmax scale and log2(e)
+        // into the query's (kAttnQueryPrescale), so that the attention kernel's scores arrive as base-2 exponents: one rounding of q as
+        // before, and 48 multiplies per key tile less in the kernel (AttnArgs::q_prescaled).
+        float out_scale = 1.0f;
+    };
+    Job job[2];
+    long ldx = 0, ldo = 0;
+    const float* cos = nullptr;  // f32 [T][D/2] indexed by (row % T); both null: no RoPE (cross-attention)
+    const float* sin = nullptr;
+    int T = 1, rows = 0, D = 0;
+    float eps = 1e-6f;
+    bool x_bf16 = false;
+    // 128, or 64 for the audio / cross-modal attention at 32 heads x 64: head h is columns h*head_dim .., rotated as its two halves with
+    // columns h*head_dim/2 .. of the cos/sin row
+    int head_dim = 128;
+};
+void launch_qknorm_rope(const QkNormRopeArgs& args, hipStream_t stream);
 
 // sequence-parallel self-attention: gathered V^T blocks [N][D][Tn] -> one V^T [D][ld] with rank r's keys at columns r*Tn ..
 void launch_sp_vt_interleave(const bf16_t* gathered, bf16_t* vt, int N, int D, int Tn, long ld, hipStream_t stream);

@@ -26,6 +26,31 @@ LTX_DEVFN float block_reduce_sum(float v, float* red) {
     return t;
 }
 
+// The cross-wave half of the multi-row kernels' reductions: K sums (one per row a workgroup holds) share ONE barrier. post_wave_sums
+// takes the K WAVE sums (wave_reduce_sum of each thread's share), lane 0 of every wave posts them, and behind its barrier
+// four_wave_total(red, k) is sum k over the workgroup, the wave sums added in wave order as block_reduce_sum adds them.
+template <int K>
+LTX_DEVFN void post_wave_sums(const float (&wave_sum)[K], float (&red)[4][K]) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < K; ++k) red[w][k] = wave_sum[k];
+    }
+    __syncthreads();
+}
+template <int K>
+LTX_DEVFN float four_wave_total(const float (&red)[4][K], int k) {
+    return red[0][k] + red[1][k] + red[2][k] + red[3][k];
+}
+// adaLN modulation of one normed value, and four results as bf16 at dst (8-byte store): the tail of every norm + modulation kernel
+LTX_DEVFN float modulate(float y, float scale, float shift) { return y * (1.0f + scale) + shift; }
+LTX_DEVFN void store_bf16x4(bf16_t* dst, f32x4 y) {
+    uint2 pk;
+    pk.x = pack_bf16x2(y[0], y[1]);
+    pk.y = pack_bf16x2(y[2], y[3]);
+    *(uint2*)dst = pk;
+}
+
 // one workgroup (256 threads) per row; NV = float4 chunks per thread (D <= NV*1024). The modulation vectors are
 // fetched together with the row, BEFORE the reduction: every workgroup of the launch is resident at once, so the kernel
 // costs one memory latency plus the transfer, and a second dependent load after the barrier doubled it (17 -> ~9 us).
@@ -103,12 +128,9 @@ __global__ __launch_bounds__(256) void norm_mod_kernel(const float* __restrict__
             }
             if (sc) {
 #pragma unroll
-                for (int e = 0; e < 4; ++e) y[e] = y[e] * (1.0f + s4[j][e]) + h4[j][e];
+                for (int e = 0; e < 4; ++e) y[e] = modulate(y[e], s4[j][e], h4[j][e]);
             }
-            uint2 pk;
-            pk.x = pack_bf16x2(y[0], y[1]);
-            pk.y = pack_bf16x2(y[2], y[3]);
-            *(uint2*)(orow + c * 4) = pk;
+            store_bf16x4(orow + c * 4, y);
         }
     }
 }
@@ -149,17 +171,11 @@ __global__ __launch_bounds__(256) void norm_mod_rows_kernel(const float* __restr
             for (int e = 0; e < 4; ++e) a += v[r][j][e] * v[r][j][e];
         ss[r] = wave_reduce_sum(a);
     }
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (lane == 0) {
-#pragma unroll
-        for (int r = 0; r < R; ++r) red[w][r] = ss[r];
-    }
-    __syncthreads();
+    post_wave_sums(ss, red);
 #pragma unroll
     for (int r = 0; r < R; ++r) {
         if (row0 + r >= rows) break;
-        // same summation order as norm_mod_kernel's block_reduce_sum: wave sums added in wave order
-        const float ms = (red[0][r] + red[1][r] + red[2][r] + red[3][r]) / (float)D;
+        const float ms = four_wave_total(red, r) / (float)D;  // norm_mod_kernel's summation order
         const float rstd = rsqrtf(ms + eps);
         bf16_t* orow = out + (long)(row0 + r) * ldo;
 #pragma unroll
@@ -169,12 +185,9 @@ __global__ __launch_bounds__(256) void norm_mod_rows_kernel(const float* __restr
             for (int e = 0; e < 4; ++e) {
                 y[e] = v[r][j][e] * rstd;
                 if (round_norm_bf16) y[e] = bf16_to_f32(f32_to_bf16(y[e]));
-                y[e] = y[e] * (1.0f + s4[j][e]) + h4[j][e];
+                y[e] = modulate(y[e], s4[j][e], h4[j][e]);
             }
-            uint2 pk;
-            pk.x = pack_bf16x2(y[0], y[1]);
-            pk.y = pack_bf16x2(y[2], y[3]);
-            *(uint2*)(orow + (threadIdx.x + j * 256) * 4) = pk;
+            store_bf16x4(orow + (threadIdx.x + j * 256) * 4, y);
         }
     }
 }
@@ -244,26 +257,20 @@ __global__ __launch_bounds__(256) void norm_mod2_kernel(const NormMod2Job j0, co
             }
             if (sc0) {
 #pragma unroll
-                for (int e = 0; e < 4; ++e) ya[e] = y[e] * (1.0f + s0[i][e]) + h0[i][e];
+                for (int e = 0; e < 4; ++e) ya[e] = modulate(y[e], s0[i][e], h0[i][e]);
             }
             if (sc1) {
 #pragma unroll
-                for (int e = 0; e < 4; ++e) yb[e] = y[e] * (1.0f + s1[i][e]) + h1[i][e];
+                for (int e = 0; e < 4; ++e) yb[e] = modulate(y[e], s1[i][e], h1[i][e]);
             }
-            uint2 pa, pb;
-            pa.x = pack_bf16x2(ya[0], ya[1]);
-            pa.y = pack_bf16x2(ya[2], ya[3]);
-            pb.x = pack_bf16x2(yb[0], yb[1]);
-            pb.y = pack_bf16x2(yb[2], yb[3]);
-            *(uint2*)(o0 + c * 4) = pa;
-            *(uint2*)(o1 + c * 4) = pb;
+            store_bf16x4(o0 + c * 4, ya);
+            store_bf16x4(o1 + c * 4, yb);
         }
     }
 }
 
-// one workgroup per row; thread handles float4 chunks of the first half `a` of a head and the matching `b` chunk.
-// blockIdx.y selects the job (q or k of the fused projection): one launch normalises and rotates both. The weight and
-// cos/sin chunks are fetched with the row, before the reduction (same reason as norm_mod_kernel).
+// ---- q/k RMSNorm + split RoPE: the pieces every kernel of the family is built from, then the three kernels ----
+// One job of a launch: q or k of a projection. blockIdx.y (or the pair kernel's own loop) selects it.
 struct QkJob {
     const float* x;
     const float* w;
@@ -271,6 +278,11 @@ struct QkJob {
     long ldx, ldo;
     float out_scale;  // multiplies the normed (and rotated) row before its ONE rounding to bf16 (1 = plain)
 };
+// row `row` of a job's input: the rows are f32, or (XB) bf16 with ldx counted in bf16 elements
+template <bool XB>
+LTX_DEVFN const float* qk_row(const float* x, long ldx, int row) {
+    return XB ? (const float*)((const bf16_t*)x + (long)row * ldx) : x + (long)row * ldx;
+}
 // four consecutive elements of a q / k projection row as f32: the row is f32, or (XB) bf16 at the same element offsets
 template <bool XB>
 LTX_DEVFN f32x4 qk_load4(const float* x_row, int col) {
@@ -282,14 +294,44 @@ LTX_DEVFN f32x4 qk_load4(const float* x_row, int col) {
         return *(const f32x4*)(x_row + col);
     }
 }
-template <int NP, bool XB = false>
+// Pair chunk p (0 .. D/8-1) of a row whose heads are HD wide: head = p / (HD/8), i4 = p % (HD/8). A thread holds four elements `a` of
+// the head's first half, at column head*HD + i4*4 of the row (LTX_QK_COL(HD, p, HD)), and the matching four `b` of its second half, HD/2
+// columns further; both rotate with the cos/sin values at column head*(HD/2) + i4*4 of the table row (LTX_QK_COL(HD, p, HD / 2)): cos/sin
+// rows are [T][D/2], head h uses columns h*HD/2 .. of them. HD = 128 is the DiT; HD = 64 is LTXAttention at 32 x 64, the audio /
+// cross-modal attention of the dual block (halves [0:32] / [32:64] of a head). The norm is across the whole row for either head dim.
+#define LTX_QK_COL(HD, p, head_width) (((p) >> ((HD) == 128 ? 4 : 3)) * (head_width) + ((p) & ((HD) / 8 - 1)) * 4)
+// Split RoPE of one element pair in place, a of a head's first half against b of its second half, on the normed and weighted f32
+// values: the reference rounds the normed q/k to its storage dtype before the f32 rotation only when that dtype is bf16 (cross-modal
+// case); in the DiT q,k are f32 here (LTXRoPE.swift:90-92). Text and not a function, like LTX_QK_COL: a function is simplified on its
+// own before it is inlined, and the kernels then come out with other instruction streams - for this line that can mean another choice
+// of fused multiply-adds, i.e. other bits (tools/compare_isa.py, profiles/row_passes_isa.txt).
+#define LTX_QK_ROTATE(a, b, c, s)               \
+    do {                                        \
+        const float a0 = (a), b0 = (b);         \
+        (a) = a0 * (c) - b0 * (s);              \
+        (b) = b0 * (c) + a0 * (s);              \
+    } while (0)
+// a chunk pair's last steps: the output scale, ONE rounding to bf16, 8-byte stores at `col` and half a head further
+template <int HD>
+LTX_DEVFN void qk_store(bf16_t* orow, int col, f32x4 a, f32x4 b, float osc) {
+    uint2 pa, pb;
+    pa.x = pack_bf16x2(a[0] * osc, a[1] * osc);
+    pa.y = pack_bf16x2(a[2] * osc, a[3] * osc);
+    pb.x = pack_bf16x2(b[0] * osc, b[1] * osc);
+    pb.y = pack_bf16x2(b[2] * osc, b[3] * osc);
+    *(uint2*)(orow + col) = pa;
+    *(uint2*)(orow + col + HD / 2) = pb;
+}
+// one workgroup per row; thread handles float4 chunks of the first half `a` of a head and the matching `b` chunk (LTX_QK_COL).
+// blockIdx.y selects the job (q or k of the fused projection): one launch normalises and rotates both. The weight and
+// cos/sin chunks are fetched with the row, before the reduction (same reason as norm_mod_kernel).
+template <int HD, int NP, bool XB>
 __global__ __launch_bounds__(256) void qknorm_rope_kernel(QkJob j0, QkJob j1, const float* __restrict__ cosT,
                                                           const float* __restrict__ sinT, int T, int D, float eps) {
     __shared__ float red[4];
     const QkJob job = blockIdx.y ? j1 : j0;
     const int row = blockIdx.x;
-    const float* xr = XB ? (const float*)((const bf16_t*)job.x + (long)row * job.ldx) : job.x + (long)row * job.ldx;
-    // pair chunk p (0 .. D/8-1): head = p / 16, i4 = p % 16 ; a at head*128 + i4*4, b at +64
+    const float* xr = qk_row<XB>(job.x, job.ldx, row);
     const int npair = D >> 3;
     const int t = row % T;
     f32x4 va[NP], vb[NP], wa[NP], wb[NP], c4[NP], s4[NP];
@@ -298,21 +340,20 @@ __global__ __launch_bounds__(256) void qknorm_rope_kernel(QkJob j0, QkJob j1, co
         const int p = threadIdx.x + j * 256;
         va[j] = vb[j] = f32x4{0.f, 0.f, 0.f, 0.f};
         if (p < npair) {
-            const int col = (p >> 4) * 128 + (p & 15) * 4;
+            const int col = LTX_QK_COL(HD, p, HD);
             va[j] = qk_load4<XB>(xr, col);
-            vb[j] = qk_load4<XB>(xr, col + 64);
+            vb[j] = qk_load4<XB>(xr, col + HD / 2);
         }
     }
 #pragma unroll
     for (int j = 0; j < NP; ++j) {
         const int p = threadIdx.x + j * 256;
         if (p < npair) {
-            const int col = (p >> 4) * 128 + (p & 15) * 4;
+            const int col = LTX_QK_COL(HD, p, HD);
             wa[j] = *(const f32x4*)(job.w + col);
-            wb[j] = *(const f32x4*)(job.w + col + 64);
+            wb[j] = *(const f32x4*)(job.w + col + HD / 2);
             if (cosT) {
-                // cos/sin rows are [T][D/2]; head h uses columns h*64 .. h*64+63
-                const int fc = (p >> 4) * 64 + (p & 15) * 4;
+                const int fc = LTX_QK_COL(HD, p, HD / 2);
                 c4[j] = *(const f32x4*)(cosT + (long)t * (D >> 1) + fc);
                 s4[j] = *(const f32x4*)(sinT + (long)t * (D >> 1) + fc);
             }
@@ -330,7 +371,7 @@ __global__ __launch_bounds__(256) void qknorm_rope_kernel(QkJob j0, QkJob j1, co
     for (int j = 0; j < NP; ++j) {
         const int p = threadIdx.x + j * 256;
         if (p < npair) {
-            const int col = (p >> 4) * 128 + (p & 15) * 4;
+            const int col = LTX_QK_COL(HD, p, HD);
             f32x4 a, b;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
@@ -338,99 +379,177 @@ __global__ __launch_bounds__(256) void qknorm_rope_kernel(QkJob j0, QkJob j1, co
                 b[e] = vb[j][e] * rstd * wb[j][e];
             }
             if (cosT) {
-                // the reference rounds the normed q/k to its storage dtype before the f32 rotation only when that
-                // dtype is bf16 (cross-modal case); in the DiT q,k are f32 here (LTXRoPE.swift:90-92).
 #pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float a0 = a[e], b0 = b[e];
-                    a[e] = a0 * c4[j][e] - b0 * s4[j][e];
-                    b[e] = b0 * c4[j][e] + a0 * s4[j][e];
-                }
+                for (int e = 0; e < 4; ++e) LTX_QK_ROTATE(a[e], b[e], c4[j][e], s4[j][e]);
             }
-            uint2 pa, pb;
-            pa.x = pack_bf16x2(a[0] * osc, a[1] * osc);
-            pa.y = pack_bf16x2(a[2] * osc, a[3] * osc);
-            pb.x = pack_bf16x2(b[0] * osc, b[1] * osc);
-            pb.y = pack_bf16x2(b[2] * osc, b[3] * osc);
-            *(uint2*)(orow + col) = pa;
-            *(uint2*)(orow + col + 64) = pb;
+            qk_store<HD>(orow, col, a, b, osc);
         }
     }
 }
 
-// The same kernel for heads of 64 (LTXAttention at 32 x 64, the audio / cross-modal attention of the dual block): head h of a row is
-// columns h*64 .. h*64+63, rotated as halves [0:32] / [32:64] with columns h*32 .. h*32+31 of the cos/sin row. The norm is still
-// across the whole row. A kernel of its own so that the head-dim-128 instantiations above stay as they are.
-template <int NP, bool XB = false>
-__global__ __launch_bounds__(256) void qknorm_rope64_kernel(QkJob j0, QkJob j1, const float* __restrict__ cosT,
-                                                          const float* __restrict__ sinT, int T, int D, float eps) {
-    __shared__ float red[4];
+// R rows per workgroup of qknorm_rope_kernel<128> (D = 4096): the norm weights are fetched once per R rows instead of once per row
+// (they are as many bytes as a row), every row is loaded before the first reduction, the R sums share one barrier pair.
+template <int R, bool XB>
+__global__ __launch_bounds__(256) void qknorm_rope_rows_kernel(QkJob j0, QkJob j1, const float* __restrict__ cosT, const float* __restrict__ sinT,
+                                                               int T, int rows, float eps) {
+    constexpr int HD = 128, NP = 2, D = 4096;
+    __shared__ float red[4][R];
     const QkJob job = blockIdx.y ? j1 : j0;
-    const int row = blockIdx.x;
-    const float* xr = XB ? (const float*)((const bf16_t*)job.x + (long)row * job.ldx) : job.x + (long)row * job.ldx;
-    // pair chunk p (0 .. D/8-1): head = p / 8, i4 = p % 8 ; a at head*64 + i4*4, b at +32
-    const int npair = D >> 3;
-    const int t = row % T;
-    f32x4 va[NP], vb[NP], wa[NP], wb[NP], c4[NP], s4[NP];
+    const int row0 = blockIdx.x * R;
+    f32x4 va[R][NP], vb[R][NP], wa[NP], wb[NP];
+    int col[NP], fc[NP];
 #pragma unroll
     for (int j = 0; j < NP; ++j) {
         const int p = threadIdx.x + j * 256;
-        va[j] = vb[j] = f32x4{0.f, 0.f, 0.f, 0.f};
-        if (p < npair) {
-            const int col = (p >> 3) * 64 + (p & 7) * 4;
-            va[j] = qk_load4<XB>(xr, col);
-            vb[j] = qk_load4<XB>(xr, col + 32);
+        col[j] = LTX_QK_COL(HD, p, HD);
+        fc[j] = LTX_QK_COL(HD, p, HD / 2);
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const int row = (row0 + r) < rows ? (row0 + r) : rows - 1;
+        const float* xr = qk_row<XB>(job.x, job.ldx, row);
+#pragma unroll
+        for (int j = 0; j < NP; ++j) {
+            va[r][j] = qk_load4<XB>(xr, col[j]);
+            vb[r][j] = qk_load4<XB>(xr, col[j] + HD / 2);
         }
     }
 #pragma unroll
     for (int j = 0; j < NP; ++j) {
-        const int p = threadIdx.x + j * 256;
-        if (p < npair) {
-            const int col = (p >> 3) * 64 + (p & 7) * 4;
-            wa[j] = *(const f32x4*)(job.w + col);
-            wb[j] = *(const f32x4*)(job.w + col + 32);
-            if (cosT) {
-                // cos/sin rows are [T][D/2]; head h uses columns h*32 .. h*32+31
-                const int fc = (p >> 3) * 32 + (p & 7) * 4;
-                c4[j] = *(const f32x4*)(cosT + (long)t * (D >> 1) + fc);
-                s4[j] = *(const f32x4*)(sinT + (long)t * (D >> 1) + fc);
+        wa[j] = *(const f32x4*)(job.w + col[j]);
+        wb[j] = *(const f32x4*)(job.w + col[j] + HD / 2);
+    }
+    // the table rows too, before the reduction: a dependent load behind the barrier costs a second memory latency per workgroup
+    f32x4 c4[R][NP], s4[R][NP];
+    if (cosT) {
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const int row = (row0 + r) < rows ? (row0 + r) : rows - 1;
+            const long tb = (long)(row % T) * (D >> 1);
+#pragma unroll
+            for (int j = 0; j < NP; ++j) {
+                c4[r][j] = *(const f32x4*)(cosT + tb + fc[j]);
+                s4[r][j] = *(const f32x4*)(sinT + tb + fc[j]);
             }
         }
     }
-    float s2 = 0.f;
+    float ss[R];
 #pragma unroll
-    for (int j = 0; j < NP; ++j)
+    for (int r = 0; r < R; ++r) {
+        float a = 0.f;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) s2 += va[j][e] * va[j][e] + vb[j][e] * vb[j][e];
-    const float rstd = rsqrtf(block_reduce_sum(s2, red) / (float)D + eps);
+        for (int j = 0; j < NP; ++j)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) a += va[r][j][e] * va[r][j][e] + vb[r][j][e] * vb[r][j][e];
+        ss[r] = wave_reduce_sum(a);
+    }
+    post_wave_sums(ss, red);
     const float osc = job.out_scale;
-    bf16_t* orow = job.out + (long)row * job.ldo;
 #pragma unroll
-    for (int j = 0; j < NP; ++j) {
-        const int p = threadIdx.x + j * 256;
-        if (p < npair) {
-            const int col = (p >> 3) * 64 + (p & 7) * 4;
+    for (int r = 0; r < R; ++r) {
+        const int row = row0 + r;
+        if (row >= rows) break;
+        const float rstd = rsqrtf(four_wave_total(red, r) / (float)D + eps);
+        bf16_t* orow = job.out + (long)row * job.ldo;
+#pragma unroll
+        for (int j = 0; j < NP; ++j) {
             f32x4 a, b;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                a[e] = va[j][e] * rstd * wa[j][e];
-                b[e] = vb[j][e] * rstd * wb[j][e];
+                a[e] = va[r][j][e] * rstd * wa[j][e];
+                b[e] = vb[r][j][e] * rstd * wb[j][e];
             }
             if (cosT) {
 #pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float a0 = a[e], b0 = b[e];
-                    a[e] = a0 * c4[j][e] - b0 * s4[j][e];
-                    b[e] = b0 * c4[j][e] + a0 * s4[j][e];
-                }
+                for (int e = 0; e < 4; ++e) LTX_QK_ROTATE(a[e], b[e], c4[r][j][e], s4[r][j][e]);
             }
-            uint2 pa, pb;
-            pa.x = pack_bf16x2(a[0] * osc, a[1] * osc);
-            pa.y = pack_bf16x2(a[2] * osc, a[3] * osc);
-            pb.x = pack_bf16x2(b[0] * osc, b[1] * osc);
-            pb.y = pack_bf16x2(b[2] * osc, b[3] * osc);
-            *(uint2*)(orow + col) = pa;
-            *(uint2*)(orow + col + 32) = pb;
+            qk_store<HD>(orow, col[j], a, b, osc);
+        }
+    }
+}
+
+// The self-attention pair (q and k of the same tokens) in one workgroup: R rows of BOTH jobs share one fetch of the rotary tables
+// (a table row is as many bytes as the f32 row it rotates; with one workgroup per job the second fetch came from L2 / Infinity Cache,
+// 768 workgroups later) and one barrier pair. The norm weights of a job are fetched behind the barrier, when its rows are finished.
+template <int R, bool XB>
+__global__ __launch_bounds__(256) void qknorm_rope_pair_kernel(QkJob j0, QkJob j1, const float* __restrict__ cosT, const float* __restrict__ sinT,
+                                                               int T, int rows, float eps) {
+    constexpr int HD = 128, NP = 2, D = 4096, NJ = 2;
+    __shared__ float red[4][NJ * R];
+    const int row0 = blockIdx.x * R;
+    f32x4 va[NJ][R][NP], vb[NJ][R][NP], c4[R][NP], s4[R][NP];
+    int col[NP], fc[NP];
+#pragma unroll
+    for (int j = 0; j < NP; ++j) {
+        const int p = threadIdx.x + j * 256;
+        col[j] = LTX_QK_COL(HD, p, HD);
+        fc[j] = LTX_QK_COL(HD, p, HD / 2);
+    }
+#pragma unroll
+    for (int q = 0; q < NJ; ++q) {
+        const QkJob& job = q ? j1 : j0;
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const int row = (row0 + r) < rows ? (row0 + r) : rows - 1;
+            const float* xr = qk_row<XB>(job.x, job.ldx, row);
+#pragma unroll
+            for (int j = 0; j < NP; ++j) {
+                va[q][r][j] = qk_load4<XB>(xr, col[j]);
+                vb[q][r][j] = qk_load4<XB>(xr, col[j] + HD / 2);
+            }
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const int row = (row0 + r) < rows ? (row0 + r) : rows - 1;
+        const long tb = (long)(row % T) * (D >> 1);
+#pragma unroll
+        for (int j = 0; j < NP; ++j) {
+            c4[r][j] = *(const f32x4*)(cosT + tb + fc[j]);
+            s4[r][j] = *(const f32x4*)(sinT + tb + fc[j]);
+        }
+    }
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+    for (int q = 0; q < NJ; ++q)
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            float a = 0.f;
+#pragma unroll
+            for (int j = 0; j < NP; ++j)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) a += va[q][r][j][e] * va[q][r][j][e] + vb[q][r][j][e] * vb[q][r][j][e];
+            a = wave_reduce_sum(a);
+            if (lane == 0) red[w][q * R + r] = a;  // posted behind each butterfly, not together (post_wave_sums): this kernel's order
+        }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < NJ; ++q) {
+        const QkJob& job = q ? j1 : j0;
+        const float osc = job.out_scale;
+        f32x4 wa[NP], wb[NP];
+#pragma unroll
+        for (int j = 0; j < NP; ++j) {
+            wa[j] = *(const f32x4*)(job.w + col[j]);
+            wb[j] = *(const f32x4*)(job.w + col[j] + HD / 2);
+        }
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const int row = row0 + r;
+            if (row >= rows) break;
+            const float rstd = rsqrtf(four_wave_total(red, q * R + r) / (float)D + eps);
+            bf16_t* orow = job.out + (long)row * job.ldo;
+#pragma unroll
+            for (int j = 0; j < NP; ++j) {
+                f32x4 a, b;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    a[e] = va[q][r][j][e] * rstd * wa[j][e];
+                    b[e] = vb[q][r][j][e] * rstd * wb[j][e];
+                    LTX_QK_ROTATE(a[e], b[e], c4[r][j][e], s4[r][j][e]);
+                }
+                qk_store<HD>(orow, col[j], a, b, osc);
+            }
         }
     }
 }
@@ -830,38 +949,36 @@ inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
 }  // namespace
 
-void launch_norm_mod(const float* x, long ldx, const float* scale, const float* shift, long mod_bstride,
-                     int rows_per_batch, bf16_t* out, long ldo, int rows, int D, int norm_kind, float eps,
-                     int round_norm_bf16, hipStream_t stream, const int32_t* row_map) {
-    LTX_REQUIRE(D % 4 == 0 && D <= MAXV * 1024 && ldx % 4 == 0 && ldo % 4 == 0, "norm_mod: D=%d ldx=%ld ldo=%ld", D, ldx, ldo);
-    LTX_REQUIRE((scale == nullptr) == (shift == nullptr), "norm_mod: scale/shift must both be set or both null");
-    const int rpb = rows_per_batch < 1 ? 1 : rows_per_batch;
+void launch_norm_mod(const NormModArgs& a, hipStream_t stream) {
+    LTX_REQUIRE(a.D % 4 == 0 && a.D <= MAXV * 1024 && a.ldx % 4 == 0 && a.ldo % 4 == 0, "norm_mod: D=%d ldx=%ld ldo=%ld", a.D, a.ldx, a.ldo);
+    LTX_REQUIRE((a.scale == nullptr) == (a.shift == nullptr), "norm_mod: scale/shift must both be set or both null");
+    const int rpb = a.rows_per_batch < 1 ? 1 : a.rows_per_batch;
 #ifdef LTX_EXPERIMENTS  // timing ablation (experiments library only): LTX_ABL_ROWS bit 0 drops this pass after the first 400 calls - the
     // buffers keep realistic stale values, so what the step then gains is the upper bound of any fusion of the pass (profiles/r04_row_ablation.txt)
     { const int abl = ltx_opt(OPT_ABL_ROWS); static long calls = 0; if ((abl & 1) && ++calls > 400) return; }
 #endif
-    ProfScope prof(PROF_ELEM, (double)rows * D * (4 + 2), stream);  // algorithmic bytes: f32 row in, bf16 row out
+    ProfScope prof(PROF_ELEM, (double)a.rows * a.D * (4 + 2), stream);  // algorithmic bytes: f32 row in, bf16 row out
     // rows per workgroup: 4 share one fetch of the modulation vectors; at 1536 rows that is 384 workgroups = 1.5 per CU, and two rows per
     // workgroup (768 = 3 per CU) are 10 % faster (9.15 vs 10.2 us alone, 36.39 vs 36.53 ms per forward); no difference from 6144 rows up
     const int r_raw = ltx_opt(OPT_NORM_ROWS);  // A/B option "norm_rows": 2 or 4, anything else is ignored
     const int r_env = (r_raw == 2 || r_raw == 4) ? r_raw : 0;
-    const int R_rows = r_env ? r_env : (rows <= 3072 ? 2 : 4);
-    if (norm_kind == LTX_NORM_RMS && scale && !row_map && D == 4096 && rows >= 512 && rpb % R_rows == 0) {
-#define LTX_ROWS_LAUNCH(R)                                                                                                                      \
-    hipLaunchKernelGGL((norm_mod_rows_kernel<4, R>), dim3((rows + R - 1) / R), dim3(256), 0, stream, x, ldx, scale, shift, mod_bstride, rpb, out, ldo, \
-                       rows, eps, round_norm_bf16)
+    const int R_rows = r_env ? r_env : (a.rows <= 3072 ? 2 : 4);
+    if (a.norm_kind == LTX_NORM_RMS && a.scale && !a.row_map && a.D == 4096 && a.rows >= 512 && rpb % R_rows == 0) {
+#define LTX_ROWS_LAUNCH(R)                                                                                                                   \
+    hipLaunchKernelGGL((norm_mod_rows_kernel<4, R>), dim3((a.rows + R - 1) / R), dim3(256), 0, stream, a.x, a.ldx, a.scale, a.shift, a.mod_bstride, \
+                       rpb, a.out, a.ldo, a.rows, a.eps, a.round_norm_bf16)
         if (R_rows == 2) LTX_ROWS_LAUNCH(2);
         else LTX_ROWS_LAUNCH(4);
 #undef LTX_ROWS_LAUNCH
         HIP_CHECK(hipGetLastError());
         return;
     }
-#define LTX_NORM_LAUNCH(NV)                                                                                              \
-    hipLaunchKernelGGL(norm_mod_kernel<NV>, dim3(rows), dim3(256), 0, stream, x, ldx, scale, shift, mod_bstride, rpb, out, \
-                       ldo, D, norm_kind, eps, round_norm_bf16, row_map)
-    if (D <= 1024) LTX_NORM_LAUNCH(1);
-    else if (D <= 2048) LTX_NORM_LAUNCH(2);
-    else if (D <= 4096) LTX_NORM_LAUNCH(4);
+#define LTX_NORM_LAUNCH(NV)                                                                                                            \
+    hipLaunchKernelGGL(norm_mod_kernel<NV>, dim3(a.rows), dim3(256), 0, stream, a.x, a.ldx, a.scale, a.shift, a.mod_bstride, rpb, a.out, \
+                       a.ldo, a.D, a.norm_kind, a.eps, a.round_norm_bf16, a.row_map)
+    if (a.D <= 1024) LTX_NORM_LAUNCH(1);
+    else if (a.D <= 2048) LTX_NORM_LAUNCH(2);
+    else if (a.D <= 4096) LTX_NORM_LAUNCH(4);
     else LTX_NORM_LAUNCH(8);
 #undef LTX_NORM_LAUNCH
     HIP_CHECK(hipGetLastError());
@@ -896,252 +1013,50 @@ void launch_norm_mod2(const NormMod2Job& video, const NormMod2Job& audio, float 
     HIP_CHECK(hipGetLastError());
 }
 
-// R rows per workgroup of qknorm_rope_kernel (D = 4096): the norm weights are fetched once per R rows instead of once per row
-// (they are as many bytes as a row), every row is loaded before the first reduction, the R sums share one barrier pair.
-template <int R, bool XB = false>
-__global__ __launch_bounds__(256) void qknorm_rope_rows_kernel(QkJob j0, QkJob j1, const float* __restrict__ cosT, const float* __restrict__ sinT,
-                                                               int T, int rows, float eps) {
-    constexpr int NP = 2, D = 4096;
-    __shared__ float red[4][R];
-    const QkJob job = blockIdx.y ? j1 : j0;
-    const int row0 = blockIdx.x * R;
-    f32x4 va[R][NP], vb[R][NP], wa[NP], wb[NP];
-    int col[NP], fc[NP];
-#pragma unroll
-    for (int j = 0; j < NP; ++j) {
-        const int p = threadIdx.x + j * 256;
-        col[j] = (p >> 4) * 128 + (p & 15) * 4;
-        fc[j] = (p >> 4) * 64 + (p & 15) * 4;
-    }
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        const int row = (row0 + r) < rows ? (row0 + r) : rows - 1;
-        const float* xr = XB ? (const float*)((const bf16_t*)job.x + (long)row * job.ldx) : job.x + (long)row * job.ldx;
-#pragma unroll
-        for (int j = 0; j < NP; ++j) {
-            va[r][j] = qk_load4<XB>(xr, col[j]);
-            vb[r][j] = qk_load4<XB>(xr, col[j] + 64);
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < NP; ++j) {
-        wa[j] = *(const f32x4*)(job.w + col[j]);
-        wb[j] = *(const f32x4*)(job.w + col[j] + 64);
-    }
-    // the table rows too, before the reduction: a dependent load behind the barrier costs a second memory latency per workgroup
-    f32x4 c4[R][NP], s4[R][NP];
-    if (cosT) {
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            const int row = (row0 + r) < rows ? (row0 + r) : rows - 1;
-            const long tb = (long)(row % T) * (D >> 1);
-#pragma unroll
-            for (int j = 0; j < NP; ++j) {
-                c4[r][j] = *(const f32x4*)(cosT + tb + fc[j]);
-                s4[r][j] = *(const f32x4*)(sinT + tb + fc[j]);
-            }
-        }
-    }
-    float ss[R];
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        float a = 0.f;
-#pragma unroll
-        for (int j = 0; j < NP; ++j)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) a += va[r][j][e] * va[r][j][e] + vb[r][j][e] * vb[r][j][e];
-        ss[r] = wave_reduce_sum(a);
-    }
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (lane == 0) {
-#pragma unroll
-        for (int r = 0; r < R; ++r) red[w][r] = ss[r];
-    }
-    __syncthreads();
-    const float osc = job.out_scale;
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        const int row = row0 + r;
-        if (row >= rows) break;
-        const float rstd = rsqrtf((red[0][r] + red[1][r] + red[2][r] + red[3][r]) / (float)D + eps);
-        bf16_t* orow = job.out + (long)row * job.ldo;
-#pragma unroll
-        for (int j = 0; j < NP; ++j) {
-            f32x4 a, b;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                a[e] = va[r][j][e] * rstd * wa[j][e];
-                b[e] = vb[r][j][e] * rstd * wb[j][e];
-            }
-            if (cosT) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float a0 = a[e], b0 = b[e];
-                    a[e] = a0 * c4[r][j][e] - b0 * s4[r][j][e];
-                    b[e] = b0 * c4[r][j][e] + a0 * s4[r][j][e];
-                }
-            }
-            uint2 pa, pb;
-            pa.x = pack_bf16x2(a[0] * osc, a[1] * osc);
-            pa.y = pack_bf16x2(a[2] * osc, a[3] * osc);
-            pb.x = pack_bf16x2(b[0] * osc, b[1] * osc);
-            pb.y = pack_bf16x2(b[2] * osc, b[3] * osc);
-            *(uint2*)(orow + col[j]) = pa;
-            *(uint2*)(orow + col[j] + 64) = pb;
-        }
-    }
+namespace {
+// the generic kernel: NP pair chunks per thread from D
+template <int HD, bool XB>
+void launch_qk_generic(const QkJob& j0, const QkJob& j1, const QkNormRopeArgs& a, dim3 grid, int t, hipStream_t stream) {
+#define LTX_QK_LAUNCH(NP) hipLaunchKernelGGL((qknorm_rope_kernel<HD, NP, XB>), grid, dim3(256), 0, stream, j0, j1, a.cos, a.sin, t, a.D, a.eps)
+    if (a.D <= 2048) LTX_QK_LAUNCH(1);
+    else if (a.D <= 4096) LTX_QK_LAUNCH(2);
+    else LTX_QK_LAUNCH(4);
+#undef LTX_QK_LAUNCH
 }
-
-// The self-attention pair (q and k of the same tokens) in one workgroup: R rows of BOTH jobs share one fetch of the rotary tables
-// (a table row is as many bytes as the f32 row it rotates; with one workgroup per job the second fetch came from L2 / Infinity Cache,
-// 768 workgroups later) and one barrier pair.
-template <int R, bool XB = false>
-__global__ __launch_bounds__(256) void qknorm_rope_pair_kernel(QkJob j0, QkJob j1, const float* __restrict__ cosT, const float* __restrict__ sinT,
-                                                               int T, int rows, float eps) {
-    constexpr int NP = 2, D = 4096, NJ = 2;
-    __shared__ float red[4][NJ * R];
-    const int row0 = blockIdx.x * R;
-    f32x4 va[NJ][R][NP], vb[NJ][R][NP], c4[R][NP], s4[R][NP];
-    int col[NP], fc[NP];
-#pragma unroll
-    for (int j = 0; j < NP; ++j) {
-        const int p = threadIdx.x + j * 256;
-        col[j] = (p >> 4) * 128 + (p & 15) * 4;
-        fc[j] = (p >> 4) * 64 + (p & 15) * 4;
-    }
-#pragma unroll
-    for (int q = 0; q < NJ; ++q) {
-        const QkJob& job = q ? j1 : j0;
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            const int row = (row0 + r) < rows ? (row0 + r) : rows - 1;
-            const float* xr = XB ? (const float*)((const bf16_t*)job.x + (long)row * job.ldx) : job.x + (long)row * job.ldx;
-#pragma unroll
-            for (int j = 0; j < NP; ++j) {
-                va[q][r][j] = qk_load4<XB>(xr, col[j]);
-                vb[q][r][j] = qk_load4<XB>(xr, col[j] + 64);
-            }
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        const int row = (row0 + r) < rows ? (row0 + r) : rows - 1;
-        const long tb = (long)(row % T) * (D >> 1);
-#pragma unroll
-        for (int j = 0; j < NP; ++j) {
-            c4[r][j] = *(const f32x4*)(cosT + tb + fc[j]);
-            s4[r][j] = *(const f32x4*)(sinT + tb + fc[j]);
-        }
-    }
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-    for (int q = 0; q < NJ; ++q)
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            float a = 0.f;
-#pragma unroll
-            for (int j = 0; j < NP; ++j)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) a += va[q][r][j][e] * va[q][r][j][e] + vb[q][r][j][e] * vb[q][r][j][e];
-            a = wave_reduce_sum(a);
-            if (lane == 0) red[w][q * R + r] = a;
-        }
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < NJ; ++q) {
-        const QkJob& job = q ? j1 : j0;
-        const float osc = job.out_scale;
-        f32x4 wa[NP], wb[NP];
-#pragma unroll
-        for (int j = 0; j < NP; ++j) {
-            wa[j] = *(const f32x4*)(job.w + col[j]);
-            wb[j] = *(const f32x4*)(job.w + col[j] + 64);
-        }
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            const int row = row0 + r;
-            if (row >= rows) break;
-            const int k = q * R + r;
-            const float rstd = rsqrtf((red[0][k] + red[1][k] + red[2][k] + red[3][k]) / (float)D + eps);
-            bf16_t* orow = job.out + (long)row * job.ldo;
-#pragma unroll
-            for (int j = 0; j < NP; ++j) {
-                f32x4 a, b;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float a0 = va[q][r][j][e] * rstd * wa[j][e], b0 = vb[q][r][j][e] * rstd * wb[j][e];
-                    a[e] = a0 * c4[r][j][e] - b0 * s4[r][j][e];
-                    b[e] = b0 * c4[r][j][e] + a0 * s4[r][j][e];
-                }
-                uint2 pa, pb;
-                pa.x = pack_bf16x2(a[0] * osc, a[1] * osc);
-                pa.y = pack_bf16x2(a[2] * osc, a[3] * osc);
-                pb.x = pack_bf16x2(b[0] * osc, b[1] * osc);
-                pb.y = pack_bf16x2(b[2] * osc, b[3] * osc);
-                *(uint2*)(orow + col[j]) = pa;
-                *(uint2*)(orow + col[j] + 64) = pb;
-            }
-        }
-    }
+// the kernel of a launch, for rows of one type
+template <bool XB>
+void launch_qk(const QkNormRopeArgs& a, hipStream_t stream) {
+    const int jobs = a.job[1].x ? 2 : 1;
+    const QkJob j0{(const float*)a.job[0].x, a.job[0].w, a.job[0].out, a.ldx, a.ldo, a.job[0].out_scale},
+        j1{(const float*)a.job[1].x, a.job[1].w, a.job[1].out, a.ldx, a.ldo, a.job[1].out_scale};
+    const dim3 grid(a.rows, jobs);
+    const int t = a.T < 1 ? 1 : a.T;
+    if (a.head_dim == 64) return launch_qk_generic<64, XB>(j0, j1, a, grid, t, stream);
+    const bool no_pair = ltx_opt(OPT_QKNORM_NO_PAIR) != 0;  // A/B option "qknorm_no_pair"
+    constexpr int R = 2;  // rows per workgroup at full width; 1 and 3: within the run-to-run noise of the forward (round 3)
+    const dim3 grid_r((a.rows + R - 1) / R, jobs);
+    if (a.D == 4096 && a.rows >= 512 && jobs == 2 && a.cos && !no_pair)  // q and k of the same tokens: one fetch of the tables (2.64 -> 2.54 ms of row passes per step)
+        hipLaunchKernelGGL((qknorm_rope_pair_kernel<R, XB>), dim3(grid_r.x), dim3(256), 0, stream, j0, j1, a.cos, a.sin, t, a.rows, a.eps);
+    else if (a.D == 4096 && a.rows >= 512)  // the DiT at full width: R rows per workgroup share one fetch of the norm weights
+        hipLaunchKernelGGL((qknorm_rope_rows_kernel<R, XB>), grid_r, dim3(256), 0, stream, j0, j1, a.cos, a.sin, t, a.rows, a.eps);
+    else
+        launch_qk_generic<128, XB>(j0, j1, a, grid, t, stream);
 }
+}  // namespace
 
-void launch_qknorm_rope2(const float* x0, const float* w0, bf16_t* out0, const float* x1, const float* w1, bf16_t* out1,
-                         long ldx, long ldo, const float* cosT, const float* sinT, int T, int rows, int D, float eps,
-                         hipStream_t stream, float out_scale0, bool x_bf16, int head_dim) {
-    LTX_REQUIRE(head_dim == 64 || head_dim == 128, "qknorm_rope: head dim %d (64 or 128)", head_dim);
-    LTX_REQUIRE(D % head_dim == 0 && D <= MAXV * 1024 && ldx % 4 == 0 && ldo % 4 == 0, "qknorm_rope: D=%d", D);
-
-    const QkJob j0{x0, w0, out0, ldx, ldo, out_scale0}, j1{x1, w1, out1, ldx, ldo, 1.0f};
-    if (head_dim == 64) {
-        ProfScope prof(PROF_ELEM, (double)rows * D * (x1 ? 2 : 1) * ((x_bf16 ? 2 : 4) + 2 + (cosT ? 4 : 0)), stream);
-        const dim3 grid(rows, x1 ? 2 : 1);
-        const int t = T < 1 ? 1 : T;
-        if (x_bf16) {
-            if (D <= 2048) hipLaunchKernelGGL((qknorm_rope64_kernel<1, true>), grid, dim3(256), 0, stream, j0, j1, cosT, sinT, t, D, eps);
-            else if (D <= 4096) hipLaunchKernelGGL((qknorm_rope64_kernel<2, true>), grid, dim3(256), 0, stream, j0, j1, cosT, sinT, t, D, eps);
-            else hipLaunchKernelGGL((qknorm_rope64_kernel<4, true>), grid, dim3(256), 0, stream, j0, j1, cosT, sinT, t, D, eps);
-        } else if (D <= 2048) hipLaunchKernelGGL(qknorm_rope64_kernel<1>, grid, dim3(256), 0, stream, j0, j1, cosT, sinT, t, D, eps);
-        else if (D <= 4096) hipLaunchKernelGGL(qknorm_rope64_kernel<2>, grid, dim3(256), 0, stream, j0, j1, cosT, sinT, t, D, eps);
-        else hipLaunchKernelGGL(qknorm_rope64_kernel<4>, grid, dim3(256), 0, stream, j0, j1, cosT, sinT, t, D, eps);
-        HIP_CHECK(hipGetLastError());
-        return;
-    }
-#ifdef LTX_EXPERIMENTS  // timing ablation: LTX_ABL_ROWS bit 1 drops the q|k pass, bit 2 the cross-attention q pass, after two forwards' worth of calls
-    { const int abl = ltx_opt(OPT_ABL_ROWS); static long c2 = 0, c1 = 0;
-      if (x1 && (abl & 2) && ++c2 > 200) return; if (!x1 && (abl & 4) && ++c1 > 300) return; }
+void launch_qknorm_rope(const QkNormRopeArgs& a, hipStream_t stream) {
+    LTX_REQUIRE(a.head_dim == 64 || a.head_dim == 128, "qknorm_rope: head dim %d (64 or 128)", a.head_dim);
+    LTX_REQUIRE(a.D % a.head_dim == 0 && a.D <= MAXV * 1024 && a.ldx % 4 == 0 && a.ldo % 4 == 0, "qknorm_rope: D=%d", a.D);
+    const int jobs = a.job[1].x ? 2 : 1;
+#ifdef LTX_EXPERIMENTS  // timing ablation (head dim 128): LTX_ABL_ROWS bit 1 drops the q|k pass, bit 2 the cross-attention q pass, after two forwards' worth of calls
+    if (a.head_dim == 128) { const int abl = ltx_opt(OPT_ABL_ROWS); static long c2 = 0, c1 = 0;
+      if (jobs == 2 && (abl & 2) && ++c2 > 200) return; if (jobs == 1 && (abl & 4) && ++c1 > 300) return; }
 #endif
     // algorithmic bytes: the f32 (or bf16) rows in, the bf16 rows out, cos/sin rows once per job
-    ProfScope prof(PROF_ELEM, (double)rows * D * (x1 ? 2 : 1) * ((x_bf16 ? 2 : 4) + 2 + (cosT ? 4 : 0)), stream);
-    const dim3 grid(rows, x1 ? 2 : 1);
-    const int t = T < 1 ? 1 : T;
-    const bool no_pair = ltx_opt(OPT_QKNORM_NO_PAIR) != 0;  // A/B option "qknorm_no_pair"
-    if (D == 4096 && rows >= 512 && x1 && cosT && !no_pair) {  // q and k of the same tokens: one fetch of the tables (2.64 -> 2.54 ms of row passes per step)
-        constexpr int R = 2;  // 1 and 3 rows per workgroup: within the run-to-run noise of the forward (round 3)
-        if (x_bf16) hipLaunchKernelGGL((qknorm_rope_pair_kernel<R, true>), dim3((rows + R - 1) / R), dim3(256), 0, stream, j0, j1, cosT, sinT, t, rows, eps);
-        else hipLaunchKernelGGL(qknorm_rope_pair_kernel<R>, dim3((rows + R - 1) / R), dim3(256), 0, stream, j0, j1, cosT, sinT, t, rows, eps);
-        HIP_CHECK(hipGetLastError());
-        return;
-    }
-    if (D == 4096 && rows >= 512) {   // the DiT at full width: R rows per workgroup share one fetch of the norm weights
-        constexpr int R = 2;
-        if (x_bf16) hipLaunchKernelGGL((qknorm_rope_rows_kernel<R, true>), dim3((rows + R - 1) / R, x1 ? 2 : 1), dim3(256), 0, stream, j0, j1, cosT, sinT, t, rows, eps);
-        else hipLaunchKernelGGL(qknorm_rope_rows_kernel<R>, dim3((rows + R - 1) / R, x1 ? 2 : 1), dim3(256), 0, stream, j0, j1, cosT, sinT, t, rows, eps);
-        HIP_CHECK(hipGetLastError());
-        return;
-    }
-    if (x_bf16) {
-        if (D <= 2048) hipLaunchKernelGGL((qknorm_rope_kernel<1, true>), grid, dim3(256), 0, stream, j0, j1, cosT, sinT, t, D, eps);
-        else if (D <= 4096) hipLaunchKernelGGL((qknorm_rope_kernel<2, true>), grid, dim3(256), 0, stream, j0, j1, cosT, sinT, t, D, eps);
-        else hipLaunchKernelGGL((qknorm_rope_kernel<4, true>), grid, dim3(256), 0, stream, j0, j1, cosT, sinT, t, D, eps);
-    } else if (D <= 2048) hipLaunchKernelGGL(qknorm_rope_kernel<1>, grid, dim3(256), 0, stream, j0, j1, cosT, sinT, t, D, eps);
-    else if (D <= 4096) hipLaunchKernelGGL(qknorm_rope_kernel<2>, grid, dim3(256), 0, stream, j0, j1, cosT, sinT, t, D, eps);
-    else hipLaunchKernelGGL(qknorm_rope_kernel<4>, grid, dim3(256), 0, stream, j0, j1, cosT, sinT, t, D, eps);
+    ProfScope prof(PROF_ELEM, (double)a.rows * a.D * jobs * ((a.x_bf16 ? 2 : 4) + 2 + (a.cos ? 4 : 0)), stream);
+    if (a.x_bf16) launch_qk<true>(a, stream);
+    else launch_qk<false>(a, stream);
     HIP_CHECK(hipGetLastError());
-}
-
-void launch_qknorm_rope(const float* x, long ldx, const float* w, const float* cosT, const float* sinT, int T,
-                        bf16_t* out, long ldo, int rows, int D, float eps, hipStream_t stream, float out_scale, bool x_bf16, int head_dim) {
-    launch_qknorm_rope2(x, w, out, nullptr, nullptr, nullptr, ldx, ldo, cosT, sinT, T, rows, D, eps, stream, out_scale, x_bf16, head_dim);
 }
 
 void launch_cast_f32_bf16(const float* x, bf16_t* out, long n, hipStream_t stream) {

@@ -2100,8 +2100,12 @@ void launch_gemm_bf16(const GemmArgs& a, hipStream_t stream, const NormAfter* na
         return;
     }
     launch_gemm(a, o, stream);
-    launch_norm_mod(a.ep.out_f32, a.ep.ld_f32, na->scale, na->shift, na->mod_bstride, na->rows_per_batch, na->out, na->ldo, a.M, a.N, na->norm_kind,
-                    na->eps, na->round_norm_bf16, stream, na->row_map);
+    NormModArgs n;  // the pass as a launch of its own, over the rows this launch wrote
+    n.x = a.ep.out_f32; n.ldx = a.ep.ld_f32; n.rows = a.M; n.D = a.N;
+    n.scale = na->scale; n.shift = na->shift; n.mod_bstride = na->mod_bstride; n.rows_per_batch = na->rows_per_batch; n.row_map = na->row_map;
+    n.out = na->out; n.ldo = na->ldo;
+    n.norm_kind = na->norm_kind; n.eps = na->eps; n.round_norm_bf16 = na->round_norm_bf16;
+    launch_norm_mod(n, stream);
 }
 
 void launch_gemv_f32(const float* a, long lda, const bf16_t* W, long ldw, const float* bias, float* out, long ldo,

@@ -8,6 +8,7 @@ text-embedding connector and the VAE encoder fixtures are cross-checked the same
     python tests/golden/make_golden.py --synthetic-digests    # only synthetic_param_digests.json; needs the built library and a GPU
     python tests/golden/make_golden.py --gemm-asm-family-digests    # only gemm_asm_family_digests.json; the same needs
     python tests/golden/make_golden.py --gemm-launcher-paths-digests    # only gemm_launcher_paths_digests.json; the same needs, 256 CUs
+    python tests/golden/make_golden.py --row-passes-digests    # only row_passes_digests.json; needs the built library and a GPU
 """
 import math
 import os
@@ -300,7 +301,38 @@ def make_gemm_launcher_paths_digests():
     print("launcher path digests:", len(d))
 
 
+def make_row_passes_digests():
+    """row_passes_digests.json: the output bits of every instantiation of the q/k norm + RoPE and norm + modulation kernels
+    (tests/helpers/row_passes.py). Records the library itself (LTX_LIB may name a build of the commit whose bits are to be kept), every
+    case twice."""
+    import importlib
+    import json
+
+    sys.path.insert(0, os.path.join(HERE, "..", ".."))
+    sys.path.insert(0, os.path.join(HERE, "..", "helpers"))
+    import row_passes as rp
+
+    ltx = importlib.import_module("ltx-video-swift-mlx_amd")
+
+    def once():
+        ctx = ltx.Context(0)
+        d = rp.all_cases(ltx, ctx)
+        ctx.close()
+        return d
+
+    d, again = once(), once()
+    unstable = sorted(k for k in d if d[k] != again[k])
+    assert not unstable, f"not reproducible between two runs: {unstable}"
+    assert sorted(d) == rp.expected_keys()
+    with open(os.path.join(HERE, "row_passes_digests.json"), "w") as f:
+        json.dump({"seed": rp.SEED, "digests": d}, f, indent=0, sort_keys=True)
+        f.write("\n")
+    print("row pass digests:", len(d))
+
+
 def main():
+    if "--row-passes-digests" in sys.argv[1:]:
+        return make_row_passes_digests()
     if "--gemm-launcher-paths-digests" in sys.argv[1:]:
         return make_gemm_launcher_paths_digests()
     if "--synthetic-digests" in sys.argv[1:]:

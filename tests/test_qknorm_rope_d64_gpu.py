@@ -1,4 +1,4 @@
-"""q/k RMSNorm + split RoPE at head dim 64 (csrc/elementwise.hip, qknorm_rope64_kernel) through ltx_op_qknorm_rope_hd, against the
+"""q/k RMSNorm + split RoPE at head dim 64 (csrc/elementwise.hip, qknorm_rope_kernel<64, NP, XB>) through ltx_op_qknorm_rope_hd, against the
 oracle's rms_norm + apply_split_rope. Bound: the one test_kernels_gpu.test_qknorm_rope uses, 2^-8 * max|ref| + 1e-4 (one rounding of
 the result to bf16)."""
 import os

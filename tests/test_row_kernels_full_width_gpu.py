@@ -1,6 +1,6 @@
 """The row kernels the DiT runs at full width (D = 4096, 512 rows and more), each against a float64 restatement of its formula.
 
-launch_norm_mod and launch_qknorm_rope2 (csrc/elementwise.hip) leave their generic one-row-per-workgroup kernels at D == 4096 and
+launch_norm_mod and launch_qknorm_rope (csrc/elementwise.hip) leave their generic one-row-per-workgroup kernels at D == 4096 and
 rows >= 512 for norm_mod_rows_kernel<4, 2 | 4>, qknorm_rope_pair_kernel<2, f32 | bf16> and qknorm_rope_rows_kernel<2, f32 | bf16>. Whole
 forwards see those at rel-L2 1e-2; here every ELEMENT is held to the rounding of its own value. The calls go through the two test
 seams ltx_op_norm_mod_ex / ltx_op_qknorm_rope_pair, which pass every argument of the launchers.
@@ -356,7 +356,7 @@ def run_qk(ctx, qk, w, cos, sin, T, rows, jobs=2, ldo=2 * D + 8):
 
 
 def qk_kernel_expected(rows, jobs, tables, no_pair=False):
-    """launch_qknorm_rope2's selection at D == 4096, restated"""
+    """launch_qknorm_rope's selection at D == 4096, restated"""
     if rows >= 512 and jobs == 2 and tables and not no_pair:
         return "pair"
     return "rows" if rows >= 512 else "generic"

@@ -11,7 +11,7 @@
 Profiler* prof_current() { return nullptr; }
 ProfRec* Profiler::begin(int, double, hipStream_t) { return nullptr; }
 void Profiler::end(ProfRec*, hipStream_t) {}
-void launch_norm_mod(const float*, long, const float*, const float*, long, int, bf16_t*, long, int, int, int, float, int, hipStream_t, const int*) { abort(); }
+void launch_norm_mod(const NormModArgs&, hipStream_t) { abort(); }
 
 int main() {
     const int M = getenv("GEMM_M") ? atoi(getenv("GEMM_M")) : 1536, N = getenv("GEMM_N") ? atoi(getenv("GEMM_N")) : 8192, K = getenv("GEMM_K") ? atoi(getenv("GEMM_K")) : 4096;
