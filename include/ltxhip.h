@@ -383,8 +383,9 @@ int ltx_attn_module_forward_dev(ltx_ctx* ctx, int index, const float* x, const v
  * with a forward of its own. It takes what LTX2Transformer.callAsFunction hands its blocks and returns both residual streams. The
  * embedders that make the modulation rows (audio_adaln_single, av_ca_*), the patchify / output heads and the caption projections are
  * "Dual video + audio model" below, which owns a stack of its own; the joint denoise loop is ltx_dual_denoise; the CLI's --audio path
- * is not part of this library yet. The modulation rows are one per batch element; the
- * reference's per-token form (image-to-video, LTX2Transformer.swift:285-312) is not implemented. A context holds one stack.
+ * is not part of this library yet. The audio modulation rows are one per batch element. The video modulation rows are one per (batch
+ * element, timestep group): n_groups and video_row_map, as ltx_dit_forward_tokens groups them - the reference's per-token form
+ * (image-to-video, LTX2Transformer.swift:285-312) with each distinct row built once. A context holds one stack.
  * ---------------------------------------------------------------------------------------------------------- */
 typedef struct ltx_dual_block_config {
     int num_layers;         /* 48 */
@@ -431,24 +432,28 @@ typedef struct ltx_dual_forward_args {
     const uint16_t* context_audio; /* [B][S][audio_context_dim] bf16 */
     const float* key_bias_video;   /* [B][S] f32 additive, (1 - mask) * -10000, or NULL (contextMask) */
     const float* key_bias_audio;
-    const float* temb_video;       /* [B][6][video_dim] f32 (TransformerArgs.timesteps) */
+    const float* temb_video;       /* [B*n_groups][6][video_dim] f32 (TransformerArgs.timesteps) */
     const float* temb_audio;       /* [B][6][audio_dim] f32 */
-    const float* cross_video_ss;   /* [B][5][video_dim] f32 (crossVideoScaleShift) */
+    const float* cross_video_ss;   /* [B*n_groups][5][video_dim] f32 (crossVideoScaleShift) */
     const float* cross_audio_ss;   /* [B][5][audio_dim] f32 (crossAudioScaleShift) */
     uint32_t phase_mask;           /* 0: all eight phases. Else bit p-1 runs phase p of every block alone - a measurement seam */
+    int n_groups;                  /* timestep groups of the video stream per batch element (1); B * n_groups <= 8. Read when struct_size
+                                      covers it, else 1 */
+    const int32_t* video_row_map;  /* [B*F*H*W] int32: video token b*F*H*W + t reads modulation row video_row_map[..] = b*n_groups +
+                                      group(b, t); entries are the caller's contract. NULL with n_groups == 1: row b */
 } ltx_dual_forward_args;
-#define LTX_DUAL_FORWARD_ARGS_INIT {sizeof(ltx_dual_forward_args), 1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}
+#define LTX_DUAL_FORWARD_ARGS_INIT {sizeof(ltx_dual_forward_args), 1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1, 0}
 /* Replaces the block loop of LTX2Transformer.callAsFunction: L x LTX2TransformerBlock.callAsFunction (LTX2TransformerBlock.swift:
  * 174-297) on both streams in place. The four RoPE table sets (LTX2Transformer.swift:136-236) are made inside from (F, H, W) and T_a and
  * cached. Asynchronous on the context stream. No stack: LTX_ERR_MODEL_NOT_LOADED; a struct_size that does not cover the fields up to
- * cross_audio_ss, B outside 1 .. 8, a dimension < 1 or a NULL stream / context / modulation pointer: LTX_ERR_INVALID_CONFIGURATION. Every
- * check comes before the first launch: a refused call writes nothing. */
+ * cross_audio_ss, B outside 1 .. 8, a dimension < 1 or a NULL stream / context / modulation pointer: LTX_ERR_INVALID_CONFIGURATION; so are
+ * n_groups < 1, B * n_groups > 8 and n_groups > 1 without a map. Every check comes before the first launch: a refused call writes nothing. */
 int ltx_dual_blocks_forward_dev(ltx_ctx* ctx, const ltx_dual_forward_args* args);
 /* One job of ltx_op_norm_mod2: rows f32 [rows][ldx] -> two bf16 outputs [rows][ldo]. */
 typedef struct ltx_norm_mod2_job {
     const float* x;
     long ldx;
-    const float* scale0; /* [B][mod_bstride] f32, row b = row / rows_per_batch; NULL with shift0 NULL: the plain norm */
+    const float* scale0; /* [B][mod_bstride] f32, row b = row_map ? row_map[row] : row / rows_per_batch; NULL with shift0 NULL: the plain norm */
     const float* shift0;
     const float* scale1;
     const float* shift1;
@@ -459,10 +464,11 @@ typedef struct ltx_norm_mod2_job {
     long ldo;
     int rows; /* 0: the job is empty */
     int D;    /* D % 4 == 0, <= 8192 */
+    const int32_t* row_map; /* DEVICE [rows] int32 or NULL: the modulation row of each row (per-token timestep groups) */
 } ltx_norm_mod2_job;
 /* Kernel hook: the cross-modal norms of the dual block in one launch (audioToVideoNorm / videoToAudioNorm and their four modulations,
  * LTX2TransformerBlock.swift:246-263). out0 = rmsnorm(x) * (1 + scale0) + shift0, out1 likewise with (scale1, shift1); each bit-equal
- * to ltx_op_norm_mod_ex with the same operands. Either job may be NULL or empty. Bad arguments are refused before the launch. */
+ * to ltx_op_norm_mod_ex with the same operands and the same row map. Either job may be NULL or empty. Bad arguments are refused before the launch. */
 int ltx_op_norm_mod2(ltx_ctx* ctx, const ltx_norm_mod2_job* video, const ltx_norm_mod2_job* audio, float eps);
 
 /* ------------------------------------------------------------------------------------------------------------
@@ -470,9 +476,10 @@ int ltx_op_norm_mod2(ltx_ctx* ctx, const ltx_norm_mod2_job* video, const ltx_nor
  * timestep vectors in, two velocities out. The model owns a block stack of its own (as "Dual video + audio transformer blocks" above)
  * and the top-level modules of LTX2Transformer.swift:28-48: the two patchify Linears, the six AdaLayerNormSingle embedders, the two
  * caption projections, the two output tables and the two output Linears. A context holds one model, in a slot of its own: loading it
- * does not disturb the ltx_dual_blocks_* stack, and the reverse. Timesteps are one value per batch element and stream; the reference's
- * per-token form (image-to-video, LTX2Transformer.swift:285-312) is not implemented, and the CLI's --audio path is not part of this
- * library yet. Within one prompt the text side of a forward does not change: ltx_dual_model_prepare_text_dev computes it once (both
+ * does not disturb the ltx_dual_blocks_* stack, and the reverse. Timesteps are one value per batch element and stream in
+ * ltx_dual_model_forward_dev; ltx_dual_model_forward_groups_dev takes video timesteps per (batch element, timestep group) and a token ->
+ * group map, which is the reference's per-token form (image-to-video, LTX2Transformer.swift:285-312). The CLI's --audio path is not
+ * part of this library yet. Within one prompt the text side of a forward does not change: ltx_dual_model_prepare_text_dev computes it once (both
  * caption projections, both mask biases and, for every block, the normed K and the V^T of the two text cross-attentions) and a forward
  * with text_cache != 0 reads it. The joint denoise loop is ltx_dual_denoise below.
  * ---------------------------------------------------------------------------------------------------------- */
@@ -531,6 +538,14 @@ typedef struct ltx_dual_model_forward_args {
  * it) without a cache of this call's (B, S): LTX_ERR_INVALID_CONFIGURATION. Every check comes before the first launch: a refused call
  * writes nothing. */
 int ltx_dual_model_forward_dev(ltx_ctx* ctx, const ltx_dual_model_forward_args* args);
+/* The same forward with timestep GROUPS on the video stream (image-to-video: frame-0 tokens at 0, the rest at sigma): the tokens of
+ * batch element b are partitioned into n_groups groups, args->video_timesteps is read as [B][n_groups], and video_row_map (DEVICE,
+ * [B*F*H*W] int32) holds b*n_groups + group(b, t) for token t of batch element b; entries are the caller's contract, as in
+ * ltx_dit_forward_dev. Every video modulation row - adaLN, both cross-modal embedders (av_ca_video_scale_shift, av_ca_a2v_gate) and the
+ * output head - is built once per (b, group) and picked per token through the map; audio timesteps stay [B]. n_groups == 1 with a NULL
+ * map IS ltx_dual_model_forward_dev. n_groups < 1, B * n_groups > 8 or n_groups > 1 without a map: LTX_ERR_INVALID_CONFIGURATION before
+ * the first launch, nothing written. Works with text_cache 0 and 1. */
+int ltx_dual_model_forward_groups_dev(ltx_ctx* ctx, const ltx_dual_model_forward_args* args, int n_groups, const int32_t* video_row_map);
 /* The timestep path of the forward alone (LTX2Transformer.swift:272-312), into caller buffers: temb_v [B][6][video_dim], temb_a
  * [B][6][audio_dim], cross_v [B][5][video_dim], cross_a [B][5][audio_dim] (rows 0-3 from the scale-shift embedder, row 4 from the
  * gate embedder), embts_v [B][video_dim], embts_a [B][audio_dim] (the embedded timesteps of the output heads), all f32 DEVICE
@@ -560,11 +575,18 @@ typedef struct ltx_dual_step_job {
     int copies;            /* 1 or 2 (a B = 2 CFG forward reads the same tokens twice) */
     float* v_out;          /* [n] f32 or NULL: the guided velocity; may alias v_cond */
     long n;                /* elements; n % 4 == 0; 0: the job is empty */
+    long n_keep;           /* frozen prefix (image-to-video: frame 0 in token layout): elements i < n_keep skip the Euler form. 0: none */
+    const float* keep_src; /* [n_keep] f32: the conditioning latent in token layout; needed with keep_noise */
+    const float* keep_noise; /* [n_keep] f32: x' = keep_src + (keep_scale * keep_noise) * (sigma_next * sigma_next), four separately
+                                rounded f32 operations - the prefix as the NEXT forward must see it (LTXPipeline.swift:1289-1294). NULL: x' = x */
+    float keep_scale;
 } ltx_dual_step_job;
 /* Kernel hook: CFG (LatentUtils.swift:131-141), the Euler step and the bf16 cast of both streams in one launch. Every operation is
  * rounded on its own (no fused multiply-add, correctly rounded division), as the reference's separate array ops are: latent and v_out
  * are bit-equal to a float32 replay of those ops. Either job may be NULL or empty. n % 4 != 0, copies outside 1 .. 2, form outside
- * 0 .. 1, a NULL latent / v_cond / tokens with n > 0, or sigma <= 0: LTX_ERR_INVALID_CONFIGURATION before the launch, nothing written. */
+ * 0 .. 1, a NULL latent / v_cond / tokens with n > 0, or sigma <= 0: LTX_ERR_INVALID_CONFIGURATION before the launch, nothing written.
+ * With a frozen prefix the tokens (both copies) and v_out are still written for the whole job. n_keep % 4 != 0, n_keep outside 0 .. n or
+ * keep_noise without keep_src are refused the same way; n_keep = 0 is the step without a prefix, bit for bit. */
 int ltx_op_dual_step(ltx_ctx* ctx, const ltx_dual_step_job* video, const ltx_dual_step_job* audio, float sigma, float sigma_next);
 
 /* ------------------------------------------------------------------------------------------------------------
@@ -690,13 +712,22 @@ typedef struct ltx_dual_denoise_args {
     int text_cache;                /* non-zero (default): the text side is computed once; 0 recomputes it every step. The same bits */
     float* step_stats;             /* HOST, 8 * (n_sigmas - 1) floats or NULL: per step mean and std of the video velocity, the video
                                       latent, the audio velocity and the audio latent. Non-NULL makes the _dev call synchronous */
+    /* image-to-video, with the meanings, layouts and memory space of the same fields of ltx_denoise_options; read when struct_size covers them */
+    const float* cond_latent;      /* [1][in_channels][1][H][W] f32 or NULL (text-to-video): the encoded image; needs F >= 2 */
+    float image_cond_noise_scale;  /* > 0 with cond_noise: frame 0 is re-noised at the start of every step (LTXPipeline.swift:1289-1294) */
+    const float* cond_noise;       /* [n_sigmas - 1][in_channels][1][H][W] f32 or NULL: the caller's draws, one slice per step */
 } ltx_dual_denoise_args;
-#define LTX_DUAL_DENOISE_ARGS_INIT {(uint32_t)sizeof(ltx_dual_denoise_args), 0, 0, 0, 0, 0, NULL, NULL, NULL, 0, NULL, NULL, NULL, 1.0f, 0.0f, 1, NULL}
-/* Replaces the denoise loop of generateVideoWithAudio (LTXPipeline.swift:1276-1417), text-to-video+audio: per step the progress
+#define LTX_DUAL_DENOISE_ARGS_INIT {(uint32_t)sizeof(ltx_dual_denoise_args), 0, 0, 0, 0, 0, NULL, NULL, NULL, 0, NULL, NULL, NULL, 1.0f, 0.0f, 1, NULL, NULL, 0.0f, NULL}
+/* Replaces the denoise loop of generateVideoWithAudio (LTXPipeline.swift:1276-1417), text-to-video+audio and (cond_latent set)
+ * image-to-video+audio: per step the progress
  * callback, ONE dual-model forward (B = 2 on [negative, positive] with CFG), optional guidance rescale of the video velocity, and ONE
  * launch for CFG + both Euler steps + the next forward's tokens (ltx_op_dual_step; video form 0, audio form 1). Both latents are held in
  * token layout for the whole loop and transposed once at entry and once at exit. Noise is the caller's (video first, then audio,
- * :1229-1236). Image-to-video, STG, GE, the two-stage path and sharding are not implemented here. DEVICE pointers except sigmas and
+ * :1229-1236). Image-to-video (:1261-1274, :1289-1303, :1383-1399): frame 0 of the latent is set to cond_latent at entry, its tokens run
+ * at timestep 0 (two timestep groups, ltx_dual_model_forward_groups_dev), it is never stepped, and with re-noising it holds cond +
+ * (scale * noise[step]) * sigma^2 during step `step` - written by the step launch of the step before, so no launch is added per step;
+ * the result's frame 0 is the last step's noised frame, or cond_latent itself without re-noising. F < 2 with cond_latent:
+ * LTX_ERR_INVALID_CONFIGURATION. STG, GE, the two-stage path and sharding are not implemented here. DEVICE pointers except sigmas and
  * step_stats; asynchronous on the context stream unless step_stats is set. No dual model: LTX_ERR_MODEL_NOT_LOADED; a short struct_size,
  * n_sigmas < 2, a dimension < 1, a NULL latent / sigmas / video_context, a sigma <= 0 before the last, or guidance_rescale > 0 without
  * CFG: LTX_ERR_INVALID_CONFIGURATION. Every check comes before the first launch: a refused call leaves both latents untouched. */

@@ -339,6 +339,35 @@ ATTN_QUERY_PRESCALE_64 = float(np.float32(0.125) * np.float32(1.4426950408889634
 # ---------------------------------------------------------------------------------------------------------------
 # device context
 # ---------------------------------------------------------------------------------------------------------------
+def timestep_groups(token_timesteps):
+    """Per-token timesteps [B][T] -> (ts [B][G] f32, row_map [B*T] int32) for ``dual_model_forward_groups_dev``: the distinct values of
+    each batch element in order of first appearance (as ``ltx_dit_forward_tokens`` groups them), G = the largest count, unused slots
+    repeat the element's first value; row_map[b*T + t] = b*G + group(b, t). More than 8 rows in all (B * G > 8) is refused."""
+    tt = np.ascontiguousarray(token_timesteps, dtype=np.float32)
+    if tt.ndim != 2 or tt.shape[0] < 1 or tt.shape[1] < 1:
+        raise ValueError("timestep_groups: token_timesteps must be [B][T]")
+    B, T = tt.shape
+    values, groups = [], np.zeros((B, T), np.int32)
+    for b in range(B):
+        vals = []
+        for t in range(T):
+            v = tt[b, t]
+            for g, u in enumerate(vals):
+                if u == v:
+                    break
+            else:
+                g = len(vals)
+                vals.append(v)
+                if B * len(vals) > 8:
+                    raise ValueError(f"timestep_groups: more than {8 // B} distinct timesteps in batch element {b} (B * G <= 8)")
+            groups[b, t] = g
+        values.append(vals)
+    G = max(len(v) for v in values)
+    ts = np.stack([np.array(v + [v[0]] * (G - len(v)), np.float32) for v in values])
+    row_map = (groups + (np.arange(B, dtype=np.int32) * G)[:, None]).astype(np.int32).reshape(-1)
+    return ts, row_map
+
+
 def _ptr(t):
     """Device/host pointer of a torch tensor or numpy array (None -> NULL)."""
     if t is None:
@@ -953,9 +982,11 @@ class Context:
         return out
 
     def dual_blocks_forward_dev(self, x_video, x_audio, context_video, context_audio, temb_video, temb_audio, cross_video_ss, cross_audio_ss,
-                                F, H, W, key_bias_video=None, key_bias_audio=None, phase_mask=0, struct_size=None, T_a=None):
+                                F, H, W, key_bias_video=None, key_bias_audio=None, phase_mask=0, struct_size=None, T_a=None, n_groups=1,
+                                video_row_map=None):
         """``ltx_dual_blocks_forward_dev``: device tensors; x_video [B][F*H*W][Dv] and x_audio [B][T_a][Da] f32 are updated in place,
-        the contexts [B][S][.] are bf16, temb_* [B][6][D], cross_*_ss [B][5][D] f32, key biases [B][S] f32 or None."""
+        the contexts [B][S][.] are bf16, temb_* [B][6][D], cross_*_ss [B][5][D] f32, key biases [B][S] f32 or None. With timestep groups
+        (``n_groups`` > 1, ``video_row_map`` [B*F*H*W] int32) temb_video / cross_video_ss have B * n_groups rows."""
         a = DualForwardArgs()
         a.struct_size = C.sizeof(DualForwardArgs) if struct_size is None else struct_size
         a.B, a.F, a.H, a.W = x_video.shape[0], F, H, W
@@ -967,6 +998,7 @@ class Context:
         a.temb_video, a.temb_audio = _ptr(temb_video), _ptr(temb_audio)
         a.cross_video_ss, a.cross_audio_ss = _ptr(cross_video_ss), _ptr(cross_audio_ss)
         a.phase_mask = phase_mask
+        a.n_groups, a.video_row_map = n_groups, _ptr(video_row_map)
         self._ck(lib.ltx_dual_blocks_forward_dev(self._h, C.byref(a)))
 
     # ---- LTX2Transformer: the dual video + audio model ----
@@ -990,9 +1022,16 @@ class Context:
             raise LTXError(-n2, lib.ltx_last_error(self._h).decode(errors="replace"))
         return out
 
+    def dual_model_forward_groups_dev(self, video_latent, audio_latent, video_context, audio_context, video_timesteps, audio_timesteps,
+                                      video_velocity, audio_velocity, F, H, W, n_groups, video_row_map, **kw):
+        """``ltx_dual_model_forward_groups_dev``: ``dual_model_forward_dev`` with timestep groups on the video stream: video_timesteps
+        [B][n_groups] f32, video_row_map [B*F*H*W] int32 (b * n_groups + group) or None with one group; see ``timestep_groups``."""
+        self.dual_model_forward_dev(video_latent, audio_latent, video_context, audio_context, video_timesteps, audio_timesteps, video_velocity,
+                                    audio_velocity, F, H, W, _groups=(int(n_groups), video_row_map), **kw)
+
     def dual_model_forward_dev(self, video_latent, audio_latent, video_context, audio_context, video_timesteps, audio_timesteps,
                                video_velocity, audio_velocity, F, H, W, video_mask=None, audio_mask=None, ungrouped=False, struct_size=None,
-                               T_a=None, text_cache=0, S=None):
+                               T_a=None, text_cache=0, S=None, _groups=None):
         """``ltx_dual_model_forward_dev``: device tensors; latents [B][T][C] and contexts [B][S][caption_channels] bf16, timesteps [B] f32
         (sigma), masks [B][S] int32 or None; the velocities [B][F*H*W][out_channels] / [B][T_a][audio_out_channels] f32 are written.
         ``text_cache`` non-zero reads the text side from ``dual_model_prepare_text``: the contexts and masks may be None (give ``S``)."""
@@ -1008,6 +1047,9 @@ class Context:
         a.video_mask, a.audio_mask = _ptr(video_mask), _ptr(audio_mask)
         a.video_velocity, a.audio_velocity = _ptr(video_velocity), _ptr(audio_velocity)
         a.ungrouped = int(ungrouped)
+        if _groups is not None:
+            self._ck(lib.ltx_dual_model_forward_groups_dev(self._h, C.byref(a), _groups[0], _ptr(_groups[1])))
+            return
         self._ck(lib.ltx_dual_model_forward_dev(self._h, C.byref(a)))
 
     def dual_model_embed_dev(self, video_timesteps, audio_timesteps, temb_v, temb_a, cross_v, cross_a, embts_v, embts_a, ungrouped=False, B=None):
@@ -1030,7 +1072,7 @@ class Context:
 
     @staticmethod
     def _dual_denoise_args(video_latent, audio_latent, sg, video_context, audio_context, mask, F, H, W, T_a, S, cfg_scale, guidance_rescale,
-                           text_cache, stats, struct_size):
+                           text_cache, stats, struct_size, cond_latent=None, image_cond_noise_scale=0.0, cond_noise=None):
         a = DualDenoiseArgs()
         a.struct_size = C.sizeof(DualDenoiseArgs) if struct_size is None else struct_size
         a.F, a.H, a.W, a.T_a, a.S = F, H, W, T_a, S
@@ -1039,26 +1081,32 @@ class Context:
         a.video_context, a.audio_context, a.mask = _ptr(video_context), _ptr(audio_context), _ptr(mask)
         a.cfg_scale, a.guidance_rescale, a.text_cache = cfg_scale, guidance_rescale, int(text_cache)
         a.step_stats = None if stats is None else stats.ctypes.data
+        a.cond_latent, a.image_cond_noise_scale, a.cond_noise = _ptr(cond_latent), image_cond_noise_scale, _ptr(cond_noise)
         return a
 
     def dual_denoise_dev(self, video_latent, audio_latent, sigmas_, video_context, F, H, W, audio_context=None, mask=None, cfg_scale=1.0,
-                         guidance_rescale=0.0, text_cache=1, step_stats=False, on_progress=None, T_a=None, S=None, struct_size=None):
+                         guidance_rescale=0.0, text_cache=1, step_stats=False, on_progress=None, T_a=None, S=None, struct_size=None,
+                         cond_latent=None, image_cond_noise_scale=0.0, cond_noise=None):
         """``ltx_dual_denoise_dev``: the joint loop on device tensors, in place. video_latent [1][C][F][H][W] f32 and audio_latent
         [1][8][T_a][16] f32, scaled by sigmas[0]; contexts [nb][S][caption_channels] bf16, nb = 2 ([negative, positive]) iff cfg_scale > 1;
-        mask [nb][S] int32 or None. Returns the step statistics [steps][8] when ``step_stats``, else None."""
+        mask [nb][S] int32 or None. Image-to-video: cond_latent [1][C][1][H][W] f32 and, for re-noising, image_cond_noise_scale > 0 with
+        cond_noise [steps][C][1][H][W] f32. Returns the step statistics [steps][8] when ``step_stats``, else None."""
         sg = np.ascontiguousarray(sigmas_, dtype=np.float32)
         cb = PROGRESS_CB(on_progress if on_progress else (lambda s, t, sig, u: None))
         stats = np.zeros((max(len(sg) - 1, 0), 8), np.float32) if step_stats else None
         a = self._dual_denoise_args(video_latent, audio_latent, sg, video_context, audio_context, mask, F, H, W,
                                     audio_latent.shape[2] if T_a is None else T_a, video_context.shape[1] if S is None else S, cfg_scale,
-                                    guidance_rescale, text_cache, stats, struct_size)
+                                    guidance_rescale, text_cache, stats, struct_size, cond_latent, image_cond_noise_scale, cond_noise)
         self._ck(lib.ltx_dual_denoise_dev(self._h, C.byref(a), cb, None))
         return stats
 
     def dual_denoise(self, video_latent, audio_latent, sigmas_, video_context_bf16, F, H, W, audio_context_bf16=None, mask=None, cfg_scale=1.0,
-                     guidance_rescale=0.0, text_cache=1, step_stats=False, on_progress=None):
-        """``ltx_dual_denoise``: the same with host arrays (contexts as bf16 bit patterns, uint16). Returns (video_latent, audio_latent)
-        or, with ``step_stats``, (video_latent, audio_latent, stats)."""
+                     guidance_rescale=0.0, text_cache=1, step_stats=False, on_progress=None, cond_latent=None, image_cond_noise_scale=0.0,
+                     cond_noise=None):
+        """``ltx_dual_denoise``: the same with host arrays (contexts as bf16 bit patterns, uint16; cond_latent / cond_noise f32). Returns
+        (video_latent, audio_latent) or, with ``step_stats``, (video_latent, audio_latent, stats)."""
+        cl = None if cond_latent is None else np.ascontiguousarray(cond_latent, dtype=np.float32)
+        cn = None if cond_noise is None else np.ascontiguousarray(cond_noise, dtype=np.float32)
         v = np.ascontiguousarray(video_latent, dtype=np.float32).copy()
         au = np.ascontiguousarray(audio_latent, dtype=np.float32).copy()
         sg = np.ascontiguousarray(sigmas_, dtype=np.float32)
@@ -1067,18 +1115,20 @@ class Context:
         mk = None if mask is None else np.ascontiguousarray(mask, dtype=np.int32)
         cb = PROGRESS_CB(on_progress if on_progress else (lambda s, t, sig, u: None))
         stats = np.zeros((max(len(sg) - 1, 0), 8), np.float32) if step_stats else None
-        a = self._dual_denoise_args(v, au, sg, cv, ca, mk, F, H, W, au.shape[2], cv.shape[1], cfg_scale, guidance_rescale, text_cache, stats, None)
+        a = self._dual_denoise_args(v, au, sg, cv, ca, mk, F, H, W, au.shape[2], cv.shape[1], cfg_scale, guidance_rescale, text_cache, stats, None,
+                                    cl, image_cond_noise_scale, cn)
         self._ck(lib.ltx_dual_denoise(self._h, C.byref(a), cb, None))
         return (v, au, stats) if step_stats else (v, au)
 
     def op_dual_step(self, video=None, audio=None, sigma=1.0, sigma_next=0.0):
         """``ltx_op_dual_step``: each job is None or a dict(latent=, v_cond=, tokens= tensors, v_uncond=None, v_out=None, cfg_scale=1.0,
-        form=0, copies=1, n= latent.numel())."""
+        form=0, copies=1, n= latent.numel(), n_keep=0, keep_src=None, keep_noise=None, keep_scale=0.0)."""
         def job(j):
             if j is None:
                 return None
             o = DualStepJob()
-            for k in ("latent", "v_cond", "v_uncond", "tokens", "v_out"):
+            o.n_keep, o.keep_scale = j.get("n_keep", 0), j.get("keep_scale", 0.0)
+            for k in ("latent", "v_cond", "v_uncond", "tokens", "v_out", "keep_src", "keep_noise"):
                 t = j.get(k)
                 setattr(o, k, None if t is None else t.data_ptr())
             o.cfg_scale, o.form, o.copies = j.get("cfg_scale", 1.0), j.get("form", 0), j.get("copies", 1)
@@ -1105,7 +1155,7 @@ class Context:
 
     def op_norm_mod2(self, video=None, audio=None, eps=1e-6):
         """``ltx_op_norm_mod2``: each job is None or a dict(x=, out0=, out1= 2-D tensors whose row strides are ldx / ldo, rows=, D=,
-        scale0=, shift0=, scale1=, shift1= (tensors or None), mod_bstride=0, rows_per_batch=rows)."""
+        scale0=, shift0=, scale1=, shift1= (tensors or None), mod_bstride=0, rows_per_batch=rows, row_map=None ([rows] int32))."""
         def job(j):
             if j is None:
                 return None
@@ -1117,6 +1167,7 @@ class Context:
             o.rows_per_batch = j.get("rows_per_batch", max(1, j["rows"]))
             o.out0, o.out1, o.ldo = j["out0"].data_ptr(), j["out1"].data_ptr(), j["out0"].stride(0)
             o.rows, o.D = j["rows"], j["D"]
+            o.row_map = _ptr(j.get("row_map"))
             return C.byref(o)
         self._ck(lib.ltx_op_norm_mod2(self._h, job(video), job(audio), eps))
 

@@ -74,7 +74,8 @@ class DualForwardArgs(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("B", C.c_int), ("F", C.c_int), ("H", C.c_int), ("W", C.c_int), ("T_a", C.c_int), ("S", C.c_int),
                 ("x_video", C.c_void_p), ("x_audio", C.c_void_p), ("context_video", C.c_void_p), ("context_audio", C.c_void_p),
                 ("key_bias_video", C.c_void_p), ("key_bias_audio", C.c_void_p), ("temb_video", C.c_void_p), ("temb_audio", C.c_void_p),
-                ("cross_video_ss", C.c_void_p), ("cross_audio_ss", C.c_void_p), ("phase_mask", C.c_uint32)]
+                ("cross_video_ss", C.c_void_p), ("cross_audio_ss", C.c_void_p), ("phase_mask", C.c_uint32), ("n_groups", C.c_int),
+                ("video_row_map", C.c_void_p)]
 
 
 class GemvJob(C.Structure):
@@ -116,14 +117,15 @@ class NormMod2Job(C.Structure):
 
     _fields_ = [("x", C.c_void_p), ("ldx", C.c_long), ("scale0", C.c_void_p), ("shift0", C.c_void_p), ("scale1", C.c_void_p),
                 ("shift1", C.c_void_p), ("mod_bstride", C.c_long), ("rows_per_batch", C.c_int), ("out0", C.c_void_p), ("out1", C.c_void_p),
-                ("ldo", C.c_long), ("rows", C.c_int), ("D", C.c_int)]
+                ("ldo", C.c_long), ("rows", C.c_int), ("D", C.c_int), ("row_map", C.c_void_p)]
 
 
 class DualStepJob(C.Structure):
     """``ltx_dual_step_job``: one job of ``ltx_op_dual_step``."""
 
     _fields_ = [("latent", C.c_void_p), ("v_cond", C.c_void_p), ("v_uncond", C.c_void_p), ("cfg_scale", C.c_float), ("form", C.c_int),
-                ("tokens", C.c_void_p), ("copies", C.c_int), ("v_out", C.c_void_p), ("n", C.c_long)]
+                ("tokens", C.c_void_p), ("copies", C.c_int), ("v_out", C.c_void_p), ("n", C.c_long), ("n_keep", C.c_long),
+                ("keep_src", C.c_void_p), ("keep_noise", C.c_void_p), ("keep_scale", C.c_float)]
 
 
 class DualDenoiseArgs(C.Structure):
@@ -132,7 +134,8 @@ class DualDenoiseArgs(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("F", C.c_int), ("H", C.c_int), ("W", C.c_int), ("T_a", C.c_int), ("S", C.c_int),
                 ("video_latent", C.c_void_p), ("audio_latent", C.c_void_p), ("sigmas", C.POINTER(C.c_float)), ("n_sigmas", C.c_int),
                 ("video_context", C.c_void_p), ("audio_context", C.c_void_p), ("mask", C.c_void_p), ("cfg_scale", C.c_float),
-                ("guidance_rescale", C.c_float), ("text_cache", C.c_int), ("step_stats", C.c_void_p)]
+                ("guidance_rescale", C.c_float), ("text_cache", C.c_int), ("step_stats", C.c_void_p), ("cond_latent", C.c_void_p),
+                ("image_cond_noise_scale", C.c_float), ("cond_noise", C.c_void_p)]
 
 
 def _load():
@@ -295,6 +298,7 @@ SIGNATURES = {
     "ltx_dual_model_unload": (_i, [_vp]),
     "ltx_dual_model_export_param": (_l, [_vp, C.c_char_p, _vp, _l]),
     "ltx_dual_model_forward_dev": (_i, [_vp, C.POINTER(DualModelForwardArgs)]),
+    "ltx_dual_model_forward_groups_dev": (_i, [_vp, C.POINTER(DualModelForwardArgs), _i, _vp]),
     "ltx_dual_model_embed_dev": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ltx_dual_model_prepare_text_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i]),
     "ltx_dual_model_text_cache_info": (_i, [_vp, _ip, _ip, C.POINTER(_l), C.POINTER(_l)]),

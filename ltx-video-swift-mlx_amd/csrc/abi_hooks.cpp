@@ -396,7 +396,7 @@ int ltx_op_norm_mod2(ltx_ctx* ctx, const ltx_norm_mod2_job* video, const ltx_nor
             o.scale0 = j->scale0; o.shift0 = j->shift0; o.scale1 = j->scale1; o.shift1 = j->shift1;
             o.mod_bstride = j->mod_bstride; o.rows_per_batch = j->rows_per_batch;
             o.out0 = j->out0; o.out1 = j->out1; o.ldo = j->ldo;
-            o.rows = j->rows; o.D = j->D;
+            o.rows = j->rows; o.D = j->D; o.row_map = j->row_map;
             return o;
         };
         launch_norm_mod2(job(video), job(audio), eps, ctx->stream);
@@ -411,6 +411,7 @@ int ltx_op_dual_step(ltx_ctx* ctx, const ltx_dual_step_job* video, const ltx_dua
             o.latent = j->latent; o.v_cond = j->v_cond; o.v_uncond = j->v_uncond;
             o.cfg_scale = j->cfg_scale; o.form = j->form;
             o.tokens = j->tokens; o.copies = j->copies; o.v_out = j->v_out; o.n = j->n;
+            o.n_keep = j->n_keep; o.keep_src = j->keep_src; o.keep_noise = j->keep_noise; o.keep_scale = j->keep_scale;
             return o;
         };
         launch_dual_step(job(video), job(audio), sigma, sigma_next, ctx->stream);

@@ -924,6 +924,8 @@ int ltx_dual_blocks_forward_dev(ltx_ctx* ctx, const ltx_dual_forward_args* args)
         a.temb_video = args->temb_video; a.temb_audio = args->temb_audio;
         a.cross_video_ss = args->cross_video_ss; a.cross_audio_ss = args->cross_audio_ss;
         if (sz >= offsetof(ltx_dual_forward_args, phase_mask) + sizeof(args->phase_mask)) a.phase_mask = args->phase_mask;
+        if (sz >= offsetof(ltx_dual_forward_args, n_groups) + sizeof(args->n_groups)) a.n_groups = args->n_groups;
+        if (sz >= offsetof(ltx_dual_forward_args, video_row_map) + sizeof(args->video_row_map)) a.video_row_map = args->video_row_map;
         dual_forward(ctx, m, a);
     });
 }
@@ -961,6 +963,9 @@ long ltx_dual_model_export_param(ltx_ctx* ctx, const char* name, float* out, lon
                              [&] { return dual_model_find(need(ctx->dual_model, kNoDualModel), name); });
 }
 int ltx_dual_model_forward_dev(ltx_ctx* ctx, const ltx_dual_model_forward_args* args) {
+    return ltx_dual_model_forward_groups_dev(ctx, args, 1, nullptr);
+}
+int ltx_dual_model_forward_groups_dev(ltx_ctx* ctx, const ltx_dual_model_forward_args* args, int n_groups, const int32_t* video_row_map) {
     if (!ctx) return LTX_ERR_INVALID_CONFIGURATION;
     return guarded(ctx, [&] {
         LTX_REQUIRE(args != nullptr, "ltx_dual_model_forward_dev: null arguments");
@@ -978,6 +983,7 @@ int ltx_dual_model_forward_dev(ltx_ctx* ctx, const ltx_dual_model_forward_args* 
         a.video_velocity = args->video_velocity; a.audio_velocity = args->audio_velocity;
         if (sz >= offsetof(ltx_dual_model_forward_args, ungrouped) + sizeof(args->ungrouped)) a.ungrouped = args->ungrouped;
         if (sz >= offsetof(ltx_dual_model_forward_args, text_cache) + sizeof(args->text_cache)) a.text_cache = args->text_cache;
+        a.n_groups = n_groups; a.video_row_map = video_row_map;
         dual_model_forward(ctx, m, a);
     });
 }
@@ -1023,6 +1029,10 @@ void dual_denoise_params(ltx_ctx* ctx, const ltx_dual_denoise_args* args, ltx_pr
     p.cfg_scale = args->cfg_scale; p.guidance_rescale = args->guidance_rescale;
     p.text_cache = args->text_cache; p.step_stats = args->step_stats;
     p.progress = cb; p.user = user;
+    if (sz >= offsetof(ltx_dual_denoise_args, cond_latent) + sizeof(args->cond_latent)) p.cond_latent = args->cond_latent;
+    if (sz >= offsetof(ltx_dual_denoise_args, image_cond_noise_scale) + sizeof(args->image_cond_noise_scale))
+        p.image_cond_noise_scale = args->image_cond_noise_scale;
+    if (sz >= offsetof(ltx_dual_denoise_args, cond_noise) + sizeof(args->cond_noise)) p.cond_noise = args->cond_noise;
 }
 }  // namespace
 
@@ -1045,6 +1055,7 @@ int ltx_dual_denoise(ltx_ctx* ctx, const ltx_dual_denoise_args* args, ltx_progre
                     "ltx_dual_denoise: bad arguments");
         LTX_REQUIRE(!(p.guidance_rescale > 0.f) || p.cfg_scale > 1.0f, "ltx_dual_denoise: guidance_rescale needs cfg_scale > 1");
         for (int i = 0; i + 1 < p.n_sigmas; ++i) LTX_REQUIRE(p.sigmas[i] > 0.f, "ltx_dual_denoise: sigmas[%d] must be positive", i);
+        LTX_REQUIRE(!p.cond_latent || p.F >= 2, "ltx_dual_denoise: image-to-video needs at least two latent frames (F=%d)", p.F);
         const int nb = p.cfg_scale > 1.0f ? 2 : 1;
         const size_t n_v = (size_t)m->cfg.in_channels * p.F * p.H * p.W * 4, n_a = (size_t)128 * p.T_a * 4;
         const size_t n_ctx = (size_t)nb * p.S * m->cfg.caption_channels * 2, n_mask = (size_t)nb * p.S * 4;
@@ -1061,6 +1072,16 @@ int ltx_dual_denoise(ltx_ctx* ctx, const ltx_dual_denoise_args* args, ltx_progre
         p.video_context = d_cv.as<bf16_t>();
         p.audio_context = p.audio_context ? d_ca.as<bf16_t>() : nullptr;
         p.mask = p.mask ? d_mask.as<int32_t>() : nullptr;
+        if (p.cond_latent) {  // the image latent and its re-noising slices, as ltx_denoise stages them
+            const size_t n_c = (size_t)m->cfg.in_channels * p.H * p.W * 4;
+            DevBuf &d_c = ctx->i2v_cond, &d_n = ctx->i2v_noise;
+            stage_in(ctx, d_c, p.cond_latent, n_c);
+            p.cond_latent = d_c.as<float>();
+            if (p.cond_noise) {
+                stage_in(ctx, d_n, p.cond_noise, n_c * (size_t)(p.n_sigmas - 1));
+                p.cond_noise = d_n.as<float>();
+            }
+        }
         dual_denoise_run(ctx, p);
         stage_out(ctx, host_v, d_v, n_v);
         stage_out(ctx, host_a, d_a, n_a);

@@ -333,6 +333,7 @@ void attn_module_core(ltx_ctx* ctx, AttnModule* m, const AttnCoreArgs& a, AttnCo
     eo.resid = 1;
     eo.gate = a.gate;
     eo.gate_bstride = a.gate_bstride;
+    eo.gate_rowmap = a.gate_rowmap;
     eo.rows_per_batch = Tq;
     gemm_linear(ao, I, m->o, (int)qrows, eo, st, sk);
 }

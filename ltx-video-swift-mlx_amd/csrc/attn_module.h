@@ -92,6 +92,7 @@ struct AttnCoreArgs {
     float* x = nullptr;            // [B][Tq][Dq] f32 stream: x += gate * to_out(attention)
     const float* gate = nullptr;   // [B][gate_bstride] rows, Dq valid columns; null = plain residual
     long gate_bstride = 0;
+    const int32_t* gate_rowmap = nullptr;  // optional [B*Tq]: gate row of query row m = gate_rowmap[m] (per-token timestep groups)
     float* split_ws = nullptr;     // optional split-K workspace of the GEMMs (floats)
     long split_ws_elems = 0;
     // K and V^T of a context that does not change between calls (attn_module_build_kv made them): both set = the k GEMM, k's norm pass

@@ -166,11 +166,11 @@ void ensure_rope(ltx_ctx* ctx, DualStack* m, int F, int H, int W, int Ta) {
 }
 
 // adaLN / FFN phase of one stream (phases 7 and 8): x += gate * ff2(gelu(ff1(norm(x) * (1 + scale) + shift)))
-void ffn_phase(float* x, int D, int T, long rows, const float* mod, long mod_bs, const LinearW& ff1, const LinearW& ff2, bf16_t* xn, bf16_t* ffh,
-               float eps, const SplitWs& sk, hipStream_t st) {
+void ffn_phase(float* x, int D, int T, long rows, const float* mod, long mod_bs, const int32_t* rmap, const LinearW& ff1, const LinearW& ff2,
+               bf16_t* xn, bf16_t* ffh, float eps, const SplitWs& sk, hipStream_t st) {
     NormModArgs n;
     n.x = x; n.ldx = D;
-    n.scale = mod + 4L * D; n.shift = mod + 3L * D; n.mod_bstride = mod_bs; n.rows_per_batch = T;
+    n.scale = mod + 4L * D; n.shift = mod + 3L * D; n.mod_bstride = mod_bs; n.rows_per_batch = T; n.row_map = rmap;
     n.out = xn; n.ldo = D;
     n.rows = (int)rows; n.D = D; n.eps = eps;
     launch_norm_mod(n, st);
@@ -186,6 +186,7 @@ void ffn_phase(float* x, int D, int T, long rows, const float* mod, long mod_bs,
     e2.gate = mod + 5L * D;
     e2.gate_bstride = mod_bs;
     e2.rows_per_batch = T;
+    e2.gate_rowmap = rmap;
     gemm_linear(ffh, 4L * D, ff2, (int)rows, e2, st, sk);
 }
 
@@ -241,6 +242,11 @@ void dual_forward(ltx_ctx* ctx, DualStack* m, const DualForwardArgs& a) {
     if (tc && (tc->B != B || tc->S != S || !tc->buf.p))
         LTX_THROW(LTXS_INVALID_CONFIGURATION, "dual blocks forward: the text cache holds B=%d S=%d, the call has B=%d S=%d", tc->B, tc->S, B, S);
     if (a.phase_mask > 0xffu) LTX_THROW(LTXS_INVALID_CONFIGURATION, "dual blocks forward: phase_mask 0x%x has bits beyond the eight phases", a.phase_mask);
+    const int G = a.n_groups;
+    if (G < 1 || (long)B * G > 8 || (G > 1 && !a.video_row_map))
+        LTX_THROW(LTXS_INVALID_CONFIGURATION, "dual blocks forward: n_groups=%d (B * n_groups = 1 .. 8; more than one group needs video_row_map)", G);
+    const int32_t* rmap = a.video_row_map;  // null: one video modulation row per batch element
+    const int BG = B * G;
     const unsigned phases = a.phase_mask ? a.phase_mask : 0xffu;
     auto on = [&](int p) { return (phases >> (p - 1)) & 1u; };
     const int Tv = a.F * a.H * a.W;
@@ -264,9 +270,9 @@ void dual_forward(ltx_ctx* ctx, DualStack* m, const DualForwardArgs& a) {
         m->ws_ffh.ensure((size_t)std::max(vrows * 4 * Dv, arows * 4 * Da) * 2);
         m->ws_splitk.ensure((size_t)8 << 22);
         if (!a.bias_video || !a.bias_audio) m->zero_bias.ensure((size_t)B * S * 4, true);  // a growing buffer is zeroed again
-        m->mod_v.ensure((size_t)B * L * 6 * Dv * 4);
+        m->mod_v.ensure((size_t)BG * L * 6 * Dv * 4);
         m->mod_a.ensure((size_t)B * L * 6 * Da * 4);
-        m->mod_ca_v.ensure((size_t)B * L * 5 * Dv * 4);
+        m->mod_ca_v.ensure((size_t)BG * L * 5 * Dv * 4);
         m->mod_ca_a.ensure((size_t)B * L * 5 * Da * 4);
     }
     ensure_rope(ctx, m, a.F, a.H, a.W, Ta);
@@ -282,23 +288,24 @@ void dual_forward(ltx_ctx* ctx, DualStack* m, const DualForwardArgs& a) {
     const float* bias_v = a.bias_video ? a.bias_video : m->zero_bias.as<float>();  // null = all zeros, bit for bit
     const float* bias_a = a.bias_audio ? a.bias_audio : m->zero_bias.as<float>();
 
-    // mod[b][l][j][:] = table[l][j][:] + rows[b][j][:] for every block at once (the reference adds them per block: :182,195,229,230)
-    launch_make_mod(m->sst_v, a.temb_video, m->mod_v.as<float>(), B, L, 6, Dv, st);
+    // mod[b][l][j][:] = table[l][j][:] + rows[b][j][:] for every block at once (the reference adds them per block: :182,195,229,230);
+    // the video rows once per (batch element, timestep group), picked per token through the row map
+    launch_make_mod(m->sst_v, a.temb_video, m->mod_v.as<float>(), BG, L, 6, Dv, st);
     launch_make_mod(m->sst_a, a.temb_audio, m->mod_a.as<float>(), B, L, 6, Da, st);
-    launch_make_mod(m->sst_ca_v, a.cross_video_ss, m->mod_ca_v.as<float>(), B, L, 5, Dv, st);
+    launch_make_mod(m->sst_ca_v, a.cross_video_ss, m->mod_ca_v.as<float>(), BG, L, 5, Dv, st);
     launch_make_mod(m->sst_ca_a, a.cross_audio_ss, m->mod_ca_a.as<float>(), B, L, 5, Da, st);
     const long mv_bs = (long)L * 6 * Dv, ma_bs = (long)L * 6 * Da, cv_bs = (long)L * 5 * Dv, ca_bs = (long)L * 5 * Da;
 
     auto core = [&](AttnModule* mod, AttnVtSlot* vt, const bf16_t* xq, const bf16_t* cx, int kvb, int Tq, int Tk, const float* qc, const float* qs,
-                    const float* kc, const float* ks, const float* bias, float* x, const float* gate, long gbs, const bf16_t* ck = nullptr,
-                    const bf16_t* cvt = nullptr) {
+                    const float* kc, const float* ks, const float* bias, float* x, const float* gate, long gbs, const int32_t* gmap,
+                    const bf16_t* ck = nullptr, const bf16_t* cvt = nullptr) {
         AttnCoreArgs c;
         c.cached_k = ck; c.cached_vt = cvt;
         c.xq = xq; c.ctx = cx; c.kv_bf16 = kvb;
         c.B = B; c.Tq = Tq; c.Tk = Tk;
         c.q_cos = qc; c.q_sin = qs; c.k_cos = kc; c.k_sin = ks;
         c.key_bias = bias;
-        c.x = x; c.gate = gate; c.gate_bstride = gbs;
+        c.x = x; c.gate = gate; c.gate_bstride = gbs; c.gate_rowmap = gmap;
         c.split_ws = sk.p; c.split_ws_elems = sk.elems;
         attn_module_core(ctx, mod, c, &m->attn_ws, vt);
     };
@@ -314,6 +321,7 @@ void dual_forward(ltx_ctx* ctx, DualStack* m, const DualForwardArgs& a) {
     // the RMS norm (+ modulation) passes of the two streams: a launch sets its scale / shift rows, their batch stride and its output
     NormModArgs nv, na;
     nv.x = xv; nv.ldx = nv.ldo = Dv; nv.rows_per_batch = Tv; nv.rows = (int)vrows; nv.D = Dv; nv.eps = eps;
+    nv.row_map = rmap;
     na.x = xa; na.ldx = na.ldo = Da; na.rows_per_batch = Ta; na.rows = (int)arows; na.D = Da; na.eps = eps;
     auto norm = [st](NormModArgs n, const float* scale, const float* shift, long mod_bs, bf16_t* out) {
         n.scale = scale; n.shift = shift; n.mod_bstride = mod_bs; n.out = out;
@@ -329,26 +337,26 @@ void dual_forward(ltx_ctx* ctx, DualStack* m, const DualForwardArgs& a) {
         const float* ca = m->mod_ca_a.as<float>() + (long)l * 5 * Da;
         if (on(1)) {  // video self-attention
             norm(nv, mv + 1L * Dv, mv, mv_bs, vn);
-            core(b.attn1, &m->vt[0], vn, nullptr, 0, Tv, Tv, rvc, rvs, nullptr, nullptr, nullptr, xv, mv + 2L * Dv, mv_bs);
+            core(b.attn1, &m->vt[0], vn, nullptr, 0, Tv, Tv, rvc, rvs, nullptr, nullptr, nullptr, xv, mv + 2L * Dv, mv_bs, rmap);
         }
         if (on(2)) {  // audio self-attention
             norm(na, ma + 1L * Da, ma, ma_bs, an);
-            core(b.audio_attn1, &m->vt[1], an, nullptr, 0, Ta, Ta, rac, ras, nullptr, nullptr, nullptr, xa, ma + 2L * Da, ma_bs);
+            core(b.audio_attn1, &m->vt[1], an, nullptr, 0, Ta, Ta, rac, ras, nullptr, nullptr, nullptr, xa, ma + 2L * Da, ma_bs, nullptr);
         }
         if (on(3)) {  // video text cross-attention on norm2(x_v)
             norm(nv, nullptr, nullptr, 0, vn);
-            core(b.attn2, &m->vt[2], vn, a.ctx_video, 1, Tv, S, nullptr, nullptr, nullptr, nullptr, bias_v, xv, nullptr, 0, tcs.k_v, tcs.vt_v);
+            core(b.attn2, &m->vt[2], vn, a.ctx_video, 1, Tv, S, nullptr, nullptr, nullptr, nullptr, bias_v, xv, nullptr, 0, nullptr, tcs.k_v, tcs.vt_v);
         }
         if (on(4)) {  // audio text cross-attention on audio_norm2(x_a)
             norm(na, nullptr, nullptr, 0, an);
-            core(b.audio_attn2, &m->vt[3], an, a.ctx_audio, 1, Ta, S, nullptr, nullptr, nullptr, nullptr, bias_a, xa, nullptr, 0, tcs.k_a, tcs.vt_a);
+            core(b.audio_attn2, &m->vt[3], an, a.ctx_audio, 1, Ta, S, nullptr, nullptr, nullptr, nullptr, bias_a, xa, nullptr, 0, nullptr, tcs.k_a, tcs.vt_a);
         }
         if (on(5) || on(6)) {
             // normVCA / normACA once, before either update; vn / an: the a2v operands, vn2 / an2: the v2a operands
             if (m->use_norm_mod2) {
                 NormMod2Job jv, ja;
                 jv.x = xv; jv.ldx = Dv; jv.scale0 = cv; jv.shift0 = cv + 1L * Dv; jv.scale1 = cv + 2L * Dv; jv.shift1 = cv + 3L * Dv;
-                jv.mod_bstride = cv_bs; jv.rows_per_batch = Tv; jv.out0 = vn; jv.out1 = vn2; jv.ldo = Dv; jv.rows = (int)vrows; jv.D = Dv;
+                jv.mod_bstride = cv_bs; jv.rows_per_batch = Tv; jv.out0 = vn; jv.out1 = vn2; jv.ldo = Dv; jv.rows = (int)vrows; jv.D = Dv; jv.row_map = rmap;
                 ja.x = xa; ja.ldx = Da; ja.scale0 = ca; ja.shift0 = ca + 1L * Da; ja.scale1 = ca + 2L * Da; ja.shift1 = ca + 3L * Da;
                 ja.mod_bstride = ca_bs; ja.rows_per_batch = Ta; ja.out0 = an; ja.out1 = an2; ja.ldo = Da; ja.rows = (int)arows; ja.D = Da;
                 launch_norm_mod2(jv, ja, eps, st);
@@ -358,10 +366,10 @@ void dual_forward(ltx_ctx* ctx, DualStack* m, const DualForwardArgs& a) {
                 norm(na, ca, ca + 1L * Da, ca_bs, an);
                 norm(na, ca + 2L * Da, ca + 3L * Da, ca_bs, an2);
             }
-            if (on(5)) core(b.a2v, &m->vt[4], vn, an, 0, Tv, Ta, cvc, cvs, cac, cas, nullptr, xv, cv + 4L * Dv, cv_bs);
-            if (on(6)) core(b.v2a, &m->vt[5], an2, vn2, 0, Ta, Tv, cac, cas, cvc, cvs, nullptr, xa, ca + 4L * Da, ca_bs);
+            if (on(5)) core(b.a2v, &m->vt[4], vn, an, 0, Tv, Ta, cvc, cvs, cac, cas, nullptr, xv, cv + 4L * Dv, cv_bs, rmap);
+            if (on(6)) core(b.v2a, &m->vt[5], an2, vn2, 0, Ta, Tv, cac, cas, cvc, cvs, nullptr, xa, ca + 4L * Da, ca_bs, nullptr);
         }
-        if (on(7)) ffn_phase(xv, Dv, Tv, vrows, mv, mv_bs, b.ff1, b.ff2, vn, ffh, eps, sk, st);
-        if (on(8)) ffn_phase(xa, Da, Ta, arows, ma, ma_bs, b.aff1, b.aff2, an, ffh, eps, sk, st);
+        if (on(7)) ffn_phase(xv, Dv, Tv, vrows, mv, mv_bs, rmap, b.ff1, b.ff2, vn, ffh, eps, sk, st);
+        if (on(8)) ffn_phase(xa, Da, Ta, arows, ma, ma_bs, nullptr, b.aff1, b.aff2, an, ffh, eps, sk, st);
     }
 }

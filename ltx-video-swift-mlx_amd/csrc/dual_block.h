@@ -4,9 +4,12 @@
 // streams. The embedders that produce those rows (audio_adaln_single, av_ca_*), the patchify / output heads and the caption projections
 // are dual_model.h, which owns a DualStack and calls dual_forward; the joint loop is dual_denoise.h; the CLI's --audio path is not built.
 //
-// Modulation inputs are ONE ROW PER BATCH ELEMENT: temb_v [B][6][Dv], temb_a [B][6][Da], cross_video_ss [B][5][Dv], cross_audio_ss
-// [B][5][Da]. The reference's per-token form (image-to-video, LTX2Transformer.swift:285-312) is not implemented, here or in
-// dual_model.h, whose timesteps are one value per batch element and stream.
+// Modulation inputs are one row per batch element on the audio stream (temb_a [B][6][Da], cross_audio_ss [B][5][Da]) and one row per
+// (batch element, timestep GROUP) on the video stream: temb_v [B*G][6][Dv], cross_video_ss [B*G][5][Dv], with video_row_map[b*Tv + t] =
+// b*G + group(b, t), as dit_forward has them. That is the reference's per-token form (image-to-video, LTX2Transformer.swift:285-312:
+// the adaLN rows AND both cross-modal embedders read the per-token video timesteps) with every distinct row built once. The map picks
+// the video adaLN rows and gates of phases 1 and 7, the a2v query / v2a key modulation of the cross-modal norms and the a2v gate.
+// G = 1 without a map is one row per batch element: the same launches, the same bits. B * G <= 8. Map entries are the caller's contract.
 //
 // The eight phases of one block, in the reference's order (x_v [B][Tv][Dv], x_a [B][Ta][Da], both f32, updated in place):
 //   1. video self-attention: adaLN rows 0 (shift) / 1 (scale), gate row 2 of scale_shift_table [6][Dv] + temb_v; heads x 128, 3-D RoPE
@@ -35,7 +38,7 @@
 //   4. v is rounded to bf16 by the projection's transposed store; P is rounded to bf16 for the PV product; attention output is bf16.
 //   5. The FFN's hidden activation (GELU-tanh) is rounded to bf16, as the DiT rounds it.
 //   6. to_out / FFN-down accumulate in f32 and add gate * (acc + bias) to the f32 stream in the GEMM's epilogue. The streams stay f32.
-// Unlike dit_forward there is no sequence parallelism, context cache, row map, STG flag, bf16 q|k store or bf16 split-K partial here.
+// Unlike dit_forward there is no sequence parallelism, context cache, STG flag, bf16 q|k store or bf16 split-K partial here.
 //
 // All four RoPE table sets (video 3-D, audio 1-D, cross-modal video-temporal, cross-modal audio) are made inside from (F, H, W) and
 // T_a with rope_tables / audio_positions / video_temporal_positions / rope_tables_positions, cached on the stack and rebuilt when
@@ -132,15 +135,18 @@ struct DualForwardArgs {
     const bf16_t* ctx_audio = nullptr;     // [B][S][audio_context_dim] bf16
     const float* bias_video = nullptr;     // [B][S] f32 additive key bias or null
     const float* bias_audio = nullptr;
-    const float* temb_video = nullptr;     // [B][6][Dv]
+    const float* temb_video = nullptr;     // [B*n_groups][6][Dv]
     const float* temb_audio = nullptr;     // [B][6][Da]
-    const float* cross_video_ss = nullptr; // [B][5][Dv]
+    const float* cross_video_ss = nullptr; // [B*n_groups][5][Dv]
     const float* cross_audio_ss = nullptr; // [B][5][Da]
     int B = 1, F = 0, H = 0, W = 0, T_a = 0, S = 0;
     unsigned phase_mask = 0;  // measurement seam (tools/bench_dual_block.py): bit p-1 set = run phase p; 0 = all eight
     // optional: phases 3 and 4 read K / V^T from here and skip their k GEMM, k norm and V^T GEMMs; ctx_video / ctx_audio are then not
     // read (they may be null). Its (B, S) must be the call's, or the forward is refused before the first launch.
     const DualTextCache* text_cache = nullptr;
+    // timestep groups of the video stream (head comment): device [B*F*H*W] int32 with entries in [0, B*n_groups), or null with one group
+    int n_groups = 1;
+    const int32_t* video_row_map = nullptr;
 };
 void dual_forward(ltx_ctx* ctx, DualStack* m, const DualForwardArgs& a);
 // Fills m->text_cache from the two projected contexts (ctx_video [B][S][video_context_dim], ctx_audio [B][S][audio_context_dim], bf16):

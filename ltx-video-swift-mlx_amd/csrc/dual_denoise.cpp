@@ -41,6 +41,12 @@ void dual_denoise_run(ltx_ctx* ctx, const DualDenoiseParams& p) {
     LTX_REQUIRE(m->cfg.audio_in_channels == Ca && m->cfg.audio_out_channels == Ca, "dual denoise: the audio stream must have %d channels", Ca);
     const int Tv = p.F * p.H * p.W, Ta = p.T_a, B = use_cfg ? 2 : 1;
     const long nv = (long)Tv * C, na = (long)Ta * Ca;
+    const bool i2v = p.cond_latent != nullptr;
+    const int HW = p.H * p.W, G = i2v ? 2 : 1;  // timestep groups per batch element: 0 = sigma, 1 = frame-0 tokens at 0
+    const long nk = i2v ? (long)HW * C : 0;     // frame 0 in token layout: the first H*W*C elements
+    if (i2v) LTX_REQUIRE(p.F >= 2, "dual denoise: image-to-video needs at least two latent frames (F=%d)", p.F);
+    const bool renoise = i2v && p.image_cond_noise_scale > 0.f && p.cond_noise;
+    const int n_noise = renoise ? steps - 1 : 0;  // slices of steps 1 ..; step 0's is applied at entry in the caller's layout
     hipStream_t st = ctx->stream;
 
     // one allocation, carved: [xv][xa][vel_v B][vel_a B][guided v][tok_v B][tok_a B][ts 4][rescale stats 4][step stats 8 steps]
@@ -51,15 +57,27 @@ void dual_denoise_run(ltx_ctx* ctx, const DualDenoiseParams& p) {
         return at;
     };
     const size_t o_xv = carve(nv * 4), o_xa = carve(na * 4), o_vv = carve(B * nv * 4), o_va = carve(B * na * 4), o_vg = carve(nv * 4),
-                 o_tv = carve(B * nv * 2), o_ta = carve(B * na * 2), o_ts = carve(16), o_rs = carve(16), o_ss = carve((size_t)steps * 32);
+                 o_tv = carve(B * nv * 2), o_ta = carve(B * na * 2), o_ts = carve(32), o_rs = carve(16), o_ss = carve((size_t)steps * 32),
+                 o_map = carve(i2v ? (size_t)B * Tv * 4 : 0), o_kc = carve(renoise ? nk * 4 : 0), o_kn = carve((size_t)n_noise * nk * 4);
     ctx->dual_dn.ensure(off);
     char* base = (char*)ctx->dual_dn.p;
     float *xv = (float*)(base + o_xv), *xa = (float*)(base + o_xa), *vel_v = (float*)(base + o_vv), *vel_a = (float*)(base + o_va),
           *vg = (float*)(base + o_vg), *ts = (float*)(base + o_ts), *rs = (float*)(base + o_rs), *ss = (float*)(base + o_ss);
     bf16_t *tok_v = (bf16_t*)(base + o_tv), *tok_a = (bf16_t*)(base + o_ta);
+    int32_t* rmap = (int32_t*)(base + o_map);
+    float *keep_c = (float*)(base + o_kc), *keep_n = (float*)(base + o_kn);
 
     const bf16_t* actx = p.audio_context ? p.audio_context : p.video_context;  // audioEncoding ?? videoEncoding
 
+    if (i2v) {  // :1261-1274, and step 0's re-noising (:1289-1294) while the latent is still in the caller's layout
+        launch_set_frame0(p.video_latent, p.cond_latent, renoise ? p.cond_noise : nullptr, p.image_cond_noise_scale, p.sigmas[0] * p.sigmas[0], C,
+                          p.F, HW, st);
+        launch_i2v_rowmap(rmap, B, Tv, HW, G, st);
+        if (renoise && n_noise > 0) {  // [C][HW] -> [HW][C], every slice in one launch
+            launch_unpatchify_f32(p.cond_latent, keep_c, 1, HW, C, st);
+            launch_unpatchify_f32(p.cond_noise + nk, keep_n, n_noise, HW, C, st);
+        }
+    }
     // entry: token layout, first tokens, the text side
     launch_unpatchify_f32(p.video_latent, xv, 1, Tv, C, st);  // [C][Tv] -> [Tv][C]: the transpose with the roles of C and T exchanged
     pack_audio(p.audio_latent, xa, Ta, false, st);
@@ -74,10 +92,15 @@ void dual_denoise_run(ltx_ctx* ctx, const DualDenoiseParams& p) {
     for (int step = 0; step < steps; ++step) {
         const float sigma = p.sigmas[step], sigma_next = p.sigmas[step + 1];
         if (p.progress) p.progress(step, steps, sigma, p.user);  // before the forward (:1285-1287)
-        launch_fill_const_f32(ts, 4, sigma, st);                 // [video B][audio B]
+        if (i2v) launch_i2v_timesteps(ts, B, G, sigma, st);       // [video B][G] = {sigma, 0}, [audio B]
+        else launch_fill_const_f32(ts, 4, sigma, st);            // [video B][audio B]
         DualModelForwardArgs f;
         f.video_latent = tok_v; f.audio_latent = tok_a;
-        f.video_timesteps = ts; f.audio_timesteps = ts + 2;
+        f.video_timesteps = ts; f.audio_timesteps = i2v ? ts + B * G : ts + 2;
+        if (i2v) {
+            f.n_groups = G;
+            f.video_row_map = rmap;
+        }
         f.B = B; f.F = p.F; f.H = p.H; f.W = p.W; f.T_a = Ta; f.S = p.S;
         f.video_velocity = vel_v; f.audio_velocity = vel_a;
         f.text_cache = p.text_cache;
@@ -91,6 +114,10 @@ void dual_denoise_run(ltx_ctx* ctx, const DualDenoiseParams& p) {
         DualStepJob jv, ja;
         jv.latent = xv; jv.v_cond = vel_v + (B - 1) * nv; jv.v_uncond = use_cfg ? vel_v : nullptr; jv.cfg_scale = p.cfg_scale;
         jv.form = 0; jv.tokens = tok_v; jv.copies = B; jv.n = nv;
+        jv.n_keep = nk;  // frame 0 is not stepped (:1383-1393); re-noised for the next step's forward, which is where the reference does it
+        if (renoise && step + 1 < steps) {
+            jv.keep_src = keep_c; jv.keep_noise = keep_n + (long)step * nk; jv.keep_scale = p.image_cond_noise_scale;
+        }
         ja.latent = xa; ja.v_cond = vel_a + (B - 1) * na; ja.v_uncond = use_cfg ? vel_a : nullptr; ja.cfg_scale = p.cfg_scale;
         ja.form = 1; ja.tokens = tok_a; ja.copies = B; ja.n = na;
         if (p.guidance_rescale > 0.f) {  // video only (:1352-1359); the step then takes the guided velocity as it is

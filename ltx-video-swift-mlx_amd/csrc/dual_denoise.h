@@ -1,5 +1,5 @@
-// dual_denoise.h - the denoise loop of generateVideoWithAudio (LTXPipeline.swift:1276-1417), text-to-video+audio, around the dual model
-// (dual_model.h). One schedule for both streams. The graph:
+// dual_denoise.h - the denoise loop of generateVideoWithAudio (LTXPipeline.swift:1276-1417), text-to-video+audio and image-to-video+audio,
+// around the dual model (dual_model.h). One schedule for both streams. The graph:
 //   entry     video [C][Tv] f32 -> token layout [Tv][C] (launch_unpatchify_f32 with the roles of C and T exchanged); audio (8, T_a, 16) ->
 //             (T_a, 128) (packAudioLatents, :540-544: eight strided 2-D copies); two launch_cast_f32_bf16 write the first tokens;
 //             dual_model_prepare_text once (text_cache)
@@ -11,8 +11,18 @@
 // Both latents stay in token layout for the whole loop, which is what makes the step elementwise: the per-step patchify, unpatchify,
 // cast and copy passes of denoise_run (pipeline.cpp) have no counterpart here. No new rounding point: the step is f32, every operation
 // rounded on its own as the reference's array ops are (elementwise.h, DualStepJob); the tokens are the one bf16 rounding of :1306-1307.
-// Every check comes before the first launch: a refused call leaves both latents untouched. Image-to-video (per-token timesteps), STG,
-// GE, the two-stage path and sharding are not implemented.
+// Image-to-video (cond_latent set, :1261-1274, :1289-1303, :1383-1399; F >= 2):
+//   entry     frame 0 of the caller's latent = cond (+ (scale * noise[0]) * sigmas[0]^2 with re-noising: launch_set_frame0); the row map
+//             of two timestep groups per batch element (launch_i2v_rowmap: frame-0 tokens group 1, the rest group 0); cond and the noise
+//             slices of steps 1 .. to token layout, once, with the entry transpose
+//   per step  video timesteps {sigma, 0} per batch element, audio sigma (ONE launch_i2v_timesteps in place of the fill); the groups
+//             forward; ONE launch_dual_step whose video job freezes the first H*W*C elements (frame 0 in token layout) and, with
+//             re-noising, writes them as the NEXT step must see them: cond + (scale * noise[step + 1]) * sigma_next^2. The reference
+//             re-noises at the start of a step (:1289-1294), where that step's sigma is this step's sigma_next; the last step re-noises
+//             nothing, so the final frame 0 is the last noised one, or cond itself without noise. No other launch per step.
+// Text-to-video (cond_latent null) runs the launches it ran before the image-to-video path existed, with the same bits.
+// Every check comes before the first launch: a refused call leaves both latents untouched. STG, GE, the two-stage path and sharding
+// are not implemented.
 #pragma once
 #include "../../include/ltxhip.h"
 #include "runtime.h"
@@ -32,5 +42,9 @@ struct DualDenoiseParams {
     float* step_stats = nullptr;            // host [n_sigmas - 1][8] or null: mean, std of video velocity, video latent, audio velocity, audio latent
     ltx_progress_cb progress = nullptr;
     void* user = nullptr;
+    // image-to-video, as ltx_denoise_options has them (device pointers)
+    const float* cond_latent = nullptr;     // [1][C][1][H][W] f32 or null (text-to-video)
+    float image_cond_noise_scale = 0.0f;
+    const float* cond_noise = nullptr;      // [n_sigmas - 1][C][1][H][W] f32 or null (no re-noising)
 };
 void dual_denoise_run(ltx_ctx* ctx, const DualDenoiseParams& p);

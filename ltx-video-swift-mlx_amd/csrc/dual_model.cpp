@@ -12,28 +12,31 @@
 
 namespace {
 
-// offsets (in floats) of embedder j's [B][D] rows inside ws_h1 / ws_h2
-long stage_offset(const DualModel* m, int j, int B) {
+// offsets (in floats) of embedder j's [M][D] rows inside ws_h1 / ws_h2; a video embedder has Mv rows (one per batch element and
+// timestep group), an audio embedder Ma (one per batch element)
+long stage_offset(const DualModel* m, int j, int Mv, int Ma) {
     long off = 0;
-    for (int i = 0; i < j; ++i) off += (long)B * (m->emb[i].audio ? m->Da : m->Dv);
+    for (int i = 0; i < j; ++i) off += m->emb[i].audio ? (long)Ma * m->Da : (long)Mv * m->Dv;
     return off;
 }
 
-void ensure_embed_scratch(DualModel* m, int B) {
-    m->ws_emb256.ensure((size_t)2 * B * 256 * 4);
-    const size_t stage = (size_t)stage_offset(m, kDualEmbedders, B) * 4;
+void ensure_embed_scratch(DualModel* m, int Mv, int Ma) {
+    m->ws_emb256.ensure((size_t)(Mv + Ma) * 256 * 4);
+    const size_t stage = (size_t)stage_offset(m, kDualEmbedders, Mv, Ma) * 4;
     m->ws_h1.ensure(stage);
     m->ws_h2.ensure(stage);
 }
 
 // The timestep path (LTX2Transformer.swift:272-312). No check and no allocation in here: the callers have done both.
-void embed_launches(ltx_ctx* ctx, DualModel* m, const float* video_ts, const float* audio_ts, int B, bool ungrouped, const DualEmbedOut& o) {
+// video_ts [Mv], audio_ts [Ma]. Mv == Ma: every stage is one grouped launch of six jobs. Mv != Ma (timestep groups): a grouped launch
+// shares one M, so every stage is two - the three video embedders at Mv rows, the three audio embedders at Ma.
+void embed_launches(ltx_ctx* ctx, DualModel* m, const float* video_ts, const float* audio_ts, int Mv, int Ma, bool ungrouped, const DualEmbedOut& o) {
     hipStream_t st = ctx->stream;
     const int Dv = m->Dv, Da = m->Da;
     float* emb_v = m->ws_emb256.as<float>();
-    float* emb_a = emb_v + (long)B * 256;
-    launch_timestep_embedding(video_ts, m->cfg.timestep_scale_multiplier, emb_v, B, 256, st);
-    launch_timestep_embedding(audio_ts, m->cfg.timestep_scale_multiplier, emb_a, B, 256, st);
+    float* emb_a = emb_v + (long)Mv * 256;
+    launch_timestep_embedding(video_ts, m->cfg.timestep_scale_multiplier, emb_v, Mv, 256, st);
+    launch_timestep_embedding(audio_ts, m->cfg.timestep_scale_multiplier, emb_a, Ma, 256, st);
     // stage 3 destinations: the four modulation tensors; the gate embedders write row 4 of the 5-row tensors
     float* dst3[kDualEmbedders] = {o.temb_v, o.temb_a, o.cross_v, o.cross_v + 4L * Dv, o.cross_a, o.cross_a + 4L * Da};
     const long ldo3[kDualEmbedders] = {6L * Dv, 6L * Da, 5L * Dv, 5L * Dv, 5L * Da, 5L * Da};
@@ -41,9 +44,9 @@ void embed_launches(ltx_ctx* ctx, DualModel* m, const float* video_ts, const flo
     for (int j = 0; j < kDualEmbedders; ++j) {
         const DualEmbedder& e = m->emb[j];
         const int D = e.audio ? Da : Dv;
-        float* h1 = m->ws_h1.as<float>() + stage_offset(m, j, B);
+        float* h1 = m->ws_h1.as<float>() + stage_offset(m, j, Mv, Ma);
         // the stage-2 outputs of adaln_single / audio_adaln_single are the embedded timesteps
-        float* h2 = j == 0 ? o.embts_v : j == 1 ? o.embts_a : m->ws_h2.as<float>() + stage_offset(m, j, B);
+        float* h2 = j == 0 ? o.embts_v : j == 1 ? o.embts_a : m->ws_h2.as<float>() + stage_offset(m, j, Mv, Ma);
         s1[j].a = e.audio ? emb_a : emb_v; s1[j].lda = 256; s1[j].W = e.l1.w; s1[j].ldw = 256; s1[j].bias = e.l1.b;
         s1[j].out = h1; s1[j].ldo = D; s1[j].N = D; s1[j].K = 256; s1[j].in_act = LTX_ACT_NONE;
         s2[j].a = h1; s2[j].lda = D; s2[j].W = e.l2.w; s2[j].ldw = D; s2[j].bias = e.l2.b;
@@ -51,15 +54,25 @@ void embed_launches(ltx_ctx* ctx, DualModel* m, const float* video_ts, const flo
         s3[j].a = h2; s3[j].lda = D; s3[j].W = e.lin.w; s3[j].ldw = D; s3[j].bias = e.lin.b;
         s3[j].out = dst3[j]; s3[j].ldo = ldo3[j]; s3[j].N = e.n * D; s3[j].K = D; s3[j].in_act = LTX_ACT_SILU;
     }
+    if (!ungrouped && Mv == Ma) {
+        launch_gemv_group(s1, kDualEmbedders, Mv, st);
+        launch_gemv_group(s2, kDualEmbedders, Mv, st);
+        launch_gemv_group(s3, kDualEmbedders, Mv, st);
+        return;
+    }
     if (!ungrouped) {
-        launch_gemv_group(s1, kDualEmbedders, B, st);
-        launch_gemv_group(s2, kDualEmbedders, B, st);
-        launch_gemv_group(s3, kDualEmbedders, B, st);
+        for (const GemvJob* s : {s1, s2, s3}) {
+            GemvJob v[kDualEmbedders], a[kDualEmbedders];
+            int nv = 0, na = 0;
+            for (int j = 0; j < kDualEmbedders; ++j) (m->emb[j].audio ? a[na++] : v[nv++]) = s[j];
+            launch_gemv_group(v, nv, Mv, st);
+            launch_gemv_group(a, na, Ma, st);
+        }
         return;
     }
     for (const GemvJob* s : {s1, s2, s3})
         for (int j = 0; j < kDualEmbedders; ++j)
-            launch_gemv_f32(s[j].a, s[j].lda, s[j].W, s[j].ldw, s[j].bias, s[j].out, s[j].ldo, B, s[j].N, s[j].K, s[j].in_act, st);
+            launch_gemv_f32(s[j].a, s[j].lda, s[j].W, s[j].ldw, s[j].bias, s[j].out, s[j].ldo, m->emb[j].audio ? Ma : Mv, s[j].N, s[j].K, s[j].in_act, st);
 }
 
 // PixArtAlphaTextProjection of one context (LTX2Transformer.swift:275,282): Linear, GELU-tanh, Linear; the hidden activation goes
@@ -170,8 +183,8 @@ void dual_model_embed(ltx_ctx* ctx, DualModel* m, const float* video_ts, const f
     if (B < 1 || B > 8) LTX_THROW(LTXS_INVALID_CONFIGURATION, "dual model embed: B=%d (1 .. 8)", B);
     if (!video_ts || !audio_ts || !o.temb_v || !o.temb_a || !o.cross_v || !o.cross_a || !o.embts_v || !o.embts_a)
         LTX_THROW(LTXS_INVALID_CONFIGURATION, "dual model embed: null timestep or output pointer");
-    ensure_embed_scratch(m, B);
-    embed_launches(ctx, m, video_ts, audio_ts, B, ungrouped, o);
+    ensure_embed_scratch(m, B, B);
+    embed_launches(ctx, m, video_ts, audio_ts, B, B, ungrouped, o);
 }
 
 void dual_model_forward(ltx_ctx* ctx, DualModel* m, const DualModelForwardArgs& a) {
@@ -180,6 +193,10 @@ void dual_model_forward(ltx_ctx* ctx, DualModel* m, const DualModelForwardArgs& 
     const int Dv = m->Dv, Da = m->Da, B = a.B, S = a.S, Ta = a.T_a;
     if (B < 1 || B > 8 || a.F < 1 || a.H < 1 || a.W < 1 || Ta < 1 || S < 1 || Ta > (1 << 20) || S > (1 << 20) || (long)a.F * a.H * a.W > (1 << 20))
         LTX_THROW(LTXS_INVALID_CONFIGURATION, "dual model forward: bad shapes B=%d (1 .. 8) F=%d H=%d W=%d T_a=%d S=%d", B, a.F, a.H, a.W, Ta, S);
+    const int G = a.n_groups;
+    if (G < 1 || (long)B * G > 8 || (G > 1 && !a.video_row_map))
+        LTX_THROW(LTXS_INVALID_CONFIGURATION, "dual model forward: n_groups=%d (B * n_groups = 1 .. 8; more than one group needs video_row_map)", G);
+    const int BG = B * G;
     const bool cached = a.text_cache != 0;
     if (!a.video_latent || !a.audio_latent || (!cached && (!a.video_context || !a.audio_context)) || !a.video_timesteps || !a.audio_timesteps ||
         !a.video_velocity || !a.audio_velocity)
@@ -203,12 +220,12 @@ void dual_model_forward(ltx_ctx* ctx, DualModel* m, const DualModelForwardArgs& 
         if (a.video_mask) m->ws_bias_v.ensure((size_t)crows * 4);
         if (a.audio_mask) m->ws_bias_a.ensure((size_t)crows * 4);
     }
-    ensure_embed_scratch(m, B);
-    m->ws_temb_v.ensure((size_t)B * 6 * Dv * 4);
+    ensure_embed_scratch(m, BG, B);
+    m->ws_temb_v.ensure((size_t)BG * 6 * Dv * 4);
     m->ws_temb_a.ensure((size_t)B * 6 * Da * 4);
-    m->ws_cross_v.ensure((size_t)B * 5 * Dv * 4);
+    m->ws_cross_v.ensure((size_t)BG * 5 * Dv * 4);
     m->ws_cross_a.ensure((size_t)B * 5 * Da * 4);
-    m->ws_modout_v.ensure((size_t)B * 2 * Dv * 4);
+    m->ws_modout_v.ensure((size_t)BG * 2 * Dv * 4);
     m->ws_modout_a.ensure((size_t)B * 2 * Da * 4);
     m->ws_xn.ensure((size_t)std::max(vrows * Dv, arows * Da) * 2);
     m->ws_splitk.ensure((size_t)8 << 22);
@@ -233,9 +250,9 @@ void dual_model_forward(ltx_ctx* ctx, DualModel* m, const DualModelForwardArgs& 
     eo.temb_a = m->ws_temb_a.as<float>();
     eo.cross_v = m->ws_cross_v.as<float>();
     eo.cross_a = m->ws_cross_a.as<float>();
-    eo.embts_v = m->ws_h2.as<float>() + stage_offset(m, 0, B);
-    eo.embts_a = m->ws_h2.as<float>() + stage_offset(m, 1, B);
-    embed_launches(ctx, m, a.video_timesteps, a.audio_timesteps, B, a.ungrouped != 0, eo);
+    eo.embts_v = m->ws_h2.as<float>() + stage_offset(m, 0, BG, B);
+    eo.embts_a = m->ws_h2.as<float>() + stage_offset(m, 1, BG, B);
+    embed_launches(ctx, m, a.video_timesteps, a.audio_timesteps, BG, B, a.ungrouped != 0, eo);
     // 3. text (:275,282,315-316); a cached forward reads what dual_model_prepare_text left
     if (!cached) {
         caption_launches(m, a.video_context, m->cap1, m->cap2, Dv, crows, m->ws_ctx_v.as<bf16_t>(), st, sk);
@@ -262,14 +279,16 @@ void dual_model_forward(ltx_ctx* ctx, DualModel* m, const DualModelForwardArgs& 
     f.cross_video_ss = eo.cross_v;
     f.cross_audio_ss = eo.cross_a;
     f.B = B; f.F = a.F; f.H = a.H; f.W = a.W; f.T_a = Ta; f.S = S;
+    f.n_groups = G; f.video_row_map = a.video_row_map;
     dual_forward(ctx, m->stack, f);
     // 5. heads (:375-389): mod[b][j][:] = table[j][:] + embedded_ts[b][:], j = 0 shift, 1 scale - launch_make_mod with the table's two
-    // rows as its "layers" and one row per batch element
-    auto head = [&](const float* x, int D, int T, long rows, const float* table, const float* embts, float* mod, const LinearW& proj, float* out) {
-        launch_make_mod(table, embts, mod, B, 2, 1, D, st);
+    // rows as its "layers" and one row per batch element (video: per batch element and timestep group, picked through the row map)
+    auto head = [&](const float* x, int D, int T, long rows, const float* table, const float* embts, int M, const int32_t* rmap, float* mod,
+                    const LinearW& proj, float* out) {
+        launch_make_mod(table, embts, mod, M, 2, 1, D, st);
         NormModArgs n;
         n.x = x; n.ldx = D;
-        n.scale = mod + D; n.shift = mod; n.mod_bstride = 2L * D; n.rows_per_batch = T;
+        n.scale = mod + D; n.shift = mod; n.mod_bstride = 2L * D; n.rows_per_batch = T; n.row_map = rmap;
         n.out = m->ws_xn.as<bf16_t>(); n.ldo = D;
         n.rows = (int)rows; n.D = D; n.norm_kind = LTX_NORM_LAYER; n.eps = eps;
         launch_norm_mod(n, st);
@@ -278,8 +297,8 @@ void dual_model_forward(ltx_ctx* ctx, DualModel* m, const DualModelForwardArgs& 
         e.ld_f32 = proj.out;
         gemm_linear(m->ws_xn.as<bf16_t>(), D, proj, (int)rows, e, st, sk);
     };
-    head(xv, Dv, Tv, vrows, m->sst_out_v, eo.embts_v, m->ws_modout_v.as<float>(), m->proj_out, a.video_velocity);
-    head(xa, Da, Ta, arows, m->sst_out_a, eo.embts_a, m->ws_modout_a.as<float>(), m->audio_proj_out, a.audio_velocity);
+    head(xv, Dv, Tv, vrows, m->sst_out_v, eo.embts_v, BG, a.video_row_map, m->ws_modout_v.as<float>(), m->proj_out, a.video_velocity);
+    head(xa, Da, Ta, arows, m->sst_out_a, eo.embts_a, B, nullptr, m->ws_modout_a.as<float>(), m->audio_proj_out, a.audio_velocity);
 }
 
 void dual_model_prepare_text(ltx_ctx* ctx, DualModel* m, const bf16_t* video_context, const bf16_t* audio_context, const int32_t* video_mask,

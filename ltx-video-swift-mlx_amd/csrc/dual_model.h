@@ -4,15 +4,19 @@
 // parameters of LTX2Transformer.swift:28-48: patchify_proj / audio_patchify_proj, the six AdaLayerNormSingle embedders (each
 // emb.linear_1, emb.linear_2, linear), caption_projection / audio_caption_projection (linear_1, linear_2), scale_shift_table [2][Dv] /
 // audio_scale_shift_table [2][Da], proj_out / audio_proj_out. norm_out / audio_norm_out are LayerNorm(affine: false): no weight.
-// The joint denoise loop is dual_denoise.h; per-token timesteps and the CLI's --audio path are not here.
+// The joint denoise loop is dual_denoise.h; the CLI's --audio path is not here.
 //
 // The text side of a forward (step 3 below and the K / V^T of the blocks' text cross-attentions) does not change within a prompt:
 // dual_model_prepare_text runs it once into model-owned buffers and the stack's DualTextCache, and a forward with text_cache set reads
 // those instead. Same launches, same operands, same bits as the forward that recomputes them.
 //
-// Timesteps are ONE VALUE PER BATCH ELEMENT per stream (video_timesteps [B], audio_timesteps [B], sigma unscaled), so every modulation
-// row is one row per batch element, as dual_block.h takes them. The reference's per-token form (image-to-video,
-// LTX2Transformer.swift:285-312) is not implemented.
+// Audio timesteps are one value per batch element (audio_timesteps [B], sigma unscaled; the reference's audioTimestep is always
+// [sigma]). Video timesteps are one value per (batch element, timestep GROUP): video_timesteps [B][n_groups] with video_row_map[b*Tv + t]
+// = b*n_groups + group(b, t), as dit_forward groups them. That is the reference's per-token form (image-to-video,
+// LTX2Transformer.swift:285-312) with each distinct timestep embedded once: the three video embedders run at M = B * n_groups rows and
+// the three audio embedders at M = B, two launch_gemv_group launches per stage (a grouped launch shares one M); the video head builds
+// its modulation for B * n_groups rows and picks them through the map. n_groups = 1 with no map keeps the single launch per stage and
+// every launch of the forward as it was, with the same bits. B * n_groups <= 8 (the grouped gemv's limit on M).
 //
 // The graph, in the reference's order:
 //   1. patchify: x_v = patchify_proj(video_latent), x_a = audio_patchify_proj(audio_latent) -> the two f32 residual streams
@@ -122,8 +126,8 @@ struct DualModelForwardArgs {
     const bf16_t* audio_latent = nullptr;   // [B][T_a][audio_in_channels] bf16
     const bf16_t* video_context = nullptr;  // [B][S][caption_channels] bf16
     const bf16_t* audio_context = nullptr;
-    const float* video_timesteps = nullptr; // [B] f32, sigma unscaled
-    const float* audio_timesteps = nullptr;
+    const float* video_timesteps = nullptr; // [B][n_groups] f32, sigma unscaled
+    const float* audio_timesteps = nullptr; // [B]
     const int32_t* video_mask = nullptr;    // [B][S] int32 or null
     const int32_t* audio_mask = nullptr;
     int B = 1, F = 0, H = 0, W = 0, T_a = 0, S = 0;
@@ -132,6 +136,8 @@ struct DualModelForwardArgs {
     int ungrouped = 0;                      // non-zero: 18 launch_gemv_f32 launches instead of the three grouped ones (bit-equal); the
                                             // grouped path is the default because it measured faster (profiles/dual_model_bench.txt)
     int text_cache = 0;                     // non-zero: the text side comes from dual_model_prepare_text; contexts and masks are not read
+    int n_groups = 1;                       // timestep groups of the video stream: video_timesteps is [B][n_groups]
+    const int32_t* video_row_map = nullptr; // device [B*F*H*W] int32, entries in [0, B*n_groups) (the caller's contract); null with one group
 };
 void dual_model_forward(ltx_ctx* ctx, DualModel* m, const DualModelForwardArgs& a);
 // Both caption projections and both launch_mask_to_bias passes (a null mask is a null bias) into model-owned buffers, then

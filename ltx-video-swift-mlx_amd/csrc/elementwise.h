@@ -31,9 +31,9 @@ void launch_norm_mod(const NormModArgs& args, hipStream_t stream);
 // video_to_audio_norm(x_a) are each computed ONCE and modulated twice - a2v query / v2a key rows of the video stream, a2v key / v2a
 // query rows of the audio stream. One launch, two jobs (video rows at Dv, audio rows at Da; rows == 0: the job is empty): every f32 row
 // is read once, RMS-normed once and written twice as bf16, out0 = norm * (1 + scale0[b]) + shift0[b] and out1 likewise with
-// (scale1, shift1), b = row / rows_per_batch. A null (scale, shift) pair writes the plain norm. D % 4 == 0 up to 8192, ldx / ldo >= D
+// (scale1, shift1), b = row_map ? row_map[row] : row / rows_per_batch. A null (scale, shift) pair writes the plain norm. D % 4 == 0 up to 8192, ldx / ldo >= D
 // and multiples of 4. Reduction order of norm_mod_kernel (wave sums added in wave order): each output is bit-equal to the
-// launch_norm_mod call (LTX_NORM_RMS, round_norm_bf16 = 0) it replaces. Every check comes before the launch.
+// launch_norm_mod call (LTX_NORM_RMS, round_norm_bf16 = 0, the same row map) it replaces. Every check comes before the launch.
 struct NormMod2Job {
     const float* x = nullptr;       // [rows][ldx] f32
     long ldx = 0;
@@ -47,6 +47,7 @@ struct NormMod2Job {
     bf16_t* out1 = nullptr;
     long ldo = 0;
     int rows = 0, D = 0;
+    const int32_t* row_map = nullptr;  // device [rows] or null: b = row_map[row] (per-token timestep groups, as NormModArgs::row_map)
 };
 void launch_norm_mod2(const NormMod2Job& video, const NormMod2Job& audio, float eps, hipStream_t stream);
 
@@ -104,6 +105,9 @@ void launch_euler_step(float* latent, const float* velocity, float sigma, float 
 void launch_set_frame0(float* latent, const float* cond, const float* noise, float scale, float sigma2, int C, int F, int HW,
                        hipStream_t stream);
 void launch_i2v_rowmap(int32_t* row_map, int B, int T, int first, int G, hipStream_t stream);
+// the joint loop's timesteps of one image-to-video step in one launch: ts[b][g] = g == 0 ? sigma : 0 ([B][G], the groups of
+// launch_i2v_rowmap), followed by B audio timesteps = sigma. B * G + B <= 64.
+void launch_i2v_timesteps(float* ts, int B, int G, float sigma, hipStream_t stream);
 // Everything between two forwards of the joint video + audio loop (generateVideoWithAudio, LTXPipeline.swift:1276-1417) in ONE launch:
 // CFG, the Euler step and the next forward's bf16 operand, for both streams. Two jobs share one grid (video, audio; n == 0: the job is
 // empty). Per element, every operation rounded on its own as the reference's separate array ops round (no contraction, correctly
@@ -124,6 +128,16 @@ struct DualStepJob {
     int copies = 1;
     float* v_out = nullptr;           // [n] f32 or null: the guided velocity; may alias v_cond
     long n = 0;
+    // frozen prefix (image-to-video: in token layout frame 0 is the first H*W*C elements). Elements i < n_keep skip the Euler form:
+    //   keep_noise set:  x' = keep_src + (keep_scale * keep_noise) * (sigma_next * sigma_next)   - frame 0 as the NEXT forward must see it
+    //                    (LTXPipeline.swift:1289-1294; four separately rounded f32 operations, as set_frame0_kernel's)
+    //   keep_noise null: x' = x
+    // tokens (both copies) and v_out are written for the whole job either way. n_keep % 4 == 0, 0 <= n_keep <= n, keep_noise needs
+    // keep_src; n_keep = 0 is the kernel without a prefix, bit for bit.
+    long n_keep = 0;
+    const float* keep_src = nullptr;    // [n_keep] f32
+    const float* keep_noise = nullptr;  // [n_keep] f32 or null
+    float keep_scale = 0.0f;
 };
 void launch_dual_step(const DualStepJob& video, const DualStepJob& audio, float sigma, float sigma_next, hipStream_t stream);
 // CFG combine v = cond + (scale-1)*(cond-uncond) (LatentUtils.swift:131-141)

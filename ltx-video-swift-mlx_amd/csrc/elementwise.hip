@@ -205,7 +205,8 @@ __global__ __launch_bounds__(256) void norm_mod2_kernel(const NormMod2Job j0, co
     const int D = second ? j1.D : j0.D;
     const long ldx = second ? j1.ldx : j0.ldx, ldo = second ? j1.ldo : j0.ldo, mbs = second ? j1.mod_bstride : j0.mod_bstride;
     const float* xr = (second ? j1.x : j0.x) + (long)row * ldx;
-    const long moff = (long)(row / (second ? j1.rows_per_batch : j0.rows_per_batch)) * mbs;
+    const int32_t* rmap = second ? j1.row_map : j0.row_map;  // per-token timestep groups (image-to-video): one uniform load
+    const long moff = (long)(rmap ? rmap[row] : row / (second ? j1.rows_per_batch : j0.rows_per_batch)) * mbs;
     const float* sc0 = second ? j1.scale0 : j0.scale0;
     const float* sh0 = second ? j1.shift0 : j0.shift0;
     const float* sc1 = second ? j1.scale1 : j0.scale1;
@@ -670,6 +671,12 @@ __global__ __launch_bounds__(256) void dual_step_kernel(const DualStepJob j0, co
     const int form = second ? j1.form : j0.form;
     const int copies = second ? j1.copies : j0.copies;
     const long n = second ? j1.n : j0.n;
+    // the frozen prefix (image-to-video: frame 0 in token layout): no Euler form, the conditioning latent re-noised for the NEXT forward
+    const long n_keep = second ? j1.n_keep : j0.n_keep;
+    const float* __restrict__ ksrc = second ? j1.keep_src : j0.keep_src;
+    const float* __restrict__ knoise = second ? j1.keep_noise : j0.keep_noise;
+    const float kscale = second ? j1.keep_scale : j0.keep_scale;
+    const float sn2 = sigma_next * sigma_next;
     const float ds = sigma_next - sigma;
     const long stride = (long)nwg * 256 * 4;
     for (long i = ((long)wg * 256 + threadIdx.x) * 4; i < n; i += stride) {  // n % 4 == 0: whole vectors only
@@ -686,7 +693,19 @@ __global__ __launch_bounds__(256) void dual_step_kernel(const DualStepJob j0, co
         }
         if (vo) *(f32x4*)(vo + i) = v;
         f32x4 y;
-        if (form == 0) {
+        if (i < n_keep) {  // n_keep % 4 == 0: a vector is inside the prefix or outside it
+            y = x;
+            if (knoise) {
+                const f32x4 c = *(const f32x4*)(ksrc + i);
+                const f32x4 z = *(const f32x4*)(knoise + i);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const float a = kscale * z[e];
+                    const float b = a * sn2;
+                    y[e] = c[e] + b;
+                }
+            }
+        } else if (form == 0) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const float sv = sigma * v[e];
@@ -1144,7 +1163,18 @@ __global__ void i2v_rowmap_kernel(int32_t* __restrict__ row_map, int B, int T, i
     const int b = (int)(i / T), t = (int)(i - (long)b * T);
     row_map[i] = b * G + (t < first ? 1 : 0);
 }
+// ts[b*G + g] = g == 0 ? sigma : 0 for b < B (the video timesteps of launch_i2v_rowmap's groups), then B audio timesteps = sigma
+__global__ void i2v_timesteps_kernel(float* __restrict__ ts, int B, int G, float sigma) {
+    const int i = threadIdx.x;
+    if (i >= B * G + B) return;
+    ts[i] = (i < B * G && i % G != 0) ? 0.f : sigma;
+}
 }  // namespace
+void launch_i2v_timesteps(float* ts, int B, int G, float sigma, hipStream_t stream) {
+    LTX_REQUIRE(B >= 1 && G >= 1 && B * G + B <= 64, "i2v_timesteps: B=%d G=%d", B, G);
+    hipLaunchKernelGGL(i2v_timesteps_kernel, dim3(1), dim3(64), 0, stream, ts, B, G, sigma);
+    HIP_CHECK(hipGetLastError());
+}
 void launch_set_frame0(float* latent, const float* cond, const float* noise, float scale, float sigma2, int C, int F, int HW,
                        hipStream_t stream) {
     hipLaunchKernelGGL(set_frame0_kernel, dim3(cdiv((long)C * HW, 256)), dim3(256), 0, stream, latent, cond, noise, scale, sigma2, C, F, HW);
@@ -1167,6 +1197,8 @@ void launch_dual_step(const DualStepJob& video, const DualStepJob& audio, float 
         LTX_REQUIRE(j->latent && j->v_cond && j->tokens, "dual_step: null latent, velocity or token pointer");
         LTX_REQUIRE(j->copies >= 1 && j->copies <= 2, "dual_step: copies=%d (1 .. 2)", j->copies);
         LTX_REQUIRE(j->form >= 0 && j->form <= 1, "dual_step: form=%d (0 .. 1)", j->form);
+        LTX_REQUIRE(j->n_keep >= 0 && j->n_keep <= j->n && j->n_keep % 4 == 0, "dual_step: n_keep=%ld (a multiple of 4, 0 .. n=%ld)", j->n_keep, j->n);
+        LTX_REQUIRE(!j->keep_noise || j->keep_src, "dual_step: keep_noise needs keep_src");
         bytes += j->n * (4 + 4 + (j->v_uncond ? 4 : 0) + 4 + (j->v_out ? 4 : 0) + 2 * j->copies);
     }
     // per job: one workgroup per 1024 elements, at most kMaxWgs (half the CUs each; the loop strides over the rest)

@@ -7,7 +7,10 @@ caption_channels 3840), L = 1, T_v = 1536 = (4, 16, 24), T_a = 126, S = 1024, a 
   * one forward with the text cache against one without (= the forward before the cache existed), alternating sample by sample;
   * ltx_dual_model_prepare_text_dev alone: what the cache costs once per prompt;
   * ltx_op_dual_step alone at the loop's sizes: the one launch per step for CFG, both Euler steps and the next tokens;
-  * an 8-step loop with and without the cache (the cached loop pays prepare_text inside every call).
+  * an 8-step loop with and without the cache (the cached loop pays prepare_text inside every call);
+  * image-to-video next to those rows: the cached forward with two timestep groups (frame-0 tokens at 0, the rest at sigma:
+    ltx_dual_model_forward_groups_dev), the step with a frozen, re-noised prefix of one frame, and the 8-step loop with cond_latent,
+    without and with re-noising. Reported as differences, with no gate on them.
 
 The method is tools/bench_dual_model.py's: each sample is `--batch` back-to-back calls between two HIP events in one process; median
 and minimum over `--iters` samples after `--warmup`; the spread of a row is (p90 - p10) / median. Gate: the cached forward must not be
@@ -100,9 +103,18 @@ def main():
         torch.cuda.synchronize()
         equal = all(torch.equal(a.view(torch.int32), b.view(torch.int32)) for a, b in zip(out_c, out_u))
         info = ctx.dual_model_text_cache_info()
-        tc, tu = measure([cached, uncached], args, torch)
+        # image-to-video: two timestep groups per batch element, {sigma, 0}; the tokens of frame 0 in group 1 (launch_i2v_rowmap's layout)
+        hw = FHW[1] * FHW[2]
+        ts_g = torch.tensor([[0.875, 0.0]] * B, device="cuda")
+        rmap = (torch.arange(T_V, device="cuda") < hw).to(torch.int32).repeat(B, 1) + 2 * torch.arange(B, device="cuda", dtype=torch.int32)[:, None]
+        rmap = rmap.reshape(-1).contiguous()
+        out_g = (torch.empty((B, T_V, 128), device="cuda"), torch.empty((B, T_A, 128), device="cuda"))
+        groups = lambda: ctx.dual_model_forward_groups_dev(lat_v, lat_a, None, None, ts_g, ts, *out_g, *FHW, 2, rmap, text_cache=1, S=S)  # noqa: E731
+        groups()
+        tc, tu, tg = measure([cached, uncached, groups], args, torch)
         (tp,) = measure([prepare], args, torch)
         row(f"forward B={B} text cache", tc)
+        row(f"forward B={B} text cache, image-to-video (2 groups)", tg)
         row(f"forward B={B} no cache (the forward before the cache)", tu)
         row(f"prepare_text B={B} (once per prompt)", tp)
         mc, mu, mp = stats(tc), stats(tu), stats(tp)
@@ -121,6 +133,13 @@ def main():
         step = lambda: ctx.op_dual_step(jv, ja, 0.725, 0.7)  # noqa: E731
         (tst,) = measure([step], args, torch, batch=50)
         row(f"dual_step B={B} ({nv} + {na} elements, 1 launch)", tst)
+        nk = hw * 128
+        jk = dict(job(nv, 0), n_keep=nk, keep_src=rn(nk), keep_noise=rn(nk), keep_scale=0.15)
+        step_keep = lambda: ctx.op_dual_step(jk, ja, 0.725, 0.7)  # noqa: E731
+        (tsk,) = measure([step_keep], args, torch, batch=50)
+        row(f"dual_step B={B} image-to-video ({nk} frozen, re-noised)", tsk)
+        lines.append(f"B={B}: image-to-video forward - text-to-video forward = {stats(tg)[0] - mc[0]:+.1f} us (three more gemv launches, mapped "
+                     f"modulation rows and gates); step with a prefix - step without = {stats(tsk)[0] - stats(tst)[0]:+.2f} us")
         nbytes = (nv + na) * (4 + 4 + (4 if B == 2 else 0) + 4 + 2 * B)
         lines.append(f"B={B}: the step moves {nbytes / 1e6:.2f} MB; it stands for " + ("2 CFG + " if B == 2 else "") +
                      "2 Euler + 2 cast" + (" + 2 copy" if B == 2 else "") + " launches of separate kernels, and in token layout the loop "
@@ -135,9 +154,19 @@ def main():
         loop(1)()
         torch.cuda.synchronize()
         tl1, tl0 = measure([loop(1), loop(0)], args, torch, batch=1)
+        cond, cnoise = rn(1, 128, 1, *FHW[1:]), rn(STEPS, 128, 1, *FHW[1:])
+        i2v = lambda scale: (lambda: ctx.dual_denoise_dev(vl.clone(), al.clone(), sig, lc, *FHW, mask=mask, cfg_scale=3.0 if B == 2 else 1.0,  # noqa: E731
+                                                           cond_latent=cond, image_cond_noise_scale=scale, cond_noise=cnoise if scale > 0 else None))
+        i2v(0.15)()
+        torch.cuda.synchronize()
+        tl1, tl0, ti0, ti1 = measure([loop(1), loop(0), i2v(0.0), i2v(0.15)], args, torch, batch=1)
         row(f"loop {STEPS} steps B={B} text cache (prepare inside)", tl1)
         row(f"loop {STEPS} steps B={B} no cache", tl0)
-        lines.append(f"B={B}: cached loop / uncached loop = {stats(tl1)[0] / stats(tl0)[0]:.3f}")
+        row(f"loop {STEPS} steps B={B} image-to-video, text cache", ti0)
+        row(f"loop {STEPS} steps B={B} image-to-video, re-noised (0.15)", ti1)
+        lines.append(f"B={B}: cached loop / uncached loop = {stats(tl1)[0] / stats(tl0)[0]:.3f}; image-to-video loop - text-to-video loop = "
+                     f"{stats(ti0)[0] - stats(tl1)[0]:+.1f} us without re-noising, {stats(ti1)[0] - stats(tl1)[0]:+.1f} us with it "
+                     f"({STEPS} forwards with groups, one set_frame0, one row map and up to two transposes at entry)")
     lines.append("default of ltx_dual_denoise_args.text_cache: " + ("1 (the gate holds at B 1 and B 2)" if all(verdicts) else
                                                                    "must become 0: the cached forward is slower beyond the spread"))
     lines.append("Not measured: a 48-block model or loop, and the per-block split of the cached saving (k GEMM, k norm, V^T GEMMs).")
