@@ -589,6 +589,37 @@ typedef struct ltx_dual_step_job {
  * keep_noise without keep_src are refused the same way; n_keep = 0 is the step without a prefix, bit for bit. */
 int ltx_op_dual_step(ltx_ctx* ctx, const ltx_dual_step_job* video, const ltx_dual_step_job* audio, float sigma, float sigma_next);
 
+/* One job of ltx_op_dual_restage: one stream's share of the bridge between the two stages of generateVideoWithAudioTwoStage
+ * (LTXPipeline.swift:1712-1752). The video job has x set and transposes; the audio job has x NULL and works in place. */
+typedef struct ltx_dual_restage_job {
+    const float* x;          /* video: [C][T] f32, the upscaled and renormalised latent (ltx_upscale_latent_dev's output); audio: NULL */
+    float* latent;           /* [T][C] f32, TOKEN layout: the stage-2 start latent. video: out; audio: in / out (the packed latent) */
+    uint16_t* tokens;        /* [T][C] bf16: the first stage-2 forward's operand */
+    int C;                   /* channels, a multiple of 32 (128) */
+    long T;                  /* tokens; 0: the job is empty */
+    const float* noise;      /* video [C][T], audio [T][C] (the reference draws it with the PACKED shape, :1734); NULL iff renoise == 0 */
+    float noise_scale;       /* s: z = s * noise + (1.0f - s) * y (:1730-1731, :1735); 0 is valid */
+    int renoise;             /* non-zero: a noise scale is given, noise must be set; 0: noise must be NULL and the blend is skipped */
+    const float* stats;      /* video: [C][2] f32 {mean, variance} of x per channel, or NULL: computed from x */
+    const float* stats_ref;  /* video: [C][2] f32 {mean, variance} of the stage-1 output, or NULL: computed from ref. Both or neither */
+    const float* ref;        /* video: [C][T_ref] f32, the stage-1 output (the AdaIN reference); needed when stats are NULL */
+    long T_ref;
+    float* stats_out;        /* video: [4 * C] f32 or NULL: receives stats then stats_ref, as the kernel used them */
+    long HW;                 /* video: tokens of frame 0 (t < HW), 1 .. T; read with cond */
+    const float* cond;       /* video: [C][HW] f32, the full-resolution image latent, or NULL (text-to-video) */
+    const float* cond_noise; /* video: [C][HW] f32, the first re-noise slice, or NULL: frame 0 = cond */
+    float cond_scale;        /* frame 0 = cond + (cond_scale * cond_noise) * cond_sigma2 (:1765-1769), three separately rounded f32 ops */
+    float cond_sigma2;       /* sigmas2[0] * sigmas2[0], the caller's f32 product */
+} ltx_dual_restage_job;
+/* Kernel hook: AdaIN at factor 1 against the stage-1 output (LatentUtils.swift:201-227), the re-noise of both streams (:1730-1735),
+ * frame 0 of an image-to-video run (:1744, :1765-1769), the transpose to token layout and the bf16 cast, in one launch. Every operation
+ * is rounded on its own (no fused multiply-add, correctly rounded division and square root): latent and tokens are bit-equal to a
+ * float32 replay of those ops from the statistics in stats_out. No AdaIN or re-noise result survives for frame-0 tokens. Either job may be
+ * NULL or empty. C % 32 != 0, a NULL x / latent / tokens with T > 0, HW outside 1 .. T with cond, cond_noise without cond, noise without
+ * renoise or renoise without noise, only one of stats / stats_ref, neither statistics nor ref, or an audio job with a video-only
+ * pointer set: LTX_ERR_INVALID_CONFIGURATION before any launch, nothing written. DEVICE pointers, asynchronous on the context stream. */
+int ltx_op_dual_restage(ltx_ctx* ctx, const ltx_dual_restage_job* video, const ltx_dual_restage_job* audio);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Text-embedding connector (VideoGemmaTextEncoderModel.encodeFromHiddenStates,
  * LTXTextEncoder.swift:574-643 - call site LTXPipeline.swift:640-700): from the 49 Gemma-3 hidden states to the
@@ -727,13 +758,65 @@ typedef struct ltx_dual_denoise_args {
  * at timestep 0 (two timestep groups, ltx_dual_model_forward_groups_dev), it is never stepped, and with re-noising it holds cond +
  * (scale * noise[step]) * sigma^2 during step `step` - written by the step launch of the step before, so no launch is added per step;
  * the result's frame 0 is the last step's noised frame, or cond_latent itself without re-noising. F < 2 with cond_latent:
- * LTX_ERR_INVALID_CONFIGURATION. STG, GE, the two-stage path and sharding are not implemented here. DEVICE pointers except sigmas and
+ * LTX_ERR_INVALID_CONFIGURATION. STG, GE and sharding are not implemented here; the two-stage path is ltx_dual_two_stage below. DEVICE pointers except sigmas and
  * step_stats; asynchronous on the context stream unless step_stats is set. No dual model: LTX_ERR_MODEL_NOT_LOADED; a short struct_size,
  * n_sigmas < 2, a dimension < 1, a NULL latent / sigmas / video_context, a sigma <= 0 before the last, or guidance_rescale > 0 without
  * CFG: LTX_ERR_INVALID_CONFIGURATION. Every check comes before the first launch: a refused call leaves both latents untouched. */
 int ltx_dual_denoise_dev(ltx_ctx* ctx, const ltx_dual_denoise_args* args, ltx_progress_cb cb, void* user);
 /* The same with HOST pointers throughout; staged through the context's staging buffers, synchronous. */
 int ltx_dual_denoise(ltx_ctx* ctx, const ltx_dual_denoise_args* args, ltx_progress_cb cb, void* user);
+
+/* Arguments of ltx_dual_two_stage(_dev); starts with its own size (LTX_DUAL_TWO_STAGE_ARGS_INIT). */
+typedef struct ltx_dual_two_stage_args {
+    uint32_t struct_size;          /* sizeof(ltx_dual_two_stage_args) in the caller's translation unit */
+    int F, H, W;                   /* STAGE-1 latent frames / height / width; stage 2 runs at F, 2H, 2W */
+    int T_a;                       /* audio latent frames */
+    int S;                         /* text tokens */
+    const float* video_latent_in;  /* [1][128][F][H][W] f32: the stage-1 noise, already scaled by sigmas1[0] (:1597); not written */
+    float* video_latent_out;       /* [1][128][F][2H][2W] f32: the final video latent */
+    float* audio_latent;           /* [1][8][T_a][16] f32, in / out, scaled by sigmas1[0] (:1598) */
+    const float* sigmas1;          /* HOST, n_sigmas1 values: the stage-1 schedule (:1587-1593) */
+    int n_sigmas1;
+    const float* sigmas2;          /* HOST, n_sigmas2 values, or NULL: ltx_stage2_sigmas (STAGE_2_DISTILLED_SIGMA_VALUES, :1727) */
+    int n_sigmas2;
+    const float* video_noise2;     /* [1][128][F][2H][2W] f32: the stage-2 video noise (:1730) */
+    const float* audio_noise2;     /* [T_a][128] f32: the stage-2 audio noise, drawn with the PACKED shape (:1734) */
+    const uint16_t* video_context; /* [1][S][caption_channels] bf16 */
+    const uint16_t* audio_context; /* the same shape, or NULL: the video context */
+    const int32_t* mask;           /* [1][S] int32 or NULL; both streams, both stages */
+    float* stage1_out;             /* [1][128][F][H][W] f32 or NULL: receives the stage-1 video latent (the AdaIN reference, :1688) */
+    /* image-to-video (:1600-1610, :1737-1751): both latents or neither; needs F >= 2 */
+    const float* cond_latent1;     /* [1][128][1][H][W] f32: the image encoded at the stage-1 resolution, or NULL */
+    const float* cond_latent2;     /* [1][128][1][2H][2W] f32: the image encoded at the stage-2 resolution, or NULL */
+    float image_cond_noise_scale;  /* > 0 with the noise of a stage: frame 0 is re-noised at the start of every step of it (:1628-1632, :1765-1769) */
+    const float* cond_noise1;      /* [n_sigmas1 - 1][128][1][H][W] f32 or NULL */
+    const float* cond_noise2;      /* [n_sigmas2 - 1][128][1][2H][2W] f32 or NULL */
+} ltx_dual_two_stage_args;
+#define LTX_DUAL_TWO_STAGE_ARGS_INIT {(uint32_t)sizeof(ltx_dual_two_stage_args), 0, 0, 0, 0, 0, NULL, NULL, NULL, NULL, 0, NULL, 0, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, 0.0f, NULL, NULL}
+/* Replaces the two denoise loops of generateVideoWithAudioTwoStage and what lies between them (LTXPipeline.swift:1613-1817); both latents
+ * stay on the device from the first noise to the final latents:
+ *   1. the text side of the dual model once, for both stages (the same B and S)
+ *   2. stage 1 as ltx_dual_denoise runs it: the video by the scheduler's Euler form, the audio by the plain form (:1666-1678),
+ *      image-to-video with two timestep groups
+ *   3. the stage-1 video latent back to the caller's layout: the AdaIN reference (:1688) and the upscaler's input (stage1_out)
+ *   4. the latent upscaler with the VAE's per-channel statistics (:1696-1710)
+ *   5. the per-channel statistics of the upscaled latent and of the stage-1 output
+ *   6. ONE launch (ltx_op_dual_restage): AdaIN (:1712), the re-noise of both streams by sigmas2[0] (:1730-1735), frame 0 of stage 2
+ *      (:1744, and step 0's :1765-1769), token layout and the first bf16 tokens
+ *   7. stage 2 from that token state: BOTH streams by the plain form x + (sigma_next - sigma) * v (:1799-1811), which is not the
+ *      scheduler's form bit for bit; image-to-video groups at the stage-2 shape
+ *   8. the final latents back to the caller's layouts
+ * The path is distilled: one forward per step and no CFG (:1646, :1783), no STG, no GE. The progress callback reports stage 1 as
+ * (step, n_sigmas1 - 1) and stage 2 as (n_sigmas1 - 1 + step, n_sigmas1 - 1 + n_sigmas2 - 1) (:1623, :1760). Noise is the caller's, in
+ * the reference's order of drawing: (1) the stage-1 video noise, (2) the audio noise [1][8][T_a][16], (3) one frame-0 slice per stage-1
+ * step, (4) the stage-2 video noise, (5) the packed audio noise [T_a][128], (6) one frame-0 slice per stage-2 step. The VAE and audio
+ * decode legs follow through ltx_vae_decode and ltx_audio_decode. No dual model, upscaler or VAE (statistics): LTX_ERR_MODEL_NOT_LOADED;
+ * a short struct_size, a NULL required pointer, a dimension < 1, fewer than 2 sigmas, a sigma <= 0 before the last of either schedule,
+ * only one of the two image latents, or F < 2 with them: LTX_ERR_INVALID_CONFIGURATION. Every check comes before the first launch: a
+ * refused call leaves both latents untouched. DEVICE pointers except the sigmas; asynchronous on the context stream. */
+int ltx_dual_two_stage_dev(ltx_ctx* ctx, const ltx_dual_two_stage_args* args, ltx_progress_cb cb, void* user);
+/* The same with HOST pointers throughout; staged through the context's staging buffers, synchronous. */
+int ltx_dual_two_stage(ltx_ctx* ctx, const ltx_dual_two_stage_args* args, ltx_progress_cb cb, void* user);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Multi-GPU: one process per GPU, one ltx_ctx per process, RCCL over xGMI called by the library itself (librccl is loaded

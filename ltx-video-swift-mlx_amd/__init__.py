@@ -16,8 +16,8 @@ import numpy as np
 
 from . import _lib
 from ._lib import (ALLGATHER_FN, DIST_ID_BYTES, SHARD_CFG, SHARD_NONE, SHARD_SEQUENCE, ConnectorConfig, PROGRESS_CB, DenoiseOptions,
-                   DualBlockConfig, DualDenoiseArgs, DualForwardArgs, DualModelConfig, DualModelForwardArgs, DualStepJob, GemmTileLaunch, GemvJob,
-                   LTXError, NormMod2Job, TransformerConfig, lib)
+                   DualBlockConfig, DualDenoiseArgs, DualForwardArgs, DualModelConfig, DualModelForwardArgs, DualRestageJob, DualStepJob, DualTwoStageArgs,
+                   GemmTileLaunch, GemvJob, LTXError, NormMod2Job, TransformerConfig, lib)
 
 __version__ = lib.ltx_version().decode()
 
@@ -772,6 +772,11 @@ class Context:
         self._ck(lib.ltx_upscale_latent(self._h, _ptr(lat), F, H, W, _ptr(out)))
         return out
 
+    def upscale_latent_dev(self, latent, out):
+        """``ltx_upscale_latent_dev``: device tensors, latent [1,128,F,H,W] f32 -> out [1,128,F,2H,2W] f32; asynchronous."""
+        _, _, F, H, W = latent.shape
+        self._ck(lib.ltx_upscale_latent_dev(self._h, _ptr(latent), F, H, W, _ptr(out)))
+
     def adain_filter_latent(self, latent, reference, factor=1.0):
         lat = np.ascontiguousarray(latent, dtype=np.float32).copy()
         ref = np.ascontiguousarray(reference, dtype=np.float32)
@@ -1135,6 +1140,91 @@ class Context:
             o.n = j["n"] if "n" in j else j["latent"].numel()
             return C.byref(o)
         self._ck(lib.ltx_op_dual_step(self._h, job(video), job(audio), sigma, sigma_next))
+
+    def op_dual_restage(self, video=None, audio=None):
+        """``ltx_op_dual_restage``: each job is None or a dict of device tensors and scalars. video: x= [C][T] f32, latent= [T][C] f32 (out),
+        tokens= [T][C] bf16 (out), noise= [C][T] or None, noise_scale=, and either stats= / stats_ref= ([C][2]) or ref= [C][T_ref] (the
+        stage-1 output; the statistics are then computed), stats_out= [4*C] or None, cond= [C][HW] or None, cond_noise=, cond_scale=,
+        cond_sigma2=. audio: latent= [T][C] f32 (in / out), tokens=, noise= [T][C] or None, noise_scale=. ``renoise`` defaults to whether
+        noise is given; C, T, T_ref and HW default to the tensors' shapes."""
+        def job(j, is_video):
+            if j is None:
+                return None
+            o = DualRestageJob()
+            for k in ("x", "latent", "tokens", "noise", "stats", "stats_ref", "ref", "stats_out", "cond", "cond_noise"):
+                t = j.get(k)
+                setattr(o, k, None if t is None else t.data_ptr())
+            lat = j.get("latent")
+            if is_video and j.get("x") is not None:
+                o.C, o.T = j["x"].shape[0], j["x"][0].numel()
+            elif lat is not None:
+                o.C, o.T = lat.shape[-1], lat.numel() // lat.shape[-1]
+            o.C, o.T = j.get("C", o.C), j.get("T", o.T)
+            o.noise_scale = j.get("noise_scale", 0.0)
+            o.renoise = int(j.get("renoise", j.get("noise") is not None))
+            o.T_ref = j.get("T_ref", j["ref"][0].numel() if j.get("ref") is not None else 0)
+            o.HW = j.get("HW", j["cond"][0].numel() if j.get("cond") is not None else 0)
+            o.cond_scale, o.cond_sigma2 = j.get("cond_scale", 0.0), j.get("cond_sigma2", 0.0)
+            return C.byref(o)
+        self._ck(lib.ltx_op_dual_restage(self._h, job(video, True), job(audio, False)))
+
+    @staticmethod
+    def _dual_two_stage_args(video_latent_in, video_latent_out, audio_latent, sg1, sg2, video_noise2, audio_noise2, video_context, audio_context,
+                             mask, F, H, W, T_a, S, stage1_out, cond_latent1, cond_latent2, image_cond_noise_scale, cond_noise1, cond_noise2,
+                             struct_size=None):
+        a = DualTwoStageArgs()
+        a.struct_size = C.sizeof(DualTwoStageArgs) if struct_size is None else struct_size
+        a.F, a.H, a.W, a.T_a, a.S = F, H, W, T_a, S
+        a.video_latent_in, a.video_latent_out, a.audio_latent = _ptr(video_latent_in), _ptr(video_latent_out), _ptr(audio_latent)
+        a.sigmas1, a.n_sigmas1 = sg1.ctypes.data_as(C.POINTER(C.c_float)), len(sg1)
+        if sg2 is not None:
+            a.sigmas2, a.n_sigmas2 = sg2.ctypes.data_as(C.POINTER(C.c_float)), len(sg2)
+        a.video_noise2, a.audio_noise2 = _ptr(video_noise2), _ptr(audio_noise2)
+        a.video_context, a.audio_context, a.mask = _ptr(video_context), _ptr(audio_context), _ptr(mask)
+        a.stage1_out = _ptr(stage1_out)
+        a.cond_latent1, a.cond_latent2, a.image_cond_noise_scale = _ptr(cond_latent1), _ptr(cond_latent2), image_cond_noise_scale
+        a.cond_noise1, a.cond_noise2 = _ptr(cond_noise1), _ptr(cond_noise2)
+        return a
+
+    def dual_two_stage_dev(self, video_latent_in, video_latent_out, audio_latent, sigmas1, video_noise2, audio_noise2, video_context, F, H, W,
+                           sigmas2=None, audio_context=None, mask=None, stage1_out=None, cond_latent1=None, cond_latent2=None,
+                           image_cond_noise_scale=0.0, cond_noise1=None, cond_noise2=None, on_progress=None, T_a=None, S=None, struct_size=None):
+        """``ltx_dual_two_stage_dev``: both stages of the two-stage video + audio path on device tensors. video_latent_in [1][128][F][H][W] f32
+        scaled by sigmas1[0] (not written), video_latent_out [1][128][F][2H][2W] f32, audio_latent [1][8][T_a][16] f32 in place;
+        video_noise2 as video_latent_out, audio_noise2 [T_a][128] (the packed shape); sigmas2 None = ``stage2_sigmas()``. Image-to-video:
+        cond_latent1 [1][128][1][H][W] and cond_latent2 [1][128][1][2H][2W], with cond_noise1 / cond_noise2 [steps][128][1][h][w] for
+        re-noising. F, H, W are the STAGE-1 latent dims."""
+        sg1 = np.ascontiguousarray(sigmas1, dtype=np.float32)
+        sg2 = None if sigmas2 is None else np.ascontiguousarray(sigmas2, dtype=np.float32)
+        cb = PROGRESS_CB(on_progress if on_progress else (lambda s, t, sig, u: None))
+        a = self._dual_two_stage_args(video_latent_in, video_latent_out, audio_latent, sg1, sg2, video_noise2, audio_noise2, video_context,
+                                      audio_context, mask, F, H, W, audio_latent.shape[2] if T_a is None else T_a,
+                                      video_context.shape[1] if S is None else S, stage1_out, cond_latent1, cond_latent2, image_cond_noise_scale,
+                                      cond_noise1, cond_noise2, struct_size)
+        self._ck(lib.ltx_dual_two_stage_dev(self._h, C.byref(a), cb, None))
+
+    def dual_two_stage(self, video_latent, audio_latent, sigmas1, video_noise2, audio_noise2, video_context_bf16, sigmas2=None,
+                       audio_context_bf16=None, mask=None, stage1_out=False, cond_latent1=None, cond_latent2=None, image_cond_noise_scale=0.0,
+                       cond_noise1=None, cond_noise2=None, on_progress=None):
+        """``ltx_dual_two_stage``: the same with host arrays (contexts as bf16 bit patterns, uint16). video_latent is the stage-1 latent
+        [1][128][F][H][W]. Returns (video_latent [1][128][F][2H][2W], audio_latent) or, with ``stage1_out``, (video, audio, stage-1 video)."""
+        f32 = lambda x: None if x is None else np.ascontiguousarray(x, dtype=np.float32)  # noqa: E731
+        v = f32(video_latent)
+        _, Cc, F, H, W = v.shape
+        out = np.zeros((1, Cc, F, 2 * H, 2 * W), np.float32)
+        au = f32(audio_latent).copy()
+        s1 = np.zeros_like(v) if stage1_out else None
+        sg1 = f32(sigmas1)
+        sg2 = f32(sigmas2)
+        cv = np.ascontiguousarray(video_context_bf16)
+        ca = None if audio_context_bf16 is None else np.ascontiguousarray(audio_context_bf16)
+        mk = None if mask is None else np.ascontiguousarray(mask, dtype=np.int32)
+        cb = PROGRESS_CB(on_progress if on_progress else (lambda s, t, sig, u: None))
+        keep = [f32(video_noise2), f32(audio_noise2), f32(cond_latent1), f32(cond_latent2), f32(cond_noise1), f32(cond_noise2)]
+        a = self._dual_two_stage_args(v, out, au, sg1, sg2, keep[0], keep[1], cv, ca, mk, F, H, W, au.shape[2], cv.shape[1], s1, keep[2], keep[3],
+                                      image_cond_noise_scale, keep[4], keep[5])
+        self._ck(lib.ltx_dual_two_stage(self._h, C.byref(a), cb, None))
+        return (out, au, s1) if stage1_out else (out, au)
 
     def op_gemv_group(self, jobs, M=None, n_jobs=None):
         """``ltx_op_gemv_group``: each job is a dict(a= [M][K] f32, W= [N][K] bf16, out= a 2-D f32 view whose row stride is ldo, bias=

@@ -138,6 +138,26 @@ class DualDenoiseArgs(C.Structure):
                 ("image_cond_noise_scale", C.c_float), ("cond_noise", C.c_void_p)]
 
 
+class DualRestageJob(C.Structure):
+    """``ltx_dual_restage_job``: one job of ``ltx_op_dual_restage``."""
+
+    _fields_ = [("x", C.c_void_p), ("latent", C.c_void_p), ("tokens", C.c_void_p), ("C", C.c_int), ("T", C.c_long), ("noise", C.c_void_p),
+                ("noise_scale", C.c_float), ("renoise", C.c_int), ("stats", C.c_void_p), ("stats_ref", C.c_void_p), ("ref", C.c_void_p),
+                ("T_ref", C.c_long), ("stats_out", C.c_void_p), ("HW", C.c_long), ("cond", C.c_void_p), ("cond_noise", C.c_void_p),
+                ("cond_scale", C.c_float), ("cond_sigma2", C.c_float)]
+
+
+class DualTwoStageArgs(C.Structure):
+    """``ltx_dual_two_stage_args``: the two loops of generateVideoWithAudioTwoStage and the bridge between them (LTXPipeline.swift:1613-1817)."""
+
+    _fields_ = [("struct_size", C.c_uint32), ("F", C.c_int), ("H", C.c_int), ("W", C.c_int), ("T_a", C.c_int), ("S", C.c_int),
+                ("video_latent_in", C.c_void_p), ("video_latent_out", C.c_void_p), ("audio_latent", C.c_void_p),
+                ("sigmas1", C.POINTER(C.c_float)), ("n_sigmas1", C.c_int), ("sigmas2", C.POINTER(C.c_float)), ("n_sigmas2", C.c_int),
+                ("video_noise2", C.c_void_p), ("audio_noise2", C.c_void_p), ("video_context", C.c_void_p), ("audio_context", C.c_void_p),
+                ("mask", C.c_void_p), ("stage1_out", C.c_void_p), ("cond_latent1", C.c_void_p), ("cond_latent2", C.c_void_p),
+                ("image_cond_noise_scale", C.c_float), ("cond_noise1", C.c_void_p), ("cond_noise2", C.c_void_p)]
+
+
 def _load():
     if not os.path.exists(SO_PATH):
         raise ImportError(
@@ -305,6 +325,9 @@ SIGNATURES = {
     "ltx_op_dual_step": (_i, [_vp, C.POINTER(DualStepJob), C.POINTER(DualStepJob), _f, _f]),
     "ltx_dual_denoise_dev": (_i, [_vp, C.POINTER(DualDenoiseArgs), PROGRESS_CB, _vp]),
     "ltx_dual_denoise": (_i, [_vp, C.POINTER(DualDenoiseArgs), PROGRESS_CB, _vp]),
+    "ltx_op_dual_restage": (_i, [_vp, C.POINTER(DualRestageJob), C.POINTER(DualRestageJob)]),
+    "ltx_dual_two_stage_dev": (_i, [_vp, C.POINTER(DualTwoStageArgs), PROGRESS_CB, _vp]),
+    "ltx_dual_two_stage": (_i, [_vp, C.POINTER(DualTwoStageArgs), PROGRESS_CB, _vp]),
     "ltx_op_attention_hd": (_i, [_vp, _vp, _vp, _vp, _l, _vp, _i, _i, _i, _i, _i, _f, _vp]),
     "ltx_attention_hd_workgroup_queries": (_i, [_i, _i, _i, _i]),
     "ltx_op_qknorm_rope_hd": (_i, [_vp, _vp, _l, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _vp]),

@@ -418,6 +418,45 @@ int ltx_op_dual_step(ltx_ctx* ctx, const ltx_dual_step_job* video, const ltx_dua
     });
 }
 
+int ltx_op_dual_restage(ltx_ctx* ctx, const ltx_dual_restage_job* video, const ltx_dual_restage_job* audio) {
+    return with_ctx(ctx, [&] {
+        auto job = [](const ltx_dual_restage_job* j) {
+            DualRestageJob o;
+            if (!j) return o;
+            o.x = j->x; o.latent = j->latent; o.tokens = j->tokens; o.C = j->C; o.T = j->T;
+            o.noise = j->noise; o.noise_scale = j->noise_scale; o.renoise = j->renoise;
+            o.stats = j->stats; o.stats_ref = j->stats_ref;
+            o.HW = j->HW; o.cond = j->cond; o.cond_noise = j->cond_noise; o.cond_scale = j->cond_scale; o.cond_sigma2 = j->cond_sigma2;
+            return o;
+        };
+        DualRestageJob v = job(video), a = job(audio);
+        const bool compute = v.T > 0 && !v.stats && !v.stats_ref;  // no statistics: two launch_mean_var, as ltx_adain_filter_latent makes them
+        float* ws = nullptr;
+        if (v.T > 0) {
+            LTX_REQUIRE((v.stats != nullptr) == (v.stats_ref != nullptr), "dual_restage: give stats and stats_ref, or neither");
+            LTX_REQUIRE(v.C >= 32 && v.C <= 4096 && v.C % 32 == 0, "dual_restage: C=%d must be a multiple of 32 (32 .. 4096)", v.C);
+            if (compute) {
+                LTX_REQUIRE(video->ref && video->T_ref >= 1 && video->T_ref <= (1L << 24), "dual_restage: no statistics and no reference latent to take them from");
+                ws = video->stats_out;
+                if (!ws) {
+                    ctx->dn_stats.ensure((size_t)v.C * 4 * 4 + 64);
+                    ws = ctx->dn_stats.as<float>();
+                }
+                v.stats = ws; v.stats_ref = ws + 2 * v.C;
+            }
+        }
+        dual_restage_check(v, a);  // every check before the first launch
+        if (compute) {
+            launch_mean_var(v.x, v.T, v.C, ws, ctx->stream);
+            launch_mean_var(video->ref, video->T_ref, v.C, ws + 2 * v.C, ctx->stream);
+        } else if (v.T > 0 && video->stats_out) {
+            HIP_CHECK(hipMemcpyAsync(video->stats_out, v.stats, (size_t)2 * v.C * 4, hipMemcpyDeviceToDevice, ctx->stream));
+            HIP_CHECK(hipMemcpyAsync(video->stats_out + 2 * v.C, v.stats_ref, (size_t)2 * v.C * 4, hipMemcpyDeviceToDevice, ctx->stream));
+        }
+        launch_dual_restage(v, a, ctx->stream);
+    });
+}
+
 int ltx_op_qknorm_rope_pair(ltx_ctx* ctx, const void* x0, const float* w0, uint16_t* out0, const void* x1, const float* w1,
                             uint16_t* out1, long ldx, long ldo, const float* cos_t, const float* sin_t, int T, int rows, int D,
                             float eps, float out_scale0, int x_bf16) {

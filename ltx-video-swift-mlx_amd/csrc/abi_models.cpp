@@ -11,6 +11,7 @@
 #include "dual_block.h"
 #include "dual_denoise.h"
 #include "dual_model.h"
+#include "dual_two_stage.h"
 #include "connector.h"
 #include "dist.h"
 #include "elementwise.h"
@@ -1085,6 +1086,92 @@ int ltx_dual_denoise(ltx_ctx* ctx, const ltx_dual_denoise_args* args, ltx_progre
         dual_denoise_run(ctx, p);
         stage_out(ctx, host_v, d_v, n_v);
         stage_out(ctx, host_a, d_a, n_a);
+        stage_sync(ctx);
+    });
+}
+
+/* ---- the two-stage video + audio path (dual_two_stage.h) ---- */
+namespace {
+void dual_two_stage_params(ltx_ctx* ctx, const ltx_dual_two_stage_args* args, ltx_progress_cb cb, void* user, const char* who, DualTwoStageParams& p) {
+    need(ctx->dual_model, kNoDualModel);
+    need(ctx->upscaler, kNoUpscaler);
+    need(ctx->vae, kNoVae);
+    LTX_REQUIRE(args != nullptr, "%s: null arguments", who);
+    const size_t sz = args->struct_size;
+    LTX_REQUIRE(sz >= sizeof(ltx_dual_two_stage_args) && sz <= 4096,
+                "ltx_dual_two_stage_args.struct_size = %zu: set it to sizeof(ltx_dual_two_stage_args) (LTX_DUAL_TWO_STAGE_ARGS_INIT); this library is ABI revision %d",
+                sz, LTX_ABI_VERSION);
+    p.F = args->F; p.H = args->H; p.W = args->W; p.T_a = args->T_a; p.S = args->S;
+    p.video_latent_in = args->video_latent_in; p.video_latent_out = args->video_latent_out; p.audio_latent = args->audio_latent;
+    p.sigmas1 = args->sigmas1; p.n_sigmas1 = args->n_sigmas1; p.sigmas2 = args->sigmas2; p.n_sigmas2 = args->n_sigmas2;
+    p.video_noise2 = args->video_noise2; p.audio_noise2 = args->audio_noise2;
+    p.video_context = args->video_context; p.audio_context = args->audio_context; p.mask = args->mask;
+    p.stage1_out = args->stage1_out;
+    p.cond_latent1 = args->cond_latent1; p.cond_latent2 = args->cond_latent2; p.image_cond_noise_scale = args->image_cond_noise_scale;
+    p.cond_noise1 = args->cond_noise1; p.cond_noise2 = args->cond_noise2;
+    p.progress = cb; p.user = user;
+}
+}  // namespace
+
+int ltx_dual_two_stage_dev(ltx_ctx* ctx, const ltx_dual_two_stage_args* args, ltx_progress_cb cb, void* user) {
+    return with_ctx(ctx, [&] {
+        DualTwoStageParams p;
+        dual_two_stage_params(ctx, args, cb, user, "ltx_dual_two_stage_dev", p);
+        dual_two_stage_run(ctx, p);
+    });
+}
+
+int ltx_dual_two_stage(ltx_ctx* ctx, const ltx_dual_two_stage_args* args, ltx_progress_cb cb, void* user) {
+    return with_ctx(ctx, [&] {
+        DualTwoStageParams p;
+        dual_two_stage_params(ctx, args, cb, user, "ltx_dual_two_stage", p);
+        dual_two_stage_check(ctx, p);  // on the host pointers: refuse before anything is staged
+        const DualModel* m = ctx->dual_model;
+        const int steps1 = p.n_sigmas1 - 1, steps2 = (p.sigmas2 ? p.n_sigmas2 : 4) - 1;
+        const size_t n_v1 = (size_t)m->cfg.in_channels * p.F * p.H * p.W * 4, n_v2 = 4 * n_v1, n_a = (size_t)128 * p.T_a * 4;
+        const size_t n_c1 = n_v1 / p.F, n_c2 = n_v2 / p.F;
+        const size_t n_ctx = (size_t)p.S * m->cfg.caption_channels * 2, n_mask = (size_t)p.S * 4;
+        DevBuf &d_v = ctx->h2d[H2D_DENOISE_LATENT], &d_a = ctx->h2d[H2D_DUAL_AUDIO_LATENT], &d_cv = ctx->h2d[H2D_DENOISE_CONTEXT],
+               &d_ca = ctx->h2d[H2D_DUAL_AUDIO_CONTEXT], &d_mask = ctx->h2d[H2D_DENOISE_MASK], &d_nv = ctx->h2d[H2D_DUAL2_VIDEO_NOISE],
+               &d_na = ctx->h2d[H2D_DUAL2_AUDIO_NOISE], &d_out = ctx->h2d[H2D_DUAL2_VIDEO_OUT];
+        DevBuf d_s1, d_c2, d_n2;  // freed on return, after the synchronisation
+        float *host_out = p.video_latent_out, *host_a = p.audio_latent, *host_s1 = p.stage1_out;
+        stage_in(ctx, d_v, p.video_latent_in, n_v1);
+        stage_in(ctx, d_a, host_a, n_a);
+        stage_in(ctx, d_nv, p.video_noise2, n_v2);
+        stage_in(ctx, d_na, p.audio_noise2, n_a);
+        stage_in(ctx, d_cv, p.video_context, n_ctx);
+        if (p.audio_context) stage_in(ctx, d_ca, p.audio_context, n_ctx);
+        if (p.mask) stage_in(ctx, d_mask, p.mask, n_mask);
+        d_out.ensure(n_v2);
+        p.video_latent_in = d_v.as<float>(); p.video_latent_out = d_out.as<float>(); p.audio_latent = d_a.as<float>();
+        p.video_noise2 = d_nv.as<float>(); p.audio_noise2 = d_na.as<float>();
+        p.video_context = d_cv.as<bf16_t>();
+        p.audio_context = p.audio_context ? d_ca.as<bf16_t>() : nullptr;
+        p.mask = p.mask ? d_mask.as<int32_t>() : nullptr;
+        if (host_s1) {
+            d_s1.ensure(n_v1);
+            p.stage1_out = d_s1.as<float>();
+        }
+        if (p.cond_latent1) {  // the image latents and their re-noising slices; stage 1's as ltx_dual_denoise stages them
+            stage_in(ctx, ctx->i2v_cond, p.cond_latent1, n_c1);
+            stage_in(ctx, d_c2, p.cond_latent2, n_c2);
+            p.cond_latent1 = ctx->i2v_cond.as<float>(); p.cond_latent2 = d_c2.as<float>();
+            if (p.cond_noise1) {
+                stage_in(ctx, ctx->i2v_noise, p.cond_noise1, n_c1 * (size_t)steps1);
+                p.cond_noise1 = ctx->i2v_noise.as<float>();
+            }
+            if (p.cond_noise2) {
+                stage_in(ctx, d_n2, p.cond_noise2, n_c2 * (size_t)steps2);
+                p.cond_noise2 = d_n2.as<float>();
+            }
+        } else {
+            p.cond_noise1 = p.cond_noise2 = nullptr;
+        }
+        dual_two_stage_run(ctx, p);
+        stage_out(ctx, host_out, d_out, n_v2);
+        stage_out(ctx, host_a, d_a, n_a);
+        if (host_s1) stage_out(ctx, host_s1, d_s1, n_v1);
         stage_sync(ctx);
     });
 }

@@ -21,12 +21,16 @@
 //             re-noises at the start of a step (:1289-1294), where that step's sigma is this step's sigma_next; the last step re-noises
 //             nothing, so the final frame 0 is the last noised one, or cond itself without noise. No other launch per step.
 // Text-to-video (cond_latent null) runs the launches it ran before the image-to-video path existed, with the same bits.
-// Every check comes before the first launch: a refused call leaves both latents untouched. STG, GE, the two-stage path and sharding
-// are not implemented.
+// Every check comes before the first launch: a refused call leaves both latents untouched. STG, GE and sharding are not implemented.
+// The run is entry, loop and exit (DualDenoiseParams::phases). The two-stage path (dual_two_stage.h) runs stage 1 as entry + loop + the
+// video exit, and stage 2 as loop + exit from the token-layout state its restage launch wrote into the same allocation: the allocation
+// is carved ONCE for the larger stage (reserve_*), so no offset moves and the audio latent stays where stage 1 left it.
 #pragma once
 #include "../../include/ltxhip.h"
 #include "runtime.h"
 
+// the parts of a run (DualDenoiseParams::phases)
+enum { DUAL_DN_ENTRY = 1, DUAL_DN_LOOP = 2, DUAL_DN_EXIT_VIDEO = 4, DUAL_DN_EXIT_AUDIO = 8, DUAL_DN_ALL = 15 };
 struct DualDenoiseParams {
     int F = 0, H = 0, W = 0, T_a = 0, S = 0;
     float* video_latent = nullptr;          // device [1][C][F][H][W] f32, in / out, scaled by sigmas[0]
@@ -46,5 +50,24 @@ struct DualDenoiseParams {
     const float* cond_latent = nullptr;     // [1][C][1][H][W] f32 or null (text-to-video)
     float image_cond_noise_scale = 0.0f;
     const float* cond_noise = nullptr;      // [n_sigmas - 1][C][1][H][W] f32 or null (no re-noising)
+    // what the two-stage path adds; the defaults are ltx_dual_denoise
+    int video_form = 0;                     // the video stream's Euler form (DualStepJob::form): 0 the scheduler's, 1 the plain one (stage 2, :1799-1811)
+    int phases = DUAL_DN_ALL;               // which parts run. Without DUAL_DN_ENTRY the latents, their tokens and frame 0 are taken as they
+                                            // stand in the allocation (token layout), and the text cache as it is
+    int progress_first = 0, progress_total = 0;  // the callback gets (progress_first + step, progress_total, or this run's steps when 0)
+    long reserve_Tv = 0;                    // carve the allocation for at least this many video tokens, ...
+    int reserve_steps = 0;                  // ... this many steps ...
+    bool reserve_renoise = false;           // ... and the re-noising slices, so that two runs of different shapes share every offset
 };
+// where the token-layout state of a run lives in ctx->dual_dn (valid until the allocation grows)
+struct DualDenoiseState {
+    float* xv = nullptr;      // [Tv][C] f32
+    float* xa = nullptr;      // [T_a][128] f32
+    bf16_t* tok_v = nullptr;  // [B][Tv][C] bf16
+    bf16_t* tok_a = nullptr;  // [B][T_a][128] bf16
+};
+// every check of dual_denoise_run and nothing else: for a caller that must refuse before a launch of its own
+void dual_denoise_check(ltx_ctx* ctx, const DualDenoiseParams& p);
+// sizes the allocation for `p` (growing it if needed) and returns the state pointers
+DualDenoiseState dual_denoise_state(ltx_ctx* ctx, const DualDenoiseParams& p);
 void dual_denoise_run(ltx_ctx* ctx, const DualDenoiseParams& p);

@@ -140,6 +140,37 @@ struct DualStepJob {
     float keep_scale = 0.0f;
 };
 void launch_dual_step(const DualStepJob& video, const DualStepJob& audio, float sigma, float sigma_next, hipStream_t stream);
+// The bridge between the two stages of generateVideoWithAudioTwoStage (LTXPipeline.swift:1712-1752, and step 0's :1765-1769) in ONE
+// launch: two jobs share one grid (video, audio; T == 0: the job is empty). Per element, every operation rounded on its own as the
+// reference's separate array ops round (no contraction, correctly rounded division and square root):
+//   video (x set): reads the upscaled latent and the noise in the caller's layout [C][T], writes the stage-2 start latent and its bf16
+//     tokens in TOKEN layout [T][C] through a padded 32x33 LDS tile (reads coalesced along t, 16-byte f32 / 8-byte bf16 stores along c)
+//       y = ((x - mu) / (sqrt(var) + 1e-8f)) * sqrt(var_ref) + mu_ref        AdaIN at factor 1 (LatentUtils.swift:201-227)
+//       z = s * noise + (1.0f - s) * y                                        (:1730-1731; 1.0f - s is one f32 scalar)
+//       t < HW with cond: z = cond, or cond + (cond_scale * cond_noise) * cond_sigma2 (:1744, :1765-1769; set_frame0_kernel's three ops);
+//       no AdaIN or re-noise result survives there
+//   audio (x null): in place on the packed latent [T][C]: z = s * noise + (1.0f - s) * x (:1734-1735), and its bf16 tokens
+// stats / stats_ref are launch_mean_var's {mean, var} pairs per channel. C % 32 == 0, HW <= T, noise exactly when renoise is set; every
+// check comes before the launch (dual_restage_check: the checks alone, for a caller that has launches of its own to make first).
+struct DualRestageJob {
+    const float* x = nullptr;           // video: [C][T] f32; null: the audio job
+    float* latent = nullptr;            // [T][C] f32: out (video), in / out (audio)
+    bf16_t* tokens = nullptr;           // [T][C] bf16
+    int C = 0;
+    long T = 0;
+    const float* noise = nullptr;       // video [C][T], audio [T][C]; set exactly when renoise is
+    float noise_scale = 0.0f;           // s
+    int renoise = 0;
+    const float* stats = nullptr;       // video: [C][2] {mean, var} of x
+    const float* stats_ref = nullptr;   // video: [C][2] {mean, var} of the stage-1 output
+    long HW = 0;                        // video: tokens of frame 0; read with cond
+    const float* cond = nullptr;        // video: [C][HW] f32 or null
+    const float* cond_noise = nullptr;  // video: [C][HW] f32 or null
+    float cond_scale = 0.0f;
+    float cond_sigma2 = 0.0f;
+};
+void dual_restage_check(const DualRestageJob& video, const DualRestageJob& audio);
+void launch_dual_restage(const DualRestageJob& video, const DualRestageJob& audio, hipStream_t stream);
 // CFG combine v = cond + (scale-1)*(cond-uncond) (LatentUtils.swift:131-141)
 void launch_cfg_combine(const float* uncond, const float* cond, float scale, float* out, long n, hipStream_t stream);
 // out = a + s*(a - b)   (STG: LTXPipeline.swift:920) ; out = g*(a-b)+b (GE: :924-927) share one kernel

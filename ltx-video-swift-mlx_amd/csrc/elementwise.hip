@@ -734,6 +734,88 @@ __global__ __launch_bounds__(256) void dual_step_kernel(const DualStepJob j0, co
         if (copies == 2) *(uint2*)(tok + n + i) = pk;
     }
 }
+// The bridge between the two stages of the two-stage video + audio path (elementwise.h, DualRestageJob). Workgroups 0 .. wgs_v-1 each
+// take one 32 (t) x 32 (c) tile of the video job, the rest stride over the audio job (uniform per workgroup). Contraction is off for
+// the whole body; division and square root are the correctly rounded ones.
+__global__ __launch_bounds__(256) void dual_restage_kernel(const DualRestageJob jv, const DualRestageJob ja, int wgs_v) {
+#pragma clang fp contract(off)
+    __shared__ float tile[32][33];
+    if ((int)blockIdx.x >= wgs_v) {  // audio: elementwise, in place
+        const int wg = (int)blockIdx.x - wgs_v, nwg = (int)gridDim.x - wgs_v;
+        const long n = ja.T * ja.C;  // C % 32 == 0: whole vectors only
+        float* __restrict__ lat = ja.latent;
+        const float* __restrict__ nz = ja.noise;
+        bf16_t* __restrict__ tok = ja.tokens;
+        const float s = ja.noise_scale, r = 1.0f - s;
+        const long stride = (long)nwg * 256 * 4;
+        for (long i = ((long)wg * 256 + threadIdx.x) * 4; i < n; i += stride) {
+            f32x4 y = *(const f32x4*)(lat + i);
+            if (nz) {
+                const f32x4 z = *(const f32x4*)(nz + i);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const float a = s * z[e];
+                    const float b = r * y[e];
+                    y[e] = a + b;
+                }
+                *(f32x4*)(lat + i) = y;
+            }
+            uint2 pk;
+            pk.x = pack_bf16x2(y[0], y[1]);
+            pk.y = pack_bf16x2(y[2], y[3]);
+            *(uint2*)(tok + i) = pk;
+        }
+        return;
+    }
+    const long T = jv.T, HW = jv.cond ? jv.HW : 0;
+    const int C = jv.C;
+    const int nt = (int)((T + 31) >> 5);
+    const long t0 = (long)((int)blockIdx.x % nt) * 32;
+    const int c0 = ((int)blockIdx.x / nt) * 32;  // C % 32 == 0: every channel of the tile exists
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    const float s = jv.noise_scale, r = 1.0f - s;
+    const long t = t0 + tx;
+    for (int k = ty; k < 32; k += 8) {
+        const int c = c0 + k;
+        float z = 0.f;
+        if (t < HW) {  // frame 0 with an image latent
+            z = jv.cond[(long)c * HW + t];
+            if (jv.cond_noise) {
+                const float a = jv.cond_scale * jv.cond_noise[(long)c * HW + t];
+                const float b = a * jv.cond_sigma2;
+                z = z + b;
+            }
+        } else if (t < T) {
+            const float mu = jv.stats[2 * c], sd = sqrtf(jv.stats[2 * c + 1]);
+            const float mur = jv.stats_ref[2 * c], sdr = sqrtf(jv.stats_ref[2 * c + 1]);
+            const float d = jv.x[(long)c * T + t] - mu;
+            const float den = sd + 1e-8f;
+            const float q = __fdiv_rn(d, den);
+            const float m = q * sdr;
+            z = m + mur;
+            if (jv.noise) {
+                const float a = s * jv.noise[(long)c * T + t];
+                const float b = r * z;
+                z = a + b;
+            }
+        }
+        tile[k][tx] = z;
+    }
+    __syncthreads();
+    const int tr = threadIdx.x >> 3, cq = (threadIdx.x & 7) * 4;  // one token row, four channels
+    const long to = t0 + tr;
+    if (to < T) {
+        f32x4 y;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) y[e] = tile[cq + e][tr];
+        const long o = to * C + c0 + cq;
+        *(f32x4*)(jv.latent + o) = y;
+        uint2 pk;
+        pk.x = pack_bf16x2(y[0], y[1]);
+        pk.y = pack_bf16x2(y[2], y[3]);
+        *(uint2*)(jv.tokens + o) = pk;
+    }
+}
 __global__ void cfg_combine_kernel(const float* __restrict__ uncond, const float* __restrict__ cond, float sm1,
                                    float* __restrict__ out, long n) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1208,6 +1290,35 @@ void launch_dual_step(const DualStepJob& video, const DualStepJob& audio, float 
     if (w0 + w1 == 0) return;
     ProfScope prof(PROF_ELEM, (double)bytes, stream);
     hipLaunchKernelGGL(dual_step_kernel, dim3((unsigned)(w0 + w1)), dim3(256), 0, stream, video, audio, w0, sigma, sigma_next);
+    HIP_CHECK(hipGetLastError());
+}
+void dual_restage_check(const DualRestageJob& video, const DualRestageJob& audio) {
+    LTX_REQUIRE(video.T == 0 || video.x, "dual_restage: the video job needs its input latent x");
+    LTX_REQUIRE(audio.T == 0 || (!audio.x && !audio.cond && !audio.cond_noise && !audio.stats && !audio.stats_ref),
+                "dual_restage: the audio job works in place: x, cond, cond_noise, stats and stats_ref must be null");
+    for (const DualRestageJob* j : {&video, &audio}) {
+        LTX_REQUIRE(j->T >= 0 && j->T <= (1L << 24), "dual_restage: T=%ld (0 .. 2^24)", j->T);
+        if (j->T == 0) continue;
+        LTX_REQUIRE(j->C >= 32 && j->C <= 4096 && j->C % 32 == 0, "dual_restage: C=%d must be a multiple of 32 (32 .. 4096)", j->C);
+        LTX_REQUIRE(j->latent && j->tokens, "dual_restage: null latent or token pointer");
+        LTX_REQUIRE(((uintptr_t)j->latent & 15) == 0 && ((uintptr_t)j->tokens & 7) == 0, "dual_restage: latent must be 16-byte and tokens 8-byte aligned");
+        LTX_REQUIRE((j->renoise != 0) == (j->noise != nullptr), "dual_restage: noise must be given exactly when a noise scale is (renoise=%d)", j->renoise);
+    }
+    if (video.T > 0) {
+        LTX_REQUIRE(video.stats && video.stats_ref, "dual_restage: null statistics");
+        LTX_REQUIRE(!video.cond_noise || video.cond, "dual_restage: cond_noise needs cond");
+        LTX_REQUIRE(!video.cond || (video.HW >= 1 && video.HW <= video.T), "dual_restage: HW=%ld (1 .. T=%ld)", video.HW, video.T);
+    }
+}
+void launch_dual_restage(const DualRestageJob& video, const DualRestageJob& audio, hipStream_t stream) {
+    dual_restage_check(video, audio);
+    const long nv = video.T * video.C, na = audio.T * audio.C;
+    const int wv = video.T ? (int)cdiv(video.T, 32) * (video.C / 32) : 0;
+    const int wa = (int)std::min<long>(cdiv(na, 4 * 256), 128);
+    if (wv + wa == 0) return;
+    // algorithmic bytes. video: x and the noise in, f32 + bf16 out; audio: the latent in (and, re-noised, the noise in and the latent out), bf16 out
+    ProfScope prof(PROF_ELEM, (double)nv * (4 + (video.noise ? 4 : 0) + 4 + 2) + (double)na * (4 + (audio.noise ? 8 : 0) + 2), stream);
+    hipLaunchKernelGGL(dual_restage_kernel, dim3((unsigned)(wv + wa)), dim3(256), 0, stream, video, audio, wv);
     HIP_CHECK(hipGetLastError());
 }
 void launch_axpby(const float* a, const float* b, float ca, float cb, float* out, long n, hipStream_t stream) {

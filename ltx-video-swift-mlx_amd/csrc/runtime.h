@@ -143,6 +143,8 @@ enum H2dSlot {
     H2D_IN = 0, H2D_OUT = 1,
     // ltx_dual_denoise: video latent / video context / mask in ltx_denoise's slots, the audio latent and context in 0-1
     H2D_DUAL_AUDIO_LATENT = 0, H2D_DUAL_AUDIO_CONTEXT = 1,
+    // ltx_dual_two_stage: ltx_dual_denoise's slots, and the stage-2 noises and the output latent in 2-4
+    H2D_DUAL2_VIDEO_NOISE = 2, H2D_DUAL2_AUDIO_NOISE = 3, H2D_DUAL2_VIDEO_OUT = 4,
     H2D_COUNT = 8
 };
 
@@ -176,6 +178,7 @@ struct ltx_ctx {
     DevBuf i2v_cond, i2v_noise;  // staged image latent / re-noising draws of the host-pointer denoise entry
     DevBuf op_ws;  // split-K workspace of the kernel-level test hook
     DevBuf dual_dn;  // joint video + audio loop (dual_denoise.h): token-layout latents, velocities, tokens, timesteps, statistics
+    DevBuf dual_ts;  // two-stage joint path (dual_two_stage.h): the stage-1 latent in the caller's layout, the AdaIN statistics
 };
 
 // synthetic weights (bench / property tests): counter-based normal fill on device
