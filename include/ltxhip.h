@@ -509,6 +509,17 @@ int ltx_dual_model_unload(ltx_ctx* ctx);
  * parameters under "transformer_blocks.{i}." as ltx_dual_blocks_export_param names them): its element count (out NULL: the count only)
  * or a negative ltx_status. Test seam, as ltx_dit_export_param. */
 long ltx_dual_model_export_param(ltx_ctx* ctx, const char* name, float* out, long cap);
+/* quantize(model: ltx2, groupSize: 64, bits: 8 | 4) on the resident dual model (LTXPipeline.swift:487-492, the audio path's use of
+ * LTXQuantizationConfig.memoryEfficient / .minimal, LTXQuantizationConfig.swift:19-62): every Linear weight of the model and of its
+ * blocks becomes codes + bf16 group scale / bias (group 64 along `in`) and the bf16 weights are RELEASED, as ltx_dit_quantize does
+ * for the DiT. Forwards, the joint loop and the two-stage driver run unchanged on the quantised model; ltx_dual_model_export_param
+ * then returns the de-quantised value bf16(q * scale + bias). The text cache is dropped (ltx_dual_model_prepare_text_dev fills it
+ * again). bits outside {8, 4}, group_size != 64 or an already quantised model: LTX_ERR_INVALID_CONFIGURATION, nothing changed. */
+int ltx_dual_model_quantize(ltx_ctx* ctx, int bits, int group_size);
+/* ltx_dit_memory_info for the dual model (what MLX's memory statistics would show the host, LTXPipeline.swift:3176-3187): the bf16
+ * Linear weights (0 once quantised), the codes + group scales / biases, the one de-quantisation scratch matrix, and everything else
+ * the model keeps (biases, norm weights, tables; the text cache). All zero when no dual model is loaded. Any pointer may be NULL. */
+int ltx_dual_model_memory_info(ltx_ctx* ctx, long* bf16_weight_bytes, long* quantised_weight_bytes, long* scratch_bytes, long* other_bytes);
 /* Arguments of ltx_dual_model_forward_dev; starts with its own size (LTX_DUAL_MODEL_FORWARD_ARGS_INIT). All pointers are DEVICE
  * pointers. */
 typedef struct ltx_dual_model_forward_args {
@@ -527,7 +538,8 @@ typedef struct ltx_dual_model_forward_args {
     float* video_velocity;           /* [B][F*H*W][out_channels] f32 */
     float* audio_velocity;           /* [B][T_a][audio_out_channels] f32 */
     int ungrouped;                   /* measurement seam: non-zero runs the timestep path as 18 ltx_op_gemv_f32-style launches instead of
-                                        three grouped ones; the same bits */
+                                        three grouped ones; the same bits. On a quantised model 1 = 18 one-job launches of the grouped
+                                        kernel on codes, 2 = per Linear de-quantise + ltx_op_gemv_f32 (the same bits again) */
     int text_cache;                  /* non-zero: read the text side from the cache ltx_dual_model_prepare_text_dev filled; the context
                                         and mask pointers are not read (they may be NULL). The same bits as 0, which recomputes it */
 } ltx_dual_model_forward_args;
@@ -988,6 +1000,26 @@ typedef struct ltx_gemv_job {
  * ltx_op_gemv_f32 on its operands. n_jobs outside 1 .. 8, M outside 1 .. 8, a K / lda / ldw that ltx_op_gemv_f32 refuses, or a NULL
  * a / W / out with N > 0: LTX_ERR_INVALID_CONFIGURATION. Every check comes before the launch: a refused call writes nothing. */
 int ltx_op_gemv_group(ltx_ctx* ctx, const ltx_gemv_job* jobs, int n_jobs, int M);
+/* One job of ltx_op_gemv_group_q: ltx_gemv_job with W as affine-quantised codes (MLX QuantizedLinear's layout, group 64 along K). */
+typedef struct ltx_gemv_job_q {
+    const float* a;         /* [M][lda] f32 */
+    long lda;               /* lda % 4 == 0 */
+    const uint8_t* codes;   /* [N][K * bits / 8]: 8 bits one code per byte; 4 bits two per byte, the even element in the low nibble */
+    const uint16_t* scales; /* [N][K / 64] bf16 */
+    const uint16_t* biases; /* [N][K / 64] bf16 */
+    const float* bias;      /* [N] f32 or NULL */
+    float* out;             /* [M][ldo] f32; may point into the middle of a wider row */
+    long ldo;
+    int N;                  /* 0: the job is skipped */
+    int K;                  /* K % 64 == 0 */
+    int in_act;             /* 0 none, 2 SiLU on the activations */
+} ltx_gemv_job_q;
+/* ltx_op_gemv_group on quantised weights, as a quantised dual model runs its timestep path (LTX2Transformer.swift:272-312 on the
+ * QuantizedLinear modules quantize(model:) leaves, LTXPipeline.swift:487-492): every job is bit-equal to ltx_op_gemv_f32 on
+ * W = bf16(q * scale + bias). bits is 8 or 4, one value per launch. n_jobs outside 1 .. 8, M outside 1 .. 8, other bits, K % 64 != 0,
+ * lda % 4 != 0 or a NULL a / codes / scales / biases / out with N > 0: LTX_ERR_INVALID_CONFIGURATION before the launch, nothing
+ * written. */
+int ltx_op_gemv_group_q(ltx_ctx* ctx, const ltx_gemv_job_q* jobs, int n_jobs, int M, int bits);
 /* O = softmax(Q K^T * scale + bias) V ; Q [B][Tq][H*128], K [B][Tk][H*128], Vt [B][H*128][ldvt] (keys contiguous,
  * ldvt >= roundup(Tk,64)), bias [B][Tk] f32 or NULL, O [B][Tq][H*128] ; all bf16. scale <= 0: Q already carries
  * (1/sqrt(128)) * log2(e) - what the DiT's q-norm + RoPE pass writes, one rounding to bf16 - and the scores are base-2 exponents:

@@ -17,7 +17,7 @@ import numpy as np
 from . import _lib
 from ._lib import (ALLGATHER_FN, DIST_ID_BYTES, SHARD_CFG, SHARD_NONE, SHARD_SEQUENCE, ConnectorConfig, PROGRESS_CB, DenoiseOptions,
                    DualBlockConfig, DualDenoiseArgs, DualForwardArgs, DualModelConfig, DualModelForwardArgs, DualRestageJob, DualStepJob, DualTwoStageArgs,
-                   GemmTileLaunch, GemvJob, LTXError, NormMod2Job, TransformerConfig, lib)
+                   GemmTileLaunch, GemvJob, GemvJobQ, LTXError, NormMod2Job, TransformerConfig, lib)
 
 __version__ = lib.ltx_version().decode()
 
@@ -1010,8 +1010,22 @@ class Context:
     def dual_model_init_synthetic(self, cfg, seed=4242):
         self._ck(lib.ltx_dual_model_init_synthetic(self._h, C.byref(cfg), seed))
 
-    def dual_model_load(self, path, cfg):
+    def dual_model_load(self, path, cfg, quant_bits=16):
+        """``ltx_dual_model_load``; ``quant_bits`` 8 or 4 then quantises the loaded model (``dual_model_quantize``), as the reference
+        quantises ``LTX2Transformer`` right after building it (LTXPipeline.swift:487-492). 16: bf16."""
         self._ck(lib.ltx_dual_model_load(self._h, str(path).encode(), C.byref(cfg)))
+        if quant_bits != 16:
+            self.dual_model_quantize(quant_bits)
+
+    def dual_model_quantize(self, bits, group_size=64):
+        """``ltx_dual_model_quantize``: ``quantize(model: ltx2, groupSize: 64, bits:)`` (LTXPipeline.swift:487-492)."""
+        self._ck(lib.ltx_dual_model_quantize(self._h, bits, group_size))
+
+    def dual_model_memory_info(self):
+        """``ltx_dual_model_memory_info`` as ``dit_memory_info``'s dict (LTXPipeline.swift:3176-3187); all zero without a model."""
+        v = [C.c_long() for _ in range(4)]
+        self._ck(lib.ltx_dual_model_memory_info(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(("bf16_weights", "quantised_weights", "scratch", "other"), (x.value for x in v)))
 
     def dual_model_unload(self):
         self._ck(lib.ltx_dual_model_unload(self._h))
@@ -1242,6 +1256,23 @@ class Context:
         if M is None:
             M = jobs[0]["a"].shape[0]
         self._ck(lib.ltx_op_gemv_group(self._h, arr, len(jobs) if n_jobs is None else n_jobs, M))
+
+    def op_gemv_group_q(self, jobs, bits, M=None, n_jobs=None):
+        """``ltx_op_gemv_group_q`` (the timestep path of a quantised LTX2Transformer, LTX2Transformer.swift:272-312): each job is a
+        dict(a= [M][K] f32, codes= [N][K * bits / 8] uint8, scales=, biases= [N][K / 64] bf16, out= a 2-D f32 view whose row stride is ldo,
+        bias= tensor or None, in_act=0); N defaults to the codes' rows and K to scales' columns x 64, and both may be given."""
+        arr = (GemvJobQ * max(1, len(jobs)))()
+        for o, j in zip(arr, jobs):
+            a, codes, scales, out = j.get("a"), j.get("codes"), j.get("scales"), j.get("out")
+            o.a, o.lda = (a.data_ptr(), j.get("lda", a.stride(0))) if a is not None else (None, j.get("lda", 0))
+            o.codes, o.scales, o.biases, o.bias = _ptr(codes), _ptr(scales), _ptr(j.get("biases")), _ptr(j.get("bias"))
+            o.out, o.ldo = (out.data_ptr(), out.stride(0)) if out is not None else (None, 0)
+            o.N = j["N"] if "N" in j else codes.shape[0]
+            o.K = j["K"] if "K" in j else scales.shape[1] * 64
+            o.in_act = j.get("in_act", 0)
+        if M is None:
+            M = jobs[0]["a"].shape[0]
+        self._ck(lib.ltx_op_gemv_group_q(self._h, arr, len(jobs) if n_jobs is None else n_jobs, M, bits))
 
     def op_norm_mod2(self, video=None, audio=None, eps=1e-6):
         """``ltx_op_norm_mod2``: each job is None or a dict(x=, out0=, out1= 2-D tensors whose row strides are ldx / ldo, rows=, D=,

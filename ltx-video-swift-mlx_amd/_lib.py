@@ -85,6 +85,13 @@ class GemvJob(C.Structure):
                 ("ldo", C.c_long), ("N", C.c_int), ("K", C.c_int), ("in_act", C.c_int)]
 
 
+class GemvJobQ(C.Structure):
+    """``ltx_gemv_job_q``: one job of ``ltx_op_gemv_group_q`` (``ltx_gemv_job`` with W as affine-quantised codes, group 64 along K)."""
+
+    _fields_ = [("a", C.c_void_p), ("lda", C.c_long), ("codes", C.c_void_p), ("scales", C.c_void_p), ("biases", C.c_void_p),
+                ("bias", C.c_void_p), ("out", C.c_void_p), ("ldo", C.c_long), ("N", C.c_int), ("K", C.c_int), ("in_act", C.c_int)]
+
+
 class GemmTileLaunch(C.Structure):
     """``ltx_gemm_tile_launch``: one launch of the 192 x 256 / 384 x 256 GEMM kernel with any epilogue it has (``ltx_op_gemm_tile``)."""
 
@@ -311,12 +318,15 @@ SIGNATURES = {
     "ltx_dual_blocks_forward_dev": (_i, [_vp, C.POINTER(DualForwardArgs)]),
     "ltx_op_norm_mod2": (_i, [_vp, C.POINTER(NormMod2Job), C.POINTER(NormMod2Job), _f]),
     "ltx_op_gemv_group": (_i, [_vp, C.POINTER(GemvJob), _i, _i]),
+    "ltx_op_gemv_group_q": (_i, [_vp, C.POINTER(GemvJobQ), _i, _i, _i]),
     "ltx_op_gemm_tile": (_i, [_vp, C.POINTER(GemmTileLaunch)]),
     "ltx_dual_model_config_default": (None, [C.POINTER(DualModelConfig)]),
     "ltx_dual_model_init_synthetic": (_i, [_vp, C.POINTER(DualModelConfig), _u64]),
     "ltx_dual_model_load": (_i, [_vp, C.c_char_p, C.POINTER(DualModelConfig)]),
     "ltx_dual_model_unload": (_i, [_vp]),
     "ltx_dual_model_export_param": (_l, [_vp, C.c_char_p, _vp, _l]),
+    "ltx_dual_model_quantize": (_i, [_vp, _i, _i]),
+    "ltx_dual_model_memory_info": (_i, [_vp, C.POINTER(_l), C.POINTER(_l), C.POINTER(_l), C.POINTER(_l)]),
     "ltx_dual_model_forward_dev": (_i, [_vp, C.POINTER(DualModelForwardArgs)]),
     "ltx_dual_model_forward_groups_dev": (_i, [_vp, C.POINTER(DualModelForwardArgs), _i, _vp]),
     "ltx_dual_model_embed_dev": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),

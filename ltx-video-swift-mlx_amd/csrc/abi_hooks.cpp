@@ -253,6 +253,19 @@ int ltx_op_gemv_group(ltx_ctx* ctx, const ltx_gemv_job* jobs, int n_jobs, int M)
     });
 }
 
+int ltx_op_gemv_group_q(ltx_ctx* ctx, const ltx_gemv_job_q* jobs, int n_jobs, int M, int bits) {
+    return with_ctx(ctx, [&] {
+        LTX_REQUIRE(jobs && n_jobs >= 1 && n_jobs <= 8, "ltx_op_gemv_group_q: %d jobs out of range (1..8)", n_jobs);
+        GemvJobQ g[8];
+        for (int j = 0; j < n_jobs; ++j) {
+            const ltx_gemv_job_q& q = jobs[j];
+            g[j].a = q.a; g[j].lda = q.lda; g[j].codes = q.codes; g[j].scales = q.scales; g[j].biases = q.biases; g[j].bias = q.bias;
+            g[j].out = q.out; g[j].ldo = q.ldo; g[j].N = q.N; g[j].K = q.K; g[j].in_act = q.in_act;
+        }
+        launch_gemv_group_q(g, n_jobs, M, bits, ctx->stream);
+    });
+}
+
 int ltx_op_conv3d(ltx_ctx* ctx, const uint16_t* x, int F, int H, int W, int Cin, const uint16_t* w, const float* bias,
                   int Cout, int causal, float* out) {
     return with_ctx(ctx, [&] {

@@ -960,8 +960,19 @@ int ltx_dual_model_unload(ltx_ctx* ctx) {
     return with_ctx(ctx, [&] { unload_model(ctx, &ctx->dual_model, dual_model_destroy); });
 }
 long ltx_dual_model_export_param(ltx_ctx* ctx, const char* name, float* out, long cap) {
-    return export_param_body(ctx, "ltx_dual_model_export_param", name, out, cap,
-                             [&] { return dual_model_find(need(ctx->dual_model, kNoDualModel), name); });
+    return export_param_body(
+        ctx, "ltx_dual_model_export_param", name, out, cap, [&] { return dual_model_find(need(ctx->dual_model, kNoDualModel), name); },
+        [&](const ParamSlot& s, float* o) { quant_export_slot(ctx, s, ctx->dual_model->quant_bits, o); });
+}
+int ltx_dual_model_quantize(ltx_ctx* ctx, int bits, int group_size) {
+    return with_ctx(ctx, [&] { dual_model_quantize(ctx, need(ctx->dual_model, kNoDualModel), bits, group_size); });
+}
+int ltx_dual_model_memory_info(ltx_ctx* ctx, long* bf16_weight_bytes, long* quantised_weight_bytes, long* scratch_bytes, long* other_bytes) {
+    return with_ctx(ctx, [&] {
+        for (long* p : {bf16_weight_bytes, quantised_weight_bytes, scratch_bytes, other_bytes})
+            if (p) *p = 0;
+        if (ctx->dual_model) dual_model_memory_info(ctx->dual_model, bf16_weight_bytes, quantised_weight_bytes, scratch_bytes, other_bytes);
+    });
 }
 int ltx_dual_model_forward_dev(ltx_ctx* ctx, const ltx_dual_model_forward_args* args) {
     return ltx_dual_model_forward_groups_dev(ctx, args, 1, nullptr);
@@ -994,7 +1005,7 @@ int ltx_dual_model_embed_dev(ltx_ctx* ctx, const float* video_timesteps, const f
         DualModel* m = need(ctx->dual_model, kNoDualModel);
         DualEmbedOut o;
         o.temb_v = temb_v; o.temb_a = temb_a; o.cross_v = cross_v; o.cross_a = cross_a; o.embts_v = embts_v; o.embts_a = embts_a;
-        dual_model_embed(ctx, m, video_timesteps, audio_timesteps, B, ungrouped != 0, o);
+        dual_model_embed(ctx, m, video_timesteps, audio_timesteps, B, ungrouped, o);
     });
 }
 int ltx_dual_model_prepare_text_dev(ltx_ctx* ctx, const uint16_t* video_context, const uint16_t* audio_context, const int32_t* video_mask,

@@ -23,9 +23,9 @@ const StTensor* find_tensor(const SafeTensors& st, const std::string& prefix, co
 }
 }  // namespace
 
-AttnModule* attn_module_create(int query_dim, int context_dim, int heads) { return attn_module_create_ex(query_dim, context_dim, heads, 64, false); }
+AttnModule* attn_module_create(int query_dim, int context_dim, int heads) { return attn_module_create_ex(query_dim, context_dim, heads, 64, false, false); }
 
-AttnModule* attn_module_create_ex(int query_dim, int context_dim, int heads, int head_dim, bool fused_qk) {
+AttnModule* attn_module_create_ex(int query_dim, int context_dim, int heads, int head_dim, bool fused_qk, bool split_weights) {
     if (heads < 1 || heads > 128 || query_dim < 64 || context_dim < 64 || query_dim % 64 != 0 || context_dim % 64 != 0 || query_dim > 8192 ||
         context_dim > 8192)
         LTX_THROW(LTXS_INVALID_CONFIGURATION, "attention module: query_dim %d / context_dim %d must be multiples of 64 up to 8192, heads %d in 1 .. 128",
@@ -61,7 +61,7 @@ AttnModule* attn_module_create_ex(int query_dim, int context_dim, int heads, int
         pt.add_linear("to_out", m->o, (int)Dq, (int)I);
         pt.add("q_norm.weight", (void**)&m->qn, SLOT_F32, I, 0);
         pt.add("k_norm.weight", (void**)&m->kn, SLOT_F32, I, 0);
-        pt.place(false);
+        pt.place(split_weights);  // true: the bf16 weights in params.warena, which a quantising owner releases
         if (fused_qk && (m->k.w != m->q.w + I * Dq || m->k.b != m->q.b + I))
             LTX_THROW(LTXS_GENERATION_FAILED, "attention module: the fused q|k rows are not contiguous");
     } catch (...) {

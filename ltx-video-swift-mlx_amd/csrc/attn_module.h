@@ -39,12 +39,14 @@ struct AttnModule {
     LinearW q, k, v, o;
     float* qn = nullptr;
     float* kn = nullptr;
-    ParamTable params;  // one arena; "to_q.weight", "to_q.bias", .., "q_norm.weight", "k_norm.weight"
+    ParamTable params;  // one arena (two with split_weights); "to_q.weight", "to_q.bias", .., "q_norm.weight", "k_norm.weight"
     DevBuf ws_xb, ws_cb, ws_qraw, ws_kraw, ws_q, ws_k, ws_vt, ws_ao;
 };
 
 AttnModule* attn_module_create(int query_dim, int context_dim, int heads);
-AttnModule* attn_module_create_ex(int query_dim, int context_dim, int heads, int head_dim, bool fused_qk);
+// split_weights: the four bf16 weights go to params.warena and only the f32 parameters to params.arena, so that an owner that quantises
+// the module (dual_model_quantize) can release the bf16 weights; false: one arena, as attn_module_create places them
+AttnModule* attn_module_create_ex(int query_dim, int context_dim, int heads, int head_dim, bool fused_qk, bool split_weights);
 void attn_module_destroy(AttnModule* m);
 void attn_module_init_synthetic(ltx_ctx* ctx, AttnModule* m, uint64_t seed);
 // shapes of a module stored under `prefix` (e.g. "transformer_blocks.0.audio_to_video_attn.") in a safetensors file; the file's own

@@ -88,19 +88,7 @@ void dit_init_synthetic(ltx_ctx* ctx, DiTModel* m, uint64_t seed) {
     for (auto* c : m->ctx_cache) c->version = 0;
 }
 
-void dit_export_slot(ltx_ctx* ctx, DiTModel* m, const ParamSlot& s, float* out) {
-    if (s.q) {  // quantised Linear weight: the value the GEMMs use, bf16(q * scale + bias)
-        DevBuf tmp;
-        tmp.ensure((size_t)s.numel * 2);
-        launch_dequant(s.q, s.qs, s.qb, s.rows, s.cols, m->quant_bits, tmp.as<bf16_t>(), ctx->stream);
-        ParamSlot d;
-        d.dst = tmp.p;
-        d.numel = s.numel;
-        param_export(ctx, d, out);
-        return;
-    }
-    param_export(ctx, s, out);
-}
+void dit_export_slot(ltx_ctx* ctx, DiTModel* m, const ParamSlot& s, float* out) { quant_export_slot(ctx, s, m->quant_bits, out); }
 
 // ---------------------------------------------------------------------------------------------------------------
 // forward

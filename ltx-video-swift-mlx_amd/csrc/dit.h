@@ -126,6 +126,16 @@ int dit_fuse_lora(ltx_ctx* ctx, DiTModel* m, const std::string& path, float scal
 // (the layout MLX's QuantizedLinear holds) and their 26 GB are released. Consumer: dit_linear_weights() below - see the note there
 // on which launches de-quantise inside the GEMM's B stage and which through the scratch matrix.
 void dit_quantize(ltx_ctx* ctx, DiTModel* m, int bits, int group);
+// The body of dit_quantize for any transformer-family model (dual_model_quantize is the second caller): `lins` are the model's Linears
+// (a fused q|k matrix as ONE entry with its full `out`), `tables` the ParamTables whose bf16 slots those Linears own. Sizes `qarena`
+// (codes + group scales / biases of every Linear) and `dq` (the largest Linear), encodes, points each Linear and each bf16 parameter
+// slot (row views of a fused matrix included) at codes / scales / biases, waits for the stream, nulls every `w` and releases the
+// tables' weight arenas. Every check comes before the first allocation. quantize_check_request: the three refusals both callers share.
+void quantize_check_request(int bits, int group, int held_bits);
+void quantize_linears(ltx_ctx* ctx, const std::vector<LinearW*>& lins, const std::vector<ParamTable*>& tables, DeviceArena& qarena,
+                      DequantScratch& dq, int bits);
+// param_export that de-quantises a quantised Linear weight's slot (`bits` of the model that owns it)
+void quant_export_slot(ltx_ctx* ctx, const ParamSlot& s, int bits, float* out);
 // bf16 weights of a Linear for a launch on `stream`: the resident matrix, or the scratch matrix filled from the codes
 const bf16_t* dit_linear_weights(const LinearW& w, hipStream_t stream);
 void launch_dequant(const uint8_t* q, const bf16_t* qs, const bf16_t* qb, long out, long in, int bits, bf16_t* dst, hipStream_t stream);

@@ -51,12 +51,12 @@ DualStack* dual_create(const DualBlockConfig& cfg) {
         for (int i = 0; i < L; ++i) {
             DualBlock& b = m->blocks[i];
             const std::string p = "transformer_blocks." + std::to_string(i) + ".";
-            b.attn1 = attn_module_create_ex(Dv, Dv, cfg.video_heads, 128, true);
-            b.attn2 = attn_module_create_ex(Dv, cfg.video_context_dim, cfg.video_heads, 128, false);
-            b.audio_attn1 = attn_module_create_ex(Da, Da, cfg.audio_heads, 64, true);
-            b.audio_attn2 = attn_module_create_ex(Da, cfg.audio_context_dim, cfg.audio_heads, 64, false);
-            b.a2v = attn_module_create_ex(Dv, Da, cfg.audio_heads, 64, false);
-            b.v2a = attn_module_create_ex(Da, Dv, cfg.audio_heads, 64, false);
+            b.attn1 = attn_module_create_ex(Dv, Dv, cfg.video_heads, 128, true, true);
+            b.attn2 = attn_module_create_ex(Dv, cfg.video_context_dim, cfg.video_heads, 128, false, true);
+            b.audio_attn1 = attn_module_create_ex(Da, Da, cfg.audio_heads, 64, true, true);
+            b.audio_attn2 = attn_module_create_ex(Da, cfg.audio_context_dim, cfg.audio_heads, 64, false, true);
+            b.a2v = attn_module_create_ex(Dv, Da, cfg.audio_heads, 64, false, true);
+            b.v2a = attn_module_create_ex(Da, Dv, cfg.audio_heads, 64, false, true);
             const std::pair<const char*, AttnModule*> mods[] = {{"attn1.", b.attn1},           {"attn2.", b.attn2},
                                                                  {"audio_attn1.", b.audio_attn1}, {"audio_attn2.", b.audio_attn2},
                                                                  {"audio_to_video_attn.", b.a2v}, {"video_to_audio_attn.", b.v2a}};

@@ -30,9 +30,10 @@ void ensure_embed_scratch(DualModel* m, int Mv, int Ma) {
 // The timestep path (LTX2Transformer.swift:272-312). No check and no allocation in here: the callers have done both.
 // video_ts [Mv], audio_ts [Ma]. Mv == Ma: every stage is one grouped launch of six jobs. Mv != Ma (timestep groups): a grouped launch
 // shares one M, so every stage is two - the three video embedders at Mv rows, the three audio embedders at Ma.
-void embed_launches(ltx_ctx* ctx, DualModel* m, const float* video_ts, const float* audio_ts, int Mv, int Ma, bool ungrouped, const DualEmbedOut& o) {
+void embed_launches(ltx_ctx* ctx, DualModel* m, const float* video_ts, const float* audio_ts, int Mv, int Ma, int mode, const DualEmbedOut& o) {
     hipStream_t st = ctx->stream;
     const int Dv = m->Dv, Da = m->Da;
+    const bool ungrouped = mode != 0;
     float* emb_v = m->ws_emb256.as<float>();
     float* emb_a = emb_v + (long)Mv * 256;
     launch_timestep_embedding(video_ts, m->cfg.timestep_scale_multiplier, emb_v, Mv, 256, st);
@@ -40,39 +41,69 @@ void embed_launches(ltx_ctx* ctx, DualModel* m, const float* video_ts, const flo
     // stage 3 destinations: the four modulation tensors; the gate embedders write row 4 of the 5-row tensors
     float* dst3[kDualEmbedders] = {o.temb_v, o.temb_a, o.cross_v, o.cross_v + 4L * Dv, o.cross_a, o.cross_a + 4L * Da};
     const long ldo3[kDualEmbedders] = {6L * Dv, 6L * Da, 5L * Dv, 5L * Dv, 5L * Da, 5L * Da};
-    GemvJob s1[kDualEmbedders], s2[kDualEmbedders], s3[kDualEmbedders];
+    // one table of the 18 Linears; the weights stay LinearW so that a bf16 and a quantised model fill the job type their kernel takes
+    struct Job {
+        const float* a; long lda; const LinearW* w; float* out; long ldo; int in_act;
+    };
+    Job s1[kDualEmbedders], s2[kDualEmbedders], s3[kDualEmbedders];
     for (int j = 0; j < kDualEmbedders; ++j) {
         const DualEmbedder& e = m->emb[j];
         const int D = e.audio ? Da : Dv;
         float* h1 = m->ws_h1.as<float>() + stage_offset(m, j, Mv, Ma);
         // the stage-2 outputs of adaln_single / audio_adaln_single are the embedded timesteps
         float* h2 = j == 0 ? o.embts_v : j == 1 ? o.embts_a : m->ws_h2.as<float>() + stage_offset(m, j, Mv, Ma);
-        s1[j].a = e.audio ? emb_a : emb_v; s1[j].lda = 256; s1[j].W = e.l1.w; s1[j].ldw = 256; s1[j].bias = e.l1.b;
-        s1[j].out = h1; s1[j].ldo = D; s1[j].N = D; s1[j].K = 256; s1[j].in_act = LTX_ACT_NONE;
-        s2[j].a = h1; s2[j].lda = D; s2[j].W = e.l2.w; s2[j].ldw = D; s2[j].bias = e.l2.b;
-        s2[j].out = h2; s2[j].ldo = D; s2[j].N = D; s2[j].K = D; s2[j].in_act = LTX_ACT_SILU;
-        s3[j].a = h2; s3[j].lda = D; s3[j].W = e.lin.w; s3[j].ldw = D; s3[j].bias = e.lin.b;
-        s3[j].out = dst3[j]; s3[j].ldo = ldo3[j]; s3[j].N = e.n * D; s3[j].K = D; s3[j].in_act = LTX_ACT_SILU;
+        s1[j] = {e.audio ? emb_a : emb_v, 256, &e.l1, h1, D, LTX_ACT_NONE};
+        s2[j] = {h1, D, &e.l2, h2, D, LTX_ACT_SILU};
+        s3[j] = {h2, D, &e.lin, dst3[j], ldo3[j], LTX_ACT_SILU};
     }
+    const bool quant = m->quant_bits != 16;
+    // n jobs of one M in one launch: launch_gemv_group on bf16 weights, launch_gemv_group_q on codes
+    auto group = [&](const Job* jobs, int n, int M) {
+        if (quant) {
+            GemvJobQ q[kDualEmbedders];
+            for (int i = 0; i < n; ++i) {
+                const Job& t = jobs[i];
+                q[i].a = t.a; q[i].lda = t.lda; q[i].codes = t.w->q; q[i].scales = t.w->qs; q[i].biases = t.w->qb; q[i].bias = t.w->b;
+                q[i].out = t.out; q[i].ldo = t.ldo; q[i].N = t.w->out; q[i].K = t.w->in; q[i].in_act = t.in_act;
+            }
+            launch_gemv_group_q(q, n, M, m->quant_bits, st);
+            return;
+        }
+        GemvJob g[kDualEmbedders];
+        for (int i = 0; i < n; ++i) {
+            const Job& t = jobs[i];
+            g[i].a = t.a; g[i].lda = t.lda; g[i].W = t.w->w; g[i].ldw = t.w->in; g[i].bias = t.w->b;
+            g[i].out = t.out; g[i].ldo = t.ldo; g[i].N = t.w->out; g[i].K = t.w->in; g[i].in_act = t.in_act;
+        }
+        launch_gemv_group(g, n, M, st);
+    };
     if (!ungrouped && Mv == Ma) {
-        launch_gemv_group(s1, kDualEmbedders, Mv, st);
-        launch_gemv_group(s2, kDualEmbedders, Mv, st);
-        launch_gemv_group(s3, kDualEmbedders, Mv, st);
+        group(s1, kDualEmbedders, Mv);
+        group(s2, kDualEmbedders, Mv);
+        group(s3, kDualEmbedders, Mv);
         return;
     }
     if (!ungrouped) {
-        for (const GemvJob* s : {s1, s2, s3}) {
-            GemvJob v[kDualEmbedders], a[kDualEmbedders];
+        for (const Job* s : {s1, s2, s3}) {
+            Job v[kDualEmbedders], a[kDualEmbedders];
             int nv = 0, na = 0;
             for (int j = 0; j < kDualEmbedders; ++j) (m->emb[j].audio ? a[na++] : v[nv++]) = s[j];
-            launch_gemv_group(v, nv, Mv, st);
-            launch_gemv_group(a, na, Ma, st);
+            group(v, nv, Mv);
+            group(a, na, Ma);
         }
         return;
     }
-    for (const GemvJob* s : {s1, s2, s3})
-        for (int j = 0; j < kDualEmbedders; ++j)
-            launch_gemv_f32(s[j].a, s[j].lda, s[j].W, s[j].ldw, s[j].bias, s[j].out, s[j].ldo, m->emb[j].audio ? Ma : Mv, s[j].N, s[j].K, s[j].in_act, st);
+    for (const Job* s : {s1, s2, s3})
+        for (int j = 0; j < kDualEmbedders; ++j) {
+            const Job& t = s[j];
+            const int M = m->emb[j].audio ? Ma : Mv;
+            if (quant && mode != 2) {
+                group(&t, 1, M);  // the same kernel, one job per launch
+                continue;
+            }
+            // bf16 weights, or (mode 2) the composed alternative on codes: de-quantise into the scratch matrix in front of the gemv
+            launch_gemv_f32(t.a, t.lda, dit_linear_weights(*t.w, st), t.w->in, t.w->b, t.out, t.ldo, M, t.w->out, t.w->in, t.in_act, st);
+        }
 }
 
 // PixArtAlphaTextProjection of one context (LTX2Transformer.swift:275,282): Linear, GELU-tanh, Linear; the hidden activation goes
@@ -174,12 +205,76 @@ void dual_model_load(ltx_ctx* ctx, DualModel* m, const std::string& path) {
                   path.c_str());
 }
 
+void dual_model_quantize(ltx_ctx* ctx, DualModel* m, int bits, int group) {
+    quantize_check_request(bits, group, m->quant_bits);
+    std::vector<LinearW*> lins = {&m->patchify, &m->audio_patchify, &m->cap1, &m->cap2, &m->acap1, &m->acap2, &m->proj_out, &m->audio_proj_out};
+    for (DualEmbedder& e : m->emb)
+        for (LinearW* l : {&e.l1, &e.l2, &e.lin}) lins.push_back(l);
+    DualStack* s = m->stack;
+    std::vector<ParamTable*> tables = {&m->params, &s->params};  // the stack's table holds copies of its modules' slots: both are re-pointed
+    std::vector<AttnModule*> fused;
+    for (DualBlock& b : s->blocks) {
+        for (AttnModule* a : {b.attn1, b.attn2, b.audio_attn1, b.audio_attn2, b.a2v, b.v2a}) {
+            tables.push_back(&a->params);
+            lins.push_back(&a->q);
+            if (a->fused_qk)
+                fused.push_back(a);  // to_k is rows [inner, 2 inner) of to_q's matrix
+            else
+                lins.push_back(&a->k);
+            lins.push_back(&a->v);
+            lins.push_back(&a->o);
+        }
+        for (LinearW* l : {&b.ff1, &b.ff2, &b.aff1, &b.aff2}) lins.push_back(l);
+    }
+    // the fused [2 inner][Dq] matrix is quantised as ONE Linear; its `out` says inner again afterwards, whatever happens in between
+    for (AttnModule* a : fused) a->q.out = 2 * a->inner;
+    try {
+        quantize_linears(ctx, lins, tables, m->qarena, m->dq, bits);
+    } catch (...) {
+        for (AttnModule* a : fused) a->q.out = a->inner;
+        throw;
+    }
+    for (AttnModule* a : fused) {
+        a->q.out = a->inner;
+        const long off = (long)a->inner * a->Dq;  // elements: whole rows, whole groups
+        a->k.q = a->q.q + off * bits / 8;
+        a->k.qs = a->q.qs + off / 64;
+        a->k.qb = a->q.qb + off / 64;
+        a->k.qbits = bits;
+        a->k.dq = a->q.dq;
+        a->k.w = nullptr;
+    }
+    m->quant_bits = bits;
+    // K / V^T of the text cache came from the bf16 weights: the next cached forward needs dual_model_prepare_text again
+    DualTextCache& tc = s->text_cache;
+    tc.buf.release();
+    tc.B = tc.S = tc.Spad = 0;
+    tc.bytes = 0;
+}
+
+void dual_model_memory_info(const DualModel* m, long* bf16_weights, long* quantised, long* scratch, long* other) {
+    size_t w = 0, o = 0;
+    auto table = [&](const ParamTable& t) {
+        w += t.warena.buf.p ? t.warena.buf.bytes : 0;
+        o += t.arena.buf.p ? t.arena.buf.bytes : 0;
+    };
+    table(m->params);
+    table(m->stack->params);
+    for (const DualBlock& b : m->stack->blocks)
+        for (const AttnModule* a : {b.attn1, b.attn2, b.audio_attn1, b.audio_attn2, b.a2v, b.v2a}) table(a->params);
+    o += m->stack->text_cache.buf.p ? m->stack->text_cache.buf.bytes : 0;
+    if (bf16_weights) *bf16_weights = (long)w;
+    if (quantised) *quantised = m->qarena.buf.p ? (long)m->qarena.buf.bytes : 0;
+    if (scratch) *scratch = m->dq.buf.p ? (long)m->dq.buf.bytes : 0;
+    if (other) *other = (long)o;
+}
+
 const ParamSlot* dual_model_find(const DualModel* m, const std::string& name) {
     const ParamSlot* s = m->params.find(name);
     return s ? s : m->stack->params.find(name);
 }
 
-void dual_model_embed(ltx_ctx* ctx, DualModel* m, const float* video_ts, const float* audio_ts, int B, bool ungrouped, const DualEmbedOut& o) {
+void dual_model_embed(ltx_ctx* ctx, DualModel* m, const float* video_ts, const float* audio_ts, int B, int ungrouped, const DualEmbedOut& o) {
     if (B < 1 || B > 8) LTX_THROW(LTXS_INVALID_CONFIGURATION, "dual model embed: B=%d (1 .. 8)", B);
     if (!video_ts || !audio_ts || !o.temb_v || !o.temb_a || !o.cross_v || !o.cross_a || !o.embts_v || !o.embts_a)
         LTX_THROW(LTXS_INVALID_CONFIGURATION, "dual model embed: null timestep or output pointer");
@@ -252,7 +347,7 @@ void dual_model_forward(ltx_ctx* ctx, DualModel* m, const DualModelForwardArgs& 
     eo.cross_a = m->ws_cross_a.as<float>();
     eo.embts_v = m->ws_h2.as<float>() + stage_offset(m, 0, BG, B);
     eo.embts_a = m->ws_h2.as<float>() + stage_offset(m, 1, BG, B);
-    embed_launches(ctx, m, a.video_timesteps, a.audio_timesteps, BG, B, a.ungrouped != 0, eo);
+    embed_launches(ctx, m, a.video_timesteps, a.audio_timesteps, BG, B, a.ungrouped, eo);
     // 3. text (:275,282,315-316); a cached forward reads what dual_model_prepare_text left
     if (!cached) {
         caption_launches(m, a.video_context, m->cap1, m->cap2, Dv, crows, m->ws_ctx_v.as<bf16_t>(), st, sk);

@@ -6,6 +6,13 @@
 // audio_scale_shift_table [2][Da], proj_out / audio_proj_out. norm_out / audio_norm_out are LayerNorm(affine: false): no weight.
 // The joint denoise loop is dual_denoise.h; the CLI's --audio path is not here.
 //
+// Quantised storage (dual_model_quantize, the reference's quantize(model: ltx2, groupSize: 64, bits: 8 | 4), LTXPipeline.swift:487-492):
+// every Linear of the model and of its blocks is held as codes + bf16 group scale / bias in ONE arena and the bf16 weights are
+// released, as dit_quantize does for the DiT. The forward is the same graph: gemm_linear / gemm_vt hand a Linear without `w` to the
+// few-row GEMM as codes (8 bits, M <= 256: every audio-stream GEMM of a block) or de-quantise it into the model's one scratch matrix,
+// and the timestep path reads the codes in launch_gemv_group_q - each job bit-equal to the gemv on the de-quantised matrix. With
+// option "qb_off" = 1 a quantised model's forward therefore equals, bit for bit, the bf16 model holding bf16(q * scale + bias).
+//
 // The text side of a forward (step 3 below and the K / V^T of the blocks' text cross-attentions) does not change within a prompt:
 // dual_model_prepare_text runs it once into model-owned buffers and the stack's DualTextCache, and a forward with text_cache set reads
 // those instead. Same launches, same operands, same bits as the forward that recomputes them.
@@ -27,7 +34,10 @@
 //      cross_video_ss [B][5][Dv] and cross_audio_ss [B][5][Da] in place: rows 0-3 of the last two from the scale-shift embedder, row 4
 //      from the gate embedder (the reference's concatenation, :298-312). Video embedders read the video timestep, audio embedders
 //      the audio timestep. The stage-2 outputs of adaln_single / audio_adaln_single are the embedded timesteps of the heads.
-//      `ungrouped` runs the same 18 Linears as 18 launch_gemv_f32 launches: bit-equal, a measurement seam.
+//      `ungrouped` runs the same 18 Linears as 18 launch_gemv_f32 launches: bit-equal, a measurement seam. On a quantised model
+//      the same three grouping modes call launch_gemv_group_q on the codes (ungrouped = one job per launch of the same kernel);
+//      ungrouped == 2 is the composed alternative that kernel replaces, per Linear launch_dequant into the scratch matrix +
+//      launch_gemv_f32 (36 launches, bit-equal, a measurement seam; on a bf16 model it is `ungrouped`).
 //   3. text: caption_projection / audio_caption_projection (Linear, GELU-tanh, Linear) -> the stack's two bf16 contexts; int32 masks
 //      [B][S] -> additive biases (launch_mask_to_bias); a null mask is a null bias
 //   4. blocks: dual_forward on the owned stack, unchanged
@@ -78,6 +88,9 @@ struct DualModel {
     DualEmbedder emb[kDualEmbedders];  // adaln_single, audio_adaln_single, av_ca_video_scale_shift, av_ca_a2v_gate, av_ca_audio_scale_shift, av_ca_v2a_gate
     float* sst_out_v = nullptr;  // [2][Dv]: row 0 shift, row 1 scale
     float* sst_out_a = nullptr;  // [2][Da]
+    DeviceArena qarena;  // after dual_model_quantize: codes + group scales / biases of every Linear, the blocks' included
+    DequantScratch dq;   // one scratch matrix for the whole model, sized by its largest Linear (adaln_single.linear: 24576 x 4096 at full width)
+    int quant_bits = 16; // 16 (bf16), 8 or 4
     ParamTable params;  // the top-level parameters by module key (arena: biases and the two output tables; warena: Linear weights); the blocks' are stack->params
 
     // scratch
@@ -108,6 +121,16 @@ void dual_model_init_synthetic(ltx_ctx* ctx, DualModel* m, uint64_t seed);
 void dual_model_load(ltx_ctx* ctx, DualModel* m, const std::string& path);
 // a parameter by module key, top-level or "transformer_blocks.{i}."; null when there is none
 const ParamSlot* dual_model_find(const DualModel* m, const std::string& name);
+// MLXNN.quantize(model: ltx2, groupSize:bits:) (LTXPipeline.swift:487-492; LTXQuantizationConfig.swift:19-62): every Linear - both patchify
+// Linears, the 18 embedder Linears, the four caption-projection Linears, both heads, and per block the six attention modules' to_q /
+// to_k / to_v / to_out (a fused q|k matrix as one [2 inner][Dq] Linear, so that its row views stay row offsets) and the four FFN
+// Linears - becomes codes + bf16 group scale / bias (group 64 along `in`), and every bf16 weight arena is released. The text cache is
+// dropped: its K / V^T came from the bf16 weights. bits outside {8, 4}, group != 64 or an already quantised model: refused as
+// dit_quantize refuses them, nothing changed.
+void dual_model_quantize(ltx_ctx* ctx, DualModel* m, int bits, int group);
+// device bytes by kind (ltx_dit_memory_info's meaning): bf16 weight arenas, the code arena, the scratch matrix, and everything else the
+// model holds as parameters or per prompt (f32 parameter arenas of the model, the stack and its modules; the text cache)
+void dual_model_memory_info(const DualModel* m, long* bf16_weights, long* quantised, long* scratch, long* other);
 
 // outputs of the timestep path (device, f32)
 struct DualEmbedOut {
@@ -119,7 +142,7 @@ struct DualEmbedOut {
     float* embts_a = nullptr;  // [B][Da]
 };
 // the timestep path alone, into caller buffers (test and measurement seam)
-void dual_model_embed(ltx_ctx* ctx, DualModel* m, const float* video_ts, const float* audio_ts, int B, bool ungrouped, const DualEmbedOut& out);
+void dual_model_embed(ltx_ctx* ctx, DualModel* m, const float* video_ts, const float* audio_ts, int B, int ungrouped, const DualEmbedOut& out);
 
 struct DualModelForwardArgs {
     const bf16_t* video_latent = nullptr;   // [B][F*H*W][in_channels] bf16

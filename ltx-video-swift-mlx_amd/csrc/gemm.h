@@ -214,3 +214,30 @@ struct GemvGroup {  // the kernel's argument: the jobs by value and the prefix t
     int M;
 };
 void launch_gemv_group(const GemvJob* jobs, int n_jobs, int M, hipStream_t stream);
+
+// launch_gemv_group on affine-quantised weights (the timestep path of a quantised dual model, dual_model_quantize): W is given as
+// codes [N][K * bits / 8] with bf16 scales / biases [N][K / 64] - the MLX affine layout with groups of 64 along K that
+// quant_encode_kernel writes (8 bits: one code per byte; 4 bits: two per byte, the even element in the low nibble). `bits` (8 or 4) is
+// one value per launch. Every job is bit-equal to launch_gemv_f32 on W = bf16(q * scale + bias), the matrix launch_dequant writes:
+// the same lane -> k mapping, each weight rounded to bf16 in front of the same fma chain, the same reduction and bias add. The rows
+// are dense (no ldw): K % 64 == 0. Throws before the launch on n_jobs outside 1 .. 8, M outside 1 .. 8, bits outside {8, 4}, a K that is
+// no multiple of 64, lda % 4 != 0, or a null a / codes / scales / biases / out with N > 0.
+struct GemvJobQ {
+    const float* a = nullptr;
+    long lda = 0;
+    const uint8_t* codes = nullptr;
+    const bf16_t* scales = nullptr;
+    const bf16_t* biases = nullptr;
+    const float* bias = nullptr;
+    float* out = nullptr;
+    long ldo = 0;
+    int N = 0, K = 0;
+    int in_act = 0;
+};
+struct GemvGroupQ {
+    GemvJobQ job[8];
+    int wg_end[8];
+    int n_jobs;
+    int M;
+};
+void launch_gemv_group_q(const GemvJobQ* jobs, int n_jobs, int M, int bits, hipStream_t stream);

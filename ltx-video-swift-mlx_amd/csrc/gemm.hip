@@ -1414,6 +1414,104 @@ __global__ __launch_bounds__(256) void gemv_group_kernel(const GemvGroup g) {
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// grouped small-M path on affine-quantised weights (gemm.h, GemvJobQ): gemv_group_kernel with the weights read as codes. A lane's 8
+// weights of a trip (k = lane * 8 + 512 * trip) lie in ONE 64-wide group, so a trip costs the lane one 8-byte (8 bits) or 4-byte
+// (4 bits) code load and one scale / bias pair. Each weight is rebuilt as bf16(q * scale + bias) - the value launch_dequant writes;
+// q <= 255 times a bf16 scale is exact in f32, so contraction cannot move it - and goes through gemv_trip: the same fma chain in the
+// same order, the same reduction and bias add, so every job is bit-equal to launch_gemv_f32 on the de-quantised matrix.
+// Scale / bias of the 8 lanes that share a group, XL true (the default, option "gemvq_sb" = 1): lanes 0 .. 8 UN - 1 load the chunk's
+// 8 UN consecutive groups once and every trip takes its pair with a cross-lane move; XL false: every lane loads its own pair per
+// trip (8 lanes read one address). Measured on the dual model's timestep path: XL true is 7 - 11 % faster.
+// ---------------------------------------------------------------------------------------------------------------
+template <int BITS> struct GemvQRaw;
+template <> struct GemvQRaw<8> { typedef uint2 type; };
+template <> struct GemvQRaw<4> { typedef uint32_t type; };
+LTX_DEVFN uint32_t gemvq_code(const uint2 raw, int e) { return ((e < 4 ? raw.x : raw.y) >> (8 * (e & 3))) & 0xffu; }
+LTX_DEVFN uint32_t gemvq_code(const uint32_t raw, int e) { return (raw >> (4 * e)) & 0xfu; }  // even element in the low nibble
+
+// UN whole trips starting at the lane's k: every code load is issued before the first fma; the fmas run in trip order
+template <int MMAX, int BITS, int UN, bool XL>
+LTX_DEVFN void gemvq_chunk(const float* __restrict__ a, long lda, const uint8_t* __restrict__ crow, const bf16_t* __restrict__ srow,
+                           const bf16_t* __restrict__ brow, int k, int lane, int M, int in_act, float (&accv)[MMAX]) {
+    typedef typename GemvQRaw<BITS>::type Raw;
+    Raw raw[UN];
+#pragma unroll
+    for (int i = 0; i < UN; ++i) raw[i] = *(const Raw*)(crow + (long)(k + 512 * i) * BITS / 8);
+    float sc[UN], bi[UN];
+    if constexpr (XL) {
+        // whole chunks only: the chunk's groups g0 .. g0 + 8 UN - 1 are all below K / 64 and every lane is active
+        const int g0 = (k >> 6) - (lane >> 3);
+        float sv = 0.f, bv = 0.f;
+        if (lane < 8 * UN) {
+            sv = bf16_to_f32(srow[g0 + lane]);
+            bv = bf16_to_f32(brow[g0 + lane]);
+        }
+#pragma unroll
+        for (int i = 0; i < UN; ++i) {
+            sc[i] = __shfl(sv, (lane >> 3) + 8 * i, 64);
+            bi[i] = __shfl(bv, (lane >> 3) + 8 * i, 64);
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < UN; ++i) {
+            sc[i] = bf16_to_f32(srow[(k + 512 * i) >> 6]);
+            bi[i] = bf16_to_f32(brow[(k + 512 * i) >> 6]);
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < UN; ++i) {
+        s16x8 wv;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) wv[e] = (short)f32_to_bf16((float)gemvq_code(raw[i], e) * sc[i] + bi[i]);
+        gemv_trip<MMAX>(a, lda, wv, k + 512 * i, M, in_act, accv);
+    }
+}
+
+template <int MMAX, int BITS, bool XL>
+__global__ __launch_bounds__(256) void gemv_group_q_kernel(const GemvGroupQ g) {
+    int j = 0;
+    while (j < g.n_jobs - 1 && (int)blockIdx.x >= g.wg_end[j]) ++j;
+    const GemvJobQ& job = g.job[j];
+    const int wg0 = j ? g.wg_end[j - 1] : 0;
+    const int lane = threadIdx.x & 63;
+    const int n = ((int)blockIdx.x - wg0) * 4 + (threadIdx.x >> 6);
+    const int M = g.M, N = job.N, K = job.K, in_act = job.in_act;
+    if (n >= N) return;
+    const float* __restrict__ a = job.a;
+    const long lda = job.lda;
+    float accv[MMAX];
+#pragma unroll
+    for (int m = 0; m < MMAX; ++m) accv[m] = 0.f;
+    const uint8_t* crow = job.codes + (long)n * K * BITS / 8;
+    const bf16_t* srow = job.scales + (long)n * (K >> 6);
+    const bf16_t* brow = job.biases + (long)n * (K >> 6);
+    int kb = 0;
+    for (; kb + 4096 <= K; kb += 4096) gemvq_chunk<MMAX, BITS, 8, XL>(a, lda, crow, srow, brow, kb + lane * 8, lane, M, in_act, accv);
+    if (kb + 2048 <= K) {
+        gemvq_chunk<MMAX, BITS, 4, XL>(a, lda, crow, srow, brow, kb + lane * 8, lane, M, in_act, accv);
+        kb += 2048;
+    }
+    if (kb + 1024 <= K) {
+        gemvq_chunk<MMAX, BITS, 2, XL>(a, lda, crow, srow, brow, kb + lane * 8, lane, M, in_act, accv);
+        kb += 1024;
+    }
+    if (kb + 512 <= K) {
+        gemvq_chunk<MMAX, BITS, 1, XL>(a, lda, crow, srow, brow, kb + lane * 8, lane, M, in_act, accv);
+        kb += 512;
+    }
+    // the partly filled last trip: K % 64 == 0, so an active lane's 8 codes and its group are inside the row; own loads (lanes diverge)
+    if (kb + lane * 8 < K) gemvq_chunk<MMAX, BITS, 1, false>(a, lda, crow, srow, brow, kb + lane * 8, lane, M, in_act, accv);
+    const float* bias = job.bias;
+    float* out = job.out;
+    const long ldo = job.ldo;
+#pragma unroll
+    for (int m = 0; m < MMAX; ++m) {
+        const float s = wave_reduce_sum(accv[m]);
+        if (lane == 0 && m < M) out[(long)m * ldo + n] = s + (bias ? bias[n] : 0.f);
+    }
+}
+
 #ifdef LTX_EXPERIMENTS  // the kernels that were measured and not selected
 #define LTX_GEMM_EXPERIMENTS_PART 1
 #include "gemm_experiments.inc"
@@ -2143,5 +2241,45 @@ void launch_gemv_group(const GemvJob* jobs, int n_jobs, int M, hipStream_t strea
         hipLaunchKernelGGL((gemv_group_kernel<2>), dim3((unsigned)wgs), dim3(256), 0, stream, g);
     else
         hipLaunchKernelGGL((gemv_group_kernel<8>), dim3((unsigned)wgs), dim3(256), 0, stream, g);
+    HIP_CHECK(hipGetLastError());
+}
+
+void launch_gemv_group_q(const GemvJobQ* jobs, int n_jobs, int M, int bits, hipStream_t stream) {
+    // every check comes before the launch: a refused call writes nothing
+    LTX_REQUIRE(jobs && n_jobs >= 1 && n_jobs <= 8, "gemv group q: %d jobs out of range (1..8)", n_jobs);
+    LTX_REQUIRE(M >= 1 && M <= 8, "gemv group q: M=%d out of range (1..8)", M);
+    LTX_REQUIRE(bits == 8 || bits == 4, "gemv group q: %d bits not supported (8, 4)", bits);
+    GemvGroupQ g;
+    g.n_jobs = n_jobs;
+    g.M = M;
+    long wgs = 0;
+    for (int j = 0; j < 8; ++j) {
+        g.job[j] = j < n_jobs ? jobs[j] : GemvJobQ{};
+        const GemvJobQ& q = g.job[j];
+        LTX_REQUIRE(q.N >= 0 && q.K >= 0 && q.K % 64 == 0 && q.lda % 4 == 0, "gemv group q: job %d N=%d K=%d (a multiple of the group, 64) lda=%ld alignment", j,
+                    q.N, q.K, q.lda);
+        LTX_REQUIRE(q.N == 0 || (q.a && q.codes && q.scales && q.biases && q.out), "gemv group q: job %d has a null a / codes / scales / biases / out", j);
+        LTX_REQUIRE(((uintptr_t)q.codes & 7) == 0 && ((uintptr_t)q.scales & 1) == 0 && ((uintptr_t)q.biases & 1) == 0,
+                    "gemv group q: job %d codes / scales / biases alignment (8 / 2 / 2 bytes)", j);
+        wgs += (q.N + 3) / 4;
+        LTX_REQUIRE(wgs < (1L << 30), "gemv group q: too many output columns");
+        g.wg_end[j] = (int)wgs;
+    }
+    if (wgs == 0) return;
+    const bool xl = ltx_opt(OPT_GEMVQ_SB) != 0;  // A/B option "gemvq_sb": how scale / bias reach the 8 lanes of a group (bit-neutral)
+    const dim3 grid((unsigned)wgs), block(256);
+#define LTX_GEMVQ_LAUNCH(MMAX, BITS)                                                                                \
+    do {                                                                                                            \
+        if (xl)                                                                                                     \
+            hipLaunchKernelGGL((gemv_group_q_kernel<MMAX, BITS, true>), grid, block, 0, stream, g);                 \
+        else                                                                                                        \
+            hipLaunchKernelGGL((gemv_group_q_kernel<MMAX, BITS, false>), grid, block, 0, stream, g);                \
+    } while (0)
+    if (M <= 2) {
+        if (bits == 8) LTX_GEMVQ_LAUNCH(2, 8); else LTX_GEMVQ_LAUNCH(2, 4);
+    } else {
+        if (bits == 8) LTX_GEMVQ_LAUNCH(8, 8); else LTX_GEMVQ_LAUNCH(8, 4);
+    }
+#undef LTX_GEMVQ_LAUNCH
     HIP_CHECK(hipGetLastError());
 }

@@ -138,14 +138,15 @@ const bf16_t* dit_linear_weights(const LinearW& w, hipStream_t stream) {
     return w.dq->buf.as<bf16_t>();
 }
 
-void dit_quantize(ltx_ctx* ctx, DiTModel* m, int bits, int group) {
+void quantize_check_request(int bits, int group, int held_bits) {
     LTX_REQUIRE(bits == 8 || bits == 4, "transformer quantization: %d bits not supported (bf16, qint8, int4)", bits);
     LTX_REQUIRE(group == 64, "transformer quantization: group size %d not supported (64)", group);
-    LTX_REQUIRE(m->quant_bits == 16, "the transformer is already quantised (%d bits)", m->quant_bits);
-    // every Linear of the model (MLXNN.quantize(model:groupSize:bits:), LTXPipeline.swift:329)
-    std::vector<LinearW*> lins = {&m->patchify, &m->ada_l1, &m->ada_l2, &m->ada_lin, &m->cap_l1, &m->cap_l2, &m->proj_out};
-    for (auto& b : m->blocks)
-        for (LinearW* l : {&b.qk1, &b.v1, &b.o1, &b.q2, &b.k2, &b.v2, &b.o2, &b.ff1, &b.ff2}) lins.push_back(l);
+    LTX_REQUIRE(held_bits == 16, "the transformer is already quantised (%d bits)", held_bits);
+}
+
+void quantize_linears(ltx_ctx* ctx, const std::vector<LinearW*>& lins, const std::vector<ParamTable*>& tables, DeviceArena& qarena,
+                      DequantScratch& dq, int bits) {
+    // 1. size: every check comes before the first allocation or launch
     size_t total = 0, largest = 0;
     for (LinearW* l : lins) {
         LTX_REQUIRE(l->w && l->in % 64 == 0, "quantize: in-features %d not a multiple of 64", l->in);
@@ -153,40 +154,67 @@ void dit_quantize(ltx_ctx* ctx, DiTModel* m, int bits, int group) {
         total += DeviceArena::padded(n * bits / 8) + 2 * DeviceArena::padded(n / 64 * 2);
         largest = std::max(largest, n);
     }
-    m->qarena.reserve(total + 256);
-    m->dq.buf.ensure(largest * 2);
+    qarena.reserve(total + 256);
+    dq.buf.ensure(largest * 2);
+    // 2. encode
     std::map<const bf16_t*, LinearW*> by_w;
     for (LinearW* l : lins) {
         const size_t n = (size_t)l->out * l->in;
-        uint8_t* codes = (uint8_t*)m->qarena.take(n * bits / 8);
-        bf16_t* qs = (bf16_t*)m->qarena.take(n / 64 * 2);
-        bf16_t* qb = (bf16_t*)m->qarena.take(n / 64 * 2);
+        uint8_t* codes = (uint8_t*)qarena.take(n * bits / 8);
+        bf16_t* qs = (bf16_t*)qarena.take(n / 64 * 2);
+        bf16_t* qb = (bf16_t*)qarena.take(n / 64 * 2);
         launch_encode(l->w, l->out, l->in, bits, codes, qs, qb, ctx->stream);
         l->q = codes;
         l->qs = qs;
         l->qb = qb;
         l->qbits = bits;
-        l->dq = &m->dq;
+        l->dq = &dq;
         by_w[l->w] = l;
     }
-    // parameter slots of the weights (incl. the to_q / to_k row views of the fused matrix) now name codes / scales / biases
-    for (auto& kv : m->params.slots) {
-        ParamSlot& sl = kv.second;
-        if (sl.kind != SLOT_BF16) continue;
-        auto it = by_w.upper_bound((const bf16_t*)sl.dst);
-        LTX_REQUIRE(it != by_w.begin(), "quantize: parameter %s has no Linear", kv.first.c_str());
-        --it;
-        LinearW* l = it->second;
-        const long off = (const bf16_t*)sl.dst - l->w;  // elements from the start of the (fused) matrix: whole rows
-        LTX_REQUIRE(off >= 0 && off + sl.numel <= (long)l->out * l->in && off % l->in == 0, "quantize: parameter %s is not a row range", kv.first.c_str());
-        sl.q = (uint8_t*)l->q + off * bits / 8;
-        sl.qs = (bf16_t*)l->qs + off / 64;
-        sl.qb = (bf16_t*)l->qb + off / 64;
-        sl.dst = nullptr;
-    }
+    // 3. parameter slots of the weights (incl. the to_q / to_k row views of a fused matrix) now name codes / scales / biases
+    for (ParamTable* t : tables)
+        for (auto& kv : t->slots) {
+            ParamSlot& sl = kv.second;
+            if (sl.kind != SLOT_BF16) continue;
+            auto it = by_w.upper_bound((const bf16_t*)sl.dst);
+            LTX_REQUIRE(it != by_w.begin(), "quantize: parameter %s has no Linear", kv.first.c_str());
+            --it;
+            LinearW* l = it->second;
+            const long off = (const bf16_t*)sl.dst - l->w;  // elements from the start of the (fused) matrix: whole rows
+            LTX_REQUIRE(off >= 0 && off + sl.numel <= (long)l->out * l->in && off % l->in == 0, "quantize: parameter %s is not a row range", kv.first.c_str());
+            sl.q = (uint8_t*)l->q + off * bits / 8;
+            sl.qs = (bf16_t*)l->qs + off / 64;
+            sl.qb = (bf16_t*)l->qb + off / 64;
+            sl.dst = nullptr;
+        }
+    // 4. the encoders have read the bf16 weights: drop them
     HIP_CHECK(hipStreamSynchronize(ctx->stream));
     for (LinearW* l : lins) l->w = nullptr;
-    m->params.warena.buf.release();   // the bf16 weights are gone: 26 GB -> 13.9 GB (8 bits) / 7.3 GB (4 bits) resident
+    for (ParamTable* t : tables) t->warena.buf.release();
+}
+
+void quant_export_slot(ltx_ctx* ctx, const ParamSlot& s, int bits, float* out) {
+    if (s.q) {  // quantised Linear weight: the value the GEMMs use, bf16(q * scale + bias)
+        DevBuf tmp;
+        tmp.ensure((size_t)s.numel * 2);
+        launch_dequant(s.q, s.qs, s.qb, s.rows, s.cols, bits, tmp.as<bf16_t>(), ctx->stream);
+        ParamSlot d;
+        d.dst = tmp.p;
+        d.numel = s.numel;
+        param_export(ctx, d, out);
+        return;
+    }
+    param_export(ctx, s, out);
+}
+
+void dit_quantize(ltx_ctx* ctx, DiTModel* m, int bits, int group) {
+    quantize_check_request(bits, group, m->quant_bits);
+    // every Linear of the model (MLXNN.quantize(model:groupSize:bits:), LTXPipeline.swift:329)
+    std::vector<LinearW*> lins = {&m->patchify, &m->ada_l1, &m->ada_l2, &m->ada_lin, &m->cap_l1, &m->cap_l2, &m->proj_out};
+    for (auto& b : m->blocks)
+        for (LinearW* l : {&b.qk1, &b.v1, &b.o1, &b.q2, &b.k2, &b.v2, &b.o2, &b.ff1, &b.ff2}) lins.push_back(l);
+    // the bf16 weights are gone afterwards: 26 GB -> 13.9 GB (8 bits) / 7.3 GB (4 bits) resident
+    quantize_linears(ctx, lins, {&m->params}, m->qarena, m->dq, bits);
     m->quant_bits = bits;
     for (auto* c : m->ctx_cache) c->version = 0;
 }

@@ -40,6 +40,7 @@ const LtxOptInfo kInfo[OPT_COUNT] = {
     {"sp_overlap", 0, 0, 1, 0, "1: sequence-parallel V^T gather on a side stream"},
     {"sp_selftest", 0, 0, 1, 0, "1: one-rank self-test of the sequence-parallel side-stream branch"},
     {"abl_rows", 0, 0, 7, 0, "row-pass ablation mask (tools only)"},
+    {"gemvq_sb", 1, 0, 1, 0, "grouped gemv on quantised codes: 1: one scale / bias load per chunk of trips and a cross-lane move (measured 7 - 11 % faster); 0: every lane loads the scale / bias of its group per trip"},
 };
 
 std::atomic<int> g_val[OPT_COUNT];

@@ -43,6 +43,7 @@ enum LtxOpt {
     OPT_SP_OVERLAP,       // 1 = sequence-parallel V^T gather on a side stream (opt-in until a >= 2-rank RCCL run exists)
     OPT_SP_SELFTEST,      // 1 = one-rank self-test of the side-stream branch
     OPT_ABL_ROWS,         // ablation of row passes (tools/bench_rows.py; experiments)
+    OPT_GEMVQ_SB,         // grouped gemv on codes: 0 = every lane loads its group's scale / bias per trip (default 1: one load per chunk + cross-lane move)
     OPT_COUNT
 };
 
