@@ -113,7 +113,8 @@ def test_lora_on_quantized_model(ltx, oracle, tmp_path):
     ctx.dit_load(path, cfg, quant_bits=8)
     assert ctx.fuse_lora(lpath, 1.0) == n_layers
     got = _fwd(ltx, ctx, inp)
-    wq = oracle.quantize_dit_weights(w, 8)
+    # the merge starts from what quant_decode_kernel writes, bf16(q * scale + bias), not from the un-rounded f32 reconstruction
+    wq = {k: oracle.bf16_round(v) for k, v in oracle.quantize_dit_weights(w, 8).items()}
     wf, _ = oracle.lora_fuse(wq, lora, 1.0)
     fused_keys = {oracle.map_lora_key(k.split(".lora_")[0]) for k in lora if ".lora_" in k}
     for k in fused_keys:
