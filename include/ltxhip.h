@@ -1093,6 +1093,74 @@ int ltx_op_conv2d_causal(ltx_ctx* ctx, const uint16_t* x, int H, int W, int Cin,
 int ltx_op_fill_normal_bf16(ltx_ctx* ctx, uint16_t* p, long n, uint64_t seed, float mean, float stddev);
 int ltx_op_fill_normal_f32(ltx_ctx* ctx, float* p, long n, uint64_t seed, float mean, float stddev);
 
+/* ---- Gemma-3 text encoder (csrc/gemma.h): token ids + attention mask -> the hidden states ltx_connector_encode* consumes ----
+ * Reference: Gemma3Model.swift (Gemma3Attention, Gemma3MLP, Gemma3DecoderLayer, Gemma3InnerModel.callAsFunction), Gemma3Config.swift,
+ * Gemma3WeightLoader.swift; call sites LTXPipeline.swift:1155-1170 and :3194-3277. Only the hidden-state extraction with an attention
+ * mask: no token generation, no KV cache, no tokenizer (token ids are inputs), no sliding-window masking (T <= sliding_window). */
+typedef struct ltx_gemma_config {
+    int hidden_size;             /* 3840 */
+    int num_hidden_layers;       /* 48 */
+    int intermediate_size;       /* 15360 */
+    int num_attention_heads;     /* 16 */
+    int head_dim;                /* 256; nothing else is accepted */
+    int num_key_value_heads;     /* 8 */
+    int vocab_size;              /* 262208 */
+    float rms_norm_eps;          /* 1e-6 */
+    float rope_theta;            /* 1e6: global layers, (i + 1) % sliding_window_pattern == 0 */
+    float rope_local_base_freq;  /* 1e4: sliding layers */
+    float query_pre_attn_scalar; /* 256: softmax scale = its inverse square root */
+    int sliding_window;          /* 1024: the longest sequence encoded */
+    int sliding_window_pattern;  /* 6 */
+} ltx_gemma_config;
+void ltx_gemma_config_default(ltx_gemma_config* cfg);
+/* paths: the n_paths safetensors shards of one checkpoint. Module keys of the reference (model.embed_tokens, model.layers.N.self_attn.
+ * {q,k,v,o}_proj / q_norm / k_norm, the four layer norms, mlp.{gate,up,down}_proj, model.norm), with or without the language_model.
+ * prefix; lm_head* is ignored. A weight may be bf16 / f16 / f32 (rounded to bf16) or MLX affine-quantised (weight as packed uint32 +
+ * scales + biases, group size 64, 4 or 8 bits; the three tensors of one Linear in the same shard), which is de-quantised to bf16 once,
+ * here. A missing parameter is weightLoadingFailed
+ * and named in the message. cfg NULL = the reference's defaults. */
+int ltx_gemma_load(ltx_ctx* ctx, const char* const* paths, int n_paths, const ltx_gemma_config* cfg);
+int ltx_gemma_init_synthetic(ltx_ctx* ctx, const ltx_gemma_config* cfg, unsigned long seed);
+int ltx_gemma_unload(ltx_ctx* ctx);
+/* device bytes the encoder holds now: parameters (+ RoPE tables), and activation workspaces; both 0 without a model */
+int ltx_gemma_memory_info(ltx_ctx* ctx, long* weight_bytes, long* workspace_bytes);
+/* token_ids, attention_mask [B][T] int32; hidden [num_hidden_layers + 1][B][T][hidden_size] bf16 - slot 0 the scaled embedding, slot
+ * i + 1 the output of layer i, the last slot model.norm of the last layer: the connector's input. The mask must be left-padded
+ * (0..0 1..1, at least one 1 per row) and T <= sliding_window, else invalidConfiguration. DEVICE pointers; ids outside [0, vocab) are
+ * clamped. Waits for the stream once (the mask check) before the layers are queued. */
+int ltx_gemma_encode_dev(ltx_ctx* ctx, const int32_t* token_ids, const int32_t* attention_mask, int B, int T, uint16_t* hidden);
+/* HOST-pointer variant; ids outside [0, vocab) are invalidConfiguration. */
+int ltx_gemma_encode(ltx_ctx* ctx, const int32_t* token_ids, const int32_t* attention_mask, int B, int T, uint16_t* hidden);
+/* ltx_gemma_encode_dev into a buffer of the encoder's, then ltx_connector_encode_dev (left padding) on it: token ids -> the context
+ * [B][T][dim] and all-ones mask the denoise entries take. Bit-equal to the two calls in turn. DEVICE pointers. */
+int ltx_text_encode_dev(ltx_ctx* ctx, const int32_t* token_ids, const int32_t* attention_mask, int B, int T, uint16_t* context,
+                        int32_t* out_mask);
+/* HOST-pointer variant of ltx_text_encode_dev: only the ids, the mask and the context cross the bus; the hidden states (385 MB per
+ * batch element at 49 x 1024 x 3840) stay on the device. Ids outside [0, vocab) are invalidConfiguration. out_mask may be NULL. */
+int ltx_text_encode(ltx_ctx* ctx, const int32_t* token_ids, const int32_t* attention_mask, int B, int T, uint16_t* context, int32_t* out_mask);
+/* Test seams of the encoder's kernels (DEVICE pointers).
+ * ltx_op_attention_causal: causal grouped-query attention over left-padded keys. Q / O [B][T][Hq*head_dim], K [B][T][Hkv*head_dim],
+ * Vt [B][Hkv*head_dim][ldvt] bf16, key_start int32 [B] or NULL; query i attends keys key_start[b] <= j <= i, rows i < key_start[b] of O
+ * are zeros. Only head_dim == 256; anything else is invalidConfiguration. ldvt >= T rounded up to 64 (and a multiple of 8); columns
+ * T..ldvt-1 of Vt, and the K / V rows below key_start, are read and must hold FINITE values: they are multiplied by P = 0, so an Inf
+ * or NaN there would come out as NaN. */
+int ltx_op_attention_causal(ltx_ctx* ctx, const uint16_t* Q, const uint16_t* K, const uint16_t* Vt, long ldvt, const int32_t* key_start,
+                            int B, int Hq, int Hkv, int T, int head_dim, float scale, uint16_t* O);
+/* r, x, h, n dense [rows][D] bf16; w, w2 [D] f32 (the stored weights; the kernel forms bf16(1 + w)). x NULL: h = norm(r); else
+ * h = x + norm(r). w2 and n together: n = norm2(h) too. h NULL (with w2, n): only n is written. */
+int ltx_op_gemma_norm(ltx_ctx* ctx, const uint16_t* r, const float* w, const uint16_t* x, const float* w2, int rows, int D, float eps,
+                      uint16_t* h, uint16_t* n);
+/* qk [rows][ld] bf16, in place: q_heads heads of 256 at column 0 (weight wq [256]), k_heads at column q_heads*256 (wk). Per head RMS
+ * norm with bf16(1 + w), then half-split RoPE from cos / sin [T][128] f32 at position row % T. */
+int ltx_op_gemma_qknorm_rope(ltx_ctx* ctx, uint16_t* qk, long ld, const float* wq, const float* wk, int q_heads, int k_heads,
+                             const float* cos_t, const float* sin_t, int T, int rows, float eps);
+/* cos / sin [T][128] f32 of positions 0 .. T-1, frequencies base^(-i/128), computed on the device */
+int ltx_op_gemma_rope_tables(ltx_ctx* ctx, int T, float base, float* cos_t, float* sin_t);
+/* gu [rows][2*I] bf16 (gate | up) -> out [rows][I] = bf16(bf16(gelu_tanh(gate)) * up) */
+int ltx_op_geglu(ltx_ctx* ctx, const uint16_t* gu, int rows, int I, uint16_t* out);
+/* out [rows][D] = bf16(table[ids[row]] * bf16(sqrt(D))); ids are clamped to [0, vocab) */
+int ltx_op_gemma_embed(ltx_ctx* ctx, const int32_t* ids, const uint16_t* table, int rows, int D, int vocab, uint16_t* out);
+
 #ifdef __cplusplus
 }
 #endif

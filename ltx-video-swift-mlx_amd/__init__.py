@@ -11,11 +11,12 @@ as ``ltx_amd``.
 """
 import contextlib
 import ctypes as C
+import os
 
 import numpy as np
 
 from . import _lib
-from ._lib import (ALLGATHER_FN, DIST_ID_BYTES, SHARD_CFG, SHARD_NONE, SHARD_SEQUENCE, ConnectorConfig, PROGRESS_CB, DenoiseOptions,
+from ._lib import (ALLGATHER_FN, DIST_ID_BYTES, SHARD_CFG, SHARD_NONE, SHARD_SEQUENCE, ConnectorConfig, GemmaConfig, PROGRESS_CB, DenoiseOptions,
                    DualBlockConfig, DualDenoiseArgs, DualForwardArgs, DualModelConfig, DualModelForwardArgs, DualRestageJob, DualStepJob, DualTwoStageArgs,
                    GemmTileLaunch, GemvJob, GemvJobQ, LTXError, NormMod2Job, TransformerConfig, lib)
 
@@ -298,6 +299,15 @@ def map_text_encoder_key(key):
 def connector_config(**kw):
     cfg = ConnectorConfig()
     lib.ltx_connector_config_default(C.byref(cfg))
+    for k, v in kw.items():
+        setattr(cfg, k, v)
+    return cfg
+
+
+def gemma_config(**kw):
+    """``ltx_gemma_config`` with the reference's ``Gemma3Config`` defaults, fields overridden by keyword."""
+    cfg = GemmaConfig()
+    lib.ltx_gemma_config_default(C.byref(cfg))
     for k, v in kw.items():
         setattr(cfg, k, v)
     return cfg
@@ -757,6 +767,82 @@ class Context:
         else:
             self._ck(lib.ltx_connector_encode_dev(self._h, _ptr(hidden), _ptr(attention_mask), B, T, int(padding_right),
                                                   _ptr(context), _ptr(out_mask)))
+
+    # ---- Gemma-3 text encoder (csrc/gemma.h) ----
+    def gemma_load(self, paths, cfg=None):
+        """``ltx_gemma_load``: one path or a list of safetensors shards."""
+        if isinstance(paths, (str, bytes, os.PathLike)):
+            paths = [paths]
+        arr = (C.c_char_p * len(paths))(*[os.fsencode(p) for p in paths])
+        self._ck(lib.ltx_gemma_load(self._h, arr, len(paths), C.byref(cfg) if cfg is not None else None))
+
+    def gemma_init_synthetic(self, cfg=None, seed=0):
+        self._ck(lib.ltx_gemma_init_synthetic(self._h, C.byref(cfg) if cfg is not None else None, seed))
+
+    def gemma_unload(self):
+        self._ck(lib.ltx_gemma_unload(self._h))
+
+    def gemma_memory_info(self):
+        """``ltx_gemma_memory_info``: device bytes of the parameters and of the activation workspaces; zeros without a model."""
+        w, ws = C.c_long(), C.c_long()
+        self._ck(lib.ltx_gemma_memory_info(self._h, C.byref(w), C.byref(ws)))
+        return {"weights": w.value, "workspace": ws.value}
+
+    def gemma_encode_dev(self, token_ids, attention_mask, hidden):
+        """Device tensors: ids, mask [B,T] int32 -> hidden [layers+1,B,T,hidden] bf16 (the connector's input)."""
+        B, T = token_ids.shape
+        self._ck(lib.ltx_gemma_encode_dev(self._h, _ptr(token_ids), _ptr(attention_mask), B, T, _ptr(hidden)))
+
+    def gemma_encode(self, token_ids, attention_mask, layers, hidden_size):
+        """HOST arrays: ids, mask [B,T] int32 -> hidden bits [layers+1,B,T,hidden] uint16."""
+        ids = np.ascontiguousarray(token_ids, dtype=np.int32)
+        m = np.ascontiguousarray(attention_mask, dtype=np.int32)
+        B, T = ids.shape
+        out = np.empty((layers + 1, B, T, hidden_size), dtype=np.uint16)
+        self._ck(lib.ltx_gemma_encode(self._h, _ptr(ids), _ptr(m), B, T, _ptr(out)))
+        return out
+
+    def text_encode_dev(self, token_ids, attention_mask, context, out_mask=None):
+        """``ltx_text_encode_dev``: the encoder, then the loaded connector. Device tensors; context [B,T,dim] bf16."""
+        B, T = token_ids.shape
+        self._ck(lib.ltx_text_encode_dev(self._h, _ptr(token_ids), _ptr(attention_mask), B, T, _ptr(context), _ptr(out_mask)))
+
+    def text_encode(self, token_ids, attention_mask, dim):
+        """``ltx_text_encode``: HOST arrays ids, mask [B,T] int32 -> (context bits [B,T,dim] uint16, mask [B,T] int32)."""
+        ids = np.ascontiguousarray(token_ids, dtype=np.int32)
+        m = np.ascontiguousarray(attention_mask, dtype=np.int32)
+        B, T = ids.shape
+        out = np.empty((B, T, dim), dtype=np.uint16)
+        om = np.empty((B, T), dtype=np.int32)
+        self._ck(lib.ltx_text_encode(self._h, _ptr(ids), _ptr(m), B, T, _ptr(out), _ptr(om)))
+        return out, om
+
+    def op_attention_causal(self, Q, K, Vt, O, scale, key_start=None, head_dim=256):
+        """``ltx_op_attention_causal``: Q / O [B,T,Hq*hd], K [B,T,Hkv*hd], Vt [B,Hkv*hd,ldvt] bf16, key_start [B] int32 or None."""
+        B, T, Dq = Q.shape
+        self._ck(lib.ltx_op_attention_causal(self._h, _ptr(Q), _ptr(K), _ptr(Vt), Vt.shape[2], _ptr(key_start), B, Dq // head_dim,
+                                             K.shape[2] // head_dim, T, head_dim, scale, _ptr(O)))
+
+    def op_gemma_norm(self, r, w, h=None, x=None, w2=None, n=None, eps=1e-6):
+        """``ltx_op_gemma_norm``: r / x / h / n [rows,D] bf16, w / w2 [D] f32."""
+        rows, D = r.shape
+        self._ck(lib.ltx_op_gemma_norm(self._h, _ptr(r), _ptr(w), _ptr(x), _ptr(w2), rows, D, eps, _ptr(h), _ptr(n)))
+
+    def op_gemma_qknorm_rope(self, qk, wq, wk, q_heads, k_heads, cos, sin, T, eps=1e-6):
+        """``ltx_op_gemma_qknorm_rope``: qk [rows,(q_heads+k_heads)*256] bf16, in place."""
+        rows, ld = qk.shape
+        self._ck(lib.ltx_op_gemma_qknorm_rope(self._h, _ptr(qk), ld, _ptr(wq), _ptr(wk), q_heads, k_heads, _ptr(cos), _ptr(sin), T, rows, eps))
+
+    def op_gemma_rope_tables(self, T, base, cos, sin):
+        self._ck(lib.ltx_op_gemma_rope_tables(self._h, T, base, _ptr(cos), _ptr(sin)))
+
+    def op_geglu(self, gu, out):
+        rows, I2 = gu.shape
+        self._ck(lib.ltx_op_geglu(self._h, _ptr(gu), rows, I2 // 2, _ptr(out)))
+
+    def op_gemma_embed(self, ids, table, out):
+        vocab, D = table.shape
+        self._ck(lib.ltx_op_gemma_embed(self._h, _ptr(ids), _ptr(table), ids.numel(), D, vocab, _ptr(out)))
 
     def upscaler_load(self, path):
         self._ck(lib.ltx_upscaler_load(self._h, str(path).encode()))

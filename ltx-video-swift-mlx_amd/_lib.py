@@ -49,6 +49,15 @@ class ConnectorConfig(C.Structure):
                 ("theta", C.c_float), ("max_pos", C.c_int)]
 
 
+class GemmaConfig(C.Structure):
+    """``ltx_gemma_config`` / reference ``Gemma3Config`` defaults (Gemma3Config.swift:42-60)."""
+
+    _fields_ = [("hidden_size", C.c_int), ("num_hidden_layers", C.c_int), ("intermediate_size", C.c_int), ("num_attention_heads", C.c_int),
+                ("head_dim", C.c_int), ("num_key_value_heads", C.c_int), ("vocab_size", C.c_int), ("rms_norm_eps", C.c_float),
+                ("rope_theta", C.c_float), ("rope_local_base_freq", C.c_float), ("query_pre_attn_scalar", C.c_float),
+                ("sliding_window", C.c_int), ("sliding_window_pattern", C.c_int)]
+
+
 class TransformerConfig(C.Structure):
     """``ltx_transformer_config`` / reference ``LTXTransformerConfig`` (LTXConfig.swift:83-177)."""
 
@@ -344,6 +353,21 @@ SIGNATURES = {
     "ltx_op_conv1d": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _vp, _i, _f, _vp]),
     "ltx_op_conv_transpose1d": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _f, _vp]),
     "ltx_op_conv2d_causal": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp]),
+    "ltx_gemma_config_default": (None, [C.POINTER(GemmaConfig)]),
+    "ltx_gemma_load": (_i, [_vp, C.POINTER(C.c_char_p), _i, C.POINTER(GemmaConfig)]),
+    "ltx_gemma_init_synthetic": (_i, [_vp, C.POINTER(GemmaConfig), C.c_ulong]),
+    "ltx_gemma_unload": (_i, [_vp]),
+    "ltx_gemma_memory_info": (_i, [_vp, C.POINTER(_l), C.POINTER(_l)]),
+    "ltx_gemma_encode_dev": (_i, [_vp, _vp, _vp, _i, _i, _vp]),
+    "ltx_gemma_encode": (_i, [_vp, _vp, _vp, _i, _i, _vp]),
+    "ltx_text_encode_dev": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp]),
+    "ltx_text_encode": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp]),
+    "ltx_op_attention_causal": (_i, [_vp, _vp, _vp, _vp, _l, _vp, _i, _i, _i, _i, _i, _f, _vp]),
+    "ltx_op_gemma_norm": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _f, _vp, _vp]),
+    "ltx_op_gemma_qknorm_rope": (_i, [_vp, _vp, _l, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _f]),
+    "ltx_op_gemma_rope_tables": (_i, [_vp, _i, _f, _vp, _vp]),
+    "ltx_op_geglu": (_i, [_vp, _vp, _i, _i, _vp]),
+    "ltx_op_gemma_embed": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
     "ltx_op_fill_normal_bf16": (_i, [_vp, _vp, _l, _u64, _f, _f]),
     "ltx_op_fill_normal_f32": (_i, [_vp, _vp, _l, _u64, _f, _f]),
 }

@@ -9,6 +9,7 @@
 #include "dual_model.h"
 #include "audio.h"
 #include "connector.h"
+#include "gemma.h"
 #include "dist.h"
 #include "hostmath.h"
 #include "options.h"
@@ -104,6 +105,16 @@ void ltx_connector_config_default(ltx_connector_config* cfg) {
     cfg->theta = k.theta; cfg->max_pos = k.max_pos;
 }
 
+void ltx_gemma_config_default(ltx_gemma_config* cfg) {
+    if (!cfg) return;
+    const GemmaConfig k;
+    cfg->hidden_size = k.hidden; cfg->num_hidden_layers = k.layers; cfg->intermediate_size = k.intermediate;
+    cfg->num_attention_heads = k.heads; cfg->head_dim = k.head_dim; cfg->num_key_value_heads = k.kv_heads; cfg->vocab_size = k.vocab;
+    cfg->rms_norm_eps = k.rms_eps; cfg->rope_theta = k.rope_theta; cfg->rope_local_base_freq = k.rope_local_base;
+    cfg->query_pre_attn_scalar = k.query_pre_attn_scalar; cfg->sliding_window = k.sliding_window;
+    cfg->sliding_window_pattern = k.sliding_window_pattern;
+}
+
 int ltx_ctx_create(int device, ltx_ctx** out) {
     if (!out) return LTX_ERR_INVALID_CONFIGURATION;
     *out = nullptr;
@@ -145,6 +156,7 @@ void ltx_ctx_destroy(ltx_ctx* ctx) {
     for (AttnModule*& m : ctx->attn_modules) drop_model(&m, attn_module_destroy);
     drop_model(&ctx->dual, dual_destroy);
     drop_model(&ctx->dual_model, dual_model_destroy);
+    drop_model(&ctx->gemma, gemma_destroy);
     if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
 }

@@ -351,6 +351,67 @@ int ltx_op_attention_hd(ltx_ctx* ctx, const uint16_t* Q, const uint16_t* K, cons
     });
 }
 
+int ltx_op_attention_causal(ltx_ctx* ctx, const uint16_t* Q, const uint16_t* K, const uint16_t* Vt, long ldvt, const int32_t* key_start,
+                            int B, int Hq, int Hkv, int T, int head_dim, float scale, uint16_t* O) {
+    return with_ctx(ctx, [&] {
+        LTX_REQUIRE(head_dim == 256, "ltx_op_attention_causal: head dim %d (256)", head_dim);
+        LTX_REQUIRE(Q && K && Vt && O, "ltx_op_attention_causal: null argument");
+        AttnArgs a;
+        const long Dq = (long)Hq * 256, Dk = (long)Hkv * 256;
+        a.head_dim = 256; a.causal = 1; a.key_start = key_start;
+        a.Q = Q; a.ldq = Dq; a.q_bstride = (long)T * Dq;
+        a.K = K; a.ldk = Dk; a.k_bstride = (long)T * Dk;
+        a.Vt = Vt; a.ldvt = ldvt; a.vt_bstride = Dk * ldvt;
+        a.O = O; a.ldo = Dq; a.o_bstride = (long)T * Dq;
+        a.B = B; a.H = Hq; a.Hkv = Hkv; a.Tq = T; a.Tk = T; a.scale = scale;
+        launch_attention(a, ctx->stream);
+    });
+}
+
+int ltx_op_gemma_norm(ltx_ctx* ctx, const uint16_t* r, const float* w, const uint16_t* x, const float* w2, int rows, int D, float eps,
+                      uint16_t* h, uint16_t* n) {
+    return with_ctx(ctx, [&] {
+        GemmaNormArgs a;
+        a.r = r; a.ldr = D; a.w = w; a.x = x; a.ldx = D; a.h = h; a.ldh = D; a.w2 = w2; a.n = n; a.ldn = D;
+        a.n_only = h ? 0 : 1; a.rows = rows; a.D = D; a.eps = eps;
+        launch_gemma_norm(a, ctx->stream);
+    });
+}
+
+int ltx_op_gemma_qknorm_rope(ltx_ctx* ctx, uint16_t* qk, long ld, const float* wq, const float* wk, int q_heads, int k_heads,
+                             const float* cos_t, const float* sin_t, int T, int rows, float eps) {
+    return with_ctx(ctx, [&] {
+        LTX_REQUIRE(qk && q_heads > 0 && k_heads >= 0 && ld >= (long)(q_heads + k_heads) * 256, "ltx_op_gemma_qknorm_rope: shape");
+        GemmaQkArgs a;
+        a.job[0].x = qk; a.job[0].ldx = ld; a.job[0].w = wq; a.job[0].out = qk; a.job[0].ldo = ld; a.job[0].heads = q_heads;
+        a.job[1].x = qk + q_heads * 256; a.job[1].ldx = ld; a.job[1].w = wk; a.job[1].out = qk + q_heads * 256; a.job[1].ldo = ld;
+        a.job[1].heads = k_heads;
+        a.cos = cos_t; a.sin = sin_t; a.T = T; a.rows = rows; a.eps = eps;
+        launch_gemma_qknorm_rope(a, ctx->stream);
+    });
+}
+
+int ltx_op_gemma_rope_tables(ltx_ctx* ctx, int T, float base, float* cos_t, float* sin_t) {
+    return with_ctx(ctx, [&] { launch_gemma_rope_tables(cos_t, sin_t, T, base, ctx->stream); });
+}
+
+int ltx_op_geglu(ltx_ctx* ctx, const uint16_t* gu, int rows, int I, uint16_t* out) {
+    return with_ctx(ctx, [&] {
+        GegluArgs a;
+        a.gu = gu; a.ldgu = 2L * I; a.out = out; a.ldo = I; a.rows = rows; a.I = I;
+        launch_geglu(a, ctx->stream);
+    });
+}
+
+int ltx_op_gemma_embed(ltx_ctx* ctx, const int32_t* ids, const uint16_t* table, int rows, int D, int vocab, uint16_t* out) {
+    return with_ctx(ctx, [&] {
+        GemmaEmbedArgs a;
+        a.ids = ids; a.table = table; a.out = out; a.rows = rows; a.D = D; a.vocab = vocab;
+        a.scale = host_bf16_to_f32(host_f32_to_bf16(sqrtf((float)D)));
+        launch_gemma_embed(a, ctx->stream);
+    });
+}
+
 int ltx_attention_hd_workgroup_queries(int B, int H, int Tq, int head_dim) {
     if (B < 1 || H < 1 || Tq < 1 || head_dim != 64) return 0;
     return attn64_queries_per_workgroup(B, H, Tq);

@@ -13,6 +13,7 @@
 #include "dual_model.h"
 #include "dual_two_stage.h"
 #include "connector.h"
+#include "gemma.h"
 #include "dist.h"
 #include "elementwise.h"
 #include "pipeline.h"
@@ -76,6 +77,17 @@ VaeDecodeArgs vae_args(const float* latent, int F, int H, int W, int has_timeste
     a.tile = tile; a.overlap = overlap;
     a.frames = frames; a.frames_cap = frames_cap; a.n_frames_out = n_frames_out;
     return a;
+}
+
+GemmaConfig to_gemma_cfg(const ltx_gemma_config* c) {
+    GemmaConfig g;
+    if (!c) return g;
+    g.hidden = c->hidden_size; g.layers = c->num_hidden_layers; g.intermediate = c->intermediate_size;
+    g.heads = c->num_attention_heads; g.head_dim = c->head_dim; g.kv_heads = c->num_key_value_heads; g.vocab = c->vocab_size;
+    g.rms_eps = c->rms_norm_eps; g.rope_theta = c->rope_theta; g.rope_local_base = c->rope_local_base_freq;
+    g.query_pre_attn_scalar = c->query_pre_attn_scalar; g.sliding_window = c->sliding_window;
+    g.sliding_window_pattern = c->sliding_window_pattern;
+    return g;
 }
 
 ConnectorConfig to_conn_cfg(const ltx_connector_config* c) {
@@ -711,6 +723,119 @@ int ltx_connector_encode(ltx_ctx* ctx, const uint16_t* hidden, const int32_t* at
         connector_encode(ctx, m, a);
         stage_out(ctx, context, d_context, ob);
         if (out_mask) stage_out(ctx, out_mask, d_out_mask, mb);
+        stage_sync(ctx);
+    });
+}
+
+/* ---- Gemma-3 text encoder ---- */
+int ltx_gemma_load(ltx_ctx* ctx, const char* const* paths, int n_paths, const ltx_gemma_config* cfg) {
+    if (!ctx || !paths || n_paths < 1) return LTX_ERR_INVALID_CONFIGURATION;
+    return guarded(ctx, [&] {
+        std::vector<std::string> shards;
+        for (int i = 0; i < n_paths; ++i) {
+            LTX_REQUIRE(paths[i], "ltx_gemma_load: null path");
+            shards.push_back(paths[i]);
+        }
+        replace_model(ctx, &ctx->gemma, [&] { return gemma_create(ctx, to_gemma_cfg(cfg)); },
+                      [&](GemmaModel* m) { gemma_load_safetensors(ctx, m, shards); }, gemma_destroy);
+    });
+}
+
+int ltx_gemma_init_synthetic(ltx_ctx* ctx, const ltx_gemma_config* cfg, unsigned long seed) {
+    return with_ctx(ctx, [&] {
+        replace_model(ctx, &ctx->gemma, [&] { return gemma_create(ctx, to_gemma_cfg(cfg)); },
+                      [&](GemmaModel* m) { gemma_init_synthetic(ctx, m, seed); }, gemma_destroy);
+    });
+}
+
+int ltx_gemma_unload(ltx_ctx* ctx) {
+    return with_ctx(ctx, [&] { unload_model(ctx, &ctx->gemma, gemma_destroy); });
+}
+
+int ltx_gemma_memory_info(ltx_ctx* ctx, long* weight_bytes, long* workspace_bytes) {
+    return with_ctx(ctx, [&] {
+        const GemmaModel* m = ctx->gemma;
+        const size_t w = m ? m->params.arena.buf.bytes + m->rope.bytes : 0;
+        if (weight_bytes) *weight_bytes = (long)w;
+        if (workspace_bytes) *workspace_bytes = m ? (long)(gemma_resident_bytes(m) - w) : 0;
+    });
+}
+
+int ltx_gemma_encode_dev(ltx_ctx* ctx, const int32_t* token_ids, const int32_t* attention_mask, int B, int T, uint16_t* hidden) {
+    return with_ctx(ctx, [&] {
+        GemmaModel* m = need(ctx->gemma, kNoGemma);
+        GemmaArgs a;
+        a.ids = token_ids; a.mask = attention_mask; a.B = B; a.T = T; a.hidden = hidden;
+        gemma_encode(ctx, m, a);
+    });
+}
+
+int ltx_gemma_encode(ltx_ctx* ctx, const int32_t* token_ids, const int32_t* attention_mask, int B, int T, uint16_t* hidden) {
+    return with_ctx(ctx, [&] {
+        GemmaModel* m = need(ctx->gemma, kNoGemma);
+        LTX_REQUIRE(token_ids && attention_mask && hidden && B >= 1 && T >= 1, "gemma_encode: bad arguments");
+        const GemmaConfig& c = m->cfg;
+        for (long i = 0; i < (long)B * T; ++i)
+            LTX_REQUIRE(token_ids[i] >= 0 && token_ids[i] < c.vocab, "gemma_encode: token id %d at position %ld is outside the vocabulary of %d",
+                        token_ids[i], i, c.vocab);
+        const size_t ib = (size_t)B * T * 4, hb = (size_t)(c.layers + 1) * B * T * c.hidden * 2;
+        DevBuf &d_ids = ctx->h2d[H2D_IN], &d_mask = ctx->h2d[H2D_CONN_MASK], &d_hidden = ctx->h2d[H2D_CONN_CONTEXT];
+        d_hidden.ensure(hb);
+        stage_in(ctx, d_ids, token_ids, ib);
+        stage_in(ctx, d_mask, attention_mask, ib);
+        GemmaArgs a;
+        a.ids = d_ids.as<int32_t>(); a.mask = d_mask.as<int32_t>(); a.B = B; a.T = T; a.hidden = d_hidden.as<bf16_t>();
+        gemma_encode(ctx, m, a);
+        stage_out(ctx, hidden, d_hidden, hb);
+        stage_sync(ctx);
+    });
+}
+
+namespace {
+void text_encode_body(ltx_ctx* ctx, const int32_t* token_ids, const int32_t* attention_mask, int B, int T, uint16_t* context, int32_t* out_mask) {
+    GemmaModel* g = need(ctx->gemma, kNoGemma);
+    ConnectorModel* m = need(ctx->connector, kNoConnector);
+    LTX_REQUIRE(B >= 1 && T >= 1 && context, "text_encode: bad arguments");
+    LTX_REQUIRE(m->cfg.states == g->cfg.layers + 1 && m->cfg.dim == g->cfg.hidden,
+                "text_encode: the connector takes %d states of %d, the encoder makes %d of %d", m->cfg.states, m->cfg.dim, g->cfg.layers + 1,
+                g->cfg.hidden);
+    g->ws_hidden.ensure((size_t)(g->cfg.layers + 1) * B * T * g->cfg.hidden * 2);
+    GemmaArgs ga;
+    ga.ids = token_ids; ga.mask = attention_mask; ga.B = B; ga.T = T; ga.hidden = g->ws_hidden.as<bf16_t>();
+    gemma_encode(ctx, g, ga);
+    ConnectorArgs a;
+    a.hidden = ga.hidden; a.mask = attention_mask; a.B = B; a.T = T; a.padding_right = 0;
+    a.out = context; a.out_mask = out_mask;
+    connector_encode(ctx, m, a);
+}
+void check_token_ids(const GemmaModel* m, const int32_t* token_ids, long n) {
+    for (long i = 0; i < n; ++i)
+        LTX_REQUIRE(token_ids[i] >= 0 && token_ids[i] < m->cfg.vocab, "gemma_encode: token id %d at position %ld is outside the vocabulary of %d",
+                    token_ids[i], i, m->cfg.vocab);
+}
+}  // namespace
+
+int ltx_text_encode_dev(ltx_ctx* ctx, const int32_t* token_ids, const int32_t* attention_mask, int B, int T, uint16_t* context,
+                        int32_t* out_mask) {
+    return with_ctx(ctx, [&] { text_encode_body(ctx, token_ids, attention_mask, B, T, context, out_mask); });
+}
+
+int ltx_text_encode(ltx_ctx* ctx, const int32_t* token_ids, const int32_t* attention_mask, int B, int T, uint16_t* context, int32_t* out_mask) {
+    return with_ctx(ctx, [&] {
+        GemmaModel* g = need(ctx->gemma, kNoGemma);
+        ConnectorModel* m = need(ctx->connector, kNoConnector);
+        LTX_REQUIRE(token_ids && attention_mask && context && B >= 1 && T >= 1, "text_encode: bad arguments");
+        check_token_ids(g, token_ids, (long)B * T);
+        const size_t ib = (size_t)B * T * 4, ob = (size_t)B * T * m->cfg.dim * 2;
+        DevBuf &d_ids = ctx->h2d[H2D_IN], &d_mask = ctx->h2d[H2D_CONN_MASK], &d_context = ctx->h2d[H2D_CONN_CONTEXT],
+               &d_out_mask = ctx->h2d[H2D_CONN_OUT_MASK];
+        d_context.ensure(ob);
+        d_out_mask.ensure(ib);
+        stage_in(ctx, d_ids, token_ids, ib);
+        stage_in(ctx, d_mask, attention_mask, ib);
+        text_encode_body(ctx, d_ids.as<int32_t>(), d_mask.as<int32_t>(), B, T, d_context.as<uint16_t>(), d_out_mask.as<int32_t>());
+        stage_out(ctx, context, d_context, ob);
+        if (out_mask) stage_out(ctx, out_mask, d_out_mask, ib);
         stage_sync(ctx);
     });
 }

@@ -23,6 +23,13 @@ struct AttnArgs {
     // exponents and `scale` is ignored. The assembly kernel then runs a stream without its 48 v_mul per key tile; the other
     // kernels run with scale = ln 2. The bias stays in the reference's units (added to score * scale).
     int q_prescaled = 0;
+    // head_dim 256 (the Gemma-3 text encoder, attn256_causal_kernel): causal grouped-query attention over left-padded keys. Q / O are
+    // [B][T][H*256], K is [B][T][Hkv*256], Vt is [B][Hkv*256][ldvt]; query head h reads K/V head h / (H / Hkv), H % Hkv == 0, Tq == Tk.
+    // Query i of batch element b attends keys key_start[b] <= j <= i; output rows i < key_start[b] are zeros. `scale` is the caller's
+    // (Gemma: query_pre_attn_scalar^-0.5, not a function of the head dim). No bias, no prescale, no key split.
+    int Hkv = 0;                         // 0: H (every kernel but the head-dim-256 one requires that)
+    int causal = 0;                      // required at head dim 256, refused elsewhere
+    const int32_t* key_start = nullptr;  // device [B] or null (no padding); values are clamped to 0 .. T
     int plain_order = 0;  // 1: workgroups in (query block, head, batch) order instead of the XCD-aware order (A/B measurements only)
     // Key split (few queries against many keys: the cross-attention of a 128-token launch is 32 workgroups walking 16 key tiles each).
     // With a workspace the launcher may divide the keys over up to 8 workgroups per (query block, head): each writes its normalised

@@ -960,7 +960,255 @@ void launch_attn64(const AttnArgs& a, hipStream_t stream) {
     HIP_CHECK(hipGetLastError());
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Head dim 256, causal, grouped-query, left-padded keys (the Gemma-3 text encoder: 16 query heads over 8 K/V heads,
+// Gemma3Model.swift Gemma3Attention; the mask is createAttentionMask's causal mask AND the padding mask). attn64_fwd_kernel's operand
+// mapping with four times the head dim:
+//   S^T = K Q^T : key block kb (16 keys) x 16 queries, the head dim is EIGHT k-steps of 32
+//   O^T = Vt P^T: d-block db (16 of the 256 channels) x 16 queries, a 64-key tile is two k-steps of 32; P stays in registers
+// A wave carries ONE block of 16 query positions for NH query heads that share a K/V head (NH = 2 when the group size Hq / Hkv is
+// even, else 1): every K / Vt fragment read from LDS feeds NH MFMAs, and both heads see the same mask. 4 waves = 64 query positions
+// per workgroup; the PV accumulator is 16 d-blocks x NH x 4 registers, Q is 8 x NH x 4: one wave per SIMD, accumulators in AGPRs.
+// Query i attends keys key_start[b] <= j <= i. The workgroup of query tile x walks key tiles key_start/64 .. x ONLY: tiles above the
+// diagonal or below the padding boundary are neither staged nor computed; the mask is applied in the diagonal tile and, when key_start
+// is not a multiple of 64, in the first one. A masked score is -inf, so its P is exactly 0 whatever the padded K / V rows hold (finite).
+// Every valid row has a valid key in its first tile (key_start itself) and in its diagonal tile (itself); a row with none so far
+// (padding rows of the first tile) runs on a maximum of 0 instead of -inf, so no NaN is ever formed. Rows i < key_start are written as
+// zeros (the connector zeroes those positions; the reference holds a uniform average there that nothing reads - DESIGN.md 6i).
+// LDS: K tile [64 keys][256 d] is 64 rows of 512 B, physical 16-B chunk p of key k holds logical chunk p ^ (4*((k>>3)&3) | (k&3)) - the
+// 16 rows of one fragment read land on the 16 slots of a bank row under the ds_read_b128 lane groups; Vt tile [256 d][64 keys] is
+// attn64's image with 256 rows. Both staged by LDS-DMA with the swizzle on the source address, 32 + 32 pieces of 1 KB per tile, two
+// stages of 64 KB, one barrier per key tile. The code object has no scratch and no spills (tests/test_attn256_metadata.py).
+// ---------------------------------------------------------------------------------------------------------------
+constexpr int D256_TILE_BYTES = 64 * 512;
+constexpr int D256_STAGE_BYTES = 2 * D256_TILE_BYTES;
+constexpr int D256_LDS = 2 * D256_STAGE_BYTES;
+LTX_DEVFN int d256_key_swizzle(int key) { return (((key >> 3) & 3) << 2) | (key & 3); }
+
+template <int NH>
+__global__ __launch_bounds__(256, 1) void attn256_causal_kernel(const AttnArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int c16 = lane & 15, g = lane >> 4;
+    const int T = a.Tq;
+    // (query tile, head group, batch) with the longest key walks first
+    const int groups = a.H / NH;
+    const int nqt = (T + 63) / 64;
+    const int x = nqt - 1 - (int)(blockIdx.x / (unsigned)(groups * a.B));
+    const int hb = (int)(blockIdx.x % (unsigned)(groups * a.B));
+    const int head0 = (hb % groups) * NH, b = hb / groups;
+    const int kvh = head0 / (a.H / a.Hkv);
+    int ks0 = a.key_start ? a.key_start[b] : 0;
+    ks0 = ks0 < 0 ? 0 : (ks0 > T ? T : ks0);
+    ks0 = __builtin_amdgcn_readfirstlane(ks0);
+    const bf16_t* Qb = a.Q + (long)b * a.q_bstride + head0 * 256;
+    const bf16_t* Kb = a.K + (long)b * a.k_bstride + kvh * 256;
+    const bf16_t* Vb = a.Vt + (long)b * a.vt_bstride + (long)kvh * 256 * a.ldvt;
+    const int qi = x * 64 + wave * 16 + c16;
+    bf16_t* orow = a.O + (long)b * a.o_bstride + (long)qi * a.ldo + head0 * 256;
+
+    if (x * 64 + 63 < ks0) {  // a tile of padding rows only (the same answer in every wave: no barrier is skipped by some)
+        if (qi < T) {
+#pragma unroll
+            for (int h = 0; h < NH; ++h)
+#pragma unroll
+                for (int db = 0; db < 16; ++db) *(uint2*)(orow + h * 256 + db * 16 + g * 4) = uint2{0u, 0u};
+        }
+        return;
+    }
+
+    // Q fragments (B operand of S^T): lane (c16, g) holds Q[q = c16][d = 32*ks + 8g + j]; rows past T read row T-1 and are not stored
+    s16x8 qf[NH][8];
+    {
+        const bf16_t* qrow = Qb + (long)(qi < T ? qi : T - 1) * a.ldq + g * 8;
+#pragma unroll
+        for (int h = 0; h < NH; ++h)
+#pragma unroll
+            for (int ks = 0; ks < 8; ++ks) qf[h][ks] = *(const s16x8*)(qrow + h * 256 + ks * 32);
+    }
+
+    // staging: a K piece is 2 keys x 512 B, a Vt piece 8 rows x 128 B; wave w issues pieces w, w + 4, .. w + 28 of each operand. Keys
+    // past T read key T-1 (above the diagonal of every stored row); Vt columns up to roundup(T, 64) exist by the launcher's check.
+    const int k_r = 2 * wave + (lane >> 5), k_pch = lane & 31;  // piece i: key k_r + 8i, whose swizzle is 4*(i&3) | (k_r&3)
+    const int v_r = 8 * wave + (lane >> 3);                     // piece i: row v_r + 32i, whose swizzle (row>>1)&7 is that of v_r
+    const bf16_t* v_src = Vb + (long)v_r * a.ldvt + (((lane & 7) ^ ((v_r >> 1) & 7)) << 3);
+    auto stage = [&](int s, int t) {
+        char* kbuf = smem + s * D256_STAGE_BYTES;
+        char* vbuf = kbuf + D256_TILE_BYTES;
+        const int k0 = t * KV_TILE;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            int gk = k0 + k_r + 8 * i;
+            gk = gk < T ? gk : T - 1;
+            const int col = (k_pch ^ d256_key_swizzle(k_r + 8 * i)) << 3;
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(Kb + (long)gk * a.ldk + col),
+                                             (__attribute__((address_space(3))) void*)(kbuf + (wave + 4 * i) * 1024), 16, 0, 0);
+        }
+#pragma unroll
+        for (int i = 0; i < 8; ++i)
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(v_src + (long)(32 * i) * a.ldvt + k0),
+                                             (__attribute__((address_space(3))) void*)(vbuf + (wave + 4 * i) * 1024), 16, 0, 0);
+    };
+
+    // fragment addresses (block 0; blocks are compile-time offsets): K row of MFMA row c16 (its swizzle is c16), Vt row c16 of a d-block
+    const int kf_row = (8 * (c16 >> 2) + (c16 & 3)) * 512, kf_sw = c16;
+    const int vf_row = c16 * 128, vf_sw = (c16 >> 1) & 7;
+
+    f32x4 o[16][NH];
+#pragma unroll
+    for (int db = 0; db < 16; ++db)
+#pragma unroll
+        for (int h = 0; h < NH; ++h) o[db][h] = f32x4{0.f, 0.f, 0.f, 0.f};
+    float m_run[NH], l_run[NH];
+#pragma unroll
+    for (int h = 0; h < NH; ++h) {
+        m_run[h] = -INFINITY;
+        l_run[h] = 0.f;
+    }
+    const float c = a.scale * 1.4426950408889634f;
+
+    const int t_lo = ks0 / KV_TILE;  // <= x: the all-padding tile returned above
+    stage(0, t_lo);
+    __syncthreads();
+    for (int t = t_lo; t <= x; ++t) {
+        const int cur = (t - t_lo) & 1;
+        if (t < x) stage(cur ^ 1, t + 1);
+        const char* kbuf = smem + cur * D256_STAGE_BYTES;
+        const char* vbuf = kbuf + D256_TILE_BYTES;
+        const int k0 = t * KV_TILE;
+
+        // S^T = K Q^T: four 16-key blocks, eight k-steps over the head dim
+        f32x4 s[4][NH];
+#pragma unroll
+        for (int kb = 0; kb < 4; ++kb) {
+#pragma unroll
+            for (int h = 0; h < NH; ++h) s[kb][h] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int ks = 0; ks < 8; ++ks) {
+                const s16x8 kf = *(const s16x8*)(kbuf + (32 * (kb >> 1) + 4 * (kb & 1)) * 512 + kf_row + ((((ks << 2) + g) ^ kf_sw) << 4));
+#pragma unroll
+                for (int h = 0; h < NH; ++h)
+                    s[kb][h] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, kf), __builtin_bit_cast(bf16x8_t, qf[h][ks]),
+                                                                       s[kb][h], 0, 0, 0);
+            }
+        }
+        // this lane's score (kb, j) is key k0 + 32*(kb>>1) + 4*(kb&1) + 8g + j of query qi, for every head: the one or two boundary tiles
+        if (t == x || k0 < ks0) {
+#pragma unroll
+            for (int kb = 0; kb < 4; ++kb)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int key = k0 + 32 * (kb >> 1) + 4 * (kb & 1) + 8 * g + j;
+                    if (key < ks0 || key > qi) {
+#pragma unroll
+                        for (int h = 0; h < NH; ++h) s[kb][h][j] = -INFINITY;
+                    }
+                }
+        }
+        s16x8 pf[NH][2];
+#pragma unroll
+        for (int h = 0; h < NH; ++h) {
+            float mloc = s[0][h][0];
+#pragma unroll
+            for (int kb = 0; kb < 4; ++kb)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) mloc = fmaxf(mloc, s[kb][h][j]);
+            mloc = fmaxf(mloc, __shfl_xor(mloc, 16, 64));
+            mloc = fmaxf(mloc, __shfl_xor(mloc, 32, 64));
+            const float m_new = fmaxf(m_run[h], mloc);
+            const float m_use = m_new == -INFINITY ? 0.f : m_new;  // no valid key yet (a padding row): P = 0, nothing to rescale
+            const float alpha = __builtin_amdgcn_exp2f((m_run[h] - m_use) * c);
+            m_run[h] = m_new;
+            const float nmc = -m_use * c;
+            float psum = 0.f;
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                s16x8 pk;
+#pragma unroll
+                for (int hh = 0; hh < 2; ++hh)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        // the denominator sums the ROUNDED weights the PV product uses: O is then an exact average under slightly
+                        // moved weights (one dominant key comes out exactly), not an average divided by another sum
+                        const bf16_t pb = f32_to_bf16(__builtin_amdgcn_exp2f(__builtin_fmaf(s[2 * i + hh][h][j], c, nmc)));
+                        psum += bf16_to_f32(pb);
+                        pk[4 * hh + j] = (short)pb;
+                    }
+                pf[h][i] = pk;
+            }
+            l_run[h] = l_run[h] * alpha + psum;
+            if (__builtin_amdgcn_ballot_w64(alpha != 1.0f) != 0) {
+#pragma unroll
+                for (int db = 0; db < 16; ++db) o[db][h] *= alpha;
+            }
+        }
+        // O^T += Vt P^T: sixteen 16-channel blocks, two k-steps of 32 keys
+#pragma unroll
+        for (int db = 0; db < 16; ++db)
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                const s16x8 vf = *(const s16x8*)(vbuf + db * 16 * 128 + vf_row + ((((i << 2) + g) ^ vf_sw) << 4));
+#pragma unroll
+                for (int h = 0; h < NH; ++h)
+                    o[db][h] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, vf), __builtin_bit_cast(bf16x8_t, pf[h][i]),
+                                                                       o[db][h], 0, 0, 0);
+            }
+        __syncthreads();
+    }
+
+    // epilogue: register j of o[db][h] is channel 16*db + 4g + j of head head0 + h, query qi; rows past T are not written, padding rows are zeros
+#pragma unroll
+    for (int h = 0; h < NH; ++h) {
+        float l = l_run[h];
+        l += __shfl_xor(l, 16, 64);
+        l += __shfl_xor(l, 32, 64);
+        const float inv = qi < ks0 ? 0.f : 1.0f / l;
+        if (qi < T) {
+#pragma unroll
+            for (int db = 0; db < 16; ++db) {
+                uint2 pk;
+                pk.x = pack_bf16x2(o[db][h][0] * inv, o[db][h][1] * inv);
+                pk.y = pack_bf16x2(o[db][h][2] * inv, o[db][h][3] * inv);
+                *(uint2*)(orow + h * 256 + db * 16 + g * 4) = pk;
+            }
+        }
+    }
+}
+
+template <int NH>
+void launch_attn256(const AttnArgs& a, hipStream_t stream) {
+    static PerDeviceOnce attr_set;
+    attr_set.run([&] { HIP_CHECK(hipFuncSetAttribute((const void*)attn256_causal_kernel<NH>, hipFuncAttributeMaxDynamicSharedMemorySize, D256_LDS)); });
+    const dim3 grid(((a.Tq + 63) / 64) * (a.H / NH) * a.B);
+    hipLaunchKernelGGL((attn256_causal_kernel<NH>), grid, dim3(256), D256_LDS, stream, a);
+    HIP_CHECK(hipGetLastError());
+}
+
 }  // namespace
+
+// Head dim 256: causal grouped-query attention over left-padded keys (attn256_causal_kernel), the only form the text encoder runs.
+static void launch_attention_d256(AttnArgs a, hipStream_t stream) {
+    if (a.Hkv == 0) a.Hkv = a.H;
+    LTX_REQUIRE(a.causal, "attention: head dim 256 is the causal kernel only");
+    LTX_REQUIRE(!a.bias && !a.q_prescaled, "attention: head dim 256 takes neither a bias nor a prescaled query");
+    LTX_REQUIRE(a.B > 0 && a.H > 0 && a.Hkv > 0 && a.Tq > 0, "attention: empty problem");
+    LTX_REQUIRE(a.Tq == a.Tk, "attention: causal attention runs on Tq == Tk (%d, %d)", a.Tq, a.Tk);
+    LTX_REQUIRE(a.H % a.Hkv == 0, "attention: %d query heads over %d K/V heads", a.H, a.Hkv);
+    LTX_REQUIRE(a.scale > 0.f, "attention: scale %g", (double)a.scale);
+    LTX_REQUIRE(a.ldq % 8 == 0 && a.ldk % 8 == 0 && a.ldvt % 8 == 0 && a.ldo % 4 == 0, "attention: leading dims");
+    LTX_REQUIRE(a.ldq >= a.H * 256 && a.ldo >= a.H * 256 && a.ldk >= a.Hkv * 256, "attention: row strides must cover %d / %d heads of 256", a.H, a.Hkv);
+    LTX_REQUIRE(a.ldvt >= ((a.Tk + 63) / 64) * 64, "attention: Vt row stride %ld must cover Tk=%d rounded up to 64", a.ldvt, a.Tk);
+    LTX_REQUIRE(((uintptr_t)a.Q & 15) == 0 && ((uintptr_t)a.K & 15) == 0 && ((uintptr_t)a.Vt & 15) == 0 && ((uintptr_t)a.O & 7) == 0,
+                "attention: pointer alignment");
+    LTX_REQUIRE(a.q_bstride % 8 == 0 && a.k_bstride % 8 == 0 && a.vt_bstride % 8 == 0 && a.o_bstride % 4 == 0, "attention: batch strides");
+    // half of the (query, key) square is above the diagonal and never computed
+    ProfScope prof(PROF_ATTN, 2.0 * a.B * a.H * (double)a.Tq * a.Tk * 256, stream);
+    if ((a.H / a.Hkv) % 2 == 0)
+        launch_attn256<2>(a, stream);
+    else
+        launch_attn256<1>(a, stream);
+}
 
 // Head dim 64: the workgroup size by grid fill. 256 queries per workgroup when that still gives every second CU a workgroup (the
 // a2v launch: 1536 video queries x 32 heads = 192 workgroups); otherwise 128, then 64 queries per workgroup, so that the launches
@@ -1024,8 +1272,10 @@ static bool launch_attention_experiment(const AttnArgs&, int, bool, hipStream_t)
 #endif
 
 void launch_attention(const AttnArgs& a_in, hipStream_t stream) {
+    if (a_in.head_dim == 256) return launch_attention_d256(a_in, stream);
+    LTX_REQUIRE(!a_in.causal && !a_in.key_start && (a_in.Hkv == 0 || a_in.Hkv == a_in.H), "attention: causal / grouped-query launches run at head dim 256 only");
     if (a_in.head_dim == 64) return launch_attention_d64(a_in, stream);
-    LTX_REQUIRE(a_in.head_dim == 128, "attention: head dim %d (64 or 128)", a_in.head_dim);
+    LTX_REQUIRE(a_in.head_dim == 128, "attention: head dim %d (64, 128 or 256)", a_in.head_dim);
     AttnArgs a = a_in;
     // q_prescaled: every kernel but the prescaled assembly stream computes exp2(score * scale * log2(e)); with Q carrying
     // scale * log2(e) already that factor must be 1, i.e. scale = ln 2

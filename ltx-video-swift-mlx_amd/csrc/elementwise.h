@@ -251,3 +251,78 @@ void launch_enc_patchify(const float* pixels, bf16_t* out, int T, int H, int W, 
 void launch_enc_s2d_residual(const float* conv, int Cc, const float* x, int Cx, float* out, int Cout, int T, int H, int W, int ft,
                              int fh, int fw, hipStream_t stream);
 void launch_enc_finish(const float* z, long ldz, const float* mean, const float* stdv, float* out, int C, long P, hipStream_t stream);
+
+// ---- Gemma-3 text encoder row passes (Gemma3Model.swift: Gemma.RMSNorm, Gemma3Attention, Gemma3MLP, Gemma3InnerModel) ----
+// Every stream is bf16, as MLX stores it; statistics and arithmetic in f32. A norm weight arrives as the file's w (f32 container of a
+// bf16 value); the kernels form g = bf16(1 + w), rounded once, as Gemma.RMSNorm forms 1.0 + weight in the weight's dtype. The mean
+// square of a row is order-independent: exact f32 squares, summed in f64, rounded to f32 once (a host replay matches it bit for bit).
+//   x == null:  h = bf16(rmsnorm(r) * g)                                   (layer 0's input norm)
+//   x != null:  h = bf16(x + bf16(rmsnorm(r) * g))                         (post-norm + Gemma.clipResidual, Gemma3Model.swift:161-166)
+//   w2 != null: n = bf16(rmsnorm(h) * g2) in the same pass                 (the next pre-norm, or model.norm after the last layer)
+//   n_only:     h is not written (the raw output of the last layer is not exported; n = model.norm(h) is)
+// One workgroup per row, D % 8 == 0 up to 8192, leading dims multiples of 8. x may alias h (each row is read before it is written).
+struct GemmaNormArgs {
+    const bf16_t* r = nullptr;  // [rows][ldr]
+    long ldr = 0;
+    const float* w = nullptr;   // [D]
+    const bf16_t* x = nullptr;  // [rows][ldx] or null
+    long ldx = 0;
+    bf16_t* h = nullptr;        // [rows][ldh]
+    long ldh = 0;
+    const float* w2 = nullptr;  // [D] or null
+    bf16_t* n = nullptr;        // [rows][ldn]
+    long ldn = 0;
+    int n_only = 0;
+    int rows = 0, D = 0;
+    float eps = 1e-6f;
+};
+void launch_gemma_norm(const GemmaNormArgs& args, hipStream_t stream);
+
+// q_norm / k_norm per head of 256 and the non-traditional RoPE (Gemma3Model.swift:88-96), q and k in ONE launch: job j is `heads` heads
+// of 256 at columns 0 .. of its row. y = bf16(rmsnorm(head) * bf16(1 + w)), then element i < 128 pairs with i + 128:
+// out[i] = bf16(y[i] cos - y[i+128] sin), out[i+128] = bf16(y[i] sin + y[i+128] cos), cos / sin = f32 [T][128] rows indexed by
+// row % T (launch_gemma_rope_tables: position p, frequency base^(-i/128)). In place when out == x. Half a wave per head.
+struct GemmaQkArgs {
+    struct Job {
+        const bf16_t* x = nullptr;  // [rows][ldx]
+        long ldx = 0;
+        const float* w = nullptr;   // [256]
+        bf16_t* out = nullptr;      // [rows][ldo]
+        long ldo = 0;
+        int heads = 0;              // 0: an empty job
+    };
+    Job job[2];
+    const float* cos = nullptr;
+    const float* sin = nullptr;
+    int T = 1, rows = 0;
+    float eps = 1e-6f;
+};
+void launch_gemma_qknorm_rope(const GemmaQkArgs& args, hipStream_t stream);
+// cos / sin [T][128] f32 of positions 0 .. T-1 for one base, made on the device: angle = p * base^(-i / 128), evaluated in f64 and
+// rounded to f32 once
+void launch_gemma_rope_tables(float* cos_t, float* sin_t, int T, float base, hipStream_t stream);
+
+// out = bf16(bf16(gelu_tanh(g)) * u) over the halves g = gu[:, :I], u = gu[:, I:] of a fused gate|up output (Gemma3Model.swift:128)
+struct GegluArgs {
+    const bf16_t* gu = nullptr;  // [rows][ldgu]
+    long ldgu = 0;
+    bf16_t* out = nullptr;       // [rows][ldo]
+    long ldo = 0;
+    int rows = 0, I = 0;         // I % 8 == 0
+};
+void launch_geglu(const GegluArgs& args, hipStream_t stream);
+
+// out[r][:] = bf16(table[id[r]][:] * scale), scale = bf16(sqrt(hidden)) (Gemma3Model.swift:209-211). Ids outside [0, vocab) are
+// CLAMPED here: a device-side caller has no host to report to (the host-pointer entry rejects them before the launch).
+struct GemmaEmbedArgs {
+    const int32_t* ids = nullptr;   // [rows]
+    const bf16_t* table = nullptr;  // [vocab][D]
+    bf16_t* out = nullptr;          // [rows][D]
+    int rows = 0, D = 0, vocab = 0;
+    float scale = 1.0f;
+};
+void launch_gemma_embed(const GemmaEmbedArgs& args, hipStream_t stream);
+
+// Left-padded mask 0..0 1..1 -> key_start[b] = index of the first 1; status[b] = 1 when row b is of that form with at least one 1
+// (values 0 / 1 only), else 0. One workgroup per batch element.
+void launch_gemma_mask_scan(const int32_t* mask, int B, int T, int32_t* key_start, int32_t* status, hipStream_t stream);

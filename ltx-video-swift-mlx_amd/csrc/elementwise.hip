@@ -1682,3 +1682,272 @@ void launch_enc_finish(const float* z, long ldz, const float* mean, const float*
     hipLaunchKernelGGL(enc_finish_kernel, dim3(cdiv((long)C * P, 256)), dim3(256), 0, stream, z, ldz, mean, stdv, out, C, P);
     HIP_CHECK(hipGetLastError());
 }
+
+// ---------------------------------------------------------------------------------------------------------------
+// Gemma-3 text encoder row passes (Gemma3Model.swift)
+// ---------------------------------------------------------------------------------------------------------------
+namespace {
+LTX_DEVFN float bf16_round(float v) { return bf16_to_f32(f32_to_bf16(v)); }
+LTX_DEVFN void load_bf16x8(const bf16_t* p, float (&v)[8]) {
+    const uint4 u = *(const uint4*)p;
+    const uint32_t w[4] = {u.x, u.y, u.z, u.w};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        v[2 * i] = __builtin_bit_cast(float, w[i] << 16);
+        v[2 * i + 1] = __builtin_bit_cast(float, w[i] & 0xffff0000u);
+    }
+}
+LTX_DEVFN void store_bf16x8(bf16_t* p, const float (&v)[8]) {
+    uint4 u;
+    u.x = pack_bf16x2(v[0], v[1]);
+    u.y = pack_bf16x2(v[2], v[3]);
+    u.z = pack_bf16x2(v[4], v[5]);
+    u.w = pack_bf16x2(v[6], v[7]);
+    *(uint4*)p = u;
+}
+LTX_DEVFN void load_gain8(const float* w, float (&g)[8]) {  // g = bf16(1 + w)
+    const f32x4 a = *(const f32x4*)w, b = *(const f32x4*)(w + 4);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        g[e] = bf16_round(1.0f + a[e]);
+        g[4 + e] = bf16_round(1.0f + b[e]);
+    }
+}
+
+// The mean square of a row of bf16 values, defined so that a host replay can reproduce it bit for bit: the squares are exact in f32,
+// their sum is taken in f64 (exact up to 2^-53, whatever the order) and rounded to f32 once; the division, the square root and the
+// reciprocal are the correctly rounded f32 operations.
+LTX_DEVFN float rstd_of(double sum_sq, int D, float eps) { return 1.0f / sqrtf((float)sum_sq / (float)D + eps); }
+LTX_DEVFN double block_reduce_sum_f64(double v, double* red) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    __syncthreads();  // protect `red` from a previous use
+    if (lane == 0) red[w] = v;
+    __syncthreads();
+    return red[0] + red[1] + red[2] + red[3];
+}
+
+// one workgroup per row; NV chunks of 8 per thread (D <= NV * 2048)
+template <int NV>
+__global__ __launch_bounds__(256) void gemma_norm_kernel(const GemmaNormArgs a) {
+    __shared__ double red[4];
+    const int row = blockIdx.x;
+    const int nchunk = a.D >> 3;
+    float v[NV][8], g[NV][8];
+    double ss = 0.0;
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+        const int c = threadIdx.x + j * 256;
+        if (c < nchunk) {
+            load_bf16x8(a.r + (long)row * a.ldr + c * 8, v[j]);
+            load_gain8(a.w + c * 8, g[j]);
+        } else {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) v[j][e] = g[j][e] = 0.f;
+        }
+#pragma unroll
+        for (int e = 0; e < 8; ++e) ss += (double)(v[j][e] * v[j][e]);
+    }
+    float rstd = rstd_of(block_reduce_sum_f64(ss, red), a.D, a.eps);
+    ss = 0.0;
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+        const int c = threadIdx.x + j * 256;
+        if (c < nchunk) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) v[j][e] = bf16_round(v[j][e] * rstd * g[j][e]);
+            if (a.x) {
+                float xr[8];
+                load_bf16x8(a.x + (long)row * a.ldx + c * 8, xr);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) v[j][e] = bf16_round(xr[e] + v[j][e]);
+            }
+            if (!a.n_only) store_bf16x8(a.h + (long)row * a.ldh + c * 8, v[j]);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) ss += (double)(v[j][e] * v[j][e]);
+        }
+    }
+    if (!a.w2) return;
+    rstd = rstd_of(block_reduce_sum_f64(ss, red), a.D, a.eps);
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+        const int c = threadIdx.x + j * 256;
+        if (c < nchunk) {
+            load_gain8(a.w2 + c * 8, g[j]);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) v[j][e] = v[j][e] * rstd * g[j][e];
+            store_bf16x8(a.n + (long)row * a.ldn + c * 8, v[j]);
+        }
+    }
+}
+
+// half a wave per (row, head): lane l of the half holds elements 4l .. 4l+3 and 128 + 4l .. of the head, i.e. both members of four pairs
+__global__ __launch_bounds__(256) void gemma_qknorm_rope_kernel(const GemmaQkArgs a, int heads_total) {
+#pragma clang fp contract(off)  // the four products and two sums of a rotation are each rounded on their own: the replay's order
+    const long unit = (long)blockIdx.x * 8 + (threadIdx.x >> 5);
+    if (unit >= (long)a.rows * heads_total) return;  // whole half-waves leave together; the shuffles below stay inside a half
+    const int row = (int)(unit / heads_total);
+    int head = (int)(unit % heads_total);
+    const bool second = head >= a.job[0].heads;
+    if (second) head -= a.job[0].heads;
+    const GemmaQkArgs::Job& j = a.job[second ? 1 : 0];
+    const int l = threadIdx.x & 31;
+    const bf16_t* xr = j.x + (long)row * j.ldx + head * 256 + 4 * l;
+    const uint2 ulo = *(const uint2*)xr, uhi = *(const uint2*)(xr + 128);
+    float lo[4] = {__builtin_bit_cast(float, ulo.x << 16), __builtin_bit_cast(float, ulo.x & 0xffff0000u), __builtin_bit_cast(float, ulo.y << 16),
+                   __builtin_bit_cast(float, ulo.y & 0xffff0000u)};
+    float hi[4] = {__builtin_bit_cast(float, uhi.x << 16), __builtin_bit_cast(float, uhi.x & 0xffff0000u), __builtin_bit_cast(float, uhi.y << 16),
+                   __builtin_bit_cast(float, uhi.y & 0xffff0000u)};
+    const f32x4 wlo = *(const f32x4*)(j.w + 4 * l), whi = *(const f32x4*)(j.w + 128 + 4 * l);
+    const long p = row % a.T;
+    const f32x4 cs = *(const f32x4*)(a.cos + p * 128 + 4 * l), sn = *(const f32x4*)(a.sin + p * 128 + 4 * l);
+    double ss = 0.0;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) ss += (double)(lo[e] * lo[e]) + (double)(hi[e] * hi[e]);
+#pragma unroll
+    for (int off = 16; off > 0; off >>= 1) ss += __shfl_xor(ss, off, 64);
+    const float rstd = rstd_of(ss, 256, a.eps);
+    float olo[4], ohi[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const float y1 = bf16_round(lo[e] * rstd * bf16_round(1.0f + wlo[e]));
+        const float y2 = bf16_round(hi[e] * rstd * bf16_round(1.0f + whi[e]));
+        olo[e] = y1 * cs[e] - y2 * sn[e];
+        ohi[e] = y1 * sn[e] + y2 * cs[e];
+    }
+    bf16_t* orow = j.out + (long)row * j.ldo + head * 256 + 4 * l;
+    uint2 pk;
+    pk.x = pack_bf16x2(olo[0], olo[1]);
+    pk.y = pack_bf16x2(olo[2], olo[3]);
+    *(uint2*)orow = pk;
+    pk.x = pack_bf16x2(ohi[0], ohi[1]);
+    pk.y = pack_bf16x2(ohi[2], ohi[3]);
+    *(uint2*)(orow + 128) = pk;
+}
+
+// f64 evaluation, one rounding to f32 per entry: the tables are made once per model, and a host replay reproduces them to the last bit
+// or two (an f32 evaluation of the angle is off by up to 1e-6 of it, i.e. 1e-3 rad at position 1023)
+__global__ void gemma_rope_tables_kernel(float* __restrict__ cos_t, float* __restrict__ sin_t, int T, double log2_base) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= T * 128) return;
+    const double ang = (double)(i >> 7) * exp2(-((double)(i & 127) / 128.0) * log2_base);
+    cos_t[i] = (float)cos(ang);
+    sin_t[i] = (float)sin(ang);
+}
+
+__global__ __launch_bounds__(256) void geglu_kernel(const GegluArgs a) {
+    const int per_row = a.I >> 3;
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long)a.rows * per_row) return;
+    const long row = i / per_row;
+    const int c = (int)(i % per_row) * 8;
+    float g[8], u[8];
+    load_bf16x8(a.gu + row * a.ldgu + c, g);
+    load_bf16x8(a.gu + row * a.ldgu + a.I + c, u);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) g[e] = bf16_round(gelu_tanh(g[e])) * u[e];
+    store_bf16x8(a.out + row * a.ldo + c, g);
+}
+
+__global__ __launch_bounds__(256) void gemma_embed_kernel(const GemmaEmbedArgs a) {
+    const int row = blockIdx.x;
+    int id = a.ids[row];
+    id = id < 0 ? 0 : (id >= a.vocab ? a.vocab - 1 : id);
+    for (int c = threadIdx.x; c < (a.D >> 3); c += 256) {
+        float v[8];
+        load_bf16x8(a.table + (long)id * a.D + c * 8, v);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] *= a.scale;
+        store_bf16x8(a.out + (long)row * a.D + c * 8, v);
+    }
+}
+
+__global__ __launch_bounds__(256) void gemma_mask_scan_kernel(const int32_t* __restrict__ mask, int T, int32_t* __restrict__ key_start,
+                                                              int32_t* __restrict__ status) {
+    __shared__ int first, ones, bad;
+    if (threadIdx.x == 0) {
+        first = T;
+        ones = 0;
+        bad = 0;
+    }
+    __syncthreads();
+    const int32_t* m = mask + (long)blockIdx.x * T;
+    int f = T, n = 0, bd = 0;
+    for (int t = threadIdx.x; t < T; t += 256) {
+        const int v = m[t];
+        if (v == 1) {
+            f = f < t ? f : t;
+            ++n;
+        } else if (v != 0) {
+            bd = 1;
+        }
+    }
+    atomicMin(&first, f);
+    atomicAdd(&ones, n);
+    if (bd) atomicOr(&bad, 1);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        key_start[blockIdx.x] = first;
+        status[blockIdx.x] = (!bad && ones >= 1 && first == T - ones) ? 1 : 0;  // every position from the first 1 on is a 1
+    }
+}
+}  // namespace
+
+void launch_gemma_norm(const GemmaNormArgs& a, hipStream_t stream) {
+    LTX_REQUIRE(a.r && a.w && (a.h || a.n_only) && a.rows > 0, "gemma_norm: null argument");
+    LTX_REQUIRE(a.D % 8 == 0 && a.D >= 8 && a.D <= 8192, "gemma_norm: D %d must be a multiple of 8 up to 8192", a.D);
+    LTX_REQUIRE(a.ldr % 8 == 0 && a.ldr >= a.D && (a.n_only || (a.ldh % 8 == 0 && a.ldh >= a.D)), "gemma_norm: leading dims");
+    LTX_REQUIRE(!a.x || (a.ldx % 8 == 0 && a.ldx >= a.D), "gemma_norm: residual leading dim");
+    LTX_REQUIRE(!a.w2 == !a.n && (!a.w2 || (a.ldn % 8 == 0 && a.ldn >= a.D)), "gemma_norm: the second norm needs w2 and n");
+    LTX_REQUIRE(!a.n_only || a.w2, "gemma_norm: n_only without a second norm writes nothing");
+    if (a.D <= 2048)
+        hipLaunchKernelGGL(gemma_norm_kernel<1>, dim3(a.rows), dim3(256), 0, stream, a);
+    else if (a.D <= 4096)
+        hipLaunchKernelGGL(gemma_norm_kernel<2>, dim3(a.rows), dim3(256), 0, stream, a);
+    else
+        hipLaunchKernelGGL(gemma_norm_kernel<4>, dim3(a.rows), dim3(256), 0, stream, a);
+    HIP_CHECK(hipGetLastError());
+}
+
+void launch_gemma_qknorm_rope(const GemmaQkArgs& a, hipStream_t stream) {
+    const int heads = a.job[0].heads + a.job[1].heads;
+    LTX_REQUIRE(a.rows > 0 && a.T > 0 && a.job[0].heads > 0 && a.job[1].heads >= 0 && a.cos && a.sin, "gemma_qknorm_rope: empty launch");
+    for (int i = 0; i < 2; ++i) {
+        const GemmaQkArgs::Job& j = a.job[i];
+        if (j.heads == 0) continue;
+        LTX_REQUIRE(j.x && j.w && j.out, "gemma_qknorm_rope: null argument");
+        LTX_REQUIRE(j.ldx % 4 == 0 && j.ldo % 4 == 0 && j.ldx >= j.heads * 256 && j.ldo >= j.heads * 256, "gemma_qknorm_rope: leading dims");
+        LTX_REQUIRE(((uintptr_t)j.x & 7) == 0 && ((uintptr_t)j.out & 7) == 0, "gemma_qknorm_rope: pointer alignment");
+    }
+    const long units = (long)a.rows * heads;
+    hipLaunchKernelGGL(gemma_qknorm_rope_kernel, dim3((unsigned)((units + 7) / 8)), dim3(256), 0, stream, a, heads);
+    HIP_CHECK(hipGetLastError());
+}
+
+void launch_gemma_rope_tables(float* cos_t, float* sin_t, int T, float base, hipStream_t stream) {
+    LTX_REQUIRE(cos_t && sin_t && T > 0 && base > 1.0f, "gemma_rope_tables: arguments");
+    hipLaunchKernelGGL(gemma_rope_tables_kernel, dim3((T * 128 + 255) / 256), dim3(256), 0, stream, cos_t, sin_t, T, log2((double)base));
+    HIP_CHECK(hipGetLastError());
+}
+
+void launch_geglu(const GegluArgs& a, hipStream_t stream) {
+    LTX_REQUIRE(a.gu && a.out && a.rows > 0, "geglu: null argument");
+    LTX_REQUIRE(a.I % 8 == 0 && a.I >= 8 && a.ldgu % 8 == 0 && a.ldgu >= 2 * a.I && a.ldo % 8 == 0 && a.ldo >= a.I, "geglu: shape");
+    const long n = (long)a.rows * (a.I >> 3);
+    hipLaunchKernelGGL(geglu_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, a);
+    HIP_CHECK(hipGetLastError());
+}
+
+void launch_gemma_embed(const GemmaEmbedArgs& a, hipStream_t stream) {
+    LTX_REQUIRE(a.ids && a.table && a.out && a.rows > 0 && a.vocab > 0, "gemma_embed: null argument");
+    LTX_REQUIRE(a.D % 8 == 0 && a.D >= 8, "gemma_embed: D %d must be a multiple of 8", a.D);
+    hipLaunchKernelGGL(gemma_embed_kernel, dim3(a.rows), dim3(256), 0, stream, a);
+    HIP_CHECK(hipGetLastError());
+}
+
+void launch_gemma_mask_scan(const int32_t* mask, int B, int T, int32_t* key_start, int32_t* status, hipStream_t stream) {
+    LTX_REQUIRE(mask && key_start && status && B > 0 && T > 0, "gemma_mask_scan: arguments");
+    hipLaunchKernelGGL(gemma_mask_scan_kernel, dim3(B), dim3(256), 0, stream, mask, T, key_start, status);
+    HIP_CHECK(hipGetLastError());
+}

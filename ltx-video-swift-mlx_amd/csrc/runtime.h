@@ -92,6 +92,7 @@ struct VocoderModel;
 struct AttnModule;
 struct DualStack;
 struct DualModel;
+struct GemmaModel;
 struct DistState;
 
 // ---- live per-kernel timing (HIP events recorded on the launch stream around each launch of a kernel family) ----
@@ -166,6 +167,7 @@ struct ltx_ctx {
     AttnModule* attn_modules[kAttnModuleSlots] = {};  // head-dim-64 attention modules by index (attn_module.h)
     DualStack* dual = nullptr;  // dual video + audio transformer blocks (dual_block.h)
     DualModel* dual_model = nullptr;  // the dual model: its own blocks + embedders, caption projections and heads (dual_model.h)
+    GemmaModel* gemma = nullptr;  // the Gemma-3 text encoder (gemma.h)
     DevBuf audio_mel, audio_op[2];  // the mel between the two audio models; haloed operands of the audio conv test hooks
     DevBuf h2d[H2D_COUNT];  // staging buffers of the host-pointer entry points, indexed by H2dSlot
     // load report of the last *_load call (mirrors the reference's "unmatched/missing" debug logs)

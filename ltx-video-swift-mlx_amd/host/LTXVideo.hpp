@@ -8,8 +8,9 @@
 //   LTXError, GenerationTimings, VideoGenerationResult     LTXVideo.swift:66-141,255-348
 //   GenerationProgress, PrecomputedEmbeddings, LTXPipeline Pipeline/LTXPipeline.swift:50-72,117-200,571-1076,2420-2741,3134
 //
-// Out of scope here: the Gemma text encoder and MP4 export. Text embeddings therefore enter through the
-// `PrecomputedEmbeddings` hook the reference already has, and every noise tensor is an explicit input (or comes from
+// Out of scope here: the tokenizer, text generation and MP4 export. Text embeddings enter through the
+// `PrecomputedEmbeddings` hook the reference already has, or come from encodePrompt on token ids (loadGemma: the Gemma-3 encoder,
+// Gemma3Model.swift); every noise tensor is an explicit input (or comes from
 // the documented splitmix64/Box-Muller generator below - NOT MLX's threefry stream, which cannot be verified here).
 #pragma once
 #include <chrono>
@@ -278,6 +279,51 @@ class LTXPipeline {
         return e;
     }
 
+    // The Gemma-3 language model of the text encoder (Gemma3Model.swift; loaded and unloaded around encoding, LTXPipeline.swift:3194-3277):
+    // the safetensors shards of one checkpoint, bf16 or MLX 4- / 8-bit.
+    void loadGemma(const std::vector<std::string>& shards, const ltx_gemma_config* cfg = nullptr) {
+        std::vector<const char*> paths;
+        for (const std::string& p : shards) paths.push_back(p.c_str());
+        check(ltx_gemma_load(ctx_, paths.data(), int(paths.size()), cfg));
+        if (cfg) gemmaCfg_ = *cfg; else ltx_gemma_config_default(&gemmaCfg_);
+        gemmaLoaded_ = true;
+    }
+    void unloadGemma() {
+        check(ltx_gemma_unload(ctx_));
+        gemmaLoaded_ = false;
+    }
+    // encodePrompt (LTXPipeline.swift:1155-1170) from the tokenizer's output: token ids + left-padded attention mask [T] -> all hidden
+    // states -> connector -> the PrecomputedEmbeddings the generate* calls take. With a negative prompt (same T) both run as one batch
+    // of 2. The tokenizer itself is not part of this library.
+    PrecomputedEmbeddings encodePrompt(const std::vector<int32_t>& tokenIds, const std::vector<int32_t>& attentionMask,
+                                       const std::vector<int32_t>* nullTokenIds = nullptr, const std::vector<int32_t>* nullAttentionMask = nullptr) {
+        if (!gemmaLoaded_) throw LTXError(LTXError::textEncodingFailed, "the Gemma text encoder is not loaded (loadGemma)");
+        if (!connectorLoaded_) throw LTXError(LTXError::modelNotLoaded, "Model not loaded: text-embedding connector");
+        const size_t T = tokenIds.size();
+        const bool two = nullTokenIds && nullAttentionMask;
+        if (T == 0 || attentionMask.size() != T || (two && (nullTokenIds->size() != T || nullAttentionMask->size() != T)))
+            throw LTXError(LTXError::textEncodingFailed, "token ids and attention masks must all be [T]");
+        const int B = two ? 2 : 1;
+        std::vector<int32_t> ids(tokenIds), mask(attentionMask);
+        if (two) {
+            ids.insert(ids.end(), nullTokenIds->begin(), nullTokenIds->end());
+            mask.insert(mask.end(), nullAttentionMask->begin(), nullAttentionMask->end());
+        }
+        // one call: only ids, mask and context cross the bus, the hidden states stay on the device
+        std::vector<uint16_t> context(size_t(B) * T * connCfg_.dim);
+        std::vector<int32_t> outMask(size_t(B) * T);
+        check(ltx_text_encode(ctx_, ids.data(), mask.data(), B, int(T), context.data(), outMask.data()));
+        PrecomputedEmbeddings e;
+        e.S = int(T);
+        e.promptEmbeddings.assign(context.begin(), context.begin() + T * connCfg_.dim);
+        e.promptMask.assign(outMask.begin(), outMask.begin() + T);
+        if (two) {
+            e.nullEmbeddings.assign(context.begin() + T * connCfg_.dim, context.end());
+            e.nullMask.assign(outMask.begin() + T, outMask.end());
+        }
+        return e;
+    }
+
     // generateVideo (LTXPipeline.swift:586-1046), text-to-video. `noise`: [1,128,F',H',W'] N(0,1) or empty (then
     // config.seed drives generateNoise above).
     VideoGenerationResult generateVideo(const LTXVideoGenerationConfig& config, const PrecomputedEmbeddings& emb,
@@ -404,7 +450,7 @@ class LTXPipeline {
     }
     static void buildContext(const PrecomputedEmbeddings& emb, bool useCFG, std::vector<uint16_t>& ctxBits, std::vector<int32_t>& mask) {
         if (emb.promptEmbeddings.empty() || emb.S <= 0)
-            throw LTXError(LTXError::textEncodingFailed, "no PrecomputedEmbeddings supplied (the Gemma text encoder is outside this path)");
+            throw LTXError(LTXError::textEncodingFailed, "no PrecomputedEmbeddings supplied (encodePrompt makes them from token ids once loadGemma and loadConnector have run)");
         const size_t per = emb.promptEmbeddings.size();
         if (useCFG) {  // batch order [negative, positive] (LTXPipeline.swift:715-716)
             ctxBits.assign(2 * per, 0);
@@ -443,8 +489,9 @@ class LTXPipeline {
     LTXModel model_;
     LTXQuantizationConfig quant_;
     MemoryOptimizationConfig mem_;
-    bool ditLoaded_ = false, vaeLoaded_ = false, connectorLoaded_ = false;
+    bool ditLoaded_ = false, vaeLoaded_ = false, connectorLoaded_ = false, gemmaLoaded_ = false;
     ltx_connector_config connCfg_{};
+    ltx_gemma_config gemmaCfg_{};
 };
 
 }  // namespace ltx

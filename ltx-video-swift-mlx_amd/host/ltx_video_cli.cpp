@@ -1,8 +1,10 @@
 // ltx_video_cli.cpp - `ltx-video` command line, same subcommands / flags / defaults / validation messages as the
 // reference CLI (Sources/LTXVideoCLI/LTXVideoCLI.swift:21-449), on top of host/LTXVideo.hpp -> libltxhip.so.
 //
-// Differences forced by scope: the Gemma text encoder, prompt enhancement, audio, I2V, downloads and MP4
-// export are not part of this path. Text conditioning comes from `--embeddings <file.safetensors>` (keys
+// Differences forced by scope: the tokenizer, prompt enhancement, audio, I2V, downloads and MP4
+// export are not part of this path. Text conditioning comes from `--gemma-weights <shards> --token-ids <file.safetensors>` (keys
+// input_ids [1,T], optional attention_mask; the Gemma-3 encoder and the connector run here), from `--gemma-hidden-states`, or from
+// `--embeddings <file.safetensors>` (keys
 // prompt_embeddings [1,S,3840], prompt_mask [1,S], optional negative_embeddings / negative_mask) - the CLI-level
 // equivalent of the reference's PrecomputedEmbeddings hook - the VAE from `--vae-weights`, and frames are written as a
 // raw float32 (F,H,W,3) file plus a JSON sidecar instead of an MP4.
@@ -37,6 +39,7 @@ struct Args {
          dryRun = false;
     // additions of this build
     std::string embeddings, vaeWeights, upscalerWeights, distilledLoraPath, pngDir, hiddenStates, connectorWeights, imageTensor;
+    std::string gemmaWeights, tokenIds, negativeTokenIds;  // the Gemma-3 text encoder: safetensors shards (comma-separated) + tokenised prompts
     std::string noiseRng = "native";
     int vaeTile = 0, vaeOverlap = 1;
     int numLayers = 0, numHeads = 0, captionChannels = 0;  // reduced architectures for tests (0 = reference default)
@@ -53,6 +56,7 @@ struct Args {
                  "  [--transformer-quant bf16|qint8|int4] [--two-stage] [--distilled-lora] [--profile] [--dry-run] [--debug]\n"
                  "  [--embeddings file] [--vae-weights file] [--upscaler-weights file] [--distilled-lora-path file]\n"
                  "  [--vae-tile N] [--vae-overlap N] [--png-dir dir] [--gemma-hidden-states file] [--connector-weights file]\n"
+                 "  [--gemma-weights file[,file...] --token-ids file [--negative-token-ids file]]\n"
                  "  [--image-tensor file] [--noise-rng native|mlx] [--hip-option name=value]...\n"
                  "decode-audio  Audio latent -> 24 kHz stereo WAV (audio VAE decoder + vocoder)\n"
                  "  (--latent file.safetensors [key audio_latent, (8,T,16)] | --synthetic [--frames 121]) [--audio-vae-weights file]\n"
@@ -116,6 +120,9 @@ Args parse_generate(int argc, char** argv, int start) {
         }
         else if (k == "--gemma-hidden-states") a.hiddenStates = need(i);
         else if (k == "--connector-weights") a.connectorWeights = need(i);
+        else if (k == "--gemma-weights") a.gemmaWeights = need(i);
+        else if (k == "--token-ids") a.tokenIds = need(i);
+        else if (k == "--negative-token-ids") a.negativeTokenIds = need(i);
         else if (k == "--image-tensor") a.imageTensor = need(i);
         else if (k == "--vae-overlap") a.vaeOverlap = std::stoi(need(i));
         else if (k == "--num-layers") a.numLayers = std::stoi(need(i));
@@ -128,6 +135,28 @@ Args parse_generate(int argc, char** argv, int start) {
     }
     if (!have_prompt) throw ValidationError("Missing expected argument '<prompt>'");
     return a;
+}
+
+std::vector<std::string> split_commas(const std::string& s) {
+    std::vector<std::string> out;
+    std::stringstream ss(s);
+    std::string tok;
+    while (std::getline(ss, tok, ','))
+        if (!tok.empty()) out.push_back(tok);
+    return out;
+}
+
+// A tokenised prompt: "input_ids" [1][T] (or [T]) int32 and, optionally, "attention_mask" of the same shape (absent: all ones)
+void read_token_ids(const std::string& path, std::vector<int32_t>& ids, std::vector<int32_t>& mask) {
+    long shp[8] = {0};
+    const int nd = ltx_st_info(path.c_str(), "input_ids", shp);
+    if (nd < 1 || nd > 2 || (nd == 2 && shp[0] != 1))
+        throw LTXError(LTXError::textEncodingFailed, "input_ids must be [1][T] or [T] int32 in " + path + ": " + ltx_last_error(nullptr));
+    const long T = shp[nd - 1];
+    ids.resize(T);
+    ltx_st_read(path.c_str(), "input_ids", 2, ids.data(), T);
+    mask.assign(T, 1);
+    if (ltx_st_info(path.c_str(), "attention_mask", shp) > 0) ltx_st_read(path.c_str(), "attention_mask", 2, mask.data(), T);
 }
 
 std::vector<int> parse_blocks(const std::string& s) {
@@ -195,6 +224,15 @@ int run_generate(const Args& a) {
         std::cout << "Two-stage pipeline: " << a.width / 2 << "x" << a.height / 2 << " -> upscale 2x -> " << a.width << "x" << a.height << "\n";
     }
     if (a.distilledLora) std::cout << "Distilled LoRA: will fuse into dev model (8 steps, no CFG)\n";
+    // the Gemma-3 text encoder of this build: weights and a tokenised prompt go together (the tokenizer is not part of it)
+    if (!a.gemmaWeights.empty() && a.tokenIds.empty()) throw ValidationError("--gemma-weights needs --token-ids (the tokenizer is outside this build)");
+    if (a.gemmaWeights.empty() && !a.tokenIds.empty()) throw ValidationError("--token-ids needs --gemma-weights");
+    if (!a.negativeTokenIds.empty() && a.tokenIds.empty()) throw ValidationError("--negative-token-ids needs --token-ids");
+    if (!a.gemmaWeights.empty() && (!a.hiddenStates.empty() || !a.embeddings.empty()))
+        throw ValidationError("--gemma-weights is an alternative to --gemma-hidden-states and --embeddings: give one of them");
+    if (!a.gemmaWeights.empty())
+        std::cout << "Text encoder: Gemma-3 (" << split_commas(a.gemmaWeights).size() << " shard(s))" << (a.negativeTokenIds.empty() ? "" : ", with a negative prompt")
+                  << "\n";
     if (a.dryRun) {
         std::cout << "Validation passed (dry run mode)\n";
         return 0;
@@ -202,8 +240,9 @@ int run_generate(const Args& a) {
     if (!a.image.empty() || a.audio || a.enhancePrompt)
         throw ValidationError("--image (file decoding) / --audio / --enhance-prompt are outside the MI355X hot path of this build; "
                               "pass the image as a float tensor with --image-tensor");
-    if (a.ltxWeights.empty() || a.vaeWeights.empty() || (a.embeddings.empty() && a.hiddenStates.empty()))
-        throw ValidationError("this build needs --ltx-weights, --vae-weights and --embeddings or --gemma-hidden-states (no downloads, no Gemma)");
+    if (a.ltxWeights.empty() || a.vaeWeights.empty() || (a.embeddings.empty() && a.hiddenStates.empty() && a.gemmaWeights.empty()))
+        throw ValidationError("this build needs --ltx-weights, --vae-weights and --embeddings or --gemma-hidden-states, or --gemma-weights with "
+                              "--token-ids (no downloads, no tokenizer)");
 
     std::cout << "Creating pipeline...\n";
     MemoryOptimizationConfig mem = MemoryOptimizationConfig::defaultConfig();
@@ -249,6 +288,17 @@ int run_generate(const Args& a) {
         std::vector<int32_t> am(T, 1);
         if (ltx_st_info(a.hiddenStates.c_str(), "attention_mask", shp) > 0) ltx_st_read(a.hiddenStates.c_str(), "attention_mask", 2, am.data(), T);
         emb = pipeline.encodeFromHiddenStates(hs, am, T);
+    } else if (!a.gemmaWeights.empty()) {
+        // text encoding in full (LTXPipeline.encodePrompt, LTXPipeline.swift:1155-1170): Gemma-3 on the tokenised prompt(s), then the
+        // connector; the encoder is unloaded afterwards, as the reference does (:3194-3277)
+        std::cout << "Encoding prompt with Gemma-3...\n";
+        pipeline.loadConnector(a.connectorWeights.empty() ? a.ltxWeights : a.connectorWeights);
+        pipeline.loadGemma(split_commas(a.gemmaWeights));
+        std::vector<int32_t> ids, am, nids, nam;
+        read_token_ids(a.tokenIds, ids, am);
+        if (!a.negativeTokenIds.empty()) read_token_ids(a.negativeTokenIds, nids, nam);
+        emb = a.negativeTokenIds.empty() ? pipeline.encodePrompt(ids, am) : pipeline.encodePrompt(ids, am, &nids, &nam);
+        pipeline.unloadGemma();
     } else {
         emb = read_embeddings(a.embeddings);
     }
