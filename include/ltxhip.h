@@ -270,6 +270,29 @@ int ltx_dit_forward_tokens(ltx_ctx* ctx, const uint16_t* latent, const uint16_t*
  * (ltx_threefry2x32); the bits -> normal pipeline could not be checked against an MLX run. Pure host code. */
 int ltx_mlx_random_normal(uint64_t seed, int draw_index, float* out, long n);
 void ltx_threefry2x32(const uint32_t key[2], const uint32_t ctr[2], uint32_t out[2]);
+/* The key of the `draw_index`-th keyless draw after MLXRandom.seed(seed): draw_index + 1 key splits (KeySequence::next). The host
+ * generator above and the device generator below share it. draw_index < 0 or a NULL key_out: LTX_ERR_INVALID_CONFIGURATION. Pure host. */
+int ltx_mlx_draw_key(uint64_t seed, int draw_index, uint32_t key_out[2]);
+/* One draw of ltx_op_mlx_normal_group: n values from `key` into dst (DEVICE), each multiplied by `scale` in one more f32 multiply after
+ * sqrt(2) * erfinv(u) - the reference's separate `noise * sigmas[0]` (LTXPipeline.swift:1243, :1597-1598); scale = 1 leaves the bits of
+ * the draw. raw_bits != 0: dst receives the n uint32 words of the hash instead (the integer half of the pipeline, for tests). */
+typedef struct ltx_noise_job {
+    uint32_t key[2];
+    float* dst;
+    long n;
+    float scale;
+    int raw_bits;
+} ltx_noise_job;
+/* The MLX-compatible normal draws of a run on the device, in ONE launch for up to 64 jobs (more are sent 64 at a time): replaces the
+ * MLXRandom.normal / generateNoise calls of a generation (LTXPipeline.swift:1225-1236, :1291, :1572-1581, :1629, :1730-1734, :1766),
+ * which ltx_mlx_random_normal makes on one host thread. One thread per counter pair of mlx_random_bits; the bits -> normal tail is the
+ * host's operation by operation (correctly rounded division, separate multiply and add, fmaf, logf), so a value differs from
+ * ltx_mlx_random_normal only where the device's logf and the host's differ in the last place. jobs is a HOST array, every dst a
+ * DEVICE pointer; asynchronous on the context stream. n_jobs < 0, n < 0, n >= 2^31 (the counters are 32 bit) or a NULL dst with n > 0:
+ * LTX_ERR_INVALID_CONFIGURATION before any launch, nothing written. Empty jobs and n_jobs == 0 are valid and do nothing. */
+int ltx_op_mlx_normal_group(ltx_ctx* ctx, const ltx_noise_job* jobs, int n_jobs);
+/* ltx_mlx_random_normal into DEVICE memory, times scale: ltx_mlx_draw_key and one job of ltx_op_mlx_normal_group. */
+int ltx_mlx_random_normal_dev(ltx_ctx* ctx, uint64_t seed, int draw_index, float* out_dev, long n, float scale);
 
 /* tensorToImages' pixel conversion: out = uint8(clip(x, 0, 1) * 255), f32 multiply then truncation toward zero. */
 int ltx_frames_to_u8(const float* frames, long n, uint8_t* out);
@@ -667,6 +690,20 @@ int ltx_connector_encode(ltx_ctx* ctx, const uint16_t* hidden, const int32_t* at
 int ltx_connector_encode_taps_dev(ltx_ctx* ctx, const uint16_t* hidden, const int32_t* attention_mask, int B, int T,
                                   int padding_right, uint16_t* context, uint16_t* norm_concat, uint16_t* fe_out,
                                   float* after_registers);
+/* The audio text context (VideoGemmaTextEncoderModel.encodeFromHiddenStates / callAsFunction, LTXTextEncoder.swift:628-636, :705-713; fed
+ * to the audio stream at LTXPipeline.swift:1173): the feature extractor ONCE, then the video Embeddings1DConnector and a second,
+ * independently weighted one (`audio_embeddings_connector.*` / `audio_connector.*`, key rules ModelDownloader.swift:930-941) on its
+ * output. ltx_connector_load reads the audio set when the file has it; ltx_connector_init_synthetic makes one from a seed of its own.
+ * video_context, audio_context [B][T][dim] bf16, out_mask [B][T] int32 (all ones; may be NULL). The video context and the mask are
+ * ltx_connector_encode(_dev)'s, bit for bit. No audio set loaded: LTX_ERR_MODEL_NOT_LOADED before any launch (callers then hand the
+ * video context to the audio stream, `audioEncoding ?? videoEncoding`). DEVICE pointers. */
+int ltx_connector_encode_av_dev(ltx_ctx* ctx, const uint16_t* hidden, const int32_t* attention_mask, int B, int T, int padding_right,
+                                uint16_t* video_context, uint16_t* audio_context, int32_t* out_mask);
+/* HOST-pointer variant of the same call. */
+int ltx_connector_encode_av(ltx_ctx* ctx, const uint16_t* hidden, const int32_t* attention_mask, int B, int T, int padding_right,
+                            uint16_t* video_context, uint16_t* audio_context, int32_t* out_mask);
+/* 1 when the loaded connector has an audio set, 0 otherwise (also without a connector or a context). */
+int ltx_connector_has_audio(ltx_ctx* ctx);
 /* mapTextEncoderWeights (ModelDownloader.swift:911-968): returns the length of the module key, 0 if the key is dropped. */
 int ltx_map_text_encoder_key(const char* file_key, char* out, int cap);
 /* Connector RoPE tables (positions 0..T-1, one axis, f64 math): cos/sin [T][dim/2] f32, before the cast to bf16. */
@@ -829,6 +866,74 @@ typedef struct ltx_dual_two_stage_args {
 int ltx_dual_two_stage_dev(ltx_ctx* ctx, const ltx_dual_two_stage_args* args, ltx_progress_cb cb, void* user);
 /* The same with HOST pointers throughout; staged through the context's staging buffers, synchronous. */
 int ltx_dual_two_stage(ltx_ctx* ctx, const ltx_dual_two_stage_args* args, ltx_progress_cb cb, void* user);
+
+/* Arguments of ltx_dual_generate(_dev) and ltx_dual_noise_plan; starts with its own size (LTX_DUAL_GENERATE_ARGS_INIT). A generation
+ * from a seed alone: the noise of ltx_dual_denoise / ltx_dual_two_stage drawn by the library, on the device, in the reference's order. */
+typedef struct ltx_dual_generate_args {
+    uint32_t struct_size;          /* sizeof(ltx_dual_generate_args) in the caller's translation unit */
+    int two_stage;                 /* 0: generateVideoWithAudio (ltx_dual_denoise); non-zero: generateVideoWithAudioTwoStage (ltx_dual_two_stage) */
+    uint64_t seed;                 /* MLXRandom.seed(seed) (LTXPipeline.swift:1224-1226, :1571-1573) */
+    int channels;                  /* latent channels (128): must be the loaded model's in_channels */
+    int F, H, W;                   /* latent frames / height / width; of STAGE 1 with two_stage (stage 2 runs at F, 2H, 2W) */
+    int T_a;                       /* audio latent frames (ltx_audio_latent_frames) */
+    int S;                         /* text tokens */
+    float* video_latent;           /* OUT [1][channels][F][H][W] f32, or [1][channels][F][2H][2W] with two_stage */
+    float* audio_latent;           /* OUT [1][8][T_a][16] f32 */
+    const float* sigmas1;          /* HOST, n_sigmas1 values: the only schedule, or stage 1's */
+    int n_sigmas1;
+    const float* sigmas2;          /* HOST, two_stage only: n_sigmas2 values, or NULL = ltx_stage2_sigmas */
+    int n_sigmas2;
+    const uint16_t* video_context; /* [nb][S][caption_channels] bf16, nb = 2 ([negative, positive]) iff cfg_scale > 1 */
+    const uint16_t* audio_context; /* the same shape, or NULL: the video context (audioEncoding ?? videoEncoding) */
+    const int32_t* mask;           /* [nb][S] int32 or NULL */
+    float cfg_scale;               /* one-stage only; the two-stage path is distilled (must be <= 1 there) */
+    float guidance_rescale;        /* one-stage only */
+    const float* cond_latent1;     /* image-to-video: [1][channels][1][H][W] f32 or NULL */
+    const float* cond_latent2;     /* two_stage image-to-video: [1][channels][1][2H][2W] f32; both or neither */
+    float image_cond_noise_scale;  /* > 0 with an image latent: one frame-0 slice is drawn per step and frame 0 re-noised with it */
+    float* noise_workspace;        /* total_floats of ltx_dual_noise_plan, or NULL: the library keeps one of its own. DEVICE memory for
+                                      ltx_dual_generate_dev; for ltx_dual_generate HOST memory that receives a copy of the draws */
+    float* stage1_out;             /* two_stage only: [1][channels][F][H][W] f32 or NULL, as ltx_dual_two_stage_args.stage1_out */
+} ltx_dual_generate_args;
+#define LTX_DUAL_GENERATE_ARGS_INIT {(uint32_t)sizeof(ltx_dual_generate_args), 0, 0, 128, 0, 0, 0, 0, 0, NULL, NULL, NULL, 0, NULL, 0, NULL, NULL, NULL, 1.0f, 0.0f, NULL, NULL, 0.0f, NULL, NULL}
+
+/* One draw of a generation. The roles, in the reference's order of drawing:
+ *   LTX_NOISE_VIDEO1  draw 0, [1][channels][F][H][W], times sigmas1[0] (LTXPipeline.swift:1229, :1243 / :1576, :1597)
+ *   LTX_NOISE_AUDIO1  draw 1, [1][8][T_a][16], times sigmas1[0] (:1233-1235, :1244 / :1580-1582, :1598)
+ *   LTX_NOISE_COND1   one [1][channels][1][H][W] slice per step of the (first) loop, unscaled (:1291 / :1629)
+ *   LTX_NOISE_VIDEO2  two_stage: [1][channels][F][2H][2W], unscaled (:1730)
+ *   LTX_NOISE_AUDIO2  two_stage: the packed shape [T_a][128], unscaled (:1734)
+ *   LTX_NOISE_COND2   two_stage: one [1][channels][1][2H][2W] slice per stage-2 step, unscaled (:1766)
+ * COND1 / COND2 exist only with an image latent and image_cond_noise_scale > 0. The reference skips a step's slice when its sigma
+ * is 0 (:1290); ltx_dual_denoise refuses a sigma <= 0 before the last, so every step draws. */
+enum { LTX_NOISE_VIDEO1 = 0, LTX_NOISE_AUDIO1 = 1, LTX_NOISE_COND1 = 2, LTX_NOISE_VIDEO2 = 3, LTX_NOISE_AUDIO2 = 4, LTX_NOISE_COND2 = 5 };
+typedef struct ltx_noise_draw {
+    int draw_index;  /* which keyless draw after seeding (the argument of ltx_mlx_random_normal) */
+    int role;        /* LTX_NOISE_* */
+    int step;        /* COND1 / COND2: the step of its loop; 0 otherwise */
+    long numel;
+    long offset;     /* in floats into the noise workspace, a multiple of 64 - except that the slices of one COND role follow each
+                        other without gaps (the loops take them as one array). -1: the draw is not in the workspace, because the loop
+                        takes it in place in a latent buffer: AUDIO1 always (audio_latent), VIDEO1 without two_stage (video_latent) */
+    float scale;
+} ltx_noise_draw;
+/* The draws of ltx_dual_generate(_dev) for these arguments, in drawing order, and the floats of the workspace that holds them. Reads
+ * two_stage, channels, F, H, W, T_a, the schedules' lengths, sigmas1[0], the image latents (as flags) and image_cond_noise_scale. Returns the number of draws -
+ * the number needed when cap is too small, in which case out is not written (total_floats is) - or -LTX_ERR_INVALID_CONFIGURATION for
+ * NULL args, a short struct_size, a dimension or channels < 1, a draw of 2^31 values or more, n_sigmas1 < 2 or NULL sigmas1, n_sigmas2 < 2
+ * with sigmas2, only one of the two image latents with two_stage, cap < 0 or a NULL out with cap > 0. The VAE decoder's own noise
+ * (ltx_vae_decode's seed) is not part of the plan. Pure host code. */
+int ltx_dual_noise_plan(const ltx_dual_generate_args* args, ltx_noise_draw* out, int cap, long* total_floats);
+/* Replaces generateVideoWithAudio (LTXPipeline.swift:1222-1417) and generateVideoWithAudioTwoStage (:1570-1817) from the noise to the
+ * final latents: builds the plan, fills every draw in ONE ltx_op_mlx_normal_group launch - VIDEO1 and AUDIO1 straight into the latent
+ * buffers where the loop takes them in place - and runs ltx_dual_denoise_dev or ltx_dual_two_stage_dev on pointers into the workspace.
+ * It adds no numerics of its own: the result is that loop's on those draws, bit for bit. The refusals of the plan and of the loop it
+ * wraps, channels != the model's in_channels, and cfg_scale > 1 or guidance_rescale > 0 with two_stage: all before the first launch, so
+ * a refused call leaves the outputs and the workspace untouched. DEVICE pointers except the sigmas; asynchronous on the context stream.
+ * The decode legs follow through ltx_vae_decode and ltx_audio_decode. Sharding of the joint loop is not implemented. */
+int ltx_dual_generate_dev(ltx_ctx* ctx, const ltx_dual_generate_args* args, ltx_progress_cb cb, void* user);
+/* The same with HOST pointers throughout (noise_workspace: see the struct); synchronous. */
+int ltx_dual_generate(ltx_ctx* ctx, const ltx_dual_generate_args* args, ltx_progress_cb cb, void* user);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Multi-GPU: one process per GPU, one ltx_ctx per process, RCCL over xGMI called by the library itself (librccl is loaded
@@ -1138,6 +1243,13 @@ int ltx_text_encode_dev(ltx_ctx* ctx, const int32_t* token_ids, const int32_t* a
 /* HOST-pointer variant of ltx_text_encode_dev: only the ids, the mask and the context cross the bus; the hidden states (385 MB per
  * batch element at 49 x 1024 x 3840) stay on the device. Ids outside [0, vocab) are invalidConfiguration. out_mask may be NULL. */
 int ltx_text_encode(ltx_ctx* ctx, const int32_t* token_ids, const int32_t* attention_mask, int B, int T, uint16_t* context, int32_t* out_mask);
+/* The same two wrappers over ltx_connector_encode_av_dev: token ids -> the video context, the audio context and the mask
+ * (LTXTextEncoder.swift:705-713). No audio set: LTX_ERR_MODEL_NOT_LOADED before the encoder runs. DEVICE pointers. */
+int ltx_text_av_encode_dev(ltx_ctx* ctx, const int32_t* token_ids, const int32_t* attention_mask, int B, int T, uint16_t* video_context,
+                           uint16_t* audio_context, int32_t* out_mask);
+/* HOST-pointer variant. */
+int ltx_text_av_encode(ltx_ctx* ctx, const int32_t* token_ids, const int32_t* attention_mask, int B, int T, uint16_t* video_context,
+                       uint16_t* audio_context, int32_t* out_mask);
 /* Test seams of the encoder's kernels (DEVICE pointers).
  * ltx_op_attention_causal: causal grouped-query attention over left-padded keys. Q / O [B][T][Hq*head_dim], K [B][T][Hkv*head_dim],
  * Vt [B][Hkv*head_dim][ldvt] bf16, key_start int32 [B] or NULL; query i attends keys key_start[b] <= j <= i, rows i < key_start[b] of O

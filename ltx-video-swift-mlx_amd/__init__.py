@@ -17,7 +17,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import (ALLGATHER_FN, DIST_ID_BYTES, SHARD_CFG, SHARD_NONE, SHARD_SEQUENCE, ConnectorConfig, GemmaConfig, PROGRESS_CB, DenoiseOptions,
-                   DualBlockConfig, DualDenoiseArgs, DualForwardArgs, DualModelConfig, DualModelForwardArgs, DualRestageJob, DualStepJob, DualTwoStageArgs,
+                   DualBlockConfig, DualDenoiseArgs, DualForwardArgs, DualGenerateArgs, NoiseDraw, NoiseJob, DualModelConfig, DualModelForwardArgs, DualRestageJob, DualStepJob, DualTwoStageArgs,
                    GemmTileLaunch, GemvJob, GemvJobQ, LTXError, NormMod2Job, TransformerConfig, lib)
 
 __version__ = lib.ltx_version().decode()
@@ -154,6 +154,57 @@ def mlx_random_normal(seed, shape, draw_index=0):
     out = np.empty(shape, np.float32)
     _check(lib.ltx_mlx_random_normal(int(seed), int(draw_index), out.ctypes.data, out.size))
     return out
+
+
+def mlx_draw_key(seed, draw_index=0):
+    """``ltx_mlx_draw_key``: the two uint32 key words of the draw_index-th keyless draw after MLXRandom.seed(seed)."""
+    o = np.empty(2, np.uint32)
+    _check(lib.ltx_mlx_draw_key(int(seed), int(draw_index), o.ctypes.data_as(C.POINTER(C.c_uint32))))
+    return o
+
+
+NOISE_ROLES = ("VIDEO1", "AUDIO1", "COND1", "VIDEO2", "AUDIO2", "COND2")
+
+
+def dual_generate_args(seed, F, H, W, T_a, S, sigmas1, two_stage=False, sigmas2=None, channels=128, video_latent=None, audio_latent=None,
+                       video_context=None, audio_context=None, mask=None, cfg_scale=1.0, guidance_rescale=0.0, cond_latent1=None,
+                       cond_latent2=None, image_cond_noise_scale=0.0, noise_workspace=None, stage1_out=None, struct_size=None):
+    """A filled ``ltx_dual_generate_args``. Tensors / arrays are passed by pointer; the struct keeps them (and the sigma arrays) alive."""
+    a = DualGenerateArgs()
+    a.struct_size = C.sizeof(DualGenerateArgs) if struct_size is None else struct_size
+    a.two_stage, a.seed, a.channels = int(bool(two_stage)), int(seed), channels
+    a.F, a.H, a.W, a.T_a, a.S = F, H, W, T_a, S
+    keep = [video_latent, audio_latent, video_context, audio_context, mask, cond_latent1, cond_latent2, noise_workspace, stage1_out]
+    a.video_latent, a.audio_latent = _ptr(video_latent), _ptr(audio_latent)
+    if sigmas1 is not None:
+        sg1 = np.ascontiguousarray(sigmas1, dtype=np.float32)
+        a.sigmas1, a.n_sigmas1 = sg1.ctypes.data_as(C.POINTER(C.c_float)), len(sg1)
+        keep.append(sg1)
+    if sigmas2 is not None:
+        sg2 = np.ascontiguousarray(sigmas2, dtype=np.float32)
+        a.sigmas2, a.n_sigmas2 = sg2.ctypes.data_as(C.POINTER(C.c_float)), len(sg2)
+        keep.append(sg2)
+    a.video_context, a.audio_context, a.mask = _ptr(video_context), _ptr(audio_context), _ptr(mask)
+    a.cfg_scale, a.guidance_rescale = cfg_scale, guidance_rescale
+    a.cond_latent1, a.cond_latent2, a.image_cond_noise_scale = _ptr(cond_latent1), _ptr(cond_latent2), image_cond_noise_scale
+    a.noise_workspace, a.stage1_out = _ptr(noise_workspace), _ptr(stage1_out)
+    a._keep = keep
+    return a
+
+
+def dual_noise_plan(args, cap=None):
+    """``ltx_dual_noise_plan``: (list of dicts(draw_index, role, step, numel, offset, scale), total_floats). ``cap`` smaller than the
+    number of draws returns (count, total_floats) instead, as the C call does."""
+    total = C.c_long(0)
+    n = lib.ltx_dual_noise_plan(C.byref(args) if args is not None else None, None, 0, C.byref(total))
+    if n < 0:
+        _check(-n)
+    if cap is not None and cap < n:
+        arr = (NoiseDraw * max(cap, 1))()
+        return lib.ltx_dual_noise_plan(C.byref(args), arr, cap, C.byref(total)), total.value
+    arr = (NoiseDraw * max(n, 1))()
+    n = lib.ltx_dual_noise_plan(C.byref(args), arr, n, C.byref(total))
+    return [dict(draw_index=d.draw_index, role=d.role, step=d.step, numel=d.numel, offset=d.offset, scale=d.scale) for d in arr[:n]], total.value
 
 
 def threefry2x32(key, ctr):
@@ -768,6 +819,27 @@ class Context:
             self._ck(lib.ltx_connector_encode_dev(self._h, _ptr(hidden), _ptr(attention_mask), B, T, int(padding_right),
                                                   _ptr(context), _ptr(out_mask)))
 
+    def connector_has_audio(self):
+        """``ltx_connector_has_audio``: whether the loaded connector has the audio weight set."""
+        return bool(lib.ltx_connector_has_audio(self._h))
+
+    def connector_encode_av_dev(self, hidden, attention_mask, video_context, audio_context, out_mask=None, padding_right=False):
+        """``ltx_connector_encode_av_dev``: the feature extractor once, then the video and the audio connector. Device tensors; both
+        contexts [B,T,dim] bf16."""
+        _, B, T, _ = hidden.shape
+        self._ck(lib.ltx_connector_encode_av_dev(self._h, _ptr(hidden), _ptr(attention_mask), B, T, int(padding_right), _ptr(video_context),
+                                                 _ptr(audio_context), _ptr(out_mask)))
+
+    def connector_encode_av(self, hidden_bits, attention_mask, padding_right=False):
+        """``ltx_connector_encode_av``: HOST arrays -> (video context bits, audio context bits, mask)."""
+        h = np.ascontiguousarray(hidden_bits, dtype=np.uint16)
+        m = np.ascontiguousarray(attention_mask, dtype=np.int32)
+        _, B, T, D = h.shape
+        out, outa = np.empty((B, T, D), dtype=np.uint16), np.empty((B, T, D), dtype=np.uint16)
+        om = np.empty((B, T), dtype=np.int32)
+        self._ck(lib.ltx_connector_encode_av(self._h, _ptr(h), _ptr(m), B, T, int(padding_right), _ptr(out), _ptr(outa), _ptr(om)))
+        return out, outa, om
+
     # ---- Gemma-3 text encoder (csrc/gemma.h) ----
     def gemma_load(self, paths, cfg=None):
         """``ltx_gemma_load``: one path or a list of safetensors shards."""
@@ -816,6 +888,22 @@ class Context:
         om = np.empty((B, T), dtype=np.int32)
         self._ck(lib.ltx_text_encode(self._h, _ptr(ids), _ptr(m), B, T, _ptr(out), _ptr(om)))
         return out, om
+
+    def text_av_encode_dev(self, token_ids, attention_mask, video_context, audio_context, out_mask=None):
+        """``ltx_text_av_encode_dev``: the encoder, then both connectors. Device tensors; contexts [B,T,dim] bf16."""
+        B, T = token_ids.shape
+        self._ck(lib.ltx_text_av_encode_dev(self._h, _ptr(token_ids), _ptr(attention_mask), B, T, _ptr(video_context), _ptr(audio_context),
+                                            _ptr(out_mask)))
+
+    def text_av_encode(self, token_ids, attention_mask, dim):
+        """``ltx_text_av_encode``: HOST arrays ids, mask [B,T] int32 -> (video context bits, audio context bits, mask)."""
+        ids = np.ascontiguousarray(token_ids, dtype=np.int32)
+        m = np.ascontiguousarray(attention_mask, dtype=np.int32)
+        B, T = ids.shape
+        out, outa = np.empty((B, T, dim), dtype=np.uint16), np.empty((B, T, dim), dtype=np.uint16)
+        om = np.empty((B, T), dtype=np.int32)
+        self._ck(lib.ltx_text_av_encode(self._h, _ptr(ids), _ptr(m), B, T, _ptr(out), _ptr(outa), _ptr(om)))
+        return out, outa, om
 
     def op_attention_causal(self, Q, K, Vt, O, scale, key_start=None, head_dim=256):
         """``ltx_op_attention_causal``: Q / O [B,T,Hq*hd], K [B,T,Hkv*hd], Vt [B,Hkv*hd,ldvt] bf16, key_start [B] int32 or None."""
@@ -1325,6 +1413,32 @@ class Context:
                                       image_cond_noise_scale, keep[4], keep[5])
         self._ck(lib.ltx_dual_two_stage(self._h, C.byref(a), cb, None))
         return (out, au, s1) if stage1_out else (out, au)
+
+    def op_mlx_normal_group(self, jobs, n_jobs=None):
+        """``ltx_op_mlx_normal_group``: each job is a dict(key= two uint32, dst= a device tensor or None, n= dst.numel(), scale=1.0,
+        raw_bits=False). One launch for up to 64 jobs."""
+        arr = (NoiseJob * max(len(jobs), 1))()
+        for o, j in zip(arr, jobs):
+            o.key[0], o.key[1] = int(j["key"][0]), int(j["key"][1])
+            dst = j.get("dst")
+            o.dst = None if dst is None else dst.data_ptr()
+            o.n = j["n"] if "n" in j else dst.numel()
+            o.scale, o.raw_bits = j.get("scale", 1.0), int(bool(j.get("raw_bits", False)))
+        self._ck(lib.ltx_op_mlx_normal_group(self._h, arr, len(jobs) if n_jobs is None else n_jobs))
+
+    def mlx_random_normal_dev(self, seed, out, draw_index=0, scale=1.0, n=None):
+        """``ltx_mlx_random_normal_dev``: ``mlx_random_normal`` into the device f32 tensor ``out``, times scale."""
+        self._ck(lib.ltx_mlx_random_normal_dev(self._h, int(seed), int(draw_index), _ptr(out), out.numel() if n is None else n, scale))
+
+    def dual_generate_dev(self, args, on_progress=None):
+        """``ltx_dual_generate_dev`` on a struct from ``dual_generate_args`` (device tensors)."""
+        cb = PROGRESS_CB(on_progress if on_progress else (lambda s, t, sig, u: None))
+        self._ck(lib.ltx_dual_generate_dev(self._h, C.byref(args) if args is not None else None, cb, None))
+
+    def dual_generate(self, args, on_progress=None):
+        """``ltx_dual_generate`` on a struct from ``dual_generate_args`` (host arrays; contexts as bf16 bit patterns)."""
+        cb = PROGRESS_CB(on_progress if on_progress else (lambda s, t, sig, u: None))
+        self._ck(lib.ltx_dual_generate(self._h, C.byref(args) if args is not None else None, cb, None))
 
     def op_gemv_group(self, jobs, M=None, n_jobs=None):
         """``ltx_op_gemv_group``: each job is a dict(a= [M][K] f32, W= [N][K] bf16, out= a 2-D f32 view whose row stride is ldo, bias=

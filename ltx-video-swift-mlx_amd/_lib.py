@@ -174,6 +174,32 @@ class DualTwoStageArgs(C.Structure):
                 ("image_cond_noise_scale", C.c_float), ("cond_noise1", C.c_void_p), ("cond_noise2", C.c_void_p)]
 
 
+class NoiseJob(C.Structure):
+    """``ltx_noise_job``: one draw of ``ltx_op_mlx_normal_group``."""
+
+    _fields_ = [("key", C.c_uint32 * 2), ("dst", C.c_void_p), ("n", C.c_long), ("scale", C.c_float), ("raw_bits", C.c_int)]
+
+
+class NoiseDraw(C.Structure):
+    """``ltx_noise_draw``: one draw of a generation's plan (``ltx_dual_noise_plan``)."""
+
+    _fields_ = [("draw_index", C.c_int), ("role", C.c_int), ("step", C.c_int), ("numel", C.c_long), ("offset", C.c_long), ("scale", C.c_float)]
+
+
+class DualGenerateArgs(C.Structure):
+    """``ltx_dual_generate_args``: generateVideoWithAudio(TwoStage) from a seed to the final latents (LTXPipeline.swift:1222-1417, :1570-1817)."""
+
+    _fields_ = [("struct_size", C.c_uint32), ("two_stage", C.c_int), ("seed", C.c_uint64), ("channels", C.c_int), ("F", C.c_int), ("H", C.c_int),
+                ("W", C.c_int), ("T_a", C.c_int), ("S", C.c_int), ("video_latent", C.c_void_p), ("audio_latent", C.c_void_p),
+                ("sigmas1", C.POINTER(C.c_float)), ("n_sigmas1", C.c_int), ("sigmas2", C.POINTER(C.c_float)), ("n_sigmas2", C.c_int),
+                ("video_context", C.c_void_p), ("audio_context", C.c_void_p), ("mask", C.c_void_p), ("cfg_scale", C.c_float),
+                ("guidance_rescale", C.c_float), ("cond_latent1", C.c_void_p), ("cond_latent2", C.c_void_p), ("image_cond_noise_scale", C.c_float),
+                ("noise_workspace", C.c_void_p), ("stage1_out", C.c_void_p)]
+
+
+NOISE_VIDEO1, NOISE_AUDIO1, NOISE_COND1, NOISE_VIDEO2, NOISE_AUDIO2, NOISE_COND2 = range(6)
+
+
 def _load():
     if not os.path.exists(SO_PATH):
         raise ImportError(
@@ -268,6 +294,17 @@ SIGNATURES = {
     "ltx_frames_to_u8": (_i, [_vp, _l, _vp]),
     "ltx_mlx_random_normal": (_i, [_u64, _i, _vp, _l]),
     "ltx_threefry2x32": (None, [_vp, _vp, _vp]),
+    "ltx_mlx_draw_key": (_i, [_u64, _i, C.POINTER(C.c_uint32)]),
+    "ltx_op_mlx_normal_group": (_i, [_vp, C.POINTER(NoiseJob), _i]),
+    "ltx_mlx_random_normal_dev": (_i, [_vp, _u64, _i, _vp, _l, _f]),
+    "ltx_dual_noise_plan": (_i, [C.POINTER(DualGenerateArgs), C.POINTER(NoiseDraw), _i, C.POINTER(_l)]),
+    "ltx_dual_generate_dev": (_i, [_vp, C.POINTER(DualGenerateArgs), PROGRESS_CB, _vp]),
+    "ltx_dual_generate": (_i, [_vp, C.POINTER(DualGenerateArgs), PROGRESS_CB, _vp]),
+    "ltx_connector_encode_av_dev": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    "ltx_connector_encode_av": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    "ltx_connector_has_audio": (_i, [_vp]),
+    "ltx_text_av_encode_dev": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),
+    "ltx_text_av_encode": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),
     "ltx_write_png": (_i, [C.c_char_p, _vp, _i, _i]),
     "ltx_upscaler_load": (_i, [_vp, C.c_char_p]),
     "ltx_upscaler_unload": (_i, [_vp]),

@@ -357,6 +357,12 @@ int ltx_mlx_random_normal(uint64_t seed, int draw_index, float* out, long n) {
     return LTX_OK;
 }
 
+int ltx_mlx_draw_key(uint64_t seed, int draw_index, uint32_t key_out[2]) {
+    if (!key_out || draw_index < 0) return LTX_ERR_INVALID_CONFIGURATION;
+    mlx_draw_key(seed, draw_index, key_out);
+    return LTX_OK;
+}
+
 void ltx_threefry2x32(const uint32_t key[2], const uint32_t ctr[2], uint32_t out[2]) { threefry2x32(key, ctr, out); }
 
 /* ---- frame and audio export ---- */

@@ -8,7 +8,9 @@
 #include "audio.h"
 #include "elementwise.h"
 #include "gemm.h"
+#include "hostmath.h"
 #include "linear_ops.h"
+#include "noise.h"
 
 namespace {
 
@@ -83,6 +85,20 @@ int ltx_op_fill_normal_bf16(ltx_ctx* ctx, uint16_t* p, long n, uint64_t seed, fl
 }
 int ltx_op_fill_normal_f32(ltx_ctx* ctx, float* p, long n, uint64_t seed, float mean, float stddev) {
     return with_ctx(ctx, [&] { launch_fill_normal_f32(p, n, seed, mean, stddev, 0, ctx->stream); });
+}
+
+// ---- MLX-compatible noise on the device (noise.h) ----
+int ltx_op_mlx_normal_group(ltx_ctx* ctx, const ltx_noise_job* jobs, int n_jobs) {
+    return with_ctx(ctx, [&] { launch_mlx_normal_group(jobs, n_jobs, ctx->stream); });
+}
+int ltx_mlx_random_normal_dev(ltx_ctx* ctx, uint64_t seed, int draw_index, float* out_dev, long n, float scale) {
+    return with_ctx(ctx, [&] {
+        LTX_REQUIRE(draw_index >= 0, "ltx_mlx_random_normal_dev: draw_index=%d", draw_index);
+        ltx_noise_job j;
+        mlx_draw_key(seed, draw_index, j.key);
+        j.dst = out_dev; j.n = n; j.scale = scale; j.raw_bits = 0;
+        launch_mlx_normal_group(&j, 1, ctx->stream);
+    });
 }
 
 // ---- GEMM ----

@@ -112,6 +112,7 @@ constexpr const char* kNoDitLora = "Model component not loaded: Transformer not 
 constexpr const char* kNoVae = "Model component not loaded: vaeDecoder";
 constexpr const char* kNoUpscaler = "Model component not loaded: spatial upscaler";
 constexpr const char* kNoConnector = "Model not loaded: text-embedding connector";
+constexpr const char* kNoAudioConnector = "Model not loaded: audio embeddings connector (the file had no audio_embeddings_connector.* tensors)";
 constexpr const char* kNoGemma = "Model not loaded: Gemma text encoder";
 constexpr const char* kNoVaeEncoder = "Model not loaded: VAE encoder failed to load";
 constexpr const char* kNoVaeStats = "Model not loaded: VAE decoder not loaded (needed for latent statistics)";

@@ -10,6 +10,7 @@
 #include "attn_module.h"
 #include "dual_block.h"
 #include "dual_denoise.h"
+#include "dual_generate.h"
 #include "dual_model.h"
 #include "dual_two_stage.h"
 #include "connector.h"
@@ -693,39 +694,69 @@ int ltx_connector_encode_taps_dev(ltx_ctx* ctx, const uint16_t* hidden, const in
     });
 }
 
+namespace {
+// ltx_connector_encode_dev and ltx_connector_encode_av_dev: `av` asks for the audio set's context too
+void connector_encode_dev_body(ltx_ctx* ctx, const uint16_t* hidden, const int32_t* attention_mask, int B, int T, int padding_right,
+                               uint16_t* context, bool av, uint16_t* audio_context, int32_t* out_mask) {
+    ConnectorModel* m = need(ctx->connector, kNoConnector);
+    if (av) {
+        need(m->audio, kNoAudioConnector);
+        LTX_REQUIRE(audio_context, "connector_encode_av: null audio context");
+    }
+    ConnectorArgs a;
+    a.hidden = hidden; a.mask = attention_mask; a.B = B; a.T = T; a.padding_right = padding_right;
+    a.out = context; a.out_audio = av ? audio_context : nullptr; a.out_mask = out_mask;
+    connector_encode(ctx, m, a);
+}
+void connector_encode_host_body(ltx_ctx* ctx, const uint16_t* hidden, const int32_t* attention_mask, int B, int T, int padding_right,
+                                uint16_t* context, bool av, uint16_t* audio_context, int32_t* out_mask) {
+    ConnectorModel* m = need(ctx->connector, kNoConnector);
+    if (av) need(m->audio, kNoAudioConnector);
+    LTX_REQUIRE(hidden && attention_mask && context && (!av || audio_context) && B >= 1 && T >= 1, "connector_encode: bad arguments");
+    const ConnectorConfig& c = m->cfg;
+    const size_t hb = (size_t)c.states * B * T * c.dim * 2, mb = (size_t)B * T * 4, ob = (size_t)B * T * c.dim * 2;
+    DevBuf &d_hidden = ctx->h2d[H2D_CONN_HIDDEN], &d_mask = ctx->h2d[H2D_CONN_MASK], &d_context = ctx->h2d[H2D_CONN_CONTEXT],
+           &d_out_mask = ctx->h2d[H2D_CONN_OUT_MASK];
+    DevBuf d_audio;  // freed on return, after the synchronisation
+    d_context.ensure(ob);
+    d_out_mask.ensure(mb);
+    if (av) d_audio.ensure(ob);
+    stage_in(ctx, d_hidden, hidden, hb);
+    stage_in(ctx, d_mask, attention_mask, mb);
+    connector_encode_dev_body(ctx, d_hidden.as<uint16_t>(), d_mask.as<int32_t>(), B, T, padding_right, d_context.as<uint16_t>(), av,
+                              d_audio.as<uint16_t>(), d_out_mask.as<int32_t>());
+    stage_out(ctx, context, d_context, ob);
+    if (av) stage_out(ctx, audio_context, d_audio, ob);
+    if (out_mask) stage_out(ctx, out_mask, d_out_mask, mb);
+    stage_sync(ctx);
+}
+}  // namespace
+
 int ltx_connector_encode_dev(ltx_ctx* ctx, const uint16_t* hidden, const int32_t* attention_mask, int B, int T,
                              int padding_right, uint16_t* context, int32_t* out_mask) {
-    return with_ctx(ctx, [&] {
-        ConnectorModel* m = need(ctx->connector, kNoConnector);
-        ConnectorArgs a;
-        a.hidden = hidden; a.mask = attention_mask; a.B = B; a.T = T; a.padding_right = padding_right;
-        a.out = context; a.out_mask = out_mask;
-        connector_encode(ctx, m, a);
-    });
+    return with_ctx(ctx, [&] { connector_encode_dev_body(ctx, hidden, attention_mask, B, T, padding_right, context, false, nullptr, out_mask); });
 }
 
 int ltx_connector_encode(ltx_ctx* ctx, const uint16_t* hidden, const int32_t* attention_mask, int B, int T,
                          int padding_right, uint16_t* context, int32_t* out_mask) {
+    return with_ctx(ctx, [&] { connector_encode_host_body(ctx, hidden, attention_mask, B, T, padding_right, context, false, nullptr, out_mask); });
+}
+
+int ltx_connector_encode_av_dev(ltx_ctx* ctx, const uint16_t* hidden, const int32_t* attention_mask, int B, int T, int padding_right,
+                                uint16_t* video_context, uint16_t* audio_context, int32_t* out_mask) {
     return with_ctx(ctx, [&] {
-        ConnectorModel* m = need(ctx->connector, kNoConnector);
-        LTX_REQUIRE(hidden && attention_mask && context && B >= 1 && T >= 1, "connector_encode: bad arguments");
-        const ConnectorConfig& c = m->cfg;
-        const size_t hb = (size_t)c.states * B * T * c.dim * 2, mb = (size_t)B * T * 4, ob = (size_t)B * T * c.dim * 2;
-        DevBuf &d_hidden = ctx->h2d[H2D_CONN_HIDDEN], &d_mask = ctx->h2d[H2D_CONN_MASK], &d_context = ctx->h2d[H2D_CONN_CONTEXT],
-               &d_out_mask = ctx->h2d[H2D_CONN_OUT_MASK];
-        d_context.ensure(ob);
-        d_out_mask.ensure(mb);
-        stage_in(ctx, d_hidden, hidden, hb);
-        stage_in(ctx, d_mask, attention_mask, mb);
-        ConnectorArgs a;
-        a.hidden = d_hidden.as<bf16_t>(); a.mask = d_mask.as<int32_t>(); a.B = B; a.T = T; a.padding_right = padding_right;
-        a.out = d_context.as<bf16_t>(); a.out_mask = d_out_mask.as<int32_t>();
-        connector_encode(ctx, m, a);
-        stage_out(ctx, context, d_context, ob);
-        if (out_mask) stage_out(ctx, out_mask, d_out_mask, mb);
-        stage_sync(ctx);
+        connector_encode_dev_body(ctx, hidden, attention_mask, B, T, padding_right, video_context, true, audio_context, out_mask);
     });
 }
+
+int ltx_connector_encode_av(ltx_ctx* ctx, const uint16_t* hidden, const int32_t* attention_mask, int B, int T, int padding_right,
+                            uint16_t* video_context, uint16_t* audio_context, int32_t* out_mask) {
+    return with_ctx(ctx, [&] {
+        connector_encode_host_body(ctx, hidden, attention_mask, B, T, padding_right, video_context, true, audio_context, out_mask);
+    });
+}
+
+int ltx_connector_has_audio(ltx_ctx* ctx) { return ctx && ctx->connector && ctx->connector->audio ? 1 : 0; }
 
 /* ---- Gemma-3 text encoder ---- */
 int ltx_gemma_load(ltx_ctx* ctx, const char* const* paths, int n_paths, const ltx_gemma_config* cfg) {
@@ -792,10 +823,12 @@ int ltx_gemma_encode(ltx_ctx* ctx, const int32_t* token_ids, const int32_t* atte
 }
 
 namespace {
-void text_encode_body(ltx_ctx* ctx, const int32_t* token_ids, const int32_t* attention_mask, int B, int T, uint16_t* context, int32_t* out_mask) {
+void text_encode_body(ltx_ctx* ctx, const int32_t* token_ids, const int32_t* attention_mask, int B, int T, uint16_t* context, bool av,
+                      uint16_t* audio_context, int32_t* out_mask) {
     GemmaModel* g = need(ctx->gemma, kNoGemma);
     ConnectorModel* m = need(ctx->connector, kNoConnector);
-    LTX_REQUIRE(B >= 1 && T >= 1 && context, "text_encode: bad arguments");
+    if (av) need(m->audio, kNoAudioConnector);
+    LTX_REQUIRE(B >= 1 && T >= 1 && context && (!av || audio_context), "text_encode: bad arguments");
     LTX_REQUIRE(m->cfg.states == g->cfg.layers + 1 && m->cfg.dim == g->cfg.hidden,
                 "text_encode: the connector takes %d states of %d, the encoder makes %d of %d", m->cfg.states, m->cfg.dim, g->cfg.layers + 1,
                 g->cfg.hidden);
@@ -805,7 +838,7 @@ void text_encode_body(ltx_ctx* ctx, const int32_t* token_ids, const int32_t* att
     gemma_encode(ctx, g, ga);
     ConnectorArgs a;
     a.hidden = ga.hidden; a.mask = attention_mask; a.B = B; a.T = T; a.padding_right = 0;
-    a.out = context; a.out_mask = out_mask;
+    a.out = context; a.out_audio = av ? audio_context : nullptr; a.out_mask = out_mask;
     connector_encode(ctx, m, a);
 }
 void check_token_ids(const GemmaModel* m, const int32_t* token_ids, long n) {
@@ -815,29 +848,49 @@ void check_token_ids(const GemmaModel* m, const int32_t* token_ids, long n) {
 }
 }  // namespace
 
+namespace {
+void text_encode_host_body(ltx_ctx* ctx, const int32_t* token_ids, const int32_t* attention_mask, int B, int T, uint16_t* context, bool av,
+                           uint16_t* audio_context, int32_t* out_mask) {
+    GemmaModel* g = need(ctx->gemma, kNoGemma);
+    ConnectorModel* m = need(ctx->connector, kNoConnector);
+    if (av) need(m->audio, kNoAudioConnector);
+    LTX_REQUIRE(token_ids && attention_mask && context && (!av || audio_context) && B >= 1 && T >= 1, "text_encode: bad arguments");
+    check_token_ids(g, token_ids, (long)B * T);
+    const size_t ib = (size_t)B * T * 4, ob = (size_t)B * T * m->cfg.dim * 2;
+    DevBuf &d_ids = ctx->h2d[H2D_IN], &d_mask = ctx->h2d[H2D_CONN_MASK], &d_context = ctx->h2d[H2D_CONN_CONTEXT],
+           &d_out_mask = ctx->h2d[H2D_CONN_OUT_MASK];
+    DevBuf d_audio;  // freed on return, after the synchronisation
+    d_context.ensure(ob);
+    d_out_mask.ensure(ib);
+    if (av) d_audio.ensure(ob);
+    stage_in(ctx, d_ids, token_ids, ib);
+    stage_in(ctx, d_mask, attention_mask, ib);
+    text_encode_body(ctx, d_ids.as<int32_t>(), d_mask.as<int32_t>(), B, T, d_context.as<uint16_t>(), av, d_audio.as<uint16_t>(),
+                     d_out_mask.as<int32_t>());
+    stage_out(ctx, context, d_context, ob);
+    if (av) stage_out(ctx, audio_context, d_audio, ob);
+    if (out_mask) stage_out(ctx, out_mask, d_out_mask, ib);
+    stage_sync(ctx);
+}
+}  // namespace
+
 int ltx_text_encode_dev(ltx_ctx* ctx, const int32_t* token_ids, const int32_t* attention_mask, int B, int T, uint16_t* context,
                         int32_t* out_mask) {
-    return with_ctx(ctx, [&] { text_encode_body(ctx, token_ids, attention_mask, B, T, context, out_mask); });
+    return with_ctx(ctx, [&] { text_encode_body(ctx, token_ids, attention_mask, B, T, context, false, nullptr, out_mask); });
 }
 
 int ltx_text_encode(ltx_ctx* ctx, const int32_t* token_ids, const int32_t* attention_mask, int B, int T, uint16_t* context, int32_t* out_mask) {
-    return with_ctx(ctx, [&] {
-        GemmaModel* g = need(ctx->gemma, kNoGemma);
-        ConnectorModel* m = need(ctx->connector, kNoConnector);
-        LTX_REQUIRE(token_ids && attention_mask && context && B >= 1 && T >= 1, "text_encode: bad arguments");
-        check_token_ids(g, token_ids, (long)B * T);
-        const size_t ib = (size_t)B * T * 4, ob = (size_t)B * T * m->cfg.dim * 2;
-        DevBuf &d_ids = ctx->h2d[H2D_IN], &d_mask = ctx->h2d[H2D_CONN_MASK], &d_context = ctx->h2d[H2D_CONN_CONTEXT],
-               &d_out_mask = ctx->h2d[H2D_CONN_OUT_MASK];
-        d_context.ensure(ob);
-        d_out_mask.ensure(ib);
-        stage_in(ctx, d_ids, token_ids, ib);
-        stage_in(ctx, d_mask, attention_mask, ib);
-        text_encode_body(ctx, d_ids.as<int32_t>(), d_mask.as<int32_t>(), B, T, d_context.as<uint16_t>(), d_out_mask.as<int32_t>());
-        stage_out(ctx, context, d_context, ob);
-        if (out_mask) stage_out(ctx, out_mask, d_out_mask, ib);
-        stage_sync(ctx);
-    });
+    return with_ctx(ctx, [&] { text_encode_host_body(ctx, token_ids, attention_mask, B, T, context, false, nullptr, out_mask); });
+}
+
+int ltx_text_av_encode_dev(ltx_ctx* ctx, const int32_t* token_ids, const int32_t* attention_mask, int B, int T, uint16_t* video_context,
+                           uint16_t* audio_context, int32_t* out_mask) {
+    return with_ctx(ctx, [&] { text_encode_body(ctx, token_ids, attention_mask, B, T, video_context, true, audio_context, out_mask); });
+}
+
+int ltx_text_av_encode(ltx_ctx* ctx, const int32_t* token_ids, const int32_t* attention_mask, int B, int T, uint16_t* video_context,
+                       uint16_t* audio_context, int32_t* out_mask) {
+    return with_ctx(ctx, [&] { text_encode_host_body(ctx, token_ids, attention_mask, B, T, video_context, true, audio_context, out_mask); });
 }
 
 /* ---- VAE encoder ---- */
@@ -1308,6 +1361,93 @@ int ltx_dual_two_stage(ltx_ctx* ctx, const ltx_dual_two_stage_args* args, ltx_pr
         stage_out(ctx, host_out, d_out, n_v2);
         stage_out(ctx, host_a, d_a, n_a);
         if (host_s1) stage_out(ctx, host_s1, d_s1, n_v1);
+        stage_sync(ctx);
+    });
+}
+
+/* ---- a generation from a seed: the draw plan, the noise launch and the loop (dual_generate.h) ---- */
+namespace {
+// the caller's struct into one with every field: what struct_size covers is copied, the rest keeps LTX_DUAL_GENERATE_ARGS_INIT
+void dual_generate_params(const ltx_dual_generate_args* args, const char* who, ltx_dual_generate_args& a) {
+    LTX_REQUIRE(args != nullptr, "%s: null arguments", who);
+    const size_t sz = args->struct_size;
+    LTX_REQUIRE(sz >= offsetof(ltx_dual_generate_args, noise_workspace) + sizeof(args->noise_workspace) && sz <= 4096,
+                "ltx_dual_generate_args.struct_size = %zu: set it to sizeof(ltx_dual_generate_args) (LTX_DUAL_GENERATE_ARGS_INIT); this library is ABI revision %d",
+                sz, LTX_ABI_VERSION);
+    const ltx_dual_generate_args init = LTX_DUAL_GENERATE_ARGS_INIT;
+    a = init;
+    memcpy(&a, args, sz < sizeof(a) ? sz : sizeof(a));
+    a.struct_size = (uint32_t)sizeof(a);
+}
+}  // namespace
+
+int ltx_dual_noise_plan(const ltx_dual_generate_args* args, ltx_noise_draw* out, int cap, long* total_floats) {
+    try {  // pure host code: no context, no device
+        ltx_dual_generate_args a;
+        dual_generate_params(args, "ltx_dual_noise_plan", a);
+        LTX_REQUIRE(cap >= 0 && (out || cap == 0), "ltx_dual_noise_plan: cap=%d, or a null array", cap);
+        const int n = dual_noise_plan(a, nullptr, 0, total_floats);
+        if (n <= cap) dual_noise_plan(a, out, cap, total_floats);  // too small: the count alone, `out` stays as it was
+        return n;
+    } catch (const LtxError& e) {
+        noctx_error() = e.msg;
+        return -e.code;
+    }
+}
+
+int ltx_dual_generate_dev(ltx_ctx* ctx, const ltx_dual_generate_args* args, ltx_progress_cb cb, void* user) {
+    return with_ctx(ctx, [&] {
+        need(ctx->dual_model, kNoDualModel);
+        ltx_dual_generate_args a;
+        dual_generate_params(args, "ltx_dual_generate_dev", a);
+        dual_generate_run(ctx, a, cb, user);
+    });
+}
+
+int ltx_dual_generate(ltx_ctx* ctx, const ltx_dual_generate_args* args, ltx_progress_cb cb, void* user) {
+    return with_ctx(ctx, [&] {
+        const DualModel* m = need(ctx->dual_model, kNoDualModel);
+        ltx_dual_generate_args a;
+        dual_generate_params(args, "ltx_dual_generate", a);
+        dual_generate_check(ctx, a);  // on the host pointers: refuse before anything is staged
+        long total = 0;
+        dual_noise_plan(a, nullptr, 0, &total);
+        const int nb = a.cfg_scale > 1.0f ? 2 : 1, up = a.two_stage ? 4 : 1;
+        const size_t n_v1 = (size_t)a.channels * a.F * a.H * a.W * 4, n_out = n_v1 * up, n_a = (size_t)128 * a.T_a * 4;
+        const size_t n_c1 = n_v1 / a.F, n_c2 = 4 * n_c1;
+        const size_t n_ctx = (size_t)nb * a.S * m->cfg.caption_channels * 2, n_mask = (size_t)nb * a.S * 4;
+        DevBuf &d_v = ctx->h2d[H2D_DENOISE_LATENT], &d_a = ctx->h2d[H2D_DUAL_AUDIO_LATENT], &d_cv = ctx->h2d[H2D_DENOISE_CONTEXT],
+               &d_ca = ctx->h2d[H2D_DUAL_AUDIO_CONTEXT], &d_mask = ctx->h2d[H2D_DENOISE_MASK];
+        DevBuf d_s1, d_c2;  // freed on return, after the synchronisation
+        float *host_v = a.video_latent, *host_a = a.audio_latent, *host_s1 = a.two_stage ? a.stage1_out : nullptr, *host_ws = a.noise_workspace;
+        d_v.ensure(n_out);
+        d_a.ensure(n_a);
+        stage_in(ctx, d_cv, a.video_context, n_ctx);
+        if (a.audio_context) stage_in(ctx, d_ca, a.audio_context, n_ctx);
+        if (a.mask) stage_in(ctx, d_mask, a.mask, n_mask);
+        a.video_latent = d_v.as<float>(); a.audio_latent = d_a.as<float>();
+        a.video_context = d_cv.as<uint16_t>();
+        a.audio_context = a.audio_context ? d_ca.as<uint16_t>() : nullptr;
+        a.mask = a.mask ? d_mask.as<int32_t>() : nullptr;
+        a.noise_workspace = nullptr;  // the library's own
+        a.stage1_out = nullptr;
+        if (host_s1) {
+            d_s1.ensure(n_v1);
+            a.stage1_out = d_s1.as<float>();
+        }
+        if (a.cond_latent1) {
+            stage_in(ctx, ctx->i2v_cond, a.cond_latent1, n_c1);
+            a.cond_latent1 = ctx->i2v_cond.as<float>();
+            if (a.two_stage) {
+                stage_in(ctx, d_c2, a.cond_latent2, n_c2);
+                a.cond_latent2 = d_c2.as<float>();
+            }
+        }
+        dual_generate_run(ctx, a, cb, user);
+        stage_out(ctx, host_v, d_v, n_out);
+        stage_out(ctx, host_a, d_a, n_a);
+        if (host_s1) stage_out(ctx, host_s1, d_s1, n_v1);
+        if (host_ws && total > 0) stage_out(ctx, host_ws, ctx->dual_noise, (size_t)total * 4);
         stage_sync(ctx);
     });
 }

@@ -26,12 +26,24 @@ struct ConnBlock {
     float* kn = nullptr;
 };
 
-struct ConnectorModel {
-    ConnectorConfig cfg;
-    ParamTable params;           // one arena
-    LinearW fe;                  // aggregate_embed [D][D*states], no bias
+// the weights of one Embeddings1DConnector: the video one, or the independently weighted audio one (LTXTextEncoder.swift:628-636)
+struct ConnStack {
     float* registers = nullptr;  // [R][D] f32 (bf16-representable)
     std::vector<ConnBlock> blocks;
+};
+// the optional second weight set (audio_embeddings_connector.*), in a table and an arena of its own so that it can be absent
+struct ConnAudioSet {
+    ParamTable params;  // the module keys of the video set ("embeddings_connector.*")
+    ConnStack stack;
+    size_t weight_bytes = 0;
+};
+
+struct ConnectorModel {
+    ConnectorConfig cfg;
+    ParamTable params;           // one arena: the feature extractor and the video set
+    LinearW fe;                  // aggregate_embed [D][D*states], no bias
+    ConnStack video;
+    ConnAudioSet* audio = nullptr;  // null: the file had no audio set (the audio stream then takes the video context)
     size_t weight_bytes = 0;
     DevBuf rope_cos, rope_sin;  // [T][D/2] f32, values rounded to bf16 (LTXTextEncoder.swift:498)
     int rope_T = 0;
@@ -41,6 +53,7 @@ struct ConnectorModel {
 ConnectorModel* connector_create(const ConnectorConfig& cfg);
 void connector_destroy(ConnectorModel* m);
 void connector_load_safetensors(ltx_ctx* ctx, ConnectorModel* m, const std::string& path);
+// the video set from `seed`, and an audio set from a seed of its own
 void connector_init_synthetic(ltx_ctx* ctx, ConnectorModel* m, uint64_t seed);
 
 struct ConnectorArgs {
@@ -49,6 +62,8 @@ struct ConnectorArgs {
     int B = 1, T = 0;
     int padding_right = 0;            // 0 = left padding (the reference's default)
     bf16_t* out = nullptr;            // device [B][T][D] bf16
+    bf16_t* out_audio = nullptr;      // device [B][T][D] bf16 or null: the audio set's context from the same feature-extractor output
+                                      // (LTXTextEncoder.swift:628-636, :705-713); no audio set loaded: modelNotLoaded before any launch
     int32_t* out_mask = nullptr;      // device [B][T] int32 (all ones) or null
     bf16_t* dbg_nc = nullptr;         // optional taps for parity tests: [B][T][D*states], [B][T][D], [B][T][D] f32
     bf16_t* dbg_fe = nullptr;

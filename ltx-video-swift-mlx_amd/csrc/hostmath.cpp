@@ -635,7 +635,7 @@ static float mlx_erfinv(float a) {  // two-branch polynomial in t = log(1 - a^2)
     return a * p;
 }
 
-void mlx_random_normal(uint64_t seed, int draw_index, long n, float* out) {
+void mlx_draw_key(uint64_t seed, int draw_index, uint32_t key_out[2]) {
     uint32_t global[2] = {uint32_t(seed >> 32), uint32_t(seed & 0xffffffffu)};
     uint32_t sub[2] = {0, 0};
     for (int d = 0; d <= draw_index; ++d) {  // KeySequence::next(): split the global key in two, keep row 0, hand out row 1
@@ -646,6 +646,13 @@ void mlx_random_normal(uint64_t seed, int draw_index, long n, float* out) {
         sub[0] = w[2];
         sub[1] = w[3];
     }
+    key_out[0] = sub[0];
+    key_out[1] = sub[1];
+}
+
+void mlx_random_normal(uint64_t seed, int draw_index, long n, float* out) {
+    uint32_t sub[2];
+    mlx_draw_key(seed, draw_index, sub);
     std::vector<uint32_t> bits((size_t)n);
     mlx_random_bits(sub, n, bits.data());
     const float lo = std::nextafter(-1.0f, 0.0f), hi = 1.0f;

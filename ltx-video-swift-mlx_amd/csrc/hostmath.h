@@ -87,6 +87,9 @@ void rope_tables_positions(const float* pos, int T, int dim, double theta, int m
 // Random123 known-answer vectors; the draw pipeline is NOT verified against an MLX run (none is possible here).
 void threefry2x32(const uint32_t key[2], const uint32_t ctr[2], uint32_t out[2]);
 void mlx_random_bits(const uint32_t key[2], long n_words, uint32_t* out);
+// the key of the `draw_index`-th keyless draw after MLXRandom.seed(seed): draw_index + 1 key splits. The host generator below and the
+// device generator (noise.h) share it
+void mlx_draw_key(uint64_t seed, int draw_index, uint32_t key_out[2]);
 // the `draw_index`-th keyless MLXRandom.normal(shape) call after MLXRandom.seed(seed) (0 = the first), n f32 values
 void mlx_random_normal(uint64_t seed, int draw_index, long n, float* out);
 

@@ -180,6 +180,7 @@ struct ltx_ctx {
     DevBuf i2v_cond, i2v_noise;  // staged image latent / re-noising draws of the host-pointer denoise entry
     DevBuf op_ws;  // split-K workspace of the kernel-level test hook
     DevBuf dual_dn;  // joint video + audio loop (dual_denoise.h): token-layout latents, velocities, tokens, timesteps, statistics
+    DevBuf dual_noise;  // a generation's noise workspace when the caller gives none (dual_generate.h): the draws the loop does not take in place
     DevBuf dual_ts;  // two-stage joint path (dual_two_stage.h): the stage-1 latent in the caller's layout, the AdaIN statistics
 };
 

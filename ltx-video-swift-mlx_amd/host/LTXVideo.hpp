@@ -10,8 +10,9 @@
 //
 // Out of scope here: the tokenizer, text generation and MP4 export. Text embeddings enter through the
 // `PrecomputedEmbeddings` hook the reference already has, or come from encodePrompt on token ids (loadGemma: the Gemma-3 encoder,
-// Gemma3Model.swift); every noise tensor is an explicit input (or comes from
-// the documented splitmix64/Box-Muller generator below - NOT MLX's threefry stream, which cannot be verified here).
+// Gemma3Model.swift); every noise tensor of the video-only calls is an explicit input (or comes from
+// the documented splitmix64/Box-Muller generator below - NOT MLX's threefry stream, which cannot be verified here). The video + audio
+// calls (generateVideoWithAudio*) always draw the MLX-compatible sequence, on the device: that sequence is what defines their draw order.
 #pragma once
 #include <chrono>
 #include <cmath>
@@ -134,6 +135,17 @@ struct GenerationTimings {
     std::vector<StepDiagnostics> stepDiagnostics;  // filled when profiling
     double totalDenoise() const { double s = 0; for (double d : denoiseSteps) s += d; return s; }
 };
+// generateVideoWithAudio's result (LTXPipeline.swift:1146-1152): the frames and the waveform of one clip
+struct AudioVideoGenerationResult {
+    std::vector<float> frames;  // (numFrames, height, width, 3) float in [0,1]
+    int numFrames = 0, height = 0, width = 0;
+    std::vector<float> audioWaveform;  // [2][audioSamples] f32 in (-1, 1)
+    long audioSamples = 0;             // per channel: ltx_audio_sample_count(audio latent frames)
+    int audioSampleRate = 0;
+    int audioLatentFrames = 0;
+    uint64_t seed = 0;
+    double generationTime = 0;
+};
 struct VideoGenerationResult {
     std::vector<float> frames;  // (numFrames, height, width, 3) float in [0,1] (LTXPipeline.swift:1040-1041)
     int numFrames = 0, height = 0, width = 0;
@@ -149,6 +161,10 @@ struct PrecomputedEmbeddings {
     std::vector<uint16_t> nullEmbeddings;    // optional (CFG)
     std::vector<int32_t> nullMask;           // optional; defaults to zeros (LTXPipeline.swift:642)
     int S = 0;
+    // the audio stream's context (the audio connector's output, LTXTextEncoder.swift:628-636), same shapes; empty = the video context
+    // (audioEncoding ?? videoEncoding, LTXPipeline.swift:1173)
+    std::vector<uint16_t> audioPromptEmbeddings;
+    std::vector<uint16_t> audioNullEmbeddings;
 };
 
 // Image-to-video conditioning (generateVideo(image:...), LTXPipeline.swift:2000-2125): the VAE-encoded image latent
@@ -157,6 +173,9 @@ struct PrecomputedEmbeddings {
 struct ImageConditioning {
     std::vector<float> imageLatent;
     std::vector<float> injectionNoise;
+    // generateVideoWithAudioTwoStage: the image encoded at the stage-1 (half) resolution too, [1][128][1][H'/2][W'/2]
+    // (LTXPipeline.swift:1600-1610). The video + audio calls draw their own re-noising slices and ignore injectionNoise.
+    std::vector<float> halfResImageLatent;
 };
 
 // Deterministic N(0,1) generator used when the caller supplies a seed instead of a noise tensor.
@@ -213,18 +232,36 @@ class LTXPipeline {
         return n;
     }
     void loadUpscaler(const std::string& path) { check(ltx_upscaler_load(ctx_, path.c_str())); }
-    // loadAudioModels / decodeAudio (LTXPipeline.swift audio branch; Vocoder.swift:325-361): the audio VAE decoder + vocoder. The dual
-    // (video + audio) transformer is not part of this build, so the audio latent [8][T][16] is an input. Empty paths with
+    // The dual video + audio transformer (loadModels with includeAudio, LTXPipeline.swift:420-540; LTX2Transformer): from the unified
+    // checkpoint, quantised afterwards as LTXQuantizationConfig says (quantize(model:), :487-492). cfg nullptr = reference architecture;
+    // synthetic = true with an empty path gives a random-init model (smoke runs without weight files).
+    void loadDualModel(const std::string& path, const ltx_dual_model_config* cfg = nullptr, bool synthetic = false) {
+        ltx_dual_model_config c;
+        if (cfg) c = *cfg; else ltx_dual_model_config_default(&c);
+        if (synthetic && path.empty()) check(ltx_dual_model_init_synthetic(ctx_, &c, 4242));
+        else check(ltx_dual_model_load(ctx_, path.c_str(), &c));
+        if (quant_.transformer != TransformerQuantization::bf16) check(ltx_dual_model_quantize(ctx_, bits(quant_.transformer), quant_.groupSize));
+        dualCfg_ = c;
+        dualLoaded_ = true;
+    }
+    void loadVAE(const std::string& vaeWeightsPath) {
+        check(ltx_vae_load(ctx_, vaeWeightsPath.c_str(), nullptr));
+        vaeLoaded_ = true;
+    }
+    // loadAudioModels / decodeAudio (LTXPipeline.swift audio branch; Vocoder.swift:325-361): the audio VAE decoder + vocoder; the audio
+    // latent [8][T][16] comes from generateVideoWithAudio* or is an input. Empty paths with
     // synthetic = true give random-init models of the reference architecture (smoke runs without weight files).
     void loadAudioModels(const std::string& audioVAEPath, const std::string& vocoderPath, bool synthetic = false) {
         if (synthetic && audioVAEPath.empty()) check(ltx_audio_vae_init_synthetic(ctx_, 0, 55));
         else check(ltx_audio_vae_load(ctx_, audioVAEPath.c_str()));
         if (synthetic && vocoderPath.empty()) check(ltx_vocoder_init_synthetic(ctx_, 0, 56));
         else check(ltx_vocoder_load(ctx_, vocoderPath.c_str()));
+        audioLoaded_ = true;
     }
     void unloadAudioModels() {
         check(ltx_audio_vae_unload(ctx_));
         check(ltx_vocoder_unload(ctx_));
+        audioLoaded_ = false;
     }
     // -> waveform [2][ltx_audio_sample_count(T)] f32 at ltx_audio_sample_rate() Hz
     std::vector<float> decodeAudio(const std::vector<float>& latents, int T) {
@@ -266,15 +303,29 @@ class LTXPipeline {
         e.S = T;
         e.promptEmbeddings.resize(size_t(T) * connCfg_.dim);
         e.promptMask.resize(T);
-        check(ltx_connector_encode(ctx_, hiddenStates.data(), attentionMask.data(), 1, T, paddingRight ? 1 : 0, e.promptEmbeddings.data(),
-                                   e.promptMask.data()));
+        // with an audio weight set in the file, the audio stream's context comes from the same feature-extractor output (:628-636)
+        const bool av = ltx_connector_has_audio(ctx_) == 1;
+        if (av) {
+            e.audioPromptEmbeddings.resize(size_t(T) * connCfg_.dim);
+            check(ltx_connector_encode_av(ctx_, hiddenStates.data(), attentionMask.data(), 1, T, paddingRight ? 1 : 0, e.promptEmbeddings.data(),
+                                          e.audioPromptEmbeddings.data(), e.promptMask.data()));
+        } else {
+            check(ltx_connector_encode(ctx_, hiddenStates.data(), attentionMask.data(), 1, T, paddingRight ? 1 : 0, e.promptEmbeddings.data(),
+                                       e.promptMask.data()));
+        }
         if (nullHiddenStates && nullAttentionMask) {
             if (nullHiddenStates->size() != need || nullAttentionMask->size() != size_t(T))
                 throw LTXError(LTXError::textEncodingFailed, "null-prompt hidden states must match the prompt's shape");
             e.nullEmbeddings.resize(size_t(T) * connCfg_.dim);
             e.nullMask.resize(T);
-            check(ltx_connector_encode(ctx_, nullHiddenStates->data(), nullAttentionMask->data(), 1, T, paddingRight ? 1 : 0,
-                                       e.nullEmbeddings.data(), e.nullMask.data()));
+            if (av) {
+                e.audioNullEmbeddings.resize(size_t(T) * connCfg_.dim);
+                check(ltx_connector_encode_av(ctx_, nullHiddenStates->data(), nullAttentionMask->data(), 1, T, paddingRight ? 1 : 0,
+                                              e.nullEmbeddings.data(), e.audioNullEmbeddings.data(), e.nullMask.data()));
+            } else {
+                check(ltx_connector_encode(ctx_, nullHiddenStates->data(), nullAttentionMask->data(), 1, T, paddingRight ? 1 : 0,
+                                           e.nullEmbeddings.data(), e.nullMask.data()));
+            }
         }
         return e;
     }
@@ -312,8 +363,15 @@ class LTXPipeline {
         // one call: only ids, mask and context cross the bus, the hidden states stay on the device
         std::vector<uint16_t> context(size_t(B) * T * connCfg_.dim);
         std::vector<int32_t> outMask(size_t(B) * T);
-        check(ltx_text_encode(ctx_, ids.data(), mask.data(), B, int(T), context.data(), outMask.data()));
+        const bool av = ltx_connector_has_audio(ctx_) == 1;  // the audio connector on the same hidden states (LTXTextEncoder.swift:705-713)
+        std::vector<uint16_t> audioContext(av ? context.size() : 0);
+        if (av) check(ltx_text_av_encode(ctx_, ids.data(), mask.data(), B, int(T), context.data(), audioContext.data(), outMask.data()));
+        else check(ltx_text_encode(ctx_, ids.data(), mask.data(), B, int(T), context.data(), outMask.data()));
         PrecomputedEmbeddings e;
+        if (av) {
+            e.audioPromptEmbeddings.assign(audioContext.begin(), audioContext.begin() + T * connCfg_.dim);
+            if (two) e.audioNullEmbeddings.assign(audioContext.begin() + T * connCfg_.dim, audioContext.end());
+        }
         e.S = int(T);
         e.promptEmbeddings.assign(context.begin(), context.begin() + T * connCfg_.dim);
         e.promptMask.assign(outMask.begin(), outMask.begin() + T);
@@ -442,9 +500,93 @@ class LTXPipeline {
         return r;
     }
 
+    // generateVideoWithAudio (LTXPipeline.swift:1146-1478): one joint denoise loop for both streams, then both decode legs. Noise is the
+    // reference's own sequence for config.seed, drawn on the device (ltx_dual_generate); `image` (imageLatent alone) makes it
+    // image-to-video, re-noised per step when config.imageCondNoiseScale > 0. vaeNoise as generateVideo takes it.
+    AudioVideoGenerationResult generateVideoWithAudio(const LTXVideoGenerationConfig& config, const PrecomputedEmbeddings& emb,
+                                                      GenerationProgressCallback onProgress = nullptr, const ImageConditioning* image = nullptr,
+                                                      const std::vector<float>& vaeNoise = {}, float fps = 24.0f) {
+        return generateAV(config, emb, onProgress, image, vaeNoise, fps, false);
+    }
+    // generateVideoWithAudioTwoStage (LTXPipeline.swift:1480-1878): stage 1 at half resolution, the latent upscaler, AdaIN and the
+    // re-noise, stage 2 at full resolution - distilled (no CFG). loadUpscaler first; image-to-video needs both image latents.
+    AudioVideoGenerationResult generateVideoWithAudioTwoStage(const LTXVideoGenerationConfig& config, const PrecomputedEmbeddings& emb,
+                                                              GenerationProgressCallback onProgress = nullptr, const ImageConditioning* image = nullptr,
+                                                              const std::vector<float>& vaeNoise = {}, float fps = 24.0f) {
+        return generateAV(config, emb, onProgress, image, vaeNoise, fps, true);
+    }
+
     ltx_ctx* context() { return ctx_; }
 
    private:
+    AudioVideoGenerationResult generateAV(const LTXVideoGenerationConfig& config, const PrecomputedEmbeddings& emb, GenerationProgressCallback onProgress,
+                                          const ImageConditioning* image, const std::vector<float>& vaeNoise, float fps, bool twoStage) {
+        LTXVideoGenerationConfig cfg = config;
+        cfg.twoStage = twoStage;
+        cfg.validate();
+        if (!dualLoaded_ || !vaeLoaded_) throw LTXError(LTXError::modelNotLoaded, "Models not loaded. Call loadDualModel() and loadVAE() first.");
+        if (!audioLoaded_) throw LTXError(LTXError::modelNotLoaded, "Audio models not loaded. Call loadAudioModels() first.");
+        const auto t0 = std::chrono::steady_clock::now();
+        const bool useCFG = cfg.cfgScale > 1.0f;
+        int F, H, W;  // the latent shape of the only stage, or of stage 1
+        ltx_latent_shape(twoStage ? cfg.width / 2 : cfg.width, twoStage ? cfg.height / 2 : cfg.height, cfg.numFrames, &F, &H, &W);
+        const int up = twoStage ? 2 : 1, C = dualCfg_.in_channels;
+        const int Ta = ltx_audio_latent_frames(cfg.numFrames, fps);  // computeAudioLatentFrames (:530-534)
+        if (image) {
+            const size_t full = size_t(C) * (up * H) * (up * W), half = size_t(C) * H * W;
+            if (image->imageLatent.size() != full) throw LTXError(LTXError::invalidConfiguration, "image latent must be [1][C][1][H/32][W/32]");
+            if (twoStage && image->halfResImageLatent.size() != half)
+                throw LTXError(LTXError::invalidConfiguration, "two-stage image-to-video needs the image latent at half resolution too");
+        }
+        float sig[128];
+        const int steps = twoStage ? 8 : cfg.numSteps;  // stage 1 runs the distilled table (:1587-1593)
+        const int ns = ltx_sigmas(twoStage || isDistilled(model_) ? 1 : 0, steps, F * H * W, sig, 128);
+        if (steps > ns - 1) throw LTXError(LTXError::invalidConfiguration, "numSteps exceeds the sigma schedule");
+        std::vector<uint16_t> ctxV, ctxA;
+        std::vector<int32_t> mask, maskA;
+        buildContext(emb, useCFG, ctxV, mask);
+        if (!emb.audioPromptEmbeddings.empty()) {  // audioEncoding ?? videoEncoding (:1173)
+            PrecomputedEmbeddings a = emb;
+            a.promptEmbeddings = emb.audioPromptEmbeddings;
+            a.nullEmbeddings = emb.audioNullEmbeddings;
+            if (a.promptEmbeddings.size() != emb.promptEmbeddings.size())
+                throw LTXError(LTXError::textEncodingFailed, "the audio context must have the video context's shape");
+            buildContext(a, useCFG, ctxA, maskA);
+        }
+        std::vector<float> video(size_t(C) * F * (up * H) * (up * W)), audio(size_t(8) * Ta * 16);
+        ltx_dual_generate_args g = LTX_DUAL_GENERATE_ARGS_INIT;
+        g.two_stage = twoStage ? 1 : 0;
+        g.seed = cfg.seed.value_or(0);
+        g.channels = C;
+        g.F = F; g.H = H; g.W = W; g.T_a = Ta; g.S = emb.S;
+        g.video_latent = video.data(); g.audio_latent = audio.data();
+        g.sigmas1 = sig; g.n_sigmas1 = steps + 1;
+        g.video_context = ctxV.data(); g.audio_context = ctxA.empty() ? nullptr : ctxA.data(); g.mask = mask.data();
+        g.cfg_scale = cfg.cfgScale; g.guidance_rescale = cfg.guidanceRescale;
+        if (image) {
+            g.cond_latent1 = twoStage ? image->halfResImageLatent.data() : image->imageLatent.data();
+            g.cond_latent2 = twoStage ? image->imageLatent.data() : nullptr;
+            g.image_cond_noise_scale = cfg.imageCondNoiseScale;
+        }
+        struct Box { GenerationProgressCallback cb; } box{onProgress};
+        auto thunk = [](int step, int total, float sigma, void* user) {
+            Box* b = static_cast<Box*>(user);
+            if (b->cb) b->cb(GenerationProgress{step, total, sigma});
+        };
+        check(ltx_dual_generate(ctx_, &g, thunk, &box));
+        GenerationTimings timings;
+        VideoGenerationResult v = decode(video, F, up * H, up * W, cfg, vaeNoise, timings);  // trims to numFrames (:1436-1442)
+        AudioVideoGenerationResult r;
+        r.frames = std::move(v.frames);
+        r.numFrames = v.numFrames; r.height = v.height; r.width = v.width;
+        r.audioWaveform = decodeAudio(audio, Ta);  // unpack -> audio VAE -> vocoder (:1444-1460)
+        r.audioLatentFrames = Ta;
+        r.audioSamples = ltx_audio_sample_count(Ta);
+        r.audioSampleRate = ltx_audio_sample_rate();
+        r.seed = cfg.seed.value_or(0);
+        r.generationTime = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        return r;
+    }
     void check(int rc) {
         if (rc != 0) throw LTXError(LTXError::Case(rc), ltx_last_error(ctx_));
     }
@@ -489,7 +631,8 @@ class LTXPipeline {
     LTXModel model_;
     LTXQuantizationConfig quant_;
     MemoryOptimizationConfig mem_;
-    bool ditLoaded_ = false, vaeLoaded_ = false, connectorLoaded_ = false, gemmaLoaded_ = false;
+    bool ditLoaded_ = false, vaeLoaded_ = false, connectorLoaded_ = false, gemmaLoaded_ = false, dualLoaded_ = false, audioLoaded_ = false;
+    ltx_dual_model_config dualCfg_{};
     ltx_connector_config connCfg_{};
     ltx_gemma_config gemmaCfg_{};
 };

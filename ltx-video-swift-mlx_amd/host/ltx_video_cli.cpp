@@ -1,8 +1,9 @@
 // ltx_video_cli.cpp - `ltx-video` command line, same subcommands / flags / defaults / validation messages as the
 // reference CLI (Sources/LTXVideoCLI/LTXVideoCLI.swift:21-449), on top of host/LTXVideo.hpp -> libltxhip.so.
 //
-// Differences forced by scope: the tokenizer, prompt enhancement, audio, I2V, downloads and MP4
-// export are not part of this path. Text conditioning comes from `--gemma-weights <shards> --token-ids <file.safetensors>` (keys
+// Differences forced by scope: the tokenizer, prompt enhancement, image file decoding, downloads and MP4
+// export are not part of this path. `--audio` runs the dual video + audio model (generateVideoWithAudio / ...TwoStage) and writes a WAV
+// next to the frames. Text conditioning comes from `--gemma-weights <shards> --token-ids <file.safetensors>` (keys
 // input_ids [1,T], optional attention_mask; the Gemma-3 encoder and the connector run here), from `--gemma-hidden-states`, or from
 // `--embeddings <file.safetensors>` (keys
 // prompt_embeddings [1,S,3840], prompt_mask [1,S], optional negative_embeddings / negative_mask) - the CLI-level
@@ -40,6 +41,8 @@ struct Args {
     // additions of this build
     std::string embeddings, vaeWeights, upscalerWeights, distilledLoraPath, pngDir, hiddenStates, connectorWeights, imageTensor;
     std::string gemmaWeights, tokenIds, negativeTokenIds;  // the Gemma-3 text encoder: safetensors shards (comma-separated) + tokenised prompts
+    std::string audioVaeWeights, vocoderWeights;           // --audio: the audio decode leg
+    int audioHeads = 0;                                    // --audio: reduced dual architecture (0 = reference default)
     std::string noiseRng = "native";
     int vaeTile = 0, vaeOverlap = 1;
     int numLayers = 0, numHeads = 0, captionChannels = 0;  // reduced architectures for tests (0 = reference default)
@@ -58,6 +61,7 @@ struct Args {
                  "  [--vae-tile N] [--vae-overlap N] [--png-dir dir] [--gemma-hidden-states file] [--connector-weights file]\n"
                  "  [--gemma-weights file[,file...] --token-ids file [--negative-token-ids file]]\n"
                  "  [--image-tensor file] [--noise-rng native|mlx] [--hip-option name=value]...\n"
+                 "  [--audio --audio-vae-weights file --vocoder-weights file [--audio-gain 1.0] [--audio-heads N]]  (--ltx-weights: the dual checkpoint)\n"
                  "decode-audio  Audio latent -> 24 kHz stereo WAV (audio VAE decoder + vocoder)\n"
                  "  (--latent file.safetensors [key audio_latent, (8,T,16)] | --synthetic [--frames 121]) [--audio-vae-weights file]\n"
                  "  [--vocoder-weights file] [--audio-gain 1.0] [-o out.wav]\n"
@@ -128,6 +132,9 @@ Args parse_generate(int argc, char** argv, int start) {
         else if (k == "--num-layers") a.numLayers = std::stoi(need(i));
         else if (k == "--num-heads") a.numHeads = std::stoi(need(i));
         else if (k == "--caption-channels") a.captionChannels = std::stoi(need(i));
+        else if (k == "--audio-vae-weights") a.audioVaeWeights = need(i);
+        else if (k == "--vocoder-weights") a.vocoderWeights = need(i);
+        else if (k == "--audio-heads") a.audioHeads = std::stoi(need(i));
         else if (k == "--help") usage(0);
         else if (!k.empty() && k[0] == '-') throw ValidationError("Unknown option '" + k + "'");
         else if (!have_prompt) { a.prompt = k; have_prompt = true; }
@@ -205,6 +212,7 @@ int run_generate(const Args& a) {
     if (a.distilledLora) std::cout << "Distilled LoRA: enabled\n";
     if (a.seed) std::cout << "Seed: " << *a.seed << "\n";
     if (a.twoStage) std::cout << "Two-stage: enabled\n";
+    if (a.audio) std::cout << "Audio: enabled\n";
     if (a.transformerQuant != "bf16") std::cout << "Transformer quantization: " << a.transformerQuant << "\n";
     std::cout << "\n";
     // validation order and messages of LTXVideoCLI.swift:168-202
@@ -237,9 +245,16 @@ int run_generate(const Args& a) {
         std::cout << "Validation passed (dry run mode)\n";
         return 0;
     }
-    if (!a.image.empty() || a.audio || a.enhancePrompt)
-        throw ValidationError("--image (file decoding) / --audio / --enhance-prompt are outside the MI355X hot path of this build; "
+    if (!a.image.empty() || a.enhancePrompt)
+        throw ValidationError("--image (file decoding) / --enhance-prompt are outside the MI355X hot path of this build; "
                               "pass the image as a float tensor with --image-tensor");
+    if (a.audio) {
+        if (a.audioVaeWeights.empty() || a.vocoderWeights.empty())
+            throw ValidationError("--audio needs --audio-vae-weights and --vocoder-weights (the audio VAE decoder and the vocoder), next to "
+                                  "--ltx-weights (the dual video+audio checkpoint) and --vae-weights");
+        if (a.twoStage && a.upscalerWeights.empty()) throw ValidationError("--audio --two-stage needs --upscaler-weights");
+        if (a.distilledLora || !a.lora.empty()) throw ValidationError("--lora / --distilled-lora are not available with --audio");
+    }
     if (a.ltxWeights.empty() || a.vaeWeights.empty() || (a.embeddings.empty() && a.hiddenStates.empty() && a.gemmaWeights.empty()))
         throw ValidationError("this build needs --ltx-weights, --vae-weights and --embeddings or --gemma-hidden-states, or --gemma-weights with "
                               "--token-ids (no downloads, no tokenizer)");
@@ -255,7 +270,21 @@ int run_generate(const Args& a) {
     if (a.numLayers) tc.num_layers = a.numLayers;
     if (a.numHeads) { tc.num_attention_heads = a.numHeads; tc.cross_attention_dim = a.numHeads * 128; }
     if (a.captionChannels) tc.caption_channels = a.captionChannels;
-    pipeline.loadModels(a.ltxWeights, a.vaeWeights, &tc);
+    if (a.audio) {
+        // the dual video + audio transformer from the same checkpoint (loadModels with includeAudio), the video VAE and the audio decode leg
+        ltx_dual_model_config dc;
+        ltx_dual_model_config_default(&dc);
+        if (a.numLayers) dc.blocks.num_layers = a.numLayers;
+        if (a.numHeads) { dc.blocks.video_heads = a.numHeads; dc.blocks.video_dim = dc.blocks.video_context_dim = a.numHeads * 128; }
+        if (a.audioHeads) { dc.blocks.audio_heads = a.audioHeads; dc.blocks.audio_dim = dc.blocks.audio_context_dim = a.audioHeads * 64; }
+        if (a.captionChannels) dc.caption_channels = a.captionChannels;
+        pipeline.loadDualModel(a.ltxWeights, &dc);
+        pipeline.loadVAE(a.vaeWeights);
+        pipeline.loadAudioModels(a.audioVaeWeights, a.vocoderWeights);
+        if (a.twoStage) pipeline.loadUpscaler(a.upscalerWeights);
+    } else {
+        pipeline.loadModels(a.ltxWeights, a.vaeWeights, &tc);
+    }
     std::cout << "Models loaded\n";
     if (a.distilledLora) {
         if (a.distilledLoraPath.empty()) throw ValidationError("--distilled-lora needs --distilled-lora-path (no downloads on this path)");
@@ -313,9 +342,26 @@ int run_generate(const Args& a) {
         ltx_st_read(a.imageTensor.c_str(), "pixels", 0, px.data(), long(px.size()));
         pipeline.loadVAEEncoder(a.vaeWeights);
         image = pipeline.encodeImage(px, a.width, a.height);
+        if (a.audio && a.twoStage) {
+            // stage 1 takes the image at half resolution (LTXPipeline.swift:1600-1610): "pixels_half" [1][3][1][H/2][W/2] when the file
+            // has it (the caller's resize), else the 2 x 2 box average of `pixels`
+            const int h2 = a.height / 2, w2 = a.width / 2;
+            std::vector<float> half(size_t(3) * h2 * w2);
+            if (ltx_st_info(a.imageTensor.c_str(), "pixels_half", shp) == 5 && shp[3] == h2 && shp[4] == w2) {
+                ltx_st_read(a.imageTensor.c_str(), "pixels_half", 0, half.data(), long(half.size()));
+            } else {
+                for (int c = 0; c < 3; ++c)
+                    for (int y = 0; y < h2; ++y)
+                        for (int x = 0; x < w2; ++x) {
+                            const float* q = px.data() + (size_t(c) * a.height + 2 * y) * a.width + 2 * x;
+                            half[(size_t(c) * h2 + y) * w2 + x] = 0.25f * (q[0] + q[1] + q[a.width] + q[a.width + 1]);
+                        }
+            }
+            image->halfResImageLatent = pipeline.encodeImage(half, w2, h2).imageLatent;
+        }
         pipeline.unloadVAEEncoder();
         cfg.imageCondNoiseScale = a.imageCondNoise;
-        if (a.imageCondNoise > 0) {  // one N(0,1) draw of the image latent's shape per step (LTXPipeline.swift:2226)
+        if (a.imageCondNoise > 0 && !a.audio) {  // one N(0,1) draw of the image latent's shape per step (LTXPipeline.swift:2226)
             int Fl, Hl, Wl;
             ltx_latent_shape(a.width, a.height, a.frames, &Fl, &Hl, &Wl);
             image->injectionNoise = generateNoise(size_t(cfg.numSteps) * 128 * Hl * Wl, a.seed.value_or(0) ^ 0x9e3779b9u);
@@ -326,7 +372,19 @@ int run_generate(const Args& a) {
         std::cout << "  Step " << p.currentStep + 1 << "/" << p.totalSteps << " (sigma=" << p.sigma << ")\n";
     };
     VideoGenerationResult r;
-    if (a.twoStage) {
+    if (a.audio) {
+        // with --audio the noise is always the MLX-compatible sequence of the seed, drawn on the device: the reference's order of drawing
+        // is what defines which draw feeds which tensor, and the native generator has none
+        AudioVideoGenerationResult av = a.twoStage ? pipeline.generateVideoWithAudioTwoStage(cfg, emb, progress, image ? &*image : nullptr)
+                                                   : pipeline.generateVideoWithAudio(cfg, emb, progress, image ? &*image : nullptr);
+        const std::string wav = a.output + ".wav";
+        if (ltx_write_wav(wav.c_str(), av.audioWaveform.data(), av.audioSamples, av.audioSampleRate, a.audioGain) != 0)
+            throw LTXError(LTXError::fileNotFound, "cannot write " + wav);
+        std::cout << "Audio: " << av.audioLatentFrames << " latent frames -> " << av.audioSamples << " samples/channel at " << av.audioSampleRate
+                  << " Hz -> " << wav << "\n";
+        r.frames = std::move(av.frames);
+        r.numFrames = av.numFrames; r.height = av.height; r.width = av.width; r.seed = av.seed; r.generationTime = av.generationTime;
+    } else if (a.twoStage) {
         if (a.upscalerWeights.empty()) throw ValidationError("--two-stage needs --upscaler-weights");
         pipeline.loadUpscaler(a.upscalerWeights);
         int F1, H1, W1, F2, H2, W2;
