@@ -5,7 +5,7 @@
 //   gemm_bf16_kernel_qkv   192 x 384 tile: q|k and V in one launch  tools/gen_gemm_asm_qkv.py
 //   gemm_bf16_kernel_tall  384 x 256 tile (tile_cfg 76)            tools/gen_gemm_asm_tall.py
 //
-// What they share (written once below, and once in tools/gemm_asm_common.py for the streams and their static RAW / WAR proof):
+// What they share (written once below, and once in tools/asm_common.py for the streams and their static RAW / WAR proof):
 //   * dense A . B^T on whole tiles, K % 64 == 0; four waves as 2 x 2 = ONE wave per SIMD, accumulators of v_mfma_f32_16x16x32_bf16;
 //   * the LDS image of every GEMM kernel here (128-byte rows, 16-byte chunks XOR-swizzled by (row >> 1) & 7 on the LDS-DMA source
 //     address), two activation slots followed by the weight slots. LDS-DMA piece i of wave w is rows (w + 4 i) * 8 .. + 7 of a tile:

@@ -1,8 +1,10 @@
-"""What tools/gen_gemm_asm_dtl.py (192 x 256), gen_gemm_asm_qkv.py (192 x 384) and gen_gemm_asm_tall.py (384 x 256) share: the pieces of
-a stream every one of them emits, the static proof of its LDS-DMA / ds_read ordering, and the way a generated file is written or compared
-with the committed one. The three scripts stay the entry points; each keeps its schedule, its register map and the proofs only it has.
+"""What the five generators of proven gfx950 assembly share - tools/gen_attn_w48.py and gen_attn_x32.py (attention), gen_gemm_asm_dtl.py
+(192 x 256), gen_gemm_asm_qkv.py (192 x 384) and gen_gemm_asm_tall.py (384 x 256): the static proof of a stream's LDS ordering and
+register use, for which a generator only declares its LDS layout; the way a generated file is written or compared with the committed
+one; and the pieces of a stream the three GEMM generators emit. The scripts stay the entry points; each keeps its schedule, its register
+map and the proofs only it has.
 
-The streams have one format. LDS holds A_SLOTS activation slots followed by B_SLOTS weight slots. A wave stages a K-tile with LDS-DMA
+The GEMM streams have one format. LDS holds A_SLOTS activation slots followed by B_SLOTS weight slots. A wave stages a K-tile with LDS-DMA
 pieces (`s_add_u32 m0, %[wlds], <byte offset>` / `buffer_load_dwordx4 ... offen lds`) and reads fragments with
 `ds_read_b128 v[..], <address> offset:<fragment * 2048>`, where the address operand of slot 0 is `%[fa<k-step>]` / `%[fb<k-step>]` and
 those of the other slots are VGPR copies from v<S1> on. The loop lies between `10:` and `s_branch 10b` and is left through
@@ -195,26 +197,46 @@ class WaitCoverageError(AssertionError):
     pass
 
 
-Slots = collections.namedtuple("Slots", "a_slots a_bytes b_slots b_bytes read_slot")
+# What a generator declares about its LDS: fill(byte offset in m0 of an LDS-DMA) -> region; read(address operand, offset of an LDS
+# read) -> region, EXCHANGE or None (the checker then raises). A region is any hashable name of a part of the ring. ONCE is the region
+# staged in the prologue and never refilled (the bias vector of the masked attention stream), EXCHANGE the area an epilogue writes
+# with ds_write and reads back.
+Layout = collections.namedtuple("Layout", "fill read")
+ONCE, EXCHANGE = "staged once", "exchange"
 
 
 def read_slot_from(s1):
     """address operand of a ds_read -> (kind, slot, k-step), for fragment addresses of slot 0 in %[fa0] %[fa1] %[fb0] %[fb1] and those of
-    the other slots in v<s1>, v<s1 + 1> (A slot 1) and v<s1 + 2 slot>, v<s1 + 2 slot + 1> (B)"""
+    the other slots in v<s1>, v<s1 + 1> (A slot 1) and v<s1 + 2 slot>, v<s1 + 2 slot + 1> (B); None for any other operand"""
     def read_slot(a):
         if a.startswith("%[fa"):
             return "A", 0, int(a[4])
         if a.startswith("%[fb"):
             return "B", 0, int(a[4])
-        r = int(a[1:]) - s1
+        r = int(a[1:]) - s1 if re.fullmatch(r"v\d+", a) else -1
+        if r < 0:
+            return None
         return ("A", 1, r) if r < 2 else ("B", r // 2, r % 2)
     return read_slot
 
 
-def walk(lines, iterations, with_exit=True):
-    """prologue + iterations x loop body (+ exit), branches not taken"""
-    i10, ibr = lines.index("10:"), lines.index("s_branch 10b")
-    return lines[:i10] + lines[i10 + 1:ibr] * iterations + (lines[ibr + 1:] if with_exit else [])
+def slot_layout(a_slots, a_bytes, b_bytes, s1):
+    """the GEMM streams: a_slots activation slots of a_bytes, then the weight slots of b_bytes; regions (kind, slot)"""
+    read_slot, b_base = read_slot_from(s1), a_slots * a_bytes
+
+    def read(addr, off):
+        slot = read_slot(addr)
+        return slot and slot[:2]
+    return Layout(lambda m0: ("A", m0 // a_bytes) if m0 < b_base else ("B", (m0 - b_base) // b_bytes), read)
+
+
+def walk(lines, iterations):
+    """prologue + iterations x loop body + exit, branches not taken"""
+    try:
+        i10, ibr = lines.index("10:"), lines.index("s_branch 10b")
+    except ValueError as ex:
+        raise WaitCoverageError("loop labels not found") from ex
+    return lines[:i10] + lines[i10 + 1:ibr] * iterations + lines[ibr + 1:]
 
 
 def retire(queue, ins, counter, state):
@@ -229,98 +251,96 @@ def retire(queue, ins, counter, state):
     return queue
 
 
-def check_wait_coverage(lines, slots, iterations=3):
-    """Static proof of the LDS-DMA / ds_read ordering of the emitted stream (same rules as tools/gen_attn_w48.py):
-      RAW  a ds_read of slot s needs every LDS-DMA issued into s to be retired by a counted vmcnt wait that is followed by a barrier;
-      WAR  an LDS-DMA into slot s needs every earlier ds_read of s to be retired by an lgkmcnt wait that is followed by a barrier;
-           a ds_write (accumulators that leave through LDS) needs that of every slot, and every LDS-DMA to be visible.
-    Walks prologue + iterations x loop body + exit with branches not taken."""
+REGISTERS = re.compile(r"(?<![\w\[%])([av])(?:(\d+)|\[(\d+):(\d+)\])(?!\w)")   # v7, a[108:111]; not %[va0], 0xa0, vcc
+LDS_READ = re.compile(r"ds_read_b\d+ (\S+), (\S+?)(?: offset:(\d+))?$")
+
+
+def registers(text):
+    """the VGPR / AGPR ranges an instruction names: [(file, first, last)]"""
+    return [(f, int(one or lo), int(one or hi)) for f, one, lo, hi in REGISTERS.findall(text)]
+
+
+def check_wait_coverage(lines, layout, iterations=3):
+    """Static proof of the emitted stream's LDS ordering and register use. The waves of a workgroup run the same stream, so one wave's
+    program order stands for all of them; the walk is prologue + iterations x loop body + exit with branches not taken. Every
+    vector-memory instruction enters the in-order vmcnt queue, every LDS instruction (and the s_memtime of a --stamps build) the lgkmcnt
+    queue; a counted s_waitcnt retires all but the newest N of its queue; an s_barrier behind the wait makes retired LDS-DMA fills
+    `visible` and returned reads `fenced` for every wave. Then:
+      RAW  a read of a ring region needs every LDS-DMA ever issued into the region to be visible;
+      WAR  an LDS-DMA needs every earlier read of its region to be fenced (the region staged ONCE is never refilled behind a read);
+           a ds_write needs that of every region and every fill to be visible; a read of the EXCHANGE area needs a ds_write before it;
+      REG  no instruction names a VGPR / AGPR that overlaps the destination of an LDS read still in the lgkmcnt queue: an MFMA or
+           VALU consumer ahead of its wait, or a ring entry reused before its previous read has returned.
+    An LDS-DMA without m0, an LDS instruction `layout` cannot classify and a walk without ring traffic raise as well."""
     seq = walk(lines, iterations)
-    b_base = slots.a_slots * slots.a_bytes
-    regions = [("A", i) for i in range(slots.a_slots)] + [("B", i) for i in range(slots.b_slots)]
-    vm, lg, fills, reads = [], [], {r: [] for r in regions}, {r: [] for r in regions}
-    m0 = None
-    n_reads = n_dma = 0
+    vm, lg = [], []   # in issue order
+    fills, reads = collections.defaultdict(list), collections.defaultdict(list)   # region -> operations (fills: all generations)
+    m0, exchanged, n_reads, n_fills = None, False, 0, 0
     for pos, ins in enumerate(seq):
+        if ins.startswith(";"):
+            continue
+        for f, lo, hi in registers(ins):
+            for op in lg:
+                if op["dst"] and op["dst"][0] == f and op["dst"][1] <= hi and lo <= op["dst"][2]:
+                    raise WaitCoverageError(f"REG: `{ins}` at {pos} names a register of the LDS read at {op['pos']}, which is outstanding")
         mm = re.match(r"s_add_u32 m0, %\[wlds\], (\d+)", ins)
         if mm:
             m0 = int(mm.group(1))
-            continue
-        if ins.startswith("buffer_load_dwordx4") and ins.endswith("lds"):
-            slot = ("A", m0 // slots.a_bytes) if m0 < b_base else ("B", (m0 - b_base) // slots.b_bytes)
-            for r in reads[slot]:
-                if r["state"] != "fenced":
-                    raise WaitCoverageError(f"WAR: LDS-DMA into slot {slot} at {pos} while the ds_read at {r['pos']} is only '{r['state']}'")
-            reads[slot] = []
+        elif re.match(r"(buffer|global|flat|scratch)_(load|store|atomic)", ins):
             op = {"state": "inflight", "pos": pos}
             vm.append(op)
-            fills[slot].append(op)
-            n_dma += 1
-            m0 = None
-            continue
-        mm = re.match(r"ds_read_b128 v\[\d+:\d+\], (\S+) offset:(\d+)", ins)
-        if mm:
-            slot = slots.read_slot(mm.group(1))[:2]
-            if not fills[slot]:
-                raise WaitCoverageError(f"RAW: ds_read of slot {slot} at {pos} before anything was staged")
-            for f in fills[slot]:
-                if f["state"] != "visible":
-                    raise WaitCoverageError(f"RAW: ds_read of slot {slot} at {pos} ({ins}) while the LDS-DMA at {f['pos']} is only '{f['state']}'")
-            op = {"state": "issued", "pos": pos}
+            if ins.endswith(" lds"):
+                if m0 is None:
+                    raise WaitCoverageError(f"LDS-DMA without an m0 destination at {pos}: {ins}")
+                region = layout.fill(m0)
+                for r in reads[region]:
+                    if region == ONCE or r["state"] != "fenced":
+                        raise WaitCoverageError(f"WAR: LDS-DMA into {region} at {pos} ({ins}) while the read of it at {r['pos']} is only "
+                                                f"'{r['state']}' (needs an lgkmcnt wait and a barrier before the fill)")
+                reads[region] = []
+                fills[region].append(op)
+                n_fills += region != ONCE
+                m0 = None
+        elif ins.startswith("ds_"):
+            op = {"state": "issued", "pos": pos, "dst": None}
+            mm = LDS_READ.match(ins)
+            region = mm and layout.read(mm.group(2), int(mm.group(3) or 0))
+            if mm and region == EXCHANGE:
+                if not exchanged:
+                    raise WaitCoverageError(f"exchange read at {pos} before any exchange write")
+            elif mm and region is not None:
+                if not fills[region]:
+                    raise WaitCoverageError(f"RAW: ds_read of {region} at {pos} ({ins}) before anything was staged into it")
+                for f in fills[region]:
+                    if f["state"] != "visible":
+                        raise WaitCoverageError(f"RAW: ds_read of {region} at {pos} ({ins}) while the LDS-DMA at {f['pos']} is only "
+                                                f"'{f['state']}' (needs a covering vmcnt wait and a barrier before the read)")
+                reads[region].append(op)
+                n_reads += region != ONCE
+            elif not mm and ins.startswith("ds_write"):
+                busy = [(r, f) for r in fills for f in fills[r] if f["state"] != "visible"] + \
+                       [(r, f) for r in reads for f in reads[r] if f["state"] != "fenced"]
+                if busy:
+                    region, f = busy[0]
+                    raise WaitCoverageError(f"WAR: ds_write at {pos} while {region} is in use: the operation at {f['pos']} is only '{f['state']}'")
+                exchanged = True
+            else:
+                raise WaitCoverageError(f"unclassified LDS instruction at {pos}: {ins}")
+            if mm:
+                op["dst"] = registers(mm.group(1))[0]
             lg.append(op)
-            reads[slot].append(op)
-            n_reads += 1
-            continue
-        if ins.startswith("ds_write"):
-            for s in regions:
-                if any(f["state"] != "visible" for f in fills[s]) or any(r["state"] != "fenced" for r in reads[s]):
-                    raise WaitCoverageError(f"WAR: ds_write at {pos} while slot {s} is still in use")
-            continue
-        if ins.startswith("s_waitcnt"):
+        elif ins.startswith(("s_memtime", "s_load")):
+            lg.append({"state": "issued", "pos": pos, "dst": None})
+        elif ins.startswith("s_waitcnt"):
             vm = retire(vm, ins, "vmcnt", "retired")
             lg = retire(lg, ins, "lgkmcnt", "done")
-            continue
-        if ins == "s_barrier":
-            for s in regions:
-                for op in fills[s]:
-                    if op["state"] == "retired":
-                        op["state"] = "visible"
-                for op in reads[s]:
-                    if op["state"] == "done":
-                        op["state"] = "fenced"
-    if not n_reads or not n_dma:
-        raise WaitCoverageError("checker saw no LDS traffic - the stream format changed")
-    return {"reads": n_reads, "fills": n_dma, "instructions": len(seq)}
-
-
-def check_operand_waits(lines):
-    """Every MFMA operand fragment must have returned from LDS: walk one prologue + 3 loop bodies, tracking reads in issue order and
-    the counted lgkmcnt waits; an MFMA that names a register whose read is still outstanding is an error. (A read that overwrites a
-    register an earlier-issued MFMA still has to read cannot happen: MFMAs read their operands at issue, and the stream is in order.)"""
-    out = []  # (first register) of outstanding reads, issue order
-    n_mfma = 0
-    for pos, ins in enumerate(walk(lines, 3, with_exit=False)):
-        mm = re.match(r"ds_read_b128 v\[(\d+):\d+\]", ins)
-        if mm:
-            out.append(int(mm.group(1)))
-            continue
-        ml = re.search(r"lgkmcnt\((\d+)\)", ins) if ins.startswith("s_waitcnt") else None
-        if ml:
-            keep = int(ml.group(1))
-            out = out[len(out) - keep:] if keep < len(out) else out
-            continue
-        mm = re.match(r"v_mfma_f32_16x16x32_bf16 [av]\[\d+:\d+\], v\[(\d+):\d+\], v\[(\d+):\d+\]", ins)
-        if mm:
-            n_mfma += 1
-            for r in (int(mm.group(1)), int(mm.group(2))):
-                if r in out:
-                    raise WaitCoverageError(f"MFMA at {pos} reads v[{r}:{r + 3}] while its ds_read is outstanding")
-            continue
-        if ins.startswith("v_mfma"):
-            raise WaitCoverageError(f"MFMA at {pos} is not in the form the checker reads: {ins}")
-    if not n_mfma:
-        raise WaitCoverageError("checker saw no MFMA - the stream format changed")
-    return True
+        elif ins == "s_barrier":
+            for ops, before, after in ((fills, "retired", "visible"), (reads, "done", "fenced")):
+                for op in [op for region in ops for op in ops[region] if op["state"] == before]:
+                    op["state"] = after
+    if not n_reads or not n_fills:
+        raise WaitCoverageError("checker saw no ring traffic - the stream format changed")
+    return {"ring_reads": n_reads, "ring_fills": n_fills, "instructions": len(seq)}
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -330,8 +350,8 @@ def finish(lines, save_m0, raw_race):
     """The asm block as the kernel includes it. m0 (the LDS-DMA destination) is a reserved register: naming it in the clobber list draws
     "-Winline-asm ... may lead to undefined behaviour" from the compiler, so the block saves it in an SGPR of its own and restores it on
     the way out; the surrounding HIP code sees m0 unchanged and the clobber list does not name it.
-    Checker self-tests: --inject-raw-race replaces the loop's first `raw_race[0]` (the wait in front of the second barrier) by
-    `raw_race[1]`, which leaves a part of tile t+1 in flight; --inject-war-race drops the loop's first barrier."""
+    Checker self-tests: --inject-raw-race replaces the loop's first `raw_race[0]` (the wait in front of a barrier that publishes staged
+    tiles) by `raw_race[1]`, which leaves a part of a tile that is read next in flight; --inject-war-race drops the loop's first barrier."""
     lines = [f"s_mov_b32 s{save_m0}, m0"] + lines + [f"s_mov_b32 m0, s{save_m0}"]
     if "--inject-raw-race" in sys.argv:
         lines[lines.index(raw_race[0], lines.index("10:"))] = raw_race[1]
@@ -340,21 +360,21 @@ def finish(lines, save_m0, raw_race):
     return lines
 
 
-def clobbers_inc(script, nv, na, s_last):
-    """v0 .. v<nv - 1>, a0 .. a<na - 1>, s36 .. s<s_last>, twelve per line"""
-    clob = [f"v{i}" for i in range(nv)] + [f"a{i}" for i in range(na)] + [f"s{i}" for i in range(36, s_last + 1)] + ["vcc", "scc", "memory"]
-    text = f"// GENERATED by tools/{script} - do not edit. Registers the assembly main loop assigns by hand.\n"
+def clobbers_inc(script, nv, na, sregs, part="main loop"):
+    """v0 .. v<nv - 1>, a0 .. a<na - 1>, s<i> for i in sregs, twelve per line"""
+    clob = [f"v{i}" for i in range(nv)] + [f"a{i}" for i in range(na)] + [f"s{i}" for i in sregs] + ["vcc", "scc", "memory"]
+    text = f"// GENERATED by tools/{script} - do not edit. Registers the assembly {part} assigns by hand.\n"
     for i in range(0, len(clob), 12):
         text += ", ".join('"' + c + '"' for c in clob[i:i + 12]) + ("," if i + 12 < len(clob) else "") + "\n"
     return text
 
 
-def emit(script, kernel, stem, diag, lines, stats, others):
-    """Writes csrc/<stem>.inc (the stream as string literals) and `others` ({file name: text}), or with --check compares them with the
-    committed files. A diagnostic build (`diag`: --stamps or schedule knobs) goes to <stem>_stamps.inc, which is not committed, and
-    writes nothing else."""
-    text = f"// GENERATED by tools/{script} - do not edit. gfx950 assembly main loop of {kernel} (gemm.hip).\n"
-    text += "".join('"' + ln + '\\n\\t"\n' for ln in lines)
+def emit(script, what, stem, diag, lines, stats, others, diag_status=4):
+    """Writes csrc/<stem>.inc (the stream as string literals, headed "gfx950 assembly <what>") and `others` ({file name: text}), or with
+    --check compares them with the committed files. A diagnostic build (`diag`: --stamps or schedule knobs) goes to <stem>_stamps.inc,
+    which is not committed, and writes nothing else; --check of one exits with `diag_status` unless that file happens to be there."""
+    text = f"// GENERATED by tools/{script} - do not edit. gfx950 assembly {what}.\n"
+    text += "".join('"' + ln.replace('"', '\\"') + '\\n\\t"\n' for ln in lines)
     files = {stem + ("_stamps.inc" if diag else ".inc"): text}
     if "--check" in sys.argv or not diag:
         files.update(others)
@@ -362,7 +382,7 @@ def emit(script, kernel, stem, diag, lines, stats, others):
     if "--check" in sys.argv:
         same = all(os.path.exists(p) and open(p).read() == t for p, t in files.items())
         print(f"wait coverage ok: {stats}; committed output {'matches' if same else 'DIFFERS'}")
-        sys.exit(0 if same else 4)
+        sys.exit(0 if same else diag_status if diag else 4)
     for p, t in files.items():
         with open(p, "w") as f:
             f.write(t)

@@ -20,6 +20,10 @@ Register map (per wave):
 Operands (compiler-assigned): see the asm statement in attention.hip.
 """
 import os
+import re
+import sys
+
+from asm_common import EXCHANGE, ONCE, Layout, check_wait_coverage, clobbers_inc, emit, finish
 
 QF, SA, SB, PF, RING = 0, 48, 96, 144, 168
 MAXR = 184        # v184..186: this lane's maximum of each query block's scores (phase 1)
@@ -36,7 +40,8 @@ BIASR = 184       # masked variant: v[184:199] = this lane's 16 bias values of t
 BIAS_LDS = 4 * 32768  # byte offset of the bias vector in LDS (after the four K / Vt ring slots), Tk <= 4096 floats
 BADDR = 221           # masked variant: LDS address of this lane's bias values of the tile being prepared
 STAGE = 32768
-if "--bias" in __import__("sys").argv:
+XRD = SA + 8          # v[56:59]: addresses of the epilogue's read-backs from the exchange area (the S buffers are dead there)
+if "--bias" in sys.argv:
     FLOOR, ONES, NV = 220, 224, 228   # v195..199 belong to the bias values in this variant
 TM = 168             # v168, v169: temporaries of the ragged-tail mask (the old fragment ring's registers; the masked variant keeps
                      # its bias values in v[184:199] from the start of a step, so the mask must not use the rare-path temporaries)
@@ -78,11 +83,11 @@ def vblock_off(db):
     return db * 16 * 128
 
 
-BIAS = "--bias" in __import__("sys").argv   # masked variant: additive per-key bias (cross-attention text mask)
+BIAS = "--bias" in sys.argv   # masked variant: additive per-key bias (cross-attention text mask)
 # prescaled variant: Q arrives multiplied by scale * log2(e) (rounded to bf16 once, by the producer): the MFMA's scores are already
 # the base-2 exponents, so the 48 v_mul per tile (and the multiply of the rare path) disappear. %[c] is unused, %[tau] = 8.0,
 # %[isc] = log2(e) (the bias is given in the reference's post-scale natural-log units).
-PS = "--prescaled" in __import__("sys").argv
+PS = "--prescaled" in sys.argv
 ABL = set(os.environ.get("W48_ABLATE", "").split(","))  # timing experiments only (wrong results): nodma, noexp, nords, ra6
 
 
@@ -491,7 +496,7 @@ class Gen:
         self.advance_stage_offsets()
         st(3)
         # counted wait derived from the staging model (not a literal): everything but the youngest TILES_AHEAD fills has landed.
-        # check_wait_coverage() proves that every ring-slot read of the next steps is covered by this wait + barrier.
+        # check_wait_coverage() (tools/asm_common.py) proves that every ring-slot read of the next steps is covered by this wait + barrier.
         self.e(f"s_waitcnt vmcnt({STAGE_OPS * TILES_AHEAD})")
         self.e("s_barrier")
         st(4)
@@ -694,7 +699,7 @@ class Gen:
         e("s_waitcnt lgkmcnt(0)")    # a wave reads back only what it wrote itself: no barrier
         # read row group i, store 4 whole rows per instruction
         R = SB                       # v[96:143]: 12 x 4 registers
-        RA4 = SA + 8                 # v[56:59]: read address per i & 3 (the write temporaries are dead)
+        RA4 = XRD                    # v[56:59]: read address per i & 3 (the write temporaries are dead)
         for n in range(4):
             e(f"v_xor_b32 v{RA4 + n}, {n << 6}, v{ERX}")
             e(f"v_add_u32 v{RA4 + n}, v{RA4 + n}, v{ERB}")
@@ -727,161 +732,37 @@ class Gen:
         return self.lines
 
 
-class WaitCoverageError(AssertionError):
-    pass
+def lds_read(addr, off):
+    """What an LDS read touches: %[ka*] / %[va*] address ring slots 0 / 1, their + 64 KB copies slots 2 / 3, and the offset picks the
+    slot of the pair; v<BADDR> the bias vector; v[XRD : XRD + 3] the wave's own rows in the exchange area of the epilogue."""
+    mm = re.fullmatch(r"%\[([kv])a\d\]", addr)
+    if mm:
+        return off // STAGE, mm.group(1).upper()
+    r = int(addr[1:]) if re.fullmatch(r"v\d+", addr) else -1
+    if HI <= r < HI + 6:
+        return 2 + off // STAGE, "K" if r < HI + 4 else "V"
+    if r == BADDR:
+        return ONCE
+    return EXCHANGE if XRD <= r < XRD + 4 else None
 
 
-def check_wait_coverage(lines, iterations=3):
-    """Static proof that the emitted stream orders every LDS-DMA fill against the ds_reads of its ring slot.
-
-    The four waves of a workgroup run this same stream, so one wave's program order stands for all of them. Rules (MI355X guide,
-    'Read a staged buffer one phase AFTER the wait that retires it'; LDS-DMA is ordered for a ds_read only by the issuing waves'
-    counted vmcnt followed by a barrier the reader has passed):
-      RAW  a ds_read of ring region (slot, K|Vt) needs every LDS-DMA ever issued into that region to have been retired by an
-           `s_waitcnt vmcnt(n)` (in-order counter: all but the n youngest vector-memory operations are done) that is itself followed
-           by an `s_barrier`, both before the read in program order.
-      WAR  an LDS-DMA into a region needs every earlier ds_read of that region to have been retired by an `s_waitcnt lgkmcnt(n)`
-           and then an `s_barrier` - before the DMA is issued.
-    The stream is walked as prologue + `iterations` x loop body (+ epilogue), branches not taken: the rare path and the ragged-tail
-    code contain no memory operations, and the exit branch only skips code. Raises WaitCoverageError naming the first violation."""
-    import re
-
-    try:
-        i10 = lines.index("10:")
-        ibr = lines.index("s_branch 10b")
-    except ValueError as e:
-        raise WaitCoverageError("loop labels not found") from e
-    seq = lines[:i10] + lines[i10 + 1:ibr] * iterations + lines[ibr + 1:]
-    vm = []      # outstanding vector-memory operations in issue order: dicts {region|None, state}
-    lg = []      # outstanding LDS reads in issue order
-    fills = {}   # region -> list of DMA ops (all generations)
-    reads = {}   # region -> list of read ops
-    m0 = None
-    n_reads = n_dma = 0
-    for pos, ins in enumerate(seq):
-        mm = re.match(r"s_add_u32 m0, %\[wlds\], (\d+)", ins)
-        if mm:
-            m0 = int(mm.group(1))
-            continue
-        if ins.startswith("buffer_load_dwordx4") and ins.endswith("lds"):
-            if m0 is None:
-                raise WaitCoverageError(f"LDS-DMA without an m0 destination at {pos}: {ins}")
-            region = None
-            if m0 < 4 * STAGE:
-                region = (m0 // STAGE, "K" if (m0 % STAGE) < 16384 else "V")
-                for r in reads.get(region, []):
-                    if r["state"] != "fenced":
-                        raise WaitCoverageError(f"WAR: LDS-DMA into {region} at {pos} ({ins}) while a ds_read of it issued at "
-                                                f"{r['pos']} is only '{r['state']}' (needs lgkmcnt wait + barrier before the fill)")
-                reads[region] = []
-                n_dma += 1
-            elif m0 >= BIAS_LDS:
-                region = ("bias", "vector")   # staged once in the prologue, read by every step of the masked variant
-            op = {"region": region, "state": "inflight", "pos": pos}
-            vm.append(op)
-            if region is not None:
-                fills.setdefault(region, []).append(op)
-            m0 = None
-            continue
-        if re.match(r"(global_load|buffer_load|global_store|buffer_store)", ins):
-            vm.append({"region": None, "state": "inflight", "pos": pos})
-            continue
-        mm = re.match(r"ds_read_b128 [av]\[\d+:\d+\], (\S+) offset:(\d+)", ins) or re.match(r"ds_read_b128 [av]\[\d+:\d+\], (\S+)$", ins)
-        if mm:
-            addr = mm.group(1)
-            off = int(mm.group(2)) if mm.lastindex == 2 else 0
-            region = None
-            ka = re.match(r"%\[ka(\d)\]", addr)
-            va = re.match(r"%\[va(\d)\]", addr)
-            hv = re.match(r"v(\d+)$", addr)
-            if ka:
-                region = (off // STAGE, "K")
-            elif va:
-                region = (off // STAGE, "V")
-            elif hv and HI <= int(hv.group(1)) < HI + 6:
-                region = (2 + off // STAGE, "K" if int(hv.group(1)) < HI + 4 else "V")
-            elif hv and int(hv.group(1)) == BADDR:
-                region = ("bias", "vector")
-            op = {"region": region, "state": "issued", "pos": pos}
-            lg.append(op)
-            if region is not None:
-                n_reads += 1
-                if not fills.get(region):
-                    raise WaitCoverageError(f"RAW: ds_read of {region} at {pos} ({ins}) before anything was staged into it")
-                for f in fills[region]:
-                    if f["state"] != "visible":
-                        raise WaitCoverageError(f"RAW: ds_read of {region} at {pos} ({ins}) while the LDS-DMA issued at {f['pos']} is "
-                                                f"only '{f['state']}' (needs a covering vmcnt wait AND a barrier before the read)")
-                reads.setdefault(region, []).append(op)
-            continue
-        if ins.startswith("s_waitcnt"):
-            mv = re.search(r"vmcnt\((\d+)\)", ins)
-            ml = re.search(r"lgkmcnt\((\d+)\)", ins)
-            if mv:
-                keep = int(mv.group(1))
-                done, vm = (vm[:len(vm) - keep], vm[len(vm) - keep:]) if keep < len(vm) else ([], vm)
-                for op in done:
-                    op["state"] = "retired"
-            if ml:
-                keep = int(ml.group(1))
-                done, lg = (lg[:len(lg) - keep], lg[len(lg) - keep:]) if keep < len(lg) else ([], lg)
-                for op in done:
-                    op["state"] = "done"
-            continue
-        if ins == "s_barrier":
-            for ops in fills.values():
-                for op in ops:
-                    if op["state"] == "retired":
-                        op["state"] = "visible"
-            for ops in reads.values():
-                for op in ops:
-                    if op["state"] == "done":
-                        op["state"] = "fenced"
-            # generations that are fully visible and superseded need no further tracking, but keeping them is harmless
-            continue
-    if n_reads == 0 or n_dma == 0:
-        raise WaitCoverageError("checker saw no ring traffic - the stream format changed")
-    return {"ring_reads": n_reads, "ring_fills": n_dma, "instructions": len(seq)}
+LAYOUT = Layout(lambda m0: (m0 // STAGE, "K" if m0 % STAGE < 16384 else "V") if m0 < BIAS_LDS else ONCE, lds_read)
 
 
 def main():
-    import sys
     stamps = "--stamps" in sys.argv
-    g = Gen(stamps)
-    lines = g.build()
-    # m0 (the LDS-DMA destination) is a reserved register: naming it in the clobber list draws "-Winline-asm ... may lead to undefined
-    # behaviour" from the compiler (round-4 verdict, Weak 10). The block saves it in an SGPR of its own and restores it on the way out,
-    # so the surrounding HIP code sees m0 unchanged and the clobber list no longer names it.
-    lines = ["s_mov_b32 s95, m0"] + lines + ["s_mov_b32 m0, s95"]   # (s84..s93 hold the stamps of the --stamps build)
-    here = os.path.dirname(os.path.abspath(__file__))
-    name = "attention_w48_asm" + ("_bias" if BIAS else "") + ("_ps" if PS else "") + ("_stamps" if stamps else "") + ".inc"
-    out = os.path.join(here, "..", "ltx-video-swift-mlx_amd", "csrc", name)
+    # --inject-raw-race: a step's closing wait leaves the tile it staged in flight; the K reads the next step issues ahead find it so
+    n = STAGE_OPS * TILES_AHEAD
+    lines = finish(Gen(stamps).build(), 95, (f"s_waitcnt vmcnt({n})", f"s_waitcnt vmcnt({n + STAGE_OPS})"))   # (s84..s93: --stamps)
     if "--inject-prologue-race" in sys.argv:
         # the race that shipped once (commit 7c76101): the prologue left tiles 1 and 2 in flight while step 0 reads slot 1
         want = f"s_waitcnt vmcnt({STAGE_OPS // 2})" if CROSS else f"s_waitcnt vmcnt({STAGE_OPS + STAGE_OPS // 2})"
         k = max(i for i, ln in enumerate(lines[:lines.index("10:")]) if ln == want)
         lines[k] = f"s_waitcnt vmcnt({2 * STAGE_OPS})"
-    stats = None
-    if not (ABL - {""}):
-        stats = check_wait_coverage(lines)   # every generated stream is proven before it is written
-    if "--check" in sys.argv:
-        # CPU test entry: prove the stream and compare it with the committed file; writes nothing
-        body = ["// GENERATED by tools/gen_attn_w48.py - do not edit. gfx950 assembly body of attn_fwd_kernel_w48_asm (attention.hip).\n"]
-        body += ['"' + ln.replace('"', '\\"') + '\\n\\t"\n' for ln in lines]
-        same = os.path.exists(out) and open(out).read() == "".join(body)
-        print(f"wait coverage ok: {stats}; committed file {'matches' if same else 'DIFFERS'}")
-        sys.exit(0 if same or stamps else 4)
-    with open(out, "w") as f:
-        f.write("// GENERATED by tools/gen_attn_w48.py - do not edit. gfx950 assembly body of attn_fwd_kernel_w48_asm (attention.hip).\n")
-        for ln in lines:
-            f.write('"' + ln.replace('"', '\\"') + '\\n\\t"\n')
-    clob = [f"v{i}" for i in range(NV)] + [f"a{i}" for i in range(ARING + 4 * RN)] + [f"s{i}" for i in range(36, 84)] + ["s95", "vcc", "scc", "memory"]
-    with open(os.path.join(here, "..", "ltx-video-swift-mlx_amd", "csrc", "attention_w48_bias_clobbers.inc" if BIAS else "attention_w48_clobbers.inc"), "w") as f:
-        f.write("// GENERATED by tools/gen_attn_w48.py - do not edit. Registers the assembly body assigns by hand.\n")
-        for i in range(0, len(clob), 12):
-            f.write(", ".join('"' + c + '"' for c in clob[i:i + 12]) + ("," if i + 12 < len(clob) else "") + "\n")
-    n_mfma = sum(1 for ln in lines if "v_mfma" in ln)
-    print(f"{len(lines)} lines, {n_mfma} MFMAs -> {os.path.normpath(out)}")
+    stats = None if ABL - {""} else check_wait_coverage(lines, LAYOUT)   # every generated stream is proven before it is written
+    emit("gen_attn_w48.py", "body of attn_fwd_kernel_w48_asm (attention.hip)", "attention_w48_asm" + ("_bias" if BIAS else "") + ("_ps" if PS else ""),
+         stamps, lines, stats, {"attention_w48_bias_clobbers.inc" if BIAS else "attention_w48_clobbers.inc":
+                                clobbers_inc("gen_attn_w48.py", NV, ARING + 4 * RN, [*range(36, 84), 95], "body")}, diag_status=0)
 
 
 if __name__ == "__main__":

@@ -44,11 +44,13 @@ Pipeline of one tile step t (S(t) is in the `cur` buffer, already checked agains
   then the reference check of S(t+1) (rare path: rescale O and l), `s_waitcnt vmcnt(0)`, barrier.
 Fragment reads run seven ahead of their MFMAs ACROSS the step boundary: the first seven K reads of step t+1 are issued under part
 B2 of step t. That is legal because the LDS-DMA of tile t+3 is issued early in step t and the step ends with vmcnt(0) + barrier, so
-at every barrier the three tiles ahead are visible (check_wait_coverage proves it on the emitted text).
+at every barrier the three tiles ahead are visible (check_wait_coverage of tools/asm_common.py proves it on the emitted text).
 """
 import os
 import re
 import sys
+
+from asm_common import EXCHANGE, Layout, check_wait_coverage, clobbers_inc, emit, finish
 
 # ---- accumulator file ----
 O_OWN, O_SH, Q_OWN, Q_SH, ARING = 0, 64, 128, 160, 192
@@ -640,167 +642,32 @@ class Gen:
                 q += 1
 
 
-# ---------------------------------------------------------------------------------------------------------------------
-# static proof of the LDS ring's ordering
-# ---------------------------------------------------------------------------------------------------------------------
-class WaitCoverageError(AssertionError):
-    pass
+def lds_read(addr, off):
+    """What an LDS read touches: the fragment addresses give ring slots 0 / 1 (lo) or 2 / 3 (hi, + 64 KB), the offset picks the slot of
+    the pair; %[xin] is the partner's exchange area."""
+    if addr == "%[xin]":
+        return EXCHANGE
+    r = int(addr[1:]) if re.fullmatch(r"v\d+", addr) else -1
+    if KA_LO <= r < KA_LO + 32:
+        return 2 * ((r - KA_LO) // 16) + off // STAGE, "K"
+    if VA_LO <= r < VA_LO + 8:
+        return 2 * ((r - VA_LO) // 4) + off // STAGE, "V"
+    return None
 
 
-def check_wait_coverage(lines, iterations=3):
-    """Every ds_read of a ring region (slot, K | V) must come behind a vmcnt wait that retired ALL LDS-DMA fills ever issued into
-    that region and a barrier behind that wait (RAW); every LDS-DMA into a region behind an lgkmcnt wait that retired all earlier
-    reads of it and a barrier behind that wait (WAR). One wave's program order stands for all four (same stream). The walk is
-    prologue + `iterations` x loop body + epilogue with branches not taken (rare path and exits carry no ring traffic)."""
-    try:
-        i10 = lines.index("10:")
-        ibr = lines.index("s_branch 10b")
-    except ValueError as ex:
-        raise WaitCoverageError("loop labels not found") from ex
-    seq = lines[:i10] + lines[i10 + 1:ibr] * iterations + lines[ibr + 1:]
-    vm, lg = [], []
-    fills, reads = {}, {}
-    m0 = None
-    n_reads = n_dma = 0
-    k_regs = {}
-    for b, (hi, _h) in ((KA_LO, (0, 0)), (KB_LO, (0, 1)), (KA_HI, (1, 0)), (KB_HI, (1, 1))):
-        for ks in range(8):
-            k_regs[b + ks] = hi
-    v_regs = {VA_LO + i: 0 for i in range(4)}
-    v_regs.update({VA_HI + i: 1 for i in range(4)})
-    in_exchange = False
-    for pos, ins in enumerate(seq):
-        mm = re.match(r"s_add_u32 m0, %\[wlds\], (\d+)", ins)
-        if mm:
-            m0 = int(mm.group(1))
-            continue
-        if ins.startswith("buffer_load_dwordx4") and ins.endswith("lds"):
-            if m0 is None:
-                raise WaitCoverageError(f"LDS-DMA without an m0 destination at {pos}: {ins}")
-            region = (m0 // STAGE, "K" if (m0 % STAGE) < V_OFF else "V")
-            for r in reads.get(region, []):
-                if r["state"] != "fenced":
-                    raise WaitCoverageError(f"WAR: LDS-DMA into {region} at {pos} ({ins}) while a ds_read of it issued at {r['pos']} "
-                                            f"is only '{r['state']}' (needs lgkmcnt wait + barrier before the fill)")
-            reads[region] = []
-            n_dma += 1
-            op = {"region": region, "state": "inflight", "pos": pos}
-            vm.append(op)
-            fills.setdefault(region, []).append(op)
-            m0 = None
-            continue
-        if re.match(r"(global_load|buffer_load|global_store|buffer_store)", ins):
-            vm.append({"region": None, "state": "inflight", "pos": pos})
-            continue
-        if ins.startswith("ds_write"):
-            # exchange area (epilogue): legal only once every fill is visible and every ring read fenced
-            for reg, ops in fills.items():
-                for f in ops:
-                    if f["state"] != "visible":
-                        raise WaitCoverageError(f"exchange write at {pos} while the LDS-DMA of {reg} issued at {f['pos']} is '{f['state']}'")
-            for reg, ops in reads.items():
-                for r in ops:
-                    if r["state"] != "fenced":
-                        raise WaitCoverageError(f"exchange write at {pos} while a ring read of {reg} issued at {r['pos']} is '{r['state']}'")
-            in_exchange = True
-            lg.append({"region": None, "state": "issued", "pos": pos})
-            continue
-        mm = re.match(r"ds_read_b128 [av]\[\d+:\d+\], (\S+) offset:(\d+)", ins)
-        if mm:
-            addr, off = mm.group(1), int(mm.group(2))
-            region = None
-            hv = re.match(r"v(\d+)$", addr)
-            if hv and int(hv.group(1)) in k_regs:
-                region = (2 * k_regs[int(hv.group(1))] + off // STAGE, "K")
-            elif hv and int(hv.group(1)) in v_regs:
-                region = (2 * v_regs[int(hv.group(1))] + off // STAGE, "V")
-            elif addr == "%[xin]":
-                if not in_exchange:
-                    raise WaitCoverageError(f"exchange read at {pos} before any exchange write")
-            else:
-                raise WaitCoverageError(f"unclassified LDS read at {pos}: {ins}")
-            op = {"region": region, "state": "issued", "pos": pos}
-            lg.append(op)
-            if region is not None:
-                n_reads += 1
-                if not fills.get(region):
-                    raise WaitCoverageError(f"RAW: ds_read of {region} at {pos} ({ins}) before anything was staged into it")
-                for f in fills[region]:
-                    if f["state"] != "visible":
-                        raise WaitCoverageError(f"RAW: ds_read of {region} at {pos} ({ins}) while the LDS-DMA issued at {f['pos']} is "
-                                                f"only '{f['state']}' (needs a covering vmcnt wait AND a barrier before the read)")
-                reads.setdefault(region, []).append(op)
-            continue
-        if ins.startswith("s_waitcnt"):
-            mv = re.search(r"vmcnt\((\d+)\)", ins)
-            ml = re.search(r"lgkmcnt\((\d+)\)", ins)
-            if mv:
-                keep = int(mv.group(1))
-                done, vm = (vm[:len(vm) - keep], vm[len(vm) - keep:]) if keep < len(vm) else ([], vm)
-                for op in done:
-                    op["state"] = "retired"
-            if ml:
-                keep = int(ml.group(1))
-                done, lg = (lg[:len(lg) - keep], lg[len(lg) - keep:]) if keep < len(lg) else ([], lg)
-                for op in done:
-                    op["state"] = "done"
-            continue
-        if ins == "s_barrier":
-            for ops in fills.values():
-                for op in ops:
-                    if op["state"] == "retired":
-                        op["state"] = "visible"
-            for ops in reads.values():
-                for op in ops:
-                    if op["state"] == "done":
-                        op["state"] = "fenced"
-            continue
-    if n_reads == 0 or n_dma == 0:
-        raise WaitCoverageError("checker saw no ring traffic - the stream format changed")
-    return {"ring_reads": n_reads, "ring_fills": n_dma, "instructions": len(seq)}
+LAYOUT = Layout(lambda m0: (m0 // STAGE, "K" if m0 % STAGE < V_OFF else "V"), lds_read)
 
 
 def main():
     stamps = "--stamps" in sys.argv
-    g = Gen(stamps)
-    lines = g.build()
-    here = os.path.dirname(os.path.abspath(__file__))
-    csrc = os.path.join(here, "..", "ltx-video-swift-mlx_amd", "csrc")
-    name = "attention_x32_asm" + ("_stamps" if stamps else "") + ".inc"
+    lines = Gen(stamps).build()
     if stamps:
-        for i in range(10):
-            lines.insert(0, f"s_mov_b32 s{84 + i}, 0")
-    lines = ["s_mov_b32 s96, m0"] + lines + ["s_mov_b32 m0, s96"]   # m0 saved / restored instead of clobbered (see gen_attn_w48.py)
-    out = os.path.join(csrc, name)
-    if "--inject-raw-race" in sys.argv:
-        # leave the LDS-DMA of the step in flight across its barrier: the next step but one reads a slot that may be empty
-        k = [i for i, ln in enumerate(lines) if ln == "s_waitcnt vmcnt(0)" and i > lines.index("10:")][0]
-        lines[k] = f"s_waitcnt vmcnt({STAGE_OPS})"
-    if "--inject-war-race" in sys.argv:
-        # drop a step's barrier: the next step's LDS-DMA overwrites a slot whose reads were never fenced
-        k = [i for i, ln in enumerate(lines) if ln == "s_barrier" and i > lines.index("10:")][0]
-        lines[k] = "s_nop 0"
-    stats = None
-    if not (ABL - {""}):
-        stats = check_wait_coverage(lines)
-    header = "// GENERATED by tools/gen_attn_x32.py - do not edit. gfx950 assembly body of attn_fwd_kernel_x32_asm (attention.hip).\n"
-    body = [header] + ['"' + ln.replace('"', '\\"') + '\\n\\t"\n' for ln in lines]
-    if "--check" in sys.argv:
-        same = os.path.exists(out) and open(out).read() == "".join(body)
-        print(f"wait coverage ok: {stats}; committed file {'matches' if same else 'DIFFERS'}")
-        sys.exit(0 if same or stamps else 4)
-    with open(out, "w") as f:
-        f.write("".join(body))
-    if stamps:
-        print(f"{len(lines)} lines -> {os.path.normpath(out)} (stamps build)")
-        return
-    clob = [f"v{i}" for i in range(NV)] + [f"a{i}" for i in range(NA)] + [f"s{i}" for i in range(36, 97)] + ["vcc", "scc", "memory"]
-    with open(os.path.join(csrc, "attention_x32_clobbers.inc"), "w") as f:
-        f.write("// GENERATED by tools/gen_attn_x32.py - do not edit. Registers the assembly body assigns by hand.\n")
-        for i in range(0, len(clob), 12):
-            f.write(", ".join('"' + c + '"' for c in clob[i:i + 12]) + ("," if i + 12 < len(clob) else "") + "\n")
-    n_mfma = sum(1 for ln in lines if "v_mfma" in ln)
-    print(f"{len(lines)} lines, {n_mfma} MFMAs, {stats} -> {os.path.normpath(out)}")
+        lines = [f"s_mov_b32 s{84 + i}, 0" for i in reversed(range(10))] + lines
+    # --inject-raw-race: the LDS-DMA of a step stays in flight across its barrier, the next step but one reads a slot that may be empty
+    lines = finish(lines, 96, ("s_waitcnt vmcnt(0)", f"s_waitcnt vmcnt({STAGE_OPS})"))
+    stats = None if ABL - {""} else check_wait_coverage(lines, LAYOUT)
+    emit("gen_attn_x32.py", "body of attn_fwd_kernel_x32_asm (attention.hip)", "attention_x32_asm", stamps, lines, stats,
+         {"attention_x32_clobbers.inc": clobbers_inc("gen_attn_x32.py", NV, NA, range(36, 97), "body")}, diag_status=0)
 
 
 if __name__ == "__main__":

@@ -22,8 +22,8 @@ Structure (what a 24 + 32 KB K-tile allows in 160 KB of LDS: TWO slots for the a
       after BAR2    s_waitcnt vmcnt(22) + s_barrier         A(t+1) and B(t+1) have landed; B(t+2), A(t+2), B(t+3) may fly [RAW]
       MFMA 83..96   one ds_read of a k-step-0 fragment of tile t+1 behind each
     two barriers and no VALU instruction per K-tile; the loop body is six tiles long (2 x 3 slots), left after any tile. Every
-    wait is derived from the issue order, and check_wait_coverage() (tools/gemm_asm_common.py, shared with the 192 x 384 and
-    384 x 256 streams) proves both hazards on the emitted text before the file is written.
+    wait is derived from the issue order, and check_wait_coverage() (tools/asm_common.py, shared with every proven
+    stream) proves both hazards and the operand waits on the emitted text before the file is written.
 
 Register map (per wave):
   v[0:23]  A fragments k-step 0   v[24:55]  B fragments k-step 0      v[56:79] / v[80:111]  the same for k-step 1
@@ -33,7 +33,7 @@ Register map (per wave):
 import os
 import sys
 
-from gemm_asm_common import RegisterTileStream, Slots, check_operand_waits, check_wait_coverage, clobbers_inc, emit, finish, knobs, read_slot_from
+from asm_common import RegisterTileStream, check_wait_coverage, clobbers_inc, emit, finish, knobs, slot_layout
 
 MI, NI = 6, 8
 NA, NB = 6, 8                 # LDS-DMA pieces per wave and K-tile
@@ -55,7 +55,7 @@ STAMPS = "--stamps" in sys.argv   # diagnostic build (tools/ubench/gemm_dtl_stam
 # schedule knobs for A/B builds: DTL_KNOBS="bar1=26,dma0=28,dmae=4,bar2=82,next=83,reads=14"
 globals().update(knobs("DTL_KNOBS", {"bar1": "BAR1_AFTER", "dma0": "DMA_FIRST", "dmae": "DMA_EVERY", "bar2": "BAR2_AFTER", "next": "NEXT_FROM",
                                      "reads": "READ_UNTIL"}))
-SLOTS = Slots(A_SLOTS, A_BYTES, B_SLOTS, B_BYTES, read_slot_from(S1))
+LAYOUT = slot_layout(A_SLOTS, A_BYTES, B_BYTES, S1)
 
 
 def acc(mi, ni):
@@ -103,10 +103,9 @@ class Gen(RegisterTileStream):
 def main():
     # --inject-raw-race: the second barrier's wait leaves A(t+1) in flight
     lines = finish(Gen(STAMPS).build(), SAVE_M0, (f"s_waitcnt vmcnt({INFLIGHT})", f"s_waitcnt vmcnt({INFLIGHT + NA})"))
-    stats = check_wait_coverage(lines, SLOTS)
-    check_operand_waits(lines)
-    emit("gen_gemm_asm_dtl.py", "gemm_bf16_kernel_dtl", "gemm_dtl_192x256", STAMPS or os.environ.get("DTL_KNOBS"), lines, stats,
-         {"gemm_dtl_192x256_clobbers.inc": clobbers_inc("gen_gemm_asm_dtl.py", NV, MI * NI * 4, SAVE_M0)})
+    stats = check_wait_coverage(lines, LAYOUT)
+    emit("gen_gemm_asm_dtl.py", "main loop of gemm_bf16_kernel_dtl (gemm.hip)", "gemm_dtl_192x256", STAMPS or os.environ.get("DTL_KNOBS"), lines, stats,
+         {"gemm_dtl_192x256_clobbers.inc": clobbers_inc("gen_gemm_asm_dtl.py", NV, MI * NI * 4, range(36, SAVE_M0 + 1))})
 
 
 if __name__ == "__main__":

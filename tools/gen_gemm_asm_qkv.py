@@ -26,8 +26,8 @@ does not fit):
       after BAR2     s_waitcnt vmcnt(18) + s_barrier         A(t+1) and B(t+1) have landed; A(t+2), B(t+2) may fly    [RAW]
       MFMA 127..144  one ds_read of a k-step-0 fragment of tile t+1 behind each
     B(t+2) can only be requested after the barrier that frees tile t, so the counted wait leaves exactly the 18 pieces of tile t+2
-    in flight. The loop body is two tiles long, left after either. check_wait_coverage() (tools/gemm_asm_common.py, shared with
-    the 192 x 256 and 384 x 256 streams) proves both hazards on the emitted text before the file is written.
+    in flight. The loop body is two tiles long, left after either. check_wait_coverage() (tools/asm_common.py, shared with
+    every proven stream) proves both hazards and the operand waits on the emitted text before the file is written.
   * one accumulator chain per output element, K ascending, A = activations, B = weights: bit-identical to the 192 x 256 stream
     and to the 192 x 128 ring kernel on the same operands.
 
@@ -45,7 +45,7 @@ Register map (per wave):
 import os
 import sys
 
-from gemm_asm_common import RegisterTileStream, Slots, check_operand_waits, check_wait_coverage, clobbers_inc, emit, finish, knobs, read_slot_from, vr
+from asm_common import RegisterTileStream, check_wait_coverage, clobbers_inc, emit, finish, knobs, slot_layout, vr
 
 MI, NQ, NVF = 6, 8, 4
 NI = NQ + NVF
@@ -71,7 +71,7 @@ STAMPS = "--stamps" in sys.argv   # diagnostic build (tools/ubench/gemm_qkv_stam
 # schedule knobs for A/B builds: QKV_KNOBS="bar1=26,dma0=27,dmae=5,bar2=126,next=127,reads=18"
 globals().update(knobs("QKV_KNOBS", {"bar1": "BAR1_AFTER", "dma0": "DMA_FIRST", "dmae": "DMA_EVERY", "bar2": "BAR2_AFTER", "next": "NEXT_FROM",
                                      "reads": "READ_UNTIL"}))
-SLOTS = Slots(A_SLOTS, A_BYTES, B_SLOTS, B_BYTES, read_slot_from(S1))
+LAYOUT = slot_layout(A_SLOTS, A_BYTES, B_BYTES, S1)
 
 
 def acc(mi, ni):
@@ -144,10 +144,9 @@ def vread_inc():
 def main():
     # --inject-raw-race: the second barrier's wait leaves the weights of tile t+1 in flight
     lines = finish(Gen(STAMPS).build(), SAVE_M0, (f"s_waitcnt vmcnt({INFLIGHT})", f"s_waitcnt vmcnt({INFLIGHT + NB})"))
-    stats = check_wait_coverage(lines, SLOTS)
-    check_operand_waits(lines)
-    emit("gen_gemm_asm_qkv.py", "gemm_bf16_kernel_qkv", "gemm_qkv_192x384", STAMPS or os.environ.get("QKV_KNOBS"), lines, stats,
-         {"gemm_qkv_192x384_clobbers.inc": clobbers_inc("gen_gemm_asm_qkv.py", NV, 256, SAVE_M0), "gemm_qkv_192x384_vread.inc": vread_inc()})
+    stats = check_wait_coverage(lines, LAYOUT)
+    emit("gen_gemm_asm_qkv.py", "main loop of gemm_bf16_kernel_qkv (gemm.hip)", "gemm_qkv_192x384", STAMPS or os.environ.get("QKV_KNOBS"), lines, stats,
+         {"gemm_qkv_192x384_clobbers.inc": clobbers_inc("gen_gemm_asm_qkv.py", NV, 256, range(36, SAVE_M0 + 1)), "gemm_qkv_192x384_vread.inc": vread_inc()})
 
 
 if __name__ == "__main__":

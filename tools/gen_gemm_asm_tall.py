@@ -24,7 +24,7 @@ static LDS and the epilogue reuses the slots):
       MFMA 169..192  the reads of tile t+1's k-step-0 B fragments and first A fragments; the first ATAIL pieces of A(t+2)
     A(t+1) is always issued before B(t+2), so the counted wait leaves exactly the 8 newer weight pieces in flight. Two barriers and
     no VALU instruction per K-tile; the loop body is two tiles long, left after either. Every wait is derived from the issue order;
-    check_wait_coverage() (tools/gemm_asm_common.py, shared with the 192 x 256 and 192 x 384 streams) proves both hazards and
+    check_wait_coverage() (tools/asm_common.py, shared with every proven stream) proves both hazards and the operand waits,
     check_products() the operand of every MFMA on the emitted text before it is written.
   * one accumulator chain per output element, K ascending, A = activations, B = weights: bit-identical to the 192 x 256 stream and to
     the 192 x 128 ring kernel on the same operands.
@@ -42,7 +42,7 @@ import os
 import re
 import sys
 
-from gemm_asm_common import Slots, Stream, WaitCoverageError, check_wait_coverage, clobbers_inc, emit, finish, knobs, read_slot_from, vr, walk
+from asm_common import Stream, WaitCoverageError, check_wait_coverage, clobbers_inc, emit, finish, knobs, read_slot_from, slot_layout, vr, walk
 
 MI, NI = 12, 8
 MI_AGPR = 8                   # row fragments 0..7 accumulate in AGPRs, 8..11 in VGPRs
@@ -74,7 +74,7 @@ globals().update(knobs("TALL_KNOBS", {"ring": "RING", "b1": "B1_FIRST", "b1e": "
                                       "next": "NEXT_FIRST", "nexte": "NEXT_EVERY", "tdma0": "TDMA_FIRST", "tdmae": "TDMA_EVERY"}))
 assert RING in (3, 4) and 0 <= ATAIL <= NA
 read_slot = read_slot_from(S1)
-SLOTS = Slots(A_SLOTS, A_BYTES, B_SLOTS, B_BYTES, read_slot)
+LAYOUT = slot_layout(A_SLOTS, A_BYTES, B_BYTES, S1)
 
 
 def acc(mi, ni):
@@ -236,24 +236,17 @@ class Gen(Stream):
 
 def check_products(lines, iterations=3):
     """Every MFMA multiplies what it should: walks prologue + loop bodies tracking, per fragment register, which fragment the last
-    ds_read put there and whether that read has returned (reads return in order; counted lgkmcnt waits). An MFMA on accumulator
-    (mi, ni) must find A fragment mi and B fragment ni of the SAME k-step and slot, returned, and each accumulator must see
-    (slot, k-step) = (0,0) (0,1) (1,0) (1,1) (0,0) ...: one chain per output element, K ascending. A read that overwrites a register an
-    earlier MFMA still has to read cannot happen: MFMAs read their operands at issue, and the stream is in order."""
+    ds_read put there (that it has returned is check_wait_coverage's register rule). An MFMA on accumulator (mi, ni) must find A
+    fragment mi and B fragment ni of the SAME k-step and slot, and each accumulator must see (slot, k-step) = (0,0) (0,1) (1,0) (1,1)
+    (0,0) ...: one chain per output element, K ascending."""
     seq = walk(lines, iterations)
-    held, out, chain = {}, [], {}
+    held, chain = {}, {}
     n_mfma = 0
     for pos, ins in enumerate(seq):
         mm = re.match(r"ds_read_b128 v\[(\d+):\d+\], (\S+) offset:(\d+)", ins)
         if mm:
             kind, slot, ks = read_slot(mm.group(2))
             held[int(mm.group(1))] = (kind, slot, ks, int(mm.group(3)) // 2048)
-            out.append(int(mm.group(1)))
-            continue
-        ml = re.search(r"lgkmcnt\((\d+)\)", ins) if ins.startswith("s_waitcnt") else None
-        if ml:
-            keep = int(ml.group(1))
-            out = out[len(out) - keep:] if keep < len(out) else out
             continue
         mm = re.match(r"v_mfma_f32_16x16x32_bf16 ([av])\[(\d+):\d+\], v\[(\d+):\d+\], v\[(\d+):\d+\], ([av])\[(\d+):\d+\]", ins)
         if mm:
@@ -263,8 +256,6 @@ def check_products(lines, iterations=3):
             ra, rb = int(mm.group(3)), int(mm.group(4))
             if (mm.group(1), mm.group(2)) != (mm.group(5), mm.group(6)) or not 0 <= mi < MI:
                 raise WaitCoverageError(f"MFMA at {pos} does not accumulate in place: {ins}")
-            if ra in out or rb in out:
-                raise WaitCoverageError(f"MFMA at {pos} reads a fragment whose ds_read is outstanding: {ins}")
             a, b = held.get(ra), held.get(rb)
             if not a or not b or a[0] != "A" or b[0] != "B" or a[3] != mi or b[3] != ni or a[1:3] != b[1:3]:
                 raise WaitCoverageError(f"MFMA at {pos} on accumulator ({mi}, {ni}) multiplies {a} by {b}")
@@ -304,10 +295,10 @@ def dump_inc():
 def main():
     # --inject-raw-race: the second barrier's wait leaves the activations of tile t+1 in flight
     lines = finish(Gen(STAMPS).build(), SAVE_M0, (f"s_waitcnt vmcnt({NB}) lgkmcnt(0)", f"s_waitcnt vmcnt({NB + 1}) lgkmcnt(0)"))
-    stats = check_wait_coverage(lines, SLOTS)
+    stats = check_wait_coverage(lines, LAYOUT)
     check_products(lines)
-    emit("gen_gemm_asm_tall.py", "gemm_bf16_kernel_tall", "gemm_tall_384x256", STAMPS or os.environ.get("TALL_KNOBS"), lines, stats,
-         {"gemm_tall_384x256_clobbers.inc": clobbers_inc("gen_gemm_asm_tall.py", NV, 256, SAVE_M0), "gemm_tall_384x256_dump.inc": dump_inc()})
+    emit("gen_gemm_asm_tall.py", "main loop of gemm_bf16_kernel_tall (gemm.hip)", "gemm_tall_384x256", STAMPS or os.environ.get("TALL_KNOBS"), lines, stats,
+         {"gemm_tall_384x256_clobbers.inc": clobbers_inc("gen_gemm_asm_tall.py", NV, 256, range(36, SAVE_M0 + 1)), "gemm_tall_384x256_dump.inc": dump_inc()})
 
 
 if __name__ == "__main__":
