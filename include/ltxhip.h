@@ -1273,6 +1273,59 @@ int ltx_op_geglu(ltx_ctx* ctx, const uint16_t* gu, int rows, int I, uint16_t* ou
 /* out [rows][D] = bf16(table[ids[row]] * bf16(sqrt(D))); ids are clamped to [0, vocab) */
 int ltx_op_gemma_embed(ltx_ctx* ctx, const int32_t* ids, const uint16_t* table, int rows, int D, int vocab, uint16_t* out);
 
+/* Test seams of the helper passes around the matrix cores: guidance, scheduler, VAE, latent upscaler and connector. DEVICE pointers
+ * throughout; each call is one launch on the context's stream and returns without waiting. A null required pointer or an empty shape
+ * is invalidConfiguration. No model has to be loaded, and no product path goes through these.
+ * stats[b] = {mean, population variance} of the n_per_batch f32 values of segment b (two passes: the mean, then the deviations) */
+int ltx_op_mean_var(ltx_ctx* ctx, const float* x, long n_per_batch, int B, float* stats);
+/* cfg [B][n_per_batch] f32, in place: cfg = phi * cfg * (std_cond / std_cfg) + (1 - phi) * cfg, std = sqrt(var + 1e-8) of the
+ * ltx_op_mean_var pairs stats_cfg / stats_cond [B][2] (LatentUtils.swift:164-183) */
+int ltx_op_guidance_rescale(ltx_ctx* ctx, float* cfg, const float* stats_cfg, const float* stats_cond, float phi, long n_per_batch, int B);
+/* x [BC][n_per_chan] f32, in place: y = (x - mean) / (sqrt(var) + 1e-8) * sqrt(var_ref) + mean_ref per channel;
+ * x = factor >= 1 ? y : factor * y + (1 - factor) * x (LatentUtils.swift:201-227). stats_x / stats_ref [BC][2] {mean, var}. */
+int ltx_op_adain(ltx_ctx* ctx, float* x, const float* stats_x, const float* stats_ref, float factor, long n_per_chan, int BC);
+/* GroupNorm over channels-last x [P][C] f32 with G groups of C / G adjacent channels (SpatialUpscaler.swift:14-58):
+ * stats[g] = {mean, 1 / sqrt(population variance + eps)} over all positions of the group's channels */
+int ltx_op_groupnorm_stats(ltx_ctx* ctx, const float* x, long P, int C, int G, float eps, float* stats);
+/* y = (x - mean_g) * rstd_g * w[c] + b[c]; resid [P][C] f32 (or NULL) is added, then SiLU when act_silu. Written as f32 [P][C]
+ * and / or bf16 [P][C] (either may be NULL, not both); out_f32 may alias resid. */
+int ltx_op_groupnorm_apply(ltx_ctx* ctx, const float* x, const float* stats, const float* w, const float* b, const float* resid,
+                           int act_silu, float* out_f32, uint16_t* out_bf16, long P, int C, int G);
+/* x [P][C] f32 -> out [P][C] bf16 = SiLU(x / sqrt(mean_c(x^2) + 1e-8) * scale[c] + shift[c]); scale and shift [C] f32 or both NULL
+ * (scale 1, shift 0). scale already holds the + 1. C % 4 == 0, C <= 2048 (VideoDecoder.swift:29-32, :118-127). */
+int ltx_op_pixelnorm_silu(ltx_ctx* ctx, const float* x, const float* scale, const float* shift, uint16_t* out, long P, int C);
+/* latent element (c, p) at [c * chan_stride + p], f32 (chan_stride >= P: a temporal tile is a view of a longer latent); noise, when
+ * not NULL, in the same layout: v = noise * noise_scale + (1 - noise_scale) * latent. out [P][C] bf16 = v * std[c] + mean[c]
+ * (VideoDecoder.swift:366-381). */
+int ltx_op_vae_prepare(ltx_ctx* ctx, const float* latent, long chan_stride, const float* noise, float noise_scale, const float* mean,
+                       const float* std_, uint16_t* out, int C, long P);
+/* x [P][C] f32 -> out [C][P] f32 = (x - mean[c]) / std[c] (SpatialUpscaler.swift:352-379) */
+int ltx_op_upscaler_finish(ltx_ctx* ctx, const float* x, const float* mean, const float* std_, float* out, long P, int C);
+/* r, nx [n_frames][frame_elems] f32; r[i] = r[i] * (1 - i / n_frames) + nx[i] * (i / n_frames), in place (VideoDecoder.swift:561-592) */
+int ltx_op_blend_frames(ltx_ctx* ctx, float* r, const float* nx, int n_frames, long frame_elems);
+/* latent [B][C][T] f32 -> tokens [B][T][C] bf16 (LatentUtils.swift:20-34), and tokens [B][T][C] f32 -> latent [B][C][T] f32 (:42-54) */
+int ltx_op_patchify_bf16(ltx_ctx* ctx, const float* latent, uint16_t* tokens, int B, int C, int T);
+int ltx_op_unpatchify_f32(ltx_ctx* ctx, const float* tokens, float* latent, int B, int C, int T);
+/* latent, velocity [n] f32: den = x - sigma * v; x = sigma_next > 0 ? den + sigma_next * (x - den) / sigma : den, in place
+ * (LTXScheduler.swift:305-327). skip_hw > 0: the latent is [C][frames][skip_hw] and frame 0 of every channel is left as it is. */
+int ltx_op_euler_step(ltx_ctx* ctx, float* latent, const float* velocity, float sigma, float sigma_next, long n, int skip_hw, int frames);
+/* latent [C][F][HW] f32: frame 0 of every channel = cond [C][HW], or cond + (scale * noise) * sigma2 with noise [C][HW] (three
+ * separately rounded f32 operations); frames >= 1 are not touched (LTXPipeline.swift:2092-2094, :2225-2229) */
+int ltx_op_set_frame0(ltx_ctx* ctx, float* latent, const float* cond, const float* noise, float scale, float sigma2, int C, int F, int HW);
+/* mod [B][L][J][D] = tables [L][J][D] + ada [B][J][D], f32 (LTXTransformerBlock.swift:163-185) */
+int ltx_op_make_mod(ltx_ctx* ctx, const float* tables, const float* ada, float* mod, int B, int L, int J, int D);
+/* The connector's feature statistics (LTXTextEncoder.swift:62-122). hidden [states][B][T][D] bf16, mask [B][T] int32; the valid
+ * tokens of row b are its last n_b (first n_b with padding_right), n_b = the number of non-zero mask entries. stats[(l*B + b)*2] =
+ * {sum over valid tokens / (n_b * D + eps), (max - min over valid tokens) + eps}. partials: scratch of
+ * ltx_fe_stats_partials_floats(states, B, T, D) floats (0 for an empty shape). D % 8 == 0. */
+long ltx_fe_stats_partials_floats(int states, int B, int T, int D);
+int ltx_op_fe_stats(ltx_ctx* ctx, const uint16_t* hidden, const int32_t* mask, int states, int B, int T, int D, int padding_right,
+                    float eps, float* partials, float* stats);
+/* out [B][T][D * states] bf16: out[b][t][d * states + l] = bf16(8 * (x - mean) / (range + eps)) with the ltx_op_fe_stats pair of plane
+ * (l, b) for a valid token, zero for a padded one */
+int ltx_op_fe_norm_concat(ltx_ctx* ctx, const uint16_t* hidden, const int32_t* mask, const float* stats, int states, int B, int T, int D,
+                          int padding_right, float eps, uint16_t* out);
+
 #ifdef __cplusplus
 }
 #endif

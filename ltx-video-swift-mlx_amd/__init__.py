@@ -440,6 +440,16 @@ def _ptr(t):
     return t.data_ptr()
 
 
+def _dptr(t):
+    """Address of a device tensor's first element (None -> NULL); the tensor may be a view at an offset into a longer one."""
+    return None if t is None else t.data_ptr()
+
+
+def fe_stats_partials_floats(states, B, T, D):
+    """f32 elements of scratch that ``Context.op_fe_stats`` needs for this shape."""
+    return int(lib.ltx_fe_stats_partials_floats(states, B, T, D))
+
+
 class Context:
     """Owns an ``ltx_ctx``. All ``*_dev`` methods take torch tensors resident on this context's GPU."""
 
@@ -931,6 +941,58 @@ class Context:
     def op_gemma_embed(self, ids, table, out):
         vocab, D = table.shape
         self._ck(lib.ltx_op_gemma_embed(self._h, _ptr(ids), _ptr(table), ids.numel(), D, vocab, _ptr(out)))
+
+    # ---- helper passes (include/ltxhip.h, "Test seams of the helper passes"): device tensors, sizes given explicitly, so that a
+    # tensor may be longer than the pass's extent (guard elements behind it) or a view into a longer one (vae_prepare's chan_stride) ----
+    def op_mean_var(self, x, n_per_batch, B, stats):
+        self._ck(lib.ltx_op_mean_var(self._h, _dptr(x), n_per_batch, B, _dptr(stats)))
+
+    def op_guidance_rescale(self, cfg, stats_cfg, stats_cond, phi, n_per_batch, B):
+        self._ck(lib.ltx_op_guidance_rescale(self._h, _dptr(cfg), _dptr(stats_cfg), _dptr(stats_cond), phi, n_per_batch, B))
+
+    def op_adain(self, x, stats_x, stats_ref, factor, n_per_chan, BC):
+        self._ck(lib.ltx_op_adain(self._h, _dptr(x), _dptr(stats_x), _dptr(stats_ref), factor, n_per_chan, BC))
+
+    def op_groupnorm_stats(self, x, P, C, G, eps, stats):
+        self._ck(lib.ltx_op_groupnorm_stats(self._h, _dptr(x), P, C, G, eps, _dptr(stats)))
+
+    def op_groupnorm_apply(self, x, stats, w, b, P, C, G, resid=None, act_silu=False, out_f32=None, out_bf16=None):
+        self._ck(lib.ltx_op_groupnorm_apply(self._h, _dptr(x), _dptr(stats), _dptr(w), _dptr(b), _dptr(resid), int(act_silu), _dptr(out_f32),
+                                            _dptr(out_bf16), P, C, G))
+
+    def op_pixelnorm_silu(self, x, out, P, C, scale=None, shift=None):
+        self._ck(lib.ltx_op_pixelnorm_silu(self._h, _dptr(x), _dptr(scale), _dptr(shift), _dptr(out), P, C))
+
+    def op_vae_prepare(self, latent, chan_stride, mean, std, out, C, P, noise=None, noise_scale=0.0):
+        self._ck(lib.ltx_op_vae_prepare(self._h, _dptr(latent), chan_stride, _dptr(noise), noise_scale, _dptr(mean), _dptr(std), _dptr(out), C, P))
+
+    def op_upscaler_finish(self, x, mean, std, out, P, C):
+        self._ck(lib.ltx_op_upscaler_finish(self._h, _dptr(x), _dptr(mean), _dptr(std), _dptr(out), P, C))
+
+    def op_blend_frames(self, r, nx, n_frames, frame_elems):
+        self._ck(lib.ltx_op_blend_frames(self._h, _dptr(r), _dptr(nx), n_frames, frame_elems))
+
+    def op_patchify_bf16(self, latent, tokens, B, C, T):
+        self._ck(lib.ltx_op_patchify_bf16(self._h, _dptr(latent), _dptr(tokens), B, C, T))
+
+    def op_unpatchify_f32(self, tokens, latent, B, C, T):
+        self._ck(lib.ltx_op_unpatchify_f32(self._h, _dptr(tokens), _dptr(latent), B, C, T))
+
+    def op_euler_step(self, latent, velocity, sigma, sigma_next, n, skip_hw=0, frames=1):
+        self._ck(lib.ltx_op_euler_step(self._h, _dptr(latent), _dptr(velocity), sigma, sigma_next, n, skip_hw, frames))
+
+    def op_set_frame0(self, latent, cond, C, F, HW, noise=None, scale=0.0, sigma2=0.0):
+        self._ck(lib.ltx_op_set_frame0(self._h, _dptr(latent), _dptr(cond), _dptr(noise), scale, sigma2, C, F, HW))
+
+    def op_make_mod(self, tables, ada, mod, B, L, J, D):
+        self._ck(lib.ltx_op_make_mod(self._h, _dptr(tables), _dptr(ada), _dptr(mod), B, L, J, D))
+
+    def op_fe_stats(self, hidden, mask, states, B, T, D, partials, stats, padding_right=False, eps=1e-6):
+        """``ltx_op_fe_stats``: partials holds at least ``fe_stats_partials_floats(states, B, T, D)`` f32."""
+        self._ck(lib.ltx_op_fe_stats(self._h, _dptr(hidden), _dptr(mask), states, B, T, D, int(padding_right), eps, _dptr(partials), _dptr(stats)))
+
+    def op_fe_norm_concat(self, hidden, mask, stats, states, B, T, D, out, padding_right=False, eps=1e-6):
+        self._ck(lib.ltx_op_fe_norm_concat(self._h, _dptr(hidden), _dptr(mask), _dptr(stats), states, B, T, D, int(padding_right), eps, _dptr(out)))
 
     def upscaler_load(self, path):
         self._ck(lib.ltx_upscaler_load(self._h, str(path).encode()))

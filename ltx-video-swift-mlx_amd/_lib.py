@@ -405,6 +405,23 @@ SIGNATURES = {
     "ltx_op_gemma_rope_tables": (_i, [_vp, _i, _f, _vp, _vp]),
     "ltx_op_geglu": (_i, [_vp, _vp, _i, _i, _vp]),
     "ltx_op_gemma_embed": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
+    "ltx_op_mean_var": (_i, [_vp, _vp, _l, _i, _vp]),
+    "ltx_op_guidance_rescale": (_i, [_vp, _vp, _vp, _vp, _f, _l, _i]),
+    "ltx_op_adain": (_i, [_vp, _vp, _vp, _vp, _f, _l, _i]),
+    "ltx_op_groupnorm_stats": (_i, [_vp, _vp, _l, _i, _i, _f, _vp]),
+    "ltx_op_groupnorm_apply": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _l, _i, _i]),
+    "ltx_op_pixelnorm_silu": (_i, [_vp, _vp, _vp, _vp, _vp, _l, _i]),
+    "ltx_op_vae_prepare": (_i, [_vp, _vp, _l, _vp, _f, _vp, _vp, _vp, _i, _l]),
+    "ltx_op_upscaler_finish": (_i, [_vp, _vp, _vp, _vp, _vp, _l, _i]),
+    "ltx_op_blend_frames": (_i, [_vp, _vp, _vp, _i, _l]),
+    "ltx_op_patchify_bf16": (_i, [_vp, _vp, _vp, _i, _i, _i]),
+    "ltx_op_unpatchify_f32": (_i, [_vp, _vp, _vp, _i, _i, _i]),
+    "ltx_op_euler_step": (_i, [_vp, _vp, _vp, _f, _f, _l, _i, _i]),
+    "ltx_op_set_frame0": (_i, [_vp, _vp, _vp, _vp, _f, _f, _i, _i, _i]),
+    "ltx_op_make_mod": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i]),
+    "ltx_fe_stats_partials_floats": (_l, [_i, _i, _i, _i]),
+    "ltx_op_fe_stats": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp]),
+    "ltx_op_fe_norm_concat": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp]),
     "ltx_op_fill_normal_bf16": (_i, [_vp, _vp, _l, _u64, _f, _f]),
     "ltx_op_fill_normal_f32": (_i, [_vp, _vp, _l, _u64, _f, _f]),
 }

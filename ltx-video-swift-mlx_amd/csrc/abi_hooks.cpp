@@ -560,6 +560,133 @@ int ltx_op_qknorm_rope_pair(ltx_ctx* ctx, const void* x0, const float* w0, uint1
     });
 }
 
+// ---- helper passes (elementwise.h: the VAE, upscaler, guidance, scheduler and connector passes around the matrix cores) ----
+// Each hook checks its pointers and sizes and makes the one launch on the context's stream; shapes are the launcher's (elementwise.h).
+int ltx_op_mean_var(ltx_ctx* ctx, const float* x, long n_per_batch, int B, float* stats) {
+    return with_ctx(ctx, [&] {
+        LTX_REQUIRE(x && stats && n_per_batch >= 1 && B >= 1, "ltx_op_mean_var: null argument or empty shape");
+        launch_mean_var(x, n_per_batch, B, stats, ctx->stream);
+    });
+}
+
+int ltx_op_guidance_rescale(ltx_ctx* ctx, float* cfg, const float* stats_cfg, const float* stats_cond, float phi, long n_per_batch, int B) {
+    return with_ctx(ctx, [&] {
+        LTX_REQUIRE(cfg && stats_cfg && stats_cond && n_per_batch >= 1 && B >= 1, "ltx_op_guidance_rescale: null argument or empty shape");
+        launch_guidance_rescale(cfg, stats_cfg, stats_cond, phi, n_per_batch, B, ctx->stream);
+    });
+}
+
+int ltx_op_adain(ltx_ctx* ctx, float* x, const float* stats_x, const float* stats_ref, float factor, long n_per_chan, int BC) {
+    return with_ctx(ctx, [&] {
+        LTX_REQUIRE(x && stats_x && stats_ref && n_per_chan >= 1 && BC >= 1, "ltx_op_adain: null argument or empty shape");
+        launch_adain(x, stats_x, stats_ref, factor, n_per_chan, BC, ctx->stream);
+    });
+}
+
+int ltx_op_groupnorm_stats(ltx_ctx* ctx, const float* x, long P, int C, int G, float eps, float* stats) {
+    return with_ctx(ctx, [&] {
+        LTX_REQUIRE(x && stats && P >= 1 && C >= 1 && G >= 1, "ltx_op_groupnorm_stats: null argument or empty shape");
+        launch_groupnorm_stats(x, P, C, G, eps, stats, ctx->stream);
+    });
+}
+
+int ltx_op_groupnorm_apply(ltx_ctx* ctx, const float* x, const float* stats, const float* w, const float* b, const float* resid,
+                           int act_silu, float* out_f32, uint16_t* out_bf16, long P, int C, int G) {
+    return with_ctx(ctx, [&] {
+        LTX_REQUIRE(x && stats && w && b && (out_f32 || out_bf16), "ltx_op_groupnorm_apply: null argument");
+        LTX_REQUIRE(P >= 1 && C >= 1 && G >= 1 && C % G == 0, "ltx_op_groupnorm_apply: P=%ld C=%d G=%d", P, C, G);
+        launch_groupnorm_apply(x, stats, w, b, resid, act_silu, out_f32, out_bf16, P, C, G, ctx->stream);
+    });
+}
+
+int ltx_op_pixelnorm_silu(ltx_ctx* ctx, const float* x, const float* scale, const float* shift, uint16_t* out, long P, int C) {
+    return with_ctx(ctx, [&] {
+        LTX_REQUIRE(x && out && P >= 1 && C >= 1, "ltx_op_pixelnorm_silu: null argument or empty shape");
+        launch_pixelnorm_silu(x, scale, shift, out, P, C, ctx->stream);
+    });
+}
+
+int ltx_op_vae_prepare(ltx_ctx* ctx, const float* latent, long chan_stride, const float* noise, float noise_scale, const float* mean,
+                       const float* std_, uint16_t* out, int C, long P) {
+    return with_ctx(ctx, [&] {
+        LTX_REQUIRE(latent && mean && std_ && out, "ltx_op_vae_prepare: null argument");
+        LTX_REQUIRE(C >= 1 && P >= 1 && chan_stride >= P, "ltx_op_vae_prepare: C=%d P=%ld chan_stride=%ld", C, P, chan_stride);
+        launch_vae_prepare(latent, chan_stride, noise, noise_scale, mean, std_, out, C, P, ctx->stream);
+    });
+}
+
+int ltx_op_upscaler_finish(ltx_ctx* ctx, const float* x, const float* mean, const float* std_, float* out, long P, int C) {
+    return with_ctx(ctx, [&] {
+        LTX_REQUIRE(x && mean && std_ && out && P >= 1 && C >= 1, "ltx_op_upscaler_finish: null argument or empty shape");
+        launch_upscaler_finish(x, mean, std_, out, P, C, ctx->stream);
+    });
+}
+
+int ltx_op_blend_frames(ltx_ctx* ctx, float* r, const float* nx, int n_frames, long frame_elems) {
+    return with_ctx(ctx, [&] {
+        LTX_REQUIRE(r && nx && n_frames >= 1 && frame_elems >= 1, "ltx_op_blend_frames: null argument or empty shape");
+        launch_blend_frames(r, nx, n_frames, frame_elems, ctx->stream);
+    });
+}
+
+int ltx_op_patchify_bf16(ltx_ctx* ctx, const float* latent, uint16_t* tokens, int B, int C, int T) {
+    return with_ctx(ctx, [&] {
+        LTX_REQUIRE(latent && tokens && B >= 1 && C >= 1 && T >= 1, "ltx_op_patchify_bf16: null argument or empty shape");
+        launch_patchify_bf16(latent, tokens, B, C, T, ctx->stream);
+    });
+}
+
+int ltx_op_unpatchify_f32(ltx_ctx* ctx, const float* tokens, float* latent, int B, int C, int T) {
+    return with_ctx(ctx, [&] {
+        LTX_REQUIRE(tokens && latent && B >= 1 && C >= 1 && T >= 1, "ltx_op_unpatchify_f32: null argument or empty shape");
+        launch_unpatchify_f32(tokens, latent, B, C, T, ctx->stream);
+    });
+}
+
+int ltx_op_euler_step(ltx_ctx* ctx, float* latent, const float* velocity, float sigma, float sigma_next, long n, int skip_hw, int frames) {
+    return with_ctx(ctx, [&] {
+        LTX_REQUIRE(latent && velocity && n >= 1 && skip_hw >= 0, "ltx_op_euler_step: null argument or empty shape");
+        launch_euler_step(latent, velocity, sigma, sigma_next, n, ctx->stream, skip_hw, frames);
+    });
+}
+
+int ltx_op_set_frame0(ltx_ctx* ctx, float* latent, const float* cond, const float* noise, float scale, float sigma2, int C, int F, int HW) {
+    return with_ctx(ctx, [&] {
+        LTX_REQUIRE(latent && cond && C >= 1 && F >= 1 && HW >= 1, "ltx_op_set_frame0: null argument or empty shape");
+        launch_set_frame0(latent, cond, noise, scale, sigma2, C, F, HW, ctx->stream);
+    });
+}
+
+int ltx_op_make_mod(ltx_ctx* ctx, const float* tables, const float* ada, float* mod, int B, int L, int J, int D) {
+    return with_ctx(ctx, [&] {
+        LTX_REQUIRE(tables && ada && mod && B >= 1 && L >= 1 && J >= 1 && D >= 1, "ltx_op_make_mod: null argument or empty shape");
+        launch_make_mod(tables, ada, mod, B, L, J, D, ctx->stream);
+    });
+}
+
+long ltx_fe_stats_partials_floats(int states, int B, int T, int D) {
+    if (states < 1 || B < 1 || T < 1 || D < 1) return 0;
+    return fe_stats_partials_floats(states, B, T, D);
+}
+
+int ltx_op_fe_stats(ltx_ctx* ctx, const uint16_t* hidden, const int32_t* mask, int states, int B, int T, int D, int padding_right,
+                    float eps, float* partials, float* stats) {
+    return with_ctx(ctx, [&] {
+        LTX_REQUIRE(hidden && mask && partials && stats, "ltx_op_fe_stats: null argument");
+        LTX_REQUIRE(states >= 1 && B >= 1 && T >= 1 && D >= 1, "ltx_op_fe_stats: states=%d B=%d T=%d D=%d", states, B, T, D);
+        launch_fe_stats(hidden, mask, states, B, T, D, padding_right, eps, partials, stats, ctx->stream);
+    });
+}
+
+int ltx_op_fe_norm_concat(ltx_ctx* ctx, const uint16_t* hidden, const int32_t* mask, const float* stats, int states, int B, int T, int D,
+                          int padding_right, float eps, uint16_t* out) {
+    return with_ctx(ctx, [&] {
+        LTX_REQUIRE(hidden && mask && stats && out, "ltx_op_fe_norm_concat: null argument");
+        LTX_REQUIRE(states >= 1 && B >= 1 && T >= 1 && D >= 1, "ltx_op_fe_norm_concat: states=%d B=%d T=%d D=%d", states, B, T, D);
+        launch_fe_norm_concat(hidden, mask, stats, states, B, T, D, padding_right, eps, out, ctx->stream);
+    });
+}
+
 // ---- audio convolutions ----
 int ltx_op_conv1d(ltx_ctx* ctx, const uint16_t* x, int L, int Cin, const uint16_t* w, const float* bias, int Cout, int k, int dilation,
                   int tile, const float* resid, int f32_act, int transposed, float* out_f32, int bf16_act, float slope,

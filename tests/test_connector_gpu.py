@@ -59,7 +59,9 @@ def _cos(a, b):
     return float((a * b).sum() / (np.linalg.norm(a) * np.linalg.norm(b)))
 
 
-@pytest.mark.parametrize("B,T,valid", [(1, 16, [11]), (2, 32, [32, 5]), (1, 64, [1])])
+# T * DIM <= 16384 is one chunk of the feature statistics (fe_stats); T = 96 is one and a half, T = 200 four: the cross-chunk reduction,
+# a ragged last chunk, and (valid = [200, 1]) chunks of a row that hold no valid token at all
+@pytest.mark.parametrize("B,T,valid", [(1, 16, [11]), (2, 32, [32, 5]), (1, 64, [1]), (1, 96, [96]), (2, 200, [200, 1]), (1, 200, [137])])
 def test_connector_parity(gpu_ctx, oracle, conn, B, T, valid):
     w = conn
     rng = np.random.default_rng(B * 100 + T)
@@ -96,18 +98,26 @@ def test_connector_host_entry_and_mask(gpu_ctx, oracle, conn):
     assert _rel(got, ref) <= 2e-2
 
 
-def test_connector_right_padding_follows_reference(gpu_ctx, oracle, conn):
-    """With right padding the reference's register plan keeps padded rows in the tail (LTXTextEncoder.swift:440-462 assumes
-    left padding); the port reproduces that behaviour instead of 'fixing' it."""
-    w = conn
+def _right_padding_case(gpu_ctx, oracle, w, T, n_valid):
     rng = np.random.default_rng(4)
-    B, T = 1, 16
+    B = 1
     hs = oracle.bf16_round(rng.standard_normal((STATES, B, T, DIM)).astype(np.float32))
     am = np.zeros((B, T), np.int32)
-    am[0, :6] = 1
+    am[0, :n_valid] = 1
     ref, _ = oracle.connector_encode(w, hs, am, padding_side="right", heads=HEADS, layers=LAYERS)
     got, _, _, _ = _run(gpu_ctx, oracle, hs, am, padding_right=True)
     assert _rel(got, ref) <= 2e-2
+
+
+def test_connector_right_padding_follows_reference(gpu_ctx, oracle, conn):
+    """With right padding the reference's register plan keeps padded rows in the tail (LTXTextEncoder.swift:440-462 assumes
+    left padding); the port reproduces that behaviour instead of 'fixing' it."""
+    _right_padding_case(gpu_ctx, oracle, conn, 16, 6)
+
+
+def test_connector_right_padding_over_two_chunks(gpu_ctx, oracle, conn):
+    """The same with T * DIM = 1.5 chunks of the feature statistics: the valid tokens fill chunk 0 and stop short of chunk 1."""
+    _right_padding_case(gpu_ctx, oracle, conn, 96, 50)
 
 
 def test_connector_errors(ltx, gpu_ctx, oracle, conn):
