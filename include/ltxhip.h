@@ -1258,6 +1258,13 @@ int ltx_text_av_encode(ltx_ctx* ctx, const int32_t* token_ids, const int32_t* at
  * or NaN there would come out as NaN. */
 int ltx_op_attention_causal(ltx_ctx* ctx, const uint16_t* Q, const uint16_t* K, const uint16_t* Vt, long ldvt, const int32_t* key_start,
                             int B, int Hq, int Hkv, int T, int head_dim, float scale, uint16_t* O);
+/* The same launch with every stride of the launcher (elements): row strides ldq / ldk / ldo, Vt row stride ldvt and the four batch
+ * strides, so an operand may be a view into a longer buffer - the encoder reads Q and K out of one fused [B*T][(Hq+Hkv)*256] row buffer
+ * and Vt out of a workspace of row stride roundup(T, 64). The Vt columns from T to ldvt-1 are read (those below roundup(T, 64)) and must be finite.
+ * ltx_op_attention_causal is this call with dense operands. No product path calls it. */
+int ltx_op_attention_causal_ld(ltx_ctx* ctx, const uint16_t* Q, long ldq, long q_bstride, const uint16_t* K, long ldk, long k_bstride,
+                               const uint16_t* Vt, long ldvt, long vt_bstride, const int32_t* key_start, int B, int Hq, int Hkv, int T,
+                               int head_dim, float scale, uint16_t* O, long ldo, long o_bstride);
 /* r, x, h, n dense [rows][D] bf16; w, w2 [D] f32 (the stored weights; the kernel forms bf16(1 + w)). x NULL: h = norm(r); else
  * h = x + norm(r). w2 and n together: n = norm2(h) too. h NULL (with w2, n): only n is written. */
 int ltx_op_gemma_norm(ltx_ctx* ctx, const uint16_t* r, const float* w, const uint16_t* x, const float* w2, int rows, int D, float eps,

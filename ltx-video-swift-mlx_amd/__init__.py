@@ -921,6 +921,13 @@ class Context:
         self._ck(lib.ltx_op_attention_causal(self._h, _ptr(Q), _ptr(K), _ptr(Vt), Vt.shape[2], _ptr(key_start), B, Dq // head_dim,
                                              K.shape[2] // head_dim, T, head_dim, scale, _ptr(O)))
 
+    def op_attention_causal_ld(self, Q, ldq, q_bstride, K, ldk, k_bstride, Vt, ldvt, vt_bstride, O, ldo, o_bstride, B, Hq, Hkv, T, scale,
+                               key_start=None, head_dim=256):
+        """``ltx_op_attention_causal_ld``: the same launch with explicit strides in elements. Q / K / Vt / O are bf16 device tensors of
+        which only the first element's address is taken, so each may be a view into a longer buffer (not contiguous)."""
+        self._ck(lib.ltx_op_attention_causal_ld(self._h, Q.data_ptr(), ldq, q_bstride, K.data_ptr(), ldk, k_bstride, Vt.data_ptr(), ldvt,
+                                                vt_bstride, _ptr(key_start), B, Hq, Hkv, T, head_dim, scale, O.data_ptr(), ldo, o_bstride))
+
     def op_gemma_norm(self, r, w, h=None, x=None, w2=None, n=None, eps=1e-6):
         """``ltx_op_gemma_norm``: r / x / h / n [rows,D] bf16, w / w2 [D] f32."""
         rows, D = r.shape

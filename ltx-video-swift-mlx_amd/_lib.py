@@ -400,6 +400,7 @@ SIGNATURES = {
     "ltx_text_encode_dev": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp]),
     "ltx_text_encode": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp]),
     "ltx_op_attention_causal": (_i, [_vp, _vp, _vp, _vp, _l, _vp, _i, _i, _i, _i, _i, _f, _vp]),
+    "ltx_op_attention_causal_ld": (_i, [_vp, _vp, _l, _l, _vp, _l, _l, _vp, _l, _l, _vp, _i, _i, _i, _i, _i, _f, _vp, _l, _l]),
     "ltx_op_gemma_norm": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _f, _vp, _vp]),
     "ltx_op_gemma_qknorm_rope": (_i, [_vp, _vp, _l, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _f]),
     "ltx_op_gemma_rope_tables": (_i, [_vp, _i, _f, _vp, _vp]),

@@ -367,21 +367,28 @@ int ltx_op_attention_hd(ltx_ctx* ctx, const uint16_t* Q, const uint16_t* K, cons
     });
 }
 
-int ltx_op_attention_causal(ltx_ctx* ctx, const uint16_t* Q, const uint16_t* K, const uint16_t* Vt, long ldvt, const int32_t* key_start,
-                            int B, int Hq, int Hkv, int T, int head_dim, float scale, uint16_t* O) {
+int ltx_op_attention_causal_ld(ltx_ctx* ctx, const uint16_t* Q, long ldq, long q_bstride, const uint16_t* K, long ldk, long k_bstride,
+                               const uint16_t* Vt, long ldvt, long vt_bstride, const int32_t* key_start, int B, int Hq, int Hkv, int T,
+                               int head_dim, float scale, uint16_t* O, long ldo, long o_bstride) {
     return with_ctx(ctx, [&] {
         LTX_REQUIRE(head_dim == 256, "ltx_op_attention_causal: head dim %d (256)", head_dim);
         LTX_REQUIRE(Q && K && Vt && O, "ltx_op_attention_causal: null argument");
         AttnArgs a;
-        const long Dq = (long)Hq * 256, Dk = (long)Hkv * 256;
         a.head_dim = 256; a.causal = 1; a.key_start = key_start;
-        a.Q = Q; a.ldq = Dq; a.q_bstride = (long)T * Dq;
-        a.K = K; a.ldk = Dk; a.k_bstride = (long)T * Dk;
-        a.Vt = Vt; a.ldvt = ldvt; a.vt_bstride = Dk * ldvt;
-        a.O = O; a.ldo = Dq; a.o_bstride = (long)T * Dq;
+        a.Q = Q; a.ldq = ldq; a.q_bstride = q_bstride;
+        a.K = K; a.ldk = ldk; a.k_bstride = k_bstride;
+        a.Vt = Vt; a.ldvt = ldvt; a.vt_bstride = vt_bstride;
+        a.O = O; a.ldo = ldo; a.o_bstride = o_bstride;
         a.B = B; a.H = Hq; a.Hkv = Hkv; a.Tq = T; a.Tk = T; a.scale = scale;
         launch_attention(a, ctx->stream);
     });
+}
+
+int ltx_op_attention_causal(ltx_ctx* ctx, const uint16_t* Q, const uint16_t* K, const uint16_t* Vt, long ldvt, const int32_t* key_start,
+                            int B, int Hq, int Hkv, int T, int head_dim, float scale, uint16_t* O) {
+    const long Dq = (long)Hq * 256, Dk = (long)Hkv * 256;  // dense operands
+    return ltx_op_attention_causal_ld(ctx, Q, Dq, (long)T * Dq, K, Dk, (long)T * Dk, Vt, ldvt, Dk * ldvt, key_start, B, Hq, Hkv, T, head_dim,
+                                      scale, O, Dq, (long)T * Dq);
 }
 
 int ltx_op_gemma_norm(ltx_ctx* ctx, const uint16_t* r, const float* w, const uint16_t* x, const float* w2, int rows, int D, float eps,
