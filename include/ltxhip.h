@@ -1333,6 +1333,82 @@ int ltx_op_fe_stats(ltx_ctx* ctx, const uint16_t* hidden, const int32_t* mask, i
 int ltx_op_fe_norm_concat(ltx_ctx* ctx, const uint16_t* hidden, const int32_t* mask, const float* stats, int states, int B, int T, int D,
                           int padding_right, float eps, uint16_t* out);
 
+/* Test seams of the remaining helper passes: the guidance combines, the casts, the timestep embedding, the connector's registers, the
+ * VAE encoder's passes and the audio row passes. Same rules as above: DEVICE pointers, one launch on the context's stream, a null
+ * required pointer, an empty shape or a shape the launcher does not take is invalidConfiguration before anything is launched.
+ * out = cond + (scale - 1) * (cond - uncond) (LatentUtils.swift:131-141) */
+int ltx_op_cfg_combine(ltx_ctx* ctx, const float* uncond, const float* cond, float scale, float* out, long n);
+/* out = ca * a + cb * b */
+int ltx_op_lincomb(ltx_ctx* ctx, const float* a, const float* b, float ca, float cb, float* out, long n);
+/* out = cb * a + ca * (a - b) (STG, LTXPipeline.swift:920) */
+int ltx_op_axpby(ltx_ctx* ctx, const float* a, const float* b, float ca, float cb, float* out, long n);
+/* out = g * (a - b) + b (GE momentum, LTXPipeline.swift:924-927) */
+int ltx_op_ge(ltx_ctx* ctx, const float* a, const float* b, float g, float* out, long n);
+/* x *= s, in place */
+int ltx_op_scale_inplace(ltx_ctx* ctx, float* x, float s, long n);
+/* x = min(max((x + 1) / 2, 0), 1), in place (VideoDecoder.swift:501-505) */
+int ltx_op_clip01(ltx_ctx* ctx, float* x, long n);
+/* bias = (1 - mask) * -10000 as f32: exactly -10000 for 0 and +0 for 1 (LTXTransformer.swift:141-156) */
+int ltx_op_mask_to_bias(ltx_ctx* ctx, const int32_t* mask, float* bias, long n);
+/* f32 -> bf16, round to nearest even, and bf16 -> f32 */
+int ltx_op_cast_f32_bf16(ltx_ctx* ctx, const float* x, uint16_t* out, long n);
+int ltx_op_cast_bf16_f32(ltx_ctx* ctx, const uint16_t* x, float* out, long n);
+/* out [n][dim] f32: row r = [cos(t f_k) | sin(t f_k)], k < dim / 2, t = ts[r] * mult, f_k = exp(-ln(10000) * k / (dim / 2))
+ * (LTXTimestepEmbedding.swift:17-54). dim even. */
+int ltx_op_timestep_embedding(ltx_ctx* ctx, const float* ts, float mult, float* out, int n, int dim);
+/* The VAE's modulation tables, n jobs (1 .. ltx_vae_mods_max_jobs()) in one launch: out [rows][C] = table [rows][C] + (te ? te : 0) +
+ * (row odd ? 1 : 0) (VideoDecoder.swift:93-113). te may be NULL. */
+typedef struct ltx_vae_mods_job {
+    const float* table;
+    const float* te;
+    float* out;
+    int rows, C;
+} ltx_vae_mods_job;
+int ltx_vae_mods_max_jobs(void);
+int ltx_op_vae_make_mods_batch(ltx_ctx* ctx, const ltx_vae_mods_job* jobs, int n);
+/* gathered [N][D][Tn] bf16 -> vt [D][ld] bf16 with rank r's keys at columns r * Tn ..; columns N * Tn .. ld-1 are not written.
+ * Tn % 8 == 0, ld % 8 == 0, ld >= N * Tn. */
+int ltx_op_sp_vt_interleave(ltx_ctx* ctx, const uint16_t* gathered, uint16_t* vt, int N, int D, int Tn, long ld);
+/* mask [B][T] int32 -> src [B][T] int32: position p keeps a token where mask[T-1-p] != 0 and then holds the index of the p-th entry
+ * of (the valid tokens in order, then the padded ones); elsewhere -1, a learnable register (LTXTextEncoder.swift:428-470) */
+int ltx_op_register_plan(ltx_ctx* ctx, const int32_t* mask, int B, int T, int32_t* src);
+/* x [B][T][D] f32: row (b, p) = src[b][p] >= 0 ? enc[b][src[b][p]] (bf16 [B][T][D]) : registers[p % R] (f32 [R][D]). R >= 1. */
+int ltx_op_register_gather(ltx_ctx* ctx, const uint16_t* enc, const float* registers, const int32_t* src, int B, int T, int D, int R,
+                           float* x);
+/* pixels [3][T][H][W] f32 -> out [T][H/4][W/4][64] bf16, channel c * 16 + pw * 4 + ph, channels 48 .. 63 zero (VideoEncoder.swift:25-31).
+ * H % 4 == 0, W % 4 == 0. */
+int ltx_op_enc_patchify(ltx_ctx* ctx, const float* pixels, uint16_t* out, int T, int H, int W);
+/* conv [T][H][W][Cc], x [T][H][W][Cx] f32 -> out [T2][H/fh][W/fw][Cout] f32 = s2d(conv) + mean over groups of G = Cx * S / Cout
+ * adjacent channels of s2d(x), S = ft * fh * fw; s2d channel c * S + (it * fh + ih) * fw + iw; T is padded in FRONT with copies of
+ * frame 0 to a multiple of ft (VideoEncoder.swift:146-167). Cc * S == Cout, (Cx * S) % Cout == 0, H % fh == 0, W % fw == 0. */
+int ltx_op_enc_s2d_residual(ltx_ctx* ctx, const float* conv, int Cc, const float* x, int Cx, float* out, int Cout, int T, int H, int W,
+                            int ft, int fh, int fw);
+/* z [P][ldz] f32 (first C columns) -> out [C][P] f32 = mean ? (z - mean[c]) / std_[c] : z; mean and std_ both or neither
+ * (LTXPipeline.swift:1920-1927). ldz >= C. */
+int ltx_op_enc_finish(ltx_ctx* ctx, const float* z, long ldz, const float* mean, const float* std_, float* out, int C, long P);
+/* row_map [B][T] int32 = b * G + (t < first ? 1 : 0): the timestep group of every token of an image-to-video forward. 0 <= first <= T. */
+int ltx_op_i2v_rowmap(ltx_ctx* ctx, int32_t* row_map, int B, int T, int first, int G);
+/* ts [B * G + B] f32: ts[b * G + g] = g == 0 ? sigma : 0, then B audio timesteps = sigma. B * G + B <= 64. */
+int ltx_op_i2v_timesteps(ltx_ctx* ctx, float* ts, int B, int G, float sigma);
+/* p [n] int32 = v */
+int ltx_op_fill_const_i32(ltx_ctx* ctx, int32_t* p, long n, int32_t v);
+/* mask [B][T] int32 -> key_start[b] = index of the first 1 (T without one); status[b] = 1 when row b is 0..0 1..1 with at least one 1
+ * and no value other than 0 and 1, else 0 */
+int ltx_op_gemma_mask_scan(ltx_ctx* ctx, const int32_t* mask, int B, int T, int32_t* key_start, int32_t* status);
+/* The audio row passes (AudioVAE.swift, Vocoder.swift). Each writes ONLY the interior of its haloed bf16 operand.
+ * x [H][W][C] f32 -> out [(H+3)][W+2][C] at (h + 2, w + 1): mode 0 SiLU(x / sqrt(mean_c(x^2) + 1e-6)), mode 1 the plain cast */
+int ltx_op_audio_pn_pad(ltx_ctx* ctx, const float* x, int H, int W, int C, int mode, uint16_t* out);
+/* x [H][W][C] f32, nearest-2x -> out [(2H+2)][2W+2][C] at (u + 1, v + 1). C % 4 == 0. */
+int ltx_op_audio_upsample_pad(ltx_ctx* ctx, const float* x, int H, int W, int C, uint16_t* out);
+/* latent [Cl][T][Wl] f32 * std_[c * Wl + w] + mean[c * Wl + w] -> out [(T+3)][Wl+2][Cpad] at (t + 2, w + 1), channels < Cl only */
+int ltx_op_audio_denorm_pad(ltx_ctx* ctx, const float* latent, const float* mean, const float* std_, int Cl, int T, int Wl, int Cpad,
+                            uint16_t* out);
+/* mel [2][T][M] f32 -> out [T][2 * M] bf16, column c * M + m */
+int ltx_op_audio_mel_pack(ltx_ctx* ctx, const float* mel, int T, int M, uint16_t* out);
+/* a, b, c [rows][C] f32 -> out [rows][ldb] bf16, columns < C: leaky((a + b + c) / 3, slope). C % 4 == 0, ldb % 4 == 0, ldb >= C. */
+int ltx_op_audio_mean3_act(ltx_ctx* ctx, const float* a, const float* b, const float* c, long rows, int C, float slope, uint16_t* out,
+                           long ldb);
+
 #ifdef __cplusplus
 }
 #endif

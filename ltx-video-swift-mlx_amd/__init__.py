@@ -1001,6 +1001,89 @@ class Context:
     def op_fe_norm_concat(self, hidden, mask, stats, states, B, T, D, out, padding_right=False, eps=1e-6):
         self._ck(lib.ltx_op_fe_norm_concat(self._h, _dptr(hidden), _dptr(mask), _dptr(stats), states, B, T, D, int(padding_right), eps, _dptr(out)))
 
+    # ---- the remaining helper passes (include/ltxhip.h, "Test seams of the remaining helper passes") ----
+    def op_cfg_combine(self, uncond, cond, scale, out, n):
+        self._ck(lib.ltx_op_cfg_combine(self._h, _dptr(uncond), _dptr(cond), scale, _dptr(out), n))
+
+    def op_lincomb(self, a, b, ca, cb, out, n):
+        self._ck(lib.ltx_op_lincomb(self._h, _dptr(a), _dptr(b), ca, cb, _dptr(out), n))
+
+    def op_axpby(self, a, b, ca, cb, out, n):
+        self._ck(lib.ltx_op_axpby(self._h, _dptr(a), _dptr(b), ca, cb, _dptr(out), n))
+
+    def op_ge(self, a, b, g, out, n):
+        self._ck(lib.ltx_op_ge(self._h, _dptr(a), _dptr(b), g, _dptr(out), n))
+
+    def op_scale_inplace(self, x, s, n):
+        self._ck(lib.ltx_op_scale_inplace(self._h, _dptr(x), s, n))
+
+    def op_clip01(self, x, n):
+        self._ck(lib.ltx_op_clip01(self._h, _dptr(x), n))
+
+    def op_mask_to_bias(self, mask, bias, n):
+        self._ck(lib.ltx_op_mask_to_bias(self._h, _dptr(mask), _dptr(bias), n))
+
+    def op_cast_f32_bf16(self, x, out, n):
+        self._ck(lib.ltx_op_cast_f32_bf16(self._h, _dptr(x), _dptr(out), n))
+
+    def op_cast_bf16_f32(self, x, out, n):
+        self._ck(lib.ltx_op_cast_bf16_f32(self._h, _dptr(x), _dptr(out), n))
+
+    def op_timestep_embedding(self, ts, mult, out, n, dim):
+        self._ck(lib.ltx_op_timestep_embedding(self._h, _dptr(ts), mult, _dptr(out), n, dim))
+
+    def op_vae_make_mods_batch(self, jobs):
+        """``ltx_op_vae_make_mods_batch``: jobs = [(table, te or None, out, rows, C), ...] of device tensors, one launch."""
+        arr = (_lib.VaeModsJob * max(len(jobs), 1))()
+        for j, (table, te, out, rows, Cc) in zip(arr, jobs):
+            j.table, j.te, j.out, j.rows, j.C = _dptr(table), _dptr(te), _dptr(out), rows, Cc
+        self._ck(lib.ltx_op_vae_make_mods_batch(self._h, arr, len(jobs)))
+
+    def op_sp_vt_interleave(self, gathered, vt, N, D, Tn, ld):
+        self._ck(lib.ltx_op_sp_vt_interleave(self._h, _dptr(gathered), _dptr(vt), N, D, Tn, ld))
+
+    def op_register_plan(self, mask, B, T, src):
+        self._ck(lib.ltx_op_register_plan(self._h, _dptr(mask), B, T, _dptr(src)))
+
+    def op_register_gather(self, enc, registers, src, B, T, D, R, x):
+        self._ck(lib.ltx_op_register_gather(self._h, _dptr(enc), _dptr(registers), _dptr(src), B, T, D, R, _dptr(x)))
+
+    def op_enc_patchify(self, pixels, out, T, H, W):
+        self._ck(lib.ltx_op_enc_patchify(self._h, _dptr(pixels), _dptr(out), T, H, W))
+
+    def op_enc_s2d_residual(self, conv, Cc, x, Cx, out, Cout, T, H, W, ft, fh, fw):
+        self._ck(lib.ltx_op_enc_s2d_residual(self._h, _dptr(conv), Cc, _dptr(x), Cx, _dptr(out), Cout, T, H, W, ft, fh, fw))
+
+    def op_enc_finish(self, z, ldz, out, C, P, mean=None, std=None):
+        self._ck(lib.ltx_op_enc_finish(self._h, _dptr(z), ldz, _dptr(mean), _dptr(std), _dptr(out), C, P))
+
+    def op_i2v_rowmap(self, row_map, B, T, first, G):
+        self._ck(lib.ltx_op_i2v_rowmap(self._h, _dptr(row_map), B, T, first, G))
+
+    def op_i2v_timesteps(self, ts, B, G, sigma):
+        self._ck(lib.ltx_op_i2v_timesteps(self._h, _dptr(ts), B, G, sigma))
+
+    def op_fill_const_i32(self, p, n, v):
+        self._ck(lib.ltx_op_fill_const_i32(self._h, _dptr(p), n, v))
+
+    def op_gemma_mask_scan(self, mask, B, T, key_start, status):
+        self._ck(lib.ltx_op_gemma_mask_scan(self._h, _dptr(mask), B, T, _dptr(key_start), _dptr(status)))
+
+    def op_audio_pn_pad(self, x, H, W, C, mode, out):
+        self._ck(lib.ltx_op_audio_pn_pad(self._h, _dptr(x), H, W, C, mode, _dptr(out)))
+
+    def op_audio_upsample_pad(self, x, H, W, C, out):
+        self._ck(lib.ltx_op_audio_upsample_pad(self._h, _dptr(x), H, W, C, _dptr(out)))
+
+    def op_audio_denorm_pad(self, latent, mean, std, Cl, T, Wl, Cpad, out):
+        self._ck(lib.ltx_op_audio_denorm_pad(self._h, _dptr(latent), _dptr(mean), _dptr(std), Cl, T, Wl, Cpad, _dptr(out)))
+
+    def op_audio_mel_pack(self, mel, T, M, out):
+        self._ck(lib.ltx_op_audio_mel_pack(self._h, _dptr(mel), T, M, _dptr(out)))
+
+    def op_audio_mean3_act(self, a, b, c, rows, C, slope, out, ldb):
+        self._ck(lib.ltx_op_audio_mean3_act(self._h, _dptr(a), _dptr(b), _dptr(c), rows, C, slope, _dptr(out), ldb))
+
     def upscaler_load(self, path):
         self._ck(lib.ltx_upscaler_load(self._h, str(path).encode()))
 

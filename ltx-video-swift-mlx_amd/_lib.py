@@ -49,6 +49,12 @@ class ConnectorConfig(C.Structure):
                 ("theta", C.c_float), ("max_pos", C.c_int)]
 
 
+class VaeModsJob(C.Structure):
+    """``ltx_vae_mods_job``: one modulation table of ``ltx_op_vae_make_mods_batch``."""
+
+    _fields_ = [("table", C.c_void_p), ("te", C.c_void_p), ("out", C.c_void_p), ("rows", C.c_int), ("C", C.c_int)]
+
+
 class GemmaConfig(C.Structure):
     """``ltx_gemma_config`` / reference ``Gemma3Config`` defaults (Gemma3Config.swift:42-60)."""
 
@@ -423,6 +429,33 @@ SIGNATURES = {
     "ltx_fe_stats_partials_floats": (_l, [_i, _i, _i, _i]),
     "ltx_op_fe_stats": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp]),
     "ltx_op_fe_norm_concat": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp]),
+    "ltx_op_cfg_combine": (_i, [_vp, _vp, _vp, _f, _vp, _l]),
+    "ltx_op_lincomb": (_i, [_vp, _vp, _vp, _f, _f, _vp, _l]),
+    "ltx_op_axpby": (_i, [_vp, _vp, _vp, _f, _f, _vp, _l]),
+    "ltx_op_ge": (_i, [_vp, _vp, _vp, _f, _vp, _l]),
+    "ltx_op_scale_inplace": (_i, [_vp, _vp, _f, _l]),
+    "ltx_op_clip01": (_i, [_vp, _vp, _l]),
+    "ltx_op_mask_to_bias": (_i, [_vp, _vp, _vp, _l]),
+    "ltx_op_cast_f32_bf16": (_i, [_vp, _vp, _vp, _l]),
+    "ltx_op_cast_bf16_f32": (_i, [_vp, _vp, _vp, _l]),
+    "ltx_op_timestep_embedding": (_i, [_vp, _vp, _f, _vp, _i, _i]),
+    "ltx_vae_mods_max_jobs": (_i, []),
+    "ltx_op_vae_make_mods_batch": (_i, [_vp, C.POINTER(VaeModsJob), _i]),
+    "ltx_op_sp_vt_interleave": (_i, [_vp, _vp, _vp, _i, _i, _i, _l]),
+    "ltx_op_register_plan": (_i, [_vp, _vp, _i, _i, _vp]),
+    "ltx_op_register_gather": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "ltx_op_enc_patchify": (_i, [_vp, _vp, _vp, _i, _i, _i]),
+    "ltx_op_enc_s2d_residual": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i]),
+    "ltx_op_enc_finish": (_i, [_vp, _vp, _l, _vp, _vp, _vp, _i, _l]),
+    "ltx_op_i2v_rowmap": (_i, [_vp, _vp, _i, _i, _i, _i]),
+    "ltx_op_i2v_timesteps": (_i, [_vp, _vp, _i, _i, _f]),
+    "ltx_op_fill_const_i32": (_i, [_vp, _vp, _l, _i]),
+    "ltx_op_gemma_mask_scan": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
+    "ltx_op_audio_pn_pad": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
+    "ltx_op_audio_upsample_pad": (_i, [_vp, _vp, _i, _i, _i, _vp]),
+    "ltx_op_audio_denorm_pad": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "ltx_op_audio_mel_pack": (_i, [_vp, _vp, _i, _i, _vp]),
+    "ltx_op_audio_mean3_act": (_i, [_vp, _vp, _vp, _vp, _l, _i, _f, _vp, _l]),
     "ltx_op_fill_normal_bf16": (_i, [_vp, _vp, _l, _u64, _f, _f]),
     "ltx_op_fill_normal_f32": (_i, [_vp, _vp, _l, _u64, _f, _f]),
 }

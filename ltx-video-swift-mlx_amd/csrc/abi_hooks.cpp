@@ -694,6 +694,216 @@ int ltx_op_fe_norm_concat(ltx_ctx* ctx, const uint16_t* hidden, const int32_t* m
     });
 }
 
+// ---- helper passes, the rest: guidance combines, casts, embedding, connector registers, VAE encoder (elementwise.h) ----
+int ltx_op_cfg_combine(ltx_ctx* ctx, const float* uncond, const float* cond, float scale, float* out, long n) {
+    return with_ctx(ctx, [&] {
+        LTX_REQUIRE(uncond && cond && out && n >= 1, "ltx_op_cfg_combine: null argument or empty shape");
+        launch_cfg_combine(uncond, cond, scale, out, n, ctx->stream);
+    });
+}
+
+int ltx_op_lincomb(ltx_ctx* ctx, const float* a, const float* b, float ca, float cb, float* out, long n) {
+    return with_ctx(ctx, [&] {
+        LTX_REQUIRE(a && b && out && n >= 1, "ltx_op_lincomb: null argument or empty shape");
+        launch_lincomb(a, b, ca, cb, out, n, ctx->stream);
+    });
+}
+
+int ltx_op_axpby(ltx_ctx* ctx, const float* a, const float* b, float ca, float cb, float* out, long n) {
+    return with_ctx(ctx, [&] {
+        LTX_REQUIRE(a && b && out && n >= 1, "ltx_op_axpby: null argument or empty shape");
+        launch_axpby(a, b, ca, cb, out, n, ctx->stream);
+    });
+}
+
+int ltx_op_ge(ltx_ctx* ctx, const float* a, const float* b, float g, float* out, long n) {
+    return with_ctx(ctx, [&] {
+        LTX_REQUIRE(a && b && out && n >= 1, "ltx_op_ge: null argument or empty shape");
+        launch_ge(a, b, g, out, n, ctx->stream);
+    });
+}
+
+int ltx_op_scale_inplace(ltx_ctx* ctx, float* x, float s, long n) {
+    return with_ctx(ctx, [&] {
+        LTX_REQUIRE(x && n >= 1, "ltx_op_scale_inplace: null argument or empty shape");
+        launch_scale_inplace(x, s, n, ctx->stream);
+    });
+}
+
+int ltx_op_clip01(ltx_ctx* ctx, float* x, long n) {
+    return with_ctx(ctx, [&] {
+        LTX_REQUIRE(x && n >= 1, "ltx_op_clip01: null argument or empty shape");
+        launch_clip01(x, n, ctx->stream);
+    });
+}
+
+int ltx_op_mask_to_bias(ltx_ctx* ctx, const int32_t* mask, float* bias, long n) {
+    return with_ctx(ctx, [&] {
+        LTX_REQUIRE(mask && bias && n >= 1, "ltx_op_mask_to_bias: null argument or empty shape");
+        launch_mask_to_bias(mask, bias, n, ctx->stream);
+    });
+}
+
+int ltx_op_cast_f32_bf16(ltx_ctx* ctx, const float* x, uint16_t* out, long n) {
+    return with_ctx(ctx, [&] {
+        LTX_REQUIRE(x && out && n >= 1, "ltx_op_cast_f32_bf16: null argument or empty shape");
+        launch_cast_f32_bf16(x, out, n, ctx->stream);
+    });
+}
+
+int ltx_op_cast_bf16_f32(ltx_ctx* ctx, const uint16_t* x, float* out, long n) {
+    return with_ctx(ctx, [&] {
+        LTX_REQUIRE(x && out && n >= 1, "ltx_op_cast_bf16_f32: null argument or empty shape");
+        launch_cast_bf16_f32(x, out, n, ctx->stream);
+    });
+}
+
+int ltx_op_timestep_embedding(ltx_ctx* ctx, const float* ts, float mult, float* out, int n, int dim) {
+    return with_ctx(ctx, [&] {
+        LTX_REQUIRE(ts && out && n >= 1, "ltx_op_timestep_embedding: null argument or empty shape");
+        LTX_REQUIRE(dim >= 2 && dim % 2 == 0, "ltx_op_timestep_embedding: dim=%d must be even", dim);
+        launch_timestep_embedding(ts, mult, out, n, dim, ctx->stream);
+    });
+}
+
+int ltx_vae_mods_max_jobs(void) { return VaeModsBatch::MAX_JOBS; }
+
+int ltx_op_vae_make_mods_batch(ltx_ctx* ctx, const ltx_vae_mods_job* jobs, int n) {
+    return with_ctx(ctx, [&] {
+        LTX_REQUIRE(jobs && n >= 1 && n <= VaeModsBatch::MAX_JOBS, "ltx_op_vae_make_mods_batch: %d jobs (1 .. %d)", n, (int)VaeModsBatch::MAX_JOBS);
+        VaeModsBatch b;
+        for (int i = 0; i < n; ++i) {
+            LTX_REQUIRE(jobs[i].table && jobs[i].out && jobs[i].rows >= 1 && jobs[i].C >= 1, "ltx_op_vae_make_mods_batch: job %d: null argument or empty shape", i);
+            b.job[i] = VaeModsJob{jobs[i].table, jobs[i].te, jobs[i].out, jobs[i].rows, jobs[i].C};
+        }
+        b.n = n;
+        launch_vae_make_mods_batch(b, ctx->stream);
+    });
+}
+
+int ltx_op_sp_vt_interleave(ltx_ctx* ctx, const uint16_t* gathered, uint16_t* vt, int N, int D, int Tn, long ld) {
+    return with_ctx(ctx, [&] {
+        LTX_REQUIRE(gathered && vt && N >= 1 && D >= 1 && Tn >= 1, "ltx_op_sp_vt_interleave: null argument or empty shape");
+        LTX_REQUIRE(Tn % 8 == 0 && ld % 8 == 0 && ld >= (long)N * Tn, "ltx_op_sp_vt_interleave: Tn=%d ld=%ld (multiples of 8, ld >= N * Tn)", Tn, ld);
+        launch_sp_vt_interleave(gathered, vt, N, D, Tn, ld, ctx->stream);
+    });
+}
+
+int ltx_op_register_plan(ltx_ctx* ctx, const int32_t* mask, int B, int T, int32_t* src) {
+    return with_ctx(ctx, [&] {
+        LTX_REQUIRE(mask && src && B >= 1 && T >= 1, "ltx_op_register_plan: null argument or empty shape");
+        launch_register_plan(mask, B, T, src, ctx->stream);
+    });
+}
+
+int ltx_op_register_gather(ltx_ctx* ctx, const uint16_t* enc, const float* registers, const int32_t* src, int B, int T, int D, int R,
+                           float* x) {
+    return with_ctx(ctx, [&] {
+        LTX_REQUIRE(enc && registers && src && x && B >= 1 && T >= 1 && D >= 1, "ltx_op_register_gather: null argument or empty shape");
+        LTX_REQUIRE(R >= 1, "ltx_op_register_gather: R=%d registers", R);
+        launch_register_gather(enc, registers, src, B, T, D, R, x, ctx->stream);
+    });
+}
+
+int ltx_op_enc_patchify(ltx_ctx* ctx, const float* pixels, uint16_t* out, int T, int H, int W) {
+    return with_ctx(ctx, [&] {
+        LTX_REQUIRE(pixels && out && T >= 1 && H >= 1 && W >= 1, "ltx_op_enc_patchify: null argument or empty shape");
+        LTX_REQUIRE(H % 4 == 0 && W % 4 == 0, "ltx_op_enc_patchify: H=%d W=%d must be multiples of 4", H, W);
+        launch_enc_patchify(pixels, out, T, H, W, ctx->stream);
+    });
+}
+
+int ltx_op_enc_s2d_residual(ltx_ctx* ctx, const float* conv, int Cc, const float* x, int Cx, float* out, int Cout, int T, int H, int W,
+                            int ft, int fh, int fw) {
+    return with_ctx(ctx, [&] {
+        LTX_REQUIRE(conv && x && out && Cc >= 1 && Cx >= 1 && Cout >= 1 && T >= 1 && H >= 1 && W >= 1,
+                    "ltx_op_enc_s2d_residual: null argument or empty shape");
+        LTX_REQUIRE(ft >= 1 && fh >= 1 && fw >= 1 && H % fh == 0 && W % fw == 0, "ltx_op_enc_s2d_residual: factors (%d,%d,%d) at H=%d W=%d",
+                    ft, fh, fw, H, W);
+        LTX_REQUIRE((long)Cc * ft * fh * fw == Cout && ((long)Cx * ft * fh * fw) % Cout == 0,
+                    "ltx_op_enc_s2d_residual: Cc=%d Cx=%d Cout=%d (Cc * S == Cout, Cx * S a multiple of Cout)", Cc, Cx, Cout);
+        launch_enc_s2d_residual(conv, Cc, x, Cx, out, Cout, T, H, W, ft, fh, fw, ctx->stream);
+    });
+}
+
+int ltx_op_enc_finish(ltx_ctx* ctx, const float* z, long ldz, const float* mean, const float* std_, float* out, int C, long P) {
+    return with_ctx(ctx, [&] {
+        LTX_REQUIRE(z && out && C >= 1 && P >= 1 && ldz >= C, "ltx_op_enc_finish: null argument, empty shape or ldz=%ld < C=%d", ldz, C);
+        LTX_REQUIRE((mean == nullptr) == (std_ == nullptr), "ltx_op_enc_finish: give mean and std, or neither");
+        launch_enc_finish(z, ldz, mean, std_, out, C, P, ctx->stream);
+    });
+}
+
+int ltx_op_i2v_rowmap(ltx_ctx* ctx, int32_t* row_map, int B, int T, int first, int G) {
+    return with_ctx(ctx, [&] {
+        LTX_REQUIRE(row_map && B >= 1 && T >= 1 && G >= 1 && first >= 0 && first <= T, "ltx_op_i2v_rowmap: B=%d T=%d first=%d G=%d", B, T, first, G);
+        launch_i2v_rowmap(row_map, B, T, first, G, ctx->stream);
+    });
+}
+
+int ltx_op_i2v_timesteps(ltx_ctx* ctx, float* ts, int B, int G, float sigma) {
+    return with_ctx(ctx, [&] {
+        LTX_REQUIRE(ts && B >= 1 && G >= 1 && (long)B * G + B <= 64, "ltx_op_i2v_timesteps: B=%d G=%d (B * G + B <= 64)", B, G);
+        launch_i2v_timesteps(ts, B, G, sigma, ctx->stream);
+    });
+}
+
+int ltx_op_fill_const_i32(ltx_ctx* ctx, int32_t* p, long n, int32_t v) {
+    return with_ctx(ctx, [&] {
+        LTX_REQUIRE(p && n >= 1, "ltx_op_fill_const_i32: null argument or empty shape");
+        launch_fill_const_i32(p, n, v, ctx->stream);
+    });
+}
+
+int ltx_op_gemma_mask_scan(ltx_ctx* ctx, const int32_t* mask, int B, int T, int32_t* key_start, int32_t* status) {
+    return with_ctx(ctx, [&] {
+        LTX_REQUIRE(mask && key_start && status && B >= 1 && T >= 1, "ltx_op_gemma_mask_scan: null argument or empty shape");
+        launch_gemma_mask_scan(mask, B, T, key_start, status, ctx->stream);
+    });
+}
+
+// ---- audio row passes (audio.h): each writes only the interior of its haloed operand ----
+int ltx_op_audio_pn_pad(ltx_ctx* ctx, const float* x, int H, int W, int C, int mode, uint16_t* out) {
+    return with_ctx(ctx, [&] {
+        LTX_REQUIRE(x && out && H >= 1 && W >= 1 && C >= 1, "ltx_op_audio_pn_pad: null argument or empty shape");
+        LTX_REQUIRE(mode == 0 || mode == 1, "ltx_op_audio_pn_pad: mode=%d (0 PixelNorm + SiLU, 1 copy)", mode);
+        launch_audio_pn_pad(x, H, W, C, mode, out, ctx->stream);
+    });
+}
+
+int ltx_op_audio_upsample_pad(ltx_ctx* ctx, const float* x, int H, int W, int C, uint16_t* out) {
+    return with_ctx(ctx, [&] {
+        LTX_REQUIRE(x && out && H >= 1 && W >= 1 && C >= 1, "ltx_op_audio_upsample_pad: null argument or empty shape");
+        LTX_REQUIRE(C % 4 == 0, "ltx_op_audio_upsample_pad: C=%d must be a multiple of 4", C);
+        launch_audio_upsample_pad(x, H, W, C, out, ctx->stream);
+    });
+}
+
+int ltx_op_audio_denorm_pad(ltx_ctx* ctx, const float* latent, const float* mean, const float* std_, int Cl, int T, int Wl, int Cpad,
+                            uint16_t* out) {
+    return with_ctx(ctx, [&] {
+        LTX_REQUIRE(latent && mean && std_ && out && Cl >= 1 && T >= 1 && Wl >= 1, "ltx_op_audio_denorm_pad: null argument or empty shape");
+        LTX_REQUIRE(Cpad >= Cl, "ltx_op_audio_denorm_pad: Cpad=%d < Cl=%d", Cpad, Cl);
+        launch_audio_denorm_pad(latent, mean, std_, Cl, T, Wl, Cpad, out, ctx->stream);
+    });
+}
+
+int ltx_op_audio_mel_pack(ltx_ctx* ctx, const float* mel, int T, int M, uint16_t* out) {
+    return with_ctx(ctx, [&] {
+        LTX_REQUIRE(mel && out && T >= 1 && M >= 1, "ltx_op_audio_mel_pack: null argument or empty shape");
+        launch_audio_mel_pack(mel, T, M, out, ctx->stream);
+    });
+}
+
+int ltx_op_audio_mean3_act(ltx_ctx* ctx, const float* a, const float* b, const float* c, long rows, int C, float slope, uint16_t* out,
+                           long ldb) {
+    return with_ctx(ctx, [&] {
+        LTX_REQUIRE(a && b && c && out && rows >= 1 && C >= 1, "ltx_op_audio_mean3_act: null argument or empty shape");
+        LTX_REQUIRE(C % 4 == 0 && ldb % 4 == 0 && ldb >= C, "ltx_op_audio_mean3_act: C=%d ldb=%ld (multiples of 4, ldb >= C)", C, ldb);
+        launch_audio_mean3_act(a, b, c, rows, C, slope, out, ldb, ctx->stream);
+    });
+}
+
 // ---- audio convolutions ----
 int ltx_op_conv1d(ltx_ctx* ctx, const uint16_t* x, int L, int Cin, const uint16_t* w, const float* bias, int Cout, int k, int dilation,
                   int tile, const float* resid, int f32_act, int transposed, float* out_f32, int bf16_act, float slope,

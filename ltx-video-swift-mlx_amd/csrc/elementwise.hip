@@ -605,7 +605,8 @@ __global__ void make_mod_kernel(const float* __restrict__ tables, const float* _
 
 __global__ void mask_to_bias_kernel(const int32_t* __restrict__ mask, float* __restrict__ bias, long n) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) bias[i] = (1.0f - (float)mask[i]) * -10000.0f;
+    // + 0.0f: an attended key (mask 1) gets +0, not the -0 that 0 * -10000 is
+    if (i < n) bias[i] = (1.0f - (float)mask[i]) * -10000.0f + 0.0f;
 }
 
 // latent [B][C][T] f32 -> tokens [B][T][C] bf16 through a 32x32 LDS transpose tile

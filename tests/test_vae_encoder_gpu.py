@@ -65,6 +65,33 @@ def test_vae_encode_normalised_latent_feeds_i2v(ltx, oracle, gpu_ctx, enc):
     gpu_ctx.vae_unload()
 
 
+def test_vae_encode_normalise_arithmetic(ltx, oracle, gpu_ctx, enc, tmp_path):
+    """normalize=True with statistics that are not mean 0 / std 1: a decoder file holding only latents_mean / latents_std, different in
+    every channel. The normalised latent is (raw - mean[c]) / std[c] of the raw latent of the same pixels: against float64 within
+    2 U |value| (one subtraction, one correctly rounded division). [1, 128, 2, 2, 3]: P = 12 positions of 128 channels."""
+    from safetensors.numpy import save_file
+
+    U = 2.0 ** -24
+    rng = np.random.default_rng(5)
+    mean = (0.2 * rng.standard_normal(128)).astype(np.float32)
+    std = (1.0 + 0.3 * rng.random(128)).astype(np.float32)
+    assert len(set(mean)) == 128 and len(set(std)) == 128
+    save_file({"latents_mean": mean, "latents_std": std}, str(tmp_path / "vae.safetensors"))
+    px = rng.uniform(-1, 1, (1, 3, 9, 64, 96)).astype(np.float32)
+    gpu_ctx.vae_load(tmp_path / "vae.safetensors")
+    try:
+        raw = gpu_ctx.vae_encode(px)
+        nrm = gpu_ctx.vae_encode(px, normalize=True)
+    finally:
+        gpu_ctx.vae_unload()
+    assert raw.shape == nrm.shape == (1, 128, 2, 2, 3)
+    want = (raw.astype(np.float64) - mean.astype(np.float64)[None, :, None, None, None]) / std.astype(np.float64)[None, :, None, None, None]
+    err = np.abs(nrm - want)
+    print(f"vae_encode normalize: worst error / (2 U |value|) = {float((err / np.maximum(2 * U * np.abs(want), 1e-300)).max()):.3f}")
+    assert np.all(err <= 2 * U * np.abs(want))
+    assert not np.allclose(nrm, raw)
+
+
 def test_encoder_index_logic_exact(ltx, oracle, gpu_ctx):
     """Patchify / space-to-depth / group-mean residual order on integer data through an encoder whose convolutions are zero:
     with all conv weights and biases 0, every resblock is the identity and each downsampler returns exactly the group mean of
