@@ -1201,7 +1201,8 @@ int ltx_op_fill_normal_f32(ltx_ctx* ctx, float* p, long n, uint64_t seed, float 
 /* ---- Gemma-3 text encoder (csrc/gemma.h): token ids + attention mask -> the hidden states ltx_connector_encode* consumes ----
  * Reference: Gemma3Model.swift (Gemma3Attention, Gemma3MLP, Gemma3DecoderLayer, Gemma3InnerModel.callAsFunction), Gemma3Config.swift,
  * Gemma3WeightLoader.swift; call sites LTXPipeline.swift:1155-1170 and :3194-3277. Only the hidden-state extraction with an attention
- * mask: no token generation, no KV cache, no tokenizer (token ids are inputs), no sliding-window masking (T <= sliding_window). */
+ * mask: no tokenizer (token ids are inputs), no sliding-window masking (T <= sliding_window). Token generation on a KV cache is the
+ * ltx_lm_ section below. */
 typedef struct ltx_gemma_config {
     int hidden_size;             /* 3840 */
     int num_hidden_layers;       /* 48 */
@@ -1279,6 +1280,75 @@ int ltx_op_gemma_rope_tables(ltx_ctx* ctx, int T, float base, float* cos_t, floa
 int ltx_op_geglu(ltx_ctx* ctx, const uint16_t* gu, int rows, int I, uint16_t* out);
 /* out [rows][D] = bf16(table[ids[row]] * bf16(sqrt(D))); ids are clamped to [0, vocab) */
 int ltx_op_gemma_embed(ltx_ctx* ctx, const int32_t* ids, const uint16_t* table, int rows, int D, int vocab, uint16_t* out);
+
+/* ---- Gemma-3 token generation on a KV cache: prompt enhancement (csrc/gemma.h, csrc/gemma_generate.cpp) ----
+ * Reference: Gemma3TextModel.generateTokens (Gemma3Model.swift:375-492) and the cache: path of Gemma3Attention (:73-110); the stage
+ * config.enhancePrompt of LTXPipeline.swift. Runs on the model ltx_gemma_load / ltx_gemma_init_synthetic loaded (without one:
+ * LTX_ERR_MODEL_NOT_LOADED). Batch 1; the tokenizer and the chat template stay outside: token ids in, token ids out. A session
+ * (ltx_lm_begin .. ltx_lm_end) holds the per-layer K and V^T caches of `capacity` positions (capacity x 393 KB at the reference's
+ * size), RoPE tables of that many positions and every buffer a step touches; nothing is allocated per token. The decode attention
+ * covers ALL cached keys on every layer - the reference decodes with mask: .none on a KVCacheSimple - and the prefill, which builds no
+ * window mask, refuses prompts longer than sliding_window (as ltx_gemma_encode does). Every refusal comes before the first launch. */
+typedef struct ltx_lm_params {
+    uint32_t struct_size;      /* sizeof(ltx_lm_params): set by ltx_lm_params_default */
+    int max_new_tokens;        /* 512 */
+    float temperature;         /* 0.7; <= 0: greedy, picked on the device (4 bytes per token cross the bus) */
+    float top_p;               /* 0.95 */
+    float repetition_penalty;  /* 1.1 */
+    int repetition_context;    /* 64 */
+    uint64_t seed;             /* the sampler's threefry key sequence: ltx_mlx_draw_key(seed, step) */
+    int n_eos;                 /* 1; up to 8 */
+    int32_t eos_ids[8];        /* {1} */
+} ltx_lm_params;
+void ltx_lm_params_default(ltx_lm_params* p);
+/* Replaces a session the context already holds. */
+int ltx_lm_begin(ltx_ctx* ctx, int capacity);
+/* freed_bytes (may be NULL): what ltx_lm_memory_info reported, cache + workspace; 0 without a session. */
+int ltx_lm_end(ltx_ctx* ctx, long* freed_bytes);
+/* Device bytes the session holds: the K / V^T caches, and everything else it allocated at begin (tables, hidden slots, step rows,
+ * logits, history, split workspace); zeros with a model and no session. The activation workspaces the prefill shares with the encoder
+ * (T rows of every intermediate) are the model's and are reported by ltx_gemma_memory_info. */
+int ltx_lm_memory_info(ltx_ctx* ctx, long* cache_bytes, long* workspace_bytes);
+/* Resets the session and fills cache positions 0 .. T-1 from ids [T]. logits [vocab] f32 of the last position, or NULL. The logits
+ * hold bf16-rounded values (the reference's asLinear on bf16 operands yields a bf16 array). DEVICE pointers; ids are clamped. */
+int ltx_lm_prefill_dev(ltx_ctx* ctx, const int32_t* ids, int T, float* logits);
+/* HOST pointers; ids outside [0, vocab) are invalidConfiguration. */
+int ltx_lm_prefill(ltx_ctx* ctx, const int32_t* ids, int T, float* logits);
+/* One token at the next position: token int32 [1] and logits [vocab] or NULL, DEVICE pointers. */
+int ltx_lm_step_dev(ltx_ctx* ctx, const int32_t* token, float* logits);
+/* HOST variant: the token by value, logits a host array or NULL. */
+int ltx_lm_step(ltx_ctx* ctx, int32_t token, float* logits);
+/* Debug seams (HOST pointers): model.norm of the newest position [hidden_size] bf16 - the logits projection's input; and rows
+ * 0 .. rows-1 of a layer's K cache, [rows][num_key_value_heads * 256] bf16. */
+int ltx_lm_last_state(ltx_ctx* ctx, uint16_t* state);
+int ltx_lm_cache_k(ltx_ctx* ctx, int layer, int rows, uint16_t* k);
+/* Prefill + the generate loop: pick, stop-id check, append, step. ids HOST [T]; out_tokens HOST [max_new_tokens]; *n_out tokens are
+ * written (a stop id ends the run and is not written). T + max_new_tokens must fit the session's capacity. params NULL: defaults. */
+int ltx_lm_generate(ltx_ctx* ctx, const int32_t* ids, int T, const ltx_lm_params* params, int32_t* out_tokens, int* n_out);
+/* The sampler of temperature > 0, pure host code (no context, no device) and THIS library's own definition: the
+ * repetition penalty in place on logits - every distinct id among the last min(context, n_generated) of `generated`:
+ * l > 0 ? l / penalty : l * penalty -, softmax of l / temperature in f64, the nucleus = the fewest tokens in decreasing probability
+ * (ties: the lower id) whose mass reaches top_p, one inverse-CDF draw with the uniform (w >> 8) * 2^-24, w = word 0 of
+ * threefry2x32(ltx_mlx_draw_key(seed, step), {0, 0}). temperature <= 0: argmax, ties to the lowest id. */
+int ltx_lm_sample_host(float* logits, int vocab, const int32_t* generated, int n_generated, int context, float penalty, float temperature,
+                       float top_p, uint64_t seed, int step, int32_t* token);
+/* Test seams of the generation kernels (DEVICE pointers).
+ * ltx_op_gemv_bf16: out[n] = sum_k x[k] W[n][k], bf16 x bf16, f32 accumulation, one rounding at the store; M must be 1. epilogue 0:
+ * out_bf16[n * out_stride] = bf16(sum); 1: out_f32[n] = the bf16-rounded sum as f32; 2 (GeGLU): W is [2N][ldw], gate rows then up
+ * rows, out_bf16[n * out_stride] = bf16(bf16(gelu_tanh(bf16(g))) * bf16(u)). Any N; K % 8 == 0, K <= 16384; ldw % 8 == 0. */
+int ltx_op_gemv_bf16(ltx_ctx* ctx, const uint16_t* x, const uint16_t* W, long ldw, int M, int N, int K, int epilogue, uint16_t* out_bf16,
+                     long out_stride, float* out_f32);
+/* output rows per workgroup of that launch (8 or 16): tests place rows on both sides of its multiples. Host-side. */
+int ltx_gemv_bf16_rows_per_workgroup(int N, int epilogue);
+/* ltx_op_attention_decode: one query q [Hq*256] against the first n_keys rows of K [cap][ldk] and columns of Vt [Hkv*256][ldvt]
+ * (ldvt >= n_keys rounded up to 64), O [Hq*256], all bf16; query head h reads K/V head h / (Hq / Hkv), up to 4 per K/V head. K rows and
+ * Vt columns at or past n_keys never influence O, whatever they hold. The split workspace is the context's. */
+int ltx_op_attention_decode(ltx_ctx* ctx, const uint16_t* q, const uint16_t* K, long ldk, const uint16_t* Vt, long ldvt, int Hq, int Hkv,
+                            int n_keys, float scale, uint16_t* O);
+/* ltx_op_lm_pick: repetition penalty (ltx_lm_sample_host's rule, over hist [n_gen] int32; the penalised values are written back to
+ * logits [vocab] f32), then argmax with ties to the lowest index; the token goes to out [1] and to hist[n_gen] (hist NULL: n_gen
+ * must be 0). Logits are finite by construction; what a NaN does to the pick is unspecified. */
+int ltx_op_lm_pick(ltx_ctx* ctx, float* logits, int vocab, int32_t* hist, int n_gen, int context, float penalty, int32_t* out);
 
 /* Test seams of the helper passes around the matrix cores: guidance, scheduler, VAE, latent upscaler and connector. DEVICE pointers
  * throughout; each call is one launch on the context's stream and returns without waiting. A null required pointer or an empty shape

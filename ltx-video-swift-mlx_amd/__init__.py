@@ -364,6 +364,39 @@ def gemma_config(**kw):
     return cfg
 
 
+def lm_params(**kw):
+    """``ltx_lm_params`` with the reference's ``generateTokens`` defaults (512 new tokens, temperature 0.7, top_p 0.95, penalty 1.1,
+    context 64, eos {1}); fields overridden by keyword. ``eos_ids`` may be given as a list of up to 8 ids (sets ``n_eos`` too)."""
+    p = _lib.LmParams()
+    lib.ltx_lm_params_default(C.byref(p))
+    eos = kw.pop("eos_ids", None)
+    for k, v in kw.items():
+        setattr(p, k, v)
+    if eos is not None:
+        eos = [int(e) for e in eos]
+        if len(eos) > 8:
+            raise ValueError("up to 8 stop ids")
+        p.n_eos = len(eos)
+        for i, e in enumerate(eos):
+            p.eos_ids[i] = e
+    return p
+
+
+def lm_sample_host(logits, generated=(), context=64, penalty=1.1, temperature=0.7, top_p=0.95, seed=0, step=0):
+    """``ltx_lm_sample_host``: this library's sampler, pure host code. ``logits`` is a float32 numpy array that the repetition penalty
+    rewrites IN PLACE; returns the token."""
+    assert isinstance(logits, np.ndarray) and logits.dtype == np.float32 and logits.flags["C_CONTIGUOUS"]
+    gen = np.ascontiguousarray(generated, dtype=np.int32)
+    tok = C.c_int32()
+    _check(lib.ltx_lm_sample_host(logits.ctypes.data, logits.size, gen.ctypes.data if gen.size else None, gen.size, context, penalty, temperature,
+                                  top_p, seed, step, C.byref(tok)))
+    return tok.value
+
+
+def gemv_bf16_rows_per_workgroup(N, epilogue=0):
+    return int(lib.ltx_gemv_bf16_rows_per_workgroup(N, epilogue))
+
+
 def rope_tables_1d(T, dim=3840, theta=10000.0, max_pos=4096):
     cos = np.empty((T, dim // 2), dtype=np.float32)
     sin = np.empty((T, dim // 2), dtype=np.float32)
@@ -948,6 +981,76 @@ class Context:
     def op_gemma_embed(self, ids, table, out):
         vocab, D = table.shape
         self._ck(lib.ltx_op_gemma_embed(self._h, _ptr(ids), _ptr(table), ids.numel(), D, vocab, _ptr(out)))
+
+    # ---- Gemma-3 token generation on a KV cache (csrc/gemma.h, second half) ----
+    def lm_begin(self, capacity):
+        self._ck(lib.ltx_lm_begin(self._h, capacity))
+
+    def lm_end(self):
+        """``ltx_lm_end``: the bytes released."""
+        n = C.c_long()
+        self._ck(lib.ltx_lm_end(self._h, C.byref(n)))
+        return n.value
+
+    def lm_memory_info(self):
+        c, w = C.c_long(), C.c_long()
+        self._ck(lib.ltx_lm_memory_info(self._h, C.byref(c), C.byref(w)))
+        return {"cache": c.value, "workspace": w.value}
+
+    def lm_prefill_dev(self, ids, logits=None):
+        """Device tensors: ids [T] int32, logits [vocab] f32 or None."""
+        self._ck(lib.ltx_lm_prefill_dev(self._h, _ptr(ids), ids.numel(), _ptr(logits)))
+
+    def lm_prefill(self, ids, vocab=None):
+        """HOST ids -> the last position's logits [vocab] f32 (None without ``vocab``)."""
+        ids = np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+        out = np.empty(vocab, np.float32) if vocab else None
+        self._ck(lib.ltx_lm_prefill(self._h, _ptr(ids), ids.size, _ptr(out)))
+        return out
+
+    def lm_step_dev(self, token, logits=None):
+        self._ck(lib.ltx_lm_step_dev(self._h, _ptr(token), _ptr(logits)))
+
+    def lm_step(self, token, vocab=None):
+        out = np.empty(vocab, np.float32) if vocab else None
+        self._ck(lib.ltx_lm_step(self._h, int(token), _ptr(out)))
+        return out
+
+    def lm_last_state(self, hidden_size):
+        """model.norm of the newest position: bf16 bits [hidden_size] uint16."""
+        out = np.empty(hidden_size, np.uint16)
+        self._ck(lib.ltx_lm_last_state(self._h, _ptr(out)))
+        return out
+
+    def lm_cache_k(self, layer, rows, width):
+        """Rows 0 .. rows-1 of a layer's K cache: bf16 bits [rows, width] uint16 (width = num_key_value_heads * 256)."""
+        out = np.empty((rows, width), np.uint16)
+        self._ck(lib.ltx_lm_cache_k(self._h, layer, rows, _ptr(out)))
+        return out
+
+    def lm_generate(self, ids, params=None):
+        """``ltx_lm_generate``: HOST ids [T] -> the generated ids (int32 array), stop id excluded."""
+        ids = np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+        if params is None:
+            params = lm_params()
+        out = np.zeros(max(params.max_new_tokens, 1), np.int32)
+        n = C.c_int()
+        self._ck(lib.ltx_lm_generate(self._h, _ptr(ids), ids.size, C.byref(params), _ptr(out), C.byref(n)))
+        return out[:n.value].copy()
+
+    def op_gemv_bf16(self, x, W, N, K, epilogue=0, out_bf16=None, out_stride=1, out_f32=None, ldw=None, M=1):
+        """``ltx_op_gemv_bf16``: x [K] and W [rows, ldw] bf16 device tensors; epilogue 0 bf16 store, 1 f32 store, 2 GeGLU."""
+        self._ck(lib.ltx_op_gemv_bf16(self._h, _dptr(x), _dptr(W), (W.shape[-1] if W is not None else 0) if ldw is None else ldw, M, N, K, epilogue, _dptr(out_bf16), out_stride,
+                                      _dptr(out_f32)))
+
+    def op_attention_decode(self, q, K, Vt, O, Hq, Hkv, n_keys, scale, ldk=None, ldvt=None):
+        """``ltx_op_attention_decode``: q / O [Hq*256], K [cap, ldk], Vt [Hkv*256, ldvt] bf16 device tensors."""
+        self._ck(lib.ltx_op_attention_decode(self._h, _dptr(q), _dptr(K), (K.shape[-1] if K is not None else 0) if ldk is None else ldk, _dptr(Vt),
+                                             (Vt.shape[-1] if Vt is not None else 0) if ldvt is None else ldvt, Hq, Hkv, n_keys, scale, _dptr(O)))
+
+    def op_lm_pick(self, logits, out, hist=None, n_gen=0, context=64, penalty=1.0, vocab=None):
+        """``ltx_op_lm_pick``: logits [vocab] f32 (penalised in place), hist int32 [>= n_gen + 1] or None, out int32 [1]."""
+        self._ck(lib.ltx_op_lm_pick(self._h, _dptr(logits), logits.numel() if vocab is None else vocab, _dptr(hist), n_gen, context, penalty, _dptr(out)))
 
     # ---- helper passes (include/ltxhip.h, "Test seams of the helper passes"): device tensors, sizes given explicitly, so that a
     # tensor may be longer than the pass's extent (guard elements behind it) or a view into a longer one (vae_prepare's chan_stride) ----

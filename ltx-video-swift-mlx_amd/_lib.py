@@ -64,6 +64,14 @@ class GemmaConfig(C.Structure):
                 ("sliding_window", C.c_int), ("sliding_window_pattern", C.c_int)]
 
 
+class LmParams(C.Structure):
+    """``ltx_lm_params``: the generate loop's settings; ``ltx_lm_params_default`` fills the reference's (Gemma3Model.swift:390-398)."""
+
+    _fields_ = [("struct_size", C.c_uint32), ("max_new_tokens", C.c_int), ("temperature", C.c_float), ("top_p", C.c_float),
+                ("repetition_penalty", C.c_float), ("repetition_context", C.c_int), ("seed", C.c_uint64), ("n_eos", C.c_int),
+                ("eos_ids", C.c_int32 * 8)]
+
+
 class TransformerConfig(C.Structure):
     """``ltx_transformer_config`` / reference ``LTXTransformerConfig`` (LTXConfig.swift:83-177)."""
 
@@ -412,6 +420,22 @@ SIGNATURES = {
     "ltx_op_gemma_rope_tables": (_i, [_vp, _i, _f, _vp, _vp]),
     "ltx_op_geglu": (_i, [_vp, _vp, _i, _i, _vp]),
     "ltx_op_gemma_embed": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
+    "ltx_lm_params_default": (None, [C.POINTER(LmParams)]),
+    "ltx_lm_begin": (_i, [_vp, _i]),
+    "ltx_lm_end": (_i, [_vp, C.POINTER(_l)]),
+    "ltx_lm_memory_info": (_i, [_vp, C.POINTER(_l), C.POINTER(_l)]),
+    "ltx_lm_prefill_dev": (_i, [_vp, _vp, _i, _vp]),
+    "ltx_lm_prefill": (_i, [_vp, _vp, _i, _vp]),
+    "ltx_lm_step_dev": (_i, [_vp, _vp, _vp]),
+    "ltx_lm_step": (_i, [_vp, C.c_int32, _vp]),
+    "ltx_lm_last_state": (_i, [_vp, _vp]),
+    "ltx_lm_cache_k": (_i, [_vp, _i, _i, _vp]),
+    "ltx_lm_generate": (_i, [_vp, _vp, _i, C.POINTER(LmParams), _vp, C.POINTER(C.c_int)]),
+    "ltx_lm_sample_host": (_i, [_vp, _i, _vp, _i, _i, _f, _f, _f, _u64, _i, C.POINTER(C.c_int32)]),
+    "ltx_op_gemv_bf16": (_i, [_vp, _vp, _vp, _l, _i, _i, _i, _i, _vp, _l, _vp]),
+    "ltx_gemv_bf16_rows_per_workgroup": (_i, [_i, _i]),
+    "ltx_op_attention_decode": (_i, [_vp, _vp, _vp, _l, _vp, _l, _i, _i, _i, _f, _vp]),
+    "ltx_op_lm_pick": (_i, [_vp, _vp, _i, _vp, _i, _i, _f, _vp]),
     "ltx_op_mean_var": (_i, [_vp, _vp, _l, _i, _vp]),
     "ltx_op_guidance_rescale": (_i, [_vp, _vp, _vp, _vp, _f, _l, _i]),
     "ltx_op_adain": (_i, [_vp, _vp, _vp, _vp, _f, _l, _i]),

@@ -435,6 +435,38 @@ int ltx_op_gemma_embed(ltx_ctx* ctx, const int32_t* ids, const uint16_t* table, 
     });
 }
 
+int ltx_op_gemv_bf16(ltx_ctx* ctx, const uint16_t* x, const uint16_t* W, long ldw, int M, int N, int K, int epilogue, uint16_t* out_bf16,
+                     long out_stride, float* out_f32) {
+    return with_ctx(ctx, [&] {
+        LTX_REQUIRE(M == 1, "ltx_op_gemv_bf16: M=%d (the decode path has one row)", M);
+        GemvBf16Args a;
+        a.x = x; a.W = W; a.ldw = ldw; a.N = N; a.K = K; a.epilogue = epilogue; a.out_bf16 = out_bf16; a.out_stride = out_stride; a.out_f32 = out_f32;
+        launch_gemv_bf16(a, ctx->stream);
+    });
+}
+
+int ltx_gemv_bf16_rows_per_workgroup(int N, int epilogue) { return gemv_bf16_rows_per_workgroup(N, epilogue); }
+
+int ltx_op_attention_decode(ltx_ctx* ctx, const uint16_t* q, const uint16_t* K, long ldk, const uint16_t* Vt, long ldvt, int Hq, int Hkv,
+                            int n_keys, float scale, uint16_t* O) {
+    return with_ctx(ctx, [&] {
+        LTX_REQUIRE(Hq >= 1 && n_keys >= 1 && n_keys <= (1 << 24), "ltx_op_attention_decode: Hq=%d n_keys=%d", Hq, n_keys);
+        ctx->op_ws.ensure((size_t)attn_decode_ws_bytes(Hq, n_keys));
+        AttnDecodeArgs a;
+        a.q = q; a.K = K; a.ldk = ldk; a.Vt = Vt; a.ldvt = ldvt; a.O = O; a.Hq = Hq; a.Hkv = Hkv; a.n_keys = n_keys; a.scale = scale;
+        a.ws = ctx->op_ws.p; a.ws_bytes = (long)ctx->op_ws.bytes;
+        launch_attention_decode(a, ctx->stream);
+    });
+}
+
+int ltx_op_lm_pick(ltx_ctx* ctx, float* logits, int vocab, int32_t* hist, int n_gen, int context, float penalty, int32_t* out) {
+    return with_ctx(ctx, [&] {
+        LmPickArgs a;
+        a.logits = logits; a.vocab = vocab; a.hist = hist; a.n_gen = n_gen; a.context = context; a.penalty = penalty; a.out = out;
+        launch_lm_pick(a, ctx->stream);
+    });
+}
+
 int ltx_attention_hd_workgroup_queries(int B, int H, int Tq, int head_dim) {
     if (B < 1 || H < 1 || Tq < 1 || head_dim != 64) return 0;
     return attn64_queries_per_workgroup(B, H, Tq);

@@ -893,6 +893,149 @@ int ltx_text_av_encode(ltx_ctx* ctx, const int32_t* token_ids, const int32_t* at
     return with_ctx(ctx, [&] { text_encode_host_body(ctx, token_ids, attention_mask, B, T, video_context, true, audio_context, out_mask); });
 }
 
+/* ---- Gemma-3 token generation (prompt enhancement) ---- */
+void ltx_lm_params_default(ltx_lm_params* p) {
+    if (!p) return;
+    const GemmaLmParams d;
+    memset(p, 0, sizeof(*p));
+    p->struct_size = (uint32_t)sizeof(*p);
+    p->max_new_tokens = d.max_new; p->temperature = d.temperature; p->top_p = d.top_p; p->repetition_penalty = d.penalty;
+    p->repetition_context = d.context; p->seed = d.seed; p->n_eos = d.n_eos;
+    for (int i = 0; i < 8; ++i) p->eos_ids[i] = d.eos[i];
+}
+
+int ltx_lm_begin(ltx_ctx* ctx, int capacity) {
+    return with_ctx(ctx, [&] { gemma_lm_begin(ctx, need(ctx->gemma, kNoGemma), capacity); });
+}
+
+int ltx_lm_end(ltx_ctx* ctx, long* freed_bytes) {
+    return with_ctx(ctx, [&] {
+        if (freed_bytes) *freed_bytes = 0;
+        const size_t n = gemma_lm_end(ctx, need(ctx->gemma, kNoGemma));
+        if (freed_bytes) *freed_bytes = (long)n;
+    });
+}
+
+int ltx_lm_memory_info(ltx_ctx* ctx, long* cache_bytes, long* workspace_bytes) {
+    return with_ctx(ctx, [&] {
+        if (cache_bytes) *cache_bytes = 0;
+        if (workspace_bytes) *workspace_bytes = 0;
+        const GemmaLm* lm = need(ctx->gemma, kNoGemma)->lm;
+        if (cache_bytes) *cache_bytes = lm ? (long)lm->cache_bytes() : 0;
+        if (workspace_bytes) *workspace_bytes = lm ? (long)lm->workspace_bytes() : 0;
+    });
+}
+
+namespace {
+GemmaModel* need_lm(ltx_ctx* ctx, const char* who) {
+    GemmaModel* m = need(ctx->gemma, kNoGemma);
+    LTX_REQUIRE(m->lm != nullptr, "%s: no generation session (ltx_lm_begin)", who);
+    return m;
+}
+void lm_logits_out(ltx_ctx* ctx, GemmaModel* m, float* logits, bool host) {
+    if (!logits) return;
+    HIP_CHECK(hipMemcpyAsync(logits, m->lm->logits.p, (size_t)m->cfg.vocab * 4, host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, ctx->stream));
+    if (host) stage_sync(ctx);
+}
+}  // namespace
+
+int ltx_lm_prefill_dev(ltx_ctx* ctx, const int32_t* ids, int T, float* logits) {
+    return with_ctx(ctx, [&] {
+        GemmaModel* m = need_lm(ctx, "ltx_lm_prefill_dev");
+        gemma_lm_prefill(ctx, m, ids, T);
+        lm_logits_out(ctx, m, logits, false);
+    });
+}
+
+int ltx_lm_prefill(ltx_ctx* ctx, const int32_t* ids, int T, float* logits) {
+    return with_ctx(ctx, [&] {
+        GemmaModel* m = need_lm(ctx, "ltx_lm_prefill");
+        LTX_REQUIRE(ids && T >= 1 && T <= m->lm->cap, "ltx_lm_prefill: null ids, an empty prompt or %d tokens above the session's capacity %d", T, m->lm->cap);
+        for (int i = 0; i < T; ++i)
+            LTX_REQUIRE(ids[i] >= 0 && ids[i] < m->cfg.vocab, "ltx_lm_prefill: token id %d at position %d is outside the vocabulary of %d", ids[i], i, m->cfg.vocab);
+        if (T > m->cfg.sliding_window) LTX_THROW(LTXS_INVALID_CONFIGURATION, "lm_prefill: %d tokens exceed the sliding window %d", T, m->cfg.sliding_window);
+        int32_t* d_ids = m->lm->hist.as<int32_t>();  // the history is unused until the first pick, and holds cap + 2 entries
+        HIP_CHECK(hipMemcpyAsync(d_ids, ids, (size_t)T * 4, hipMemcpyHostToDevice, ctx->stream));
+        gemma_lm_prefill(ctx, m, d_ids, T);
+        lm_logits_out(ctx, m, logits, true);
+        stage_sync(ctx);  // ids is the caller's
+    });
+}
+
+int ltx_lm_step_dev(ltx_ctx* ctx, const int32_t* token, float* logits) {
+    return with_ctx(ctx, [&] {
+        GemmaModel* m = need_lm(ctx, "ltx_lm_step_dev");
+        gemma_lm_step(ctx, m, token);
+        lm_logits_out(ctx, m, logits, false);
+    });
+}
+
+int ltx_lm_step(ltx_ctx* ctx, int32_t token, float* logits) {
+    return with_ctx(ctx, [&] {
+        GemmaModel* m = need_lm(ctx, "ltx_lm_step");
+        LTX_REQUIRE(token >= 0 && token < m->cfg.vocab, "ltx_lm_step: token id %d is outside the vocabulary of %d", token, m->cfg.vocab);
+        LTX_REQUIRE(m->lm->len >= 1 && m->lm->len < m->lm->cap, "ltx_lm_step: no prompt in the session, or the cache is full (%d of %d positions)",
+                    m->lm->len, m->lm->cap);
+        int32_t* d_tok = m->lm->hist.as<int32_t>() + m->lm->cap;  // the staged-token entry
+        HIP_CHECK(hipMemcpyAsync(d_tok, &token, 4, hipMemcpyHostToDevice, ctx->stream));
+        gemma_lm_step(ctx, m, d_tok);
+        lm_logits_out(ctx, m, logits, true);
+        stage_sync(ctx);  // token is a parameter of this call
+    });
+}
+
+int ltx_lm_last_state(ltx_ctx* ctx, uint16_t* state) {
+    return with_ctx(ctx, [&] {
+        GemmaModel* m = need_lm(ctx, "ltx_lm_last_state");
+        LTX_REQUIRE(state && m->lm->len >= 1, "ltx_lm_last_state: null output or no prompt in the session");
+        HIP_CHECK(hipMemcpyAsync(state, gemma_lm_state(m), (size_t)m->cfg.hidden * 2, hipMemcpyDeviceToHost, ctx->stream));
+        stage_sync(ctx);
+    });
+}
+
+int ltx_lm_cache_k(ltx_ctx* ctx, int layer, int rows, uint16_t* k) {
+    return with_ctx(ctx, [&] {
+        GemmaModel* m = need_lm(ctx, "ltx_lm_cache_k");
+        LTX_REQUIRE(k && layer >= 0 && layer < m->cfg.layers && rows >= 1 && rows <= m->lm->len, "ltx_lm_cache_k: layer %d, %d rows of %d filled", layer, rows,
+                    m->lm->len);
+        const size_t Dk = (size_t)m->cfg.kv_heads * 256;
+        HIP_CHECK(hipMemcpyAsync(k, m->lm->kc.as<bf16_t>() + (size_t)layer * m->lm->cap * Dk, (size_t)rows * Dk * 2, hipMemcpyDeviceToHost, ctx->stream));
+        stage_sync(ctx);
+    });
+}
+
+int ltx_lm_generate(ltx_ctx* ctx, const int32_t* ids, int T, const ltx_lm_params* params, int32_t* out_tokens, int* n_out) {
+    return with_ctx(ctx, [&] {
+        if (n_out) *n_out = 0;
+        GemmaModel* m = need_lm(ctx, "ltx_lm_generate");
+        LTX_REQUIRE(n_out != nullptr, "ltx_lm_generate: null n_out");
+        GemmaLmParams p;
+        if (params) {
+            const size_t sz = params->struct_size;
+            LTX_REQUIRE(sz >= offsetof(ltx_lm_params, eos_ids) + sizeof(params->eos_ids) && sz <= 4096,
+                        "ltx_lm_params.struct_size = %zu: set it to sizeof(ltx_lm_params) (ltx_lm_params_default); this library is ABI revision %d", sz,
+                        LTX_ABI_VERSION);
+            LTX_REQUIRE(params->n_eos >= 0 && params->n_eos <= 8, "ltx_lm_generate: %d stop ids (up to 8)", params->n_eos);
+            p.max_new = params->max_new_tokens; p.temperature = params->temperature; p.top_p = params->top_p; p.penalty = params->repetition_penalty;
+            p.context = params->repetition_context; p.seed = params->seed; p.n_eos = params->n_eos;
+            for (int i = 0; i < 8; ++i) p.eos[i] = params->eos_ids[i];
+        }
+        *n_out = gemma_lm_generate(ctx, m, ids, T, p, out_tokens);
+    });
+}
+
+int ltx_lm_sample_host(float* logits, int vocab, const int32_t* generated, int n_generated, int context, float penalty, float temperature,
+                       float top_p, uint64_t seed, int step, int32_t* token) {
+    return guarded(nullptr, [&] {
+        LTX_REQUIRE(logits && token && vocab >= 1, "ltx_lm_sample_host: null logits / token or an empty vocabulary");
+        LTX_REQUIRE(n_generated >= 0 && context >= 0 && (generated || n_generated == 0), "ltx_lm_sample_host: n_generated=%d context=%d need the tokens", n_generated,
+                    context);
+        LTX_REQUIRE(penalty > 0.f && (temperature <= 0.f || (top_p > 0.f && top_p <= 1.f)), "ltx_lm_sample_host: penalty %g must be positive, top_p %g in (0, 1]",
+                    (double)penalty, (double)top_p);
+        *token = lm_sample_host(logits, vocab, generated, n_generated, context, penalty, temperature, top_p, seed, step);
+    });
+}
+
 /* ---- VAE encoder ---- */
 int ltx_vae_encoder_load(ltx_ctx* ctx, const char* path, int channel_base) {
     if (!ctx || !path) return LTX_ERR_INVALID_CONFIGURATION;

@@ -54,3 +54,25 @@ constexpr float kAttnQueryPrescale64 = 0.125f * 1.4426950408889634f;
 int attn64_queries_per_workgroup(int B, int H, int Tq);
 
 void launch_attention(const AttnArgs& args, hipStream_t stream);
+
+// Head-dim-256 attention decode (token generation on a KV cache): one query per head against the first n_keys rows of a cache.
+// Query head h reads K/V head h / (Hq / Hkv); at most 4 query heads per K/V head. P stays f32. The keys are cut into splits of 64, one
+// workgroup per (split, K/V head); a second small launch combines the splits' (m, l, o) exactly. Cache rows of K and columns of V^T
+// at or past n_keys never influence the result, whatever bits they hold: the rows are not read, the columns are replaced by select.
+struct AttnDecodeArgs {
+    const bf16_t* q = nullptr;   // [Hq * 256]
+    const bf16_t* K = nullptr;   // [cap][ldk], K/V head h at columns h * 256 ..
+    long ldk = 0;
+    const bf16_t* Vt = nullptr;  // [Hkv * 256][ldvt], keys contiguous, ldvt >= roundup(n_keys, 64)
+    long ldvt = 0;
+    bf16_t* O = nullptr;         // [Hq * 256]
+    int Hq = 0, Hkv = 0, n_keys = 0;
+    float scale = 0.0625f;
+    void* ws = nullptr;          // attn_decode_ws_bytes(Hq, n_keys) bytes, 16-byte aligned
+    long ws_bytes = 0;
+    // set by the launcher
+    float* part_o = nullptr;     // [splits][Hq][256] unnormalised outputs
+    float* part_ml = nullptr;    // [splits][Hq][2] maximum, denominator
+};
+long attn_decode_ws_bytes(int Hq, int n_keys);
+void launch_attention_decode(const AttnDecodeArgs& args, hipStream_t stream);

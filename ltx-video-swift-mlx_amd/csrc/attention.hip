@@ -1381,3 +1381,174 @@ void launch_attention(const AttnArgs& a_in, hipStream_t stream) {
         hipLaunchKernelGGL((attn_fwd_kernel<false>), grid, dim3(256), lds, stream, a);
     HIP_CHECK(hipGetLastError());
 }
+
+// ---------------------------------------------------------------------------------------------------------------
+// Head-dim-256 attention decode (attention.h, AttnDecodeArgs): ONE query per head against n_keys cached keys. A weight-free copy
+// kernel: K and V^T go straight to VGPRs, and the (up to 4) query heads of a group share one read of their K/V head. The key range
+// is cut into splits of 64 keys, one workgroup of 4 waves per (split, K/V head), so 8 K/V heads x 24 splits fill the chip at 1536
+// keys.
+//   scores: half a wave per key (32 lanes x 16 bytes = one 256-wide row), 16 keys per wave, all 8 row loads of a wave issued before
+//           the first product; the 32-lane sums go to LDS as f32 scores, -inf (by select) for keys at or past n_keys, whose rows are
+//           never read (the row index is clamped).
+//   P:      every wave forms the split's maximum, p = exp(s - m) (0 by select past n_keys) and l = sum p from the 64 scores. f32, never
+//           rounded: there is no MFMA here.
+//   P.V:    thread d of 256 reads the 64 keys of V^T row d (128 contiguous bytes) and accumulates o[g][d] = sum_j p[g][j] v[d][j];
+//           columns at or past n_keys are replaced by 0 by select, so neither an Inf nor a NaN behind the cache's end reaches a sum.
+// Each split leaves (m, l) and its unnormalised o; attn256_decode_combine_kernel - a SECOND small launch, one workgroup per query
+// head - forms o = sum_s o_s e^(m_s - m) / sum_s l_s e^(m_s - m) with m = max m_s, exact in form, and rounds to bf16 once.
+// ---------------------------------------------------------------------------------------------------------------
+namespace {
+constexpr int DEC_KEYS = 64;  // keys per split
+constexpr int DEC_GMAX = 4;   // most query heads per K/V head (the kernel is instantiated for 1 .. 4)
+
+LTX_DEVFN void dec_unpack8(const uint4 u, float (&v)[8]) {
+    const uint32_t w[4] = {u.x, u.y, u.z, u.w};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        v[2 * i] = __builtin_bit_cast(float, w[i] << 16);
+        v[2 * i + 1] = __builtin_bit_cast(float, w[i] & 0xffff0000u);
+    }
+}
+
+template <int G>  // query heads per K/V head
+__global__ __launch_bounds__(256) void attn256_decode_kernel(const AttnDecodeArgs a) {
+    __shared__ __attribute__((aligned(16))) float sc[G][DEC_KEYS];
+    const int split = blockIdx.x, hk = blockIdx.y;
+    const int key0 = split * DEC_KEYS;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int half = lane >> 5, sub = lane & 31;
+    const float ninf = -__builtin_inff();
+
+    // ---- scores ----
+    float q[G][8];
+#pragma unroll
+    for (int g = 0; g < G; ++g) dec_unpack8(*(const uint4*)(a.q + (long)(hk * G + g) * 256 + sub * 8), q[g]);
+    uint4 kv[8];
+#pragma unroll
+    for (int it = 0; it < 8; ++it) {
+        int key = key0 + wave * 16 + it * 2 + half;
+        key = key < a.n_keys ? key : a.n_keys - 1;
+        kv[it] = *(const uint4*)(a.K + (long)key * a.ldk + hk * 256 + sub * 8);
+    }
+#pragma unroll
+    for (int it = 0; it < 8; ++it) {
+        float kf[8];
+        dec_unpack8(kv[it], kf);
+        const int local = wave * 16 + it * 2 + half;
+        const bool valid = key0 + local < a.n_keys;
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            float s = 0.f;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) s = __builtin_fmaf(q[g][e], kf[e], s);
+#pragma unroll
+            for (int off = 16; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+            if (sub == 0) sc[g][local] = valid ? s * a.scale : ninf;
+        }
+    }
+    __syncthreads();
+
+    // ---- P (every wave the same values; the first key of a split is always valid, so m is finite) ----
+    float m[G], l[G];
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+        const float s = sc[g][lane];
+        m[g] = wave_reduce_max(s);
+        const float p = key0 + lane < a.n_keys ? __expf(s - m[g]) : 0.f;
+        l[g] = wave_reduce_sum(p);
+    }
+    __syncthreads();  // every wave has read the scores
+    if (wave == 0) {
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            const float s = sc[g][lane];
+            sc[g][lane] = key0 + lane < a.n_keys ? __expf(s - m[g]) : 0.f;
+        }
+    }
+    __syncthreads();
+
+    // ---- P.V: thread d owns V^T row d of this K/V head ----
+    const int d = threadIdx.x;
+    const bf16_t* vrow = a.Vt + (long)(hk * 256 + d) * a.ldvt + key0;
+    uint4 vv[8];
+#pragma unroll
+    for (int c = 0; c < 8; ++c) vv[c] = *(const uint4*)(vrow + c * 8);
+    float o[G];
+#pragma unroll
+    for (int g = 0; g < G; ++g) o[g] = 0.f;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+        float vf[8];
+        dec_unpack8(vv[c], vf);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) vf[e] = key0 + c * 8 + e < a.n_keys ? vf[e] : 0.f;
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            const f32x4 p0 = *(const f32x4*)&sc[g][c * 8], p1 = *(const f32x4*)&sc[g][c * 8 + 4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) o[g] = __builtin_fmaf(p0[e], vf[e], o[g]);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) o[g] = __builtin_fmaf(p1[e], vf[4 + e], o[g]);
+        }
+    }
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+        const long slot = (long)split * a.Hq + hk * G + g;
+        a.part_o[slot * 256 + d] = o[g];
+        if (d == 0) {
+            a.part_ml[slot * 2] = m[g];
+            a.part_ml[slot * 2 + 1] = l[g];
+        }
+    }
+}
+
+// one workgroup per query head, thread d: the exact combine of the splits' (m, l, o)
+__global__ __launch_bounds__(256) void attn256_decode_combine_kernel(const AttnDecodeArgs a, int splits) {
+    const int h = blockIdx.x, d = threadIdx.x;
+    float m = -__builtin_inff();
+    for (int s = 0; s < splits; ++s) m = fmaxf(m, a.part_ml[((long)s * a.Hq + h) * 2]);
+    float num = 0.f, den = 0.f;
+    for (int s = 0; s < splits; ++s) {
+        const long slot = (long)s * a.Hq + h;
+        const float w = __expf(a.part_ml[slot * 2] - m);
+        num = __builtin_fmaf(a.part_o[slot * 256 + d], w, num);
+        den = __builtin_fmaf(a.part_ml[slot * 2 + 1], w, den);
+    }
+    a.O[(long)h * 256 + d] = f32_to_bf16(__fdiv_rn(num, den));
+}
+}  // namespace
+
+long attn_decode_ws_bytes(int Hq, int n_keys) {
+    const long splits = (n_keys + DEC_KEYS - 1) / DEC_KEYS;
+    return splits * Hq * (256 + 2) * 4;
+}
+
+void launch_attention_decode(const AttnDecodeArgs& args, hipStream_t stream) {
+    // every check comes before the first launch: a refused call writes nothing
+    LTX_REQUIRE(args.q && args.K && args.Vt && args.O && args.ws, "attention decode: null argument");
+    LTX_REQUIRE(args.Hq >= 1 && args.Hkv >= 1 && args.Hq % args.Hkv == 0 && args.Hq / args.Hkv <= DEC_GMAX,
+                "attention decode: %d query heads over %d K/V heads (a whole number of up to %d per K/V head)", args.Hq, args.Hkv, DEC_GMAX);
+    LTX_REQUIRE(args.n_keys >= 1, "attention decode: n_keys=%d", args.n_keys);
+    LTX_REQUIRE(args.ldk % 8 == 0 && args.ldk >= (long)args.Hkv * 256, "attention decode: ldk=%ld must be a multiple of 8, at least %d", args.ldk, args.Hkv * 256);
+    const long kpad = (long)(args.n_keys + DEC_KEYS - 1) / DEC_KEYS * DEC_KEYS;
+    LTX_REQUIRE(args.ldvt % 8 == 0 && args.ldvt >= kpad, "attention decode: ldvt=%ld must be a multiple of 8, at least n_keys rounded up to 64 (%ld)", args.ldvt, kpad);
+    LTX_REQUIRE(((uintptr_t)args.q & 15) == 0 && ((uintptr_t)args.K & 15) == 0 && ((uintptr_t)args.Vt & 15) == 0 && ((uintptr_t)args.ws & 15) == 0,
+                "attention decode: q / K / Vt / workspace must be 16-byte aligned");
+    LTX_REQUIRE(args.ws_bytes >= attn_decode_ws_bytes(args.Hq, args.n_keys), "attention decode: workspace of %ld bytes, %ld needed", args.ws_bytes,
+                attn_decode_ws_bytes(args.Hq, args.n_keys));
+    AttnDecodeArgs a = args;
+    const int splits = (a.n_keys + DEC_KEYS - 1) / DEC_KEYS;
+    a.part_o = (float*)a.ws;
+    a.part_ml = a.part_o + (long)splits * a.Hq * 256;
+    ProfScope prof(PROF_ATTN, 4.0 * a.Hq * (double)a.n_keys * 256, stream);
+    const dim3 grid(splits, a.Hkv), block(256);
+    switch (a.Hq / a.Hkv) {
+        case 1: hipLaunchKernelGGL(attn256_decode_kernel<1>, grid, block, 0, stream, a); break;
+        case 2: hipLaunchKernelGGL(attn256_decode_kernel<2>, grid, block, 0, stream, a); break;
+        case 3: hipLaunchKernelGGL(attn256_decode_kernel<3>, grid, block, 0, stream, a); break;
+        default: hipLaunchKernelGGL(attn256_decode_kernel<4>, grid, block, 0, stream, a); break;
+    }
+    HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(attn256_decode_combine_kernel, dim3(a.Hq), dim3(256), 0, stream, a, splits);
+    HIP_CHECK(hipGetLastError());
+}

@@ -323,6 +323,23 @@ struct GemmaEmbedArgs {
 };
 void launch_gemma_embed(const GemmaEmbedArgs& args, hipStream_t stream);
 
+// Greedy token pick on the device (Gemma3Model.swift:438-467): the repetition penalty, then argmax, so a generated token costs the
+// host one 4-byte read. hist holds the tokens generated so far; the penalty goes to every DISTINCT id among its last
+// min(context, n_gen) entries: l > 0 ? l / penalty (IEEE division) : l * penalty. Nothing is applied while n_gen == 0 or when
+// penalty == 1; ids outside [0, vocab) are passed over. The penalised values are written back into `logits` (the reference makes a
+// penalised copy; the buffer is refilled by the next step). Argmax ties go to the LOWEST index. The logits are finite by construction
+// (a bf16 dot product of finite values); what a NaN does to the pick is unspecified. The token goes to *out and, when hist is
+// given, to hist[n_gen] - where the next step's embedding reads it. One workgroup of 1024 threads; logits 16-byte aligned.
+struct LmPickArgs {
+    float* logits = nullptr;   // [vocab]
+    int vocab = 0;
+    int32_t* hist = nullptr;   // [>= n_gen + 1] or null (then n_gen must be 0)
+    int n_gen = 0, context = 0;
+    float penalty = 1.0f;
+    int32_t* out = nullptr;    // [1]
+};
+void launch_lm_pick(const LmPickArgs& args, hipStream_t stream);
+
 // Left-padded mask 0..0 1..1 -> key_start[b] = index of the first 1; status[b] = 1 when row b is of that form with at least one 1
 // (values 0 / 1 only), else 0. One workgroup per batch element.
 void launch_gemma_mask_scan(const int32_t* mask, int B, int T, int32_t* key_start, int32_t* status, hipStream_t stream);

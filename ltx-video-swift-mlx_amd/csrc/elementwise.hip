@@ -1893,6 +1893,58 @@ __global__ __launch_bounds__(256) void gemma_mask_scan_kernel(const int32_t* __r
         status[blockIdx.x] = (!bad && ones >= 1 && first == T - ones) ? 1 : 0;  // every position from the first 1 on is a 1
     }
 }
+
+// (value, index) order of the argmax: the greater value, and the LOWER index among equal values
+LTX_DEVFN void pick_better(float& v, int& i, float v2, int i2) {
+    if (v2 > v || (v2 == v && i2 < i)) {
+        v = v2;
+        i = i2;
+    }
+}
+// one workgroup of 1024 threads. Phase 1: the penalty, in place - the thread that holds the FIRST occurrence of an id among the
+// recent tokens rewrites that logit, so an id that occurs twice is penalised once. Phase 2 (behind the barrier): per-thread argmax
+// over 16-byte vectors in ascending index order, then the wave and workgroup reductions in the order above.
+__global__ __launch_bounds__(1024) void lm_pick_kernel(const LmPickArgs a) {
+    __shared__ float best_v[16];
+    __shared__ int best_i[16];
+    const int tid = threadIdx.x;
+    const int n_recent = a.n_gen < a.context ? a.n_gen : a.context;
+    if (a.penalty != 1.0f && n_recent > 0) {
+        const int32_t* recent = a.hist + (a.n_gen - n_recent);
+        for (int t = tid; t < n_recent; t += 1024) {
+            const int id = recent[t];
+            bool first = id >= 0 && id < a.vocab;
+            for (int u = 0; u < t && first; ++u) first = recent[u] != id;
+            if (first) {
+                const float l = a.logits[id];
+                a.logits[id] = l > 0.f ? __fdiv_rn(l, a.penalty) : l * a.penalty;
+            }
+        }
+    }
+    __syncthreads();  // the rewritten logits are visible to the workgroup
+    float v = -__builtin_inff();
+    int idx = 0x7fffffff;
+    const int nvec = a.vocab >> 2;
+    for (int c = tid; c < nvec; c += 1024) {
+        const f32x4 x = *(const f32x4*)(a.logits + 4 * c);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) pick_better(v, idx, x[e], 4 * c + e);
+    }
+    for (int i = 4 * nvec + tid; i < a.vocab; i += 1024) pick_better(v, idx, a.logits[i], i);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) pick_better(v, idx, __shfl_xor(v, off, 64), __shfl_xor(idx, off, 64));
+    if ((tid & 63) == 0) {
+        best_v[tid >> 6] = v;
+        best_i[tid >> 6] = idx;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        for (int w = 1; w < 16; ++w) pick_better(v, idx, best_v[w], best_i[w]);
+        if (idx == 0x7fffffff) idx = 0;  // nothing compared greater than -inf
+        *a.out = idx;
+        if (a.hist) a.hist[a.n_gen] = idx;
+    }
+}
 }  // namespace
 
 void launch_gemma_norm(const GemmaNormArgs& a, hipStream_t stream) {
@@ -1944,6 +1996,15 @@ void launch_gemma_embed(const GemmaEmbedArgs& a, hipStream_t stream) {
     LTX_REQUIRE(a.ids && a.table && a.out && a.rows > 0 && a.vocab > 0, "gemma_embed: null argument");
     LTX_REQUIRE(a.D % 8 == 0 && a.D >= 8, "gemma_embed: D %d must be a multiple of 8", a.D);
     hipLaunchKernelGGL(gemma_embed_kernel, dim3(a.rows), dim3(256), 0, stream, a);
+    HIP_CHECK(hipGetLastError());
+}
+
+void launch_lm_pick(const LmPickArgs& a, hipStream_t stream) {
+    LTX_REQUIRE(a.logits && a.out && a.vocab >= 1, "lm_pick: null logits / out or an empty vocabulary");
+    LTX_REQUIRE(((uintptr_t)a.logits & 15) == 0, "lm_pick: logits must be 16-byte aligned");
+    LTX_REQUIRE(a.n_gen >= 0 && a.context >= 0 && (a.hist || a.n_gen == 0), "lm_pick: n_gen=%d context=%d need a history buffer", a.n_gen, a.context);
+    LTX_REQUIRE(a.penalty > 0.f, "lm_pick: penalty %g must be positive", (double)a.penalty);
+    hipLaunchKernelGGL(lm_pick_kernel, dim3(1), dim3(1024), 0, stream, a);
     HIP_CHECK(hipGetLastError());
 }
 

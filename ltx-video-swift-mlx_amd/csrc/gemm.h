@@ -241,3 +241,27 @@ struct GemvGroupQ {
     int M;
 };
 void launch_gemv_group_q(const GemvJobQ* jobs, int n_jobs, int M, int bits, hipStream_t stream);
+
+// Decode path (M = 1): out[n] = sum_k x[k] * W[n][k], bf16 x bf16 with f32 accumulation and ONE rounding at the store. A bandwidth
+// kernel (gemv_bf16_kernel): every weight byte is read once, 16 bytes per lane straight to registers through the non-temporal policy
+// (as the few-row GEMM's b_nt), 16 weight vectors in flight per lane; the activation row is read once per workgroup into LDS and
+// shared by its 4 waves. A wave owns 2 or 4 adjacent weight rows. Epilogues:
+//   GEMV_EPI_BF16:  out_bf16[n * out_stride] = bf16(sum)            (out_stride > 1 scatters, e.g. into one column of a V^T cache)
+//   GEMV_EPI_F32:   out_f32[n] = float(bf16(sum))                   (the logits: the bf16 value MLX's asLinear yields, held as f32)
+//   GEMV_EPI_GEGLU: W is a fused gate|up matrix [2N][ldw]; g = row n, u = row N + n;
+//                   out_bf16[n * out_stride] = bf16(bf16(gelu_tanh(bf16(g))) * bf16(u))   (geglu_kernel behind the GEMM's bf16 store)
+// N is free; K % 8 == 0, K <= 16384, ldw % 8 == 0, ldw >= K; x and W 16-byte aligned. Throws before the launch otherwise.
+enum { GEMV_EPI_BF16 = 0, GEMV_EPI_F32 = 1, GEMV_EPI_GEGLU = 2 };
+struct GemvBf16Args {
+    const bf16_t* x = nullptr;  // [K]
+    const bf16_t* W = nullptr;  // [N][ldw] ([2N][ldw] with GEMV_EPI_GEGLU)
+    long ldw = 0;
+    int N = 0, K = 0;
+    int epilogue = GEMV_EPI_BF16;
+    bf16_t* out_bf16 = nullptr;
+    long out_stride = 1;
+    float* out_f32 = nullptr;
+};
+// output rows one workgroup of the launch owns (8 or 16; tests place rows on both sides of its multiples)
+int gemv_bf16_rows_per_workgroup(int N, int epilogue);
+void launch_gemv_bf16(const GemvBf16Args& args, hipStream_t stream);

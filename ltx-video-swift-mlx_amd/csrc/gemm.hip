@@ -1415,6 +1415,100 @@ __global__ __launch_bounds__(256) void gemv_group_kernel(const GemvGroup g) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// decode path, M = 1, bf16 x bf16 -> bf16 (gemm.h, GemvBf16Args): token generation reads every weight once per token, so this is a
+// copy kernel with a dot product attached. The activation row goes to LDS once per workgroup (K <= 16384: 32 KB); a wave owns NR
+// weight rows and walks K in trips of 512 (lane * 8 + 512 * trip, 16 bytes per lane). All NR * UN weight vectors of a chunk are
+// issued before the first fma - straight to VGPRs, non-temporal, no LDS round trip - and the x vector of a trip is one ds_read_b128
+// shared by the NR rows. NR * UN = 16 vectors (64 VGPRs) in flight per lane. Rows at or past N are clamped to row N - 1 for the
+// loads (the address stays inside W) and their stores are skipped.
+// ---------------------------------------------------------------------------------------------------------------
+typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;  // the non-temporal builtin takes clang vectors, not HIP's uint4
+LTX_DEVFN void gemv_bf16_fma8(const u32x4 w, const u32x4 x, float& acc) {
+    const uint32_t wv[4] = {w[0], w[1], w[2], w[3]}, xv[4] = {x[0], x[1], x[2], x[3]};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        acc = __builtin_fmaf(__builtin_bit_cast(float, xv[i] << 16), __builtin_bit_cast(float, wv[i] << 16), acc);
+        acc = __builtin_fmaf(__builtin_bit_cast(float, xv[i] & 0xffff0000u), __builtin_bit_cast(float, wv[i] & 0xffff0000u), acc);
+    }
+}
+template <int NR, int UN>
+LTX_DEVFN void gemv_bf16_chunk(const bf16_t* const (&wrow)[NR], const u32x4* xs, int k, float (&acc)[NR]) {
+    u32x4 wv[UN][NR];
+#pragma unroll
+    for (int i = 0; i < UN; ++i)
+#pragma unroll
+        for (int r = 0; r < NR; ++r) wv[i][r] = __builtin_nontemporal_load((const u32x4*)(wrow[r] + k + 512 * i));
+#pragma unroll
+    for (int i = 0; i < UN; ++i) {
+        const u32x4 x = xs[(k >> 3) + 64 * i];
+#pragma unroll
+        for (int r = 0; r < NR; ++r) gemv_bf16_fma8(wv[i][r], x, acc[r]);
+    }
+}
+LTX_DEVFN float gemv_bf16_round(float v) { return bf16_to_f32(f32_to_bf16(v)); }
+
+// NR weight rows per wave; GEGLU: rows 0 .. NR/2-1 are gate rows n, rows NR/2 .. are up rows N + n of the same outputs
+template <int NR, bool GEGLU>
+__global__ __launch_bounds__(256) void gemv_bf16_kernel(const GemvBf16Args a) {
+    __shared__ u32x4 xs[2048];
+    constexpr int NO = GEGLU ? NR / 2 : NR;  // outputs per wave
+    constexpr int UN = 16 / NR;
+    const int K = a.K, N = a.N;
+    for (int c = threadIdx.x; c < (K >> 3); c += 256) xs[c] = ((const u32x4*)a.x)[c];
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const long n0 = ((long)blockIdx.x * 4 + (threadIdx.x >> 6)) * NO;
+    if (n0 >= N) return;
+    const bf16_t* wrow[NR];
+#pragma unroll
+    for (int r = 0; r < NR; ++r) {
+        long n = n0 + (r % NO);
+        n = n < N ? n : N - 1;
+        if (GEGLU && r >= NO) n += N;
+        wrow[r] = a.W + n * a.ldw;
+    }
+    float acc[NR];
+#pragma unroll
+    for (int r = 0; r < NR; ++r) acc[r] = 0.f;
+    // whole chunks need no lane predicate: kb is uniform and every lane's k of the chunk is below K
+    int kb = 0;
+    for (; kb + 512 * UN <= K; kb += 512 * UN) gemv_bf16_chunk<NR, UN>(wrow, xs, kb + lane * 8, acc);
+    if constexpr (UN > 4) {
+        if (kb + 2048 <= K) {
+            gemv_bf16_chunk<NR, 4>(wrow, xs, kb + lane * 8, acc);
+            kb += 2048;
+        }
+    }
+    if constexpr (UN > 2) {
+        if (kb + 1024 <= K) {
+            gemv_bf16_chunk<NR, 2>(wrow, xs, kb + lane * 8, acc);
+            kb += 1024;
+        }
+    }
+    if (kb + 512 <= K) {
+        gemv_bf16_chunk<NR, 1>(wrow, xs, kb + lane * 8, acc);
+        kb += 512;
+    }
+    if (kb + lane * 8 < K) gemv_bf16_chunk<NR, 1>(wrow, xs, kb + lane * 8, acc);  // the partly filled last trip
+#pragma unroll
+    for (int r = 0; r < NR; ++r) acc[r] = wave_reduce_sum(acc[r]);
+    if (lane != 0) return;
+#pragma unroll
+    for (int o = 0; o < NO; ++o) {
+        const long n = n0 + o;
+        if (n >= N) break;
+        if constexpr (GEGLU) {
+            const float g = gemv_bf16_round(acc[o]), u = gemv_bf16_round(acc[NO + o]);
+            a.out_bf16[n * a.out_stride] = f32_to_bf16(gemv_bf16_round(gelu_tanh(g)) * u);
+        } else if (a.epilogue == GEMV_EPI_F32) {
+            a.out_f32[n] = gemv_bf16_round(acc[o]);
+        } else {
+            a.out_bf16[n * a.out_stride] = f32_to_bf16(acc[o]);
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // grouped small-M path on affine-quantised weights (gemm.h, GemvJobQ): gemv_group_kernel with the weights read as codes. A lane's 8
 // weights of a trip (k = lane * 8 + 512 * trip) lie in ONE 64-wide group, so a trip costs the lane one 8-byte (8 bits) or 4-byte
 // (4 bits) code load and one scale / bias pair. Each weight is rebuilt as bf16(q * scale + bias) - the value launch_dequant writes;
@@ -2241,6 +2335,29 @@ void launch_gemv_group(const GemvJob* jobs, int n_jobs, int M, hipStream_t strea
         hipLaunchKernelGGL((gemv_group_kernel<2>), dim3((unsigned)wgs), dim3(256), 0, stream, g);
     else
         hipLaunchKernelGGL((gemv_group_kernel<8>), dim3((unsigned)wgs), dim3(256), 0, stream, g);
+    HIP_CHECK(hipGetLastError());
+}
+
+// 4 rows per wave once that still gives 1024 workgroups (the logits: 16 388 of them); 2 below, so that a 3840-row Linear is 480
+int gemv_bf16_rows_per_workgroup(int N, int epilogue) { return epilogue != GEMV_EPI_GEGLU && N >= 16384 ? 16 : 8; }
+
+void launch_gemv_bf16(const GemvBf16Args& a, hipStream_t stream) {
+    // every check comes before the launch: a refused call writes nothing
+    LTX_REQUIRE(a.x && a.W, "gemv bf16: null x / W");
+    LTX_REQUIRE(a.epilogue == GEMV_EPI_BF16 || a.epilogue == GEMV_EPI_F32 || a.epilogue == GEMV_EPI_GEGLU, "gemv bf16: epilogue %d (0 bf16, 1 f32, 2 geglu)", a.epilogue);
+    LTX_REQUIRE(a.N >= 1 && a.N < (1 << 30), "gemv bf16: N=%d out of range", a.N);
+    LTX_REQUIRE(a.K >= 8 && a.K % 8 == 0 && a.K <= 16384, "gemv bf16: K=%d must be a multiple of 8 up to 16384", a.K);
+    LTX_REQUIRE(a.ldw % 8 == 0 && a.ldw >= a.K, "gemv bf16: ldw=%ld must be a multiple of 8, at least K=%d", a.ldw, a.K);
+    LTX_REQUIRE(((uintptr_t)a.x & 15) == 0 && ((uintptr_t)a.W & 15) == 0, "gemv bf16: x / W must be 16-byte aligned");
+    LTX_REQUIRE(a.epilogue == GEMV_EPI_F32 ? a.out_f32 != nullptr : (a.out_bf16 != nullptr && a.out_stride >= 1), "gemv bf16: null output or out_stride < 1");
+    const int per_wg = gemv_bf16_rows_per_workgroup(a.N, a.epilogue);
+    const dim3 grid((unsigned)((a.N + per_wg - 1) / per_wg)), block(256);
+    if (a.epilogue == GEMV_EPI_GEGLU)
+        hipLaunchKernelGGL((gemv_bf16_kernel<4, true>), grid, block, 0, stream, a);
+    else if (per_wg == 16)
+        hipLaunchKernelGGL((gemv_bf16_kernel<4, false>), grid, block, 0, stream, a);
+    else
+        hipLaunchKernelGGL((gemv_bf16_kernel<2, false>), grid, block, 0, stream, a);
     HIP_CHECK(hipGetLastError());
 }
 

@@ -79,7 +79,10 @@ GemmaModel* gemma_create(ltx_ctx* ctx, const GemmaConfig& cfg) {
     return m;
 }
 
-void gemma_destroy(GemmaModel* m) { delete m; }
+void gemma_destroy(GemmaModel* m) {
+    if (m) delete m->lm;
+    delete m;
+}
 
 size_t gemma_resident_bytes(const GemmaModel* m) {
     size_t n = m->params.arena.buf.bytes + m->rope.bytes;
@@ -162,24 +165,14 @@ void gemma_init_synthetic(ltx_ctx* ctx, GemmaModel* m, uint64_t seed) {
 
 void gemma_encode(ltx_ctx* ctx, GemmaModel* m, const GemmaArgs& a) {
     const GemmaConfig& c = m->cfg;
-    const int B = a.B, T = a.T, H = c.hidden, I = c.intermediate, L = c.layers;
-    const int Dq = c.heads * 256, Dk = c.kv_heads * 256, Dqk = Dq + Dk;
+    const int B = a.B, T = a.T, H = c.hidden;
     LTX_REQUIRE(a.ids && a.mask && a.hidden, "gemma_encode: null argument");
     LTX_REQUIRE(B >= 1 && T >= 1, "gemma_encode: empty batch");
     if (T > c.sliding_window)  // window masking is not built; the tokenizer truncates to the window
         LTX_THROW(LTXS_INVALID_CONFIGURATION, "gemma_encode: %d tokens exceed the sliding window %d", T, c.sliding_window);
     hipStream_t st = ctx->stream;
     const long rows = (long)B * T;
-    const int Tpad = ((T + 63) / 64) * 64;
     m->ws_ks.ensure((size_t)2 * B * 4);
-    m->ws_xn.ensure((size_t)rows * H * 2);
-    m->ws_qk.ensure((size_t)rows * Dqk * 2);
-    m->ws_vt.ensure((size_t)B * Dk * Tpad * 2, true);
-    m->ws_ao.ensure((size_t)rows * Dq * 2);
-    m->ws_r.ensure((size_t)rows * H * 2);
-    m->ws_h.ensure((size_t)rows * H * 2);
-    m->ws_gu.ensure((size_t)rows * 2 * I * 2);
-    m->ws_ff.ensure((size_t)rows * I * 2);
 
     // key_start[b] from the mask, on the device; the form 0..0 1..1 is checked there and reported here
     int32_t* key_start = m->ws_ks.as<int32_t>();
@@ -191,45 +184,74 @@ void gemma_encode(ltx_ctx* ctx, GemmaModel* m, const GemmaArgs& a) {
         if (!status[b])
             LTX_THROW(LTXS_INVALID_CONFIGURATION, "gemma_encode: the attention mask of batch element %d is not left-padded (0..0 1..1 with at least one 1)", b);
 
+    GemmaEmbedArgs em;  // slot 0: embedding * bf16(sqrt(hidden)) (Gemma3Model.swift:209-211)
+    em.ids = a.ids; em.table = m->embed; em.out = a.hidden; em.rows = (int)rows; em.D = H; em.vocab = c.vocab;
+    em.scale = host_bf16_to_f32(host_f32_to_bf16(sqrtf((float)H)));
+    launch_gemma_embed(em, st);
+    GemmaStackRun s;
+    s.B = B; s.T = T; s.key_start = key_start;
+    s.rope = m->rope.as<float>(); s.tab = (size_t)c.sliding_window * 128;
+    s.hidden = a.hidden;
+    gemma_run_layers(ctx, m, s);
+}
+
+void gemma_run_layers(ltx_ctx* ctx, GemmaModel* m, const GemmaStackRun& s) {
+    const GemmaConfig& c = m->cfg;
+    const int B = s.B, T = s.T, H = c.hidden, I = c.intermediate, L = c.layers;
+    const int Dq = c.heads * 256, Dk = c.kv_heads * 256, Dqk = Dq + Dk;
+    LTX_REQUIRE(!s.vtcache || B == 1, "gemma: a V^T cache holds one sequence");
+    hipStream_t st = ctx->stream;
+    const long rows = (long)B * T;
+    const int Tpad = ((T + 63) / 64) * 64;
+    m->ws_xn.ensure((size_t)rows * H * 2);
+    m->ws_qk.ensure((size_t)rows * Dqk * 2);
+    if (!s.vtcache) m->ws_vt.ensure((size_t)B * Dk * Tpad * 2, true);
+    m->ws_ao.ensure((size_t)rows * Dq * 2);
+    m->ws_r.ensure((size_t)rows * H * 2);
+    m->ws_h.ensure((size_t)rows * H * 2);
+    m->ws_gu.ensure((size_t)rows * 2 * I * 2);
+    m->ws_ff.ensure((size_t)rows * I * 2);
+
     bf16_t* xn = m->ws_xn.as<bf16_t>();
     bf16_t* qk = m->ws_qk.as<bf16_t>();
-    bf16_t* vt = m->ws_vt.as<bf16_t>();
     bf16_t* ao = m->ws_ao.as<bf16_t>();
     bf16_t* r = m->ws_r.as<bf16_t>();
     bf16_t* h = m->ws_h.as<bf16_t>();
     bf16_t* gu = m->ws_gu.as<bf16_t>();
     bf16_t* ff = m->ws_ff.as<bf16_t>();
     const size_t slot = (size_t)rows * H;
+    auto slot_in = [&](int l) { return s.hidden + (size_t)(s.ping_pong ? (l & 1) : l) * slot; };
+    auto slot_out = [&](int l) { return s.hidden + (size_t)(s.ping_pong ? ((l + 1) & 1) : l + 1) * slot; };
 
-    GemmaEmbedArgs em;  // slot 0: embedding * bf16(sqrt(hidden)) (Gemma3Model.swift:209-211)
-    em.ids = a.ids; em.table = m->embed; em.out = a.hidden; em.rows = (int)rows; em.D = H; em.vocab = c.vocab;
-    em.scale = host_bf16_to_f32(host_f32_to_bf16(sqrtf((float)H)));
-    launch_gemma_embed(em, st);
     GemmaNormArgs n0;  // layer 0's input norm
-    n0.r = a.hidden; n0.ldr = H; n0.w = m->layers[0].in_norm; n0.h = xn; n0.ldh = H; n0.rows = (int)rows; n0.D = H; n0.eps = c.rms_eps;
+    n0.r = s.hidden; n0.ldr = H; n0.w = m->layers[0].in_norm; n0.h = xn; n0.ldh = H; n0.rows = (int)rows; n0.D = H; n0.eps = c.rms_eps;
     launch_gemma_norm(n0, st);
 
-    const size_t tab = (size_t)c.sliding_window * 128;
     for (int l = 0; l < L; ++l) {
         const GemmaLayer& ly = m->layers[l];
-        const bf16_t* x = a.hidden + (size_t)l * slot;
+        const bf16_t* x = slot_in(l);
+        // where this layer's K rows and V^T live: the row buffer and the workspace (encoder), or the session's cache (prefill)
+        bf16_t* kdst = s.kcache ? s.kcache + (size_t)l * s.k_stride : qk + Dq;
+        const long ldk = s.kcache ? Dk : Dqk;
+        bf16_t* vt = s.vtcache ? s.vtcache + (size_t)l * s.vt_stride : m->ws_vt.as<bf16_t>();
+        const long ldvt = s.vtcache ? s.ldvt : Tpad;
         // q|k row-major, V as V^T per batch element (the DiT's pair of launches; q and k differ in width, so not the fused one)
         GemmEpilogue eqk;
         eqk.out_bf16 = qk;
         eqk.ld_bf16 = Dqk;
         gemm_linear(xn, H, ly.qk, (int)rows, eqk, st);
-        for (int b = 0; b < B; ++b) gemm_vt(xn + (size_t)b * T * H, H, T, ly.v, vt + (size_t)b * Dk * Tpad, Tpad, st);
-        GemmaQkArgs qa;  // in place
+        for (int b = 0; b < B; ++b) gemm_vt(xn + (size_t)b * T * H, H, T, ly.v, vt + (size_t)b * Dk * ldvt, ldvt, st);
+        GemmaQkArgs qa;  // q in place; k in place, or straight into the cache rows
         qa.job[0].x = qk; qa.job[0].ldx = Dqk; qa.job[0].w = ly.qn; qa.job[0].out = qk; qa.job[0].ldo = Dqk; qa.job[0].heads = c.heads;
-        qa.job[1].x = qk + Dq; qa.job[1].ldx = Dqk; qa.job[1].w = ly.kn; qa.job[1].out = qk + Dq; qa.job[1].ldo = Dqk; qa.job[1].heads = c.kv_heads;
-        const float* tb = m->rope.as<float>() + (gemma_layer_is_global(c, l) ? 2 * tab : 0);
-        qa.cos = tb; qa.sin = tb + tab; qa.T = T; qa.rows = (int)rows; qa.eps = c.rms_eps;
+        qa.job[1].x = qk + Dq; qa.job[1].ldx = Dqk; qa.job[1].w = ly.kn; qa.job[1].out = kdst; qa.job[1].ldo = ldk; qa.job[1].heads = c.kv_heads;
+        const float* tb = s.rope + (gemma_layer_is_global(c, l) ? 2 * s.tab : 0);
+        qa.cos = tb; qa.sin = tb + s.tab; qa.T = T; qa.rows = (int)rows; qa.eps = c.rms_eps;
         launch_gemma_qknorm_rope(qa, st);
         AttnArgs at;
-        at.head_dim = 256; at.causal = 1; at.key_start = key_start;
+        at.head_dim = 256; at.causal = 1; at.key_start = s.key_start;
         at.Q = qk; at.ldq = Dqk; at.q_bstride = (long)T * Dqk;
-        at.K = qk + Dq; at.ldk = Dqk; at.k_bstride = (long)T * Dqk;
-        at.Vt = vt; at.ldvt = Tpad; at.vt_bstride = (long)Dk * Tpad;
+        at.K = kdst; at.ldk = ldk; at.k_bstride = (long)T * ldk;
+        at.Vt = vt; at.ldvt = ldvt; at.vt_bstride = (long)Dk * ldvt;
         at.O = ao; at.ldo = Dq; at.o_bstride = (long)T * Dq;
         at.B = B; at.H = c.heads; at.Hkv = c.kv_heads; at.Tq = T; at.Tk = T;
         at.scale = 1.0f / sqrtf(c.query_pre_attn_scalar);  // not a function of the head dim (Gemma3Model.swift:41-42)
@@ -256,11 +278,14 @@ void gemma_encode(ltx_ctx* ctx, GemmaModel* m, const GemmaArgs& a) {
         GemmaNormArgs n2;  // out = h + post_feedforward_layernorm(r), straight into its slot; the next input norm, or model.norm, beside it
         n2.r = r; n2.ldr = H; n2.w = ly.post_ff; n2.x = h; n2.ldx = H; n2.rows = (int)rows; n2.D = H; n2.eps = c.rms_eps;
         if (l + 1 < L) {
-            n2.h = a.hidden + (size_t)(l + 1) * slot; n2.ldh = H;
+            n2.h = slot_out(l); n2.ldh = H;
             n2.w2 = m->layers[l + 1].in_norm; n2.n = xn; n2.ldn = H;
         } else {  // the raw output of the last layer is not exported: the last slot is model.norm of it (Gemma3Model.swift:286-300)
             n2.n_only = 1;
-            n2.w2 = m->final_norm; n2.n = a.hidden + (size_t)L * slot; n2.ldn = H;
+            n2.w2 = m->final_norm; n2.n = slot_out(l); n2.ldn = H;
+            if (s.final_out) {  // generation: only the last row's model.norm is read (:433)
+                n2.r = r + (size_t)(rows - 1) * H; n2.x = h + (size_t)(rows - 1) * H; n2.n = s.final_out; n2.rows = 1;
+            }
         }
         launch_gemma_norm(n2, st);
     }

@@ -41,6 +41,7 @@ const LtxOptInfo kInfo[OPT_COUNT] = {
     {"sp_selftest", 0, 0, 1, 0, "1: one-rank self-test of the sequence-parallel side-stream branch"},
     {"abl_rows", 0, 0, 7, 0, "row-pass ablation mask (tools only)"},
     {"gemvq_sb", 1, 0, 1, 0, "grouped gemv on quantised codes: 1: one scale / bias load per chunk of trips and a cross-lane move (measured 7 - 11 % faster); 0: every lane loads the scale / bias of its group per trip"},
+    {"lm_gemm", 0, 0, 1, 1, "1: the Linears of a token-generation step through the few-row GEMM at M = 1 (one row padded to a 128-row tile) instead of the bf16 gemv kernel: the measurement baseline, another accumulation order"},
 };
 
 std::atomic<int> g_val[OPT_COUNT];

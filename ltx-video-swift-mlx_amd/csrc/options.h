@@ -44,6 +44,8 @@ enum LtxOpt {
     OPT_SP_SELFTEST,      // 1 = one-rank self-test of the side-stream branch
     OPT_ABL_ROWS,         // ablation of row passes (tools/bench_rows.py; experiments)
     OPT_GEMVQ_SB,         // grouped gemv on codes: 0 = every lane loads its group's scale / bias per trip (default 1: one load per chunk + cross-lane move)
+    OPT_LM_GEMM,          // 1 = every Linear of a generation step through the few-row GEMM at M = 1 instead of gemv_bf16_kernel (numerics: another
+                          // accumulation order; the measurement baseline of tools/bench_lm_generate.py)
     OPT_COUNT
 };
 

@@ -343,6 +343,27 @@ class LTXPipeline {
         check(ltx_gemma_unload(ctx_));
         gemmaLoaded_ = false;
     }
+    // Prompt enhancement (config.enhancePrompt, LTXPipeline.swift:669-674, :2862-2971; Gemma3TextModel.generateTokens,
+    // Gemma3Model.swift:375-492) on token ids: the chat-templated prompt, tokenised outside, in; the generated ids out, for the caller to
+    // detokenise. A KV-cache session of chatIds.size() + max_new_tokens positions lives for the call. params null: the reference's
+    // defaults (512 new tokens, temperature 0.7, top_p 0.95, repetition penalty 1.1 over 64 tokens, eos {1}).
+    std::vector<int32_t> enhancePromptTokens(const std::vector<int32_t>& chatIds, const ltx_lm_params* params = nullptr) {
+        if (!gemmaLoaded_) throw LTXError(LTXError::textEncodingFailed, "the Gemma text encoder is not loaded (loadGemma)");
+        if (chatIds.empty()) throw LTXError(LTXError::textEncodingFailed, "prompt enhancement needs the tokenised chat prompt");
+        ltx_lm_params p;
+        ltx_lm_params_default(&p);
+        if (params) p = *params;
+        if (p.max_new_tokens < 0) throw LTXError(LTXError::invalidConfiguration, "max_new_tokens must not be negative");
+        check(ltx_lm_begin(ctx_, int(chatIds.size()) + p.max_new_tokens));
+        std::vector<int32_t> out(size_t(p.max_new_tokens) + 1);
+        int n = 0;
+        const int rc = ltx_lm_generate(ctx_, chatIds.data(), int(chatIds.size()), &p, out.data(), &n);
+        const std::string why = rc ? ltx_last_error(ctx_) : "";
+        ltx_lm_end(ctx_, nullptr);  // the session goes either way
+        if (rc) throw LTXError(LTXError::Case(rc), why);
+        out.resize(size_t(n));
+        return out;
+    }
     // encodePrompt (LTXPipeline.swift:1155-1170) from the tokenizer's output: token ids + left-padded attention mask [T] -> all hidden
     // states -> connector -> the PrecomputedEmbeddings the generate* calls take. With a negative prompt (same T) both run as one batch
     // of 2. The tokenizer itself is not part of this library.

@@ -1,7 +1,7 @@
 // ltx_video_cli.cpp - `ltx-video` command line, same subcommands / flags / defaults / validation messages as the
 // reference CLI (Sources/LTXVideoCLI/LTXVideoCLI.swift:21-449), on top of host/LTXVideo.hpp -> libltxhip.so.
 //
-// Differences forced by scope: the tokenizer, prompt enhancement, image file decoding, downloads and MP4
+// Differences forced by scope: the tokenizer (prompt enhancement runs on token ids: enhance-prompt), image file decoding, downloads and MP4
 // export are not part of this path. `--audio` runs the dual video + audio model (generateVideoWithAudio / ...TwoStage) and writes a WAV
 // next to the frames. Text conditioning comes from `--gemma-weights <shards> --token-ids <file.safetensors>` (keys
 // input_ids [1,T], optional attention_mask; the Gemma-3 encoder and the connector run here), from `--gemma-hidden-states`, or from
@@ -65,6 +65,9 @@ struct Args {
                  "decode-audio  Audio latent -> 24 kHz stereo WAV (audio VAE decoder + vocoder)\n"
                  "  (--latent file.safetensors [key audio_latent, (8,T,16)] | --synthetic [--frames 121]) [--audio-vae-weights file]\n"
                  "  [--vocoder-weights file] [--audio-gain 1.0] [-o out.wav]\n"
+                 "enhance-prompt  Gemma-3 prompt enhancement on token ids (the tokenizer and chat template stay outside)\n"
+                 "  --gemma-weights file[,file...] --token-ids chat.safetensors [--max-tokens 512] [--temperature 0.7] [--top-p 0.95]\n"
+                 "  [--repetition-penalty 1.1] [--seed 0] [--eos-ids 1[,id...]] [-o/--output ids.safetensors]\n"
                  "options     List the library's launcher switches (name, default, range, numerics flag) for --hip-option\n";
     std::exit(code);
 }
@@ -247,7 +250,8 @@ int run_generate(const Args& a) {
     }
     if (!a.image.empty() || a.enhancePrompt)
         throw ValidationError("--image (file decoding) / --enhance-prompt are outside the MI355X hot path of this build; "
-                              "pass the image as a float tensor with --image-tensor");
+                              "pass the image as a float tensor with --image-tensor, and enhance a tokenised prompt with the "
+                              "enhance-prompt subcommand (token ids in, token ids out; the tokenizer is outside this build)");
     if (a.audio) {
         if (a.audioVaeWeights.empty() || a.vocoderWeights.empty())
             throw ValidationError("--audio needs --audio-vae-weights and --vocoder-weights (the audio VAE decoder and the vocoder), next to "
@@ -561,6 +565,78 @@ int run_decode_audio(int argc, char** argv) {
     return 0;
 }
 
+// enhance-prompt: the prompt-enhancement stage (config.enhancePrompt, LTXPipeline.swift:2862-2971; Gemma3TextModel.generateTokens) on
+// token ids. Input: the chat-templated prompt, tokenised outside (input_ids [1][T] or [T]); output: the generated ids as input_ids
+// [1][n] int32, for the caller to detokenise.
+void write_token_ids(const std::string& path, const std::vector<int32_t>& ids) {
+    const std::string body = "{\"input_ids\":{\"dtype\":\"I32\",\"shape\":[1," + std::to_string(ids.size()) + "],\"data_offsets\":[0," +
+                             std::to_string(ids.size() * 4) + "]}}";
+    std::string header = body;
+    while (header.size() % 8) header += ' ';
+    const uint64_t n = header.size();
+    std::ofstream f(path, std::ios::binary);
+    f.write(reinterpret_cast<const char*>(&n), 8);
+    f.write(header.data(), std::streamsize(header.size()));
+    f.write(reinterpret_cast<const char*>(ids.data()), std::streamsize(ids.size() * 4));
+    if (!f) throw LTXError(LTXError::fileNotFound, "cannot write " + path);
+}
+
+int run_enhance_prompt(int argc, char** argv) {
+    std::string gemmaWeights, tokenIds, output = "enhanced_ids.safetensors";
+    ltx_lm_params p;
+    ltx_lm_params_default(&p);
+    ltx_gemma_config gc;
+    ltx_gemma_config_default(&gc);
+    bool customConfig = false;
+    auto need = [&](int& i) -> std::string {
+        if (i + 1 >= argc) throw ValidationError(std::string("Missing value for '") + argv[i] + "'");
+        return argv[++i];
+    };
+    auto dim = [&](int& i, int& field) {  // checkpoints smaller than the reference's (tests)
+        field = std::stoi(need(i));
+        customConfig = true;
+    };
+    for (int i = 2; i < argc; ++i) {
+        const std::string k = argv[i];
+        if (k == "--gemma-weights") gemmaWeights = need(i);
+        else if (k == "--token-ids") tokenIds = need(i);
+        else if (k == "--max-tokens") p.max_new_tokens = std::stoi(need(i));
+        else if (k == "--temperature") p.temperature = std::stof(need(i));
+        else if (k == "--top-p") p.top_p = std::stof(need(i));
+        else if (k == "--repetition-penalty") p.repetition_penalty = std::stof(need(i));
+        else if (k == "--seed") p.seed = std::stoull(need(i));
+        else if (k == "--eos-ids") {
+            const std::vector<int> ids = parse_blocks(need(i));
+            if (ids.empty() || ids.size() > 8) throw ValidationError("--eos-ids takes 1 to 8 comma-separated token ids");
+            p.n_eos = int(ids.size());
+            for (size_t j = 0; j < ids.size(); ++j) p.eos_ids[j] = ids[j];
+        }
+        else if (k == "--gemma-hidden-size") dim(i, gc.hidden_size);
+        else if (k == "--gemma-layers") dim(i, gc.num_hidden_layers);
+        else if (k == "--gemma-intermediate-size") dim(i, gc.intermediate_size);
+        else if (k == "--gemma-heads") dim(i, gc.num_attention_heads);
+        else if (k == "--gemma-kv-heads") dim(i, gc.num_key_value_heads);
+        else if (k == "--gemma-vocab-size") dim(i, gc.vocab_size);
+        else if (k == "-o" || k == "--output") output = need(i);
+        else throw ValidationError("Unknown option '" + k + "'");
+    }
+    if (gemmaWeights.empty()) throw ValidationError("enhance-prompt needs --gemma-weights file[,file...] (the Gemma-3 checkpoint's safetensors shards)");
+    if (tokenIds.empty()) throw ValidationError("enhance-prompt needs --token-ids file.safetensors (the chat-templated prompt, tokenised outside: input_ids [1,T])");
+    if (p.max_new_tokens < 1) throw ValidationError("--max-tokens must be positive");
+    if (p.temperature > 0.f && !(p.top_p > 0.f && p.top_p <= 1.f)) throw ValidationError("--top-p must be in (0, 1]");
+    std::vector<int32_t> ids, am;
+    read_token_ids(tokenIds, ids, am);
+    LTXPipeline pipeline;
+    pipeline.loadGemma(split_commas(gemmaWeights), customConfig ? &gc : nullptr);
+    std::cout << "Enhancing prompt: " << ids.size() << " prompt tokens, up to " << p.max_new_tokens << " new ("
+              << (p.temperature > 0.f ? "sampled" : "greedy") << ")...\n";
+    const std::vector<int32_t> out = pipeline.enhancePromptTokens(ids, &p);
+    pipeline.unloadGemma();
+    write_token_ids(output, out);
+    std::cout << "Generated " << out.size() << " tokens -> " << output << "\n";
+    return 0;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -592,6 +668,7 @@ int main(int argc, char** argv) {
         if (sub == "generate") return run_generate(parse_generate(argc, argv, 2));
         if (sub == "bench") return run_bench(argc, argv);
         if (sub == "decode-audio") return run_decode_audio(argc, argv);
+        if (sub == "enhance-prompt") return run_enhance_prompt(argc, argv);
         throw ValidationError("Unknown subcommand '" + sub + "'");
     } catch (const ValidationError& e) {
         std::cerr << "Error: " << e.what() << "\n";
