@@ -1319,9 +1319,12 @@ int ltx_lm_step_dev(ltx_ctx* ctx, const int32_t* token, float* logits);
 /* HOST variant: the token by value, logits a host array or NULL. */
 int ltx_lm_step(ltx_ctx* ctx, int32_t token, float* logits);
 /* Debug seams (HOST pointers): model.norm of the newest position [hidden_size] bf16 - the logits projection's input; and rows
- * 0 .. rows-1 of a layer's K cache, [rows][num_key_value_heads * 256] bf16. */
+ * 0 .. rows-1 of a layer's K cache, [rows][num_key_value_heads * 256] bf16; and columns 0 .. cols-1 of every row of a layer's V^T
+ * cache, [num_key_value_heads * 256][cols] bf16, 1 <= cols <= the padded width roundup(capacity, 64) - the columns past the filled
+ * positions are the session's own and zero since ltx_lm_begin. */
 int ltx_lm_last_state(ltx_ctx* ctx, uint16_t* state);
 int ltx_lm_cache_k(ltx_ctx* ctx, int layer, int rows, uint16_t* k);
+int ltx_lm_cache_vt(ltx_ctx* ctx, int layer, int cols, uint16_t* vt);
 /* Prefill + the generate loop: pick, stop-id check, append, step. ids HOST [T]; out_tokens HOST [max_new_tokens]; *n_out tokens are
  * written (a stop id ends the run and is not written). T + max_new_tokens must fit the session's capacity. params NULL: defaults. */
 int ltx_lm_generate(ltx_ctx* ctx, const int32_t* ids, int T, const ltx_lm_params* params, int32_t* out_tokens, int* n_out);

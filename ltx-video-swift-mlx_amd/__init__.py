@@ -1028,6 +1028,13 @@ class Context:
         self._ck(lib.ltx_lm_cache_k(self._h, layer, rows, _ptr(out)))
         return out
 
+    def lm_cache_vt(self, layer, cols, width):
+        """Columns 0 .. cols-1 of a layer's V^T cache: bf16 bits [width, cols] uint16 (width = num_key_value_heads * 256; cols up to the
+        padded width roundup(capacity, 64))."""
+        out = np.empty((width, cols), np.uint16)
+        self._ck(lib.ltx_lm_cache_vt(self._h, layer, cols, _ptr(out)))
+        return out
+
     def lm_generate(self, ids, params=None):
         """``ltx_lm_generate``: HOST ids [T] -> the generated ids (int32 array), stop id excluded."""
         ids = np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)

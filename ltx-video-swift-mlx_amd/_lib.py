@@ -430,6 +430,7 @@ SIGNATURES = {
     "ltx_lm_step": (_i, [_vp, C.c_int32, _vp]),
     "ltx_lm_last_state": (_i, [_vp, _vp]),
     "ltx_lm_cache_k": (_i, [_vp, _i, _i, _vp]),
+    "ltx_lm_cache_vt": (_i, [_vp, _i, _i, _vp]),
     "ltx_lm_generate": (_i, [_vp, _vp, _i, C.POINTER(LmParams), _vp, C.POINTER(C.c_int)]),
     "ltx_lm_sample_host": (_i, [_vp, _i, _vp, _i, _i, _f, _f, _f, _u64, _i, C.POINTER(C.c_int32)]),
     "ltx_op_gemv_bf16": (_i, [_vp, _vp, _vp, _l, _i, _i, _i, _i, _vp, _l, _vp]),

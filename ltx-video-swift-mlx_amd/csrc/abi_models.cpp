@@ -1004,6 +1004,18 @@ int ltx_lm_cache_k(ltx_ctx* ctx, int layer, int rows, uint16_t* k) {
     });
 }
 
+int ltx_lm_cache_vt(ltx_ctx* ctx, int layer, int cols, uint16_t* vt) {
+    return with_ctx(ctx, [&] {
+        GemmaModel* m = need_lm(ctx, "ltx_lm_cache_vt");
+        const long ldvt = m->lm->ldvt;
+        LTX_REQUIRE(vt && layer >= 0 && layer < m->cfg.layers && cols >= 1 && cols <= ldvt, "ltx_lm_cache_vt: layer %d, %d columns of %ld", layer, cols, ldvt);
+        const size_t Dk = (size_t)m->cfg.kv_heads * 256;
+        HIP_CHECK(hipMemcpy2DAsync(vt, (size_t)cols * 2, m->lm->vt.as<bf16_t>() + (size_t)layer * Dk * ldvt, (size_t)ldvt * 2, (size_t)cols * 2, Dk,
+                                   hipMemcpyDeviceToHost, ctx->stream));
+        stage_sync(ctx);
+    });
+}
+
 int ltx_lm_generate(ltx_ctx* ctx, const int32_t* ids, int T, const ltx_lm_params* params, int32_t* out_tokens, int* n_out) {
     return with_ctx(ctx, [&] {
         if (n_out) *n_out = 0;

@@ -81,6 +81,18 @@ def step(cfg, w, cache, token, gemm_f64=False):
     return state, logits_of(w, state, gemm_f64)
 
 
+def forced_run(cfg, w, ids, n_prefill, gemm_f64=False):
+    """Prefill ids[:n_prefill], then one forced step per remaining id -> (states [n][hidden], logits [n][vocab], cache) with
+    n = len(ids) - n_prefill + 1: entry i belongs to position n_prefill - 1 + i."""
+    cache, state, logits = prefill(cfg, w, ids[:n_prefill], gemm_f64)
+    states, lgs = [state], [logits]
+    for t in ids[n_prefill:]:
+        state, logits = step(cfg, w, cache, int(t), gemm_f64)
+        states.append(state)
+        lgs.append(logits)
+    return np.stack(states), np.stack(lgs), cache
+
+
 # ---- penalty, pick, sampler ----
 def penalize(logits, generated, context, penalty):
     """A penalised copy: every DISTINCT id among the last min(context, len(generated)) generated tokens, l > 0 ? l / p : l * p in f32."""

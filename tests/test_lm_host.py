@@ -17,7 +17,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TINY = ref.Config(hidden=384, layers=7, intermediate=768, heads=2, kv_heads=1, vocab=1000)
 
 NEW_ENTRIES = ("ltx_lm_params_default", "ltx_lm_begin", "ltx_lm_end", "ltx_lm_memory_info", "ltx_lm_prefill_dev", "ltx_lm_prefill", "ltx_lm_step_dev",
-               "ltx_lm_step", "ltx_lm_last_state", "ltx_lm_cache_k", "ltx_lm_generate", "ltx_lm_sample_host", "ltx_op_gemv_bf16",
+               "ltx_lm_step", "ltx_lm_last_state", "ltx_lm_cache_k", "ltx_lm_cache_vt", "ltx_lm_generate", "ltx_lm_sample_host", "ltx_op_gemv_bf16",
                "ltx_gemv_bf16_rows_per_workgroup", "ltx_op_attention_decode", "ltx_op_lm_pick")
 
 
@@ -40,6 +40,40 @@ def test_cached_replay_agrees_with_the_full_prefix_replay():
     assert worst <= 1e-2, worst
 
 
+def test_long_run_bound_sees_a_key_lost_in_the_second_split(monkeypatch):
+    """The bound of tests/test_lm_cache_gpu.py::test_long_forced_run_against_the_replay - twice what the replay moves against itself
+    when its GEMMs accumulate in f64 - has teeth: the same model (4 / 2 heads, window 48), a 40-token prefill forced to position 140,
+    with key 64 (the first of the second split) dropped from every single-row step's attention. The damaged replay must leave the f32
+    one by at least twice that bound at some position after 64. Measured: state 8.6e-2 against the bound 1.56e-2."""
+    cfg = ref.Config(hidden=384, layers=7, intermediate=768, heads=4, kv_heads=2, vocab=1000, sliding_window=48)
+    w = ref.synth_weights(cfg, 4, embed_std=0.4)
+    ids = np.random.default_rng(8).integers(0, cfg.vocab, 141).astype(np.int32)
+    want_s, want_l, _ = dec.forced_run(cfg, w, ids, 40)
+    other_s, other_l, _ = dec.forced_run(cfg, w, ids, 40, True)
+    attend = dec._attend
+
+    def without_key_64(q, k, v, Hq, Hkv, scale, first_pos):
+        if q.shape[0] == 1 and first_pos >= 64:
+            keep = np.arange(first_pos + 1) != 64
+            return attend(q, k[:first_pos + 1][keep], v[:first_pos + 1][keep], Hq, Hkv, scale, first_pos - 1)
+        return attend(q, k, v, Hq, Hkv, scale, first_pos)
+
+    monkeypatch.setattr(dec, "_attend", without_key_64)
+    bad_s, bad_l, _ = dec.forced_run(cfg, w, ids, 40)
+    rel = lambda a, b: float(np.linalg.norm(a.astype(np.float64) - b) / np.linalg.norm(b))
+    n = len(want_s)
+    s_floor = max(rel(other_s[i], want_s[i]) for i in range(n))
+    l_floor = max(rel(other_l[i], want_l[i]) for i in range(n))
+    assert all(np.array_equal(bad_s[i], want_s[i]) for i in range(64 - 39))  # positions 39 .. 63 hold no key 64 to lose
+    s_bad = [rel(bad_s[i], want_s[i]) for i in range(n)]
+    l_bad = [rel(bad_l[i], want_l[i]) for i in range(n)]
+    first = 65 - 39  # the entry of position 65
+    at = first + int(np.argmax(s_bad[first:]))
+    print(f"floors: state {s_floor:.3e}, logits {l_floor:.3e}; without key 64: worst state {s_bad[at]:.3e} at position {39 + at}, "
+          f"worst logits {max(l_bad[first:]):.3e}; at position 140 state {s_bad[-1]:.3e}, logits {l_bad[-1]:.3e}")
+    assert s_bad[at] >= 2.0 * (2.0 * s_floor) and max(l_bad[first:]) >= 2.0 * (2.0 * l_floor)
+
+
 def test_new_entries_are_declared_exported_and_bound(ltx):
     hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "ltxhip.h")).read(), flags=re.S)
     declared = set(re.findall(r"\b(ltx_[a-z0-9_]+)\s*\(", hdr))
@@ -51,7 +85,7 @@ def test_new_entries_are_declared_exported_and_bound(ltx):
         assert name in declared and hasattr(so, name) and name in lib_mod.SIGNATURES, name
     assert {n for n in declared if n.startswith("ltx_lm_")} <= set(NEW_ENTRIES)
     for attr in ("lm_begin", "lm_end", "lm_memory_info", "lm_prefill_dev", "lm_prefill", "lm_step_dev", "lm_step", "lm_last_state", "lm_cache_k",
-                 "lm_generate", "op_gemv_bf16", "op_attention_decode", "op_lm_pick"):
+                 "lm_cache_vt", "lm_generate", "op_gemv_bf16", "op_attention_decode", "op_lm_pick"):
         assert hasattr(ltx.Context, attr), attr
     assert lib_mod.LmParams._fields_[0][0] == "struct_size" and lib_mod.LmParams.struct_size.offset == 0
 
